@@ -19,9 +19,15 @@ N > 1: every epoch's DR query domains and DN passes are dealt to the ranks by lo
 cost THAT epoch's sampled plan will execute (mamdr_amd/parallel.py: BalancedMAMDR), with ONE all-reduce per
 epoch (DN displacement + the phi hand-over); total work is fixed -> "scaling": "strong".
 
-Besides the headline line the JSON carries `targets.taobao30` (BASELINE.json configs[3] / north_star: Taobao-30
-bs 4096, same run), `gather` (the embedding gather on Amazon-6-sized tables, 316 MB > the 256 MiB infinity
-cache) and `cpu_baseline` (torch-CPU fp32 restatement of the TF1.12 step on this box's host cores).
+A plain run does only what the headline needs: set up, warm up, time the K epochs, print the line.  With `--full` the
+JSON also carries the per-kernel figures of one more profiled epoch (`roofline`, `kernels_avg_us`, ...), `targets`
+(Taobao-30 bs 4096 = BASELINE.json configs[3] / north_star, Amazon-6 and Amazon-13, same run), `gather` (the embedding
+gather on Amazon-6-sized tables, 316 MB > the 256 MiB infinity cache), `cpu_baseline` (torch-CPU fp32 restatement of
+the TF1.12 step on the host's cores) and `lanes`.
+
+`--dump-outputs DIR` writes what the last timed epoch computed -- theta, phi [domains, P] and the engine's live weights
+-- as DIR/<name>.npy (float32, 64 MB at most: larger vectors are cut to a fixed, seeded sample of positions).  The
+timed epochs start from the same state in every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ import os
 import subprocess
 import sys
 import time
+import types
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -433,8 +440,32 @@ def gather_hbm_record(device, n_rows=1 << 19, reps=12):
                     "3 x 512-B rows read + 384 floats written per position"}
 
 
+# ---------------------------------------------------------------------------------------------- outputs of the timed path
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """arrays: {name: device tensor [P] or list of device tensors [P] (one row each)} -> out_dir/<name>.npy, float32.  Each name
+    gets an equal share of `budget`; where a name's rows hold more elements than its share, every row is cut to the same
+    fixed, seeded sample of positions (sorted), the same in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = budget // 4 // max(len(arrays), 1)
+    for k, (name, rows) in enumerate(sorted(arrays.items())):
+        one = torch.is_tensor(rows)
+        rows = [rows] if one else list(rows)
+        n, per_row = rows[0].numel(), cap // max(len(rows), 1)
+        idx = None
+        if n > per_row:
+            idx = np.unique(np.random.RandomState(1000 + k).randint(0, n, size=per_row))
+            idx = torch.from_numpy(idx).to(rows[0].device)
+        host = [(r.reshape(-1) if idx is None else r.reshape(-1).index_select(0, idx)).float().cpu().numpy() for r in rows]
+        np.save(os.path.join(out_dir, name + ".npy"), host[0] if one else np.stack(host))
+
+
 # ---------------------------------------------------------------------------------------------- one workload
-def run_workload(wl_name, steps, warmup, rank, world, profile=True, cpu_budget=0.0):
+def run_workload(wl_name, steps, warmup, rank, world, profile=True, cpu_budget=0.0, dump_dir=None):
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -449,7 +480,6 @@ def run_workload(wl_name, steps, warmup, rank, world, profile=True, cpu_budget=0
     g = synthetic.generate(wl["shape"], batch_size=batch, seed=TRAIN["seed"], row_scale=row_scale, splits=("train",))
     D = g["n_domain"]
     tower = wl.get("tower", "mlp")
-    eng = setup_engine(g, batch, trainable, tower)
 
     def full_params(seed=1024):
         if tower == "star":      # Keras defaults of the Star layers (mamdr_amd/model_zoo/star.py)
@@ -463,95 +493,103 @@ def run_workload(wl_name, steps, warmup, rank, world, profile=True, cpu_budget=0
             p["user_emb"] = (rs_.standard_normal((g["n_user"], 128)) * 1e-4).astype(np.float32)
             p["item_emb"] = (rs_.standard_normal((g["n_item"], 128)) * 1e-4).astype(np.float32)
         return p
-    sizes = [eng.n_rows(d, "train") for d in range(D)]
-    steps_per_domain = [-(-n // batch) for n in sizes]
 
-    def initial_vector(seed=1024):
-        """one random initialisation of the whole model as a flat device vector.  Frozen-table workloads: packed on
-        the host (0.56 MB).  Trainable tables (79 - 92 M floats): the dense tensors come from the same host
-        initialisers, the two big tables are drawn ON the device with their layer's distribution (deepctr
-        SparseFeat N(0, 1e-4^2), Keras Embedding U(-0.05, 0.05) for the Star tower) -- D + 1 host draws of 92 M
-        normals would cost the default run half a minute."""
-        if not trainable:
-            return eng.pack(full_params(seed))
-        keep = (g["n_user"], g["n_item"])
-        g["n_user"], g["n_item"] = 8, 8                      # host initialisers for everything but the two tables
-        try:
-            small = full_params(seed)
-        finally:
-            g["n_user"], g["n_item"] = keep
-        v = torch.zeros(eng.n_params, dtype=torch.float32, device=eng.device)
-        gen = torch.Generator(device=eng.device)
-        gen.manual_seed(seed)
-        for name, (off, cnt) in eng.segments.items():
-            if name in ("user_emb", "item_emb"):
-                if tower == "star":
-                    v[off:off + cnt].uniform_(-0.05, 0.05, generator=gen)
+    def new_run():
+        """engine, model state and epoch() of one run of this workload, from its initial state: the same bits in every
+        run, which the timed epochs start from (the prewarm below runs on a run of its own)."""
+        eng = setup_engine(g, batch, trainable, tower)
+        sizes = [eng.n_rows(d, "train") for d in range(D)]
+        steps_per_domain = [-(-n // batch) for n in sizes]
+
+        def initial_vector(seed=1024):
+            """one random initialisation of the whole model as a flat device vector.  Frozen-table workloads: packed on
+            the host (0.56 MB).  Trainable tables (79 - 92 M floats): the dense tensors come from the same host
+            initialisers, the two big tables are drawn ON the device with their layer's distribution (deepctr
+            SparseFeat N(0, 1e-4^2), Keras Embedding U(-0.05, 0.05) for the Star tower) -- D + 1 host draws of 92 M
+            normals would cost the default run half a minute."""
+            if not trainable:
+                return eng.pack(full_params(seed))
+            keep = (g["n_user"], g["n_item"])
+            g["n_user"], g["n_item"] = 8, 8                      # host initialisers for everything but the two tables
+            try:
+                small = full_params(seed)
+            finally:
+                g["n_user"], g["n_item"] = keep
+            v = torch.zeros(eng.n_params, dtype=torch.float32, device=eng.device)
+            gen = torch.Generator(device=eng.device)
+            gen.manual_seed(seed)
+            for name, (off, cnt) in eng.segments.items():
+                if name in ("user_emb", "item_emb"):
+                    if tower == "star":
+                        v[off:off + cnt].uniform_(-0.05, 0.05, generator=gen)
+                    else:
+                        v[off:off + cnt].normal_(0.0, 1e-4, generator=gen)
+                elif name in ("lin_user", "lin_item"):
+                    pass                                             # DeepFM linear tables start at zero
                 else:
-                    v[off:off + cnt].normal_(0.0, 1e-4, generator=gen)
-            elif name in ("lin_user", "lin_item"):
-                pass                                             # DeepFM linear tables start at zero
-            else:
-                v[off:off + cnt] = torch.from_numpy(np.ascontiguousarray(small[name], np.float32).ravel()).to(eng.device)
-        return v
+                    v[off:off + cnt] = torch.from_numpy(np.ascontiguousarray(small[name], np.float32).ravel()).to(eng.device)
+            return v
 
-    full0 = initial_vector()
-    eng.set_weights(full0)                 # tensors outside theta (Star: PN, specific kernels, output unit)
-    theta = full0[:eng.n_meta].clone()
-    del full0
-    wrapper = wl.get("wrapper", "mamdr")
-    # phi_d starts as a second random init of the whole model (mamdr.py:31-33); every rank draws all of them
-    balanced = None
-    if wrapper == "mamdr":
-        phis = {d: initial_vector(seed=2000 + d)[:eng.n_meta] for d in range(D)}
-        balanced = parallel.BalancedMAMDR(eng, meta, theta, phis, steps_per_domain,
-                                          dn_mode=os.environ.get("MAMDR_BENCH_DN_MODE", "sharded"))
-        del phis
-    delta, zero = eng.new_vector(meta=True), eng.new_vector(meta=True)
-    planner = mplan.EpochPlanner(range(D), TRAIN["sample_num"], TRAIN["add_query_domain"], True, TRAIN["seed"])
-    shuffles = mplan.EpochShuffles(mplan.PassShuffler(sizes, TRAIN["shuffle_buffer_size"], TRAIN["seed"] + rank),
-                                   eng.device)
-    loads = []
-    host_prep_s = [0.0]
-    next_plan = [None]
-    prefetch = os.environ.get("MAMDR_BENCH_NO_PREFETCH", "0") in ("", "0")      # A/B switch
+        full0 = initial_vector()
+        eng.set_weights(full0)                 # tensors outside theta (Star: PN, specific kernels, output unit)
+        theta = full0[:eng.n_meta].clone()
+        del full0
+        wrapper = wl.get("wrapper", "mamdr")
+        # phi_d starts as a second random init of the whole model (mamdr.py:31-33); every rank draws all of them
+        balanced = None
+        if wrapper == "mamdr":
+            phis = {d: initial_vector(seed=2000 + d)[:eng.n_meta] for d in range(D)}
+            balanced = parallel.BalancedMAMDR(eng, meta, theta, phis, steps_per_domain,
+                                              dn_mode=os.environ.get("MAMDR_BENCH_DN_MODE", "sharded"))
+            del phis
+        delta, zero = eng.new_vector(meta=True), eng.new_vector(meta=True)
+        planner = mplan.EpochPlanner(range(D), TRAIN["sample_num"], TRAIN["add_query_domain"], True, TRAIN["seed"])
+        shuffles = mplan.EpochShuffles(mplan.PassShuffler(sizes, TRAIN["shuffle_buffer_size"], TRAIN["seed"] + rank),
+                                       eng.device)
+        loads = []
+        host_prep_s = [0.0]
+        next_plan = [None]
+        prefetch = os.environ.get("MAMDR_BENCH_NO_PREFETCH", "0") in ("", "0")      # A/B switch
 
-    def epoch():
-        th0 = time.perf_counter()
-        if wrapper == "dn":               # Domain Negotiation only (domain_negotiation.py:37-88)
-            p = next_plan[0] if next_plan[0] is not None else planner.next_epoch(with_dr=False)
-            owner = parallel.lpt_partition(steps_per_domain, world)
-            local = [d for d in p["seq"] if owner[d] == rank]
-            shuffles.prepare([(d, 0) for d in local])
+        def epoch():
+            th0 = time.perf_counter()
+            if wrapper == "dn":               # Domain Negotiation only (domain_negotiation.py:37-88)
+                p = next_plan[0] if next_plan[0] is not None else planner.next_epoch(with_dr=False)
+                owner = parallel.lpt_partition(steps_per_domain, world)
+                local = [d for d in p["seq"] if owner[d] == rank]
+                shuffles.prepare([(d, 0) for d in local])
+                host_prep_s[0] += time.perf_counter() - th0
+                tr = []
+                parallel.dn_phase_sharded(eng, meta, theta, local, shuffles, batch, TRAIN["learning_rate"],
+                                          TRAIN["meta_learning_rate"], tr, delta, zero)
+                eng.set_weights(theta)
+                if prefetch:
+                    th1 = time.perf_counter()
+                    next_plan[0] = planner.next_epoch(with_dr=False)
+                    shuffles.prefetch([(d, 0) for d in next_plan[0]["seq"] if owner[d] == rank])
+                    host_prep_s[0] += time.perf_counter() - th1
+                return tr, mplan.plan_steps(p, steps_per_domain)
+            p = next_plan[0] if next_plan[0] is not None else planner.next_epoch()    # same seed on every rank -> same global plan
+            next_plan[0] = None
             host_prep_s[0] += time.perf_counter() - th0
-            tr = []
-            parallel.dn_phase_sharded(eng, meta, theta, local, shuffles, batch, TRAIN["learning_rate"],
-                                      TRAIN["meta_learning_rate"], tr, delta, zero)
-            eng.set_weights(theta)
-            if prefetch:
-                th1 = time.perf_counter()
-                next_plan[0] = planner.next_epoch(with_dr=False)
-                shuffles.prefetch([(d, 0) for d in next_plan[0]["seq"] if owner[d] == rank])
-                host_prep_s[0] += time.perf_counter() - th1
-            return tr, mplan.plan_steps(p, steps_per_domain)
-        p = next_plan[0] if next_plan[0] is not None else planner.next_epoch()    # same seed on every rank -> same global plan
-        next_plan[0] = None
-        host_prep_s[0] += time.perf_counter() - th0
 
-        # the NEXT epoch's plan is a function of the seed alone: its shuffles are drawn on a worker thread while this epoch is
-        # enqueued and run (plan.EpochShuffles.lookahead: a few passes in; the work stays inside the timed region, off the
-        # critical path of the epoch boundary, whose run-ahead margin is 2 - 3 ms of queued launches)
-        def look():
-            th1 = time.perf_counter()
-            next_plan[0] = planner.next_epoch()
-            shuffles.prefetch(balanced.local_passes(next_plan[0]))
-            host_prep_s[0] += time.perf_counter() - th1
-        shuffles.lookahead = look if prefetch else None
-        tr = balanced.epoch(p, shuffles.prepare, shuffles, batch, TRAIN["learning_rate"], TRAIN["meta_learning_rate"],
-                            TRAIN["merged_method"])
-        if balanced.last_load is not None:
-            loads.append(balanced.last_load)
-        return tr, mplan.plan_steps(p, steps_per_domain)
+            # the NEXT epoch's plan is a function of the seed alone: its shuffles are drawn on a worker thread while this epoch is
+            # enqueued and run (plan.EpochShuffles.lookahead: a few passes in; the work stays inside the timed region, off the
+            # critical path of the epoch boundary, whose run-ahead margin is 2 - 3 ms of queued launches)
+            def look():
+                th1 = time.perf_counter()
+                next_plan[0] = planner.next_epoch()
+                shuffles.prefetch(balanced.local_passes(next_plan[0]))
+                host_prep_s[0] += time.perf_counter() - th1
+            shuffles.lookahead = look if prefetch else None
+            tr = balanced.epoch(p, shuffles.prepare, shuffles, batch, TRAIN["learning_rate"], TRAIN["meta_learning_rate"],
+                                TRAIN["merged_method"])
+            if balanced.last_load is not None:
+                loads.append(balanced.last_load)
+            return tr, mplan.plan_steps(p, steps_per_domain)
+
+        return types.SimpleNamespace(eng=eng, epoch=epoch, theta=theta, balanced=balanced, shuffles=shuffles, loads=loads,
+                                     host_prep_s=host_prep_s, sizes=sizes)
 
     def barrier():
         if world > 1:
@@ -560,17 +598,27 @@ def run_workload(wl_name, steps, warmup, rank, world, profile=True, cpu_budget=0
 
     # device warm-up before the W warm-up epochs the contract asks for: the first process on a box that has just come up runs
     # its first second at lower clocks (measured: 43.3 K on such a run against 44.6 K on every later one, kernel times of the
-    # later profile pass identical) -- W = 3 epochs are 85 ms.  Untimed, reported as `prewarm_s`.
+    # later profile pass identical) -- W = 3 epochs are 85 ms.  Untimed, reported as `prewarm_s`.  How many epochs fit in that
+    # time varies from run to run, so they run on a run of their own, closed afterwards: the W warm-up and the timed epochs
+    # start from the initial state in every run (their results are comparable across runs and builds: --dump-outputs).
     prewarm_s = float(os.environ.get("MAMDR_BENCH_PREWARM_S", "0.75"))
-    tw = time.perf_counter()
-    while prewarm_s > 0:
-        epoch()
-        torch.cuda.synchronize()
-        go_on = torch.tensor([1.0 if time.perf_counter() - tw < prewarm_s else 0.0], device=eng.device)
-        if world > 1:
-            parallel.all_reduce(go_on, "min")        # (ranks / lanes leave the loop together)
-        if float(go_on.item()) == 0.0:
-            break
+    if prewarm_s > 0:
+        pre = new_run()
+        tw = time.perf_counter()
+        while True:
+            pre.epoch()
+            torch.cuda.synchronize()
+            go_on = torch.tensor([1.0 if time.perf_counter() - tw < prewarm_s else 0.0], device=pre.eng.device)
+            if world > 1:
+                parallel.all_reduce(go_on, "min")        # (ranks / lanes leave the loop together)
+            if float(go_on.item()) == 0.0:
+                break
+        pre.shuffles.cancel()
+        pre.eng.close()
+        del pre
+    run = new_run()
+    eng, epoch, theta, balanced, shuffles = run.eng, run.epoch, run.theta, run.balanced, run.shuffles
+    loads, host_prep_s, sizes = run.loads, run.host_prep_s, run.sizes
     for _ in range(warmup):
         epoch()
     barrier()
@@ -597,6 +645,19 @@ def run_workload(wl_name, steps, warmup, rank, world, profile=True, cpu_budget=0
         assert int(round(float(t[1]))) == global_steps, (float(t[1]), global_steps)
         local_passes = int(round(float(t[2])))
         host_ms = [float(t[3]) / world / steps * 1e3, float(tmax[3]) / steps * 1e3]      # mean, max over ranks
+    if dump_dir is not None:
+        # what the caller of the timed path holds after its last epoch, before anything else runs: theta, every phi_d
+        # (gathered onto every rank first) and the live weights of the engine
+        if balanced is not None:
+            balanced.sync_phis()
+        weights = eng.weights                   # (flushes the lazily updated table rows)
+        torch.cuda.synchronize()
+        if rank == 0:
+            out = {"theta": theta, "weights": weights}
+            if balanced is not None:
+                out["phi"] = [balanced.phis[d] for d in sorted(balanced.phis)]
+            dump_outputs(dump_dir, out)
+        del weights
 
     # ---- per-kernel device time (HIP events on the launch stream) over one more epoch of
     #      the same workload; reported for the dominant kernel, k_tower<train>
@@ -923,20 +984,36 @@ def summary_block(result, targets, lanes_rec):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20, help="timed MAMDR meta-epochs")
+    ap.add_argument("--steps", type=int, default=20, help="timed MAMDR meta-epochs (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="taobao10", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline work (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event pass")
-    ap.add_argument("--no-targets", action="store_true", help="skip the Taobao-30 record and the Amazon-6-sized gather")
-    ap.add_argument("--lanes", type=int, default=4,
-                    help="single GPU: also time the same epochs sharded over this many lanes of one process (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-kernel HIP-event pass, the other workloads and the "
+                         "Amazon-6-sized gather (Taobao-10), the CPU baseline, the lanes.  Without it a run sets up, warms up, "
+                         "times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (theta, phi, the live weights) as DIR/<name>.npy")
+    ap.add_argument("--cpu-budget", type=float, default=None,
+                    help="seconds of CPU-baseline work (0 = skip; default 20 with --full, else 0)")
+    ap.add_argument("--no-profile", action="store_true", help="--full: skip the per-kernel HIP-event pass")
+    ap.add_argument("--no-targets", action="store_true", help="--full: skip the other workloads and the Amazon-6-sized gather")
+    ap.add_argument("--lanes", type=int, default=None,
+                    help="single GPU: also time the same epochs sharded over this many lanes of one process "
+                         "(0 = skip; default 4 with --full, else 0)")
     ap.add_argument("--rank-lanes", type=int, default=0,
                     help="several ranks: also time the epochs with this many lanes PER RANK (ranks x lanes: one world of "
                          "gpus * rank-lanes participants; 0 = skip)")
     ap.add_argument("--no-preflight", action="store_true",
                     help="several ranks: skip the first-contact check of the communicator (all-reduce, send / recv ring, broadcast)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.cpu_budget is None:
+        args.cpu_budget = 20.0 if args.full else 0.0
+    if args.lanes is None:
+        args.lanes = 4 if args.full else 0
+    args.no_profile = args.no_profile or not args.full
+    args.no_targets = args.no_targets or not args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
@@ -986,7 +1063,8 @@ def main():
         print("warning: --gpus %d but WORLD_SIZE %d" % (args.gpus, world), file=sys.stderr)
 
     main_rec = run_workload(args.workload, args.steps, args.warmup, rank, world, not args.no_profile,
-                            args.cpu_budget * (0.5 if not args.no_targets and args.workload == "taobao10" else 1.0))
+                            args.cpu_budget * (0.5 if not args.no_targets and args.workload == "taobao10" else 1.0),
+                            dump_dir=args.dump_outputs)
     targets, gather = {}, None
     if not args.no_targets and args.workload == "taobao10":
         # north_star's target configuration in the same run: Taobao-30 bs 4096

@@ -776,24 +776,21 @@ def test_scattered_meta_parms_through_the_run_entry(tmp_path, monkeypatch):
 def test_configs_mirror_the_reference():
     """config/ carries the reference's 40 run configurations value for value (every key of the reference's file, same
     value; this build only ADDS keys: `dataset.synthetic`, defaults the reference's loader fills in) plus three BASELINE
-    cases the reference has no file for.  Compared against /root/reference where it exists (this container)."""
-    ref = "/root/reference/config"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree is not here")
+    cases the reference has no file for.  The reference's files are stored as tests/golden/reference_configs.json
+    ("<split>/<name>.json" -> the file's contents)."""
+    with open(os.path.join(ROOT, "tests", "golden", "reference_configs.json")) as f:
+        ref = json.load(f)
     ours = os.path.join(ROOT, "config")
     n = 0
-    for split in sorted(os.listdir(ref)):
-        for name in sorted(os.listdir(os.path.join(ref, split))):
-            if not name.endswith(".json"):
-                continue
-            with open(os.path.join(ref, split, name)) as f:
-                a = json.load(f)
-            with open(os.path.join(ours, split, name)) as f:
-                b = json.load(f)
-            for sec, kv in a.items():
-                for k, v in kv.items():
-                    assert b[sec][k] == v, (split, name, sec, k, v, b[sec].get(k))
-            n += 1
+    for key in sorted(ref):
+        split, name = key.split("/")
+        a = ref[key]
+        with open(os.path.join(ours, split, name)) as f:
+            b = json.load(f)
+        for sec, kv in a.items():
+            for k, v in kv.items():
+                assert b[sec][k] == v, (split, name, sec, k, v, b[sec].get(k))
+        n += 1
     assert n == 40
     extra = {"Amazon_13/star_DN+DR.json", "Amazon_6/deepfm_DN.json", "Taobao_30/deepctr_DN+DR_bs4096.json"}
     have = {"%s/%s" % (s, f) for s in os.listdir(ours) for f in os.listdir(os.path.join(ours, s)) if f.endswith(".json")}

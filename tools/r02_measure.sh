@@ -8,16 +8,16 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 REPO=$PWD
-python bench.py > "$OUT/bench_taobao10.json" 2> "$OUT/bench_taobao10.err"
-python bench.py --workload taobao30 --steps 10 --no-targets > "$OUT/bench_taobao30.json" 2> "$OUT/bench_taobao30.err"
-MAMDR_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 5 --warmup 2 --cpu-budget 0 --no-targets > "$OUT/bench_taobao10_2ranks_shared.json" 2> "$OUT/bench_2ranks.err"
+python bench.py --full > "$OUT/bench_taobao10.json" 2> "$OUT/bench_taobao10.err"
+python bench.py --full --workload taobao30 --steps 10 --no-targets > "$OUT/bench_taobao30.json" 2> "$OUT/bench_taobao30.err"
+MAMDR_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --steps 5 --warmup 2 --cpu-budget 0 --no-targets > "$OUT/bench_taobao10_2ranks_shared.json" 2> "$OUT/bench_2ranks.err"
 cd /tmp
-rocprofv3 --kernel-trace --stats -d "$OUT/prof10" -o run -- python3 "$REPO/bench.py" --steps 5 --warmup 1 --cpu-budget 0 --no-targets > "$OUT/prof10.log" 2>&1
-rocprofv3 --kernel-trace --stats -d "$OUT/prof30" -o run -- python3 "$REPO/bench.py" --workload taobao30 --steps 2 --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/prof30.log" 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o run -- python3 "$REPO/bench.py" --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o run -- python3 "$REPO/bench.py" --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc_write.log" 2>&1
-rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc30_fetch" -o run -- python3 "$REPO/bench.py" --workload taobao30 --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc30_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc30_write" -o run -- python3 "$REPO/bench.py" --workload taobao30 --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc30_write.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/prof10" -o run -- python3 "$REPO/bench.py" --full --steps 5 --warmup 1 --cpu-budget 0 --no-targets > "$OUT/prof10.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/prof30" -o run -- python3 "$REPO/bench.py" --full --workload taobao30 --steps 2 --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/prof30.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_fetch" -o run -- python3 "$REPO/bench.py" --full --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc_fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_write" -o run -- python3 "$REPO/bench.py" --full --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc_write.log" 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc30_fetch" -o run -- python3 "$REPO/bench.py" --full --workload taobao30 --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc30_fetch.log" 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc30_write" -o run -- python3 "$REPO/bench.py" --full --workload taobao30 --steps 1 --warmup 1 --cpu-budget 0 --no-profile --no-targets > "$OUT/pmc30_write.log" 2>&1
 rocprofv3 --kernel-trace --stats -d "$OUT/gather_trace" -o run -- python3 "$REPO/tools/gather_hbm.py" > "$OUT/gather_trace.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/gather_fetch" -o run -- python3 "$REPO/tools/gather_hbm.py" > "$OUT/gather_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/gather_write" -o run -- python3 "$REPO/tools/gather_hbm.py" > "$OUT/gather_write.log" 2>&1

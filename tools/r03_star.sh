@@ -7,13 +7,13 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 REPO=$PWD
 python -m pytest tests/test_gpu_parity.py -q -k "star" 2>&1 | tail -5
-python bench.py --workload amazon13 --steps 1 --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/bench_amazon13.json" 2> "$OUT/bench_amazon13.err"
+python bench.py --full --workload amazon13 --steps 1 --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/bench_amazon13.json" 2> "$OUT/bench_amazon13.err"
 python - "$OUT/bench_amazon13.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); print("amazon13 %.0f steps/s %.2f us/step" % (d["value"], d["us_per_domain_step"]))
 PY
 cd /tmp
-MAMDR_BENCH_ROW_SCALE=0.25 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- python3 "$REPO/bench.py" --workload amazon13 --steps 1 --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/prof.log" 2>&1
+MAMDR_BENCH_ROW_SCALE=0.25 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- python3 "$REPO/bench.py" --full --workload amazon13 --steps 1 --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/prof.log" 2>&1
 cd "$REPO"
 python tools/rocpd_summary.py stats "$(find "$OUT/prof" -name '*.db' | head -1)" "$OUT/kernel_stats_amazon13_q.csv"
 rm -rf "$OUT/prof"

@@ -5,7 +5,7 @@ OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 run() {   # name, workload, steps, env...
     local name=$1 wl=$2 steps=$3; shift 3
-    env "$@" python bench.py --workload $wl --steps $steps --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/$name.json" 2> "$OUT/$name.err"
+    env "$@" python bench.py --full --workload $wl --steps $steps --warmup 1 --cpu-budget 0 --no-targets --no-profile > "$OUT/$name.json" 2> "$OUT/$name.err"
     python - "$OUT/$name.json" "$name" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@ D=gpurun_out/${OUTDIR:-r04l}
 mkdir -p $D
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_edges.py tests/test_gpu_fullsize.py -m gpu -q -x -k "lazy or trainable or star or amazon or flush" 2>&1 | tail -3
 for W in amazon6 amazon13; do
-  python bench.py --workload $W --steps 1 --warmup 1 --cpu-budget 0 --no-targets 2>/dev/null | tail -1 > $D/bench_$W.json
+  python bench.py --full --workload $W --steps 1 --warmup 1 --cpu-budget 0 --no-targets 2>/dev/null | tail -1 > $D/bench_$W.json
   python - $D/bench_$W.json <<'PY'
 import json,sys
 j=json.load(open(sys.argv[1]))

@@ -6,7 +6,7 @@ for rep in 1 2; do
 for V in lds base; do
   L=""; [ $V = base ] && L=$PWD/mamdr_amd/build/variants/libflushbase.so
 for W in amazon6 amazon13; do
-  MAMDR_LIB_PATH=$L python bench.py --workload $W --steps 1 --warmup 1 --cpu-budget 0 --no-targets 2>/dev/null | tail -1 > $D/bench_${V}_${W}_$rep.json
+  MAMDR_LIB_PATH=$L python bench.py --full --workload $W --steps 1 --warmup 1 --cpu-budget 0 --no-targets 2>/dev/null | tail -1 > $D/bench_${V}_${W}_$rep.json
   python - $D/bench_${V}_${W}_$rep.json $V <<'PY'
 import json,sys
 j=json.load(open(sys.argv[1]))

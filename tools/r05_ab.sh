@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 has() { [[ " $STAGES " == *" $1 "* ]]; }
 run() {   # file, name, workload, steps, env...
     local file=$1 name=$2 wl=$3 steps=$4; shift 4
-    env "$@" timeout 400 python bench.py --workload $wl --steps $steps --warmup 1 --cpu-budget 0 --no-targets 2>/dev/null | python -c "
+    env "$@" timeout 400 python bench.py --full --workload $wl --steps $steps --warmup 1 --cpu-budget 0 --no-targets 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print('$name', round(d['value'],1), 'steps/s', round(d['us_per_domain_step'],3), 'us/step', {k.split(' ')[0]:(v['launches'],round(v['avg_us'],2)) for k,v in d['kernels_avg_us'].items() if isinstance(v,dict)})" >> "$OUT/$file"
 }

@@ -26,14 +26,14 @@ if has test; then
 fi
 if has bench; then
     T0=$(date +%s)
-    timeout 600 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+    timeout 600 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
     echo "default bench.py run: $(( $(date +%s) - T0 )) s wall"
-    MAMDR_BENCH_SHARE_GPU=1 timeout 300 python bench.py --gpus 2 --steps 5 --warmup 2 --cpu-budget 0 --no-targets > "$OUT/bench_taobao10_2ranks_shared.json" 2> "$OUT/bench_2ranks.err"
+    MAMDR_BENCH_SHARE_GPU=1 timeout 300 python bench.py --full --gpus 2 --steps 5 --warmup 2 --cpu-budget 0 --no-targets > "$OUT/bench_taobao10_2ranks_shared.json" 2> "$OUT/bench_2ranks.err"
 fi
 cd /tmp
 if has prof; then
     # (--lanes 0: the lane leg stretches the kernels it shares the device with; these summaries are the single chain's)
-    timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof10" -o run -- python3 "$REPO/bench.py" --steps 5 --warmup 1 --cpu-budget 0 --no-targets --lanes 0 > "$OUT/prof10.log" 2>&1
+    timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof10" -o run -- python3 "$REPO/bench.py" --full --steps 5 --warmup 1 --cpu-budget 0 --no-targets --lanes 0 > "$OUT/prof10.log" 2>&1
     timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof30" -o run -- python3 "$REPO/bench.py" --workload taobao30 --steps 2 --warmup 1 --cpu-budget 0 --no-targets --no-profile --lanes 0 > "$OUT/prof30.log" 2>&1
     timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/profa6" -o run -- python3 "$REPO/bench.py" --workload amazon6 --steps 1 --warmup 1 --cpu-budget 0 --no-targets --no-profile --lanes 0 > "$OUT/profa6.log" 2>&1
     timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/profa13" -o run -- python3 "$REPO/bench.py" --workload amazon13 --steps 1 --warmup 1 --cpu-budget 0 --no-targets --no-profile --lanes 0 > "$OUT/profa13.log" 2>&1

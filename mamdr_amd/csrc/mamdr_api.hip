@@ -1115,9 +1115,13 @@ int mamdr_set_counters(mamdr_ctx* c, int64_t optimizer_steps, int64_t dropout_st
     c->flush_t = optimizer_steps;
     c->adam_t = optimizer_steps;
     float b1 = 1.0f, b2 = 1.0f;                 // TF's running products, one fp32 rounding per step (as the step loop forms them)
-    for (int64_t t = 0; t < optimizer_steps && (b1 != 0.f || b2 != 0.f); ++t) {      // (both products end at 0: ~1e5 steps)
-        b1 = b1 * c->cfg.adam_beta1;
-        b2 = b2 * c->cfg.adam_beta2;
+    for (int64_t t = 0; t < optimizer_steps; ++t) {
+        const float n1 = b1 * c->cfg.adam_beta1, n2 = b2 * c->cfg.adam_beta2;
+        // both products at a fixed point: every further step leaves them as they are.  0.9 / 0.999 end on denormal fixed
+        // points (4 and 500 x 2^-149) after ~1,000 / ~1.6e5 steps; beta = 1 keeps the product at 1 from the start
+        if (n1 == b1 && n2 == b2) break;
+        b1 = n1;
+        b2 = n2;
     }
     c->b1p = b1;
     c->b2p = b2;

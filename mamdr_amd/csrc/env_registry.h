@@ -22,24 +22,14 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_LAZY_FLUSH_EVERY", "lib", "steps between forced replays of lagging table rows (default 32)"},
     {"MAMDR_LAZY_LOG_CAP", "lib", "capacity of the alpha ring of the lazy table Adam (tests: force it to wrap)"},
     {"MAMDR_NO_TAILFUSE", "lib", "1: the table kernels as launches of their own instead of riders"},
-    {"MAMDR_NO_W0LIN", "lib", "1: dW0[256:384] from tiles instead of by linearity (rounding-level differences)"},
     {"MAMDR_TOWER_TILE", "lib,bench", "rows per tower workgroup: 0 automatic, 4, 16 (initial value of mamdr_set_tower_tile)"},
-    {"MAMDR_RPG", "lib", "rows per row group of k_wgrad (multiple of 8; diagnostic sweep)"},
-    {"MAMDR_MAX_GROUPS", "lib", "upper bound of k_wgrad's row groups (diagnostic sweep)"},
     {"MAMDR_FUSED", "lib", "0: slab path everywhere; 2: k_wgrad_adam path for every batch size (default: up to 4 rows x CUs)"},
-    {"MAMDR_FUSED_PF", "lib", "1: prefetch riders in k_wgrad_adam's launch (measured, off)"},
     {"MAMDR_DM_EACH", "lib", "1: k_dm_finish after every step (diagnostic; same bits)"},
     {"MAMDR_DM_CALL", "lib", "1: k_dm_finish closes every call (diagnostic; same bits)"},
     {"MAMDR_T4_NO_W1L", "lib", "1: k_tower4 without the W1 image in LDS (diagnostic)"},
     {"MAMDR_NO_W2_DIRECT", "lib", "1: k_transpose_w opens a call instead of the W2-in-place tower instance"},
     {"MAMDR_NO_PREGATHER", "lib,bench", "1: no k_pass_prep; the tower gathers its rows itself"},
-    {"MAMDR_NO_GATHER_PF", "lib", "1: no rider workgroups touching the next step's gather"},
-    {"MAMDR_GATHER_PF_IN", "lib", "update: the gather riders in k_update's launch (default: k_wgrad's)"},
-    {"MAMDR_WGRAD_PAIRS", "lib", "1: k_wgrad8 in -DMAMDR_WGRAD8 builds (measured, off)"},
     {"MAMDR_STAR_DENSE_SLICES", "lib", "1: every per-domain Star slice swept every step (diagnostic; same bits)"},
-    {"MAMDR_STAR_PNB_KERNEL", "lib", "1: PartitionedNorm backward partials as a launch of their own (same bits)"},
-    {"MAMDR_STAR_PNB_FUSED", "lib", "1: PartitionedNorm backward inside k_emb_reduce (measured, not adopted: parity)"},
-    {"MAMDR_STAR_PNB_APPLY", "lib", "1: k_star_pnb_apply as a launch of its own inside a call too (same bits; diagnostic)"},
     // ---- library, generic-layer engine (read at mamdr_graph_create)
     {"MAMDR_GRAPH_NO_GROUP", "lib", "1: one launch per expert instead of grouped launches"},
     {"MAMDR_GRAPH_NO_DEFER", "lib", "1: a pair of weight-gradient launches per layer instead of the queued flat grid"},

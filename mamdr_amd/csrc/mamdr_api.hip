@@ -109,17 +109,6 @@ struct mamdr_ctx {
     bool fused = false;
     float* star_alpha = nullptr;    // Star tower: alphas of the current call's steps (lazy replay of the other domains' slices)
     int star_dense_slices = 0;      // MAMDR_STAR_DENSE_SLICES=1: every slice swept every step (diagnostic; same bits)
-    bool star_pn_in_tower = true;   // PartitionedNorm backward: per-tile sums in the tower's tail (MAMDR_STAR_PNB_KERNEL=1:
-                                    // k_star_pnb_partial as a launch of its own; same bits)
-    // MAMDR_STAR_PNB_FUSED=1 (measured, not adopted -- DESIGN.md section 8): no k_star_pnb_apply either; the table rows
-    // get PartitionedNorm's backward inside k_emb_reduce and the domain row's gradient comes in closed form from
-    // k_star_pnb_final.  Saves the 6.3 us launch, costs 2.3 us in k_wgrad_reduce -- and the closed form is EXACTLY zero
-    // where the per-row sum leaves rounding residue, which Adam turns into a random walk of the domain row (in the
-    // reference too): the moving statistics then lag differently and validation AUC moves by ~1e-3.
-    bool star_pn_fused = false;
-    // k_star_pnb_apply's work spread over the launches around it inside a call (StarPnBwdArgs::fused == 2; same bits).
-    // MAMDR_STAR_PNB_APPLY=1 keeps the launch (diagnostic).
-    bool star_pn_no_apply = true;
     int t4_no_w1l = 0;              // MAMDR_T4_NO_W1L=1: k_tower4 without the W1 image in LDS (diagnostic)
     int fused_max_batch = 1024;     // batches up to this size take the fused path (MAMDR_FUSED=2: every batch size):
                                     // 4 rows x the CU count, set at mamdr_create
@@ -138,14 +127,6 @@ struct mamdr_ctx {
     size_t pg_pos = 0;
     int64_t pg_hits = 0;            // calls served from an entry (mamdr_pregather_hits)
     int64_t pg_launches = 0;        // hints that launched k_pass_prep_multi (mamdr_pregather_launches)
-    bool gather_pf = true;          // MAMDR_NO_GATHER_PF=1: no riders in k_update's launch touching the next step's gather
-    bool wgrad_pairs = false;          // MAMDR_WGRAD_PAIRS=1: k_wgrad8 (eight waves, one slab per pair of row groups) where a step has > 8 groups
-    bool gather_pf_in_wgrad = true;    // the riders of the next step's gather sit in k_wgrad's launch (round 5: k_update, bound by what it pulls over
-                                       // the fabric, loses 0.42 us without them, k_wgrad gains 0.13; profiles/r05_ab_riders_place.txt);
-                                       // MAMDR_GATHER_PF_IN=update: in k_update's launch as in rounds 3 - 4
-    bool fused_pf = false;          // MAMDR_FUSED_PF=1: riders in k_wgrad_adam's launch touch the next tower launch's pre-gathered rows (round 5:
-                                    // measured and left off -- the tower gains 0.08 us, k_wgrad_adam's second round of blocks costs 0.8;
-                                    // profiles/r05_ab_fused_pf.txt)
     bool use_pre = true;            // MAMDR_NO_PREGATHER=1: the towers gather through perm / uid / pid every step
     float* dmsnap[2] = {nullptr, nullptr};
     int dm_cur = 0;
@@ -192,9 +173,7 @@ struct mamdr_ctx {
     float* loss_part = nullptr;     // train: per tile of a batch
     float* eval_part = nullptr;     // eval: per tile of a split (grown on bind)
     int64_t eval_part_cap = 0;
-    float* slabs = nullptr;
-    int max_groups = 16;
-    int rpg_override = 0;       // MAMDR_RPG: rows per K-split group of k_wgrad (diagnostic)
+    float* slabs = nullptr;         // [WGRAD_MAX_GROUPS][slab_ld]
     bool tail_fuse = true;      // MAMDR_NO_TAILFUSE=1: k_emb_reduce / k_lin_sweep as launches of their own
     // the other half of the row / map double buffer: the NEXT step's k_emb_rows rides in this step's last launch
     int32_t* urow_alt = nullptr;
@@ -378,11 +357,6 @@ static void fill_emb_args(const mamdr_ctx* c, int32_t optimizer, float alpha, fl
     ea.alpha_log = c->alpha_log;
     ea.log_mask = c->log_cap - 1;
     ea.t_now = (int)c->adam_t;
-    if (c->star && c->star_pn_fused) {         // PartitionedNorm's backward rides in k_emb_reduce (EmbStepArgs::pn_sums)
-        ea.pn_sums = c->star_sums;
-        ea.pn_means = c->star_sums + 2 * XDIM + EMB;
-        ea.pn = c->pn;
-    }
     EmbTable& tu = ea.t[0];
     EmbTable& ti = ea.t[1];
     tu.n_rows = c->cfg.n_user;
@@ -412,6 +386,7 @@ static void fill_emb_args(const mamdr_ctx* c, int32_t optimizer, float alpha, fl
 }
 
 constexpr int STAR_ALPHA_CAP = 1 << 12;      // steps between two replays of the lagging Star slices (power of two)
+constexpr int WGRAD_MAX_GROUPS = 16;         // row groups of k_wgrad at most (= gradient slabs k_update sums)
 static float table_two_l2(const mamdr_ctx* c) { return c->star ? 0.f : 2.0f * c->cfg.l2_emb; }
 
 // materialise a domain-table step the k_wgrad_adam path left pending
@@ -525,25 +500,176 @@ static void emb_post_step(mamdr_ctx* c, int32_t optimizer, float alpha, float om
     }
 }
 
-// ---- Star tower: one training step on `rows` rows of domain `domain` (star.py:70-97; kernels in star_kernels.hip)
-// next_rows (nullable): the NEXT step's k_emb_rows arguments (alternate buffers), riding in this step's last launch
-// lazy_idx >= 0: only slice `domain` of the per-domain tensors is stepped (the others are replayed by the caller,
-// k_star_catchup) and the step's alpha is logged at that slot
-static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const int32_t* d_perm, int64_t row_base, int rows,
-                           int32_t optimizer, float alpha, float omb1, float omb2, float* loss_out,
-                           const EmbRowsArgs* next_rows, const EmbStepArgs* next_catchup, int lazy_idx, bool eff_current,
-                           bool eff_for_next) {
-    const int rows_pad = (rows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
+// ---- the decisions of a training call, each made in one place (mamdr_step_path / mamdr_tower_tile report the same ones)
+// a step's rows padded to whole 16-row tiles
+static int64_t pad_rows(int64_t rows) { return (rows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS; }
+// rows of the batch at row_base of a pass of pass_rows rows (the last batch of a pass may be short)
+static int rows_at(int64_t pass_rows, int64_t row_base, int batch) { return (int)std::min<int64_t>(batch, pass_rows - row_base); }
+// one path per call (the pending domain-table step lives across the steps of a call): k_wgrad_adam for batches up to
+// fused_max_batch rows (measured: 27.3 vs 29.5 us / step at 1,024 rows, a tie at 4,096), k_wgrad -> slabs -> k_update above
+static bool takes_fused_path(const mamdr_ctx* c, int64_t batch) { return c->fused && pad_rows(batch) <= c->fused_max_batch; }
+// small steps run the 4-row-tile tower (all CUs busy), the others the 16-row one (the only one of the Star tower)
+static bool takes_tower4(const mamdr_ctx* c, int64_t rows_pad) {
+    return !c->star && c->tower_tile != 16 && (c->tower_tile == 4 || rows_pad <= c->tower4_max_rows);
+}
+// row groups of k_wgrad (= gradient slabs) of a step and the rows of each (measured: 1024 rows, 8 groups of 128: 31.0 us /
+// step vs 32.0 with 4 of 256; batches of <= 512 rows keep 256-row groups: one or two slabs)
+static int wgrad_groups(int rows_pad, int* rpg) {
+    int r = rows_pad <= 512 ? 256 : (rows_pad <= 1024 ? 128 : (rows_pad <= 4096 ? 256 : 512));
+    int groups = (rows_pad + r - 1) / r;
+    if (groups > WGRAD_MAX_GROUPS) {
+        r = ((rows_pad + WGRAD_MAX_GROUPS - 1) / WGRAD_MAX_GROUPS + 7) / 8 * 8;
+        groups = (rows_pad + r - 1) / r;
+    }
+    *rpg = r;
+    return groups;
+}
+// TF1 Adam's step size from the running beta powers
+static float adam_alpha(float lr, float b1p, float b2p) { return lr * sqrtf(1.0f - b2p) / (1.0f - b1p); }
+// the counters of the step about to run: Adam's step count and fp32 beta powers advance; returns the step's alpha (lr
+// for SGD / accumulate)
+static float advance_step(mamdr_ctx* c, int32_t optimizer, float lr) {
+    if (optimizer != MAMDR_OPT_ADAM) return lr;
+    c->adam_t += 1;
+    c->b1p = c->b1p * c->cfg.adam_beta1;
+    c->b2p = c->b2p * c->cfg.adam_beta2;
+    return adam_alpha(lr, c->b1p, c->b2p);
+}
+
+// one mamdr_train_steps_n call: its arguments, then what is decided for it once, before its first launch (plan_call)
+enum class StepPath { star, fused, slab };
+struct CallPlan {
+    const SplitData* d;
+    int domain;
+    const int32_t* perm;
+    int64_t pass_rows, first_step, n_steps;
+    int batch;
+    int32_t optimizer;
+    float lr, omb1, omb2;
+    float* loss_out;            // nullable: [n_steps] the loss of every step
+    uint32_t seed, drop_thresh;
+    float keep_scale;
+    int use_dropout;
+    StepPath path = StepPath::slab;
+    // lazy table Adam with fused tails: the table kernels ride in the dense launches, and the NEXT step's k_emb_rows /
+    // k_emb_catchup in this step's (profiling runs keep them apart for per-kernel times; a reported loss reads the tables
+    // between the two and keeps them apart too)
+    bool tail = false;
+    bool pre = false;           // k_wgrad_adam path: the rows of the whole call resolved and gathered once (k_pass_prep)
+    bool pre_cached = false;    // ... by mamdr_pregather_passes ahead of the call: row pre_pos0 sits at pre_base
+    int64_t pre_pos0 = 0, pre_n = 0, pre_base = 0;
+    bool need_wT = false;       // a step of the call runs k_tower4, which reads the transposed W1 / W2 copies
+    bool build_wT = false;      // ... which are built at the start of the call
+    bool w2_direct = false;     // ... or not: the call's first tower reads W2 in place
+    bool star_lazy = false;     // Star: the other domains' slices are replayed by k_star_catchup, not stepped every step
+};
+
+static void plan_call(mamdr_ctx* c, CallPlan& P) {
+    P.path = c->star ? StepPath::star : (takes_fused_path(c, P.batch) ? StepPath::fused : StepPath::slab);
+    const bool fused = P.path == StepPath::fused;
+    const bool accumulate = P.optimizer == MAMDR_OPT_ACCUMULATE;
+    P.tail = c->tail_fuse && c->cfg.emb_trainable && c->lazy && P.optimizer == MAMDR_OPT_ADAM && !c->profile && !P.loss_out;
+    const int first_rows = rows_at(P.pass_rows, P.first_step * P.batch, P.batch);
+    // the four-row tower needs transposed W1 / W2 copies: refreshed at the start of a call because the caller may have
+    // assigned new weights, kept current by k_update -- only when a step of THIS call is small enough for that tower (the
+    // rows of a pass's steps never grow: the last one is the smallest); a 4,096-row call over a domain without a short last
+    // batch needs no copies at all
+    P.need_wT = takes_tower4(c, pad_rows(rows_at(P.pass_rows, (P.first_step + P.n_steps - 1) * P.batch, P.batch)));
+    // on the k_wgrad_adam path the rows of the whole call are resolved and gathered once (frozen tables; 4-row tower)
+    P.pre_pos0 = P.first_step * P.batch;
+    P.pre_n = std::min<int64_t>((P.first_step + P.n_steps) * P.batch, P.pass_rows) - P.pre_pos0;
+    P.pre = fused && c->use_pre && P.pre_n > 0;
+    // the transposed copies: built at the start of the call unless the previous call's steps left them current (no
+    // sync_tables since).  On the k_wgrad_adam path with the W1 image (k_tower4<.., W1L, PRE>) only W2T is read, and only
+    // the call's FIRST tower can find it stale -- k_wgrad_adam rewrites every copy with the step -- so that tower reads W2
+    // itself (w2_direct: 32 B runs of 128 rows, four loads per lane) and nothing is transposed at all
+    P.build_wT = P.need_wT && !c->wT_valid;
+    if (P.build_wT && P.pre && c->w2_direct_ok && !accumulate && !c->t4_no_w1l && c->tower_tile != 16 && tower4_w1l_ready() &&
+        tower4_takes_w1l(first_rows, c->t4_no_w1l)) {
+        P.build_wT = false;
+        P.w2_direct = true;
+    }
+    // ... and a call whose FIRST step runs the 16-row tower (which reads no copy) needs none built either: k_update
+    // rewrites the copy of every element it steps, so they are current from the call's second step on -- before the
+    // short last batch that runs the four-row tower
+    if (P.build_wT && !accumulate && !fused && !c->star && !takes_tower4(c, pad_rows(first_rows)) && P.n_steps > 1)
+        P.build_wT = false;
+    // ... unless mamdr_pregather_passes gathered this pass ahead of the call: entries are consumed in order (an entry
+    // stays current while calls keep working on its pass); a call that matches none drops them all
+    if (P.pre) {
+        for (size_t k = c->pg_pos; k < c->pg.size(); ++k) {
+            const mamdr_ctx::PgEntry& e = c->pg[k];
+            if (e.domain == P.domain && e.perm == P.perm && e.n == P.pass_rows && e.batch == P.batch) {
+                c->pg_pos = k;
+                P.pre_base = e.off + P.pre_pos0;
+                P.pre_cached = true;
+                c->pg_hits += 1;
+                break;
+            }
+        }
+        if (!P.pre_cached) c->pg.clear();
+    }
+    // Star tower: a batch carries one domain, so D - 1 of the D slices of every per-domain tensor see a zero gradient
+    // and only decay -- TF1's dense Adam still moves them every step (star_kernels.hip).  Inside a call those steps are
+    // postponed: k_star_update covers the live slice only and logs the step's alpha, k_star_catchup replays the
+    // skipped steps when the call ends (the same arithmetic in the same order: bit-identical; one sweep of the 13
+    // slices per call instead of one per step).  Calls of a single step gain nothing and sweep as before.
+    P.star_lazy = c->star && P.optimizer == MAMDR_OPT_ADAM && P.n_steps >= 2 && !P.loss_out && !c->star_dense_slices &&
+                  c->cfg.n_domain > 1;
+}
+
+// the NEXT step of this call (Adam step adam_t + 1, its batch at row_base), lazy table Adam with fused tails: its row ids
+// and maps are resolved into the alternate buffers in this step's k_wgrad launch (nr), its catch-up runs in this step's
+// last launch (nea)
+static void fill_next_step(const mamdr_ctx* c, const CallPlan& P, int64_t row_base, EmbRowsArgs& nr, EmbStepArgs& nea) {
+    const int rows = rows_at(P.pass_rows, row_base, P.batch);
+    const float alpha = adam_alpha(P.lr, c->b1p * c->cfg.adam_beta1, c->b2p * c->cfg.adam_beta2);
+    fill_rows_args(c, *P.d, P.perm, row_base, rows, (int)pad_rows(rows), alpha, c->adam_t + 1, true, nr);
+    fill_emb_args(c, MAMDR_OPT_ADAM, alpha, P.omb1, P.omb2, table_two_l2(c), rows, c->star ? XDIM : 2 * EMB, nea);
+    nea.t_now = (int)c->adam_t + 1;
+    nea.t[0].brow = c->urow_alt;
+    nea.t[0].map = c->map_u_alt;
+    nea.t[1].brow = c->irow_alt;
+    nea.t[1].map = c->map_i_alt;
+}
+
+// ... and once those launches are issued, the alternate buffers hold the rows of the step about to run, caught up
+static void take_next_rows(mamdr_ctx* c) {
+    std::swap(c->urow, c->urow_alt);
+    std::swap(c->irow, c->irow_alt);
+    std::swap(c->map_u, c->map_u_alt);
+    std::swap(c->map_i, c->map_i_alt);
+    c->rows_ready = true;
+    c->catchup_ready = true;
+    c->tables_dirty = true;
+}
+
+// ---- Star tower: step s of a call (star.py:70-97; kernels in star_kernels.hip)
+static int star_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
+    const SplitData& d = *P.d;
+    const int domain = P.domain;
+    const int32_t optimizer = P.optimizer;
+    const float omb1 = P.omb1, omb2 = P.omb2;
+    float* const loss_out = P.loss_out ? P.loss_out + s : nullptr;
+    const int64_t row_base = (P.first_step + s) * P.batch;
+    const int rows = rows_at(P.pass_rows, row_base, P.batch);
+    const int rows_pad = (int)pad_rows(rows);
     const int chunks = (rows + STAR_CHUNK - 1) / STAR_CHUNK;
+    // lazy slices: only slice `domain` of the per-domain tensors is stepped and the step's alpha is logged at lazy_idx
+    const int lazy_idx = (int)(s & (STAR_ALPHA_CAP - 1));
+    const bool next = P.tail && s + 1 < P.n_steps;
+    EmbRowsArgs nr;
+    EmbStepArgs nea;
+    if (next) fill_next_step(c, P, row_base + P.batch, nr, nea);
     float* blk = c->params + c->table_floats;
     TowerArgs ta;
     fill_tower_common(c, d, ta);
-    ta.perm = d_perm;
+    ta.perm = P.perm;
     ta.row_base = row_base;
     ta.rows = rows;
     ta.batch = rows;
     if (c->cfg.emb_trainable && c->lazy && optimizer == MAMDR_OPT_ADAM)
-        emb_pre_step(c, d, d_perm, row_base, rows, rows_pad, alpha, omb1, omb2);
+        emb_pre_step(c, d, P.perm, row_base, rows, rows_pad, alpha, omb1, omb2);
     StarPrepArgs pa;
     memset(&pa, 0, sizeof(pa));
     pa.blk = blk;
@@ -559,7 +685,7 @@ static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const i
     pa.aux = c->aux;
     pa.AL = c->AL;
     pa.train = 1;
-    pa.skip_eff = eff_current ? 1 : 0;      // (the previous step of this call wrote it: k_star_update, eff_out)
+    pa.skip_eff = P.star_lazy && s > 0 ? 1 : 0;     // (the previous step of this call wrote it: k_star_update, eff_out)
     {
         Prof p(c, MAMDR_KERNEL_AUX);            // k_star_stats + k_star_prep as one timed group
         // forward statistics read the raw rows (domain table straight from the flat vector: SL.dm == L.dm == 0)
@@ -569,7 +695,7 @@ static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const i
 
     ta.dense = c->eff;
     ta.pn_aff = c->pn;
-    ta.pn_part = c->star_pn_in_tower ? c->star_part : nullptr;
+    ta.pn_part = c->star_part;    // PartitionedNorm backward: per-tile sums in the tower's tail
     ta.use_dropout = 0;
     ta.keep_scale = 1.0f;
     ta.acts = c->acts;
@@ -599,13 +725,8 @@ static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const i
     wa.tiles = c->tiles;
     wa.n_tiles = c->n_tiles;
     wa.rows_pad = rows_pad;
-    int rpg = rows_pad <= 512 ? 256 : (rows_pad <= 1024 ? 128 : (rows_pad <= 4096 ? 256 : 512));
-    if (c->rpg_override > 0) rpg = c->rpg_override;        // MAMDR_RPG (diagnostic)
-    int groups = (rows_pad + rpg - 1) / rpg;
-    if (groups > c->max_groups) {
-        rpg = ((rows_pad + c->max_groups - 1) / c->max_groups + 7) / 8 * 8;
-        groups = (rows_pad + rpg - 1) / rpg;
-    }
+    int rpg = 0;
+    const int groups = wgrad_groups(rows_pad, &rpg);
     wa.n_groups = groups;
     wa.rows_per_group = rpg;
     wa.slabs = c->slabs;
@@ -636,20 +757,17 @@ static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const i
     ba.dmpart = c->star_dmpart;
     ba.dmsum = c->star_sums + 2 * XDIM;
     ba.means = c->star_sums + 2 * XDIM + EMB;
-    ba.fused = c->star_pn_fused ? 1 : 0;
     // lazy table Adam with fused tails: PartitionedNorm's backward first (it only needs the tower's outputs), then
     // [k_wgrad + k_emb_reduce(t) + k_emb_rows(t+1)], then [k_star_update + k_emb_catchup(t+1)]
-    const bool tail = c->tail_fuse && c->cfg.emb_trainable && c->lazy && optimizer == MAMDR_OPT_ADAM && !c->profile &&
-                      !loss_out;
     // ... and (round 6) without k_star_pnb_apply when a catch-up launch follows: the table rows take PartitionedNorm's
     // backward inside k_emb_reduce, the domain columns' partial sums ride in k_wgrad_reduce and are finished and stepped
     // in k_star_update_catchup (StarPnBwdArgs::fused == 2; the same roundings in the same order as the launch it replaces)
-    const bool no_apply = tail && next_catchup && !ba.fused && c->star_pn_no_apply;
-    if (no_apply) ba.fused = 2;
-    if (tail) {
+    const bool no_apply = next;
+    ba.fused = no_apply ? 2 : 0;
+    if (P.tail) {
         {
             Prof p(c, MAMDR_KERNEL_AUX);
-            launch_star_pn_bwd(ba, false, c->stream, c->star_pn_in_tower);   // (its last kernel, the domain-row column sums, rides below)
+            launch_star_pn_bwd(ba, false, c->stream);   // (its last kernel, the domain-row column sums, rides below)
         }
         EmbStepArgs tea;
         fill_emb_args(c, optimizer, alpha, omb1, omb2, table_two_l2(c), rows, XDIM, tea);
@@ -661,14 +779,14 @@ static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const i
             tea.pn = c->pn;
         }
         Prof p(c, MAMDR_KERNEL_WGRAD);
-        launch_wgrad_reduce(wa, tea, next_rows, ba.fused == 1 ? nullptr : &ba, c->stream);
+        launch_wgrad_reduce(wa, tea, next ? &nr : nullptr, &ba, c->stream);
     } else {
         {
             Prof p(c, MAMDR_KERNEL_WGRAD);
             launch_wgrad(wa, c->stream);
         }
         Prof p(c, MAMDR_KERNEL_AUX);                  // PartitionedNorm's backward: 4 launches as one timed group
-        launch_star_pn_bwd(ba, true, c->stream, c->star_pn_in_tower);
+        launch_star_pn_bwd(ba, true, c->stream);
     }
 
     float* slot_m = optimizer == MAMDR_OPT_ACCUMULATE ? c->accum : c->adam_m;
@@ -693,28 +811,322 @@ static int star_train_step(mamdr_ctx* c, const SplitData& d, int domain, const i
     ua.opt.omb2 = omb2;
     ua.opt.eps = c->cfg.adam_eps;
     ua.opt.two_l2 = 0.f;
-    if (lazy_idx >= 0) {
+    if (P.star_lazy) {
         ua.only_live = 1;
         ua.alpha_log = c->star_alpha;
         ua.log_idx = lazy_idx;
-        if (eff_for_next) ua.eff_out = c->eff;
+        if (s + 1 < P.n_steps) ua.eff_out = c->eff;
     }
     {
         Prof p(c, MAMDR_KERNEL_UPDATE);
         ua.dm_elsewhere = no_apply ? 1 : 0;
-        if (tail && next_catchup) launch_star_update_catchup(ua, *next_catchup, no_apply ? &ba : nullptr, c->stream);
+        if (next) launch_star_update_catchup(ua, nea, no_apply ? &ba : nullptr, c->stream);
         else launch_star_update(ua, c->stream);
     }
-    if (tail && next_rows) {
-        std::swap(c->urow, c->urow_alt);
-        std::swap(c->irow, c->irow_alt);
-        std::swap(c->map_u, c->map_u_alt);
-        std::swap(c->map_i, c->map_i_alt);
-        c->rows_ready = true;
-        c->catchup_ready = next_catchup != nullptr;
-        c->tables_dirty = true;
+    if (next) take_next_rows(c);
+    if (c->cfg.emb_trainable && !P.tail) emb_post_step(c, optimizer, alpha, omb1, omb2, rows);
+    c->global_step += 1;
+    // the other slices catch up: alpha log full / call over
+    if (P.star_lazy && (lazy_idx + 1 == STAR_ALPHA_CAP || s + 1 == P.n_steps)) {
+        StarCatchArgs ca;
+        memset(&ca, 0, sizeof(ca));
+        ca.p = c->params + c->table_floats;
+        ca.m = c->adam_m + c->table_floats;
+        ca.v = c->adam_v + c->table_floats;
+        ca.SL = c->SL;
+        ca.n_domain = c->cfg.n_domain;
+        ca.d_live = domain;
+        ca.alpha_log = c->star_alpha;
+        ca.first_idx = 0;
+        ca.n_steps = lazy_idx + 1;
+        ca.log_mask = STAR_ALPHA_CAP - 1;
+        ca.omb1 = omb1;
+        ca.omb2 = omb2;
+        ca.eps = c->cfg.adam_eps;
+        Prof p(c, MAMDR_KERNEL_AUX);
+        launch_star_catchup(ca, c->stream);
     }
-    if (c->cfg.emb_trainable && !tail) emb_post_step(c, optimizer, alpha, omb1, omb2, rows);
+    return MAMDR_OK;
+}
+
+// ---- the mlp-family towers (mlp / deepfm / wdl / pnn / nfm): the tower launch of step s, shared by both paths
+static void fill_step_tower(const mamdr_ctx* c, const CallPlan& P, int64_t row_base, int rows, TowerArgs& ta) {
+    fill_tower_common(c, *P.d, ta);
+    ta.perm = P.perm;
+    ta.row_base = row_base;
+    ta.rows = rows;
+    ta.batch = rows;
+    ta.seed = P.seed;
+    ta.step = c->global_step;
+    ta.drop_thresh = P.drop_thresh;
+    ta.keep_scale = P.keep_scale;
+    ta.use_dropout = P.use_dropout;
+    ta.acts = c->acts;
+    ta.dz = c->dz;
+    ta.dlogit = c->dlogit;
+    ta.domrow = c->domrow;
+    ta.dxe = c->dxe;
+    ta.dx_ld = 2 * EMB;
+    ta.urow = c->urow;
+    ta.irow = c->irow;
+    ta.map_u = c->map_u;
+    ta.map_i = c->map_i;
+    ta.loss_part = c->loss_part;
+    ta.fmq = c->fmq;
+    if (c->L.lv_count > 0) ta.uw_off = c->L.lv + P.domain;
+#ifdef MAMDR_STAMPS
+    ta.stamps = c->stamps ? c->stamps + (c->global_step & 1) * 16384 : nullptr;      // two steps side by side
+#endif
+    ta.wT = c->wT;
+    ta.no_w1l = c->t4_no_w1l;
+}
+
+static int run_step_tower(mamdr_ctx* c, const TowerArgs& ta, bool use4, int64_t s) {
+    if ((c->pnn || c->nfm) && !use4)
+        return fail(MAMDR_ENOTBUILT, "pnn / nfm tower: a training step of %d rows needs the four-row tower (MAMDR_TOWER_TILE=16?)", ta.rows);
+    Prof p(c, MAMDR_KERNEL_FWD_BWD);
+#ifdef MAMDR_TOWER_TWICE
+    // diagnostic build (tools/stamp_tower.py with MAMDR_DIAG_FLAGS=-DMAMDR_TOWER_TWICE): the same tower launch twice in a
+    // row -- idempotent (the pending domain-table step is formed from its snapshot, every output is overwritten) -- so that
+    // the stamps of the SECOND launch show the kernel with its own code and data still where the first left them
+    if (use4) (void)launch_tower4_train(ta, c->stream);
+#endif
+    const int t4e = use4 ? launch_tower4_train(ta, c->stream) : (launch_tower_train(ta, c->stream), 0);
+    if (t4e == T4_E_W2D_LDS) return fail(MAMDR_EHIP, "k_tower4<W2D> was refused its LDS limit (hipFuncSetAttribute)");
+    if (t4e) return fail(MAMDR_ESTATE, "w2_direct without the W1-image instance of k_tower4 (step %lld of the call)", (long long)s);
+    return MAMDR_OK;
+}
+
+// ---- k_wgrad_adam path (frozen-table mlp): tower + weight gradients and optimiser step in one launch; the domain table's
+// step stays pending (DmStep): the next step's tower kernel applies it
+static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
+    const int32_t optimizer = P.optimizer;
+    const int64_t row_base = (P.first_step + s) * P.batch;
+    const int rows = rows_at(P.pass_rows, row_base, P.batch);
+    const int rows_pad = (int)pad_rows(rows);
+    const bool use4 = takes_tower4(c, rows_pad);
+    DmStep& dm_pending = c->dm_pending;
+    float* const dense_m = (optimizer == MAMDR_OPT_ACCUMULATE ? c->accum : c->adam_m) + c->table_floats;
+    TowerArgs ta;
+    fill_step_tower(c, P, row_base, rows, ta);
+    ta.w0dom_snap = c->w0dom_copy;
+    c->dm_cur ^= 1;
+    ta.dms = dm_pending;                       // the previous step of this call (snap == null: none)
+    ta.dm_hint = P.domain;
+    if (P.pre) {
+        const int64_t at = P.pre_base + row_base - P.pre_pos0;
+        ta.xpre = c->xpre + (size_t)at * 2 * EMB;
+        ta.pdom = c->pdom + at;
+        ta.plabel = c->plabel + at;
+    }
+    ta.dm_live_p = c->params + c->table_floats + c->L.dm;
+    ta.dm_live_m = dense_m + c->L.dm;
+    ta.dm_live_v = c->adam_v + c->table_floats + c->L.dm;
+    ta.dm_snap_out = c->dmsnap[c->dm_cur];
+    ta.w2_direct = (P.w2_direct && s == 0) ? 1 : 0;
+    if (int rc = run_step_tower(c, ta, use4, s)) return rc;
+    FusedArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.acts = c->acts;
+    fa.dz = c->dz;
+    fa.dlogit = c->dlogit;
+    fa.domrow = c->domrow;
+    fa.xa = ta.xpre ? ta.xpre : c->acts;
+    fa.xa_ld = ta.xpre ? 2 * EMB : ACT_LD;
+    fa.rows_pad = rows_pad;
+    fa.rows = rows;
+    fa.p = c->params + c->table_floats;
+    fa.m = dense_m;
+    fa.v = c->adam_v + c->table_floats;
+    fa.L = c->L;
+    fa.n_domain = c->cfg.n_domain;
+    fa.w0dom_snap = c->w0dom_copy;
+    fa.dm_snap = c->dmsnap[c->dm_cur];         // p plane: the domain table as this step's forward pass saw it
+    fa.pdm = c->pdm;
+    fa.wT = (P.need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
+    fa.optimizer = optimizer;
+    fa.alpha = alpha;
+    fa.omb1 = P.omb1;
+    fa.omb2 = P.omb2;
+    fa.eps = c->cfg.adam_eps;
+    fa.two_l2 = 2.0f * c->cfg.l2_emb;
+    fa.loss_part = c->loss_part;
+    fa.n_loss_tiles = use4 ? rows_pad / 4 : rows_pad / TILE_ROWS;
+    fa.frozen_sumsq = c->frozen_sumsq;
+    fa.l2_emb = c->cfg.l2_emb;
+    fa.loss_out = P.loss_out ? P.loss_out + s : nullptr;
+#ifdef MAMDR_STAMPS
+    fa.stamps = c->stamps ? c->stamps + 65536 + (c->global_step & 1) * 4096 : nullptr;
+#endif
+    {
+        Prof p(c, MAMDR_KERNEL_WGRAD);
+        launch_wgrad_adam(fa, c->stream);
+    }
+    // the domain table's step stays pending: the next step's tower kernel applies it, the last one of the call is
+    // materialised below
+    dm_pending.snap = c->dmsnap[c->dm_cur];
+    dm_pending.pdm = c->pdm;
+    dm_pending.n_part = DM_PARTS;
+    dm_pending.n_domain = c->cfg.n_domain;
+    dm_pending.optimizer = optimizer;
+    dm_pending.alpha = alpha;
+    dm_pending.omb1 = P.omb1;
+    dm_pending.omb2 = P.omb2;
+    dm_pending.eps = c->cfg.adam_eps;
+    dm_pending.two_l2 = 2.0f * c->cfg.l2_emb;
+    // (an Adam call leaves its last step pending for the next call's first tower / the next sync_tables)
+    if (c->dm_finish_each || (s + 1 == P.n_steps && (optimizer != MAMDR_OPT_ADAM || c->dm_finish_call))) finish_dm(c);
+    c->global_step += 1;
+    return MAMDR_OK;
+}
+
+// ---- slab path: tower, k_wgrad (row groups -> gradient slabs), k_update (sums the slabs in order, optimiser step)
+static int slab_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
+    const SplitData& d = *P.d;
+    const int32_t optimizer = P.optimizer;
+    const float omb1 = P.omb1, omb2 = P.omb2;
+    const int64_t row_base = (P.first_step + s) * P.batch;
+    const int rows = rows_at(P.pass_rows, row_base, P.batch);
+    const int rows_pad = (int)pad_rows(rows);
+    const bool use4 = takes_tower4(c, rows_pad);
+    if (c->cfg.emb_trainable && c->lazy && optimizer == MAMDR_OPT_ADAM)
+        emb_pre_step(c, d, P.perm, row_base, rows, rows_pad, alpha, omb1, omb2);
+    TowerArgs ta;
+    fill_step_tower(c, P, row_base, rows, ta);
+    if (int rc = run_step_tower(c, ta, use4, s)) return rc;
+
+    if (c->cfg.emb_trainable && P.loss_out) {
+        prof_break(c);
+        // the regulariser of the reported loss needs the current tables' sums of squares
+        launch_sumsq(c->params, (int64_t)c->cfg.n_user * EMB, c->sumsq_partials, c->frozen_sumsq + 0, c->stream);
+        launch_sumsq(c->params + (size_t)c->cfg.n_user * EMB, (int64_t)c->cfg.n_item * EMB, c->sumsq_partials,
+                     c->frozen_sumsq + 1, c->stream);
+        if (c->deepfm) {
+            launch_sumsq(c->params + c->lin_user_off, c->cfg.n_user, c->sumsq_partials, c->frozen_sumsq + 2, c->stream);
+            launch_sumsq(c->params + c->lin_item_off, c->cfg.n_item, c->sumsq_partials, c->frozen_sumsq + 3, c->stream);
+        }
+    }
+    WgradArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.acts = c->acts;
+    wa.dz = c->dz;
+    wa.dlogit = c->dlogit;
+    wa.domrow = c->domrow;
+    wa.fmq = c->fmq;
+    wa.ipbuf = c->ipbuf;
+    wa.ld_off = c->L.ld;
+    wa.ld_count = c->L.ld_count;
+    wa.l2_lin = c->cfg.l2_linear;
+    wa.lv_off = c->L.lv;
+    wa.lv_count = c->L.lv_count;
+    wa.uw_d = P.domain;
+    wa.tiles = c->tiles;
+    wa.n_tiles = c->n_tiles;
+    wa.rows_pad = rows_pad;
+    int rpg = 0;
+    const int groups = wgrad_groups(rows_pad, &rpg);
+    wa.n_groups = groups;
+    wa.rows_per_group = rpg;
+    wa.slabs = c->slabs;
+    wa.slab_ld = c->slab_ld;
+    wa.w0dom = c->params + c->table_floats + c->L.w0 + (size_t)(2 * EMB) * H1;
+    wa.w0dom_copy = c->w0dom_copy;
+    wa.dm_copy = c->lin_w0dom ? c->dm_copy : nullptr;
+    wa.loss_part = c->loss_part;
+    wa.n_loss_tiles = use4 ? rows_pad / 4 : rows_pad / TILE_ROWS;
+    wa.rows = rows;
+    wa.dense = c->params + c->table_floats;
+    wa.dm_count = c->cfg.n_domain * EMB;
+    wa.l2_emb = c->cfg.l2_emb;
+    wa.frozen_sumsq = c->frozen_sumsq;
+    wa.loss_out = P.loss_out ? P.loss_out + s : nullptr;
+#ifdef MAMDR_STAMPS
+    wa.stamps = c->stamps ? c->stamps + 65536 : nullptr;
+#endif
+    // lazy table Adam: k_emb_reduce (and DeepFM's k_lin_sweep) only need the tower's outputs and write state no dense
+    // kernel touches -> they ride in k_wgrad's / k_update's launches
+    EmbStepArgs tea, nea;
+    EmbRowsArgs nr;
+    const bool next = P.tail && s + 1 < P.n_steps;
+    if (P.tail) {
+        fill_emb_args(c, optimizer, alpha, omb1, omb2, table_two_l2(c), rows, 2 * EMB, tea);
+        tea.flags_done = 1;
+        tea.apply_now = 1;
+    }
+    if (next) fill_next_step(c, P, row_base + P.batch, nr, nea);
+    // frozen tables, another step of this call follows on the 16-row tower: its gather is touched by riders in k_wgrad's
+    // launch (GatherPf, mamdr_kernels.h; round 5: in k_update's launch, bound by what it pulls over the fabric, it lost 0.42 us
+    // without them, k_wgrad gains 0.13 -- profiles/r05_ab_riders_place.txt)
+    GatherPf pf;
+    memset(&pf, 0, sizeof(pf));
+    if (!P.tail && !c->cfg.emb_trainable && s + 1 < P.n_steps) {
+        const int64_t nb = row_base + P.batch;
+        const int nrows = rows_at(P.pass_rows, nb, P.batch);
+        const int npad = (int)pad_rows(nrows);
+        if (nrows > 0 && !takes_tower4(c, npad)) {
+            pf.perm = P.perm;
+            pf.uid = d.uid;
+            pf.pid = d.pid;
+            pf.dom = d.dom;
+            pf.label = d.label;
+            pf.user_tab = c->user_tab;
+            pf.item_tab = c->item_tab;
+            pf.row_base = nb;
+            pf.n_rows_split = d.n;
+            pf.rows = nrows;
+            pf.n_user = c->cfg.n_user;
+            pf.n_item = c->cfg.n_item;
+            pf.n_tiles = npad / TILE_ROWS;
+            pf.sink = c->loss_part;
+        }
+    }
+    {
+        Prof p(c, MAMDR_KERNEL_WGRAD);
+        if (P.tail) launch_wgrad_reduce(wa, tea, next ? &nr : nullptr, nullptr, c->stream);
+        else launch_wgrad(wa, c->stream, &pf);
+    }
+
+    UpdateArgs ua;
+    memset(&ua, 0, sizeof(ua));
+    ua.p = c->params + c->table_floats;
+    ua.m = (optimizer == MAMDR_OPT_ACCUMULATE ? c->accum : c->adam_m) + c->table_floats;
+    ua.v = c->adam_v + c->table_floats;
+    ua.slabs = c->slabs;
+    ua.n_groups = groups;
+#ifdef MAMDR_STAMPS
+    ua.stamps = c->stamps ? c->stamps + 65536 + 8192 : nullptr;
+#endif
+    ua.slab_ld = c->slab_ld;
+    ua.s_off = c->L.alloc;
+    ua.w0dom_copy = c->w0dom_copy;
+    ua.dm_copy = c->lin_w0dom ? c->dm_copy : nullptr;
+    ua.n_domain = c->cfg.n_domain;
+    ua.count4 = c->L.alloc / 4;
+    ua.dm_count = c->cfg.n_domain * EMB;
+    ua.two_l2 = 2.0f * c->cfg.l2_emb;
+    ua.s2_off = c->s2_off;
+    ua.ld_off = c->L.ld;
+    ua.ld_count = c->L.ld_count;
+    ua.two_l2_lin = 2.0f * c->cfg.l2_linear;
+    ua.optimizer = optimizer;
+    ua.alpha = alpha;
+    ua.omb1 = omb1;
+    ua.omb2 = omb2;
+    ua.eps = c->cfg.adam_eps;
+    ua.wT = (P.need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
+    ua.w1_off = c->L.w1;
+    ua.w2_off = c->L.w2;
+    ua.w0_off = c->L.w0;
+    ua.w0t = (c->cfg.emb_trainable && !c->nfm) ? 1 : 0;
+    ua.no_sdm = c->nfm ? 1 : 0;
+    {
+        Prof p(c, MAMDR_KERNEL_UPDATE);
+        if (P.tail) launch_update_lin(ua, tea, c->deepfm, next ? &nea : nullptr, c->stream);
+        else launch_update(ua, c->stream);
+    }
+    if (next) take_next_rows(c);
+    if (c->cfg.emb_trainable && !P.tail) emb_post_step(c, optimizer, alpha, omb1, omb2, rows);
+    c->global_step += 1;
     return MAMDR_OK;
 }
 
@@ -822,7 +1234,7 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
     // dW0[256:384] without tiles: Dm^T . S in k_update, or (Star: one normalised domain row per batch) the
     // rank-1 form in k_star_update
     // (NFM: rows 256..383 of the input tile carry the bi-interaction, not the domain row: plain tiles)
-    c->lin_w0dom = (c->star || cfg->n_domain <= 64) && !getenv("MAMDR_NO_W0LIN") && !c->nfm;
+    c->lin_w0dom = (c->star || cfg->n_domain <= 64) && !c->nfm;
     std::vector<TileDesc> tiles = build_tiles(c->L, cfg->n_domain, c->deepfm, c->s2_off, c->lin_w0dom, c->star, c->pnn, c->nfm);
     c->n_tiles = (int)tiles.size();
     float thr[500];
@@ -921,24 +1333,14 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
         }
     }
     if (const char* ev = getenv("MAMDR_NO_TAILFUSE")) c->tail_fuse = atoi(ev) == 0;
-    if (const char* ev = getenv("MAMDR_STAR_PNB_KERNEL")) c->star_pn_in_tower = atoi(ev) == 0;
-    if (const char* ev = getenv("MAMDR_STAR_PNB_FUSED")) c->star_pn_fused = atoi(ev) != 0 && c->star_pn_in_tower;
-    if (const char* ev = getenv("MAMDR_STAR_PNB_APPLY")) c->star_pn_no_apply = atoi(ev) == 0;
-    if (const char* ev = getenv("MAMDR_MAX_GROUPS")) c->max_groups = atoi(ev) > 0 ? atoi(ev) : c->max_groups;   // diagnostic
-    if (const char* ev = getenv("MAMDR_RPG")) c->rpg_override = atoi(ev) / 8 * 8;
-    if (const char* ev = getenv("MAMDR_NO_GATHER_PF")) c->gather_pf = atoi(ev) == 0;
-    if (const char* ev = getenv("MAMDR_FUSED_PF")) c->fused_pf = atoi(ev) != 0;
-    if (const char* ev = getenv("MAMDR_WGRAD_PAIRS")) c->wgrad_pairs = atoi(ev) != 0;
-    if (const char* ev = getenv("MAMDR_GATHER_PF_IN")) c->gather_pf_in_wgrad = strcmp(ev, "update") != 0;
-    ALLOC(c->slabs, (size_t)c->max_groups * c->slab_ld * sizeof(float));
+    ALLOC(c->slabs, (size_t)WGRAD_MAX_GROUPS * c->slab_ld * sizeof(float));
     ALLOC(c->tiles, tiles.size() * sizeof(TileDesc));
     ALLOC(c->thresholds, sizeof(thr));
     ALLOC(c->frozen_sumsq, 4 * sizeof(float));
     ALLOC(c->sumsq_partials, 1024 * sizeof(float));
 #undef ALLOC
-    hipError_t e = hipMemsetAsync(c->slabs, 0, (size_t)c->max_groups * c->slab_ld * sizeof(float), c->stream);
+    hipError_t e = hipMemsetAsync(c->slabs, 0, (size_t)WGRAD_MAX_GROUPS * c->slab_ld * sizeof(float), c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(c->frozen_sumsq, 0, 4 * sizeof(float), c->stream);
-    if (const char* ev = getenv("MAMDR_RPG")) c->rpg_override = atoi(ev) / 8 * 8;
     if (cfg->emb_trainable) {
         if (e == hipSuccess) e = hipMemsetAsync(c->hasdup_u, 0, rp * sizeof(int32_t), c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(c->hasdup_i, 0, rp * sizeof(int32_t), c->stream);
@@ -1216,8 +1618,7 @@ int mamdr_pregather_passes(mamdr_ctx* c, int32_t n_passes, const int32_t* h_doma
     c->pg.clear();
     c->pg_pos = 0;
     // a hint: it only has an effect where a call would gather its pass itself (frozen tables, k_wgrad_adam path)
-    if (n_passes == 0 || batch <= 0 || batch > c->cfg.max_batch || !c->use_pre ||
-        !(c->fused && (batch + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS <= c->fused_max_batch))
+    if (n_passes == 0 || batch <= 0 || batch > c->cfg.max_batch || !c->use_pre || !takes_fused_path(c, batch))
         return MAMDR_OK;
     if (n_passes > PREP_MAX_PASSES) n_passes = PREP_MAX_PASSES;      // the later ones gather themselves
     PassPrepMultiArgs a;
@@ -1304,77 +1705,24 @@ int mamdr_train_steps_n(mamdr_ctx* c, int domain, const int32_t* d_perm, int64_t
     const uint32_t drop_thresh = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)(int64_t)thr;
     const float keep_scale = (float)(1.0 / (1.0 - (double)rate));
     const float omb1 = 1.0f - c->cfg.adam_beta1, omb2 = 1.0f - c->cfg.adam_beta2;
+    // the meta pass runs with the Keras learning phase at its default (0): dropout off
+    const int use_dropout = (rate > 0.f && optimizer != MAMDR_OPT_ACCUMULATE) ? 1 : 0;
+    CallPlan P{d, domain, d_perm, pass_rows, first_step, n_steps, batch, optimizer, lr, omb1, omb2, d_loss_out,
+               dropout_seed, drop_thresh, keep_scale, use_dropout};
     // SGD / accumulate steps update the tables densely: bring every lagging row up to date first
     if (optimizer != MAMDR_OPT_ADAM) sync_tables(c);
-
-    // small batches run the 4-row-tile tower (all CUs busy); it needs transposed W1 / W2 copies:
-    // refreshed here because the caller may have assigned new weights, kept current by k_update
-    const bool may_use4 = !c->star && c->tower_tile != 16;
-    // ... only when a step of THIS call is small enough for that tower (the rows of a pass's steps never grow: the
-    // last one is the smallest) -- a 4,096-row call over a domain without a short last batch needs no copies at all
-    bool need_wT = false;
-    if (may_use4 && n_steps > 0) {
-        const int64_t last_base = (first_step + n_steps - 1) * (int64_t)batch;
-        const int64_t last_rows = std::min<int64_t>(batch, pass_rows - last_base);
-        const int64_t last_pad = (last_rows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
-        need_wT = c->tower_tile == 4 || last_pad <= c->tower4_max_rows;
-    }
+    plan_call(c, P);
 
     c->rows_ready = false;
     c->catchup_ready = false;
     prof_break(c);
-    // one path per call (the pending domain-table step lives across the steps of a call): k_wgrad_adam for batches up
-    // to fused_max_batch rows (measured: 27.3 vs 29.5 us / step at 1,024 rows, a tie at 4,096)
-    const bool fused = c->fused && (batch + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS <= c->fused_max_batch;
     // k_wgrad_adam path: the domain table's step of the previous step -- of this call or, between two Adam calls, of
     // the previous call (c->dm_pending); every other kind of call starts from the materialised table
-    DmStep& dm_pending = c->dm_pending;
-    if (!(fused && optimizer == MAMDR_OPT_ADAM)) finish_dm(c);
-    // ... and on that path the rows of the whole call are resolved and gathered once (frozen tables; 4-row tower)
-    const int64_t pre_pos0 = first_step * batch;
-    const int64_t pre_n = std::min<int64_t>((first_step + n_steps) * (int64_t)batch, pass_rows) - pre_pos0;
-    const bool pre = fused && c->use_pre && n_steps > 0 && pre_n > 0;
-    // the transposed copies: built here unless the previous call's steps left them current (no sync_tables since).  On
-    // the k_wgrad_adam path with the W1 image (k_tower4<.., W1L, PRE>) only W2T is read, and only the call's FIRST tower
-    // can find it stale -- k_wgrad_adam rewrites every copy with the step -- so that tower reads W2 itself (w2_direct:
-    // 32 B runs of 128 rows, four loads per lane) and nothing is transposed at all
-    bool build_wT = need_wT && !c->wT_valid;
-    bool w2_direct = false;
-    if (build_wT && pre && c->w2_direct_ok && optimizer != MAMDR_OPT_ACCUMULATE && !c->t4_no_w1l && c->tower_tile != 16 &&
-        tower4_w1l_ready() &&
-        tower4_takes_w1l(std::min<int64_t>(batch, pass_rows - first_step * (int64_t)batch), c->t4_no_w1l)) {
-        build_wT = false;
-        w2_direct = true;
-    }
-    // ... unless mamdr_pregather_passes gathered this pass ahead of the call: entries are consumed in order (an entry
-    // stays current while calls keep working on its pass); a call that matches none drops them all
-    int64_t pre_base = 0;              // position of row pre_pos0 inside the pass buffer
-    bool pre_cached = false;
-    // ... and a call whose FIRST step runs the 16-row tower (which reads no copy) needs none built either: k_update
-    // rewrites the copy of every element it steps, so they are current from the call's second step on -- before the
-    // short last batch that runs the four-row tower (the rows of a pass's steps never grow)
-    if (build_wT && optimizer != MAMDR_OPT_ACCUMULATE && !fused && !c->star) {
-        const int64_t first_rows = std::min<int64_t>(batch, pass_rows - first_step * (int64_t)batch);
-        const int64_t first_pad = (first_rows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
-        if (!(c->tower_tile == 4 || first_pad <= c->tower4_max_rows) && n_steps > 1) build_wT = false;
-    }
-    if (pre) {
-        for (size_t k = c->pg_pos; k < c->pg.size(); ++k) {
-            const mamdr_ctx::PgEntry& e = c->pg[k];
-            if (e.domain == domain && e.perm == d_perm && e.n == pass_rows && e.batch == batch) {
-                c->pg_pos = k;
-                pre_base = e.off + pre_pos0;
-                pre_cached = true;
-                c->pg_hits += 1;
-                break;
-            }
-        }
-        if (!pre_cached) c->pg.clear();
-    }
-    if (pre && pre_cached) {
-        if (build_wT) launch_transpose_w(c->params + c->table_floats, c->L, c->wT, c->stream);
-    } else if (pre) {
-        if (int rc = grow_pass_buffer(c, pre_n + 16)) return rc;
+    if (!(P.path == StepPath::fused && optimizer == MAMDR_OPT_ADAM)) finish_dm(c);
+    if (P.pre && P.pre_cached) {
+        if (P.build_wT) launch_transpose_w(c->params + c->table_floats, c->L, c->wT, c->stream);
+    } else if (P.pre) {
+        if (int rc = grow_pass_buffer(c, P.pre_n + 16)) return rc;
         PassPrepArgs pa;
         memset(&pa, 0, sizeof(pa));
         pa.user_tab = c->user_tab;
@@ -1384,8 +1732,8 @@ int mamdr_train_steps_n(mamdr_ctx* c, int domain, const int32_t* d_perm, int64_t
         pa.dom = d->dom;
         pa.label = d->label;
         pa.perm = d_perm;
-        pa.pos0 = pre_pos0;
-        pa.n = pre_n;
+        pa.pos0 = P.pre_pos0;
+        pa.n = P.pre_n;
         pa.n_rows_split = d->n;
         pa.n_user = c->cfg.n_user;
         pa.n_item = c->cfg.n_item;
@@ -1394,413 +1742,29 @@ int mamdr_train_steps_n(mamdr_ctx* c, int domain, const int32_t* d_perm, int64_t
         pa.xpre = c->xpre;
         pa.pdom = c->pdom;
         pa.plabel = c->plabel;
-        if (build_wT) {                // ... in k_pass_prep's launch (one launch less per call)
+        if (P.build_wT) {                // ... in k_pass_prep's launch (one launch less per call)
             pa.tw_dense = c->params + c->table_floats;
             pa.tw_L = c->L;
             pa.tw_wT = c->wT;
         }
         Prof p(c, MAMDR_KERNEL_AUX);
         launch_pass_prep(pa, c->stream);
-    } else if (build_wT) {
+    } else if (P.build_wT) {
         launch_transpose_w(c->params + c->table_floats, c->L, c->wT, c->stream);
     }
     // (what the call's steps leave behind: k_wgrad_adam / k_update keep the copies of what they step current when the
     // call uses them; steps without them make them stale; accumulate steps change no weight)
-    if (optimizer != MAMDR_OPT_ACCUMULATE) c->wT_valid = need_wT;
-    else if (build_wT) c->wT_valid = true;
-    // Star tower: a batch carries one domain, so D - 1 of the D slices of every per-domain tensor see a zero gradient
-    // and only decay -- TF1's dense Adam still moves them every step (star_kernels.hip).  Inside a call those steps are
-    // postponed: k_star_update covers the live slice only and logs the step's alpha, k_star_catchup replays the
-    // skipped steps when the call ends (the same arithmetic in the same order: bit-identical; one sweep of the 13
-    // slices per call instead of one per step).  Calls of a single step gain nothing and sweep as before.
-    const bool star_lazy = c->star && optimizer == MAMDR_OPT_ADAM && n_steps >= 2 && !d_loss_out && !c->star_dense_slices &&
-                           c->cfg.n_domain > 1;
-    int64_t star_lag = 0;
+    if (optimizer != MAMDR_OPT_ACCUMULATE) c->wT_valid = P.need_wT;
+    else if (P.build_wT) c->wT_valid = true;
     for (int64_t s = 0; s < n_steps; ++s) {
-        const int64_t row_base = (first_step + s) * batch;
-        const int rows = (int)((pass_rows - row_base) < batch ? (pass_rows - row_base) : batch);
-        const int rows_pad = (rows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
         // the reported loss carries l2 * sum(table^2) over EVERY row: bring lagging rows up to date first
         // (only callers that ask for the per-step loss pay this flush; the meta loops do not)
         if (d_loss_out) sync_tables(c);
-        float step_alpha = lr;
-        if (optimizer == MAMDR_OPT_ADAM) {
-            c->adam_t += 1;
-            c->b1p = c->b1p * c->cfg.adam_beta1;
-            c->b2p = c->b2p * c->cfg.adam_beta2;
-            step_alpha = lr * sqrtf(1.0f - c->b2p) / (1.0f - c->b1p);
-        }
-        if (c->star) {
-            // the next step of this call (lazy Adam, launches fused): its rows are resolved in this step's last launch
-            EmbRowsArgs nr;
-            const bool pre = s + 1 < n_steps && c->tail_fuse && c->cfg.emb_trainable && c->lazy &&
-                             optimizer == MAMDR_OPT_ADAM && !c->profile && !d_loss_out;
-            if (pre) {
-                const int64_t nb = (first_step + s + 1) * batch;
-                const int nrows = (int)((pass_rows - nb) < batch ? (pass_rows - nb) : batch);
-                const float b1n = c->b1p * c->cfg.adam_beta1, b2n = c->b2p * c->cfg.adam_beta2;
-                fill_rows_args(c, *d, d_perm, nb, nrows, (nrows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS,
-                               lr * sqrtf(1.0f - b2n) / (1.0f - b1n), c->adam_t + 1, true, nr);
-            }
-            EmbStepArgs nea;
-            if (pre) {
-                fill_emb_args(c, MAMDR_OPT_ADAM, nr.alpha, omb1, omb2, table_two_l2(c), nr.rows, XDIM, nea);
-                nea.t_now = (int)c->adam_t + 1;
-                nea.t[0].brow = c->urow_alt;
-                nea.t[0].map = c->map_u_alt;
-                nea.t[1].brow = c->irow_alt;
-                nea.t[1].map = c->map_i_alt;
-            }
-            const int rc = star_train_step(c, *d, domain, d_perm, row_base, rows, optimizer, step_alpha, omb1, omb2,
-                                           d_loss_out ? d_loss_out + s : nullptr, pre ? &nr : nullptr, pre ? &nea : nullptr,
-                                           star_lazy ? (int)(star_lag & (STAR_ALPHA_CAP - 1)) : -1, star_lazy && s > 0,
-                                           star_lazy && s + 1 < n_steps);
-            if (rc) return rc;
-            c->global_step += 1;
-            if (star_lazy) {
-                star_lag += 1;
-                if (star_lag == STAR_ALPHA_CAP || s + 1 == n_steps) {       // the other slices catch up: log full / call over
-                    StarCatchArgs ca;
-                    memset(&ca, 0, sizeof(ca));
-                    ca.p = c->params + c->table_floats;
-                    ca.m = c->adam_m + c->table_floats;
-                    ca.v = c->adam_v + c->table_floats;
-                    ca.SL = c->SL;
-                    ca.n_domain = c->cfg.n_domain;
-                    ca.d_live = domain;
-                    ca.alpha_log = c->star_alpha;
-                    ca.first_idx = 0;
-                    ca.n_steps = (int)star_lag;
-                    ca.log_mask = STAR_ALPHA_CAP - 1;
-                    ca.omb1 = omb1;
-                    ca.omb2 = omb2;
-                    ca.eps = c->cfg.adam_eps;
-                    {
-                        Prof p(c, MAMDR_KERNEL_AUX);
-                        launch_star_catchup(ca, c->stream);
-                    }
-                    star_lag = 0;
-                }
-            }
-            continue;
-        }
-
-        if (c->cfg.emb_trainable && c->lazy && optimizer == MAMDR_OPT_ADAM)
-            emb_pre_step(c, *d, d_perm, row_base, rows, rows_pad, step_alpha, omb1, omb2);
-        TowerArgs ta;
-        fill_tower_common(c, *d, ta);
-        ta.perm = d_perm;
-        ta.row_base = row_base;
-        ta.rows = rows;
-        ta.batch = rows;
-        ta.seed = dropout_seed;
-        ta.step = c->global_step;
-        ta.drop_thresh = drop_thresh;
-        ta.keep_scale = keep_scale;
-        // the meta pass runs with the Keras learning phase at its default (0): dropout off
-        ta.use_dropout = (rate > 0.f && optimizer != MAMDR_OPT_ACCUMULATE) ? 1 : 0;
-        ta.acts = c->acts;
-        ta.dz = c->dz;
-        ta.dlogit = c->dlogit;
-        ta.domrow = c->domrow;
-        ta.dxe = c->dxe;
-        ta.dx_ld = 2 * EMB;
-        ta.urow = c->urow;
-        ta.irow = c->irow;
-        ta.map_u = c->map_u;
-        ta.map_i = c->map_i;
-        ta.loss_part = c->loss_part;
-        ta.fmq = c->fmq;
-        if (c->L.lv_count > 0) ta.uw_off = c->L.lv + domain;
-#ifdef MAMDR_STAMPS
-        ta.stamps = c->stamps ? c->stamps + (c->global_step & 1) * 16384 : nullptr;      // two steps side by side
-#endif
-        ta.wT = c->wT;
-        ta.no_w1l = c->t4_no_w1l;
-        float* const dense_m = (optimizer == MAMDR_OPT_ACCUMULATE ? c->accum : c->adam_m) + c->table_floats;
-        const bool use4 = may_use4 && (c->tower_tile == 4 || rows_pad <= c->tower4_max_rows);
-        if ((c->pnn || c->nfm) && !use4)
-            return fail(MAMDR_ENOTBUILT, "pnn / nfm tower: a training step of %d rows needs the four-row tower (MAMDR_TOWER_TILE=16?)", rows);
-        if (fused) {
-            ta.w0dom_snap = c->w0dom_copy;
-            c->dm_cur ^= 1;
-            ta.dms = dm_pending;                       // the previous step of this call (snap == null: none)
-            ta.dm_hint = domain;
-            if (pre) {
-                ta.xpre = c->xpre + (size_t)(pre_base + row_base - pre_pos0) * 2 * EMB;
-                ta.pdom = c->pdom + (pre_base + row_base - pre_pos0);
-                ta.plabel = c->plabel + (pre_base + row_base - pre_pos0);
-            }
-            ta.dm_live_p = c->params + c->table_floats + c->L.dm;
-            ta.dm_live_m = dense_m + c->L.dm;
-            ta.dm_live_v = c->adam_v + c->table_floats + c->L.dm;
-            ta.dm_snap_out = c->dmsnap[c->dm_cur];
-            ta.w2_direct = (w2_direct && s == 0) ? 1 : 0;
-        }
-        {
-            Prof p(c, MAMDR_KERNEL_FWD_BWD);
-#ifdef MAMDR_TOWER_TWICE
-            // diagnostic build (tools/stamp_tower.py with MAMDR_DIAG_FLAGS=-DMAMDR_TOWER_TWICE): the same tower launch twice in a
-            // row -- idempotent (the pending domain-table step is formed from its snapshot, every output is overwritten) -- so that
-            // the stamps of the SECOND launch show the kernel with its own code and data still where the first left them
-            if (use4) (void)launch_tower4_train(ta, c->stream);
-#endif
-            const int t4e = use4 ? launch_tower4_train(ta, c->stream) : (launch_tower_train(ta, c->stream), 0);
-            if (t4e == T4_E_W2D_LDS) return fail(MAMDR_EHIP, "k_tower4<W2D> was refused its LDS limit (hipFuncSetAttribute)");
-            if (t4e) return fail(MAMDR_ESTATE, "w2_direct without the W1-image instance of k_tower4 (step %lld of the call)", (long long)s);
-        }
-        if (fused) {
-            FusedArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.acts = c->acts;
-            fa.dz = c->dz;
-            fa.dlogit = c->dlogit;
-            fa.domrow = c->domrow;
-            fa.xa = ta.xpre ? ta.xpre : c->acts;
-            fa.xa_ld = ta.xpre ? 2 * EMB : ACT_LD;
-            fa.rows_pad = rows_pad;
-            fa.rows = rows;
-            fa.p = c->params + c->table_floats;
-            fa.m = dense_m;
-            fa.v = c->adam_v + c->table_floats;
-            fa.L = c->L;
-            fa.n_domain = c->cfg.n_domain;
-            fa.w0dom_snap = c->w0dom_copy;
-            fa.dm_snap = c->dmsnap[c->dm_cur];         // p plane: the domain table as this step's forward pass saw it
-            fa.pdm = c->pdm;
-            fa.wT = (need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
-            fa.optimizer = optimizer;
-            fa.alpha = step_alpha;
-            fa.omb1 = omb1;
-            fa.omb2 = omb2;
-            fa.eps = c->cfg.adam_eps;
-            fa.two_l2 = 2.0f * c->cfg.l2_emb;
-            fa.loss_part = c->loss_part;
-            fa.n_loss_tiles = use4 ? rows_pad / 4 : rows_pad / TILE_ROWS;
-            fa.frozen_sumsq = c->frozen_sumsq;
-            fa.l2_emb = c->cfg.l2_emb;
-            fa.loss_out = d_loss_out ? d_loss_out + s : nullptr;
-#ifdef MAMDR_STAMPS
-            fa.stamps = c->stamps ? c->stamps + 65536 + (c->global_step & 1) * 4096 : nullptr;
-#endif
-            // prefetch riders: the next tower launch's pre-gathered rows -- the next step of this call, or (last step) the
-            // first step of the pass the pregather hint says the next call will run
-            if (pre && c->fused_pf && ta.xpre) {
-                const int64_t here = pre_base + row_base - pre_pos0;         // this step's first row in the pass buffer
-                int64_t next_off = -1, next_rows = 0;
-                if (s + 1 < n_steps) {
-                    next_off = here + batch;
-                    next_rows = std::min<int64_t>(batch, pass_rows - (row_base + batch));
-                } else if (pre_cached && c->pg_pos + 1 < c->pg.size() && c->pg[c->pg_pos + 1].batch == batch) {
-                    const mamdr_ctx::PgEntry& e = c->pg[c->pg_pos + 1];
-                    next_off = e.off;
-                    next_rows = std::min<int64_t>(batch, e.n);
-                }
-                if (next_off >= 0 && next_rows > 0) {
-                    fa.pf_x = c->xpre + (size_t)next_off * 2 * EMB;
-                    fa.pf_dom = c->pdom + next_off;
-                    fa.pf_lab = c->plabel + next_off;
-                    fa.pf_tiles = (int)((next_rows + 3) / 4);
-                    fa.pf_sink = c->loss_part;
-                }
-            }
-            {
-                Prof p(c, MAMDR_KERNEL_WGRAD);
-                launch_wgrad_adam(fa, c->stream);
-            }
-            // the domain table's step stays pending: the next step's tower kernel applies it, the last one of the
-            // call is materialised below
-            dm_pending.snap = c->dmsnap[c->dm_cur];
-            dm_pending.pdm = c->pdm;
-            dm_pending.n_part = DM_PARTS;
-            dm_pending.n_domain = c->cfg.n_domain;
-            dm_pending.optimizer = optimizer;
-            dm_pending.alpha = step_alpha;
-            dm_pending.omb1 = omb1;
-            dm_pending.omb2 = omb2;
-            dm_pending.eps = c->cfg.adam_eps;
-            dm_pending.two_l2 = 2.0f * c->cfg.l2_emb;
-            // (an Adam call leaves its last step pending for the next call's first tower / the next sync_tables)
-            if (c->dm_finish_each || (s + 1 == n_steps && (optimizer != MAMDR_OPT_ADAM || c->dm_finish_call))) finish_dm(c);
-            c->global_step += 1;
-            continue;
-        }
-
-        if (c->cfg.emb_trainable && d_loss_out) {
-            prof_break(c);
-            // the regulariser of the reported loss needs the current tables' sums of squares
-            launch_sumsq(c->params, (int64_t)c->cfg.n_user * EMB, c->sumsq_partials, c->frozen_sumsq + 0, c->stream);
-            launch_sumsq(c->params + (size_t)c->cfg.n_user * EMB, (int64_t)c->cfg.n_item * EMB, c->sumsq_partials,
-                         c->frozen_sumsq + 1, c->stream);
-            if (c->deepfm) {
-                launch_sumsq(c->params + c->lin_user_off, c->cfg.n_user, c->sumsq_partials, c->frozen_sumsq + 2, c->stream);
-                launch_sumsq(c->params + c->lin_item_off, c->cfg.n_item, c->sumsq_partials, c->frozen_sumsq + 3, c->stream);
-            }
-        }
-        WgradArgs wa;
-        memset(&wa, 0, sizeof(wa));
-        wa.acts = c->acts;
-        wa.dz = c->dz;
-        wa.dlogit = c->dlogit;
-        wa.domrow = c->domrow;
-        wa.fmq = c->fmq;
-        wa.ipbuf = c->ipbuf;
-        wa.ld_off = c->L.ld;
-        wa.ld_count = c->L.ld_count;
-        wa.l2_lin = c->cfg.l2_linear;
-        wa.lv_off = c->L.lv;
-        wa.lv_count = c->L.lv_count;
-        wa.uw_d = domain;
-        wa.tiles = c->tiles;
-        wa.n_tiles = c->n_tiles;
-        wa.rows_pad = rows_pad;
-        // rows per K-split group (measured: 1024 rows, 8 groups of 128: 31.0 us/step vs 32.0 with 4 of 256;
-        // batches of <= 512 rows keep 256-row groups: one or two slabs)
-        int rpg = rows_pad <= 512 ? 256 : (rows_pad <= 1024 ? 128 : (rows_pad <= 4096 ? 256 : 512));
-        if (c->rpg_override > 0) rpg = c->rpg_override;        // MAMDR_RPG (diagnostic)
-        int groups = (rows_pad + rpg - 1) / rpg;
-        if (groups > c->max_groups) {
-            rpg = ((rows_pad + c->max_groups - 1) / c->max_groups + 7) / 8 * 8;
-            groups = (rows_pad + rpg - 1) / rpg;
-        }
-        wa.n_groups = groups;
-        wa.rows_per_group = rpg;
-        wa.slabs = c->slabs;
-        wa.slab_ld = c->slab_ld;
-        wa.w0dom = c->params + c->table_floats + c->L.w0 + (size_t)(2 * EMB) * H1;
-        wa.w0dom_copy = c->w0dom_copy;
-        wa.dm_copy = c->lin_w0dom ? c->dm_copy : nullptr;
-        wa.loss_part = c->loss_part;
-        wa.n_loss_tiles = use4 ? rows_pad / 4 : rows_pad / TILE_ROWS;
-        wa.rows = rows;
-        wa.dense = c->params + c->table_floats;
-        wa.dm_count = c->cfg.n_domain * EMB;
-        wa.l2_emb = c->cfg.l2_emb;
-        wa.frozen_sumsq = c->frozen_sumsq;
-        wa.loss_out = d_loss_out ? d_loss_out + s : nullptr;
-#ifdef MAMDR_STAMPS
-        wa.stamps = c->stamps ? c->stamps + 65536 : nullptr;
-#endif
-        // lazy table Adam: k_emb_reduce (and DeepFM's k_lin_sweep) only need the tower's outputs and write state
-        // no dense kernel touches -> they ride in k_wgrad's / k_update's launches (profiling runs keep them apart
-        // for per-kernel times; a reported loss reads the tables between the two and keeps them apart too)
-        const bool tail = c->tail_fuse && c->cfg.emb_trainable && c->lazy && optimizer == MAMDR_OPT_ADAM && !d_loss_out &&
-                          !c->profile;
-        EmbStepArgs tea, nea;
-        EmbRowsArgs nr;
-        // the next step of this call is known: its row ids / maps are resolved in this step's k_wgrad launch (into
-        // the alternate buffers) and its catch-up runs in this step's k_update launch
-        const bool pre = tail && s + 1 < n_steps;
-        if (tail) {
-            fill_emb_args(c, optimizer, step_alpha, omb1, omb2, table_two_l2(c), rows, 2 * EMB, tea);
-            tea.flags_done = 1;
-            tea.apply_now = 1;
-        }
-        if (pre) {
-            const int64_t nb = (first_step + s + 1) * batch;
-            const int nrows = (int)((pass_rows - nb) < batch ? (pass_rows - nb) : batch);
-            const float b1n = c->b1p * c->cfg.adam_beta1, b2n = c->b2p * c->cfg.adam_beta2;
-            const float alpha_n = lr * sqrtf(1.0f - b2n) / (1.0f - b1n);
-            fill_rows_args(c, *d, d_perm, nb, nrows, (nrows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS, alpha_n, c->adam_t + 1,
-                           true, nr);
-            fill_emb_args(c, MAMDR_OPT_ADAM, alpha_n, omb1, omb2, table_two_l2(c), nrows, 2 * EMB, nea);
-            nea.t_now = (int)c->adam_t + 1;
-            nea.t[0].brow = c->urow_alt;
-            nea.t[0].map = c->map_u_alt;
-            nea.t[1].brow = c->irow_alt;
-            nea.t[1].map = c->map_i_alt;
-        }
-        // frozen tables, another step of this call follows on the 16-row tower: its gather is touched by riders (GatherPf,
-        // mamdr_kernels.h) -- in k_wgrad's launch (default since round 5), or (MAMDR_GATHER_PF_IN=update) in k_update's
-        GatherPf pf;
-        memset(&pf, 0, sizeof(pf));
-        if (!tail && c->gather_pf && !c->cfg.emb_trainable && !c->star && s + 1 < n_steps) {
-            const int64_t nb = row_base + batch;
-            const int nrows = (int)std::min<int64_t>(batch, pass_rows - nb);
-            const int npad = (nrows + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
-            const bool next4 = may_use4 && (c->tower_tile == 4 || npad <= c->tower4_max_rows);
-            if (nrows > 0 && !next4) {
-                pf.perm = d_perm;
-                pf.uid = d->uid;
-                pf.pid = d->pid;
-                pf.dom = d->dom;
-                pf.label = d->label;
-                pf.user_tab = c->user_tab;
-                pf.item_tab = c->item_tab;
-                pf.row_base = nb;
-                pf.n_rows_split = d->n;
-                pf.rows = nrows;
-                pf.n_user = c->cfg.n_user;
-                pf.n_item = c->cfg.n_item;
-                pf.n_tiles = npad / TILE_ROWS;
-                pf.sink = c->loss_part;
-            }
-        }
-        bool paired = false;        // k_wgrad8: one slab per PAIR of row groups (MAMDR_WGRAD_PAIRS; steps of more than 8 groups)
-        {
-            Prof p(c, MAMDR_KERNEL_WGRAD);
-            if (tail) launch_wgrad_reduce(wa, tea, pre ? &nr : nullptr, nullptr, c->stream);
-            else {
-                if (c->wgrad_pairs && !c->star && !c->cfg.emb_trainable && groups > 8)
-                    paired = launch_wgrad_pairs(wa, c->stream, c->gather_pf_in_wgrad ? &pf : nullptr);
-                if (!paired) launch_wgrad(wa, c->stream, c->gather_pf_in_wgrad ? &pf : nullptr);
-            }
-        }
-
-        UpdateArgs ua;
-        memset(&ua, 0, sizeof(ua));
-        ua.p = c->params + c->table_floats;
-        ua.m = (optimizer == MAMDR_OPT_ACCUMULATE ? c->accum : c->adam_m) + c->table_floats;
-        ua.v = c->adam_v + c->table_floats;
-        ua.slabs = c->slabs;
-        ua.n_groups = paired ? (groups + 1) / 2 : groups;
-#ifdef MAMDR_STAMPS
-        ua.stamps = c->stamps ? c->stamps + 65536 + 8192 : nullptr;
-#endif
-        ua.slab_ld = c->slab_ld;
-        ua.s_off = c->L.alloc;
-        ua.w0dom_copy = c->w0dom_copy;
-        ua.dm_copy = c->lin_w0dom ? c->dm_copy : nullptr;
-        ua.n_domain = c->cfg.n_domain;
-        ua.count4 = c->L.alloc / 4;
-        ua.dm_count = c->cfg.n_domain * EMB;
-        ua.two_l2 = 2.0f * c->cfg.l2_emb;
-        ua.s2_off = c->s2_off;
-        ua.ld_off = c->L.ld;
-        ua.ld_count = c->L.ld_count;
-        ua.two_l2_lin = 2.0f * c->cfg.l2_linear;
-        ua.optimizer = optimizer;
-        ua.alpha = step_alpha;
-        ua.omb1 = omb1;
-        ua.omb2 = omb2;
-        ua.eps = c->cfg.adam_eps;
-        ua.wT = (need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
-        ua.w1_off = c->L.w1;
-        ua.w2_off = c->L.w2;
-        ua.w0_off = c->L.w0;
-        ua.w0t = (c->cfg.emb_trainable && !c->nfm) ? 1 : 0;
-        ua.no_sdm = c->nfm ? 1 : 0;
-        {
-            Prof p(c, MAMDR_KERNEL_UPDATE);
-            if (tail) {
-                launch_update_lin(ua, tea, c->deepfm, pre ? &nea : nullptr, c->stream);
-                if (pre) {
-                    std::swap(c->urow, c->urow_alt);
-                    std::swap(c->irow, c->irow_alt);
-                    std::swap(c->map_u, c->map_u_alt);
-                    std::swap(c->map_i, c->map_i_alt);
-                    c->rows_ready = true;
-                    c->catchup_ready = true;
-                    c->tables_dirty = true;
-                }
-            } else {
-                // frozen tables, another step of this call follows on the 16-row tower: its gather is touched by riders
-                // (GatherPf, mamdr_kernels.h)
-                launch_update(ua, c->stream, c->gather_pf_in_wgrad ? nullptr : &pf);
-            }
-        }
-        if (c->cfg.emb_trainable && !tail) emb_post_step(c, optimizer, ua.alpha, omb1, omb2, rows);
-        c->global_step += 1;
+        const float alpha = advance_step(c, optimizer, lr);
+        const int rc = P.path == StepPath::star    ? star_step(c, P, s, alpha)
+                       : P.path == StepPath::fused ? fused_step(c, P, s, alpha)
+                                                   : slab_step(c, P, s, alpha);
+        if (rc) return rc;
     }
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;
@@ -2091,10 +2055,7 @@ int mamdr_debug_set_stamps(mamdr_ctx* c, unsigned long long* d_stamps) {
 // ---- profiling
 int64_t mamdr_dropout_steps(const mamdr_ctx* c) { return c ? (int64_t)c->global_step : 0; }
 
-int mamdr_step_path(const mamdr_ctx* c, int32_t batch) {
-    if (!c || !c->fused) return 0;
-    return (batch + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS <= c->fused_max_batch ? 1 : 0;
-}
+int mamdr_step_path(const mamdr_ctx* c, int32_t batch) { return c && takes_fused_path(c, batch) ? 1 : 0; }
 
 int mamdr_set_tower_tile(mamdr_ctx* c, int32_t rows) {
     if (check_ctx(c)) return MAMDR_EINVAL;
@@ -2108,9 +2069,7 @@ int mamdr_set_tower_tile(mamdr_ctx* c, int32_t rows) {
 }
 int mamdr_tower_tile(const mamdr_ctx* c, int32_t batch) {
     if (!c || batch <= 0) return MAMDR_EINVAL;
-    const int64_t pad = ((int64_t)batch + TILE_ROWS - 1) / TILE_ROWS * TILE_ROWS;
-    const bool may_use4 = !c->star && c->tower_tile != 16;
-    return may_use4 && (c->tower_tile == 4 || pad <= c->tower4_max_rows) ? 4 : 16;
+    return takes_tower4(c, pad_rows(batch)) ? 4 : 16;
 }
 int mamdr_profile_enable(mamdr_ctx* c, int32_t enable) {
     if (check_ctx(c)) return MAMDR_EINVAL;

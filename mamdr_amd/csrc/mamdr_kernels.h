@@ -131,7 +131,7 @@ struct TowerArgs {
     int dx_ld;                 // 256, or 384 for the Star tower
     const float* pn_aff;       // Star: [scale 384 | shift 384 | mean 384 | inv 384 | ...] of PartitionedNorm, null otherwise
     float* pn_part;            // Star training: [tiles][2][384] per-tile sums of PartitionedNorm's backward (s1 = sum dxn,
-                               // s2 = sum dxn * xhat), written by the tower's tail -- k_star_pnb_partial's work without its launch
+                               // s2 = sum dxn * xhat), written by the tower's tail and summed by k_star_pnb_final
     int32_t* urow;             // [rows_pad] user row of each batch position (-1 = padding)
     int32_t* irow;             // [rows_pad]
     int32_t* map_u;            // [n_user] / [n_item]: atomicMin of the batch position touching the row (null: frozen tables)
@@ -495,15 +495,6 @@ struct FusedArgs {
     const float* frozen_sumsq;
     float l2_emb;
     float* loss_out;
-    // rider workgroups (round 5): the NEXT tower launch's pre-gathered rows, touched ahead of time from the XCD whose
-    // workgroup will read them (workgroup b of a 1-d grid runs on XCD b mod 8; what a kernel leaves in an XCD's L2
-    // survives the kernel boundary: 240 cycles instead of 1,400 cold -- see GatherPf).  The tower's prologue waits
-    // 5.3 K cycles for its first data (profiles/r05_stamps_tower4_taobao10_bs1024.txt); pf_tiles = 0: no rider
-    const float* pf_x;         // next step's rows in the pass buffer [pf_rows][2 EMB]
-    const int32_t* pf_dom;
-    const float* pf_lab;
-    int pf_tiles;              // four-row tiles of the next step
-    float* pf_sink;
 #ifdef MAMDR_STAMPS
     unsigned long long* stamps; // diagnostic build only: [workgroups][8] s_memtime stamps of wave 0
 #endif
@@ -625,8 +616,7 @@ struct EvalFinishArgs {
 void launch_eval_finish(const EvalFinishArgs& a, hipStream_t s);
 struct GatherPf;
 void launch_wgrad(const WgradArgs& a, hipStream_t s, const GatherPf* pf = nullptr);
-bool launch_wgrad_pairs(const WgradArgs& a, hipStream_t s, const GatherPf* pf);      // false: the 96 KB of LDS were refused
-// the NEXT step's gather, touched ahead of time by rider workgroups in k_update's launch.  What one kernel leaves in an
+// the NEXT step's gather, touched ahead of time by rider workgroups in k_wgrad's launch.  What one kernel leaves in an
 // XCD's L2 survives the kernel boundary (tools/probes/l2_survive_probe.hip: 240 cycles for a line the same workgroup id
 // touched in the kernel before, 1,400 cold, 600 when another XCD touched it), and workgroup b of any 1-d grid runs on XCD
 // b mod 8: rider b' = tile (mod 8) walks tile's dependent chain perm -> uid / pid / domain / label -> table rows, so the
@@ -639,7 +629,7 @@ struct GatherPf {
     int rows, n_user, n_item, n_tiles;     // n_tiles = 0: no rider
     float* sink;
 };
-void launch_update(const UpdateArgs& a, hipStream_t s, const GatherPf* pf = nullptr);
+void launch_update(const UpdateArgs& a, hipStream_t s);
 void launch_gather(const TowerArgs& a, float* out, hipStream_t s);
 void launch_sumsq(const float* x, int64_t n, float* partials /*>=1024 floats*/, float* out, hipStream_t s);
 
@@ -680,7 +670,7 @@ struct EmbStepArgs {
     // Star tower: dxe holds d loss / d NORMALISED input; PartitionedNorm's backward through the batch statistics,
     // dx = coef (( dxn - s1 / B) - xhat s2 / B), xhat = (x - mean) inv, is applied to every gathered gradient row on the
     // fly (x = the table row itself) -- k_star_pnb_apply's arithmetic without its pass over the batch.  null = dxe is d x
-    const float* pn_sums;      // [2][384] column sums s1, s2 over the batch (k_star_pnb_final); non-null = the switch
+    const float* pn_sums;      // [2][384] column sums s1, s2 over the batch (k_star_pnb_final); null: dxe is d x
     const float* pn_means;     // [2][384] s1 / B, s2 / B (k_star_pnb_final forms the quotients once: the same IEEE division
                                // every consumer did per element)
     const float* pn;           // PartitionedNorm workspace [scale | shift | mean | inv | coef | ...] x 384
@@ -743,8 +733,7 @@ struct StarPnBwdArgs {
     float* means;              // [2][384] s1 / B, s2 / B
     float* dmpart;             // [chunks][EMB] column sums of dx[:, 256:384]
     float* dmsum;              // [EMB] their total
-    int fused;                 // 1: k_star_pnb_final is the only launch (it also finishes dmsum; the table rows get their
-                               // d x inside k_emb_reduce); 0: k_star_pnb_apply rewrites dxe, k_star_dm_final sums dmpart;
+    int fused;                 // 0: k_star_pnb_apply rewrites dxe, k_star_dm_final sums dmpart;
                                // 2 (the default inside a call, round 6): k_star_pnb_final is the only launch, the table
                                // rows get their d x inside k_emb_reduce, the domain columns' partials are formed by
                                // star_pnb_dom_body in k_wgrad_reduce and summed + stepped by star_dm_step_body in
@@ -787,7 +776,7 @@ struct StarCatchArgs {
 void launch_star_catchup(const StarCatchArgs& a, hipStream_t s);
 void launch_star_stats(const TowerArgs& a, float* part, float* step_counter, hipStream_t s);
 void launch_star_prep(const StarPrepArgs& a, hipStream_t s);
-void launch_star_pn_bwd(const StarPnBwdArgs& a, bool dm_final, hipStream_t s, bool partial_done = false);
+void launch_star_pn_bwd(const StarPnBwdArgs& a, bool dm_final, hipStream_t s);
 void launch_star_update(const StarUpdateArgs& a, hipStream_t s);
 // k_star_update + the NEXT step's k_emb_catchup in one launch (lazy table Adam)
 void launch_star_update_catchup(const StarUpdateArgs& a, const EmbStepArgs& next_catchup, const StarPnBwdArgs* dm, hipStream_t s);

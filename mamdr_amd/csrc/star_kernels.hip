@@ -288,24 +288,6 @@ __device__ __forceinline__ void star_load_chunk(const StarPnBwdArgs& a, int r0, 
     for (int r = 0; r < STAR_CHUNK; ++r) k.xh[r] = (x[r] - mean) * inv;
 }
 
-__global__ __launch_bounds__(XDIM) void k_star_pnb_partial(const StarPnBwdArgs a) {
-    __shared__ int rowi[2 * STAR_CHUNK];
-    const int c = threadIdx.x, ch = blockIdx.x;
-    const int r0 = ch * STAR_CHUNK;
-    const int nb = min(STAR_CHUNK, a.rows - r0);
-    PnChunk k;
-    star_load_chunk(a, r0, nb, c, rowi, k);
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int r = 0; r < STAR_CHUNK; ++r) {
-        if (r < nb) {
-            s1 += k.g[r];
-            s2 += k.g[r] * k.xh[r];
-        }
-    }
-    a.part[(size_t)ch * 2 * XDIM + c] = s1;
-    a.part[(size_t)ch * 2 * XDIM + XDIM + c] = s2;
-}
 __global__ __launch_bounds__(512) void k_star_pnb_final(const StarPnBwdArgs a) {
     __shared__ float sh1[PN_LANES][PN_COLS], sh2[PN_LANES][PN_COLS];
     const int cl = threadIdx.x & (PN_COLS - 1), j = threadIdx.x / PN_COLS;
@@ -342,17 +324,6 @@ __global__ __launch_bounds__(512) void k_star_pnb_final(const StarPnBwdArgs a) {
         a.means[c] = s1 / B;
         a.means[XDIM + c] = s2 / B;
     }
-    // fused form (a.fused): nobody walks the batch again for d x.  The table rows get PartitionedNorm's backward
-    // inside k_emb_reduce (EmbStepArgs::pn_sums); the domain row's gradient is the column sum of
-    // dx = coef ((dxn - s1 / B) - xhat s2 / B) over the batch, and every sample of the batch carries the SAME domain row
-    // (one xhat), so the sum is available here in closed form.  In exact arithmetic it vanishes (the normalised input of
-    // a constant column is 0): what is left is rounding residue, as on the per-row path and as in the reference.
-    if (a.fused == 1 && c >= 2 * EMB) {
-        const float B = (float)a.rows;
-        const float m1 = s1 / B, m2 = s2 / B;
-        const float xh = (a.dm_row[c - 2 * EMB] - a.pn[2 * XDIM + c]) * a.pn[3 * XDIM + c];
-        a.dmsum[c - 2 * EMB] = a.pn[4 * XDIM + c] * ((s1 - B * m1) - xh * (B * m2));
-    }
 }
 __global__ __launch_bounds__(XDIM) void k_star_pnb_apply(const StarPnBwdArgs a) {
     __shared__ int rowi[2 * STAR_CHUNK];
@@ -381,9 +352,8 @@ __global__ __launch_bounds__(512) void k_star_dm_final(const StarPnBwdArgs a) {
     star_dm_final_body<DMF_COLS>(a, (int)blockIdx.x, sh);
 }
 // dm_final = false: the caller lets the domain-row column sums ride in its next launch (k_wgrad_reduce)
-// partial_done: the tower's tail already wrote the per-tile sums (TowerArgs::pn_part)
-void launch_star_pn_bwd(const StarPnBwdArgs& a, bool dm_final, hipStream_t s, bool partial_done) {
-    if (!partial_done) hipLaunchKernelGGL(k_star_pnb_partial, dim3(a.n_chunks), dim3(XDIM), 0, s, a);
+// (the per-tile sums are already there: the tower's tail wrote them, TowerArgs::pn_part)
+void launch_star_pn_bwd(const StarPnBwdArgs& a, bool dm_final, hipStream_t s) {
     if (a.fused) {      // the column sums are all that is left of PartitionedNorm's backward as a launch
         MAMDR_LAUNCH(k_star_pnb_final, dim3(PN_BLOCKS), dim3(512), 0, s, a);
         return;

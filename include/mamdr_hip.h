@@ -385,6 +385,8 @@ typedef struct mamdr_graph mamdr_graph;
 typedef struct mamdr_graph_config {
     int32_t abi_version;        /* MAMDR_ABI_VERSION */
     int32_t kind;               /* MAMDR_GRAPH_* */
+    /* emb_dim = model.user_dim == item_dim == domain_dim.  MAMDR_GRAPH_MLP / _WDL / _DEEPFM: 32, 64, 128 or 256; every other
+     * kind: 128 only (MAMDR_EINVAL otherwise, before any device call; mamdr_graph_last_error() names the accepted set) */
     int32_t n_user, n_item, n_domain, emb_dim, max_batch, emb_trainable;
     int32_t n_expert_hidden; int32_t expert_hidden[4];   /* model.hidden_dim: bottom / expert DNN (deep_mtl_ctr.py:26,33,44) */
     int32_t n_tower_hidden;  int32_t tower_hidden[4];    /* model.tower_hidden_dim (:27,34,43) */

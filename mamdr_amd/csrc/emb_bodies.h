@@ -49,10 +49,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // lazy mode: the representative wave of k_emb_reduce applies Adam step t_now to its row right away
 // (columns 2*lane, 2*lane+1 of row r; the row was brought to t_now - 1 by k_emb_catchup before the gather)
+// (E = the tables' row width: 128 wherever the step engine instantiates these bodies; the generic-layer engine also
+// runs them at 32 / 64 / 256 -- only WHICH element a lane owns depends on it, never the arithmetic on the element)
+template <int E = EMB>
 __device__ __forceinline__ void emb_apply_row(const EmbStepArgs& a, const EmbTable& T, bool second, int r, int lane,
                                               f32x2 gsum) {
 #pragma clang fp contract(off)
-    const size_t e = ((size_t)(second ? a.t[0].n_rows : 0) + r) * EMB + 2 * lane;
+    const size_t e = ((size_t)(second ? a.t[0].n_rows : 0) + r) * E + 2 * lane;
     f32x2 p = *reinterpret_cast<const f32x2*>(a.p + e);
     f32x2 m = *reinterpret_cast<const f32x2*>(a.m + e);
     f32x2 v = *reinterpret_cast<const f32x2*>(a.v + e);
@@ -73,10 +76,11 @@ __device__ __forceinline__ void emb_apply_row(const EmbStepArgs& a, const EmbTab
 }
 
 // the same step on columns 4*c4 .. 4*c4+3 (the no-duplicate path: half a wave per row)
+template <int E = EMB>
 __device__ __forceinline__ void emb_apply_row4(const EmbStepArgs& a, const EmbTable& T, bool second, int r, int c4,
                                                f32x4 gsum) {
 #pragma clang fp contract(off)
-    const size_t e = ((size_t)(second ? a.t[0].n_rows : 0) + r) * EMB + 4 * c4;
+    const size_t e = ((size_t)(second ? a.t[0].n_rows : 0) + r) * E + 4 * c4;
     f32x4 p = *reinterpret_cast<const f32x4*>(a.p + e);
     f32x4 m = *reinterpret_cast<const f32x4*>(a.m + e);
     f32x4 v = *reinterpret_cast<const f32x4*>(a.v + e);
@@ -134,13 +138,25 @@ constexpr int RED_STEP = 512;                  // positions per scan step (8 per
 constexpr int RED_CAP = 2 * RED_STEP;          // list entries per wave
 // (bx, table) = the workgroup's coordinates; list_all = [4 waves][RED_CAP] uint16 of LDS (positions fit 16 bits:
 // max_batch <= 16384).  A body, so that the kernel can also ride in another kernel's launch (k_wgrad_reduce).
+// Row width E (128 above): phase A gives a position E / 4 lanes x float4, so a wave serves EmbRed<E>::PPW = 256 / E
+// positions (8 / 4 / 2 / 1 at 32 / 64 / 128 / 256) and a workgroup 4 x as many; in phase B lane l owns columns 2l, 2l+1 of
+// every 128-column block of the row (lanes beyond E / 2 only scan at E < 128; two blocks per lane at E = 256).
+template <int E>
+struct EmbRed {
+    static constexpr int LPP = E / 4;           // lanes per position (phase A)
+    static constexpr int PPW = 64 / LPP;        // positions per wave
+    static constexpr int PPG = 4 * PPW;         // positions per 256-thread workgroup
+    static constexpr int NB = E > 128 ? E / 128 : 1;        // 128-column blocks per lane (phase B)
+};
+template <int E = EMB>
 __device__ __forceinline__ void emb_reduce_body(const EmbStepArgs& a, int bx, int table, uint16_t (*list_all)[RED_CAP]) {
 #pragma clang fp contract(off)
+    constexpr int LPP = EmbRed<E>::LPP, PPW = EmbRed<E>::PPW, PPG = EmbRed<E>::PPG, NB = EmbRed<E>::NB;
     const EmbTable& T = a.t[table];
     const bool second = table != 0;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int h = lane >> 5, c4 = lane & 31;
-    const int b = bx * 8 + w * 2 + h;  // this half-wave's position
+    const int h = lane / LPP, c4 = lane % LPP;
+    const int b = bx * PPG + w * PPW + h;  // this lane group's position
     int r = -1;
     bool dupf = false;
     if (b < a.rows) {
@@ -154,15 +170,15 @@ __device__ __forceinline__ void emb_reduce_body(const EmbStepArgs& a, int bx, in
     if (r >= 0 && !dupf) {
         f32x4 g4 = *reinterpret_cast<const f32x4*>(a.dxe + (size_t)b * a.dx_ld + T.dx_off + 4 * c4);
         if (a.pn_sums) {
-            const f32x4 x4 = *reinterpret_cast<const f32x4*>(a.p + ((size_t)(second ? a.t[0].n_rows : 0) + r) * EMB + 4 * c4);
+            const f32x4 x4 = *reinterpret_cast<const f32x4*>(a.p + ((size_t)(second ? a.t[0].n_rows : 0) + r) * E + 4 * c4);
 #pragma unroll
             for (int k = 0; k < 4; ++k) g4[k] = pn_fix1(a, T.dx_off + 4 * c4 + k, g4[k], x4[k]);
         }
         if (T.lin_p && c4 == 0) T.glin[b] = a.dlogit[b];
-        if (a.apply_now) emb_apply_row4(a, T, second, r, c4, g4);
-        else *reinterpret_cast<f32x4*>(T.gbuf + (size_t)b * EMB + 4 * c4) = g4;
+        if (a.apply_now) emb_apply_row4<E>(a, T, second, r, c4, g4);
+        else *reinterpret_cast<f32x4*>(T.gbuf + (size_t)b * E + 4 * c4) = g4;
     }
-    const unsigned long long dmask = __ballot(dupf);       // bits 0..31: position h = 0, bits 32..63: h = 1
+    const unsigned long long dmask = __ballot(dupf);       // bits [LPP h, LPP (h + 1)): position h of the wave
     if (dmask == 0ull) return;                              // wave-uniform
     // ---- phase B
     uint16_t* L = list_all[w];
@@ -170,15 +186,18 @@ __device__ __forceinline__ void emb_reduce_body(const EmbStepArgs& a, int bx, in
     const int rows8 = (a.rows + 7) / 8;                     // brow is allocated (and -1 padded) to a multiple of 16
     const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll 1
-    for (int s = 0; s < 2; ++s) {
-        if (((dmask >> (32 * s)) & 1ull) == 0ull) continue;            // wave-uniform
-        const int bs = bx * 8 + w * 2 + s;
-        const int rs = __shfl(r, 32 * s);
-        const float* gcol = a.dxe + T.dx_off + 2 * lane;
+    for (int s = 0; s < PPW; ++s) {
+        if (((dmask >> (LPP * s)) & 1ull) == 0ull) continue;            // wave-uniform
+        const int bs = bx * PPG + w * PPW + s;
+        const int rs = __shfl(r, LPP * s);
+        // lane l owns columns 2l, 2l+1 of every 128-column block; at E < 128 the lanes beyond E / 2 own none: they add up
+        // the row's first columns again (in bounds, no branch in the loops below) and store nothing
+        const bool owns = E >= 128 || 2 * lane < E;
+        const float* gcol = a.dxe + T.dx_off + (owns ? 2 * lane : 0);
         // Star: every position's gradient goes through PartitionedNorm's backward before it is added (the row's own
         // values: the same for all positions of the row)
         f32x2 xrow = (f32x2){0.f, 0.f};
-        if (a.pn_sums) xrow = *reinterpret_cast<const f32x2*>(a.p + ((size_t)(second ? a.t[0].n_rows : 0) + rs) * EMB + 2 * lane);
+        if (a.pn_sums) xrow = *reinterpret_cast<const f32x2*>(a.p + ((size_t)(second ? a.t[0].n_rows : 0) + rs) * E + 2 * lane);
         auto fix = [&](f32x2 gq) {
             if (a.pn_sums) {
                 gq[0] = pn_fix1(a, T.dx_off + 2 * lane, gq[0], xrow[0]);
@@ -186,7 +205,10 @@ __device__ __forceinline__ void emb_reduce_body(const EmbStepArgs& a, int bx, in
             }
             return gq;
         };
-        f32x2 acc = fix(*reinterpret_cast<const f32x2*>(gcol + (size_t)bs * a.dx_ld));
+        f32x2 acc[NB];      // (block 0 through `fix`: PartitionedNorm is the Star tower's, E = 128, one block)
+        acc[0] = fix(*reinterpret_cast<const f32x2*>(gcol + (size_t)bs * a.dx_ld));
+#pragma unroll
+        for (int nb = 1; nb < NB; ++nb) acc[nb] = *reinterpret_cast<const f32x2*>(gcol + 128 * nb + (size_t)bs * a.dx_ld);
         float accl = T.lin_p ? a.dlogit[bs] : 0.f;         // DeepFM: the 1-d linear table's row gradient
         int cnt = 0;                           // wave-uniform
         auto drain = [&]() {
@@ -197,9 +219,12 @@ __device__ __forceinline__ void emb_reduce_body(const EmbStepArgs& a, int bx, in
 #pragma unroll
                 for (int u = 0; u < 8; ++u) v8[u] = *reinterpret_cast<const f32x2*>(gcol + (size_t)L[k + u] * a.dx_ld);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) acc += fix(v8[u]);
+                for (int u = 0; u < 8; ++u) acc[0] += fix(v8[u]);
             }
-            for (; k < cnt; ++k) acc += fix(*reinterpret_cast<const f32x2*>(gcol + (size_t)L[k] * a.dx_ld));
+            for (; k < cnt; ++k) acc[0] += fix(*reinterpret_cast<const f32x2*>(gcol + (size_t)L[k] * a.dx_ld));
+#pragma unroll
+            for (int nb = 1; nb < NB; ++nb)        // E = 256: the row's second 128-column block, same order
+                for (int q = 0; q < cnt; ++q) acc[nb] += *reinterpret_cast<const f32x2*>(gcol + 128 * nb + (size_t)L[q] * a.dx_ld);
             if (T.lin_p)
                 for (int q = 0; q < cnt; ++q) accl += a.dlogit[L[q]];
             __builtin_amdgcn_wave_barrier();
@@ -251,8 +276,11 @@ __device__ __forceinline__ void emb_reduce_body(const EmbStepArgs& a, int bx, in
             T.hasdup[bs] = 0;                  // reset for the next step (read above by every lane that needs it)
             if (T.lin_p) T.glin[bs] = accl;
         }
-        if (a.apply_now) emb_apply_row(a, T, second, rs, lane, acc);
-        else *reinterpret_cast<f32x2*>(T.gbuf + (size_t)bs * EMB + 2 * lane) = acc;
+        if (a.apply_now) emb_apply_row<E>(a, T, second, rs, lane, acc[0]);      // (the lazy mode is the step engine's: E = 128)
+        else if constexpr (E == 128) *reinterpret_cast<f32x2*>(T.gbuf + (size_t)bs * E + 2 * lane) = acc[0];
+        else if (owns)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) *reinterpret_cast<f32x2*>(T.gbuf + (size_t)bs * E + 128 * nb + 2 * lane) = acc[nb];
     }
 }
 

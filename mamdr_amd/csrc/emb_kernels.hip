@@ -35,24 +35,25 @@ __global__ __launch_bounds__(256) void k_emb_flag(const EmbStepArgs a) {
     if (rep != b) T.hasdup[rep] = 1;           // same value from every writer
 }
 
+template <int E>
 __global__ __launch_bounds__(256) void k_emb_reduce(const EmbStepArgs a) {
     __shared__ uint16_t list_all[4][RED_CAP];
-    emb_reduce_body(a, (int)blockIdx.x, (int)blockIdx.y, list_all);
+    emb_reduce_body<E>(a, (int)blockIdx.x, (int)blockIdx.y, list_all);
 }
 
 // 16 B per lane over [user table | item table] (contiguous in the flat vector); a wave covers two
-// 512-B rows, so map[] is read once per half wave.  Without the DeepFM pass, the lane that owns a
+// 512-B rows (E = 128; 256 / E rows of E floats in general), so map[] is read once per half wave.  Without the DeepFM pass, the lane that owns a
 // row's first float4 resets the row's map entry (the other 31 lanes of the row read it in the same
 // instruction, no other thread ever does).  OPT: 0 Adam, 1 SGD, 2 accumulate (a.m = accumulator);
 // all streaming loads of an element are issued before the (rare) dependent gbuf fetch.
-template <int OPT>
+template <int OPT, int E>
 __global__ __launch_bounds__(256) void k_emb_sweep(const EmbStepArgs a) {
     const int64_t n0 = a.t[0].n_rows;
-    const int64_t n4 = (n0 + a.t[1].n_rows) * (EMB / 4);
+    const int64_t n4 = (n0 + a.t[1].n_rows) * (E / 4);
     const bool reset = a.t[0].lin_p == nullptr;
     for (int64_t e4 = (int64_t)blockIdx.x * 256 + threadIdx.x; e4 < n4; e4 += (int64_t)gridDim.x * 256) {
-        const int64_t row = e4 >> 5;
-        const int c4 = (int)(e4 & 31);
+        const int64_t row = e4 / (E / 4);          // (E / 4 is a power of two)
+        const int c4 = (int)(e4 & (E / 4 - 1));
         // (explicit selects: indexing a.t[] with a per-lane value would spill the struct to scratch)
         const bool second = row >= n0;
         int32_t* map = second ? a.t[1].map : a.t[0].map;
@@ -75,7 +76,7 @@ __global__ __launch_bounds__(256) void k_emb_sweep(const EmbStepArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) g[k] = __fmul_rn(a.opt.two_l2, p[k]);
         if (rep != EMB_UNTOUCHED) {
-            const f32x4 gb = reinterpret_cast<const f32x4*>(gbuf + (size_t)rep * EMB)[c4];
+            const f32x4 gb = reinterpret_cast<const f32x4*>(gbuf + (size_t)rep * E)[c4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) g[k] = __fadd_rn(g[k], gb[k]);
             if (reset && c4 == 0) map[lrow] = EMB_UNTOUCHED;
@@ -175,20 +176,41 @@ void launch_emb_flush(const EmbStepArgs& a, hipStream_t s) {
     MAMDR_LAUNCH(k_emb_flush, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, a);
 }
 
-void launch_emb_reduce(const EmbStepArgs& a, hipStream_t s) {
-    if (!a.flags_done) hipLaunchKernelGGL(k_emb_flag, dim3((a.rows + 255) / 256, 2), dim3(256), 0, s, a);
-    MAMDR_LAUNCH(k_emb_reduce, dim3((a.rows + 7) / 8, 2), dim3(256), 0, s, a);
+// emb = the tables' row width: 128 from the step engine; 32 / 64 / 128 / 256 from the generic-layer engine (which
+// validates it at mamdr_graph_create)
+template <int E>
+static void launch_emb_reduce_e(const EmbStepArgs& a, hipStream_t s) {
+    constexpr int PPG = EmbRed<E>::PPG;
+    MAMDR_LAUNCH(k_emb_reduce<E>, dim3((a.rows + PPG - 1) / PPG, 2), dim3(256), 0, s, a);
 }
-void launch_emb_sweep(const EmbStepArgs& a, hipStream_t s) {
+void launch_emb_reduce(const EmbStepArgs& a, hipStream_t s, int emb) {
+    if (!a.flags_done) hipLaunchKernelGGL(k_emb_flag, dim3((a.rows + 255) / 256, 2), dim3(256), 0, s, a);
+    switch (emb) {
+        case 32: launch_emb_reduce_e<32>(a, s); break;
+        case 64: launch_emb_reduce_e<64>(a, s); break;
+        case 256: launch_emb_reduce_e<256>(a, s); break;
+        default: launch_emb_reduce_e<EMB>(a, s); break;
+    }
+}
+template <int E>
+static void launch_emb_sweep_e(const EmbStepArgs& a, hipStream_t s) {
     const int64_t n_all = a.t[0].n_rows + a.t[1].n_rows;
-    const int64_t n4 = n_all * (EMB / 4);
+    const int64_t n4 = n_all * (E / 4);
     int64_t blocks = (n4 + 255) / 256;
     // one float4 per thread: measured on Amazon-6 (79 M elements) 349 us uncapped vs 415 us with a
     // 4096-workgroup grid-stride loop; the cap only guards the 32-bit grid dimension
     if (blocks > 0x7fffffff) blocks = 0x7fffffff;
-    if (a.opt.optimizer == 0) MAMDR_LAUNCH(k_emb_sweep<0>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else if (a.opt.optimizer == 1) MAMDR_LAUNCH(k_emb_sweep<1>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else MAMDR_LAUNCH(k_emb_sweep<2>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    if (a.opt.optimizer == 0) MAMDR_LAUNCH((k_emb_sweep<0, E>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    else if (a.opt.optimizer == 1) MAMDR_LAUNCH((k_emb_sweep<1, E>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+    else MAMDR_LAUNCH((k_emb_sweep<2, E>), dim3((unsigned)blocks), dim3(256), 0, s, a);
+}
+void launch_emb_sweep(const EmbStepArgs& a, hipStream_t s, int emb) {
+    switch (emb) {
+        case 32: launch_emb_sweep_e<32>(a, s); break;
+        case 64: launch_emb_sweep_e<64>(a, s); break;
+        case 256: launch_emb_sweep_e<256>(a, s); break;
+        default: launch_emb_sweep_e<EMB>(a, s); break;
+    }
 }
 void launch_lin_sweep(const EmbStepArgs& a, hipStream_t s) {
     const int64_t n_all = a.t[0].n_rows + a.t[1].n_rows;

@@ -30,6 +30,10 @@
 // through the table kernels of emb_kernels.hip in their per-step form (k_emb_flag / k_emb_reduce: duplicates summed
 // in batch order by the row's first position; k_emb_sweep: one HBM pass over both tables).
 //
+// Field width: 128 for every tower; MLP / WDL / DeepFM also run at 32, 64 and 256 (cfg.emb_dim = model.user_dim; deepctr.py:95-102
+// hands it to SparseFeat): k_graph_gather<E>, k_graph_fm_fwd / _bwd<E>, k_emb_reduce<E> / k_emb_sweep<OPT, E> index by it, the
+// first layer's 3 E input columns need no multiple of 64 (gemm_tile32's zero tail, GemmArgs::m_rows), the flat vector is unpadded.
+//
 // The single-output deepctr towers on the same layers (deepctr.py:33-46; ONE task serves every domain):
 //   NFM      f = bi-interaction of the three fields (k_graph_feat_fwd/bwd), DNN over f, + deepctr's linear logit
 //   PNN      DNN over [x | the 3 pairwise inner products] (the 3 extra kernel rows ride as a rank-3 epilogue of the GEMM)
@@ -96,19 +100,33 @@ struct GatherArgs {
     float* extra;                               // NFM: sum of the linear terms per position
     float* xt;                                  // AutoInt: compact [rows_pad][384] copy of x (token-major: row 3 b + t)
 };
-// one wave per batch position: lanes 0..31 copy the user row, 32..63 the item row, then lanes 0..31 the domain row
+// E = 128: one wave per batch position -- lanes 0..31 copy the user row, 32..63 the item row, then lanes 0..31 the domain row.
+// Any accepted width E (32 / 64 / 128 / 256): a row's [user | item] pair is 2 E floats = E / 2 lanes of 16 bytes, so a wave
+// serves 128 / E rows (4 at E = 32, where a table row is exactly one 128-byte line and 8 neighbouring lanes read it whole;
+// 2 at E = 64) and at E = 256 every lane takes two vectors per field.  The first E / 4 lanes of a row's group then copy
+// the domain row.  `sub` = the lane's float4 within the 2 E floats of [user | item].
+template <int E>
 __global__ __launch_bounds__(256) void k_graph_gather(const GatherArgs a) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    constexpr int LPF = E / 4;                              // lanes (float4s) per field
+    constexpr int GROUP = 2 * LPF < 64 ? 2 * LPF : 64;      // lanes that share a row
+    constexpr int RPW = 64 / GROUP;                         // rows per wave
+    constexpr int NJ = 2 * LPF / GROUP;                     // vectors per lane and pass
+    const int lane = threadIdx.x & 63;
+    const int r = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / GROUP, sub0 = lane % GROUP;
     if (r >= a.rows_pad) return;
     float* xr = a.x + (size_t)r * a.ld;
     if (r >= a.rows) {          // padding rows: zeros in, nothing out (their d loss / d logit is zero)
-        *reinterpret_cast<f32x4*>(xr + 4 * lane) = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (lane < 32) *reinterpret_cast<f32x4*>(xr + 2 * EMB + 4 * lane) = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (a.xt) {
-            *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 4 * lane) = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (lane < 32) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 2 * EMB + 4 * lane) = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int sub = sub0 + 64 * j;
+            *reinterpret_cast<f32x4*>(xr + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (sub < LPF) *reinterpret_cast<f32x4*>(xr + 2 * E + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (E == EMB && a.xt) {
+                *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
+                if (sub < LPF) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 2 * EMB + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
+            }
         }
-        if (lane == 0) {
+        if (sub0 == 0) {
             a.domrow[r] = -1;
             a.y[r] = 0.f;
             if (a.urow) { a.urow[r] = -1; a.irow[r] = -1; }
@@ -122,16 +140,20 @@ __global__ __launch_bounds__(256) void k_graph_gather(const GatherArgs a) {
     u = u < 0 ? 0 : (u >= a.n_user ? a.n_user - 1 : u);
     it = it < 0 ? 0 : (it >= a.n_item ? a.n_item - 1 : it);
     d = d < 0 ? 0 : (d >= a.n_domain ? a.n_domain - 1 : d);
-    const float* row = lane < 32 ? a.user_tab + (size_t)u * EMB + 4 * lane : a.item_tab + (size_t)it * EMB + 4 * (lane - 32);
-    const f32x4 v0 = *reinterpret_cast<const f32x4*>(row);
-    *reinterpret_cast<f32x4*>(xr + 4 * lane) = v0;
-    if (a.xt) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 4 * lane) = v0;
-    if (lane < 32) {
-        const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.dm + (size_t)d * EMB + 4 * lane);
-        *reinterpret_cast<f32x4*>(xr + 2 * EMB + 4 * lane) = v1;
-        if (a.xt) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 2 * EMB + 4 * lane) = v1;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const int sub = sub0 + 64 * j;
+        const float* row = sub < LPF ? a.user_tab + (size_t)u * E + 4 * sub : a.item_tab + (size_t)it * E + 4 * (sub - LPF);
+        const f32x4 v0 = *reinterpret_cast<const f32x4*>(row);
+        *reinterpret_cast<f32x4*>(xr + 4 * sub) = v0;
+        if (E == EMB && a.xt) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 4 * sub) = v0;
+        if (sub < LPF) {
+            const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.dm + (size_t)d * E + 4 * sub);
+            *reinterpret_cast<f32x4*>(xr + 2 * E + 4 * sub) = v1;
+            if (E == EMB && a.xt) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 2 * EMB + 4 * sub) = v1;
+        }
     }
-    if (lane == 0) {
+    if (sub0 == 0) {
         a.domrow[r] = d;
         a.y[r] = a.label[src];
         if (a.extra) a.extra[r] = ((a.lin_u ? a.lin_u[u] : 0.f) + (a.lin_i ? a.lin_i[it] : 0.f)) + a.lin_d[d];
@@ -143,12 +165,21 @@ __global__ __launch_bounds__(256) void k_graph_gather(const GatherArgs a) {
         }
     }
 }
+// rows_pad is a multiple of 64, a workgroup serves 4 waves x 128 / E rows (at most 16)
+static void launch_graph_gather(const GatherArgs& a, int emb, hipStream_t s) {
+    switch (emb) {
+        case 32: GLAUNCH(k_graph_gather<32>, dim3(a.rows_pad / 16), dim3(256), 0, s, a); break;
+        case 64: GLAUNCH(k_graph_gather<64>, dim3(a.rows_pad / 8), dim3(256), 0, s, a); break;
+        case 256: GLAUNCH(k_graph_gather<256>, dim3(a.rows_pad / 4), dim3(256), 0, s, a); break;
+        default: GLAUNCH(k_graph_gather<EMB>, dim3(a.rows_pad / 4), dim3(256), 0, s, a); break;
+    }
+}
 
 // ------------------------------------------------------------------ dense contractions
 // MODE 0:  C[M x N] = A[M x K] . B[K x N]        + bias, relu, dropout           (layer forward)
 // MODE 1:  C[M x N] = A[M x K] . B[N x K]^T      x the gate of gate_y, += C        (d input = dz . W^T)
 // MODE 2:  C[M x N] = A[K x M]^T . B[K x N]                                        (dW = in^T . dz, K = batch rows)
-// M, N multiples of 64, K a multiple of 16.  64x64 tile per workgroup, 4 waves own its 32x32 quadrants
+// M, N multiples of 64, K a multiple of 16 (MODE 2: M may end inside its last tile, see m_rows).  64x64 tile per workgroup, 4 waves own its 32x32 quadrants
 // (`32x32x2`, A / B fragments read from LDS as one float per lane: [k][m] images, conflict-free).
 struct GemmArgs {
     const float* A; int lda;
@@ -163,6 +194,10 @@ struct GemmArgs {
     const float* xe; int xe_ld; const float* we; int n_xe;
     // MODE 2 only: blockIdx.z owns K rows [z K, (z + 1) K) of A and B and writes its partial product at C + z zstride
     size_t zstride;
+    // MODE 2 only: rows of C that exist (0: every tile is whole).  A first layer on 3 E input columns has M = 96 at E = 32:
+    // the last tile reads 64 columns of A (its neighbours in the workspace, whatever they hold -- row m of C depends on
+    // column m of A alone) and stores the rows below m_rows only
+    int m_rows;
 };
 constexpr int MAX_GROUP = 32;
 struct GroupTab {
@@ -245,6 +280,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, const int bx, const
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kk;
+        if (MODE == 2 && a.m_rows && row >= a.m_rows) continue;
         float v = acc[r];
         if (MODE == 0) {
             for (int j = 0; j < a.n_xe; ++j) v = fmaf(a.xe[(size_t)row * a.xe_ld + j], a.we[(size_t)j * a.n_cols + col], v);
@@ -553,6 +589,7 @@ struct WMulti {
     const float* A[MAX_WQ]; const float* B[MAX_WQ]; float* C[MAX_WQ];       // C: the partial products' base, or dW itself (split 1)
     int lda[MAX_WQ], ldb[MAX_WQ], N[MAX_WQ], tx[MAX_WQ], ty[MAX_WQ], K[MAX_WQ];     // K = batch rows per split
     int mn[MAX_WQ];                 // M x N (stride between the splits' partial products)
+    int M[MAX_WQ];                  // rows of dW (ty = the tiles that cover them, the last one possibly in part)
 };
 __global__ __launch_bounds__(256) void k_graph_wgrad_multi(const WMulti t) {
     int p = 0;
@@ -571,6 +608,7 @@ __global__ __launch_bounds__(256) void k_graph_wgrad_multi(const WMulti t) {
     a.ldc = t.N[p];
     a.K = t.K[p];
     a.zstride = (size_t)t.mn[p];
+    a.m_rows = t.M[p];
     gemm_tile<2>(a, bx, by, bz);
 }
 // ... and their ends: per problem, the workgroups that add the splits' partial products in a fixed order, then the ones
@@ -861,6 +899,53 @@ __global__ __launch_bounds__(256) void k_graph_feat_bwd(const FeatArgs a) {
         *reinterpret_cast<f32x2*>(drow + EMB + 2 * lane) = di;
     }
     *reinterpret_cast<f32x2*>(drow + 2 * EMB + 2 * lane) = dd;
+}
+// DeepFM at a field width E other than 128 (32 / 64 / 256; the 128-wide tower stays on kind 2 above, whose summation order
+// its recorded results are held to).  A row's field is E / 4 lanes of 16 bytes, so a wave serves 256 / E rows (8 at E = 32,
+// 4 at E = 64, 1 at E = 256) and the FM term  sum_k (u i + u d + i d)_k  is a butterfly over the row's lanes alone.
+template <int E>
+__global__ __launch_bounds__(256) void k_graph_fm_fwd(const FeatArgs a) {
+    constexpr int LPR = E / 4, RPW = 64 / LPR;              // lanes per row, rows per wave
+    const int lane = threadIdx.x & 63, c4 = lane % LPR;
+    const int r = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    if (r >= a.rows_pad) return;        // (rows_pad is a multiple of 64: the row's lanes leave together)
+    const float* row = a.act + (size_t)r * a.ld + 4 * c4;
+    const f32x4 u = *reinterpret_cast<const f32x4*>(row), it = *reinterpret_cast<const f32x4*>(row + E),
+                d = *reinterpret_cast<const f32x4*>(row + 2 * E);
+    float f = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f += fmaf(it[k], d[k], fmaf(u[k], d[k], u[k] * it[k]));
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) f += __shfl_xor(f, o);
+    if (c4 == 0) a.extra[r] += f;
+}
+// d fm / d e_f = d logit x the sum of the other two fields' rows, ADDED to what the DNN's first layer left in d x
+// (user / item columns only when the tables train)
+template <int E>
+__global__ __launch_bounds__(256) void k_graph_fm_bwd(const FeatArgs a) {
+    constexpr int LPR = E / 4, RPW = 64 / LPR;
+    const int lane = threadIdx.x & 63, c4 = lane % LPR;
+    const int r = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    if (r >= a.rows_pad) return;
+    const float* row = a.act + (size_t)r * a.ld + 4 * c4;
+    float* drow = a.dact + (size_t)r * a.ld + 4 * c4;
+    const f32x4 u = *reinterpret_cast<const f32x4*>(row), it = *reinterpret_cast<const f32x4*>(row + E),
+                d = *reinterpret_cast<const f32x4*>(row + 2 * E);
+    const float dl = a.dlogit[r];
+    f32x4 dd = *reinterpret_cast<const f32x4*>(drow + 2 * E);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dd[k] = dd[k] + dl * (u[k] + it[k]);
+    *reinterpret_cast<f32x4*>(drow + 2 * E) = dd;
+    if (a.dx_all) {
+        f32x4 du = *reinterpret_cast<const f32x4*>(drow), di = *reinterpret_cast<const f32x4*>(drow + E);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            du[k] = du[k] + dl * (it[k] + d[k]);
+            di[k] = di[k] + dl * (u[k] + d[k]);
+        }
+        *reinterpret_cast<f32x4*>(drow) = du;
+        *reinterpret_cast<f32x4*>(drow + E) = di;
+    }
 }
 // NFM's linear domain table: g[d] = sum over the batch rows of domain d of d loss / d logit  +  2 l2_lin w[d]
 // one workgroup per domain: rows strided over the 256 threads, LDS tree in a fixed order
@@ -1307,16 +1392,17 @@ __global__ void k_graph_scale(float* x, float s) { x[0] *= s; }
 // g[d][c] = sum over the batch rows of domain d of d x[b][256 + c]  +  2 l2 Dm[d][c]   (rows in batch order)
 // grid (8 column blocks, domains): 16 columns x 16 row groups per workgroup, 8 loads in flight, summed through LDS in a
 // fixed order; a domain with no row in the batch (all but one of them in a domain step) leaves after one look at the ids.
+// (emb = the table's width: emb / 16 column blocks, first column x_col = 2 emb of d x)
 __device__ __forceinline__ void domain_grad_body(const float* dx, int ld, int x_col, const int32_t* domrow, int rows,
                                                  const float* dm, float two_l2, float* g, const int bx, const int by,
-                                                 const GradSink& sk) {
+                                                 const int emb, const GradSink& sk) {
     __shared__ float red[CS_GROUPS][CS_COLS + 1];
     const int d = by, c = threadIdx.x & (CS_COLS - 1), rg = threadIdx.x / CS_COLS;
     const int col = bx * CS_COLS + c;
     int mine = 0;
     for (int b = threadIdx.x; b < rows; b += 256) mine |= domrow[b] == d;
     if (!__syncthreads_or(mine)) {
-        if (rg == 0) sink1(sk, g + d * EMB + col, two_l2 * dm[d * EMB + col]);
+        if (rg == 0) sink1(sk, g + d * emb + col, two_l2 * dm[d * emb + col]);
         return;
     }
     const float* p = dx + x_col + col;
@@ -1340,14 +1426,14 @@ __device__ __forceinline__ void domain_grad_body(const float* dx, int ld, int x_
         float t = 0.f;
 #pragma unroll
         for (int k = 0; k < CS_GROUPS; ++k) t += red[k][c];
-        sink1(sk, g + d * EMB + col, t + two_l2 * dm[d * EMB + col]);
+        sink1(sk, g + d * emb + col, t + two_l2 * dm[d * emb + col]);
     }
 }
 __global__ __launch_bounds__(256) void k_graph_domain_grad(const float* dx, int ld, int x_col, const int32_t* domrow, int rows,
-                                                           const float* dm, float two_l2, float* g) {
+                                                           const float* dm, float two_l2, float* g, int emb) {
     GradSink none;
     none.p = nullptr;
-    domain_grad_body(dx, ld, x_col, domrow, rows, dm, two_l2, g, blockIdx.x, blockIdx.y, none);
+    domain_grad_body(dx, ld, x_col, domrow, rows, dm, two_l2, g, blockIdx.x, blockIdx.y, emb, none);
 }
 // ---- the tail of a step's backward pass in ONE launch: the ends of the queued weight gradients (k_graph_wfinish_multi's
 // workgroups), the narrow contractions that were queued with them (head / gate kernels, PNN's inner-product rows, the
@@ -1359,7 +1445,8 @@ struct TailJobs {
     int tn_first[MAX_TQ + 1];       // first workgroup (behind the weight gradients' ends) of narrow contraction q
     const float* in[MAX_TQ]; const float* d[MAX_TQ]; float* out[MAX_TQ]; float* sum_out[MAX_TQ];
     int in_ld[MAX_TQ], d_ld[MAX_TQ], rows[MAX_TQ], n_j[MAX_TQ], n_e[MAX_TQ];
-    int dg_first, dg_blocks;        // the domain table's gradient: 8 column blocks x n_domain (0 blocks: not in this launch)
+    int dg_first, dg_blocks;        // the domain table's gradient: dg_emb / 16 column blocks x n_domain (0 blocks: not in this launch)
+    int dg_emb;                     // ... its width
     const float* dx; int ld, x_col; const int32_t* domrow; int dg_rows; const float* dm; float two_l2; float* g_dm;
     int lin_blocks;                 // the 1-d linear domain table's gradient (k_graph_lin_domain_grad's workgroups: one per domain)
     const float* lin_dlogit; const float* lin_w; float lin_two_l2; float* lin_g;
@@ -1382,8 +1469,8 @@ __global__ __launch_bounds__(256) void k_graph_tail(const WFinish f, const TailJ
     }
     bid -= j.dg_first;
     if (bid < j.dg_blocks) {
-        domain_grad_body(j.dx, j.ld, j.x_col, j.domrow, j.dg_rows, j.dm, j.two_l2, j.g_dm, bid % (EMB / CS_COLS), bid / (EMB / CS_COLS),
-                         j.sink);
+        const int cb = j.dg_emb / CS_COLS;
+        domain_grad_body(j.dx, j.ld, j.x_col, j.domrow, j.dg_rows, j.dm, j.two_l2, j.g_dm, bid % cb, bid / cb, j.dg_emb, j.sink);
         return;
     }
     bid -= j.dg_blocks;
@@ -1510,6 +1597,7 @@ struct mamdr_graph {
     int32_t* domrow = nullptr;
     float *thresholds = nullptr, *frozen_sumsq = nullptr, *sumsq_partials = nullptr, *eval_acc = nullptr;
     // trainable tables
+    int emb = EMB;              // width of the three tables' rows (cfg.emb_dim; other than 128 for mlp / wdl / deepfm only)
     bool tables = false;
     int64_t table_floats = 0;
     int32_t *urow = nullptr, *irow = nullptr, *map_u = nullptr, *map_i = nullptr, *hasdup_u = nullptr, *hasdup_i = nullptr;
@@ -1548,13 +1636,13 @@ int add_dnn(mamdr_graph* g, const std::string& name, int in_dim, const int32_t* 
 // most of the 256 CUs idle (a 384 x 512 kernel is 48 tiles); the partial products meet in k_graph_wfinish, which also
 // carries the layer's bias gradient (column sums of `dz` into `db`, skipped when db is null)
 struct DomainGradJob { const float* dx; int ld, x_col; const int32_t* domrow; int rows; const float* dm; float two_l2; float* g_dm;
-                       int n_domain;
+                       int n_domain, emb;
                        const float* lin_dlogit; const float* lin_w; float lin_two_l2; float* lin_g; };     // lin_g null: no linear table
 void flush_wgrads(mamdr_graph* g, const DomainGradJob* dg = nullptr) {
     const int n = (int)g->wq.size();
     if (!n && g->tq.empty() && !dg) return;
     int tiles = 0;
-    for (const auto& q : g->wq) tiles += (q.M / GT) * (q.N / GT);
+    for (const auto& q : g->wq) tiles += ((q.M + GT - 1) / GT) * (q.N / GT);
     int S = 1;
     while (S < 16 && tiles * S < g->wq_blocks) S *= 2;
     int split[MAX_WQ];
@@ -1590,9 +1678,10 @@ void flush_wgrads(mamdr_graph* g, const DomainGradJob* dg = nullptr) {
         m.C[p] = sp > 1 ? part : q.out;
         m.N[p] = q.N;
         m.tx[p] = q.N / GT;
-        m.ty[p] = q.M / GT;
+        m.ty[p] = (q.M + GT - 1) / GT;
         m.K[p] = q.rows / sp;
         m.mn[p] = q.M * q.N;
+        m.M[p] = q.M;
         nb += m.tx[p] * m.ty[p] * sp;
         f.first[p] = nf;
         f.part[p] = sp > 1 ? part : q.out;
@@ -1632,7 +1721,8 @@ void flush_wgrads(mamdr_graph* g, const DomainGradJob* dg = nullptr) {
     j.tn_first[j.n_tn] = nt;
     j.dg_first = nt;
     if (dg) {
-        j.dg_blocks = (EMB / CS_COLS) * dg->n_domain;
+        j.dg_blocks = (dg->emb / CS_COLS) * dg->n_domain;
+        j.dg_emb = dg->emb;
         j.dx = dg->dx;
         j.ld = dg->ld;
         j.x_col = dg->x_col;
@@ -1681,7 +1771,7 @@ void launch_wgrad(mamdr_graph* g, GemmArgs a, int M, int N, int rows, const floa
         queue_wgrad(g, a.A, a.lda, a.B, a.ldb, a.C, M, N, rows, dz, db);
         return;
     }
-    const int tiles = (M / GT) * (N / GT), nkt = rows / GK;
+    const int ty = (M + GT - 1) / GT, tiles = ty * (N / GT), nkt = rows / GK;
     int split = 1;
     while (split < 16 && tiles * split < 256 && nkt % (2 * split) == 0 && nkt / (2 * split) >= 4 &&
            (size_t)(2 * split) * M * N <= g->wpart_floats)
@@ -1689,8 +1779,9 @@ void launch_wgrad(mamdr_graph* g, GemmArgs a, int M, int N, int rows, const floa
     float* out = a.C;
     a.K = rows / split;
     a.zstride = (size_t)M * N;
+    a.m_rows = M;
     if (split > 1) a.C = g->wpart;
-    GLAUNCH(k_graph_gemm<2>, dim3(N / GT, M / GT, split), dim3(256), 0, g->stream, a);
+    GLAUNCH(k_graph_gemm<2>, dim3(N / GT, ty, split), dim3(256), 0, g->stream, a);
     const int64_t n4 = (int64_t)M * N / 4;
     const int nb_red = split > 1 ? (int)((n4 + 255) / 256) : 0, nb_cs = db ? (N + CS_COLS - 1) / CS_COLS : 0;
     if (nb_red + nb_cs)
@@ -1704,8 +1795,9 @@ void launch_wgrad(mamdr_graph* g, GemmArgs a, int M, int N, int rows, const floa
 // changed the rounding of every generic-layer run after it in the same session)
 constexpr int TILE32_BELOW_DEFAULT = 512;
 std::atomic<int> g_tile32_below{TILE32_BELOW_DEFAULT};
+// (a width that is no multiple of 64 -- d x of a first layer on 32- or 96-wide fields -- has no 64 x 64 tiling at all)
 inline bool use_tile32(int M, int N, int n_group = 1) {
-    return (M / GT) * (N / GT) * n_group < g_tile32_below.load(std::memory_order_relaxed) && N % T32 == 0;
+    return N % T32 == 0 && (N % GT != 0 || (M / GT) * (N / GT) * n_group < g_tile32_below.load(std::memory_order_relaxed));
 }
 void launch_gemm(int mode, const GemmArgs& a, int M, int N, hipStream_t s) {
     const dim3 grid(N / GT, M / GT), block(256);
@@ -2076,7 +2168,12 @@ int task_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
         }
         FeatArgs fa;
         fill_feat(g, t, sc, fa);
-        GLAUNCH(k_graph_feat_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa);
+        switch (g->emb) {       // (other than 128: DeepFM alone)
+            case 32: GLAUNCH(k_graph_fm_fwd<32>, dim3(sc.rp / 32), dim3(256), 0, g->stream, fa); break;
+            case 64: GLAUNCH(k_graph_fm_fwd<64>, dim3(sc.rp / 16), dim3(256), 0, g->stream, fa); break;
+            case 256: GLAUNCH(k_graph_fm_fwd<256>, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
+            default: GLAUNCH(k_graph_feat_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
+        }
         const bool nfm = kind == MAMDR_GRAPH_NFM;
         dnn_forward(g, g->dnns[t.tower], t.col[0], nfm ? g->f_col : 0, sc, kind == MAMDR_GRAPH_PNN ? g->f_col : -1);
         return t.col[0].back();
@@ -2109,8 +2206,8 @@ int check(const mamdr_graph* g) {
 }
 // trainable tables: the regulariser term of a reported loss needs their current sums of squares
 void refresh_sumsq(mamdr_graph* g) {
-    launch_sumsq(g->params, (int64_t)g->cfg.n_user * EMB, g->sumsq_partials, g->frozen_sumsq + 0, g->stream);
-    launch_sumsq(g->params + (size_t)g->cfg.n_user * EMB, (int64_t)g->cfg.n_item * EMB, g->sumsq_partials, g->frozen_sumsq + 1,
+    launch_sumsq(g->params, (int64_t)g->cfg.n_user * g->emb, g->sumsq_partials, g->frozen_sumsq + 0, g->stream);
+    launch_sumsq(g->params + (size_t)g->cfg.n_user * g->emb, (int64_t)g->cfg.n_item * g->emb, g->sumsq_partials, g->frozen_sumsq + 1,
                  g->stream);
     if (g->has_lin) {
         launch_sumsq(g->params + g->lin_u_off, g->cfg.n_user, g->sumsq_partials, g->frozen_sumsq + 2, g->stream);
@@ -2176,11 +2273,17 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     *out = nullptr;
     (void)mamdr::env_warn_unknown();
     if (cfg->abi_version != MAMDR_ABI_VERSION) return gfail(MAMDR_EINVAL, "abi_version %d != %d", cfg->abi_version, MAMDR_ABI_VERSION);
-    if (cfg->emb_dim != EMB) return gfail(MAMDR_EINVAL, "emb_dim must be %d", EMB);
     if (cfg->n_user <= 0 || cfg->n_item <= 0 || cfg->n_domain <= 0 || cfg->max_batch <= 0) return gfail(MAMDR_EINVAL, "bad sizes");
     if (cfg->emb_trainable && cfg->max_batch > 16384) return gfail(MAMDR_EINVAL, "trainable tables: max_batch <= 16384");
     if (cfg->kind < MAMDR_GRAPH_SHARED_BOTTOM || cfg->kind > MAMDR_GRAPH_DEEPFM)
         return gfail(MAMDR_EINVAL, "unknown graph tower kind %d", cfg->kind);
+    {       // the field width: gather, FM term and table updates are instantiated for the accepted widths alone
+        const bool any_width = cfg->kind == MAMDR_GRAPH_MLP || cfg->kind == MAMDR_GRAPH_WDL || cfg->kind == MAMDR_GRAPH_DEEPFM;
+        const int e = cfg->emb_dim;
+        if (e != EMB && !(any_width && (e == 32 || e == 64 || e == 256)))
+            return gfail(MAMDR_EINVAL, "emb_dim %d: the mlp / wdl / deepfm towers take emb_dim 32, 64, 128 or 256, every other tower "
+                                       "emb_dim 128 only", e);
+    }
     if (!(cfg->dropout >= 0.f && cfg->dropout < 1.f)) return gfail(MAMDR_EINVAL, "dropout rate must be in [0,1)");
     const bool single = cfg->kind >= MAMDR_GRAPH_NFM;
     const bool has_lin = cfg->kind == MAMDR_GRAPH_NFM || cfg->kind == MAMDR_GRAPH_CCPM || cfg->kind == MAMDR_GRAPH_AUTOINT ||
@@ -2209,6 +2312,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     mamdr_graph* g = new (std::nothrow) mamdr_graph();
     if (!g) return gfail(MAMDR_EHIP, "out of host memory");
     g->cfg = *cfg;
+    g->emb = cfg->emb_dim;
     g->stream = (hipStream_t)stream;
     if (const char* ev = getenv("MAMDR_GRAPH_NO_GROUP")) g->group_ok = atoi(ev) == 0;
     if (const char* ev = getenv("MAMDR_GRAPH_NO_DEFER")) g->defer_w = atoi(ev) == 0;
@@ -2228,15 +2332,15 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     uint32_t next_id = 0;
     g->tables = cfg->emb_trainable != 0;
     if (g->tables) {        // [user table | item table] contiguous at the head (k_emb_sweep walks them as one range)
-        add_tensor(g, "user_emb", cfg->n_user, EMB);
-        add_tensor(g, "item_emb", cfg->n_item, EMB);
+        add_tensor(g, "user_emb", cfg->n_user, g->emb);
+        add_tensor(g, "item_emb", cfg->n_item, g->emb);
         if (has_lin) {      // their 1-d linear tables train with them (deepctr: same feature column)
             g->lin_u_off = add_tensor(g, "lin_user", cfg->n_user, 1);
             g->lin_i_off = add_tensor(g, "lin_item", cfg->n_item, 1);
         }
         g->table_floats = g->n_params;
     }
-    g->dm_off = add_tensor(g, "domain_emb", cfg->n_domain, EMB);
+    g->dm_off = add_tensor(g, "domain_emb", cfg->n_domain, g->emb);
     std::vector<int> shared;
     for (int e = 0; e < n_shared; ++e) {
         const std::string nm = cfg->kind == MAMDR_GRAPH_SHARED_BOTTOM ? "bottom"
@@ -2266,7 +2370,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
             g->att_w[1] = add_tensor(g, "att1_w", ATT_OUT, ATT_P);
             g->att_w[2] = add_tensor(g, "att2_w", ATT_OUT, ATT_P);
         }
-        d.in_dim = nfm ? EMB : (ccpm ? 4 * EMB : XDIM);
+        d.in_dim = nfm ? EMB : (ccpm ? 4 * EMB : 3 * g->emb);      // (NFM / CCPM: 128-wide fields only)
         int in = d.in_dim;
         for (int l = 0; l < cfg->n_expert_hidden; ++l) {
             Layer L;
@@ -2287,7 +2391,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
         if (cfg->uncertainty_weight) g->lv_off = add_tensor(g, "log_var", cfg->n_domain, 1);
         g->shared_end = g->n_params;
         t.blk_off = t.blk_end = g->n_params;
-        int c = XDIM;
+        int c = 3 * g->emb;
         g->f_col = c;
         c += nfm ? EMB : (ccpm ? 4 * EMB : 4);
         if (ccpm) { g->cg_col = c; c += 64; }
@@ -2377,8 +2481,8 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
         alloc((void**)&g->hasdup_i, rp * sizeof(int32_t));
         alloc((void**)&g->map_u, (size_t)cfg->n_user * sizeof(int32_t));
         alloc((void**)&g->map_i, (size_t)cfg->n_item * sizeof(int32_t));
-        alloc((void**)&g->gbuf_u, rp * EMB * sizeof(float));
-        alloc((void**)&g->gbuf_i, rp * EMB * sizeof(float));
+        alloc((void**)&g->gbuf_u, rp * g->emb * sizeof(float));
+        alloc((void**)&g->gbuf_i, rp * g->emb * sizeof(float));
     }
     alloc((void**)&g->dlogit, rp * sizeof(float));
     alloc((void**)&g->rowloss, rp * sizeof(float));
@@ -2477,7 +2581,7 @@ int mamdr_graph_bind_state(mamdr_graph* g, float* d_params, float* d_m, float* d
     g->adam_v = d_v;
     if (g->tables) {
         g->user_tab = d_params;
-        g->item_tab = d_params + (size_t)g->cfg.n_user * EMB;
+        g->item_tab = d_params + (size_t)g->cfg.n_user * g->emb;
     }
     return MAMDR_OK;
 }
@@ -2526,11 +2630,11 @@ int mamdr_graph_bind_table(mamdr_graph* g, int seg, const float* d_rows, int64_t
     if (seg == MAMDR_SEG_USER_EMB) {
         if (n_rows != g->cfg.n_user) return gfail(MAMDR_EINVAL, "user table has %lld rows, config says %d", (long long)n_rows, g->cfg.n_user);
         g->user_tab = d_rows;
-        launch_sumsq(d_rows, n_rows * EMB, g->sumsq_partials, g->frozen_sumsq + 0, g->stream);
+        launch_sumsq(d_rows, n_rows * g->emb, g->sumsq_partials, g->frozen_sumsq + 0, g->stream);
     } else if (seg == MAMDR_SEG_ITEM_EMB) {
         if (n_rows != g->cfg.n_item) return gfail(MAMDR_EINVAL, "item table has %lld rows, config says %d", (long long)n_rows, g->cfg.n_item);
         g->item_tab = d_rows;
-        launch_sumsq(d_rows, n_rows * EMB, g->sumsq_partials, g->frozen_sumsq + 1, g->stream);
+        launch_sumsq(d_rows, n_rows * g->emb, g->sumsq_partials, g->frozen_sumsq + 1, g->stream);
     } else {
         return gfail(MAMDR_EINVAL, "segment %d is not a bindable table", seg);
     }
@@ -2654,7 +2758,7 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
         }
         GatherArgs ga;
         fill_gather(g, *d, d_perm, row_base, sc, ga);
-        GLAUNCH(k_graph_gather, dim3(sc.rp / 4), dim3(256), 0, g->stream, ga);
+        launch_graph_gather(ga, g->emb, g->stream);
         const int t_col = task_forward(g, t, sc);
         const Dnn& tower = g->dnns[t.tower];
         HeadArgs ha;
@@ -2687,7 +2791,7 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
         if (d_loss_out && g->tables) refresh_sumsq(g);
         if (d_loss_out || weighted)     // the weighted loss takes d / d log_var from the batch's mean BCE: this launch, always
             GLAUNCH(k_graph_loss, dim3(1), dim3(256), 0, g->stream, g->rowloss, sc.rows, g->params + g->dm_off,
-                               g->cfg.n_domain * EMB, g->cfg.l2_emb, g->frozen_sumsq, d_loss_out ? d_loss_out + s : g->eval_acc + 1, 0,
+                               g->cfg.n_domain * g->emb, g->cfg.l2_emb, g->frozen_sumsq, d_loss_out ? d_loss_out + s : g->eval_acc + 1, 0,
                                g->extra ? g->params + g->lin_d_off : nullptr, g->cfg.n_domain, g->cfg.l2_linear,
                                weighted ? g->params + g->lv_off : nullptr, g->domrow, weighted ? g->G(g->lv_off) : nullptr,
                                g->cfg.n_domain);
@@ -2699,7 +2803,7 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
         // the x columns of the gradient workspace collect d x from every first layer (the domain columns alone while the
         // tables are frozen): the first writer overwrites, the others add
         bool dx_started = false;
-        const int dx_first = g->tables ? 0 : 2 * EMB, dx_n = g->tables ? 0 : EMB;
+        const int dx_first = g->tables ? 0 : 2 * g->emb, dx_n = g->tables ? 0 : g->emb;
         if (g->single && g->cfg.kind == MAMDR_GRAPH_AUTOINT) {
             // DNN on x as any first layer; then the attention stack from the head's d [attention output] down to d x
             dnn_backward(g, tower, t.col[0], 0, 0, -1, false, dx_first, dx_n, sc);
@@ -2784,7 +2888,12 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
             if (g->cfg.kind == MAMDR_GRAPH_DEEPFM) {
                 FeatArgs fa;
                 fill_feat(g, t, sc, fa);
-                GLAUNCH(k_graph_feat_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa);
+                switch (g->emb) {
+                    case 32: GLAUNCH(k_graph_fm_bwd<32>, dim3(sc.rp / 32), dim3(256), 0, g->stream, fa); break;
+                    case 64: GLAUNCH(k_graph_fm_bwd<64>, dim3(sc.rp / 16), dim3(256), 0, g->stream, fa); break;
+                    case 256: GLAUNCH(k_graph_fm_bwd<256>, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
+                    default: GLAUNCH(k_graph_feat_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
+                }
             }
             if (g->has_lin && !g->defer_w)
                 launch_lin_domain_grad(g->stream, g->dlogit, g->domrow, sc.rows, g->params + g->lin_d_off, 2.0f * g->cfg.l2_linear,
@@ -2836,13 +2945,13 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
         }
         if (g->defer_w) {       // every layer's dW / db of this step, the narrow contractions, the domain table's gradient:
             const bool lin = g->single && g->has_lin;
-            const DomainGradJob dg{g->dact, g->ld, 2 * EMB, g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb,
-                                   g->G(g->dm_off), g->cfg.n_domain, g->dlogit, lin ? g->params + g->lin_d_off : nullptr,
+            const DomainGradJob dg{g->dact, g->ld, 2 * g->emb, g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb,
+                                   g->G(g->dm_off), g->cfg.n_domain, g->emb, g->dlogit, lin ? g->params + g->lin_d_off : nullptr,
                                    2.0f * g->cfg.l2_linear, lin ? g->G(g->lin_d_off) : nullptr};      // one pair of launches
             flush_wgrads(g, &dg);
         } else {
-            GLAUNCH(k_graph_domain_grad, dim3(EMB / CS_COLS, g->cfg.n_domain), dim3(256), 0, g->stream, g->dact, g->ld, 2 * EMB,
-                    g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb, g->G(g->dm_off));
+            GLAUNCH(k_graph_domain_grad, dim3(g->emb / CS_COLS, g->cfg.n_domain), dim3(256), 0, g->stream, g->dact, g->ld, 2 * g->emb,
+                    g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb, g->G(g->dm_off), g->emb);
         }
         if (g->tables) {
             // TF1's dense step over both tables: g = 2 l2 p + scatter-add of d x[:, user | item columns]
@@ -2873,7 +2982,7 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
             ea.t[1].map = g->map_i;
             ea.t[1].gbuf = g->gbuf_i;
             ea.t[1].hasdup = g->hasdup_i;
-            ea.t[1].dx_off = EMB;
+            ea.t[1].dx_off = g->emb;
             if (g->has_lin) {       // their 1-d linear tables: scatter-add of d loss / d logit, same rule
                 ea.two_l2_lin = 2.0f * g->cfg.l2_linear;
                 ea.t[0].lin_p = g->params + g->lin_u_off;
@@ -2885,8 +2994,8 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
                 ea.t[1].lin_v = g->adam_v + g->lin_i_off;
                 ea.t[1].glin = g->glin_i;
             }
-            launch_emb_reduce(ea, g->stream);
-            launch_emb_sweep(ea, g->stream);
+            launch_emb_reduce(ea, g->stream, g->emb);
+            launch_emb_sweep(ea, g->stream, g->emb);
             if (g->has_lin) launch_lin_sweep(ea, g->stream);      // (reads the row maps, then resets them)
         }
         // ---- optimiser on the two ranges this task's model trains (one launch; none when the tail launch stepped them)
@@ -2947,7 +3056,7 @@ int mamdr_graph_eval_domain(mamdr_graph* g, int domain, int split, int32_t batch
         sc.keep_scale = 1.0f;
         GatherArgs ga;
         fill_gather(g, *d, nullptr, row_base, sc, ga);
-        GLAUNCH(k_graph_gather, dim3(sc.rp / 4), dim3(256), 0, g->stream, ga);
+        launch_graph_gather(ga, g->emb, g->stream);
         const int t_col = task_forward(g, t, sc);
         HeadArgs ha;
         memset(&ha, 0, sizeof(ha));
@@ -2970,7 +3079,7 @@ int mamdr_graph_eval_domain(mamdr_graph* g, int domain, int split, int32_t batch
         ha.pred_out = d_pred_out ? d_pred_out + row_base : nullptr;
         GLAUNCH(k_graph_head, dim3(sc.rp / 4), dim3(256), 0, g->stream, ha);
         GLAUNCH(k_graph_loss, dim3(1), dim3(256), 0, g->stream, g->rowloss, sc.rows, g->params + g->dm_off,
-                           g->cfg.n_domain * EMB, g->cfg.l2_emb, g->frozen_sumsq, g->eval_acc, 1,
+                           g->cfg.n_domain * g->emb, g->cfg.l2_emb, g->frozen_sumsq, g->eval_acc, 1,
                            g->extra ? g->params + g->lin_d_off : nullptr, g->cfg.n_domain, g->cfg.l2_linear);
     }
     GLAUNCH(k_graph_scale, dim3(1), dim3(1), 0, g->stream, g->eval_acc, 1.0f / (float)n_batches);

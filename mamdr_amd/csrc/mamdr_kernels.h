@@ -698,8 +698,8 @@ void launch_wgrad_reduce(const WgradArgs& a, const EmbStepArgs& e, const EmbRows
 void launch_update_lin(const UpdateArgs& a, const EmbStepArgs& e, bool lin, const EmbStepArgs* next_catchup, hipStream_t s);
 void launch_emb_catchup(const EmbStepArgs& a, hipStream_t s);     // rows of the batch -> current at t_now - 1
 void launch_emb_flush(const EmbStepArgs& a, hipStream_t s);       // every row -> current at t_now
-void launch_emb_reduce(const EmbStepArgs& a, hipStream_t s);
-void launch_emb_sweep(const EmbStepArgs& a, hipStream_t s);
+void launch_emb_reduce(const EmbStepArgs& a, hipStream_t s, int emb = EMB);     // emb: row width (generic-layer engine: 32 / 64 / 128 / 256)
+void launch_emb_sweep(const EmbStepArgs& a, hipStream_t s, int emb = EMB);
 void launch_lin_sweep(const EmbStepArgs& a, hipStream_t s);
 void launch_emb_map_init(int32_t* map, int64_t n, hipStream_t s);
 

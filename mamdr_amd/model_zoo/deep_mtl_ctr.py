@@ -15,7 +15,7 @@ import random
 import numpy as np
 
 from .base_model import BaseModel
-from .deepctr import glorot_normal
+from .deepctr import check_emb_width, glorot_normal
 
 KINDS = ("shared_bottom", "mmoe", "ple")
 
@@ -88,6 +88,7 @@ class DeepMTLCTR(BaseModel):
             raise NotImplementedError("ple with num_levels = %r: the reference's configs all use one level" % mc.get("num_levels"))
         factory = self.engine_factory
         if factory is None:
+            check_emb_width(kind, mc["user_dim"], False)
             from ..graph_engine import GraphEngine
             factory = GraphEngine
         self.tables_trainable = bool(tc["emb_trainable"]) or not bool(tc["load_pretrain_emb"])

@@ -20,6 +20,21 @@ import numpy as np
 from .base_model import BaseModel
 
 GRAPH_TOWERS = ("nfm", "pnn", "ccpm", "autoint")
+# embedding widths (user_dim == item_dim == domain_dim) of the mlp / wdl / deepfm towers: the step kernels are built for
+# 128, the generic-layer engine's gather / FM / table kernels for these (mamdr_graph_create checks the same set)
+EMB_WIDTHS = (32, 64, 128, 256)
+
+
+def check_emb_width(tower, emb_dim, any_width):
+    """the width limit of a tower that runs on a HIP engine: NotImplementedError for a tower whose kernels know 128 only,
+    ValueError for a width outside EMB_WIDTHS."""
+    if emb_dim == 128:
+        return
+    if not any_width:
+        raise NotImplementedError("user_dim %r: the '%s' tower is built for 128-wide embeddings only (mlp / wdl / deepfm "
+                                  "take user_dim in %r)" % (emb_dim, tower, EMB_WIDTHS))
+    if emb_dim not in EMB_WIDTHS:
+        raise ValueError("user_dim %r: the '%s' tower takes an embedding width in %r" % (emb_dim, tower, EMB_WIDTHS))
 
 
 def glorot_normal(rs, fan_in, fan_out, shape):
@@ -93,8 +108,18 @@ class DeepCTR(BaseModel):
         if tower == "star" and n_hidden != 3:
             raise ValueError("hidden_dim %r: the Star tower's kernels are built for three hidden layers (the reference's "
                              "configs all have [256, 128, 64])" % (mc["hidden_dim"],))
-        self.graph_dnn = (tower not in GRAPH_TOWERS and tower != "star" and tuple(mc["hidden_dim"]) != (256, 128, 64))
+        # ... and so does a user_dim other than the reference configs' 128 (deepctr.py:95-102 hands the three dims to
+        # SparseFeat(embedding_dim=...)), whatever hidden_dim is: the generic-layer engine takes the widths of EMB_WIDTHS
+        plain = tower not in GRAPH_TOWERS and tower != "star"
+        self.graph_dnn = plain and (tuple(mc["hidden_dim"]) != (256, 128, 64) or mc["user_dim"] != 128)
+        if tc["load_pretrain_emb"]:
+            for what, table in (("user", self.dataset.user_emb), ("item", self.dataset.item_emb)):
+                if table is not None and table.shape[1] != mc["user_dim"]:
+                    raise ValueError("the pretrained %s table is %d wide, model.user_dim says %d (synthetic data: "
+                                     "dataset.synthetic_emb_dim)" % (what, table.shape[1], mc["user_dim"]))
         factory = self.engine_factory
+        if factory is None:           # (an injected factory -- the tests' CPU stand-in -- takes any width)
+            check_emb_width(tower, mc["user_dim"], plain)
         # PNN and NFM on the step kernels (round 4: MAMDR_TOWER_PNN = the mlp tower + the inner products' three rows of the
         # first kernel; MAMDR_TOWER_NFM = WDL's linear tables + the DNN on the bi-interaction in the domain field's place;
         # both on k_tower4's FM instances): batches of up to 2,048 rows and hidden_dim [256, 128, 64] -- every reference

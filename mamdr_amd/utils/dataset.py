@@ -97,9 +97,11 @@ class MultiDomainDataset(object):
         if conf.get("synthetic"):
             # (synthetic_seed: the generated logs' own seed, so that runs with different `seed` -- planner, shuffles,
             # initial tensors -- can share one data set; default: the run's seed)
+            # (synthetic_emb_dim: width of the generated "pretrained" tables = model.user_dim of the run; default 128)
             self._from_generated(synthetic.generate(conf["synthetic"], batch_size=self.batch_size,
                                                     seed=int(conf.get("synthetic_seed", self.seed)),
-                                                    scale=float(conf.get("synthetic_scale", 1.0))))
+                                                    scale=float(conf.get("synthetic_scale", 1.0)),
+                                                    emb_dim=int(conf.get("synthetic_emb_dim", 128))))
         else:
             self._from_files()
         print("Found {} domain, in: {}".format(self.n_domain, self.domain_split_path))

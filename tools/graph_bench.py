@@ -1,9 +1,10 @@
 """Throughput of the generic-layer engine (csrc/graph_engine.hip) on the reference's Taobao-10 multi-task configurations
 and on the deepctr single-output towers it hosts: domain-steps/s of the alternate training loop (deep_mtl_ctr.py:69-96 /
 deepctr.py:63-93: one full pass per domain per epoch), synthetic Taobao-10 logs, batch 1024, inputs resident in HBM.
-usage: python tools/graph_bench.py [epochs [tower,tower...|all [inproc]]]    -> one JSON line per tower
+usage: python tools/graph_bench.py [epochs [tower,tower...|all [inproc|- [emb_dim [hidden]]]]]    -> one JSON line per tower
 (`inproc`: every tower in THIS process -- what a profiler needs, which must not see a process that has initialised the GPU
-start another program)"""
+start another program; emb_dim: user_dim = item_dim = domain_dim of the run and the width of the generated tables, for
+the towers that take one -- mlp / wdl / deepfm, named explicitly, e.g. `3 mlp - 64 128x64`; hidden: hidden_dim as AxBxC)"""
 import json
 import os
 import sys
@@ -20,6 +21,8 @@ from mamdr_amd.utils import MultiDomainDataset  # noqa: E402
 EPOCHS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 ONLY = sys.argv[2].split(",") if len(sys.argv) > 2 and sys.argv[2] != "all" else None
 INPROC = len(sys.argv) > 3 and sys.argv[3] == "inproc"
+EMB_DIM = int(sys.argv[4]) if len(sys.argv) > 4 else None
+HIDDEN = [int(h) for h in sys.argv[5].split("x")] if len(sys.argv) > 5 else None
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -49,10 +52,11 @@ if not INPROC and (ONLY is None or len(ONLY) > 1):
     import subprocess
     for name in TOWERS:
         if ONLY is None or name in ONLY:
-            subprocess.run([sys.executable, os.path.abspath(__file__), str(EPOCHS), name], check=False)
+            subprocess.run([sys.executable, os.path.abspath(__file__), str(EPOCHS), name, "-"] + sys.argv[4:], check=False)
     sys.exit(0)
 
-for cfg_name in TOWERS:
+# (mlp / wdl / deepfm run here when named: on this engine with a width or a hidden_dim the step kernels are not built for)
+for cfg_name in TOWERS + tuple(n for n in (ONLY or ()) if n not in TOWERS):
     if ONLY is not None and cfg_name not in ONLY:
         continue
     path = os.path.join(ROOT, "config", "Taobao-10", cfg_name + ".json")
@@ -62,6 +66,11 @@ for cfg_name in TOWERS:
         cfg = json.load(open(os.path.join(ROOT, "config", "Taobao-10", "deepctr_taobao_10.json")))
         cfg["model"]["name"] = cfg_name
     cfg["train"].update(result_save_path="/tmp/graph_bench/result", checkpoint_path="/tmp/graph_bench/ckpt")
+    if EMB_DIM is not None:
+        cfg["model"].update(user_dim=EMB_DIM, item_dim=EMB_DIM, domain_dim=EMB_DIM)
+        cfg["dataset"]["synthetic_emb_dim"] = EMB_DIM
+    if HIDDEN is not None:
+        cfg["model"]["hidden_dim"] = HIDDEN
     ds = MultiDomainDataset(cfg["dataset"])
     if os.environ.get("MAMDR_GRAPH_DIAG_REPLAY"):      # stream capture needs a stream of its own (not the legacy default one)
         torch.cuda.set_stream(torch.cuda.Stream())
@@ -100,5 +109,6 @@ for cfg_name in TOWERS:
                       "value": steps_per_epoch * EPOCHS / dt, "unit": "domain-steps/s",
                       "us_per_domain_step": dt / (steps_per_epoch * EPOCHS) * 1e6, "batch": ds.batch_size, "roofline": roofline,
                       "params": int(eng.n_params), "params_on_a_step_path": int(n_path) or int(eng.n_params),
+                      "emb_dim": cfg["model"]["user_dim"],
                       "model": {k: cfg["model"][k] for k in cfg["model"] if "hidden" in k or "expert" in k}}))
     eng.close()

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define MAMDR_ABI_VERSION 18
+#define MAMDR_ABI_VERSION 19
 
 enum {
     MAMDR_OK = 0,
@@ -380,7 +380,15 @@ enum { MAMDR_GRAPH_SHARED_BOTTOM = 0,   /* deep_mtl_ctr.py:25-30  models.SharedB
         * Flat layout = oracle/tower.param_names: [tables | 1-d linear tables] domain_emb | W0.. | b0.. | wo | gb | lin_domain */
        MAMDR_GRAPH_MLP = 7,             /* deepctr.py:118-136 build_mlp: DNN(x) -> Dense(1) -> sigmoid */
        MAMDR_GRAPH_WDL = 8,             /* deepctr.py:29-32  models.WDL: linear tables + DNN(x) */
-       MAMDR_GRAPH_DEEPFM = 9 };        /* deepctr.py:36-38  models.DeepFM: linear tables + FM second-order term + DNN(x) */
+       MAMDR_GRAPH_DEEPFM = 9,          /* deepctr.py:36-38  models.DeepFM: linear tables + FM second-order term + DNN(x) */
+       /* model_zoo/Star/star.py:70-96 as a family (ABI 19): norm none / PartitionedNorm / BatchNormalization (star_norm), plain
+        * Dense or StarFCN hidden layers (star_dense), the auxiliary network (auxiliary_dim), hidden_dim of 1..4 layers in
+        * expert_hidden; 128-wide embeddings only.  No dropout and no regularisers (dropout, l2_emb, l2_linear are ignored).  The
+        * per-domain tensors are read at d = the domain id of the batch's FIRST row; the other domains' slices take a zero
+        * gradient and still the Adam step.  Flat layout: [user_emb item_emb if trainable] domain_emb | Ws0.. bs0.. (dense: W0..
+        * b0..) | pn_gamma_shared pn_beta_shared pn_gamma_spec pn_beta_spec (bn: bn_gamma bn_beta) | Wd0.. bd0.. | wo gb | aux_W
+        * aux_b.  The norm layer's moving statistics live outside the flat vector: mamdr_graph_aux_count / mamdr_graph_bind_aux */
+       MAMDR_GRAPH_STAR = 10 };
 typedef struct mamdr_graph mamdr_graph;
 typedef struct mamdr_graph_config {
     int32_t abi_version;        /* MAMDR_ABI_VERSION */
@@ -398,6 +406,10 @@ typedef struct mamdr_graph_config {
     int32_t uncertainty_weight;                          /* single-output towers: the weighted loss of uncertainty_weight/
                                                           * weighted_loss.py:30-43 (one trainable `log_var` per domain, last
                                                           * tensor of the flat vector); evaluation stays unweighted */
+    /* MAMDR_GRAPH_STAR only (ABI 19; ignored by every other kind) */
+    int32_t star_norm;          /* 0 none, 1 pn (PartitionedNorm), 2 bn (Keras BatchNormalization, momentum 0.99, eps 1e-3) */
+    int32_t star_dense;         /* 0 dense (plain kernels), 1 star (StarFCN: shared (.) specific[d]) */
+    int32_t auxiliary_dim;      /* 0: no auxiliary network; otherwise = the last hidden width (MAMDR_EINVAL if not) */
 } mamdr_graph_config;
 const char* mamdr_graph_last_error(void);
 int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph** out);   /* build_model, deep_mtl_ctr.py:21-67 */
@@ -418,6 +430,12 @@ int mamdr_graph_optimizer_reset(mamdr_graph* g);
  * (epsilon = K.epsilon() = 1e-7) where the shared optimiser of :53-56 is tf.train.AdamOptimizer (1e-8) */
 int mamdr_graph_set_adam_eps(mamdr_graph* g, float eps);
 int64_t mamdr_graph_optimizer_steps(const mamdr_graph* g);
+/* MAMDR_GRAPH_STAR: floats of non-trainable state and the device buffer that holds them (as mamdr_aux_count / mamdr_bind_aux).
+ * pn: [mov_mean | mov_var | biased_mean | biased_var] each [D][384], then steps [D], padded to 4 floats -- the step engine's
+ * layout; bn: [mov_mean | mov_var] each [384] (initial zeros / ones; updated without zero-debias); none: count 0.  A step or
+ * an evaluation before the buffer is bound: MAMDR_ESTATE, nothing launched. */
+int64_t mamdr_graph_aux_count(const mamdr_graph* g);
+int mamdr_graph_bind_aux(mamdr_graph* g, float* d_aux);
 /* kernel launches this process has issued through mamdr_graph_* calls so far (measurement: launches per step) */
 int64_t mamdr_graph_launch_count(void);
 int64_t mamdr_graph_dropout_steps(const mamdr_graph* g);

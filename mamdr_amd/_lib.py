@@ -9,7 +9,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MAMDR_LIB_PATH") or os.path.join(HERE, "libmamdr_hip.so")      # (MAMDR_LIB_PATH: A/B of diagnostic builds, tools/build_variant.sh)
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 OK, EINVAL, ESTATE, EHIP, ENOTBUILT = 0, -1, -2, -3, -4
 TOWER_MLP, TOWER_DEEPFM, TOWER_STAR, TOWER_WDL, TOWER_PNN, TOWER_NFM = 0, 1, 2, 3, 4, 5
 SPLIT_TRAIN, SPLIT_VAL, SPLIT_TEST = 0, 1, 2
@@ -51,6 +51,9 @@ class Config(C.Structure):
 
 GRAPH_SHARED_BOTTOM, GRAPH_MMOE, GRAPH_PLE, GRAPH_NFM, GRAPH_PNN, GRAPH_CCPM, GRAPH_AUTOINT = 0, 1, 2, 3, 4, 5, 6
 GRAPH_MLP, GRAPH_WDL, GRAPH_DEEPFM = 7, 8, 9       # the step kernels' towers with any hidden_dim of 1..4 layers
+GRAPH_STAR = 10                                    # star.py:70-96: norm none / pn / bn, dense / star, auxiliary network
+STAR_NORMS = {"none": 0, "pn": 1, "bn": 2}
+STAR_DENSES = {"dense": 0, "star": 1}
 
 
 class GraphConfig(C.Structure):
@@ -63,6 +66,7 @@ class GraphConfig(C.Structure):
         ("num_experts", C.c_int32), ("shared_expert_num", C.c_int32), ("specific_expert_num", C.c_int32),
         ("dropout", C.c_float), ("l2_emb", C.c_float), ("adam_beta1", C.c_float), ("adam_beta2", C.c_float),
         ("adam_eps", C.c_float), ("l2_linear", C.c_float), ("uncertainty_weight", C.c_int32),
+        ("star_norm", C.c_int32), ("star_dense", C.c_int32), ("auxiliary_dim", C.c_int32),      # GRAPH_STAR only
     ]
 
 
@@ -128,6 +132,8 @@ SIGNATURES = {
     "mamdr_graph_bind_state": (C.c_int, [_VP, _VP, _VP, _VP]),
     "mamdr_graph_optimizer_reset": (C.c_int, [_VP]),
     "mamdr_graph_set_adam_eps": (C.c_int, [_VP, _F]),
+    "mamdr_graph_aux_count": (_I64, [_VP]),
+    "mamdr_graph_bind_aux": (C.c_int, [_VP, _VP]),
     "mamdr_graph_launch_count": (_I64, []),
     "mamdr_graph_optimizer_steps": (_I64, [_VP]),
     "mamdr_graph_dropout_steps": (_I64, [_VP]),

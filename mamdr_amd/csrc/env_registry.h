@@ -47,6 +47,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_PASS_WINDOW_ROWS", "host", "row budget of a pass window"},
     {"MAMDR_PNN_ENGINE", "host", "graph: PNN on the generic-layer engine (default: step kernels)"},
     {"MAMDR_NFM_ENGINE", "host", "graph: NFM on the generic-layer engine"},
+    {"MAMDR_STAR_ENGINE", "host", "graph: Star's PartitionedNorm + StarFCN form on the generic-layer engine (default: step kernels)"},
     // ---- bench.py
     {"MAMDR_BENCH_*", "bench", "bench.py knobs: _BATCH _ROW_SCALE _DN_MODE _NO_PREFETCH _PREP_TIMING _PREWARM_S _SHARE_GPU _COMM_TIMEOUT _SKIP_<WORKLOAD>"},
     // ---- tools/ and tests/

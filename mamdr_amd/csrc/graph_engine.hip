@@ -40,6 +40,9 @@
 //   CCPM     Conv2D (6,1) -> max over the fields -> Conv2D (5,1) centre tap, tanh (k_graph_ccpm_fwd/bwd), DNN over 512 features
 //   AutoInt  3 x multi-head self-attention over the 3 field tokens on compact token-major buffers (projections as GEMMs
 //            over 3 B token rows, the 3 x 3 attention core in k_graph_att_fwd/bwd), beside the DNN; head over [96 | DNN]
+//   Star     star.py:70-96 as a family: norm none / PartitionedNorm / BatchNormalization over x (k_star_colstats, k_star_norm_fwd /
+//            _bwd), Dense or StarFCN layers on the kernels of the batch's first-row domain (k_star_eff, k_star_chain), the auxiliary
+//            network joined at the head (k_star_join_fwd / _bwd); moving statistics outside the flat vector (mamdr_graph_bind_aux)
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -1505,6 +1508,272 @@ __global__ __launch_bounds__(256) void k_graph_adam(const AdamArgs a) {
     if (a.optimizer == MAMDR_OPT_ADAM) reinterpret_cast<f32x4*>(a.v)[i] = v;
 }
 
+// ------------------------------------------------------------------ Star forms (MAMDR_GRAPH_STAR)
+// model_zoo/Star/star.py:70-96 as a family: norm none / PartitionedNorm / BatchNormalization, Dense / StarFCN hidden layers,
+// the auxiliary network.  Everything per-domain is selected by d = the domain id of the batch's FIRST row, read on the
+// device (partitioned_norm.py:136, star_fcn.py:112, auxiliary_net.py:100).  The contractions are the engine's own; here:
+//   k_star_colstats<false>  per-chunk sum x / sum x^2 of the 384 input columns, double partials          (forward)
+//   k_star_norm_fwd         the partials summed in chunk order, batch moments, x -> xn, the moving statistics' update of the
+//                           right flavour (PN: domain d's pair, zero-debiased; BN: one pair, plain); evaluation: moving statistics
+//   k_star_colstats<true>   per-chunk sum dxn / sum dxn x^                                                 (backward)
+//   k_star_norm_bwd         s1, s2 finished in chunk order, dx, the norm's parameter gradients (zeros for the other domains)
+//   k_star_eff              the step's effective tensors into scratch: Ws (.) Wd[d], bs + bd[d], aux_W[d], aux_b[d]
+//   k_star_chain            scratch gradients dK / db -> g(Ws), g(Wd[d]), g(bs), g(bd[d]), g(aux_W[d]), g(aux_b[d]), zeros elsewhere
+//   k_star_join_fwd / bwd   top = h_n + a; d top through both relu gates
+// BatchNormalization's moving-average rule is restated from Keras' `_assign_moving_average` of TF 1.12 (no zero-debias) and,
+// like every inner-step statement of this project, is PARITY UNPINNED against TF itself.
+constexpr int SN_ROWS = 128;            // batch rows per chunk of a column reduction
+constexpr int SN_VEC = XDIM / 4;        // float4 columns of a row (96); a block = 96 x 4 row lanes
+constexpr float BN_DECAY = 0.01f;       // float32(1.0 - 0.99): Keras hands `1.0 - momentum` over as a Python float
+struct StarNormArgs {
+    const float* x; float* xn; int ld;          // raw input columns / normalised columns of the activation workspace
+    const float* dxn; float* dx;                // their gradients
+    int rows, rows_pad, n_chunks, n_domain;
+    int norm, train;                            // 1 pn, 2 bn
+    const int32_t* domrow;
+    double* part;                               // [n_chunks][2][384]
+    float* pnv;                                 // this step's [mean | inv | gamma inv], 3 x 384
+    const float *gs, *bs, *gd, *bd;             // pn: shared / specific; bn: gs = gamma, bs = beta
+    float *g_gs, *g_bs, *g_gd, *g_bd;
+    float* aux;                                 // pn: [mov_mean | mov_var | biased_mean | biased_var] [D][384] each, steps [D]; bn: [mov_mean | mov_var] [384]
+};
+template <bool BWD>
+__global__ __launch_bounds__(XDIM) void k_star_colstats(const StarNormArgs a) {
+    __shared__ double sh[4][2][XDIM];
+    const int tid = threadIdx.x, v = tid % SN_VEC, rl = tid / SN_VEC;
+    const int r0 = blockIdx.x * SN_ROWS, r1 = min(r0 + SN_ROWS, a.rows);
+    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
+    f32x4 mean = {0.f, 0.f, 0.f, 0.f}, inv = mean;
+    if (BWD) {
+        mean = *reinterpret_cast<const f32x4*>(a.pnv + 4 * v);
+        inv = *reinterpret_cast<const f32x4*>(a.pnv + XDIM + 4 * v);
+    }
+    for (int r = r0 + rl; r < r1; r += 4) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + (size_t)r * a.ld + 4 * v);
+        if (BWD) {
+            const f32x4 gv = *reinterpret_cast<const f32x4*>(a.dxn + (size_t)r * a.ld + 4 * v);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float xh = __fmul_rn(__fsub_rn(xv[k], mean[k]), inv[k]);
+                s1[k] += (double)gv[k];
+                s2[k] += (double)__fmul_rn(gv[k], xh);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double xd = (double)xv[k];
+                s1[k] += xd;
+                s2[k] += xd * xd;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        sh[rl][0][4 * v + k] = s1[k];
+        sh[rl][1][4 * v + k] = s2[k];
+    }
+    __syncthreads();
+    double t1 = 0.0, t2 = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {       // row lanes in lane order: fixed
+        t1 += sh[q][0][tid];
+        t2 += sh[q][1][tid];
+    }
+    a.part[(size_t)blockIdx.x * 2 * XDIM + tid] = t1;
+    a.part[(size_t)blockIdx.x * 2 * XDIM + XDIM + tid] = t2;
+}
+// every block sums the chunks' partials itself (chunk order: the same bits in every block), block 0 keeps the results
+__global__ __launch_bounds__(XDIM) void k_star_norm_fwd(const StarNormArgs a) {
+    __shared__ __attribute__((aligned(16))) float sh_scale[XDIM], sh_shift[XDIM];
+    const int c = threadIdx.x, d = a.domrow[0];
+    const bool pn = a.norm == 1, keep = blockIdx.x == 0;
+    const size_t o = pn ? (size_t)d * XDIM + c : (size_t)c;
+    const size_t dx = pn ? (size_t)a.n_domain * XDIM : (size_t)XDIM;       // floats per statistic
+    float mean, var;
+    if (a.train) {
+        double S1 = 0.0, S2 = 0.0;
+        for (int ch = 0; ch < a.n_chunks; ++ch) {
+            S1 += a.part[(size_t)ch * 2 * XDIM + c];
+            S2 += a.part[(size_t)ch * 2 * XDIM + XDIM + c];
+        }
+        // nn.moments: mean, then the population variance about that fp32 mean -- E[x^2] - 2 mean E[x] + mean^2 in double
+        const double B = (double)a.rows, mu = S1 / B;
+        mean = (float)mu;
+        const double mf = (double)mean, vd = S2 / B - 2.0 * mf * mu + mf * mf;
+        var = (float)(vd > 0.0 ? vd : 0.0);
+        if (keep && pn) {
+            // assign_moving_average(zero_debias=True): biased += (value - biased)(1 - momentum); moving = biased / (1 - momentum^step)
+            const float t_step = a.aux[4 * dx + d] + 1.0f;
+            const float factor = 1.0f - powf(PN_MOMENTUM, t_step), omm = 1.0f - PN_MOMENTUM;
+            float bm = a.aux[2 * dx + o], bv = a.aux[3 * dx + o];
+            bm += (mean - bm) * omm;
+            bv += (var - bv) * omm;
+            a.aux[2 * dx + o] = bm;
+            a.aux[3 * dx + o] = bv;
+            a.aux[o] = bm / factor;
+            a.aux[dx + o] = bv / factor;
+            __syncthreads();            // (every thread of the block has read the old step)
+            if (c == 0) a.aux[4 * dx + d] = t_step;
+        } else if (keep) {
+            // Keras BatchNormalization._assign_moving_average (TF 1.12): moving -= (moving - value)(1 - momentum)
+            const float mm = a.aux[o], mv = a.aux[dx + o];
+            a.aux[o] = __fsub_rn(mm, __fmul_rn(__fsub_rn(mm, mean), BN_DECAY));
+            a.aux[dx + o] = __fsub_rn(mv, __fmul_rn(__fsub_rn(mv, var), BN_DECAY));
+        }
+    } else {
+        mean = a.aux[o];
+        var = a.aux[dx + o];
+    }
+    const float inv = 1.0f / sqrtf(var + PN_EPS);
+    const float gamma = pn ? a.gs[c] * a.gd[(size_t)d * XDIM + c] : a.gs[c];
+    const float beta = pn ? a.bs[c] + a.bd[(size_t)d * XDIM + c] : a.bs[c];
+    const float scale = __fmul_rn(inv, gamma);
+    sh_scale[c] = scale;
+    sh_shift[c] = __fsub_rn(beta, __fmul_rn(mean, scale));
+    if (keep && a.train) {
+        a.pnv[c] = mean;
+        a.pnv[XDIM + c] = inv;
+        a.pnv[2 * XDIM + c] = __fmul_rn(gamma, inv);
+    }
+    __syncthreads();
+    const int v = c % SN_VEC, rl = c / SN_VEC;
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(sh_scale + 4 * v), sf = *reinterpret_cast<const f32x4*>(sh_shift + 4 * v);
+    const int r0 = blockIdx.x * SN_ROWS, r1 = min(r0 + SN_ROWS, a.rows_pad);
+    for (int r = r0 + rl; r < r1; r += 4) {
+        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + (size_t)r * a.ld + 4 * v);
+        f32x4 y;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = __fadd_rn(__fmul_rn(xv[k], sc[k]), sf[k]);
+        *reinterpret_cast<f32x4*>(a.xn + (size_t)r * a.ld + 4 * v) = y;
+    }
+}
+// s1 = sum dxn, s2 = sum dxn x^ (chunk order); dx = gamma inv (dxn - s1 / B - x^ s2 / B); block 0: the parameter gradients
+__global__ __launch_bounds__(XDIM) void k_star_norm_bwd(const StarNormArgs a) {
+    __shared__ __attribute__((aligned(16))) float sh_t1[XDIM], sh_t2[XDIM];
+    const int c = threadIdx.x, d = a.domrow[0];
+    double S1 = 0.0, S2 = 0.0;
+    for (int ch = 0; ch < a.n_chunks; ++ch) {
+        S1 += a.part[(size_t)ch * 2 * XDIM + c];
+        S2 += a.part[(size_t)ch * 2 * XDIM + XDIM + c];
+    }
+    const float s1 = (float)S1, s2 = (float)S2, B = (float)a.rows;
+    sh_t1[c] = __fdiv_rn(s1, B);
+    sh_t2[c] = __fdiv_rn(s2, B);
+    if (blockIdx.x == 0) {
+        if (a.norm == 1) {
+            a.g_bs[c] = s1;
+            a.g_gs[c] = __fmul_rn(s2, a.gd[(size_t)d * XDIM + c]);
+            const float gg = __fmul_rn(s2, a.gs[c]);
+            for (int j = 0; j < a.n_domain; ++j) {
+                a.g_gd[(size_t)j * XDIM + c] = j == d ? gg : 0.f;
+                a.g_bd[(size_t)j * XDIM + c] = j == d ? s1 : 0.f;
+            }
+        } else {
+            a.g_bs[c] = s1;
+            a.g_gs[c] = s2;
+        }
+    }
+    __syncthreads();
+    const int v = c % SN_VEC, rl = c / SN_VEC;
+    const f32x4 t1 = *reinterpret_cast<const f32x4*>(sh_t1 + 4 * v), t2 = *reinterpret_cast<const f32x4*>(sh_t2 + 4 * v);
+    const f32x4 mean = *reinterpret_cast<const f32x4*>(a.pnv + 4 * v), inv = *reinterpret_cast<const f32x4*>(a.pnv + XDIM + 4 * v);
+    const f32x4 coef = *reinterpret_cast<const f32x4*>(a.pnv + 2 * XDIM + 4 * v);
+    const int r0 = blockIdx.x * SN_ROWS, r1 = min(r0 + SN_ROWS, a.rows_pad);
+    for (int r = r0 + rl; r < r1; r += 4) {
+        f32x4 y = {0.f, 0.f, 0.f, 0.f};
+        if (r < a.rows) {
+            const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + (size_t)r * a.ld + 4 * v);
+            const f32x4 gv = *reinterpret_cast<const f32x4*>(a.dxn + (size_t)r * a.ld + 4 * v);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float xh = __fmul_rn(__fsub_rn(xv[k], mean[k]), inv[k]);
+                y[k] = __fmul_rn(coef[k], __fsub_rn(__fsub_rn(gv[k], t1[k]), __fmul_rn(xh, t2[k])));
+            }
+        }
+        *reinterpret_cast<f32x4*>(a.dx + (size_t)r * a.ld + 4 * v) = y;
+    }
+}
+// the per-domain tensors of a step: segment s of the scratch block = op(shared tensor, slice d of the specific tensor)
+constexpr int MAX_SSEG = 10;            // 4 layers x (kernel, bias) + the auxiliary network's pair
+enum { SSEG_MUL = 0, SSEG_ADD = 1, SSEG_COPY = 2 };
+struct StarTab {
+    int n;
+    int first4[MAX_SSEG + 1];           // first float4 of segment s in the scratch block
+    int64_t shared[MAX_SSEG], spec[MAX_SSEG];       // flat-vector offsets (shared unused for SSEG_COPY)
+    int cnt[MAX_SSEG], op[MAX_SSEG];    // floats per slice
+};
+__global__ __launch_bounds__(256) void k_star_eff(const StarTab t, const float* params, const int32_t* domrow, float* eff) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.first4[t.n]) return;
+    int s = 0;
+    while (s + 1 < t.n && i >= t.first4[s + 1]) ++s;
+    const int e = 4 * (i - t.first4[s]), d = domrow[0];
+    const f32x4 sp = *reinterpret_cast<const f32x4*>(params + t.spec[s] + (size_t)d * t.cnt[s] + e);
+    f32x4 out = sp;
+    if (t.op[s] != SSEG_COPY) {
+        const f32x4 sh = *reinterpret_cast<const f32x4*>(params + t.shared[s] + e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[k] = t.op[s] == SSEG_MUL ? __fmul_rn(sh[k], sp[k]) : __fadd_rn(sh[k], sp[k]);
+    }
+    *reinterpret_cast<f32x4*>(eff + 4 * (size_t)i) = out;
+}
+// gbase is addressed like the flat vector (gradient of element `off` at gbase + off)
+__global__ __launch_bounds__(256) void k_star_chain(const StarTab t, const float* params, const int32_t* domrow, const float* deff,
+                                                    float* gbase, int n_domain) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= t.first4[t.n]) return;
+    int s = 0;
+    while (s + 1 < t.n && i >= t.first4[s + 1]) ++s;
+    const int e = 4 * (i - t.first4[s]), d = domrow[0];
+    const f32x4 dk = *reinterpret_cast<const f32x4*>(deff + 4 * (size_t)i);
+    f32x4 gd = dk;
+    if (t.op[s] == SSEG_MUL) {
+        const f32x4 ws = *reinterpret_cast<const f32x4*>(params + t.shared[s] + e);
+        const f32x4 wd = *reinterpret_cast<const f32x4*>(params + t.spec[s] + (size_t)d * t.cnt[s] + e);
+        f32x4 gs;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            gs[k] = __fmul_rn(dk[k], wd[k]);
+            gd[k] = __fmul_rn(dk[k], ws[k]);
+        }
+        *reinterpret_cast<f32x4*>(gbase + t.shared[s] + e) = gs;
+    } else if (t.op[s] == SSEG_ADD) {
+        *reinterpret_cast<f32x4*>(gbase + t.shared[s] + e) = dk;
+    }
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < n_domain; ++j)
+        *reinterpret_cast<f32x4*>(gbase + t.spec[s] + (size_t)j * t.cnt[s] + e) = j == d ? gd : zero;
+}
+// the auxiliary branch's join (star.py:92-93): top = h_n + a; backward: d top through the relu of each summand
+__global__ __launch_bounds__(256) void k_star_join_fwd(float* act, int ld, int h_col, int a_col, int top_col, int n, int rows_pad) {
+    const int i = blockIdx.x * 256 + threadIdx.x, n4 = n / 4;
+    if (i >= rows_pad * n4) return;
+    float* row = act + (size_t)(i / n4) * ld;
+    const int c = 4 * (i % n4);
+    const f32x4 h = *reinterpret_cast<const f32x4*>(row + h_col + c), av = *reinterpret_cast<const f32x4*>(row + a_col + c);
+    f32x4 y;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = __fadd_rn(h[k], av[k]);
+    *reinterpret_cast<f32x4*>(row + top_col + c) = y;
+}
+__global__ __launch_bounds__(256) void k_star_join_bwd(const float* act, float* dact, int ld, int h_col, int a_col, int top_col, int n,
+                                                       int rows_pad) {
+    const int i = blockIdx.x * 256 + threadIdx.x, n4 = n / 4;
+    if (i >= rows_pad * n4) return;
+    const size_t ro = (size_t)(i / n4) * ld;
+    const int c = 4 * (i % n4);
+    const f32x4 h = *reinterpret_cast<const f32x4*>(act + ro + h_col + c), av = *reinterpret_cast<const f32x4*>(act + ro + a_col + c);
+    const f32x4 dt = *reinterpret_cast<const f32x4*>(dact + ro + top_col + c);
+    f32x4 dh, da;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        dh[k] = h[k] > 0.f ? dt[k] : 0.f;
+        da[k] = av[k] > 0.f ? dt[k] : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(dact + ro + h_col + c) = dh;
+    *reinterpret_cast<f32x4*>(dact + ro + a_col + c) = da;
+}
+
 // ------------------------------------------------------------------ host side: structure of the tower
 struct Layer {
     int64_t w_off, b_off;
@@ -1566,6 +1835,18 @@ struct mamdr_graph {
     int64_t lv_off = -1;        // weighted loss: `log_var` [n_domain], the last tensor (-1: plain loss)
     int64_t lin_u_off = 0, lin_i_off = 0;       // ... of the user / item features (trainable tables only)
     float *extra = nullptr, *glin_u = nullptr, *glin_i = nullptr;
+    // Star forms (MAMDR_GRAPH_STAR): cfg.star_norm / star_dense / auxiliary_dim
+    bool star = false;
+    int xn_col = 0, a_col = 0, jtop_col = 0;       // normalised input (0 = x itself without a norm), auxiliary output, h_n + a
+    int64_t norm_off[4] = {0, 0, 0, 0};             // pn: gamma_shared beta_shared gamma_spec beta_spec; bn: gamma beta
+    StarTab stab;                                   // the step's effective tensors (k_star_eff / k_star_chain)
+    int seg_k[4] = {-1, -1, -1, -1}, seg_b[4] = {-1, -1, -1, -1}, seg_aw = -1, seg_ab = -1;     // their segments
+    float *eff = nullptr, *deff = nullptr, *pnv = nullptr;
+    double* spart = nullptr;
+    float* aux = nullptr;                           // moving statistics (mamdr_graph_bind_aux)
+    int64_t aux_count = 0;
+    float* E(int seg) const { return eff + 4 * (size_t)stab.first4[seg]; }
+    float* DE(int seg) const { return deff + 4 * (size_t)stab.first4[seg]; }
     // bound state
     float *params = nullptr, *adam_m = nullptr, *adam_v = nullptr;
     float* accum = nullptr;     // meta-gradient accumulator of MAMDR_OPT_ACCUMULATE steps (mamdr_graph_bind_accumulator)
@@ -2123,7 +2404,159 @@ void fill_ccpm(const mamdr_graph* g, const StepCtx& sc, CcpmArgs& ca) {
     ca.conv = g->params + g->conv_off;
 }
 
+// ---- Star forms: kernel / bias of hidden layer l as this step uses them (StarFCN: the scratch block of k_star_eff)
+const float* star_kernel(const mamdr_graph* g, const Layer& L, int l) { return g->seg_k[l] >= 0 ? g->E(g->seg_k[l]) : g->params + L.w_off; }
+const float* star_bias(const mamdr_graph* g, const Layer& L, int l) { return g->seg_b[l] >= 0 ? g->E(g->seg_b[l]) : g->params + L.b_off; }
+void fill_star_norm(const mamdr_graph* g, const StepCtx& sc, StarNormArgs& na) {
+    memset(&na, 0, sizeof(na));
+    na.x = g->act;
+    na.xn = g->act + g->xn_col;
+    na.ld = g->ld;
+    na.dxn = g->dact + g->xn_col;
+    na.dx = g->dact;
+    na.rows = sc.rows;
+    na.rows_pad = sc.rp;
+    na.n_chunks = (sc.rows + SN_ROWS - 1) / SN_ROWS;
+    na.n_domain = g->cfg.n_domain;
+    na.norm = g->cfg.star_norm;
+    na.train = sc.train ? 1 : 0;
+    na.domrow = g->domrow;
+    na.part = g->spart;
+    na.pnv = g->pnv;
+    na.gs = g->params + g->norm_off[0];
+    na.bs = g->params + g->norm_off[1];
+    na.g_gs = g->G(g->norm_off[0]);
+    na.g_bs = g->G(g->norm_off[1]);
+    if (g->cfg.star_norm == 1) {
+        na.gd = g->params + g->norm_off[2];
+        na.bd = g->params + g->norm_off[3];
+        na.g_gd = g->G(g->norm_off[2]);
+        na.g_bd = g->G(g->norm_off[3]);
+    }
+    na.aux = g->aux;
+}
+int star_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    const Dnn& d = g->dnns[t.tower];
+    const int A = g->cfg.auxiliary_dim;
+    if (g->stab.n)
+        GLAUNCH(k_star_eff, dim3((g->stab.first4[g->stab.n] + 255) / 256), dim3(256), 0, g->stream, g->stab, g->params, g->domrow,
+                g->eff);
+    if (g->cfg.star_norm) {
+        StarNormArgs na;
+        fill_star_norm(g, sc, na);
+        if (sc.train) GLAUNCH(k_star_colstats<false>, dim3(na.n_chunks), dim3(XDIM), 0, g->stream, na);
+        GLAUNCH(k_star_norm_fwd, dim3((sc.rp + SN_ROWS - 1) / SN_ROWS), dim3(XDIM), 0, g->stream, na);
+    }
+    GemmArgs a;
+    int src = g->xn_col;
+    for (size_t l = 0; l < d.layers.size(); ++l) {
+        const Layer& L = d.layers[l];
+        memset(&a, 0, sizeof(a));
+        a.A = g->act + src;
+        a.lda = g->ld;
+        a.B = star_kernel(g, L, (int)l);
+        a.ldb = L.out;
+        a.C = g->act + t.col[0][l];
+        a.ldc = g->ld;
+        a.K = L.in;
+        a.bias = star_bias(g, L, (int)l);
+        a.relu = 1;
+        a.keep_scale = 1.0f;
+        a.n_cols = L.out;
+        launch_gemm(0, a, sc.rp, L.out, g->stream);
+        src = t.col[0][l];
+    }
+    if (!A) return src;
+    memset(&a, 0, sizeof(a));       // a = relu(xn . aux_W[d] + aux_b[d]): the NORMALISED input (star.py:76-82)
+    a.A = g->act + g->xn_col;
+    a.lda = g->ld;
+    a.B = g->E(g->seg_aw);
+    a.ldb = A;
+    a.C = g->act + g->a_col;
+    a.ldc = g->ld;
+    a.K = XDIM;
+    a.bias = g->E(g->seg_ab);
+    a.relu = 1;
+    a.keep_scale = 1.0f;
+    a.n_cols = A;
+    launch_gemm(0, a, sc.rp, A, g->stream);
+    GLAUNCH(k_star_join_fwd, dim3((sc.rp * (A / 4) + 255) / 256), dim3(256), 0, g->stream, g->act, g->ld, src, g->a_col, g->jtop_col,
+            A, sc.rp);
+    return g->jtop_col;
+}
+// backward from the head's d top down to d x (the x columns of the gradient workspace); weight gradients are queued
+void star_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    const Dnn& d = g->dnns[t.tower];
+    const int A = g->cfg.auxiliary_dim, n = (int)d.layers.size();
+    if (A)
+        GLAUNCH(k_star_join_bwd, dim3((sc.rp * (A / 4) + 255) / 256), dim3(256), 0, g->stream, g->act, g->dact, g->ld,
+                t.col[0][n - 1], g->a_col, g->jtop_col, A, sc.rp);
+    // without a norm d xn IS d x: the domain columns alone matter while the tables are frozen
+    const bool part = !g->cfg.star_norm && !g->tables;
+    const int first = part ? 2 * EMB : 0, nx = part ? EMB : XDIM;
+    GemmArgs a;
+    for (int l = n - 1; l >= 0; --l) {
+        const Layer& L = d.layers[l];
+        const int src = l == 0 ? g->xn_col : t.col[0][l - 1];
+        const bool sf = g->seg_k[l] >= 0;
+        memset(&a, 0, sizeof(a));
+        a.A = g->act + src;             // dK = in^T dz, into scratch under StarFCN (k_star_chain splits it)
+        a.lda = g->ld;
+        a.B = g->dact + t.col[0][l];
+        a.ldb = g->ld;
+        a.C = sf ? g->DE(g->seg_k[l]) : g->G(L.w_off);
+        a.ldc = L.out;
+        launch_wgrad(g, a, L.in, L.out, sc.rp, g->dact + t.col[0][l], sf ? g->DE(g->seg_b[l]) : g->G(L.b_off));
+        memset(&a, 0, sizeof(a));
+        a.A = g->dact + t.col[0][l];    // d in = dz K^T
+        a.lda = g->ld;
+        a.K = L.out;
+        a.gate_scale = 1.0f;
+        a.ldb = L.out;
+        a.ldc = g->ld;
+        if (l > 0) {
+            a.B = star_kernel(g, L, l);
+            a.C = g->dact + t.col[0][l - 1];
+            a.gate_y = g->act + t.col[0][l - 1];
+            a.gate_ld = g->ld;
+            launch_gemm(1, a, sc.rp, L.in, g->stream);
+        } else {
+            a.B = star_kernel(g, L, l) + (size_t)first * L.out;
+            a.C = g->dact + g->xn_col + first;
+            launch_gemm(1, a, sc.rp, nx, g->stream);
+        }
+    }
+    if (A) {
+        memset(&a, 0, sizeof(a));
+        a.A = g->act + g->xn_col;
+        a.lda = g->ld;
+        a.B = g->dact + g->a_col;
+        a.ldb = g->ld;
+        a.C = g->DE(g->seg_aw);
+        a.ldc = A;
+        launch_wgrad(g, a, XDIM, A, sc.rp, g->dact + g->a_col, g->DE(g->seg_ab));
+        memset(&a, 0, sizeof(a));       // d xn += dz_a . aux_W[d]^T
+        a.A = g->dact + g->a_col;
+        a.lda = g->ld;
+        a.K = A;
+        a.gate_scale = 1.0f;
+        a.B = g->E(g->seg_aw) + (size_t)first * A;
+        a.ldb = A;
+        a.C = g->dact + g->xn_col + first;
+        a.ldc = g->ld;
+        a.accumulate = 1;
+        launch_gemm(1, a, sc.rp, nx, g->stream);
+    }
+    if (g->cfg.star_norm) {
+        StarNormArgs na;
+        fill_star_norm(g, sc, na);
+        GLAUNCH(k_star_colstats<true>, dim3(na.n_chunks), dim3(XDIM), 0, g->stream, na);
+        GLAUNCH(k_star_norm_bwd, dim3((sc.rp + SN_ROWS - 1) / SN_ROWS), dim3(XDIM), 0, g->stream, na);
+    }
+}
+
 int task_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    if (g->star) return star_forward(g, t, sc);
     if (g->single && g->cfg.kind == MAMDR_GRAPH_AUTOINT) {
         for (int l = 0; l < 3; ++l) {
             const int d_in = l == 0 ? EMB : ATT_OUT;
@@ -2217,6 +2650,7 @@ void refresh_sumsq(mamdr_graph* g) {
 int ready(const mamdr_graph* g) {
     if (!g->params) return gfail(MAMDR_ESTATE, "mamdr_graph_bind_state has not been called");
     if (!g->tables && (!g->user_tab || !g->item_tab)) return gfail(MAMDR_ESTATE, "frozen user / item tables are not bound");
+    if (g->aux_count && !g->aux) return gfail(MAMDR_ESTATE, "mamdr_graph_bind_aux has not been called (the norm layer's moving statistics)");
     return MAMDR_OK;
 }
 SplitData* split_of(mamdr_graph* g, int domain, int split) {
@@ -2275,7 +2709,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     if (cfg->abi_version != MAMDR_ABI_VERSION) return gfail(MAMDR_EINVAL, "abi_version %d != %d", cfg->abi_version, MAMDR_ABI_VERSION);
     if (cfg->n_user <= 0 || cfg->n_item <= 0 || cfg->n_domain <= 0 || cfg->max_batch <= 0) return gfail(MAMDR_EINVAL, "bad sizes");
     if (cfg->emb_trainable && cfg->max_batch > 16384) return gfail(MAMDR_EINVAL, "trainable tables: max_batch <= 16384");
-    if (cfg->kind < MAMDR_GRAPH_SHARED_BOTTOM || cfg->kind > MAMDR_GRAPH_DEEPFM)
+    if (cfg->kind < MAMDR_GRAPH_SHARED_BOTTOM || cfg->kind > MAMDR_GRAPH_STAR)
         return gfail(MAMDR_EINVAL, "unknown graph tower kind %d", cfg->kind);
     {       // the field width: gather, FM term and table updates are instantiated for the accepted widths alone
         const bool any_width = cfg->kind == MAMDR_GRAPH_MLP || cfg->kind == MAMDR_GRAPH_WDL || cfg->kind == MAMDR_GRAPH_DEEPFM;
@@ -2286,6 +2720,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     }
     if (!(cfg->dropout >= 0.f && cfg->dropout < 1.f)) return gfail(MAMDR_EINVAL, "dropout rate must be in [0,1)");
     const bool single = cfg->kind >= MAMDR_GRAPH_NFM;
+    const bool star = cfg->kind == MAMDR_GRAPH_STAR;
     const bool has_lin = cfg->kind == MAMDR_GRAPH_NFM || cfg->kind == MAMDR_GRAPH_CCPM || cfg->kind == MAMDR_GRAPH_AUTOINT ||
                          cfg->kind == MAMDR_GRAPH_WDL || cfg->kind == MAMDR_GRAPH_DEEPFM;
     const bool gated = cfg->kind == MAMDR_GRAPH_MMOE || cfg->kind == MAMDR_GRAPH_PLE;
@@ -2308,10 +2743,28 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
         return gfail(MAMDR_EINVAL, "a task must mix 1..%d experts", MAX_MIX);
     if (!single && cfg->uncertainty_weight)     // uncertainty_weight.py:41-45 wraps model.inputs / outputs[0] of ONE Keras model
         return gfail(MAMDR_ENOTBUILT, "the weighted loss wraps a single-output tower (the multi-task towers are a dict of models)");
+    if (star) {
+        if (cfg->star_norm < 0 || cfg->star_norm > 2) return gfail(MAMDR_EINVAL, "star_norm %d: 0 none, 1 pn, 2 bn", cfg->star_norm);
+        if (cfg->star_dense < 0 || cfg->star_dense > 1) return gfail(MAMDR_EINVAL, "star_dense %d: 0 dense, 1 star", cfg->star_dense);
+        const int last = cfg->expert_hidden[cfg->n_expert_hidden - 1];
+        if (cfg->auxiliary_dim < 0 || (cfg->auxiliary_dim > 0 && cfg->auxiliary_dim != last))
+            return gfail(MAMDR_EINVAL, "auxiliary_dim %d != the last hidden width %d (star.py:92-93 adds the two outputs)",
+                         cfg->auxiliary_dim, last);
+        if (cfg->uncertainty_weight) return gfail(MAMDR_ENOTBUILT, "the weighted loss is not built for the Star forms");
+    }
 
     mamdr_graph* g = new (std::nothrow) mamdr_graph();
     if (!g) return gfail(MAMDR_EHIP, "out of host memory");
     g->cfg = *cfg;
+    g->star = star;
+    memset(&g->stab, 0, sizeof(g->stab));
+    if (star) {             // star.py:70-96 builds no dropout and no regulariser: the config's values are ignored
+        g->cfg.dropout = 0.f;
+        g->cfg.l2_emb = 0.f;
+        g->cfg.l2_linear = 0.f;
+    } else {
+        g->cfg.star_norm = g->cfg.star_dense = g->cfg.auxiliary_dim = 0;
+    }
     g->emb = cfg->emb_dim;
     g->stream = (hipStream_t)stream;
     if (const char* ev = getenv("MAMDR_GRAPH_NO_GROUP")) g->group_ok = atoi(ev) == 0;
@@ -2350,7 +2803,80 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     g->shared_end = g->n_params;
     g->tasks.resize(single ? 1 : cfg->n_domain);
     int max_cols = 0;
-    if (single) {
+    if (star) {
+        // oracle/star.param_names generalised: domain_emb | Ws0.. bs0.. (or W0.. b0..) | the norm's tensors | Wd0.. bd0.. | wo | gb |
+        // aux_W aux_b -- the reference's Star filter (emb, kernel_shared, bias_shared) selects a prefix
+        Task& t = g->tasks[0];
+        Dnn d;
+        d.name = "dnn";
+        d.in_dim = XDIM;
+        const bool sf = cfg->star_dense == 1;
+        const int nl = cfg->n_expert_hidden, D = cfg->n_domain, A = cfg->auxiliary_dim;
+        int in = XDIM;
+        for (int l = 0; l < nl; ++l) {
+            Layer L;
+            L.in = in;
+            L.out = cfg->expert_hidden[l];
+            L.w_off = add_tensor(g, (sf ? "Ws" : "W") + std::to_string(l), in, L.out);
+            L.b_off = 0;
+            L.id = (uint32_t)l;
+            d.layers.push_back(L);
+            in = L.out;
+        }
+        for (int l = 0; l < nl; ++l) d.layers[l].b_off = add_tensor(g, (sf ? "bs" : "b") + std::to_string(l), 1, d.layers[l].out);
+        if (cfg->star_norm == 1) {
+            g->norm_off[0] = add_tensor(g, "pn_gamma_shared", 1, XDIM);
+            g->norm_off[1] = add_tensor(g, "pn_beta_shared", 1, XDIM);
+            g->norm_off[2] = add_tensor(g, "pn_gamma_spec", D, XDIM);
+            g->norm_off[3] = add_tensor(g, "pn_beta_spec", D, XDIM);
+            g->aux_count = ((int64_t)4 * D * XDIM + D + 3) & ~(int64_t)3;
+        } else if (cfg->star_norm == 2) {
+            g->norm_off[0] = add_tensor(g, "bn_gamma", 1, XDIM);
+            g->norm_off[1] = add_tensor(g, "bn_beta", 1, XDIM);
+            g->aux_count = 2 * XDIM;
+        }
+        StarTab& st = g->stab;
+        auto add_seg = [&](int64_t shared, int64_t spec, int cnt, int op) {
+            st.shared[st.n] = shared;
+            st.spec[st.n] = spec;
+            st.cnt[st.n] = cnt;
+            st.op[st.n] = op;
+            st.first4[st.n + 1] = st.first4[st.n] + cnt / 4;
+            return st.n++;
+        };
+        if (sf) {
+            for (int l = 0; l < nl; ++l) {
+                const Layer& L = d.layers[l];
+                g->seg_k[l] = add_seg(L.w_off, add_tensor(g, "Wd" + std::to_string(l), (int64_t)D * L.in, L.out), L.in * L.out, SSEG_MUL);
+            }
+            for (int l = 0; l < nl; ++l) {
+                const Layer& L = d.layers[l];
+                g->seg_b[l] = add_seg(L.b_off, add_tensor(g, "bd" + std::to_string(l), D, L.out), L.out, SSEG_ADD);
+            }
+        }
+        g->dnns.push_back(d);
+        t.tower = 0;
+        t.head_w = add_tensor(g, "wo", in, 1);
+        t.head_gb = add_tensor(g, "gb", 1, 1);
+        if (A) {
+            g->seg_aw = add_seg(0, add_tensor(g, "aux_W", (int64_t)D * XDIM, A), XDIM * A, SSEG_COPY);
+            g->seg_ab = add_seg(0, add_tensor(g, "aux_b", D, A), A, SSEG_COPY);
+        }
+        g->shared_end = g->n_params;
+        t.blk_off = t.blk_end = g->n_params;
+        int c = XDIM;
+        if (cfg->star_norm) { g->xn_col = c; c += XDIM; }
+        t.path.push_back(0);
+        std::vector<int> cols;
+        for (const Layer& L : d.layers) { cols.push_back(c); c += L.out; }
+        t.col.push_back(cols);
+        if (A) {
+            g->a_col = c; c += A;
+            g->jtop_col = c; c += A;
+        }
+        t.n_cols = c;
+        max_cols = c;
+    } else if (single) {
         // oracle/fmnets.py param_names: domain_emb | W0 W1 W2 | b0 b1 b2 | wo | gb | (NFM) lin_domain -- one block, all of it
         // trained by every step.  NFM: DNN on the 128 interaction columns; PNN: on x (+ 3 inner products into W0's last rows)
         Task& t = g->tasks[0];
@@ -2467,7 +2993,18 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
         }
         g->wpart_floats = std::max(g->wpart_floats, 8 * max_path);
     }
+    if (star && cfg->auxiliary_dim) g->wpart_floats += 16 * (size_t)XDIM * cfg->auxiliary_dim;       // the auxiliary kernel's splits
     alloc((void**)&g->wpart, g->wpart_floats * sizeof(float));
+    if (star) {
+        if (g->stab.n) {
+            alloc((void**)&g->eff, 4 * (size_t)g->stab.first4[g->stab.n] * sizeof(float));
+            alloc((void**)&g->deff, 4 * (size_t)g->stab.first4[g->stab.n] * sizeof(float));
+        }
+        if (cfg->star_norm) {
+            alloc((void**)&g->spart, (rp + SN_ROWS - 1) / SN_ROWS * 2 * XDIM * sizeof(double));
+            alloc((void**)&g->pnv, 3 * XDIM * sizeof(float));
+        }
+    }
     size_t max_mix = 0;
     for (const Task& t : g->tasks) max_mix = std::max(max_mix, t.mix.size());
     if (g->gated && g->group_ok && max_mix > 1) {
@@ -2538,7 +3075,7 @@ int mamdr_graph_destroy(mamdr_graph* g) {
                     g->sumsq_partials, g->eval_acc, g->urow, g->irow, g->map_u, g->map_i, g->hasdup_u, g->hasdup_i,
                     g->gbuf_u, g->gbuf_i, g->extra, g->glin_u, g->glin_i, g->xt, g->dxt, g->wpart, g->dxpart,
                     g->attP[0], g->attP[1], g->attP[2], g->attdP[0], g->attdP[1], g->attdP[2], g->attA[0], g->attA[1], g->attA[2],
-                    g->attY[0], g->attY[1], g->attY[2], g->attdY[0], g->attdY[1], g->attdY[2]};
+                    g->attY[0], g->attY[1], g->attY[2], g->attdY[0], g->attdY[1], g->attdY[2], g->eff, g->deff, g->pnv, g->spart};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete g;
@@ -2617,6 +3154,15 @@ int mamdr_graph_set_adam_eps(mamdr_graph* g, float eps) {
     if (check(g)) return MAMDR_EINVAL;
     if (!(eps > 0.f)) return gfail(MAMDR_EINVAL, "adam epsilon %g", (double)eps);
     g->cfg.adam_eps = eps;
+    return MAMDR_OK;
+}
+/* non-trainable state of the Star forms' norm layer (layout: include/mamdr_hip.h) */
+int64_t mamdr_graph_aux_count(const mamdr_graph* g) { return g ? g->aux_count : 0; }
+int mamdr_graph_bind_aux(mamdr_graph* g, float* d_aux) {
+    if (check(g)) return MAMDR_EINVAL;
+    if (!g->aux_count) return gfail(MAMDR_ESTATE, "this tower has no state outside the flat vector");
+    if (!d_aux || ((uintptr_t)d_aux & 15)) return gfail(MAMDR_EINVAL, "aux pointer null or not 16-byte aligned");
+    g->aux = d_aux;
     return MAMDR_OK;
 }
 int64_t mamdr_graph_launch_count(void) { return (int64_t)g_graph_launches.load(); }
@@ -2743,7 +3289,8 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
             g->b2p *= g->cfg.adam_beta2;
             alpha = lr * sqrtf(1.0f - g->b2p) / (1.0f - g->b1p);
         }
-        const bool fuse_opt = g->defer_w && g->tail_opt && g->lv_off < 0;
+        // (Star forms: their weight gradients land in scratch and pass through k_star_chain -- k_graph_adam steps the vector)
+        const bool fuse_opt = g->defer_w && g->tail_opt && g->lv_off < 0 && !g->star;
         g->sink.p = nullptr;
         if (fuse_opt) {
             g->sink.g_base = g->grad;
@@ -2804,7 +3351,9 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
         // tables are frozen): the first writer overwrites, the others add
         bool dx_started = false;
         const int dx_first = g->tables ? 0 : 2 * g->emb, dx_n = g->tables ? 0 : g->emb;
-        if (g->single && g->cfg.kind == MAMDR_GRAPH_AUTOINT) {
+        if (g->star) {
+            star_backward(g, t, sc);
+        } else if (g->single && g->cfg.kind == MAMDR_GRAPH_AUTOINT) {
             // DNN on x as any first layer; then the attention stack from the head's d [attention output] down to d x
             dnn_backward(g, tower, t.col[0], 0, 0, -1, false, dx_first, dx_n, sc);
             for (int l = 2; l >= 0; --l) {
@@ -2953,6 +3502,9 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
             GLAUNCH(k_graph_domain_grad, dim3(g->emb / CS_COLS, g->cfg.n_domain), dim3(256), 0, g->stream, g->dact, g->ld, 2 * g->emb,
                     g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb, g->G(g->dm_off), g->emb);
         }
+        if (g->star && g->stab.n)       // scratch gradients -> the flat gradient (zeros for the other domains' slices)
+            GLAUNCH(k_star_chain, dim3((g->stab.first4[g->stab.n] + 255) / 256), dim3(256), 0, g->stream, g->stab, g->params,
+                    g->domrow, g->deff, g->grad - g->table_floats, g->cfg.n_domain);
         if (g->tables) {
             // TF1's dense step over both tables: g = 2 l2 p + scatter-add of d x[:, user | item columns]
             EmbStepArgs ea;

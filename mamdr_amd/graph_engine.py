@@ -18,7 +18,28 @@ from . import _lib as L
 from .engine import FlatVectorOps, _ptr, auc_from_histogram
 
 KINDS = {"shared_bottom": L.GRAPH_SHARED_BOTTOM, "mmoe": L.GRAPH_MMOE, "ple": L.GRAPH_PLE, "nfm": L.GRAPH_NFM, "pnn": L.GRAPH_PNN,
-         "ccpm": L.GRAPH_CCPM, "autoint": L.GRAPH_AUTOINT, "mlp": L.GRAPH_MLP, "wdl": L.GRAPH_WDL, "deepfm": L.GRAPH_DEEPFM}
+         "ccpm": L.GRAPH_CCPM, "autoint": L.GRAPH_AUTOINT, "mlp": L.GRAPH_MLP, "wdl": L.GRAPH_WDL, "deepfm": L.GRAPH_DEEPFM,
+         "star": L.GRAPH_STAR}
+
+
+def star_keras_names(segments, dense):
+    """{tensor: Keras variable name} of a Star form: TowerEngine.KERAS_NAMES' shared / specific names for any layer count,
+    auxiliary_net/*, batch_normalization/*; with dense "dense" the numbered Keras Dense layers (output unit last)."""
+    from .engine import TowerEngine
+    names = dict(TowerEngine.KERAS_NAMES)
+    names.update({"user_emb": "user_emb/embeddings", "item_emb": "item_emb/embeddings", "domain_emb": "domain_emb/embeddings",
+                  "aux_W": "auxiliary_net/kernel_specific", "aux_b": "auxiliary_net/bias_specific",
+                  "bn_gamma": "batch_normalization/gamma", "bn_beta": "batch_normalization/beta"})
+    for l in range(4):
+        names["Ws%d" % l], names["bs%d" % l] = "kernel_shared_%d" % l, "bias_shared_%d" % l
+        names["Wd%d" % l], names["bd%d" % l] = "kernel_specific_%d" % l, "bias_specific_%d" % l
+    if dense == "dense":
+        n = len([s for s in segments if s in ("W0", "W1", "W2", "W3")])
+        for l in range(n):
+            stem = "dense" if l == 0 else "dense_%d" % l
+            names["W%d" % l], names["b%d" % l] = stem + "/kernel", stem + "/bias"
+        names["wo"], names["gb"] = "dense_%d/kernel" % n, "dense_%d/bias" % n
+    return names
 
 
 def _arr4(values):
@@ -30,7 +51,9 @@ class GraphEngine(FlatVectorOps):
     def __init__(self, kind, n_user, n_item, n_domain, batch_size, expert_hidden, tower_hidden, gate_hidden=(),
                  num_experts=0, shared_expert_num=0, specific_expert_num=0, dropout=0.5, emb_trainable=False, emb_dim=128,
                  l2_emb=1e-5, device=None, dropout_seed=1024, l2_linear=1e-5, uncertainty_weight=False,
-                 adam_beta1=0.9, adam_beta2=0.999):
+                 adam_beta1=0.9, adam_beta2=0.999, norm="pn", dense="star", auxiliary_dim=0):
+        """kind "star" (star.py:70-96): norm "none" / "pn" / "bn", dense "dense" / "star", auxiliary_dim 0 (no auxiliary
+        network) or the last hidden width; every other kind ignores the three."""
         self.lib = L.load()
         if not torch.cuda.is_available():
             raise RuntimeError("GraphEngine needs a HIP device (no CPU fallback)")
@@ -40,6 +63,9 @@ class GraphEngine(FlatVectorOps):
         torch.cuda.set_device(self.device)
         self.stream = torch.cuda.current_stream(self.device)
         self.kind = kind
+        self.norm, self.dense, self.auxiliary_dim = (norm, dense, int(auxiliary_dim)) if kind == "star" else ("none", "dense", 0)
+        if kind == "star" and (norm not in L.STAR_NORMS or dense not in L.STAR_DENSES):
+            raise ValueError("Star: norm %r / dense %r (norm none, pn or bn; dense dense or star)" % (norm, dense))
         self.n_user, self.n_item, self.n_domain = int(n_user), int(n_item), int(n_domain)
         self.batch_size = int(batch_size)
         self.dropout_seed = int(dropout_seed) & 0xFFFFFFFF
@@ -51,7 +77,8 @@ class GraphEngine(FlatVectorOps):
                             _arr4(tower_hidden), len(gate_hidden), _arr4(gate_hidden), int(num_experts),
                             int(shared_expert_num), int(specific_expert_num), float(dropout), float(l2_emb), float(adam_beta1),
                             float(adam_beta2), 1e-8,
-                            float(l2_linear), 1 if uncertainty_weight else 0)
+                            float(l2_linear), 1 if uncertainty_weight else 0,
+                            L.STAR_NORMS[self.norm], L.STAR_DENSES[self.dense], self.auxiliary_dim)
         handle = C.c_void_p()
         L.check(self.lib.mamdr_graph_create(C.byref(cfg), C.c_void_p(self.stream.cuda_stream), C.byref(handle)), graph=True)
         self.ctx = handle
@@ -69,7 +96,15 @@ class GraphEngine(FlatVectorOps):
         self._adam_m = self.new_vector()
         self._adam_v = self.new_vector()
         L.check(self.lib.mamdr_graph_bind_state(self.ctx, _ptr(self._weights), _ptr(self._adam_m), _ptr(self._adam_v)), graph=True)
+        # non-trainable state of the Star forms' norm layer: PartitionedNorm's moving statistics in TowerEngine's layout
+        # (mean 0 / variance 1 per domain, biased accumulators, steps), BatchNormalization's one pair (zeros / ones)
         self.aux = None
+        n_aux = int(self.lib.mamdr_graph_aux_count(self.ctx))
+        if n_aux:
+            self.aux = torch.zeros(n_aux, dtype=torch.float32, device=self.device)
+            dx = self.n_domain * 384 if self.norm == "pn" else 384
+            self.aux[dx:2 * dx] = 1.0
+            self.bind_aux(self.aux)
         self.tables, self.data = {}, {}
         self._acc, self._ema = None, None
         self._hist = torch.zeros(2 * 501, dtype=torch.int32, device=self.device)
@@ -105,8 +140,28 @@ class GraphEngine(FlatVectorOps):
             return like.clone()
         return torch.zeros(self.n_meta if meta else self.n_params, dtype=torch.float32, device=self.device)
 
+    def bind_aux(self, aux):
+        L.check(self.lib.mamdr_graph_bind_aux(self.ctx, _ptr(aux)), graph=True)
+
     def keras_name(self, segment):
+        """Keras variable names for the reference's substring filters (maml.py:153-179); the Star forms carry the names of
+        model_zoo/Star's layers, every other kind its tensor names."""
+        if self.kind == "star":
+            return star_keras_names(self.segments, self.dense).get(segment, segment)
         return segment
+
+    def aux_state(self):
+        """Star forms: the norm layer's moving statistics as numpy -- pn: as TowerEngine.aux_state; bn: {mov_mean, mov_var} [384]."""
+        if self.aux is None:
+            return {}
+        h = self.aux.cpu().numpy()
+        if self.norm == "bn":
+            return {"mov_mean": h[0:384].copy(), "mov_var": h[384:768].copy()}
+        D, dx = self.n_domain, self.n_domain * 384
+        out = {k: h[i * dx:(i + 1) * dx].reshape(D, 384).copy()
+               for i, k in enumerate(("mov_mean", "mov_var", "biased_mean", "biased_var"))}
+        out["steps"] = h[4 * dx:4 * dx + D].copy()
+        return out
 
     def pack(self, named):
         host = np.zeros(self.n_params, np.float32)

@@ -105,7 +105,10 @@ class DeepCTR(BaseModel):
         # mlp / wdl / deepfm with a hidden_dim other than the reference configs' [256, 128, 64] (deepctr.py:26-49 passes any
         # list through as dnn_hidden_units): the step kernels are built for that one shape, the generic-layer engine takes
         # 1 - 4 layers of widths that are multiples of 64 (MAMDR_GRAPH_MLP / WDL / DEEPFM, round 5)
-        if tower == "star" and n_hidden != 3:
+        # Star forms beyond the step kernels' one (star.py:70-96: bn, the mixed forms, the auxiliary network, any hidden_dim) run
+        # on the generic-layer engine as kind "star" (MAMDR_GRAPH_STAR); MAMDR_STAR_ENGINE=graph sends the step form there too
+        star_graph = self.star_graph_kwargs() if tower == "star" else None
+        if tower == "star" and star_graph is None and n_hidden != 3:
             raise ValueError("hidden_dim %r: the Star tower's kernels are built for three hidden layers (the reference's "
                              "configs all have [256, 128, 64])" % (mc["hidden_dim"],))
         # ... and so does a user_dim other than the reference configs' 128 (deepctr.py:95-102 hands the three dims to
@@ -133,6 +136,14 @@ class DeepCTR(BaseModel):
         if self.step_pnn:
             from ..engine import TowerEngine
             factory = TowerEngine
+        elif star_graph is not None:
+            if factory is None:
+                if any(h <= 0 or h % 64 for h in mc["hidden_dim"]):
+                    raise ValueError("hidden_dim %r: layer widths must be multiples of 64" % (mc["hidden_dim"],))
+                from ..graph_engine import GraphEngine
+                factory = GraphEngine
+            else:
+                factory = factory.star_graph
         elif self.graph_dnn:
             if factory is None:       # (an injected factory -- the tests' CPU stand-in -- takes `hidden` itself)
                 if any(h <= 0 or h % 64 for h in mc["hidden_dim"]):
@@ -158,7 +169,9 @@ class DeepCTR(BaseModel):
         # deepctr.py:104-116: `trainable=emb_trainable` reaches SparseFeat only on the pretrained branch; without
         # pretrained tables the column is built with deepctr's default (trainable) WHATEVER emb_trainable says
         self.tables_trainable = bool(tc["emb_trainable"]) or not bool(tc["load_pretrain_emb"])
-        if (tower in GRAPH_TOWERS and not self.step_pnn) or self.graph_dnn:
+        if star_graph is not None:
+            kw.update(star_graph)
+        if (tower in GRAPH_TOWERS and not self.step_pnn) or self.graph_dnn or star_graph is not None:
             eng = factory(tower, self.n_uid, self.n_pid, self.n_domain, self.batch_size, expert_hidden=tuple(mc["hidden_dim"]),
                           tower_hidden=(), dropout=self.dropout_rate(), emb_trainable=self.tables_trainable,
                           emb_dim=mc["user_dim"], **kw)
@@ -187,6 +200,10 @@ class DeepCTR(BaseModel):
         if tc["loss"] != "binary_crossentropy":
             raise NotImplementedError("loss '%s': only binary_crossentropy is on the hot path" % tc["loss"])
         return eng
+
+    def star_graph_kwargs(self):
+        """Star: the generic-layer form's keyword arguments, None for every tower that does not run there as kind "star"."""
+        return None
 
     def engine_kwargs(self):
         """extra keyword arguments of the engine (subclasses: Star's plain-DNN form has no regularisers)."""

@@ -1,11 +1,19 @@
 """Star tower -- host-side mirror of model_zoo/Star/star.py.
 
-Structure (star.py:70-97): 3 x 128-d embeddings -> PartitionedNorm (`norm: "pn"`) -> StarFCN per hidden
-width (`dense: "star"`) -> Dense(1, sigmoid); the AuxiliaryNet branch is built by the reference but only
-joins the graph when `auxiliary_net` is true, which no BASELINE config sets -- it raises here.  `norm: "none"` with
-`dense: "dense"` (star.py:74-87: no normalisation, plain Keras Dense layers) is the mlp tower without dropout and
-without regularisers, Keras initial values, Keras variable names (`dense/kernel` ...): it runs on the mlp engines
-(step kernels for [256, 128, 64], the generic-layer engine otherwise).  `norm: "bn"` and the mixed forms raise.  The
+Structure (star.py:70-97): 3 x 128-d embeddings -> norm (`none`, PartitionedNorm `pn`, BatchNormalization `bn`) -> one
+hidden layer per width (`dense: "star"` StarFCN, `dense: "dense"` Keras Dense) -> [+ the AuxiliaryNet's output when
+`auxiliary_net` is true] -> Dense(1, sigmoid).  Which engine runs which member of the family:
+
+    pn + star, no auxiliary net, hidden_dim [256, 128, 64]    the step kernels, `TowerEngine(tower="star")`
+                                                              (MAMDR_STAR_ENGINE=graph: the generic-layer engine, its parity twin)
+    none + dense, no auxiliary net                            the mlp tower without dropout / regularisers, Keras initial values
+                                                              and variable names (`dense/kernel` ...), on the mlp engines
+    everything else: bn, the mixed forms, auxiliary_net,      `GraphEngine("star", norm=, dense=, auxiliary_dim=)`
+    1 - 4 hidden layers of multiples of 64                    (csrc/graph_engine.hip, MAMDR_GRAPH_STAR)
+
+`auxiliary_net: true` needs `auxiliary_dim == hidden_dim[-1]` (Keras' Add).  `bn` keeps one pair of moving statistics whose
+shape the several-process / several-lane synchronisation does not know: it raises there.  An injected engine factory (the
+tests' CPU stand-ins) gets the generic-layer forms only if it offers them as `factory.star_graph`.  The
 plain `star` name trains with the same alternate loop as DeepCTR (star.py:34-69 == deepctr.py:63-93).
 Initial tensors follow the Keras defaults of the reference's layers: Embedding uniform(-0.05, 0.05)
 unless pretrained (star.py:113-127), glorot-uniform kernels (fans of the 3-d specific kernel include
@@ -58,21 +66,90 @@ def dense_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, user_em
     return t
 
 
+def forms_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, norm, dense, auxiliary_dim, user_emb=None,
+                          item_emb=None):
+    """Keras defaults of every member of the family, drawn in `initial_tensors`' order (the pn + star form without the
+    auxiliary network at three layers draws exactly its values): glorot-uniform kernels -- the 3-d specific ones and
+    `aux_W` with the fans Keras computes from the 3-d shape --, zero biases, gamma one, beta zero."""
+    t = {}
+    t["user_emb"] = user_emb if user_emb is not None else rs.uniform(-0.05, 0.05, (n_user, emb_dim)).astype(np.float32)
+    t["item_emb"] = item_emb if item_emb is not None else rs.uniform(-0.05, 0.05, (n_item, emb_dim)).astype(np.float32)
+    t["domain_emb"] = rs.uniform(-0.05, 0.05, (n_domain, emb_dim)).astype(np.float32)
+    dims = (3 * emb_dim,) + tuple(hidden)
+    if norm == "pn":
+        t["pn_gamma_shared"] = np.ones(dims[0], np.float32)
+        t["pn_beta_shared"] = np.zeros(dims[0], np.float32)
+        t["pn_gamma_spec"] = np.ones((n_domain, dims[0]), np.float32)
+        t["pn_beta_spec"] = np.zeros((n_domain, dims[0]), np.float32)
+    elif norm == "bn":
+        t["bn_gamma"] = np.ones(dims[0], np.float32)
+        t["bn_beta"] = np.zeros(dims[0], np.float32)
+    for l in range(len(hidden)):
+        if dense == "star":
+            t["Wd%d" % l] = glorot_uniform(rs, (n_domain, dims[l], dims[l + 1]), dims[l] * n_domain, dims[l + 1] * n_domain)
+            t["bd%d" % l] = np.zeros((n_domain, dims[l + 1]), np.float32)
+            t["Ws%d" % l] = glorot_uniform(rs, (dims[l], dims[l + 1]), dims[l], dims[l + 1])
+            t["bs%d" % l] = np.zeros(dims[l + 1], np.float32)
+        else:
+            t["W%d" % l] = glorot_uniform(rs, (dims[l], dims[l + 1]), dims[l], dims[l + 1])
+            t["b%d" % l] = np.zeros(dims[l + 1], np.float32)
+    t["wo"] = glorot_uniform(rs, (dims[-1], 1), dims[-1], 1)
+    t["gb"] = np.zeros(1, np.float32)
+    if auxiliary_dim:
+        A = int(auxiliary_dim)
+        t["aux_W"] = glorot_uniform(rs, (n_domain, dims[0], A), dims[0] * n_domain, A * n_domain)
+        t["aux_b"] = np.zeros((n_domain, A), np.float32)
+    return t
+
+
 class Star(DeepCTR):
+    NORMS, DENSES = ("none", "pn", "bn"), ("dense", "star")
+
     def plain_dnn(self):
         mc = self.model_config
-        return mc.get("norm") == "none" and mc.get("dense") == "dense"
+        return mc.get("norm") == "none" and mc.get("dense") == "dense" and not mc.get("auxiliary_net")
+
+    def has_star_graph(self):
+        """the generic-layer Star forms exist: on the HIP engine, or on an injected factory that offers `star_graph`."""
+        return self.engine_factory is None or hasattr(self.engine_factory, "star_graph")
 
     def tower_kind(self):
         mc = self.model_config
         if mc.get("auxiliary_net"):
-            raise NotImplementedError("auxiliary_net (model_zoo/Star/auxiliary_net.py) is not built")
+            if not self.has_star_graph():
+                raise NotImplementedError("auxiliary_net (model_zoo/Star/auxiliary_net.py) is not built")
+            if mc.get("auxiliary_dim") != mc["hidden_dim"][-1]:
+                raise ValueError("auxiliary_net: auxiliary_dim %r != hidden_dim[-1] %r (star.py:92-93 adds the two outputs)"
+                                 % (mc.get("auxiliary_dim"), mc["hidden_dim"][-1]))
         if self.plain_dnn():
             return "mlp"
         if mc.get("norm") != "pn" or mc.get("dense") != "star":
-            raise NotImplementedError("Star with norm=%r dense=%r: built are the PartitionedNorm + StarFCN form of the BASELINE "
-                                      "configs and the plain form (norm none, dense dense)" % (mc.get("norm"), mc.get("dense")))
+            if not self.has_star_graph():
+                raise NotImplementedError("Star with norm=%r dense=%r: built are the PartitionedNorm + StarFCN form of the BASELINE "
+                                          "configs and the plain form (norm none, dense dense)" % (mc.get("norm"), mc.get("dense")))
+            if mc.get("norm") not in self.NORMS or mc.get("dense") not in self.DENSES:
+                raise ValueError("Star with norm=%r dense=%r: norm is one of %r, dense one of %r"
+                                 % (mc.get("norm"), mc.get("dense"), self.NORMS, self.DENSES))
         return "star"
+
+    def star_graph_kwargs(self):
+        """keyword arguments of `GraphEngine("star", ...)` when this config runs there, else None (step kernels / mlp engines)."""
+        mc = self.model_config
+        if self.plain_dnn() or not self.has_star_graph():
+            return None
+        import os
+        aux = bool(mc.get("auxiliary_net"))
+        step_form = (mc.get("norm") == "pn" and mc.get("dense") == "star" and not aux and
+                     tuple(mc["hidden_dim"]) == (256, 128, 64))
+        if step_form and os.environ.get("MAMDR_STAR_ENGINE", "step") != "graph":
+            return None
+        if mc.get("norm") == "bn":
+            from .. import parallel
+            if parallel.world()[1] > 1:
+                raise NotImplementedError("Star with norm 'bn' under several processes or lanes: BatchNormalization keeps ONE pair "
+                                          "of moving statistics [384], not the per-domain state the tail synchronisation "
+                                          "of parallel.py combines")
+        return dict(norm=mc.get("norm"), dense=mc.get("dense"), auxiliary_dim=int(mc["auxiliary_dim"]) if aux else 0)
 
     def engine_kwargs(self):
         # star.py:74-95 attaches no regulariser to any layer and has no dropout
@@ -83,6 +160,7 @@ class Star(DeepCTR):
 
     def build_model(self):
         eng = super(Star, self).build_model()
+        self.star_form = self.star_graph_kwargs()
         if self.plain_dnn():
             # Keras names of star.py's layers (for the substring filters of maml.py:153-179): Embedding layers named after
             # their attribute, Dense layers numbered in creation order, the output unit last
@@ -97,6 +175,11 @@ class Star(DeepCTR):
 
     def draw_initial_tensors(self):
         mc = self.model_config
+        form = self.star_graph_kwargs()
+        if form is not None:
+            return forms_initial_tensors(self.init_rs, self.n_uid, self.n_pid, self.n_domain, mc["user_dim"],
+                                         tuple(mc["hidden_dim"]), form["norm"], form["dense"], form["auxiliary_dim"],
+                                         self.pretrained[0], self.pretrained[1])
         make = dense_initial_tensors if self.plain_dnn() else initial_tensors
         return make(self.init_rs, self.n_uid, self.n_pid, self.n_domain, mc["user_dim"],
                     tuple(mc["hidden_dim"]), self.pretrained[0], self.pretrained[1])

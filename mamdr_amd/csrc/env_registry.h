@@ -31,12 +31,9 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_NO_PREGATHER", "lib,bench", "1: no k_pass_prep; the tower gathers its rows itself"},
     {"MAMDR_STAR_DENSE_SLICES", "lib", "1: every per-domain Star slice swept every step (diagnostic; same bits)"},
     // ---- library, generic-layer engine (read at mamdr_graph_create)
-    {"MAMDR_GRAPH_NO_GROUP", "lib", "1: one launch per expert instead of grouped launches"},
     {"MAMDR_GRAPH_NO_DEFER", "lib", "1: a pair of weight-gradient launches per layer instead of the queued flat grid"},
     {"MAMDR_GRAPH_TILE32_BELOW", "lib", "row count below which the 32 x 32 GEMM tile is used (0: 64 x 64 everywhere)"},
     {"MAMDR_GRAPH_NO_TAIL_OPT", "lib", "1: k_graph_adam as a launch of its own (same bits)"},
-    {"MAMDR_GRAPH_WQ_BLOCKS", "lib", "workgroups of the queued weight-gradient launch"},
-    {"MAMDR_GRAPH_DIAG_REPLAY", "lib", "-DMAMDR_DIAG builds only: replay a step for the stamp tools"},
     // ---- Python host (mamdr_amd/*.py)
     {"MAMDR_LIB_PATH", "host,bench", "load this build of the library instead of mamdr_amd/libmamdr_hip.so (tools/build_variant.sh)"},
     {"MAMDR_LANES", "host", "lanes per process (overrides train.lanes)"},

@@ -9,21 +9,22 @@
 //   every expert task d mixes: DNN = per layer  relu(h W + b) * dropout       k_graph_gemm<0>  (mfma, 64x64 tiles)
 //   gate_d: DNN, then softmax(q Wg) and the mixture sum_e gate_e expert_e     k_graph_gate_fwd (one workgroup per row)
 //   tower_d: DNN;  head: sigmoid(t w + gb), Keras BCE, d loss / d logit       k_graph_head     (one wave per row)
-//   backward, layer by layer: dW = in^T dz (k_graph_gemm<2>, the batch rows split over up to 16 workgroups per tile,
-//   launch_wgrad), k_graph_wfinish = the partial products summed in a fixed order + db = column sums in the same launch,
-//   d in = dz W^T times the producer's relu / dropout gate (k_graph_gemm<1>); the mixture's backward
-//   (k_graph_gate_bwd) between tower and experts; the first layers add into d x[:, domain columns]
+//   backward, layer by layer (dnn_backward): dW = in^T dz (launch_wgrad: queued for the step's flat grid, or k_graph_gemm<2>
+//   with the batch rows split over up to 16 workgroups per tile + k_graph_wfinish = the partial products summed in a fixed
+//   order and db = column sums), d in = dz W^T times the producer's relu / dropout gate (k_graph_gemm<1>); the mixture's
+//   backward (k_graph_gate_bwd) between tower and experts; the first layers add into d x[:, domain columns]
 //   domain table: segment sum of d x over the batch's domain ids + 2 l2 Dm    k_graph_domain_grad
 //   TF1 Adam (or SGD) on the two ranges of the flat vector task d's model trains: the shared block (domain table +
 //   shared experts) and task d's block (its experts, gate, tower, head)       k_graph_adam     (hbm)
-// Launch plan since round 4 (the per-layer launches above remain under MAMDR_GRAPH_NO_DEFER=1):
+// Launch plan (the per-layer launches above remain under MAMDR_GRAPH_NO_DEFER=1):
 //   * forward / d-input contractions of fewer than 512 tiles of 64 x 64 run on 32 x 32 tiles with the reduction index
 //     split over the workgroup's four waves (gemm_tile32, k_graph_gemm32*: 4 x the workgroups, 128-deep stages);
 //   * the weight gradients are QUEUED by the backward pass and contracted in one flat grid at its end
-//     (queue_wgrad / flush_wgrads, k_graph_wgrad_multi);
+//     (launch_wgrad -> queue_wgrad, flush_wgrads: k_graph_wgrad_multi; the queue's launch aims at WQ_BLOCKS workgroups);
 //   * one tail launch (k_graph_tail) finishes them (split sums, bias column sums), runs the narrow contractions
 //     (head / gate kernels, PNN's rows, attention projections), the domain table's and the linear table's gradients --
-//     and steps every parameter where its gradient is finished (GradSink; k_graph_adam only for the weighted loss).
+//     and steps every parameter where its gradient is finished (GradSink, open_sink; k_graph_adam -- adam_step -- for the
+//     weighted loss, the Star forms, MAMDR_GRAPH_NO_TAIL_OPT=1 and a step whose queue ran full).
 // All fp32 (`v_mfma_f32_32x32x2_f32`: exact fp32 products), every reduction in a fixed order (no float atomics).
 // Trainable user / item tables (the Amazon configs: no pretraining) sit at the head of the flat vector; their step is
 // TF1's dense Adam over every row -- regulariser gradient 2 l2 p + the scatter-add of the batch's row gradients --
@@ -43,6 +44,19 @@
 //   Star     star.py:70-96 as a family: norm none / PartitionedNorm / BatchNormalization over x (k_star_colstats, k_star_norm_fwd /
 //            _bwd), Dense or StarFCN layers on the kernels of the batch's first-row domain (k_star_eff, k_star_chain), the auxiliary
 //            network joined at the head (k_star_join_fwd / _bwd); moving statistics outside the flat vector (mamdr_graph_bind_aux)
+//
+// Host side, from "host side: structure of the tower" on:
+//   contractions   gemm_args / fwd_args / din_args describe a GemmArgs by role, launch_wgrad takes a weight gradient's operands;
+//                  dnn_forward / dnn_backward walk ONE DNN over its layers' operands of this step (LayerOps: layers_of, and
+//                  star_layers / star_aux_net for the scratch blocks of k_star_eff / k_star_chain), dnn_forward_group /
+//                  dnn_backward_group a group of experts of one shape (same_shape) in single launches per layer
+//   towers         one <family>_forward / _backward pair each -- star, single_dnn (MLP / WDL), feat (NFM / PNN / DeepFM), ccpm,
+//                  autoint, shared_bottom, gated (MMOE / PLE) -- behind ONE switch per direction: task_forward / task_backward
+//   a step         mamdr_graph_train_steps_n: step_ctx, advance_optimizer, open_sink, launch_gather, task_forward, launch_head,
+//                  launch_loss, task_backward, finish_grads, star_chain, table_step, adam_step; mamdr_graph_eval_domain shares
+//                  step_ctx / launch_gather / task_forward / launch_head / launch_loss.  Nothing in a step allocates.
+//   a context      mamdr_graph_create: validate_config, layout_one_task (layout_star / layout_single) or layout_multi_task,
+//                  alloc_workspace; every device pointer comes from dev_alloc and is freed from its record (mamdr_graph::allocs)
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -715,11 +729,6 @@ __device__ __forceinline__ void wfinish_multi_body(const WFinish& t, const int b
         for (int k = 0; k < CS_GROUPS; ++k) v += red[k][c];
         sink1(sk, t.db[p] + col, v);
     }
-}
-__global__ __launch_bounds__(256) void k_graph_wfinish_multi(const WFinish t) {
-    GradSink none;
-    none.p = nullptr;
-    wfinish_multi_body(t, blockIdx.x, none);
 }
 // d x of a group's first layers: out[b][c] (+)= sum over the members of part[e][b][c], in member order
 __global__ __launch_bounds__(256) void k_graph_dx_reduce(const float* part, int n_part, size_t stride, int rows, int n4_row,
@@ -1438,7 +1447,7 @@ __global__ __launch_bounds__(256) void k_graph_domain_grad(const float* dx, int 
     none.p = nullptr;
     domain_grad_body(dx, ld, x_col, domrow, rows, dm, two_l2, g, blockIdx.x, blockIdx.y, emb, none);
 }
-// ---- the tail of a step's backward pass in ONE launch: the ends of the queued weight gradients (k_graph_wfinish_multi's
+// ---- the tail of a step's backward pass in ONE launch: the ends of the queued weight gradients (wfinish_multi_body's
 // workgroups), the narrow contractions that were queued with them (head / gate kernels, PNN's inner-product rows, the
 // attention projections: k_graph_small_tn's workgroups) and the domain table's gradient (k_graph_domain_grad's) -- all of
 // them read what the backward pass left in the workspaces and write gradients nothing but the optimiser reads.
@@ -1775,6 +1784,7 @@ __global__ __launch_bounds__(256) void k_star_join_bwd(const float* act, float* 
 }
 
 // ------------------------------------------------------------------ host side: structure of the tower
+constexpr int MAX_LAYERS = 4;   // hidden layers of one DNN (validate_config)
 struct Layer {
     int64_t w_off, b_off;
     int in, out;
@@ -1823,6 +1833,8 @@ struct mamdr_graph {
     bool single = false;
     bool has_lin = false;       // NFM / CCPM / AutoInt: the three 1-d linear tables (deepctr get_linear_logit)
     int f_col = 0;              // interaction features: NFM 128 columns, PNN 3 (+ 1 pad), CCPM 512
+    int in_col = 0;             // what the single tower's DNN reads: the features (NFM, CCPM) or x (0)
+    int xe_col = -1;            // PNN: the inner products that ride in the first layer's epilogue (-1: none)
     int cg_col = 0;             // CCPM: 64 columns of the gradient workspace for the rows' shares of the 48 conv gradients
     int64_t conv_off = 0;       // CCPM: [w1 6x4 | b1 | w2 4x4 | b2]
     // AutoInt: three attention layers on compact token-major buffers (row 3 b + t = field t of batch row b)
@@ -1856,13 +1868,14 @@ struct mamdr_graph {
     float b1p = 1.f, b2p = 1.f;
     uint32_t global_step = 0;
     // workspace
+    std::vector<void*> allocs;  // every device allocation of this context (dev_alloc): what mamdr_graph_destroy frees
+    hipError_t alloc_err = hipSuccess;
     int rows_pad_max = 0, ld = 0;
     float *act = nullptr, *dact = nullptr, *grad = nullptr, *dlogit = nullptr, *rowloss = nullptr, *y = nullptr;
     float* wpart = nullptr;     // split-K partial products of one weight gradient (launch_wgrad)
     size_t wpart_floats = 0;
     float* dxpart = nullptr;    // the members' products of a group's first-layer d x (dnn_backward_group)
     size_t dxpart_floats = 0;
-    bool group_ok = true;       // MAMDR_GRAPH_NO_GROUP=1: one launch per expert and layer (A/B, parity of the grouped launches)
     // the step's weight gradients, queued by the backward pass and run in ONE pair of launches at its end (flush_wgrads);
     // MAMDR_GRAPH_NO_DEFER=1: a pair of launches per layer, where the backward pass meets it (A/B)
     struct WProb { const float* A; int lda; const float* B; int ldb; float* out; int M, N, rows; const float* dz; float* db; };
@@ -1874,7 +1887,6 @@ struct mamdr_graph {
     // Off for the weighted loss (k_graph_loss writes d / d log_var) and under MAMDR_GRAPH_NO_TAIL_OPT=1 (A/B; same bits)
     bool tail_opt = true;
     GradSink sink;              // this step's sink (p null: gradients are stored, k_graph_adam follows)
-    int wq_blocks = 512;        // the queue's launch splits the batch rows until it has about this many workgroups
     int32_t* domrow = nullptr;
     float *thresholds = nullptr, *frozen_sumsq = nullptr, *sumsq_partials = nullptr, *eval_acc = nullptr;
     // trainable tables
@@ -1884,9 +1896,91 @@ struct mamdr_graph {
     int32_t *urow = nullptr, *irow = nullptr, *map_u = nullptr, *map_i = nullptr, *hasdup_u = nullptr, *hasdup_i = nullptr;
     float *gbuf_u = nullptr, *gbuf_i = nullptr;
     float* G(int64_t off) const { return grad + (off - table_floats); }      // gradient of the flat vector's element `off`
+    // the x columns of the gradient workspace that a first layer on x fills: the domain columns alone while the tables are
+    // frozen (n 0: all of them)
+    int dx_first() const { return tables ? 0 : 2 * emb; }
+    int dx_n() const { return tables ? 0 : emb; }
 };
 
 namespace {
+
+// the queue's launch splits the batch rows until it has about this many workgroups (256 and 1024 are within 1 - 4 % either
+// way: profiles/r04f_graph_tail_launch.txt)
+constexpr int WQ_BLOCKS = 512;
+
+struct StepCtx {
+    int rows, rp;               // rows of the batch, padded to 64
+    bool train;
+    uint32_t seed, step, drop_thresh;
+    float keep_scale;
+    bool use_dropout;
+};
+// what one step of the optimiser applies: the same rule in the tail launch's sink, the table step and k_graph_adam
+struct OptStep {
+    int optimizer;
+    float alpha, omb1, omb2, eps;
+    float* slot_m;              // Adam's m, or the accumulator of MAMDR_OPT_ACCUMULATE
+};
+
+// ---- a layer as ONE step uses it: kernel, bias and where their gradients go.  The flat vector and its gradient for every
+// tower (layers_of); a StarFCN layer reads the scratch block of k_star_eff and leaves its gradients in that of k_star_chain
+struct LayerOps {
+    const float *w, *b;
+    float *gw, *gb;
+    int in, out;
+    uint32_t id;
+};
+struct DnnOps {
+    LayerOps l[MAX_LAYERS];
+    int n;
+};
+DnnOps layers_of(const mamdr_graph* g, const Dnn& d) {
+    DnnOps o;
+    o.n = (int)d.layers.size();
+    for (int l = 0; l < o.n; ++l) {
+        const Layer& L = d.layers[l];
+        o.l[l] = LayerOps{g->params + L.w_off, g->params + L.b_off, g->G(L.w_off), g->G(L.b_off), L.in, L.out, L.id};
+    }
+    return o;
+}
+
+// ---- one description per kind of contraction (GemmArgs: what k_graph_gemm* read)
+GemmArgs gemm_args(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int K) {
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = A;
+    a.lda = lda;
+    a.B = B;
+    a.ldb = ldb;
+    a.C = C;
+    a.ldc = ldc;
+    a.K = K;
+    return a;
+}
+// layer forward on the activation workspace: columns dst = relu(columns src . W + b) * dropout
+GemmArgs fwd_args(const mamdr_graph* g, const LayerOps& L, int src_col, int dst_col, const StepCtx& sc) {
+    GemmArgs a = gemm_args(g->act + src_col, g->ld, L.w, L.out, g->act + dst_col, g->ld, L.in);
+    a.bias = L.b;
+    a.relu = 1;
+    a.use_dropout = sc.use_dropout ? 1 : 0;
+    a.drop_key = dropout_layer_key(sc.seed, sc.step, L.id);
+    a.drop_thresh = sc.drop_thresh;
+    a.keep_scale = sc.keep_scale;
+    a.n_cols = L.out;
+    return a;
+}
+// d input on the gradient workspace: columns dst (+)= columns dz (n_dz wide) . W^T, times the relu / dropout gate of the
+// activation columns `gate_col` when >= 0
+GemmArgs din_args(const mamdr_graph* g, int dz_col, int n_dz, const float* W, int dst_col, int gate_col, bool acc, const StepCtx& sc) {
+    GemmArgs a = gemm_args(g->dact + dz_col, g->ld, W, n_dz, g->dact + dst_col, g->ld, n_dz);
+    a.gate_scale = sc.keep_scale;
+    if (gate_col >= 0) {
+        a.gate_y = g->act + gate_col;
+        a.gate_ld = g->ld;
+    }
+    a.accumulate = acc ? 1 : 0;
+    return a;
+}
 
 int64_t add_tensor(mamdr_graph* g, const std::string& name, int64_t rows, int64_t cols) {
     const int64_t off = g->n_params;
@@ -1916,16 +2010,15 @@ int add_dnn(mamdr_graph* g, const std::string& name, int in_dim, const int32_t* 
 // dW[M x N] = A[rows x M]^T . B[rows x N], the rows split over up to 16 workgroups per tile when the tiles alone leave
 // most of the 256 CUs idle (a 384 x 512 kernel is 48 tiles); the partial products meet in k_graph_wfinish, which also
 // carries the layer's bias gradient (column sums of `dz` into `db`, skipped when db is null)
-struct DomainGradJob { const float* dx; int ld, x_col; const int32_t* domrow; int rows; const float* dm; float two_l2; float* g_dm;
-                       int n_domain, emb;
-                       const float* lin_dlogit; const float* lin_w; float lin_two_l2; float* lin_g; };     // lin_g null: no linear table
-void flush_wgrads(mamdr_graph* g, const DomainGradJob* dg = nullptr) {
+// `end`: the flush that ends a step's backward pass -- its tail launch also carries the domain table's gradient and the 1-d
+// linear domain table's (null: a queue ran full in mid-step)
+void flush_wgrads(mamdr_graph* g, const StepCtx* end = nullptr) {
     const int n = (int)g->wq.size();
-    if (!n && g->tq.empty() && !dg) return;
+    if (!n && g->tq.empty() && !end) return;
     int tiles = 0;
     for (const auto& q : g->wq) tiles += ((q.M + GT - 1) / GT) * (q.N / GT);
     int S = 1;
-    while (S < 16 && tiles * S < g->wq_blocks) S *= 2;
+    while (S < 16 && tiles * S < WQ_BLOCKS) S *= 2;
     int split[MAX_WQ];
     for (;; S /= 2) {       // per problem: the largest power of two <= S that leaves every split >= 4 k-tiles; all must fit
         size_t need = 0;
@@ -2001,23 +2094,23 @@ void flush_wgrads(mamdr_graph* g, const DomainGradJob* dg = nullptr) {
     }
     j.tn_first[j.n_tn] = nt;
     j.dg_first = nt;
-    if (dg) {
-        j.dg_blocks = (dg->emb / CS_COLS) * dg->n_domain;
-        j.dg_emb = dg->emb;
-        j.dx = dg->dx;
-        j.ld = dg->ld;
-        j.x_col = dg->x_col;
-        j.domrow = dg->domrow;
-        j.dg_rows = dg->rows;
-        j.dm = dg->dm;
-        j.two_l2 = dg->two_l2;
-        j.g_dm = dg->g_dm;
-        if (dg->lin_g) {
-            j.lin_blocks = dg->n_domain;
-            j.lin_dlogit = dg->lin_dlogit;
-            j.lin_w = dg->lin_w;
-            j.lin_two_l2 = dg->lin_two_l2;
-            j.lin_g = dg->lin_g;
+    if (end) {
+        j.dg_blocks = (g->emb / CS_COLS) * g->cfg.n_domain;
+        j.dg_emb = g->emb;
+        j.dx = g->dact;
+        j.ld = g->ld;
+        j.x_col = 2 * g->emb;
+        j.domrow = g->domrow;
+        j.dg_rows = end->rows;
+        j.dm = g->params + g->dm_off;
+        j.two_l2 = 2.0f * g->cfg.l2_emb;
+        j.g_dm = g->G(g->dm_off);
+        if (g->has_lin) {
+            j.lin_blocks = g->cfg.n_domain;
+            j.lin_dlogit = g->dlogit;
+            j.lin_w = g->params + g->lin_d_off;
+            j.lin_two_l2 = 2.0f * g->cfg.l2_linear;
+            j.lin_g = g->G(g->lin_d_off);
         }
     }
     j.sink = g->sink;
@@ -2047,9 +2140,11 @@ void queue_wgrad(mamdr_graph* g, const float* A, int lda, const float* B, int ld
     }
     g->wq.push_back(mamdr_graph::WProb{A, lda, B, ldb, out, M, N, rows, dz, db});
 }
-void launch_wgrad(mamdr_graph* g, GemmArgs a, int M, int N, int rows, const float* dz, float* db) {
+// weight gradient out[M x N] = A^T B over `rows` rows (+ db = column sums of dz): queued, or a pair of launches right here
+void launch_wgrad(mamdr_graph* g, const float* A, int lda, const float* B, int ldb, float* out, int M, int N, int rows,
+                  const float* dz, float* db) {
     if (g->defer_w) {
-        queue_wgrad(g, a.A, a.lda, a.B, a.ldb, a.C, M, N, rows, dz, db);
+        queue_wgrad(g, A, lda, B, ldb, out, M, N, rows, dz, db);
         return;
     }
     const int ty = (M + GT - 1) / GT, tiles = ty * (N / GT), nkt = rows / GK;
@@ -2057,11 +2152,9 @@ void launch_wgrad(mamdr_graph* g, GemmArgs a, int M, int N, int rows, const floa
     while (split < 16 && tiles * split < 256 && nkt % (2 * split) == 0 && nkt / (2 * split) >= 4 &&
            (size_t)(2 * split) * M * N <= g->wpart_floats)
         split *= 2;
-    float* out = a.C;
-    a.K = rows / split;
+    GemmArgs a = gemm_args(A, lda, B, ldb, split > 1 ? g->wpart : out, N, rows / split);
     a.zstride = (size_t)M * N;
     a.m_rows = M;
-    if (split > 1) a.C = g->wpart;
     GLAUNCH(k_graph_gemm<2>, dim3(N / GT, ty, split), dim3(256), 0, g->stream, a);
     const int64_t n4 = (int64_t)M * N / 4;
     const int nb_red = split > 1 ? (int)((n4 + 255) / 256) : 0, nb_cs = db ? (N + CS_COLS - 1) / CS_COLS : 0;
@@ -2092,94 +2185,52 @@ void launch_gemm(int mode, const GemmArgs& a, int M, int N, hipStream_t s) {
     else if (mode == 1) GLAUNCH(k_graph_gemm<1>, grid, block, 0, s, a);
     else GLAUNCH(k_graph_gemm<2>, grid, block, 0, s, a);
 }
+// the grouped forms of modes 0 / 1: `n` problems of one [sc.rp x N] shape in one grid
+template <int MODE>
+void launch_gemm_group(mamdr_graph* g, const GemmArgs& a, const GroupTab& t, int N, const StepCtx& sc) {
+    if (use_tile32(sc.rp, N, t.n))
+        GLAUNCH(k_graph_gemm32_group<MODE>, dim3(N / T32, sc.rp / T32, t.n), dim3(256), 0, g->stream, a, t);
+    else
+        GLAUNCH(k_graph_gemm_group<MODE>, dim3(N / GT, sc.rp / GT, t.n), dim3(256), 0, g->stream, a, t);
+}
 
-struct StepCtx {
-    int rows, rp;               // rows of the batch, padded to 64
-    bool train;
-    uint32_t seed, step, drop_thresh;
-    float keep_scale;
-    bool use_dropout;
-};
-
-// forward of one DNN: input columns `in_col` (width in_dim) of the activation workspace
-void dnn_forward(mamdr_graph* g, const Dnn& d, const std::vector<int>& cols, int in_col, const StepCtx& sc, int xe_col = -1) {
-    int src = in_col;
-    for (size_t l = 0; l < d.layers.size(); ++l) {
-        const Layer& L = d.layers[l];
-        GemmArgs a;
-        memset(&a, 0, sizeof(a));
-        if (l == 0 && xe_col >= 0) {        // PNN: the three inner products times rows 384..386 of the first kernel
+// forward of one DNN: input columns `in_col` of the activation workspace, layer l's output at cols[l]; xe_col >= 0 (PNN):
+// the three inner products there times rows in..in + 2 of the first kernel
+void dnn_forward(mamdr_graph* g, const DnnOps& d, const int* cols, int in_col, const StepCtx& sc, int xe_col = -1) {
+    for (int l = 0; l < d.n; ++l) {
+        const LayerOps& L = d.l[l];
+        GemmArgs a = fwd_args(g, L, l == 0 ? in_col : cols[l - 1], cols[l], sc);
+        if (l == 0 && xe_col >= 0) {
             a.xe = g->act + xe_col;
             a.xe_ld = g->ld;
-            a.we = g->params + L.w_off + (size_t)L.in * L.out;
+            a.we = L.w + (size_t)L.in * L.out;
             a.n_xe = 3;
         }
-        a.A = g->act + src;
-        a.lda = g->ld;
-        a.B = g->params + L.w_off;
-        a.ldb = L.out;
-        a.C = g->act + cols[l];
-        a.ldc = g->ld;
-        a.K = L.in;
-        a.bias = g->params + L.b_off;
-        a.relu = 1;
-        a.use_dropout = sc.use_dropout ? 1 : 0;
-        a.drop_key = dropout_layer_key(sc.seed, sc.step, L.id);
-        a.drop_thresh = sc.drop_thresh;
-        a.keep_scale = sc.keep_scale;
-        a.n_cols = L.out;
         launch_gemm(0, a, sc.rp, L.out, g->stream);
-        src = cols[l];
     }
 }
 // backward of one DNN whose last layer's d z already sits in the gradient workspace.  The input's gradient goes to
 // `din_col` of the gradient workspace: times the gate of `in_gate_col` (the producer's relu / dropout) when >= 0;
 // accumulated when `din_acc`; only columns [din_first, din_first + din_n) of the input when din_n > 0 (first layers
 // on x: the domain columns alone matter while the tables are frozen); skipped when din_col < 0.
-void dnn_backward(mamdr_graph* g, const Dnn& d, const std::vector<int>& cols, int in_col, int din_col, int in_gate_col,
-                  bool din_acc, int din_first, int din_n, const StepCtx& sc) {
-    for (int l = (int)d.layers.size() - 1; l >= 0; --l) {
-        const Layer& L = d.layers[l];
-        const int src = l == 0 ? in_col : cols[l - 1];
-        GemmArgs a;
-        memset(&a, 0, sizeof(a));
-        a.A = g->act + src;             // dW = in^T dz
-        a.lda = g->ld;
-        a.B = g->dact + cols[l];
-        a.ldb = g->ld;
-        a.C = g->G(L.w_off);
-        a.ldc = L.out;
-        launch_wgrad(g, a, L.in, L.out, sc.rp, g->dact + cols[l], g->G(L.b_off));
-        memset(&a, 0, sizeof(a));
-        a.A = g->dact + cols[l];        // d in = dz W^T
-        a.lda = g->ld;
-        a.K = L.out;
-        a.gate_scale = sc.keep_scale;
+void dnn_backward(mamdr_graph* g, const DnnOps& d, const int* cols, int in_col, int din_col, int in_gate_col, bool din_acc,
+                  int din_first, int din_n, const StepCtx& sc) {
+    for (int l = d.n - 1; l >= 0; --l) {
+        const LayerOps& L = d.l[l];
+        launch_wgrad(g, g->act + (l == 0 ? in_col : cols[l - 1]), g->ld, g->dact + cols[l], g->ld, L.gw, L.in, L.out, sc.rp,
+                     g->dact + cols[l], L.gb);
         if (l > 0) {
-            a.B = g->params + L.w_off;
-            a.ldb = L.out;
-            a.C = g->dact + cols[l - 1];
-            a.ldc = g->ld;
-            a.gate_y = g->act + cols[l - 1];
-            a.gate_ld = g->ld;
-            launch_gemm(1, a, sc.rp, L.in, g->stream);
+            launch_gemm(1, din_args(g, cols[l], L.out, L.w, cols[l - 1], cols[l - 1], false, sc), sc.rp, L.in, g->stream);
         } else if (din_col >= 0) {
             const int first = din_n > 0 ? din_first : 0, n = din_n > 0 ? din_n : L.in;
-            a.B = g->params + L.w_off + (size_t)first * L.out;
-            a.ldb = L.out;
-            a.C = g->dact + din_col + first;
-            a.ldc = g->ld;
-            if (in_gate_col >= 0) {
-                a.gate_y = g->act + in_gate_col + first;
-                a.gate_ld = g->ld;
-            }
-            a.accumulate = din_acc ? 1 : 0;
-            launch_gemm(1, a, sc.rp, n, g->stream);
+            launch_gemm(1, din_args(g, cols[0], L.out, L.w + (size_t)first * L.out, din_col + first,
+                                    in_gate_col >= 0 ? in_gate_col + first : -1, din_acc, sc), sc.rp, n, g->stream);
         }
     }
 }
 
-// ---- a group of DNNs of ONE shape on ONE input (the experts a task mixes), layer by layer in single launches
+// ---- a group of DNNs of ONE shape on ONE input (the experts a task mixes), layer by layer in single launches.  The
+// members' operands are offsets (GroupTab) from the workspaces' and the flat vector's bases; cols[e] = member e's columns
 bool same_shape(const mamdr_graph* g, const std::vector<int>& ids) {
     if (ids.size() < 2 || ids.size() > (size_t)MAX_GROUP) return false;
     const Dnn& d0 = g->dnns[ids[0]];
@@ -2191,30 +2242,15 @@ bool same_shape(const mamdr_graph* g, const std::vector<int>& ids) {
     }
     return true;
 }
-void dnn_forward_group(mamdr_graph* g, const std::vector<int>& ids, const std::vector<std::vector<int>>& cols, int in_col,
-                       const StepCtx& sc) {
+void dnn_forward_group(mamdr_graph* g, const std::vector<int>& ids, const std::vector<int>* cols, int in_col, const StepCtx& sc) {
     const Dnn& d0 = g->dnns[ids[0]];
     const int n = (int)ids.size();
     for (size_t l = 0; l < d0.layers.size(); ++l) {
         const Layer& L0 = d0.layers[l];
-        GemmArgs a;
-        memset(&a, 0, sizeof(a));
+        const GemmArgs a = fwd_args(g, LayerOps{g->params, g->params, nullptr, nullptr, L0.in, L0.out, 0}, 0, 0, sc);
         GroupTab t;
         memset(&t, 0, sizeof(t));
         t.n = n;
-        a.A = g->act;
-        a.lda = g->ld;
-        a.B = g->params;
-        a.ldb = L0.out;
-        a.C = g->act;
-        a.ldc = g->ld;
-        a.K = L0.in;
-        a.bias = g->params;
-        a.relu = 1;
-        a.use_dropout = sc.use_dropout ? 1 : 0;
-        a.drop_thresh = sc.drop_thresh;
-        a.keep_scale = sc.keep_scale;
-        a.n_cols = L0.out;
         for (int e = 0; e < n; ++e) {
             const Layer& L = g->dnns[ids[e]].layers[l];
             t.a_off[e] = l == 0 ? in_col : cols[e][l - 1];
@@ -2223,16 +2259,13 @@ void dnn_forward_group(mamdr_graph* g, const std::vector<int>& ids, const std::v
             t.bias_off[e] = L.b_off;
             t.drop_key[e] = dropout_layer_key(sc.seed, sc.step, L.id);
         }
-        if (use_tile32(sc.rp, L0.out, n))
-            GLAUNCH(k_graph_gemm32_group<0>, dim3(L0.out / T32, sc.rp / T32, n), dim3(256), 0, g->stream, a, t);
-        else
-            GLAUNCH(k_graph_gemm_group<0>, dim3(L0.out / GT, sc.rp / GT, n), dim3(256), 0, g->stream, a, t);
+        launch_gemm_group<0>(g, a, t, L0.out, sc);
     }
 }
 // backward of the group (every member's last-layer d z sits in the gradient workspace): weight / bias gradients and the
 // inner layers' d inputs in grouped launches; the FIRST layers' d x adds up over the members and stays one launch each
-void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::vector<std::vector<int>>& cols, int in_col,
-                        bool din_acc, int din_first, int din_n, const StepCtx& sc) {
+void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::vector<int>* cols, int in_col, bool din_acc,
+                        int din_first, int din_n, const StepCtx& sc) {
     const Dnn& d0 = g->dnns[ids[0]];
     const int n = (int)ids.size();
     for (int l = (int)d0.layers.size() - 1; l >= 0; --l) {
@@ -2250,21 +2283,13 @@ void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::
             while (split < 16 && tiles * n * split < 256 && nkt % (2 * split) == 0 && nkt / (2 * split) >= 4 &&
                    (size_t)(2 * split) * n * M * N <= g->wpart_floats)
                 split *= 2;
-            GemmArgs a;
-            memset(&a, 0, sizeof(a));
+            GemmArgs a = gemm_args(g->act, g->ld, g->dact, g->ld, split > 1 ? g->wpart : g->grad, N, sc.rp / split);
+            a.zstride = (size_t)M * N;
             GroupTab t, f;
             memset(&t, 0, sizeof(t));
             memset(&f, 0, sizeof(f));
             t.n = f.n = n;
             t.tiles_y = M / GT;
-            a.A = g->act;
-            a.lda = g->ld;
-            a.B = g->dact;
-            a.ldb = g->ld;
-            a.C = split > 1 ? g->wpart : g->grad;
-            a.ldc = N;
-            a.K = sc.rp / split;
-            a.zstride = (size_t)M * N;
             for (int e = 0; e < n; ++e) {
                 const Layer& L = g->dnns[ids[e]].layers[l];
                 t.a_off[e] = l == 0 ? in_col : cols[e][l - 1];
@@ -2280,133 +2305,73 @@ void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::
             GLAUNCH(k_graph_wfinish_group, dim3(nb_red + nb_cs, n), dim3(256), 0, g->stream, g->wpart, split,
                                a.zstride, n4, g->grad, nb_red, g->dact, g->ld, sc.rp, g->grad, N, f);
         }
+        GroupTab t;
+        memset(&t, 0, sizeof(t));
+        t.n = n;
         if (l > 0) {    // d in_e = dz_e W_e^T through the producer's relu / dropout gate
-            GemmArgs a;
-            memset(&a, 0, sizeof(a));
-            GroupTab t;
-            memset(&t, 0, sizeof(t));
-            t.n = n;
-            a.A = g->dact;
-            a.lda = g->ld;
-            a.B = g->params;
-            a.ldb = N;
-            a.C = g->dact;
-            a.ldc = g->ld;
-            a.K = N;
-            a.gate_scale = sc.keep_scale;
-            a.gate_y = g->act;
-            a.gate_ld = g->ld;
+            const GemmArgs a = din_args(g, 0, N, g->params, 0, 0, false, sc);
             for (int e = 0; e < n; ++e) {
-                const Layer& L = g->dnns[ids[e]].layers[l];
                 t.a_off[e] = cols[e][l];
-                t.b_off[e] = L.w_off;
+                t.b_off[e] = g->dnns[ids[e]].layers[l].w_off;
                 t.c_off[e] = cols[e][l - 1];
                 t.gate_off[e] = cols[e][l - 1];
             }
-            if (use_tile32(sc.rp, M, n))
-                GLAUNCH(k_graph_gemm32_group<1>, dim3(M / T32, sc.rp / T32, n), dim3(256), 0, g->stream, a, t);
+            launch_gemm_group<1>(g, a, t, M, sc);
+            continue;
+        }
+        // d x = sum_e dz_e W_e[first : first + nn]^T
+        const int first = din_n > 0 ? din_first : 0, nn = din_n > 0 ? din_n : M;
+        GemmArgs a = din_args(g, 0, N, g->params + (size_t)first * N, in_col + first, -1, false, sc);
+        for (int e = 0; e < n; ++e) {
+            t.a_off[e] = cols[e][0];
+            t.b_off[e] = g->dnns[ids[e]].layers[0].w_off;
+        }
+        const size_t stride = (size_t)sc.rp * nn;
+        if ((size_t)n * stride <= g->dxpart_floats) {
+            // every member's product as a launch-mate of the others (n x the tiles), summed in member order
+            a.C = g->dxpart;
+            a.ldc = nn;
+            for (int e = 0; e < n; ++e) t.c_off[e] = (int64_t)e * stride;
+            launch_gemm_group<1>(g, a, t, nn, sc);
+            const int64_t tot = (int64_t)sc.rp * (nn / 4);
+            GLAUNCH(k_graph_dx_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, g->stream, g->dxpart, n,
+                               stride, sc.rp, nn / 4, g->dact + in_col + first, g->ld, din_acc ? 1 : 0);
+        } else {    // one contraction whose reduction index runs through all members
+            a.accumulate = din_acc ? 1 : 0;
+            if (use_tile32(sc.rp, nn))
+                GLAUNCH(k_graph_gemm32_kcat, dim3(nn / T32, sc.rp / T32), dim3(256), 0, g->stream, a, t);
             else
-                GLAUNCH(k_graph_gemm_group<1>, dim3(M / GT, sc.rp / GT, n), dim3(256), 0, g->stream, a, t);
-        } else {
-            // d x = sum_e dz_e W_e[first : first + nn]^T
-            const int first = din_n > 0 ? din_first : 0, nn = din_n > 0 ? din_n : M;
-            GemmArgs a;
-            memset(&a, 0, sizeof(a));
-            GroupTab t;
-            memset(&t, 0, sizeof(t));
-            t.n = n;
-            a.A = g->dact;
-            a.lda = g->ld;
-            a.K = N;
-            a.gate_scale = sc.keep_scale;
-            a.B = g->params + (size_t)first * N;
-            a.ldb = N;
-            const size_t stride = (size_t)sc.rp * nn;
-            if ((size_t)n * stride <= g->dxpart_floats) {
-                // every member's product as a launch-mate of the others (n x the tiles), summed in member order
-                a.C = g->dxpart;
-                a.ldc = nn;
-                for (int e = 0; e < n; ++e) {
-                    t.a_off[e] = cols[e][0];
-                    t.b_off[e] = g->dnns[ids[e]].layers[0].w_off;
-                    t.c_off[e] = (int64_t)e * stride;
-                }
-                if (use_tile32(sc.rp, nn, n))
-                    GLAUNCH(k_graph_gemm32_group<1>, dim3(nn / T32, sc.rp / T32, n), dim3(256), 0, g->stream, a, t);
-                else
-                    GLAUNCH(k_graph_gemm_group<1>, dim3(nn / GT, sc.rp / GT, n), dim3(256), 0, g->stream, a, t);
-                const int64_t tot = (int64_t)sc.rp * (nn / 4);
-                GLAUNCH(k_graph_dx_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, g->stream, g->dxpart, n,
-                                   stride, sc.rp, nn / 4, g->dact + in_col + first, g->ld, din_acc ? 1 : 0);
-            } else {    // one contraction whose reduction index runs through all members
-                a.C = g->dact + in_col + first;
-                a.ldc = g->ld;
-                a.accumulate = din_acc ? 1 : 0;
-                for (int e = 0; e < n; ++e) {
-                    t.a_off[e] = cols[e][0];
-                    t.b_off[e] = g->dnns[ids[e]].layers[0].w_off;
-                }
-                if (use_tile32(sc.rp, nn))
-                    GLAUNCH(k_graph_gemm32_kcat, dim3(nn / T32, sc.rp / T32), dim3(256), 0, g->stream, a, t);
-                else
-                    GLAUNCH(k_graph_gemm_kcat, dim3(nn / GT, sc.rp / GT), dim3(256), 0, g->stream, a, t);
-            }
+                GLAUNCH(k_graph_gemm_kcat, dim3(nn / GT, sc.rp / GT), dim3(256), 0, g->stream, a, t);
         }
     }
 }
 
-void fill_gate(const mamdr_graph* g, const Task& t, const StepCtx& sc, GateArgs& ga) {
-    memset(&ga, 0, sizeof(ga));
-    ga.act = g->act;
-    ga.dact = g->dact;
-    ga.ld = g->ld;
-    const size_t gi = t.mix.size();                 // position of the gate DNN in `path`
-    const Dnn& gd = g->dnns[t.gate];
-    ga.q_col = t.col[gi].back();
-    ga.n_q = gd.layers.back().out;
-    ga.wg = g->params + t.wg_off;
-    ga.n_e = (int)t.mix.size();
-    for (size_t e = 0; e < t.mix.size(); ++e) ga.e_col[e] = t.col[e].back();
-    ga.n_h = g->n_h;
-    ga.g_col = t.g_col;
-    ga.m_col = t.m_col;
-    ga.rows_pad = sc.rp;
-    ga.gate_scale = sc.keep_scale;
-}
+// ================================================================== the towers, one pair of functions per family.
+// forward: from the gathered x to the head's input, -> its first column; backward: from the head's d input (k_graph_head)
+// down to d x, every weight gradient through launch_wgrad / small_tn / queue_wgrad.  (Star stands first and launch_feat
+// names its forward kernels before its backward ones: the device code object lists a kernel template's instances in the
+// order the host code first names them, and this order keeps it comparable byte for byte across host-only changes)
 
-// forward of task d on the gathered batch; -> column of the tower's output
-void fill_feat(const mamdr_graph* g, const Task& t, const StepCtx& sc, FeatArgs& fa) {
-    memset(&fa, 0, sizeof(fa));
-    fa.act = g->act;
-    fa.dact = g->dact;
-    fa.ld = g->ld;
-    fa.f_col = g->f_col;
-    fa.rows_pad = sc.rp;
-    fa.kind = g->cfg.kind == MAMDR_GRAPH_NFM ? 0 : (g->cfg.kind == MAMDR_GRAPH_DEEPFM ? 2 : 1);
-    fa.extra = g->extra;
-    fa.dlogit = g->dlogit;
-    fa.dx_all = g->tables ? 1 : 0;
-    const Layer& L0 = g->dnns[t.tower].layers[0];
-    fa.w_ip = g->params + L0.w_off + (size_t)L0.in * L0.out;
-    fa.z_col = t.col[0][0];
-    fa.n_out = L0.out;
+// ---- Star forms: the norm over x, Dense or StarFCN layers on the kernels of the batch's first-row domain, the auxiliary
+// network joined at the head.  The layers and the auxiliary net run on dnn_forward / dnn_backward: a StarFCN layer and the
+// auxiliary net read the scratch block of k_star_eff and leave their gradients in the scratch block k_star_chain splits
+DnnOps star_layers(const mamdr_graph* g, const Dnn& d) {
+    DnnOps o = layers_of(g, d);
+    for (int l = 0; l < o.n; ++l)
+        if (g->seg_k[l] >= 0) {
+            o.l[l].w = g->E(g->seg_k[l]);
+            o.l[l].b = g->E(g->seg_b[l]);
+            o.l[l].gw = g->DE(g->seg_k[l]);
+            o.l[l].gb = g->DE(g->seg_b[l]);
+        }
+    return o;
 }
-
-void fill_ccpm(const mamdr_graph* g, const StepCtx& sc, CcpmArgs& ca) {
-    memset(&ca, 0, sizeof(ca));
-    ca.act = g->act;
-    ca.dact = g->dact;
-    ca.ld = g->ld;
-    ca.f_col = g->f_col;
-    ca.cg_col = g->cg_col;
-    ca.rows_pad = sc.rp;
-    ca.dx_all = g->tables ? 1 : 0;
-    ca.conv = g->params + g->conv_off;
+DnnOps star_aux_net(const mamdr_graph* g) {     // a = relu(xn . aux_W[d] + aux_b[d]): one layer on the NORMALISED input (star.py:76-82)
+    DnnOps o;
+    o.n = 1;
+    o.l[0] = LayerOps{g->E(g->seg_aw), g->E(g->seg_ab), g->DE(g->seg_aw), g->DE(g->seg_ab), XDIM, g->cfg.auxiliary_dim, 0};
+    return o;
 }
-
-// ---- Star forms: kernel / bias of hidden layer l as this step uses them (StarFCN: the scratch block of k_star_eff)
-const float* star_kernel(const mamdr_graph* g, const Layer& L, int l) { return g->seg_k[l] >= 0 ? g->E(g->seg_k[l]) : g->params + L.w_off; }
-const float* star_bias(const mamdr_graph* g, const Layer& L, int l) { return g->seg_b[l] >= 0 ? g->E(g->seg_b[l]) : g->params + L.b_off; }
 void fill_star_norm(const mamdr_graph* g, const StepCtx& sc, StarNormArgs& na) {
     memset(&na, 0, sizeof(na));
     na.x = g->act;
@@ -2436,7 +2401,6 @@ void fill_star_norm(const mamdr_graph* g, const StepCtx& sc, StarNormArgs& na) {
     na.aux = g->aux;
 }
 int star_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
-    const Dnn& d = g->dnns[t.tower];
     const int A = g->cfg.auxiliary_dim;
     if (g->stab.n)
         GLAUNCH(k_star_eff, dim3((g->stab.first4[g->stab.n] + 255) / 256), dim3(256), 0, g->stream, g->stab, g->params, g->domrow,
@@ -2447,106 +2411,23 @@ int star_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
         if (sc.train) GLAUNCH(k_star_colstats<false>, dim3(na.n_chunks), dim3(XDIM), 0, g->stream, na);
         GLAUNCH(k_star_norm_fwd, dim3((sc.rp + SN_ROWS - 1) / SN_ROWS), dim3(XDIM), 0, g->stream, na);
     }
-    GemmArgs a;
-    int src = g->xn_col;
-    for (size_t l = 0; l < d.layers.size(); ++l) {
-        const Layer& L = d.layers[l];
-        memset(&a, 0, sizeof(a));
-        a.A = g->act + src;
-        a.lda = g->ld;
-        a.B = star_kernel(g, L, (int)l);
-        a.ldb = L.out;
-        a.C = g->act + t.col[0][l];
-        a.ldc = g->ld;
-        a.K = L.in;
-        a.bias = star_bias(g, L, (int)l);
-        a.relu = 1;
-        a.keep_scale = 1.0f;
-        a.n_cols = L.out;
-        launch_gemm(0, a, sc.rp, L.out, g->stream);
-        src = t.col[0][l];
-    }
-    if (!A) return src;
-    memset(&a, 0, sizeof(a));       // a = relu(xn . aux_W[d] + aux_b[d]): the NORMALISED input (star.py:76-82)
-    a.A = g->act + g->xn_col;
-    a.lda = g->ld;
-    a.B = g->E(g->seg_aw);
-    a.ldb = A;
-    a.C = g->act + g->a_col;
-    a.ldc = g->ld;
-    a.K = XDIM;
-    a.bias = g->E(g->seg_ab);
-    a.relu = 1;
-    a.keep_scale = 1.0f;
-    a.n_cols = A;
-    launch_gemm(0, a, sc.rp, A, g->stream);
-    GLAUNCH(k_star_join_fwd, dim3((sc.rp * (A / 4) + 255) / 256), dim3(256), 0, g->stream, g->act, g->ld, src, g->a_col, g->jtop_col,
-            A, sc.rp);
+    dnn_forward(g, star_layers(g, g->dnns[t.tower]), t.col[0].data(), g->xn_col, sc);
+    if (!A) return t.col[0].back();
+    dnn_forward(g, star_aux_net(g), &g->a_col, g->xn_col, sc);
+    GLAUNCH(k_star_join_fwd, dim3((sc.rp * (A / 4) + 255) / 256), dim3(256), 0, g->stream, g->act, g->ld, t.col[0].back(), g->a_col,
+            g->jtop_col, A, sc.rp);
     return g->jtop_col;
 }
-// backward from the head's d top down to d x (the x columns of the gradient workspace); weight gradients are queued
 void star_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
-    const Dnn& d = g->dnns[t.tower];
-    const int A = g->cfg.auxiliary_dim, n = (int)d.layers.size();
+    const int A = g->cfg.auxiliary_dim;
     if (A)
         GLAUNCH(k_star_join_bwd, dim3((sc.rp * (A / 4) + 255) / 256), dim3(256), 0, g->stream, g->act, g->dact, g->ld,
-                t.col[0][n - 1], g->a_col, g->jtop_col, A, sc.rp);
+                t.col[0].back(), g->a_col, g->jtop_col, A, sc.rp);
     // without a norm d xn IS d x: the domain columns alone matter while the tables are frozen
     const bool part = !g->cfg.star_norm && !g->tables;
     const int first = part ? 2 * EMB : 0, nx = part ? EMB : XDIM;
-    GemmArgs a;
-    for (int l = n - 1; l >= 0; --l) {
-        const Layer& L = d.layers[l];
-        const int src = l == 0 ? g->xn_col : t.col[0][l - 1];
-        const bool sf = g->seg_k[l] >= 0;
-        memset(&a, 0, sizeof(a));
-        a.A = g->act + src;             // dK = in^T dz, into scratch under StarFCN (k_star_chain splits it)
-        a.lda = g->ld;
-        a.B = g->dact + t.col[0][l];
-        a.ldb = g->ld;
-        a.C = sf ? g->DE(g->seg_k[l]) : g->G(L.w_off);
-        a.ldc = L.out;
-        launch_wgrad(g, a, L.in, L.out, sc.rp, g->dact + t.col[0][l], sf ? g->DE(g->seg_b[l]) : g->G(L.b_off));
-        memset(&a, 0, sizeof(a));
-        a.A = g->dact + t.col[0][l];    // d in = dz K^T
-        a.lda = g->ld;
-        a.K = L.out;
-        a.gate_scale = 1.0f;
-        a.ldb = L.out;
-        a.ldc = g->ld;
-        if (l > 0) {
-            a.B = star_kernel(g, L, l);
-            a.C = g->dact + t.col[0][l - 1];
-            a.gate_y = g->act + t.col[0][l - 1];
-            a.gate_ld = g->ld;
-            launch_gemm(1, a, sc.rp, L.in, g->stream);
-        } else {
-            a.B = star_kernel(g, L, l) + (size_t)first * L.out;
-            a.C = g->dact + g->xn_col + first;
-            launch_gemm(1, a, sc.rp, nx, g->stream);
-        }
-    }
-    if (A) {
-        memset(&a, 0, sizeof(a));
-        a.A = g->act + g->xn_col;
-        a.lda = g->ld;
-        a.B = g->dact + g->a_col;
-        a.ldb = g->ld;
-        a.C = g->DE(g->seg_aw);
-        a.ldc = A;
-        launch_wgrad(g, a, XDIM, A, sc.rp, g->dact + g->a_col, g->DE(g->seg_ab));
-        memset(&a, 0, sizeof(a));       // d xn += dz_a . aux_W[d]^T
-        a.A = g->dact + g->a_col;
-        a.lda = g->ld;
-        a.K = A;
-        a.gate_scale = 1.0f;
-        a.B = g->E(g->seg_aw) + (size_t)first * A;
-        a.ldb = A;
-        a.C = g->dact + g->xn_col + first;
-        a.ldc = g->ld;
-        a.accumulate = 1;
-        launch_gemm(1, a, sc.rp, nx, g->stream);
-    }
+    dnn_backward(g, star_layers(g, g->dnns[t.tower]), t.col[0].data(), g->xn_col, g->xn_col, -1, false, first, nx, sc);
+    if (A) dnn_backward(g, star_aux_net(g), &g->a_col, g->xn_col, g->xn_col, -1, true, first, nx, sc);     // d xn += dz_a . aux_W[d]^T
     if (g->cfg.star_norm) {
         StarNormArgs na;
         fill_star_norm(g, sc, na);
@@ -2555,82 +2436,238 @@ void star_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
     }
 }
 
-int task_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
-    if (g->star) return star_forward(g, t, sc);
-    if (g->single && g->cfg.kind == MAMDR_GRAPH_AUTOINT) {
-        for (int l = 0; l < 3; ++l) {
-            const int d_in = l == 0 ? EMB : ATT_OUT;
-            GemmArgs a;
-            memset(&a, 0, sizeof(a));
-            a.A = l == 0 ? g->xt : g->attY[l - 1];     // token-major [3 rows_pad][d]
-            a.lda = d_in;
-            a.B = g->params + g->att_w[l];
-            a.ldb = ATT_P;
-            a.C = g->attP[l];
-            a.ldc = ATT_P;
-            a.K = d_in;
-            a.n_cols = ATT_P;
-            launch_gemm(0, a, 3 * sc.rp, ATT_P, g->stream);
-            AttArgs aa;
-            memset(&aa, 0, sizeof(aa));
-            aa.P = g->attP[l];
-            aa.A = g->attA[l];
-            aa.Y = g->attY[l];
-            aa.rows_pad = sc.rp;
-            if (l == 2) {
-                aa.top = g->act + g->top_col;
-                aa.top_ld = g->ld;
-            }
-            GLAUNCH(k_graph_att_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, aa);
-        }
-        dnn_forward(g, g->dnns[t.tower], t.col[0], 0, sc);
-        return g->top_col;
-    }
-    if (g->single) {
-        if (g->cfg.kind == MAMDR_GRAPH_CCPM) {
-            CcpmArgs ca;
-            fill_ccpm(g, sc, ca);
-            GLAUNCH(k_graph_ccpm_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, ca);
-            dnn_forward(g, g->dnns[t.tower], t.col[0], g->f_col, sc);
-            return t.col[0].back();
-        }
-        const int kind = g->cfg.kind;
-        if (kind == MAMDR_GRAPH_MLP || kind == MAMDR_GRAPH_WDL) {       // the plain DNN on x (WDL's linear part rides in `extra`)
-            dnn_forward(g, g->dnns[t.tower], t.col[0], 0, sc);
-            return t.col[0].back();
-        }
-        FeatArgs fa;
-        fill_feat(g, t, sc, fa);
+void fill_gate(const mamdr_graph* g, const Task& t, const StepCtx& sc, GateArgs& ga) {
+    memset(&ga, 0, sizeof(ga));
+    ga.act = g->act;
+    ga.dact = g->dact;
+    ga.ld = g->ld;
+    const size_t gi = t.mix.size();                 // position of the gate DNN in `path`
+    const Dnn& gd = g->dnns[t.gate];
+    ga.q_col = t.col[gi].back();
+    ga.n_q = gd.layers.back().out;
+    ga.wg = g->params + t.wg_off;
+    ga.n_e = (int)t.mix.size();
+    for (size_t e = 0; e < t.mix.size(); ++e) ga.e_col[e] = t.col[e].back();
+    ga.n_h = g->n_h;
+    ga.g_col = t.g_col;
+    ga.m_col = t.m_col;
+    ga.rows_pad = sc.rp;
+    ga.gate_scale = sc.keep_scale;
+}
+// the interaction features: NFM's bi-interaction, PNN's inner products, DeepFM's FM term (at its field width)
+void launch_feat(mamdr_graph* g, const Task& t, const StepCtx& sc, bool bwd) {
+    FeatArgs fa;
+    memset(&fa, 0, sizeof(fa));
+    fa.act = g->act;
+    fa.dact = g->dact;
+    fa.ld = g->ld;
+    fa.f_col = g->f_col;
+    fa.rows_pad = sc.rp;
+    fa.kind = g->cfg.kind == MAMDR_GRAPH_NFM ? 0 : (g->cfg.kind == MAMDR_GRAPH_DEEPFM ? 2 : 1);
+    fa.extra = g->extra;
+    fa.dlogit = g->dlogit;
+    fa.dx_all = g->tables ? 1 : 0;
+    const Layer& L0 = g->dnns[t.tower].layers[0];
+    fa.w_ip = g->params + L0.w_off + (size_t)L0.in * L0.out;
+    fa.z_col = t.col[0][0];
+    fa.n_out = L0.out;
+    if (!bwd) {
         switch (g->emb) {       // (other than 128: DeepFM alone)
             case 32: GLAUNCH(k_graph_fm_fwd<32>, dim3(sc.rp / 32), dim3(256), 0, g->stream, fa); break;
             case 64: GLAUNCH(k_graph_fm_fwd<64>, dim3(sc.rp / 16), dim3(256), 0, g->stream, fa); break;
             case 256: GLAUNCH(k_graph_fm_fwd<256>, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
             default: GLAUNCH(k_graph_feat_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
         }
-        const bool nfm = kind == MAMDR_GRAPH_NFM;
-        dnn_forward(g, g->dnns[t.tower], t.col[0], nfm ? g->f_col : 0, sc, kind == MAMDR_GRAPH_PNN ? g->f_col : -1);
-        return t.col[0].back();
+        return;
     }
-    if (g->group_ok && same_shape(g, t.mix)) {
-        std::vector<std::vector<int>> mc(t.col.begin(), t.col.begin() + t.mix.size());
-        dnn_forward_group(g, t.mix, mc, 0, sc);
-    } else {
-        for (size_t e = 0; e < t.mix.size(); ++e) dnn_forward(g, g->dnns[t.mix[e]], t.col[e], 0, sc);
+    switch (g->emb) {
+        case 32: GLAUNCH(k_graph_fm_bwd<32>, dim3(sc.rp / 32), dim3(256), 0, g->stream, fa); break;
+        case 64: GLAUNCH(k_graph_fm_bwd<64>, dim3(sc.rp / 16), dim3(256), 0, g->stream, fa); break;
+        case 256: GLAUNCH(k_graph_fm_bwd<256>, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
+        default: GLAUNCH(k_graph_feat_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
     }
-    int tower_in;
-    if (g->gated) {
-        const size_t gi = t.mix.size();
-        dnn_forward(g, g->dnns[t.gate], t.col[gi], 0, sc);
-        GateArgs ga;
-        fill_gate(g, t, sc, ga);
-        GLAUNCH(k_graph_gate_fwd, dim3(sc.rp), dim3(256), 0, g->stream, ga);
-        tower_in = t.m_col;
-    } else {
-        tower_in = t.col[0].back();
+}
+void fill_ccpm(const mamdr_graph* g, const StepCtx& sc, CcpmArgs& ca) {
+    memset(&ca, 0, sizeof(ca));
+    ca.act = g->act;
+    ca.dact = g->dact;
+    ca.ld = g->ld;
+    ca.f_col = g->f_col;
+    ca.cg_col = g->cg_col;
+    ca.rows_pad = sc.rp;
+    ca.dx_all = g->tables ? 1 : 0;
+    ca.conv = g->params + g->conv_off;
+}
+void fill_att(const mamdr_graph* g, int l, const StepCtx& sc, bool bwd, AttArgs& aa) {
+    memset(&aa, 0, sizeof(aa));
+    aa.P = g->attP[l];
+    aa.A = g->attA[l];
+    aa.Y = g->attY[l];
+    aa.rows_pad = sc.rp;
+    if (bwd) {
+        aa.dY = g->attdY[l];
+        aa.dP = g->attdP[l];
     }
-    const size_t ti = t.path.size() - 1;
-    dnn_forward(g, g->dnns[t.tower], t.col[ti], tower_in, sc);
+    if (l == 2 && bwd) {
+        aa.dtop = g->dact + g->top_col;
+        aa.dtop_ld = g->ld;
+    } else if (l == 2) {
+        aa.top = g->act + g->top_col;
+        aa.top_ld = g->ld;
+    }
+}
+
+// ---- the single towers' DNN on g->in_col (x, or the interaction features), PNN's epilogue included: MLP / WDL as they are
+int single_dnn_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    dnn_forward(g, layers_of(g, g->dnns[t.tower]), t.col[0].data(), g->in_col, sc, g->xe_col);
+    return t.col[0].back();
+}
+void single_dnn_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    const bool on_x = g->in_col == 0;       // as any first layer on x; otherwise d features, whole
+    dnn_backward(g, layers_of(g, g->dnns[t.tower]), t.col[0].data(), g->in_col, g->in_col, -1, false, on_x ? g->dx_first() : 0,
+                 on_x ? g->dx_n() : 0, sc);
+}
+// ---- NFM / PNN / DeepFM: the feature kernel beside that DNN
+int feat_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    launch_feat(g, t, sc, false);
+    return single_dnn_forward(g, t, sc);
+}
+void feat_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    single_dnn_backward(g, t, sc);
+    if (g->xe_col >= 0) {       // PNN: rows in..in + 2 of the first kernel against the inner products
+        const Layer& L0 = g->dnns[t.tower].layers[0];
+        small_tn(g, g->act + g->xe_col, g->ld, g->dact + t.col[0][0], g->ld, sc.rp, 3, L0.out, g->G(L0.w_off + (int64_t)L0.in * L0.out));
+    }
+    launch_feat(g, t, sc, true);            // d x from d features (NFM) / the inner products / the FM term
+}
+// ---- CCPM: the convolutions' kernel, the DNN over its 512 features
+int ccpm_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    CcpmArgs ca;
+    fill_ccpm(g, sc, ca);
+    GLAUNCH(k_graph_ccpm_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, ca);
+    return single_dnn_forward(g, t, sc);
+}
+void ccpm_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    // d features from the first layer; the convolutions' backward per row; their 48 gradients summed over the batch
+    single_dnn_backward(g, t, sc);
+    CcpmArgs ca;
+    fill_ccpm(g, sc, ca);
+    GLAUNCH(k_graph_ccpm_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, ca);
+    if (g->defer_w)     // the 48 column sums as a queue entry without a contraction (its end = the bias-gradient workgroups)
+        queue_wgrad(g, nullptr, 0, nullptr, 0, nullptr, 0, 48, sc.rp, g->dact + g->cg_col, g->G(g->conv_off));
+    else
+        launch_colsum(g->stream, g->dact + g->cg_col, g->ld, sc.rp, g->G(g->conv_off), 48);
+}
+// ---- AutoInt: the attention stack on the token-major buffers [3 rows_pad][d], beside the DNN on x
+int autoint_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    for (int l = 0; l < 3; ++l) {
+        const int d_in = l == 0 ? EMB : ATT_OUT;
+        GemmArgs a = gemm_args(l == 0 ? g->xt : g->attY[l - 1], d_in, g->params + g->att_w[l], ATT_P, g->attP[l], ATT_P, d_in);
+        a.n_cols = ATT_P;
+        launch_gemm(0, a, 3 * sc.rp, ATT_P, g->stream);
+        AttArgs aa;
+        fill_att(g, l, sc, false, aa);
+        GLAUNCH(k_graph_att_fwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, aa);
+    }
+    single_dnn_forward(g, t, sc);
+    return g->top_col;
+}
+void autoint_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    single_dnn_backward(g, t, sc);
+    for (int l = 2; l >= 0; --l) {          // from the head's d [attention output] down to d x
+        const int d_in = l == 0 ? EMB : ATT_OUT;
+        AttArgs aa;
+        fill_att(g, l, sc, true, aa);
+        GLAUNCH(k_graph_att_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, aa);
+        const float *xin = l == 0 ? g->xt : g->attY[l - 1], *W = g->params + g->att_w[l];
+        float* dxin = l == 0 ? g->dxt : g->attdY[l - 1];
+        // dW = X^T dP over the 3 B token rows; d X = dP W^T
+        if (l == 0) launch_wgrad(g, xin, d_in, g->attdP[l], ATT_P, g->G(g->att_w[l]), d_in, ATT_P, 3 * sc.rp, nullptr, nullptr);
+        else small_tn(g, xin, d_in, g->attdP[l], ATT_P, 3 * sc.rp, d_in, ATT_P, g->G(g->att_w[l]));
+        if (l == 0 || use_tile32(3 * sc.rp, d_in))
+            launch_gemm(1, gemm_args(g->attdP[l], ATT_P, W, ATT_P, dxin, d_in, ATT_P), 3 * sc.rp, d_in, g->stream);
+        else
+            GLAUNCH(k_graph_small_nt, dim3((3 * sc.rp * d_in + 255) / 256), dim3(256), 0, g->stream, g->attdP[l], ATT_P, W, d_in,
+                    3 * sc.rp, dxin);
+    }
+    const int first = g->tables ? 0 : 2 * EMB, n = g->tables ? XDIM : EMB;
+    GLAUNCH(k_graph_add_x, dim3((sc.rp * n + 255) / 256), dim3(256), 0, g->stream, g->dact, g->ld, g->dxt, sc.rp, first, n);
+}
+// ---- shared-bottom: one expert, the tower on its last layer
+int shared_bottom_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    dnn_forward(g, layers_of(g, g->dnns[t.mix[0]]), t.col[0].data(), 0, sc);
+    dnn_forward(g, layers_of(g, g->dnns[t.tower]), t.col[1].data(), t.col[0].back(), sc);
+    return t.col[1].back();
+}
+void shared_bottom_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    // the tower's input IS the bottom's output: its gradient passes through the bottom's last relu / dropout gate
+    const int b = t.col[0].back();
+    dnn_backward(g, layers_of(g, g->dnns[t.tower]), t.col[1].data(), b, b, b, false, 0, 0, sc);
+    dnn_backward(g, layers_of(g, g->dnns[t.mix[0]]), t.col[0].data(), 0, 0, -1, false, g->dx_first(), g->dx_n(), sc);
+}
+// ---- MMOE / PLE: the experts (one grid per layer when they share a shape), the gate and its mixture, the tower.  The x
+// columns of the gradient workspace collect d x from every first layer: the gate's overwrites, the experts' add
+int gated_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    const size_t gi = t.mix.size(), ti = gi + 1;
+    if (same_shape(g, t.mix))
+        dnn_forward_group(g, t.mix, t.col.data(), 0, sc);
+    else
+        for (size_t e = 0; e < gi; ++e) dnn_forward(g, layers_of(g, g->dnns[t.mix[e]]), t.col[e].data(), 0, sc);
+    dnn_forward(g, layers_of(g, g->dnns[t.gate]), t.col[gi].data(), 0, sc);
+    GateArgs ga;
+    fill_gate(g, t, sc, ga);
+    GLAUNCH(k_graph_gate_fwd, dim3(sc.rp), dim3(256), 0, g->stream, ga);
+    dnn_forward(g, layers_of(g, g->dnns[t.tower]), t.col[ti].data(), t.m_col, sc);
     return t.col[ti].back();
+}
+void gated_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    const size_t gi = t.mix.size(), ti = gi + 1;
+    const int dx_first = g->dx_first(), dx_n = g->dx_n();
+    dnn_backward(g, layers_of(g, g->dnns[t.tower]), t.col[ti].data(), t.m_col, t.m_col, -1, false, 0, 0, sc);
+    GateArgs ga;
+    fill_gate(g, t, sc, ga);
+    GLAUNCH(k_graph_gate_bwd, dim3(sc.rp), dim3(256), 0, g->stream, ga);
+    small_tn(g, g->act + ga.q_col, g->ld, g->dact + t.g_col, g->ld, sc.rp, ga.n_q, ga.n_e, g->G(t.wg_off));
+    dnn_backward(g, layers_of(g, g->dnns[t.gate]), t.col[gi].data(), 0, 0, -1, false, dx_first, dx_n, sc);
+    if (same_shape(g, t.mix))
+        dnn_backward_group(g, t.mix, t.col.data(), 0, true, dx_first, dx_n, sc);
+    else
+        for (size_t e = 0; e < gi; ++e) dnn_backward(g, layers_of(g, g->dnns[t.mix[e]]), t.col[e].data(), 0, 0, -1, true, dx_first, dx_n, sc);
+}
+// ---- one dispatch per direction
+int task_forward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    switch (g->cfg.kind) {
+        case MAMDR_GRAPH_SHARED_BOTTOM: return shared_bottom_forward(g, t, sc);
+        case MAMDR_GRAPH_MMOE:
+        case MAMDR_GRAPH_PLE: return gated_forward(g, t, sc);
+        case MAMDR_GRAPH_NFM:
+        case MAMDR_GRAPH_PNN:
+        case MAMDR_GRAPH_DEEPFM: return feat_forward(g, t, sc);
+        case MAMDR_GRAPH_CCPM: return ccpm_forward(g, t, sc);
+        case MAMDR_GRAPH_AUTOINT: return autoint_forward(g, t, sc);
+        case MAMDR_GRAPH_MLP:
+        case MAMDR_GRAPH_WDL: return single_dnn_forward(g, t, sc);      // (WDL's linear part rides in `extra`)
+        default: return star_forward(g, t, sc);
+    }
+}
+void task_backward(mamdr_graph* g, const Task& t, const StepCtx& sc) {
+    switch (g->cfg.kind) {
+        case MAMDR_GRAPH_SHARED_BOTTOM: shared_bottom_backward(g, t, sc); break;
+        case MAMDR_GRAPH_MMOE:
+        case MAMDR_GRAPH_PLE: gated_backward(g, t, sc); break;
+        case MAMDR_GRAPH_NFM:
+        case MAMDR_GRAPH_PNN:
+        case MAMDR_GRAPH_DEEPFM: feat_backward(g, t, sc); break;
+        case MAMDR_GRAPH_CCPM: ccpm_backward(g, t, sc); break;
+        case MAMDR_GRAPH_AUTOINT: autoint_backward(g, t, sc); break;
+        case MAMDR_GRAPH_MLP:
+        case MAMDR_GRAPH_WDL: single_dnn_backward(g, t, sc); break;
+        default: star_backward(g, t, sc); break;
+    }
+    // the 1-d linear domain table's gradient: the last launch of every tower that has one (in the tail launch when deferred)
+    if (g->has_lin && !g->defer_w)
+        launch_lin_domain_grad(g->stream, g->dlogit, g->domrow, sc.rows, g->params + g->lin_d_off, 2.0f * g->cfg.l2_linear,
+                               g->cfg.n_domain, g->G(g->lin_d_off));
 }
 
 int check(const mamdr_graph* g) {
@@ -2657,8 +2694,57 @@ SplitData* split_of(mamdr_graph* g, int domain, int split) {
     if (domain < 0 || domain >= g->cfg.n_domain || split < 0 || split > 2) return nullptr;
     return &g->data[(size_t)domain * 3 + split];
 }
-void fill_gather(const mamdr_graph* g, const SplitData& d, const int32_t* perm, int64_t row_base, const StepCtx& sc,
-                 GatherArgs& ga) {
+
+// ================================================================== the parts of a step, in the order the step loop runs them
+// rows [row_base, row_base + batch) of a pass over `n_rows` rows; the dropout of a training step that is no meta pass
+// (MAMDR_OPT_ACCUMULATE runs in learning phase 0: maml.py:107-109)
+StepCtx step_ctx(const mamdr_graph* g, int64_t n_rows, int64_t row_base, int batch, bool train, uint32_t seed, bool dropout) {
+    StepCtx sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.rows = (int)((n_rows - row_base) < batch ? (n_rows - row_base) : batch);
+    sc.rp = (sc.rows + GT - 1) / GT * GT;
+    sc.train = train;
+    sc.keep_scale = 1.0f;
+    if (!train) return sc;
+    const float rate = g->cfg.dropout;
+    const double thr = (double)rate * 4294967296.0;
+    sc.seed = seed;
+    sc.step = g->global_step;
+    sc.drop_thresh = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)(int64_t)thr;
+    sc.use_dropout = rate > 0.f && dropout;
+    if (sc.use_dropout) sc.keep_scale = (float)(1.0 / (1.0 - (double)rate));
+    return sc;
+}
+// ONE optimizer object for all domain models: its beta powers advance with every Adam step, whichever task it trains
+OptStep advance_optimizer(mamdr_graph* g, int optimizer, float lr) {
+    OptStep o{optimizer, lr, 1.0f - g->cfg.adam_beta1, 1.0f - g->cfg.adam_beta2, g->cfg.adam_eps,
+              optimizer == MAMDR_OPT_ACCUMULATE ? g->accum : g->adam_m};
+    if (optimizer == MAMDR_OPT_ADAM) {
+        g->adam_t += 1;
+        g->b1p *= g->cfg.adam_beta1;
+        g->b2p *= g->cfg.adam_beta2;
+        o.alpha = lr * sqrtf(1.0f - g->b2p) / (1.0f - g->b1p);
+    }
+    return o;
+}
+// the tail launch steps every parameter where its gradient is finished -- unless the step has gradients that the tail does
+// not finish: the weighted loss (k_graph_loss writes d / d log_var), the Star forms (their weight gradients land in scratch
+// and pass through k_star_chain), the per-layer plan.  Closed (p null): gradients are stored, k_graph_adam steps the vector
+void open_sink(mamdr_graph* g, const OptStep& o) {
+    g->sink.p = nullptr;
+    if (!(g->defer_w && g->tail_opt && g->lv_off < 0 && !g->star)) return;
+    g->sink.g_base = g->grad;
+    g->sink.p = g->params + g->table_floats;
+    g->sink.m = o.slot_m + g->table_floats;
+    g->sink.v = g->adam_v + g->table_floats;
+    g->sink.optimizer = o.optimizer;
+    g->sink.alpha = o.alpha;
+    g->sink.omb1 = o.omb1;
+    g->sink.omb2 = o.omb2;
+    g->sink.eps = o.eps;
+}
+void launch_gather(mamdr_graph* g, const SplitData& d, const int32_t* perm, int64_t row_base, const StepCtx& sc) {
+    GatherArgs ga;
     memset(&ga, 0, sizeof(ga));
     ga.user_tab = g->user_tab;
     ga.item_tab = g->item_tab;
@@ -2694,18 +2780,133 @@ void fill_gather(const mamdr_graph* g, const SplitData& d, const int32_t* perm, 
         ga.map_u = g->map_u;
         ga.map_i = g->map_i;
     }
+    launch_graph_gather(ga, g->emb, g->stream);
+}
+// the head over columns [t_col, ...) of the activation workspace (AutoInt: [attention output | last DNN layer]).  A training
+// step leaves d logit and the head's d input; evaluation counts the histogram and writes the predictions.  -> its width
+int launch_head(mamdr_graph* g, const Task& t, const StepCtx& sc, int t_col, uint32_t* hist, float* pred_out) {
+    const bool autoint = g->cfg.kind == MAMDR_GRAPH_AUTOINT;
+    HeadArgs ha;
+    memset(&ha, 0, sizeof(ha));
+    ha.act = g->act;
+    ha.dact = g->dact;
+    ha.ld = g->ld;
+    ha.t_col = t_col;
+    ha.n_plain = autoint ? 3 * ATT_OUT : 0;
+    ha.n_t = g->dnns[t.tower].layers.back().out + ha.n_plain;
+    ha.w = g->params + t.head_w;
+    ha.gb = g->params + t.head_gb;
+    ha.y = g->y;
+    ha.rows = sc.rows;
+    ha.rows_pad = sc.rp;
+    ha.dlogit = g->dlogit;
+    ha.rowloss = g->rowloss;
+    ha.extra = g->extra;
+    ha.train = sc.train ? 1 : 0;
+    ha.gate_scale = sc.keep_scale;
+    if (sc.train && g->lv_off >= 0) {
+        ha.log_var = g->params + g->lv_off;
+        ha.domrow = g->domrow;
+    }
+    if (!sc.train) {
+        ha.thresholds = g->thresholds;
+        ha.hist = hist;
+        ha.pred_out = pred_out;
+    }
+    GLAUNCH(k_graph_head, dim3(sc.rp / 4), dim3(256), 0, g->stream, ha);
+    return ha.n_t;
+}
+// batch loss into out[0] (accumulate: added to it); the weighted loss of a training step also leaves d / d log_var
+void launch_loss(mamdr_graph* g, const StepCtx& sc, float* out, bool accumulate) {
+    const bool weighted = sc.train && g->lv_off >= 0;
+    GLAUNCH(k_graph_loss, dim3(1), dim3(256), 0, g->stream, g->rowloss, sc.rows, g->params + g->dm_off, g->cfg.n_domain * g->emb,
+            g->cfg.l2_emb, g->frozen_sumsq, out, accumulate ? 1 : 0, g->extra ? g->params + g->lin_d_off : nullptr, g->cfg.n_domain,
+            g->cfg.l2_linear, weighted ? g->params + g->lv_off : nullptr, g->domrow, weighted ? g->G(g->lv_off) : nullptr,
+            g->cfg.n_domain);
+}
+// every layer's dW / db of the step, the narrow contractions, the domain table's and the linear table's gradients: one pair
+// of launches (the tail steps the parameters when the sink is open); per-layer plan: the domain table's gradient alone
+void finish_grads(mamdr_graph* g, const StepCtx& sc) {
+    if (g->defer_w)
+        flush_wgrads(g, &sc);
+    else
+        GLAUNCH(k_graph_domain_grad, dim3(g->emb / CS_COLS, g->cfg.n_domain), dim3(256), 0, g->stream, g->dact, g->ld, 2 * g->emb,
+                g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb, g->G(g->dm_off), g->emb);
+}
+// Star: scratch gradients -> the flat gradient (zeros for the other domains' slices)
+void star_chain(mamdr_graph* g) {
+    if (g->stab.n)
+        GLAUNCH(k_star_chain, dim3((g->stab.first4[g->stab.n] + 255) / 256), dim3(256), 0, g->stream, g->stab, g->params, g->domrow,
+                g->deff, g->grad - g->table_floats, g->cfg.n_domain);
+}
+// TF1's dense step over both trainable tables: g = 2 l2 p + scatter-add of d x[:, user | item columns]; their 1-d linear
+// tables by the same rule from d loss / d logit
+void table_step(mamdr_graph* g, const StepCtx& sc, const OptStep& o) {
+    EmbStepArgs ea;
+    memset(&ea, 0, sizeof(ea));
+    ea.p = g->params;
+    ea.m = o.slot_m;
+    ea.v = g->adam_v;
+    ea.dxe = g->dact;
+    ea.dx_ld = g->ld;
+    ea.dlogit = g->dlogit;
+    ea.rows = sc.rows;
+    ea.opt.optimizer = o.optimizer;
+    ea.opt.alpha = o.alpha;
+    ea.opt.omb1 = o.omb1;
+    ea.opt.omb2 = o.omb2;
+    ea.opt.eps = o.eps;
+    ea.opt.two_l2 = 2.0f * g->cfg.l2_emb;
+    const int n_rows[2] = {g->cfg.n_user, g->cfg.n_item};
+    int32_t *const brow[2] = {g->urow, g->irow}, *const map[2] = {g->map_u, g->map_i}, *const hasdup[2] = {g->hasdup_u, g->hasdup_i};
+    float *const gbuf[2] = {g->gbuf_u, g->gbuf_i}, *const glin[2] = {g->glin_u, g->glin_i};
+    const int64_t lin_off[2] = {g->lin_u_off, g->lin_i_off};
+    if (g->has_lin) ea.two_l2_lin = 2.0f * g->cfg.l2_linear;
+    for (int k = 0; k < 2; ++k) {
+        ea.t[k].n_rows = n_rows[k];
+        ea.t[k].brow = brow[k];
+        ea.t[k].map = map[k];
+        ea.t[k].gbuf = gbuf[k];
+        ea.t[k].hasdup = hasdup[k];
+        ea.t[k].dx_off = k * g->emb;
+        if (g->has_lin) {
+            ea.t[k].lin_p = g->params + lin_off[k];
+            ea.t[k].lin_m = o.slot_m + lin_off[k];
+            ea.t[k].lin_v = g->adam_v + lin_off[k];
+            ea.t[k].glin = glin[k];
+        }
+    }
+    launch_emb_reduce(ea, g->stream, g->emb);
+    launch_emb_sweep(ea, g->stream, g->emb);
+    if (g->has_lin) launch_lin_sweep(ea, g->stream);      // (reads the row maps, then resets them)
+}
+// the optimiser on the two ranges this task's model trains, in one launch
+void adam_step(mamdr_graph* g, const Task& t, const OptStep& o) {
+    AdamArgs aa;
+    aa.p = g->params;
+    aa.m = o.slot_m;
+    aa.v = g->adam_v;
+    aa.g = g->grad - g->table_floats;       // G(off) = grad + off - table_floats
+    aa.off4[0] = g->dm_off / 4;
+    aa.n4[0] = (g->shared_end - g->dm_off) / 4;
+    aa.off4[1] = t.blk_off / 4;
+    aa.n4[1] = (t.blk_end - t.blk_off) / 4;
+    aa.optimizer = o.optimizer;
+    aa.alpha = o.alpha;
+    aa.omb1 = o.omb1;
+    aa.omb2 = o.omb2;
+    aa.eps = o.eps;
+    const int64_t n4 = aa.n4[0] + aa.n4[1];
+    if (n4 > 0) GLAUNCH(k_graph_adam, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, g->stream, aa);
 }
 
-}  // namespace
-
-extern "C" {
-
-const char* mamdr_graph_last_error(void) { return g_gerr; }
-
-int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph** out) {
-    if (!cfg || !out) return gfail(MAMDR_EINVAL, "null argument");
-    *out = nullptr;
-    (void)mamdr::env_warn_unknown();
+// ================================================================== mamdr_graph_create in three steps
+// experts every task shares / owns (multi-task towers)
+void expert_counts(const mamdr_graph_config& cfg, int& n_shared, int& n_specific) {
+    n_shared = cfg.kind == MAMDR_GRAPH_MMOE ? cfg.num_experts : (cfg.kind == MAMDR_GRAPH_PLE ? cfg.shared_expert_num : 1);
+    n_specific = cfg.kind == MAMDR_GRAPH_PLE ? cfg.specific_expert_num : 0;
+}
+int validate_config(const mamdr_graph_config* cfg) {
     if (cfg->abi_version != MAMDR_ABI_VERSION) return gfail(MAMDR_EINVAL, "abi_version %d != %d", cfg->abi_version, MAMDR_ABI_VERSION);
     if (cfg->n_user <= 0 || cfg->n_item <= 0 || cfg->n_domain <= 0 || cfg->max_batch <= 0) return gfail(MAMDR_EINVAL, "bad sizes");
     if (cfg->emb_trainable && cfg->max_batch > 16384) return gfail(MAMDR_EINVAL, "trainable tables: max_batch <= 16384");
@@ -2720,12 +2921,9 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     }
     if (!(cfg->dropout >= 0.f && cfg->dropout < 1.f)) return gfail(MAMDR_EINVAL, "dropout rate must be in [0,1)");
     const bool single = cfg->kind >= MAMDR_GRAPH_NFM;
-    const bool star = cfg->kind == MAMDR_GRAPH_STAR;
-    const bool has_lin = cfg->kind == MAMDR_GRAPH_NFM || cfg->kind == MAMDR_GRAPH_CCPM || cfg->kind == MAMDR_GRAPH_AUTOINT ||
-                         cfg->kind == MAMDR_GRAPH_WDL || cfg->kind == MAMDR_GRAPH_DEEPFM;
     const bool gated = cfg->kind == MAMDR_GRAPH_MMOE || cfg->kind == MAMDR_GRAPH_PLE;
-    if (cfg->n_expert_hidden < 1 || cfg->n_expert_hidden > 4 || (!single && (cfg->n_tower_hidden < 1 || cfg->n_tower_hidden > 4)) ||
-        (gated && (cfg->n_gate_hidden < 1 || cfg->n_gate_hidden > 4)))
+    auto depth_ok = [](int n) { return n >= 1 && n <= MAX_LAYERS; };
+    if (!depth_ok(cfg->n_expert_hidden) || (!single && !depth_ok(cfg->n_tower_hidden)) || (gated && !depth_ok(cfg->n_gate_hidden)))
         return gfail(MAMDR_EINVAL, "hidden_dim%s need 1..4 layers", single ? "" : (gated ? " / tower_hidden_dim / gate_dnn_hidden_units"
                                                                                            : " / tower_hidden_dim"));
     auto widths_ok = [](const int32_t* h, int n) {
@@ -2736,14 +2934,13 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     if (!widths_ok(cfg->expert_hidden, cfg->n_expert_hidden) || (!single && !widths_ok(cfg->tower_hidden, cfg->n_tower_hidden)) ||
         (gated && !widths_ok(cfg->gate_hidden, cfg->n_gate_hidden)))
         return gfail(MAMDR_EINVAL, "layer widths must be multiples of 64 (the reference's configs use 64 ... 512)");
-    int n_shared = single ? 0 : 1, n_specific = 0;
-    if (cfg->kind == MAMDR_GRAPH_MMOE) n_shared = cfg->num_experts;
-    if (cfg->kind == MAMDR_GRAPH_PLE) { n_shared = cfg->shared_expert_num; n_specific = cfg->specific_expert_num; }
+    int n_shared, n_specific;
+    expert_counts(*cfg, n_shared, n_specific);
     if (!single && (n_shared < 0 || n_specific < 0 || n_shared + n_specific < 1 || n_shared + n_specific > MAX_MIX))
         return gfail(MAMDR_EINVAL, "a task must mix 1..%d experts", MAX_MIX);
     if (!single && cfg->uncertainty_weight)     // uncertainty_weight.py:41-45 wraps model.inputs / outputs[0] of ONE Keras model
         return gfail(MAMDR_ENOTBUILT, "the weighted loss wraps a single-output tower (the multi-task towers are a dict of models)");
-    if (star) {
+    if (cfg->kind == MAMDR_GRAPH_STAR) {
         if (cfg->star_norm < 0 || cfg->star_norm > 2) return gfail(MAMDR_EINVAL, "star_norm %d: 0 none, 1 pn, 2 bn", cfg->star_norm);
         if (cfg->star_dense < 0 || cfg->star_dense > 1) return gfail(MAMDR_EINVAL, "star_dense %d: 0 dense, 1 star", cfg->star_dense);
         const int last = cfg->expert_hidden[cfg->n_expert_hidden - 1];
@@ -2752,13 +2949,309 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
                          cfg->auxiliary_dim, last);
         if (cfg->uncertainty_weight) return gfail(MAMDR_ENOTBUILT, "the weighted loss is not built for the Star forms");
     }
+    return MAMDR_OK;
+}
 
+// ---- the flat vector behind the tables and the domain table, and the column plan of the workspaces: one layout per family.
+// -> columns the widest task needs
+// the single towers' DNN as ONE block: every kernel, then every bias (oracle/fmnets.py, oracle/star.py param_names);
+// `extra_rows` more rows in the first kernel (PNN's inner products)
+Dnn& add_dnn_wb(mamdr_graph* g, const char* w, const char* b, int in_dim, int extra_rows) {
+    Dnn d;
+    d.name = "dnn";
+    d.in_dim = in_dim;
+    int in = in_dim;
+    for (int l = 0; l < g->cfg.n_expert_hidden; ++l) {
+        Layer L;
+        L.in = in;
+        L.out = g->cfg.expert_hidden[l];
+        L.w_off = add_tensor(g, w + std::to_string(l), l == 0 ? in + extra_rows : in, L.out);
+        L.b_off = 0;
+        L.id = (uint32_t)l;
+        d.layers.push_back(L);
+        in = L.out;
+    }
+    for (size_t l = 0; l < d.layers.size(); ++l) d.layers[l].b_off = add_tensor(g, b + std::to_string(l), 1, d.layers[l].out);
+    g->dnns.push_back(d);
+    return g->dnns.back();
+}
+// the columns of one DNN's layer outputs, from column c on
+void plan_cols(Task& t, const Dnn& d, int& c) {
+    std::vector<int> cols;
+    for (const Layer& L : d.layers) {
+        cols.push_back(c);
+        c += L.out;
+    }
+    t.col.push_back(cols);
+}
+// oracle/star.param_names generalised: domain_emb | Ws0.. bs0.. (or W0.. b0..) | the norm's tensors | Wd0.. bd0.. | wo | gb |
+// aux_W aux_b -- the reference's Star filter (emb, kernel_shared, bias_shared) selects a prefix
+int layout_star(mamdr_graph* g) {
+    const mamdr_graph_config& cfg = g->cfg;
+    Task& t = g->tasks[0];
+    const bool sf = cfg.star_dense == 1;
+    const int D = cfg.n_domain, A = cfg.auxiliary_dim;
+    const Dnn& d = add_dnn_wb(g, sf ? "Ws" : "W", sf ? "bs" : "b", XDIM, 0);
+    if (cfg.star_norm == 1) {
+        g->norm_off[0] = add_tensor(g, "pn_gamma_shared", 1, XDIM);
+        g->norm_off[1] = add_tensor(g, "pn_beta_shared", 1, XDIM);
+        g->norm_off[2] = add_tensor(g, "pn_gamma_spec", D, XDIM);
+        g->norm_off[3] = add_tensor(g, "pn_beta_spec", D, XDIM);
+        g->aux_count = ((int64_t)4 * D * XDIM + D + 3) & ~(int64_t)3;
+    } else if (cfg.star_norm == 2) {
+        g->norm_off[0] = add_tensor(g, "bn_gamma", 1, XDIM);
+        g->norm_off[1] = add_tensor(g, "bn_beta", 1, XDIM);
+        g->aux_count = 2 * XDIM;
+    }
+    StarTab& st = g->stab;
+    auto add_seg = [&](int64_t shared, int64_t spec, int cnt, int op) {
+        st.shared[st.n] = shared;
+        st.spec[st.n] = spec;
+        st.cnt[st.n] = cnt;
+        st.op[st.n] = op;
+        st.first4[st.n + 1] = st.first4[st.n] + cnt / 4;
+        return st.n++;
+    };
+    const int nl = (int)d.layers.size();
+    for (int l = 0; sf && l < nl; ++l) {
+        const Layer& L = d.layers[l];
+        g->seg_k[l] = add_seg(L.w_off, add_tensor(g, "Wd" + std::to_string(l), (int64_t)D * L.in, L.out), L.in * L.out, SSEG_MUL);
+    }
+    for (int l = 0; sf && l < nl; ++l) {
+        const Layer& L = d.layers[l];
+        g->seg_b[l] = add_seg(L.b_off, add_tensor(g, "bd" + std::to_string(l), D, L.out), L.out, SSEG_ADD);
+    }
+    t.head_w = add_tensor(g, "wo", d.layers.back().out, 1);
+    t.head_gb = add_tensor(g, "gb", 1, 1);
+    if (A) {
+        g->seg_aw = add_seg(0, add_tensor(g, "aux_W", (int64_t)D * XDIM, A), XDIM * A, SSEG_COPY);
+        g->seg_ab = add_seg(0, add_tensor(g, "aux_b", D, A), A, SSEG_COPY);
+    }
+    int c = XDIM;
+    if (cfg.star_norm) { g->xn_col = c; c += XDIM; }
+    plan_cols(t, d, c);
+    if (A) {
+        g->a_col = c; c += A;
+        g->jtop_col = c; c += A;
+    }
+    return c;
+}
+// oracle/fmnets.py param_names: domain_emb | W0 W1 W2 | b0 b1 b2 | wo | gb | (NFM) lin_domain -- one block, all of it
+// trained by every step.  NFM: DNN on the 128 interaction columns; PNN: on x (+ 3 inner products into W0's last rows)
+int layout_single(mamdr_graph* g) {
+    const mamdr_graph_config& cfg = g->cfg;
+    Task& t = g->tasks[0];
+    const bool nfm = cfg.kind == MAMDR_GRAPH_NFM, pnn = cfg.kind == MAMDR_GRAPH_PNN, ccpm = cfg.kind == MAMDR_GRAPH_CCPM,
+               autoint = cfg.kind == MAMDR_GRAPH_AUTOINT;
+    if (ccpm) {         // conv1_w [6][4] | conv1_b [4] | conv2_w [4 in][4 out] | conv2_b [4]: 48 contiguous floats
+        g->conv_off = add_tensor(g, "conv1_w", 6, 4);
+        add_tensor(g, "conv1_b", 1, 4);
+        add_tensor(g, "conv2_w", 4, 4);
+        add_tensor(g, "conv2_b", 1, 4);
+    }
+    if (autoint) {      // [W_query | W_key | W_value | W_res] per layer: [128][128], then [32][128] twice
+        g->att_w[0] = add_tensor(g, "att0_w", EMB, ATT_P);
+        g->att_w[1] = add_tensor(g, "att1_w", ATT_OUT, ATT_P);
+        g->att_w[2] = add_tensor(g, "att2_w", ATT_OUT, ATT_P);
+    }
+    // (NFM / CCPM: 128-wide fields only)
+    const Dnn& d = add_dnn_wb(g, "W", "b", nfm ? EMB : (ccpm ? 4 * EMB : 3 * g->emb), pnn ? 3 : 0);
+    t.head_w = add_tensor(g, "wo", (autoint ? 3 * ATT_OUT : 0) + d.layers.back().out, 1);
+    t.head_gb = add_tensor(g, "gb", 1, 1);
+    if (g->has_lin) g->lin_d_off = add_tensor(g, "lin_domain", cfg.n_domain, 1);
+    if (cfg.uncertainty_weight) g->lv_off = add_tensor(g, "log_var", cfg.n_domain, 1);
+    int c = 3 * g->emb;
+    g->f_col = c;
+    if (nfm || ccpm) g->in_col = c;
+    if (pnn) g->xe_col = c;
+    c += nfm ? EMB : (ccpm ? 4 * EMB : 4);
+    if (ccpm) { g->cg_col = c; c += 64; }
+    std::vector<int> cols;
+    for (size_t l = 0; l < d.layers.size(); ++l) {
+        if (autoint && l + 1 == d.layers.size()) {      // head input = [attention output 96 | last DNN layer]
+            g->top_col = c;
+            c += 3 * ATT_OUT;
+        }
+        cols.push_back(c);
+        c += d.layers[l].out;
+    }
+    t.col.push_back(cols);
+    return c;
+}
+// Star and the deepctr towers: ONE task whose block is the shared one (all of it trained by every step)
+int layout_one_task(mamdr_graph* g) {
+    Task& t = g->tasks[0];
+    t.tower = 0;
+    t.path.push_back(0);
+    const int c = g->star ? layout_star(g) : layout_single(g);
+    g->shared_end = g->n_params;
+    t.blk_off = t.blk_end = g->n_params;
+    t.n_cols = c;
+    return c;
+}
+// oracle/mtl.py Spec.tensors: the block every task's model trains (the shared experts), then one block per task: its own
+// experts, gate, tower, head.  Columns: x | every layer output on the path | gate probabilities | mixture
+int layout_multi_task(mamdr_graph* g) {
+    const mamdr_graph_config& cfg = g->cfg;
+    int n_shared, n_specific;
+    expert_counts(cfg, n_shared, n_specific);
+    uint32_t next_id = 0;
+    std::vector<int> shared;
+    for (int e = 0; e < n_shared; ++e) {
+        const std::string nm = cfg.kind == MAMDR_GRAPH_SHARED_BOTTOM ? "bottom"
+                               : (cfg.kind == MAMDR_GRAPH_MMOE ? "expert_" + std::to_string(e) : "shared_expert_" + std::to_string(e));
+        shared.push_back(add_dnn(g, nm, XDIM, cfg.expert_hidden, cfg.n_expert_hidden, next_id));
+    }
+    g->shared_end = g->n_params;
+    int max_cols = 0;
+    for (int d = 0; d < cfg.n_domain; ++d) {
+        Task& t = g->tasks[d];
+        const std::string ds = std::to_string(d);
+        t.blk_off = g->n_params;
+        for (int e = 0; e < n_specific; ++e)
+            t.mix.push_back(add_dnn(g, "task_" + ds + "_expert_" + std::to_string(e), XDIM, cfg.expert_hidden, cfg.n_expert_hidden, next_id));
+        for (int s : shared) t.mix.push_back(s);
+        if (g->gated) {
+            t.gate = add_dnn(g, "gate_" + ds, XDIM, cfg.gate_hidden, cfg.n_gate_hidden, next_id);
+            t.wg_off = add_tensor(g, "gate_" + ds + "/Wg", cfg.gate_hidden[cfg.n_gate_hidden - 1], (int64_t)t.mix.size());
+        }
+        t.tower = add_dnn(g, "tower_" + ds, g->n_h, cfg.tower_hidden, cfg.n_tower_hidden, next_id);
+        t.head_w = add_tensor(g, "head_" + ds + "/w", cfg.tower_hidden[cfg.n_tower_hidden - 1], 1);
+        t.head_gb = add_tensor(g, "head_" + ds + "/gb", 1, 1);
+        t.blk_end = g->n_params;
+        int c = XDIM;
+        t.path = t.mix;
+        if (g->gated) t.path.push_back(t.gate);
+        t.path.push_back(t.tower);
+        for (int di : t.path) plan_cols(t, g->dnns[di], c);
+        if (g->gated) {
+            t.g_col = c; c += ((int)t.mix.size() + 3) & ~3;
+            t.m_col = c; c += g->n_h;
+        }
+        t.n_cols = c;
+        if (c > max_cols) max_cols = c;
+    }
+    return max_cols;
+}
+
+// every device allocation of a context goes through here: mamdr_graph_destroy frees what this recorded (after the first
+// failure nothing more is allocated; alloc_workspace reports it)
+template <typename T>
+void dev_alloc(mamdr_graph* g, T** p, size_t count) {
+    if (g->alloc_err != hipSuccess) return;
+    g->alloc_err = hipMalloc((void**)p, count * sizeof(T));
+    if (g->alloc_err == hipSuccess) g->allocs.push_back(*p);
+}
+hipError_t alloc_workspace(mamdr_graph* g) {
+    const mamdr_graph_config& cfg = g->cfg;
+    float thr[500];
+    thr[0] = (float)(0.0 - 1e-7);
+    for (int i = 0; i < 498; ++i) thr[i + 1] = (float)((double)(i + 1) * 1.0 / (double)(500 - 1));
+    thr[499] = (float)(1.0 + 1e-7);
+    const size_t rp = (size_t)g->rows_pad_max, n_grad = (size_t)(g->n_params - g->table_floats);
+    dev_alloc(g, &g->act, rp * g->ld);
+    dev_alloc(g, &g->dact, rp * g->ld);
+    dev_alloc(g, &g->grad, n_grad);
+    size_t max_w = (size_t)EMB * ATT_P;
+    for (const Dnn& d : g->dnns)
+        for (const Layer& L : d.layers) max_w = std::max(max_w, (size_t)L.in * L.out);
+    g->wpart_floats = 16 * max_w;
+    if (g->defer_w) {       // the queue holds every problem's partial products at once: 8 splits of the widest step's kernels
+        size_t max_path = 3 * (size_t)EMB * ATT_P;
+        for (const Task& t : g->tasks) {
+            size_t w = cfg.kind == MAMDR_GRAPH_AUTOINT ? 3 * (size_t)EMB * ATT_P : 0;
+            for (int id : t.path)
+                for (const Layer& L : g->dnns[id].layers) w += (size_t)L.in * L.out;
+            max_path = std::max(max_path, w);
+        }
+        g->wpart_floats = std::max(g->wpart_floats, 8 * max_path);
+    }
+    g->wpart_floats += 16 * (size_t)XDIM * cfg.auxiliary_dim;       // Star: the auxiliary kernel's splits
+    dev_alloc(g, &g->wpart, g->wpart_floats);
+    if (g->stab.n) {
+        dev_alloc(g, &g->eff, 4 * (size_t)g->stab.first4[g->stab.n]);
+        dev_alloc(g, &g->deff, 4 * (size_t)g->stab.first4[g->stab.n]);
+    }
+    if (cfg.star_norm) {
+        dev_alloc(g, &g->spart, (rp + SN_ROWS - 1) / SN_ROWS * 2 * XDIM);
+        dev_alloc(g, &g->pnv, (size_t)3 * XDIM);
+    }
+    size_t max_mix = 0;
+    for (const Task& t : g->tasks) max_mix = std::max(max_mix, t.mix.size());
+    if (g->gated && max_mix > 1) {
+        g->dxpart_floats = max_mix * rp * (size_t)(g->tables ? XDIM : EMB);
+        dev_alloc(g, &g->dxpart, g->dxpart_floats);
+    }
+    if (g->tables) {
+        dev_alloc(g, &g->urow, rp);
+        dev_alloc(g, &g->irow, rp);
+        dev_alloc(g, &g->hasdup_u, rp);
+        dev_alloc(g, &g->hasdup_i, rp);
+        dev_alloc(g, &g->map_u, (size_t)cfg.n_user);
+        dev_alloc(g, &g->map_i, (size_t)cfg.n_item);
+        dev_alloc(g, &g->gbuf_u, rp * g->emb);
+        dev_alloc(g, &g->gbuf_i, rp * g->emb);
+    }
+    dev_alloc(g, &g->dlogit, rp);
+    dev_alloc(g, &g->rowloss, rp);
+    dev_alloc(g, &g->y, rp);
+    dev_alloc(g, &g->domrow, rp);
+    dev_alloc(g, &g->thresholds, (size_t)500);
+    dev_alloc(g, &g->frozen_sumsq, (size_t)4);
+    dev_alloc(g, &g->sumsq_partials, (size_t)1024);
+    dev_alloc(g, &g->eval_acc, (size_t)4);
+    if (cfg.kind == MAMDR_GRAPH_AUTOINT) {
+        dev_alloc(g, &g->xt, rp * XDIM);
+        dev_alloc(g, &g->dxt, rp * XDIM);
+        for (int l = 0; l < 3; ++l) {
+            dev_alloc(g, &g->attP[l], 3 * rp * ATT_P);
+            dev_alloc(g, &g->attdP[l], 3 * rp * ATT_P);
+            dev_alloc(g, &g->attA[l], rp * 36);
+            dev_alloc(g, &g->attY[l], 3 * rp * ATT_OUT);
+            dev_alloc(g, &g->attdY[l], 3 * rp * ATT_OUT);
+        }
+    }
+    if (g->has_lin) {
+        dev_alloc(g, &g->extra, rp);
+        if (g->tables) {
+            dev_alloc(g, &g->glin_u, rp);
+            dev_alloc(g, &g->glin_i, rp);
+        }
+    }
+    hipError_t e = g->alloc_err;
+    if (e == hipSuccess) e = hipMemsetAsync(g->grad, 0, n_grad * sizeof(float), g->stream);
+    if (g->tables && e == hipSuccess) {
+        e = hipMemsetAsync(g->hasdup_u, 0, rp * sizeof(int32_t), g->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(g->hasdup_i, 0, rp * sizeof(int32_t), g->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(g->urow, 0xff, rp * sizeof(int32_t), g->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(g->irow, 0xff, rp * sizeof(int32_t), g->stream);
+        launch_emb_map_init(g->map_u, cfg.n_user, g->stream);
+        launch_emb_map_init(g->map_i, cfg.n_item, g->stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(g->dact, 0, rp * g->ld * sizeof(float), g->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(g->frozen_sumsq, 0, 4 * sizeof(float), g->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(g->thresholds, thr, sizeof(thr), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    return e;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* mamdr_graph_last_error(void) { return g_gerr; }
+
+int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph** out) {
+    if (!cfg || !out) return gfail(MAMDR_EINVAL, "null argument");
+    *out = nullptr;
+    (void)mamdr::env_warn_unknown();
+    if (const int rc = validate_config(cfg)) return rc;
     mamdr_graph* g = new (std::nothrow) mamdr_graph();
     if (!g) return gfail(MAMDR_EHIP, "out of host memory");
     g->cfg = *cfg;
-    g->star = star;
+    g->star = cfg->kind == MAMDR_GRAPH_STAR;
     memset(&g->stab, 0, sizeof(g->stab));
-    if (star) {             // star.py:70-96 builds no dropout and no regulariser: the config's values are ignored
+    if (g->star) {          // star.py:70-96 builds no dropout and no regulariser: the config's values are ignored
         g->cfg.dropout = 0.f;
         g->cfg.l2_emb = 0.f;
         g->cfg.l2_linear = 0.f;
@@ -2767,7 +3260,6 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     }
     g->emb = cfg->emb_dim;
     g->stream = (hipStream_t)stream;
-    if (const char* ev = getenv("MAMDR_GRAPH_NO_GROUP")) g->group_ok = atoi(ev) == 0;
     if (const char* ev = getenv("MAMDR_GRAPH_NO_DEFER")) g->defer_w = atoi(ev) == 0;
     {
         const char* ev = getenv("MAMDR_GRAPH_TILE32_BELOW");
@@ -2775,291 +3267,28 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     }
     if (const char* ev = getenv("MAMDR_GRAPH_NO_TAIL_OPT")) g->tail_opt = atoi(ev) == 0;
     g->sink.p = nullptr;
-    if (const char* ev = getenv("MAMDR_GRAPH_WQ_BLOCKS")) g->wq_blocks = atoi(ev) > 0 ? atoi(ev) : g->wq_blocks;
-    g->gated = gated;
-    g->single = single;
-    g->has_lin = has_lin;
+    g->gated = cfg->kind == MAMDR_GRAPH_MMOE || cfg->kind == MAMDR_GRAPH_PLE;
+    g->single = cfg->kind >= MAMDR_GRAPH_NFM;
+    g->has_lin = cfg->kind == MAMDR_GRAPH_NFM || cfg->kind == MAMDR_GRAPH_CCPM || cfg->kind == MAMDR_GRAPH_AUTOINT ||
+                 cfg->kind == MAMDR_GRAPH_WDL || cfg->kind == MAMDR_GRAPH_DEEPFM;
     g->n_h = cfg->expert_hidden[cfg->n_expert_hidden - 1];
     g->data.resize((size_t)cfg->n_domain * 3);
-    // ---- flat vector: the block every task's model trains, then one block per task (oracle/mtl.py Spec.tensors)
-    uint32_t next_id = 0;
     g->tables = cfg->emb_trainable != 0;
     if (g->tables) {        // [user table | item table] contiguous at the head (k_emb_sweep walks them as one range)
         add_tensor(g, "user_emb", cfg->n_user, g->emb);
         add_tensor(g, "item_emb", cfg->n_item, g->emb);
-        if (has_lin) {      // their 1-d linear tables train with them (deepctr: same feature column)
+        if (g->has_lin) {   // their 1-d linear tables train with them (deepctr: same feature column)
             g->lin_u_off = add_tensor(g, "lin_user", cfg->n_user, 1);
             g->lin_i_off = add_tensor(g, "lin_item", cfg->n_item, 1);
         }
         g->table_floats = g->n_params;
     }
     g->dm_off = add_tensor(g, "domain_emb", cfg->n_domain, g->emb);
-    std::vector<int> shared;
-    for (int e = 0; e < n_shared; ++e) {
-        const std::string nm = cfg->kind == MAMDR_GRAPH_SHARED_BOTTOM ? "bottom"
-                               : (cfg->kind == MAMDR_GRAPH_MMOE ? "expert_" + std::to_string(e) : "shared_expert_" + std::to_string(e));
-        shared.push_back(add_dnn(g, nm, XDIM, cfg->expert_hidden, cfg->n_expert_hidden, next_id));
-    }
-    g->shared_end = g->n_params;
-    g->tasks.resize(single ? 1 : cfg->n_domain);
-    int max_cols = 0;
-    if (star) {
-        // oracle/star.param_names generalised: domain_emb | Ws0.. bs0.. (or W0.. b0..) | the norm's tensors | Wd0.. bd0.. | wo | gb |
-        // aux_W aux_b -- the reference's Star filter (emb, kernel_shared, bias_shared) selects a prefix
-        Task& t = g->tasks[0];
-        Dnn d;
-        d.name = "dnn";
-        d.in_dim = XDIM;
-        const bool sf = cfg->star_dense == 1;
-        const int nl = cfg->n_expert_hidden, D = cfg->n_domain, A = cfg->auxiliary_dim;
-        int in = XDIM;
-        for (int l = 0; l < nl; ++l) {
-            Layer L;
-            L.in = in;
-            L.out = cfg->expert_hidden[l];
-            L.w_off = add_tensor(g, (sf ? "Ws" : "W") + std::to_string(l), in, L.out);
-            L.b_off = 0;
-            L.id = (uint32_t)l;
-            d.layers.push_back(L);
-            in = L.out;
-        }
-        for (int l = 0; l < nl; ++l) d.layers[l].b_off = add_tensor(g, (sf ? "bs" : "b") + std::to_string(l), 1, d.layers[l].out);
-        if (cfg->star_norm == 1) {
-            g->norm_off[0] = add_tensor(g, "pn_gamma_shared", 1, XDIM);
-            g->norm_off[1] = add_tensor(g, "pn_beta_shared", 1, XDIM);
-            g->norm_off[2] = add_tensor(g, "pn_gamma_spec", D, XDIM);
-            g->norm_off[3] = add_tensor(g, "pn_beta_spec", D, XDIM);
-            g->aux_count = ((int64_t)4 * D * XDIM + D + 3) & ~(int64_t)3;
-        } else if (cfg->star_norm == 2) {
-            g->norm_off[0] = add_tensor(g, "bn_gamma", 1, XDIM);
-            g->norm_off[1] = add_tensor(g, "bn_beta", 1, XDIM);
-            g->aux_count = 2 * XDIM;
-        }
-        StarTab& st = g->stab;
-        auto add_seg = [&](int64_t shared, int64_t spec, int cnt, int op) {
-            st.shared[st.n] = shared;
-            st.spec[st.n] = spec;
-            st.cnt[st.n] = cnt;
-            st.op[st.n] = op;
-            st.first4[st.n + 1] = st.first4[st.n] + cnt / 4;
-            return st.n++;
-        };
-        if (sf) {
-            for (int l = 0; l < nl; ++l) {
-                const Layer& L = d.layers[l];
-                g->seg_k[l] = add_seg(L.w_off, add_tensor(g, "Wd" + std::to_string(l), (int64_t)D * L.in, L.out), L.in * L.out, SSEG_MUL);
-            }
-            for (int l = 0; l < nl; ++l) {
-                const Layer& L = d.layers[l];
-                g->seg_b[l] = add_seg(L.b_off, add_tensor(g, "bd" + std::to_string(l), D, L.out), L.out, SSEG_ADD);
-            }
-        }
-        g->dnns.push_back(d);
-        t.tower = 0;
-        t.head_w = add_tensor(g, "wo", in, 1);
-        t.head_gb = add_tensor(g, "gb", 1, 1);
-        if (A) {
-            g->seg_aw = add_seg(0, add_tensor(g, "aux_W", (int64_t)D * XDIM, A), XDIM * A, SSEG_COPY);
-            g->seg_ab = add_seg(0, add_tensor(g, "aux_b", D, A), A, SSEG_COPY);
-        }
-        g->shared_end = g->n_params;
-        t.blk_off = t.blk_end = g->n_params;
-        int c = XDIM;
-        if (cfg->star_norm) { g->xn_col = c; c += XDIM; }
-        t.path.push_back(0);
-        std::vector<int> cols;
-        for (const Layer& L : d.layers) { cols.push_back(c); c += L.out; }
-        t.col.push_back(cols);
-        if (A) {
-            g->a_col = c; c += A;
-            g->jtop_col = c; c += A;
-        }
-        t.n_cols = c;
-        max_cols = c;
-    } else if (single) {
-        // oracle/fmnets.py param_names: domain_emb | W0 W1 W2 | b0 b1 b2 | wo | gb | (NFM) lin_domain -- one block, all of it
-        // trained by every step.  NFM: DNN on the 128 interaction columns; PNN: on x (+ 3 inner products into W0's last rows)
-        Task& t = g->tasks[0];
-        Dnn d;
-        d.name = "dnn";
-        const int nfm = cfg->kind == MAMDR_GRAPH_NFM;
-        const bool ccpm = cfg->kind == MAMDR_GRAPH_CCPM;
-        if (ccpm) {         // conv1_w [6][4] | conv1_b [4] | conv2_w [4 in][4 out] | conv2_b [4]: 48 contiguous floats
-            g->conv_off = add_tensor(g, "conv1_w", 6, 4);
-            add_tensor(g, "conv1_b", 1, 4);
-            add_tensor(g, "conv2_w", 4, 4);
-            add_tensor(g, "conv2_b", 1, 4);
-        }
-        const bool autoint = cfg->kind == MAMDR_GRAPH_AUTOINT;
-        if (autoint) {      // [W_query | W_key | W_value | W_res] per layer: [128][128], then [32][128] twice
-            g->att_w[0] = add_tensor(g, "att0_w", EMB, ATT_P);
-            g->att_w[1] = add_tensor(g, "att1_w", ATT_OUT, ATT_P);
-            g->att_w[2] = add_tensor(g, "att2_w", ATT_OUT, ATT_P);
-        }
-        d.in_dim = nfm ? EMB : (ccpm ? 4 * EMB : 3 * g->emb);      // (NFM / CCPM: 128-wide fields only)
-        int in = d.in_dim;
-        for (int l = 0; l < cfg->n_expert_hidden; ++l) {
-            Layer L;
-            L.in = in;
-            L.out = cfg->expert_hidden[l];
-            L.w_off = add_tensor(g, "W" + std::to_string(l), (l == 0 && cfg->kind == MAMDR_GRAPH_PNN) ? in + 3 : in, L.out);
-            L.b_off = 0;
-            L.id = (uint32_t)l;
-            d.layers.push_back(L);
-            in = L.out;
-        }
-        for (int l = 0; l < cfg->n_expert_hidden; ++l) d.layers[l].b_off = add_tensor(g, "b" + std::to_string(l), 1, d.layers[l].out);
-        g->dnns.push_back(d);
-        t.tower = 0;
-        t.head_w = add_tensor(g, "wo", autoint ? 3 * ATT_OUT + in : in, 1);
-        t.head_gb = add_tensor(g, "gb", 1, 1);
-        if (has_lin) g->lin_d_off = add_tensor(g, "lin_domain", cfg->n_domain, 1);
-        if (cfg->uncertainty_weight) g->lv_off = add_tensor(g, "log_var", cfg->n_domain, 1);
-        g->shared_end = g->n_params;
-        t.blk_off = t.blk_end = g->n_params;
-        int c = 3 * g->emb;
-        g->f_col = c;
-        c += nfm ? EMB : (ccpm ? 4 * EMB : 4);
-        if (ccpm) { g->cg_col = c; c += 64; }
-        t.path.push_back(0);
-        std::vector<int> cols;
-        for (size_t l = 0; l < d.layers.size(); ++l) {
-            if (autoint && l + 1 == d.layers.size()) {      // head input = [attention output 96 | last DNN layer]
-                g->top_col = c;
-                c += 3 * ATT_OUT;
-            }
-            cols.push_back(c);
-            c += d.layers[l].out;
-        }
-        t.col.push_back(cols);
-        t.n_cols = c;
-        max_cols = c;
-    }
-    for (int d = 0; d < (single ? 0 : cfg->n_domain); ++d) {
-        Task& t = g->tasks[d];
-        t.blk_off = g->n_params;
-        for (int e = 0; e < n_specific; ++e)
-            t.mix.push_back(add_dnn(g, "task_" + std::to_string(d) + "_expert_" + std::to_string(e), XDIM, cfg->expert_hidden,
-                                    cfg->n_expert_hidden, next_id));
-        for (int s : shared) t.mix.push_back(s);
-        if (gated) {
-            t.gate = add_dnn(g, "gate_" + std::to_string(d), XDIM, cfg->gate_hidden, cfg->n_gate_hidden, next_id);
-            t.wg_off = add_tensor(g, "gate_" + std::to_string(d) + "/Wg", cfg->gate_hidden[cfg->n_gate_hidden - 1], (int64_t)t.mix.size());
-        }
-        t.tower = add_dnn(g, "tower_" + std::to_string(d), g->n_h, cfg->tower_hidden, cfg->n_tower_hidden, next_id);
-        t.head_w = add_tensor(g, "head_" + std::to_string(d) + "/w", cfg->tower_hidden[cfg->n_tower_hidden - 1], 1);
-        t.head_gb = add_tensor(g, "head_" + std::to_string(d) + "/gb", 1, 1);
-        t.blk_end = g->n_params;
-        // column plan: x | every layer output on the path | gate probabilities | mixture
-        int c = XDIM;
-        t.path = t.mix;
-        if (gated) t.path.push_back(t.gate);
-        t.path.push_back(t.tower);
-        for (int di : t.path) {
-            std::vector<int> cols;
-            for (const Layer& L : g->dnns[di].layers) { cols.push_back(c); c += L.out; }
-            t.col.push_back(cols);
-        }
-        if (gated) {
-            t.g_col = c; c += ((int)t.mix.size() + 3) & ~3;
-            t.m_col = c; c += g->n_h;
-        }
-        t.n_cols = c;
-        if (c > max_cols) max_cols = c;
-    }
+    g->tasks.resize(g->single ? 1 : cfg->n_domain);
+    const int max_cols = g->single ? layout_one_task(g) : layout_multi_task(g);
     g->ld = (max_cols + 3) & ~3;
     g->rows_pad_max = (cfg->max_batch + GT - 1) / GT * GT;
-    float thr[500];
-    thr[0] = (float)(0.0 - 1e-7);
-    for (int i = 0; i < 498; ++i) thr[i + 1] = (float)((double)(i + 1) * 1.0 / (double)(500 - 1));
-    thr[499] = (float)(1.0 + 1e-7);
-    const size_t rp = (size_t)g->rows_pad_max;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
-    alloc((void**)&g->act, rp * g->ld * sizeof(float));
-    alloc((void**)&g->dact, rp * g->ld * sizeof(float));
-    alloc((void**)&g->grad, (size_t)(g->n_params - g->table_floats) * sizeof(float));
-    size_t max_w = (size_t)EMB * ATT_P;
-    for (const Dnn& d : g->dnns)
-        for (const Layer& L : d.layers) max_w = std::max(max_w, (size_t)L.in * L.out);
-    g->wpart_floats = 16 * max_w;
-    if (g->defer_w) {       // the queue holds every problem's partial products at once: 8 splits of the widest step's kernels
-        size_t max_path = 3 * (size_t)EMB * ATT_P;
-        for (const Task& t : g->tasks) {
-            size_t w = cfg->kind == MAMDR_GRAPH_AUTOINT ? 3 * (size_t)EMB * ATT_P : 0;
-            for (int id : t.path)
-                for (const Layer& L : g->dnns[id].layers) w += (size_t)L.in * L.out;
-            max_path = std::max(max_path, w);
-        }
-        g->wpart_floats = std::max(g->wpart_floats, 8 * max_path);
-    }
-    if (star && cfg->auxiliary_dim) g->wpart_floats += 16 * (size_t)XDIM * cfg->auxiliary_dim;       // the auxiliary kernel's splits
-    alloc((void**)&g->wpart, g->wpart_floats * sizeof(float));
-    if (star) {
-        if (g->stab.n) {
-            alloc((void**)&g->eff, 4 * (size_t)g->stab.first4[g->stab.n] * sizeof(float));
-            alloc((void**)&g->deff, 4 * (size_t)g->stab.first4[g->stab.n] * sizeof(float));
-        }
-        if (cfg->star_norm) {
-            alloc((void**)&g->spart, (rp + SN_ROWS - 1) / SN_ROWS * 2 * XDIM * sizeof(double));
-            alloc((void**)&g->pnv, 3 * XDIM * sizeof(float));
-        }
-    }
-    size_t max_mix = 0;
-    for (const Task& t : g->tasks) max_mix = std::max(max_mix, t.mix.size());
-    if (g->gated && g->group_ok && max_mix > 1) {
-        g->dxpart_floats = max_mix * rp * (size_t)(g->tables ? XDIM : EMB);
-        alloc((void**)&g->dxpart, g->dxpart_floats * sizeof(float));
-    }
-    if (g->tables) {
-        alloc((void**)&g->urow, rp * sizeof(int32_t));
-        alloc((void**)&g->irow, rp * sizeof(int32_t));
-        alloc((void**)&g->hasdup_u, rp * sizeof(int32_t));
-        alloc((void**)&g->hasdup_i, rp * sizeof(int32_t));
-        alloc((void**)&g->map_u, (size_t)cfg->n_user * sizeof(int32_t));
-        alloc((void**)&g->map_i, (size_t)cfg->n_item * sizeof(int32_t));
-        alloc((void**)&g->gbuf_u, rp * g->emb * sizeof(float));
-        alloc((void**)&g->gbuf_i, rp * g->emb * sizeof(float));
-    }
-    alloc((void**)&g->dlogit, rp * sizeof(float));
-    alloc((void**)&g->rowloss, rp * sizeof(float));
-    alloc((void**)&g->y, rp * sizeof(float));
-    alloc((void**)&g->domrow, rp * sizeof(int32_t));
-    alloc((void**)&g->thresholds, sizeof(thr));
-    alloc((void**)&g->frozen_sumsq, 4 * sizeof(float));
-    alloc((void**)&g->sumsq_partials, 1024 * sizeof(float));
-    alloc((void**)&g->eval_acc, 4 * sizeof(float));
-    if (cfg->kind == MAMDR_GRAPH_AUTOINT) {
-        alloc((void**)&g->xt, rp * XDIM * sizeof(float));
-        alloc((void**)&g->dxt, rp * XDIM * sizeof(float));
-        for (int l = 0; l < 3; ++l) {
-            alloc((void**)&g->attP[l], 3 * rp * ATT_P * sizeof(float));
-            alloc((void**)&g->attdP[l], 3 * rp * ATT_P * sizeof(float));
-            alloc((void**)&g->attA[l], rp * 36 * sizeof(float));
-            alloc((void**)&g->attY[l], 3 * rp * ATT_OUT * sizeof(float));
-            alloc((void**)&g->attdY[l], 3 * rp * ATT_OUT * sizeof(float));
-        }
-    }
-    if (has_lin) {
-        alloc((void**)&g->extra, rp * sizeof(float));
-        if (g->tables) {
-            alloc((void**)&g->glin_u, rp * sizeof(float));
-            alloc((void**)&g->glin_i, rp * sizeof(float));
-        }
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(g->grad, 0, (size_t)(g->n_params - g->table_floats) * sizeof(float), g->stream);
-    if (g->tables && e == hipSuccess) {
-        e = hipMemsetAsync(g->hasdup_u, 0, rp * sizeof(int32_t), g->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(g->hasdup_i, 0, rp * sizeof(int32_t), g->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(g->urow, 0xff, rp * sizeof(int32_t), g->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(g->irow, 0xff, rp * sizeof(int32_t), g->stream);
-        launch_emb_map_init(g->map_u, cfg->n_user, g->stream);
-        launch_emb_map_init(g->map_i, cfg->n_item, g->stream);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(g->dact, 0, rp * g->ld * sizeof(float), g->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(g->frozen_sumsq, 0, 4 * sizeof(float), g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(g->thresholds, thr, sizeof(thr), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
+    const hipError_t e = alloc_workspace(g);
     if (e != hipSuccess) {
         mamdr_graph_destroy(g);
         return gfail(MAMDR_EHIP, "workspace: %s", hipGetErrorString(e));
@@ -3071,13 +3300,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
 int mamdr_graph_destroy(mamdr_graph* g) {
     if (!g) return MAMDR_OK;
     (void)hipStreamSynchronize(g->stream);
-    void* ptrs[] = {g->act, g->dact, g->grad, g->dlogit, g->rowloss, g->y, g->domrow, g->thresholds, g->frozen_sumsq,
-                    g->sumsq_partials, g->eval_acc, g->urow, g->irow, g->map_u, g->map_i, g->hasdup_u, g->hasdup_i,
-                    g->gbuf_u, g->gbuf_i, g->extra, g->glin_u, g->glin_i, g->xt, g->dxt, g->wpart, g->dxpart,
-                    g->attP[0], g->attP[1], g->attP[2], g->attdP[0], g->attdP[1], g->attdP[2], g->attA[0], g->attA[1], g->attA[2],
-                    g->attY[0], g->attY[1], g->attY[2], g->attdY[0], g->attdY[1], g->attdY[2], g->eff, g->deff, g->pnv, g->spart};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    for (void* p : g->allocs) (void)hipFree(p);
     delete g;
     return MAMDR_OK;
 }
@@ -3232,348 +3455,27 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
                      (long long)(first_step + n_steps), (long long)pass_steps, domain);
     if (n_steps == 0) return MAMDR_OK;
     const Task& t = g->tasks[g->single ? 0 : domain];
-    const float rate = g->cfg.dropout;
-    double thr = (double)rate * 4294967296.0;
-    const float omb1 = 1.0f - g->cfg.adam_beta1, omb2 = 1.0f - g->cfg.adam_beta2;
-    // DIAGNOSTIC (MAMDR_GRAPH_DIAG_REPLAY=1, wrong values, right timing): the second step of a call is captured into a
-    // hipGraph and REPLAYED for the full-batch steps that follow -- what a step costs when the host issues one graph launch
-    // instead of ~21 kernel launches (launch-rate sensitivity)
-    // Compiled in only with -DMAMDR_DIAG (tools/build_variant.sh): a production build that finds the variable set says so
-    // once and ignores it -- a replayed step reuses the captured batch, dropout position and Adam alpha.
-#ifdef MAMDR_DIAG
-    static const bool diag_replay = getenv("MAMDR_GRAPH_DIAG_REPLAY") && atoi(getenv("MAMDR_GRAPH_DIAG_REPLAY")) != 0;
-#else
-    constexpr bool diag_replay = false;
-    static const bool diag_warned = []() {
-        if (getenv("MAMDR_GRAPH_DIAG_REPLAY") && atoi(getenv("MAMDR_GRAPH_DIAG_REPLAY")) != 0)
-            fprintf(stderr, "mamdr: MAMDR_GRAPH_DIAG_REPLAY is a diagnostic of -DMAMDR_DIAG builds (wrong values by design); ignored\n");
-        return true;
-    }();
-    (void)diag_warned;
-#endif
-    hipGraph_t dgraph = nullptr;
-    hipGraphExec_t dexec = nullptr;
     for (int64_t s = 0; s < n_steps; ++s) {
         const int64_t row_base = (first_step + s) * batch;
         g->wq.clear();          // (a step that failed half-way leaves its queues behind)
         g->tq.clear();
-        if (diag_replay && dexec && pass_rows - row_base >= batch) {
-            (void)hipGraphLaunch(dexec, g->stream);
-            g->global_step += 1;
-            continue;
-        }
-        const bool capturing = diag_replay && !dexec && s == 1 && pass_rows - row_base >= batch && !d_loss_out;
-        if (capturing) (void)hipStreamBeginCapture(g->stream, hipStreamCaptureModeThreadLocal);
-        struct EndCap {
-            bool on; hipStream_t st; hipGraph_t* gr; hipGraphExec_t* ex;
-            ~EndCap() {
-                if (!on) return;
-                if (hipStreamEndCapture(st, gr) == hipSuccess && hipGraphInstantiate(ex, *gr, nullptr, nullptr, 0) == hipSuccess)
-                    (void)hipGraphLaunch(*ex, st);
-            }
-        } endcap{capturing, g->stream, &dgraph, &dexec};
-        StepCtx sc;
-        sc.rows = (int)((pass_rows - row_base) < batch ? (pass_rows - row_base) : batch);
-        sc.rp = (sc.rows + GT - 1) / GT * GT;
-        sc.train = true;
-        sc.seed = dropout_seed;
-        sc.step = g->global_step;
-        sc.drop_thresh = thr >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)(int64_t)thr;
-        sc.keep_scale = (float)(1.0 / (1.0 - (double)rate));
-        sc.use_dropout = rate > 0.f && optimizer != MAMDR_OPT_ACCUMULATE;     // the meta pass runs in learning phase 0 (maml.py:107-109)
-        if (!sc.use_dropout) sc.keep_scale = 1.0f;
-        float alpha = lr;
-        if (optimizer == MAMDR_OPT_ADAM) {      // ONE optimizer object for all domain models: its beta powers advance every step
-            g->adam_t += 1;
-            g->b1p *= g->cfg.adam_beta1;
-            g->b2p *= g->cfg.adam_beta2;
-            alpha = lr * sqrtf(1.0f - g->b2p) / (1.0f - g->b1p);
-        }
-        // (Star forms: their weight gradients land in scratch and pass through k_star_chain -- k_graph_adam steps the vector)
-        const bool fuse_opt = g->defer_w && g->tail_opt && g->lv_off < 0 && !g->star;
-        g->sink.p = nullptr;
-        if (fuse_opt) {
-            g->sink.g_base = g->grad;
-            g->sink.p = g->params + g->table_floats;
-            g->sink.m = (optimizer == MAMDR_OPT_ACCUMULATE ? g->accum : g->adam_m) + g->table_floats;
-            g->sink.v = g->adam_v + g->table_floats;
-            g->sink.optimizer = optimizer;
-            g->sink.alpha = alpha;
-            g->sink.omb1 = omb1;
-            g->sink.omb2 = omb2;
-            g->sink.eps = g->cfg.adam_eps;
-        }
-        GatherArgs ga;
-        fill_gather(g, *d, d_perm, row_base, sc, ga);
-        launch_graph_gather(ga, g->emb, g->stream);
+        const StepCtx sc = step_ctx(g, pass_rows, row_base, batch, true, dropout_seed, optimizer != MAMDR_OPT_ACCUMULATE);
+        const OptStep opt = advance_optimizer(g, optimizer, lr);
+        open_sink(g, opt);
+        launch_gather(g, *d, d_perm, row_base, sc);
         const int t_col = task_forward(g, t, sc);
-        const Dnn& tower = g->dnns[t.tower];
-        HeadArgs ha;
-        memset(&ha, 0, sizeof(ha));
-        ha.act = g->act;
-        ha.dact = g->dact;
-        ha.ld = g->ld;
-        ha.t_col = t_col;
-        ha.n_t = tower.layers.back().out;
-        if (g->cfg.kind == MAMDR_GRAPH_AUTOINT) {       // head on [attention output | last DNN layer]
-            ha.n_t += 3 * ATT_OUT;
-            ha.n_plain = 3 * ATT_OUT;
-        }
-        ha.w = g->params + t.head_w;
-        ha.gb = g->params + t.head_gb;
-        ha.y = g->y;
-        ha.rows = sc.rows;
-        ha.rows_pad = sc.rp;
-        ha.dlogit = g->dlogit;
-        ha.rowloss = g->rowloss;
-        ha.extra = g->extra;
-        ha.train = 1;
-        ha.gate_scale = sc.keep_scale;
-        const bool weighted = g->lv_off >= 0;
-        if (weighted) {
-            ha.log_var = g->params + g->lv_off;
-            ha.domrow = g->domrow;
-        }
-        GLAUNCH(k_graph_head, dim3(sc.rp / 4), dim3(256), 0, g->stream, ha);
+        const int n_t = launch_head(g, t, sc, t_col, nullptr, nullptr);
         if (d_loss_out && g->tables) refresh_sumsq(g);
-        if (d_loss_out || weighted)     // the weighted loss takes d / d log_var from the batch's mean BCE: this launch, always
-            GLAUNCH(k_graph_loss, dim3(1), dim3(256), 0, g->stream, g->rowloss, sc.rows, g->params + g->dm_off,
-                               g->cfg.n_domain * g->emb, g->cfg.l2_emb, g->frozen_sumsq, d_loss_out ? d_loss_out + s : g->eval_acc + 1, 0,
-                               g->extra ? g->params + g->lin_d_off : nullptr, g->cfg.n_domain, g->cfg.l2_linear,
-                               weighted ? g->params + g->lv_off : nullptr, g->domrow, weighted ? g->G(g->lv_off) : nullptr,
-                               g->cfg.n_domain);
-        // ---- backward
-        // head: dw = t^T dlogit, dgb = sum dlogit
-        small_tn(g, g->act + t_col, g->ld, g->dlogit, 1,
-                           sc.rp, ha.n_t, 1, g->G(t.head_w), g->G(t.head_gb));
-        const size_t ti = t.path.size() - 1;
-        // the x columns of the gradient workspace collect d x from every first layer (the domain columns alone while the
-        // tables are frozen): the first writer overwrites, the others add
-        bool dx_started = false;
-        const int dx_first = g->tables ? 0 : 2 * g->emb, dx_n = g->tables ? 0 : g->emb;
-        if (g->star) {
-            star_backward(g, t, sc);
-        } else if (g->single && g->cfg.kind == MAMDR_GRAPH_AUTOINT) {
-            // DNN on x as any first layer; then the attention stack from the head's d [attention output] down to d x
-            dnn_backward(g, tower, t.col[0], 0, 0, -1, false, dx_first, dx_n, sc);
-            for (int l = 2; l >= 0; --l) {
-                const int d_in = l == 0 ? EMB : ATT_OUT;
-                AttArgs aa;
-                memset(&aa, 0, sizeof(aa));
-                aa.P = g->attP[l];
-                aa.A = g->attA[l];
-                aa.Y = g->attY[l];
-                aa.dY = g->attdY[l];
-                aa.dP = g->attdP[l];
-                aa.rows_pad = sc.rp;
-                if (l == 2) {
-                    aa.dtop = g->dact + g->top_col;
-                    aa.dtop_ld = g->ld;
-                }
-                GLAUNCH(k_graph_att_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, aa);
-                const float* xin = l == 0 ? g->xt : g->attY[l - 1];
-                if (l == 0) {
-                    GemmArgs a;
-                    memset(&a, 0, sizeof(a));
-                    a.A = xin;                      // dW = X^T dP over the 3 B token rows
-                    a.lda = d_in;
-                    a.B = g->attdP[l];
-                    a.ldb = ATT_P;
-                    a.C = g->G(g->att_w[l]);
-                    a.ldc = ATT_P;
-                    launch_wgrad(g, a, d_in, ATT_P, 3 * sc.rp, nullptr, nullptr);
-                    memset(&a, 0, sizeof(a));
-                    a.A = g->attdP[l];              // d X = dP W^T
-                    a.lda = ATT_P;
-                    a.B = g->params + g->att_w[l];
-                    a.ldb = ATT_P;
-                    a.C = g->dxt;
-                    a.ldc = d_in;
-                    a.K = ATT_P;
-                    launch_gemm(1, a, 3 * sc.rp, d_in, g->stream);
-                    const int first = g->tables ? 0 : 2 * EMB, n = g->tables ? XDIM : EMB;
-                    GLAUNCH(k_graph_add_x, dim3((sc.rp * n + 255) / 256), dim3(256), 0, g->stream, g->dact, g->ld, g->dxt,
-                                       sc.rp, first, n);
-                } else {
-                    small_tn(g, xin, d_in,
-                                       g->attdP[l], ATT_P, 3 * sc.rp, d_in, ATT_P, g->G(g->att_w[l]));
-                    if (use_tile32(3 * sc.rp, d_in)) {      // d Y[l-1] = d P . W^T, [3 B x 128] x [32 x 128]^T
-                        GemmArgs a;
-                        memset(&a, 0, sizeof(a));
-                        a.A = g->attdP[l];
-                        a.lda = ATT_P;
-                        a.B = g->params + g->att_w[l];
-                        a.ldb = ATT_P;
-                        a.C = g->attdY[l - 1];
-                        a.ldc = d_in;
-                        a.K = ATT_P;
-                        launch_gemm(1, a, 3 * sc.rp, d_in, g->stream);
-                    } else {
-                        GLAUNCH(k_graph_small_nt, dim3((3 * sc.rp * d_in + 255) / 256), dim3(256), 0, g->stream, g->attdP[l],
-                                ATT_P, g->params + g->att_w[l], d_in, 3 * sc.rp, g->attdY[l - 1]);
-                    }
-                }
-            }
-            if (!g->defer_w) launch_lin_domain_grad(g->stream, g->dlogit,
-                               g->domrow, sc.rows, g->params + g->lin_d_off, 2.0f * g->cfg.l2_linear, g->cfg.n_domain,
-                               g->G(g->lin_d_off));
-        } else if (g->single && g->cfg.kind == MAMDR_GRAPH_CCPM) {
-            // d features from the first layer; the convolutions' backward per row; their 48 gradients summed over the batch
-            dnn_backward(g, tower, t.col[0], g->f_col, g->f_col, -1, false, 0, 0, sc);
-            CcpmArgs ca;
-            fill_ccpm(g, sc, ca);
-            GLAUNCH(k_graph_ccpm_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, ca);
-            if (g->defer_w)     // the 48 column sums as a queue entry without a contraction (its end = the bias-gradient workgroups)
-                queue_wgrad(g, nullptr, 0, nullptr, 0, nullptr, 0, 48, sc.rp, g->dact + g->cg_col, g->G(g->conv_off));
-            else
-                launch_colsum(g->stream, g->dact + g->cg_col, g->ld, sc.rp, g->G(g->conv_off), 48);
-            if (!g->defer_w) launch_lin_domain_grad(g->stream, g->dlogit,
-                               g->domrow, sc.rows, g->params + g->lin_d_off, 2.0f * g->cfg.l2_linear, g->cfg.n_domain,
-                               g->G(g->lin_d_off));
-        } else if (g->single && (g->cfg.kind == MAMDR_GRAPH_MLP || g->cfg.kind == MAMDR_GRAPH_WDL ||
-                                 g->cfg.kind == MAMDR_GRAPH_DEEPFM)) {
-            // the DNN on x as any first layer (deepctr.py:26-32,36-38 with any hidden_dim); DeepFM: + the FM term's d x
-            dnn_backward(g, tower, t.col[0], 0, 0, -1, false, dx_first, dx_n, sc);
-            if (g->cfg.kind == MAMDR_GRAPH_DEEPFM) {
-                FeatArgs fa;
-                fill_feat(g, t, sc, fa);
-                switch (g->emb) {
-                    case 32: GLAUNCH(k_graph_fm_bwd<32>, dim3(sc.rp / 32), dim3(256), 0, g->stream, fa); break;
-                    case 64: GLAUNCH(k_graph_fm_bwd<64>, dim3(sc.rp / 16), dim3(256), 0, g->stream, fa); break;
-                    case 256: GLAUNCH(k_graph_fm_bwd<256>, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
-                    default: GLAUNCH(k_graph_feat_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa); break;
-                }
-            }
-            if (g->has_lin && !g->defer_w)
-                launch_lin_domain_grad(g->stream, g->dlogit, g->domrow, sc.rows, g->params + g->lin_d_off, 2.0f * g->cfg.l2_linear,
-                                       g->cfg.n_domain, g->G(g->lin_d_off));
-        } else if (g->single) {
-            const bool nfm = g->cfg.kind == MAMDR_GRAPH_NFM;
-            FeatArgs fa;
-            fill_feat(g, t, sc, fa);
-            if (nfm) {
-                // d(interaction columns) from the first layer, then d x = df (sum of the other two fields)
-                dnn_backward(g, tower, t.col[0], g->f_col, g->f_col, -1, false, 0, 0, sc);
-            } else {
-                // rows 0..383 of the first kernel as any first layer on x; rows 384..386 against the inner products
-                dnn_backward(g, tower, t.col[0], 0, 0, -1, false, dx_first, dx_n, sc);
-                const Layer& L0 = tower.layers[0];
-                small_tn(g, g->act + g->f_col, g->ld,
-                                   g->dact + t.col[0][0], g->ld, sc.rp, 3, L0.out, g->G(L0.w_off + (int64_t)L0.in * L0.out));
-            }
-            GLAUNCH(k_graph_feat_bwd, dim3(sc.rp / 4), dim3(256), 0, g->stream, fa);
-            if (nfm)
-                if (!g->defer_w) launch_lin_domain_grad(g->stream, g->dlogit,
-                                   g->domrow, sc.rows, g->params + g->lin_d_off, 2.0f * g->cfg.l2_linear, g->cfg.n_domain,
-                                   g->G(g->lin_d_off));
-        } else if (g->gated) {
-            dnn_backward(g, tower, t.col[ti], t.m_col, t.m_col, -1, false, 0, 0, sc);
-            GateArgs gta;
-            fill_gate(g, t, sc, gta);
-            GLAUNCH(k_graph_gate_bwd, dim3(sc.rp), dim3(256), 0, g->stream, gta);
-            const size_t gi = t.mix.size();
-            const Dnn& gd = g->dnns[t.gate];
-            small_tn(g, g->act + gta.q_col,
-                               g->ld, g->dact + t.g_col, g->ld, sc.rp, gta.n_q, gta.n_e, g->G(t.wg_off));
-            dnn_backward(g, gd, t.col[gi], 0, 0, -1, dx_started, dx_first, dx_n, sc);
-            dx_started = true;
-            if (g->group_ok && same_shape(g, t.mix)) {
-                std::vector<std::vector<int>> mc(t.col.begin(), t.col.begin() + t.mix.size());
-                dnn_backward_group(g, t.mix, mc, 0, dx_started, dx_first, dx_n, sc);
-                dx_started = true;
-            } else {
-                for (size_t e = 0; e < t.mix.size(); ++e) {
-                    dnn_backward(g, g->dnns[t.mix[e]], t.col[e], 0, 0, -1, dx_started, dx_first, dx_n, sc);
-                    dx_started = true;
-                }
-            }
-        } else {
-            // the tower's input IS the bottom's output: its gradient passes through the bottom's last relu / dropout gate
-            dnn_backward(g, tower, t.col[ti], t.col[0].back(), t.col[0].back(), t.col[0].back(), false, 0, 0, sc);
-            dnn_backward(g, g->dnns[t.mix[0]], t.col[0], 0, 0, -1, false, dx_first, dx_n, sc);
-        }
-        if (g->defer_w) {       // every layer's dW / db of this step, the narrow contractions, the domain table's gradient:
-            const bool lin = g->single && g->has_lin;
-            const DomainGradJob dg{g->dact, g->ld, 2 * g->emb, g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb,
-                                   g->G(g->dm_off), g->cfg.n_domain, g->emb, g->dlogit, lin ? g->params + g->lin_d_off : nullptr,
-                                   2.0f * g->cfg.l2_linear, lin ? g->G(g->lin_d_off) : nullptr};      // one pair of launches
-            flush_wgrads(g, &dg);
-        } else {
-            GLAUNCH(k_graph_domain_grad, dim3(g->emb / CS_COLS, g->cfg.n_domain), dim3(256), 0, g->stream, g->dact, g->ld, 2 * g->emb,
-                    g->domrow, sc.rows, g->params + g->dm_off, 2.0f * g->cfg.l2_emb, g->G(g->dm_off), g->emb);
-        }
-        if (g->star && g->stab.n)       // scratch gradients -> the flat gradient (zeros for the other domains' slices)
-            GLAUNCH(k_star_chain, dim3((g->stab.first4[g->stab.n] + 255) / 256), dim3(256), 0, g->stream, g->stab, g->params,
-                    g->domrow, g->deff, g->grad - g->table_floats, g->cfg.n_domain);
-        if (g->tables) {
-            // TF1's dense step over both tables: g = 2 l2 p + scatter-add of d x[:, user | item columns]
-            EmbStepArgs ea;
-            memset(&ea, 0, sizeof(ea));
-            float* const slot_m = optimizer == MAMDR_OPT_ACCUMULATE ? g->accum : g->adam_m;
-            ea.p = g->params;
-            ea.m = slot_m;
-            ea.v = g->adam_v;
-            ea.dxe = g->dact;
-            ea.dx_ld = g->ld;
-            ea.dlogit = g->dlogit;
-            ea.rows = sc.rows;
-            ea.opt.optimizer = optimizer;
-            ea.opt.alpha = alpha;
-            ea.opt.omb1 = omb1;
-            ea.opt.omb2 = omb2;
-            ea.opt.eps = g->cfg.adam_eps;
-            ea.opt.two_l2 = 2.0f * g->cfg.l2_emb;
-            ea.t[0].n_rows = g->cfg.n_user;
-            ea.t[0].brow = g->urow;
-            ea.t[0].map = g->map_u;
-            ea.t[0].gbuf = g->gbuf_u;
-            ea.t[0].hasdup = g->hasdup_u;
-            ea.t[0].dx_off = 0;
-            ea.t[1].n_rows = g->cfg.n_item;
-            ea.t[1].brow = g->irow;
-            ea.t[1].map = g->map_i;
-            ea.t[1].gbuf = g->gbuf_i;
-            ea.t[1].hasdup = g->hasdup_i;
-            ea.t[1].dx_off = g->emb;
-            if (g->has_lin) {       // their 1-d linear tables: scatter-add of d loss / d logit, same rule
-                ea.two_l2_lin = 2.0f * g->cfg.l2_linear;
-                ea.t[0].lin_p = g->params + g->lin_u_off;
-                ea.t[0].lin_m = slot_m + g->lin_u_off;
-                ea.t[0].lin_v = g->adam_v + g->lin_u_off;
-                ea.t[0].glin = g->glin_u;
-                ea.t[1].lin_p = g->params + g->lin_i_off;
-                ea.t[1].lin_m = slot_m + g->lin_i_off;
-                ea.t[1].lin_v = g->adam_v + g->lin_i_off;
-                ea.t[1].glin = g->glin_i;
-            }
-            launch_emb_reduce(ea, g->stream, g->emb);
-            launch_emb_sweep(ea, g->stream, g->emb);
-            if (g->has_lin) launch_lin_sweep(ea, g->stream);      // (reads the row maps, then resets them)
-        }
-        // ---- optimiser on the two ranges this task's model trains (one launch; none when the tail launch stepped them)
-        if (!fuse_opt || !g->sink.p) {      // (sink dropped: a queue overflowed in mid-step)
-            const int64_t off[2] = {g->dm_off, t.blk_off}, cnt[2] = {g->shared_end - g->dm_off, t.blk_end - t.blk_off};
-            AdamArgs aa;
-            aa.p = g->params;
-            aa.m = optimizer == MAMDR_OPT_ACCUMULATE ? g->accum : g->adam_m;
-            aa.v = g->adam_v;
-            aa.g = g->grad - g->table_floats;       // G(off) = grad + off - table_floats
-            for (int k = 0; k < 2; ++k) {
-                aa.off4[k] = off[k] / 4;
-                aa.n4[k] = cnt[k] / 4;
-            }
-            aa.optimizer = optimizer;
-            aa.alpha = alpha;
-            aa.omb1 = omb1;
-            aa.omb2 = omb2;
-            aa.eps = g->cfg.adam_eps;
-            const int64_t n4 = aa.n4[0] + aa.n4[1];
-            if (n4 > 0) GLAUNCH(k_graph_adam, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, g->stream, aa);
-        }
+        if (d_loss_out || g->lv_off >= 0)       // the weighted loss takes d / d log_var from the batch's mean BCE: this launch, always
+            launch_loss(g, sc, d_loss_out ? d_loss_out + s : g->eval_acc + 1, false);
+        small_tn(g, g->act + t_col, g->ld, g->dlogit, 1, sc.rp, n_t, 1, g->G(t.head_w), g->G(t.head_gb));   // head: dw = t^T dlogit, dgb = sum dlogit
+        task_backward(g, t, sc);
+        finish_grads(g, sc);
+        if (g->star) star_chain(g);
+        if (g->tables) table_step(g, sc, opt);
+        if (!g->sink.p) adam_step(g, t, opt);   // (closed from the start, or dropped: a queue overflowed in mid-step)
         g->global_step += 1;
     }
-    if (dexec) (void)hipGraphExecDestroy(dexec);
-    if (dgraph) (void)hipGraphDestroy(dgraph);
     GHIP(hipGetLastError());
     return MAMDR_OK;
 }
@@ -3600,39 +3502,12 @@ int mamdr_graph_eval_domain(mamdr_graph* g, int domain, int split, int32_t batch
     if (g->tables) refresh_sumsq(g);
     const int64_t n_batches = (d->n + batch - 1) / batch;
     for (int64_t b = 0; b < n_batches; ++b) {
-        StepCtx sc;
-        memset(&sc, 0, sizeof(sc));
         const int64_t row_base = b * batch;
-        sc.rows = (int)((d->n - row_base) < batch ? (d->n - row_base) : batch);
-        sc.rp = (sc.rows + GT - 1) / GT * GT;
-        sc.keep_scale = 1.0f;
-        GatherArgs ga;
-        fill_gather(g, *d, nullptr, row_base, sc, ga);
-        launch_graph_gather(ga, g->emb, g->stream);
+        const StepCtx sc = step_ctx(g, d->n, row_base, batch, false, 0, false);
+        launch_gather(g, *d, nullptr, row_base, sc);
         const int t_col = task_forward(g, t, sc);
-        HeadArgs ha;
-        memset(&ha, 0, sizeof(ha));
-        ha.act = g->act;
-        ha.dact = g->dact;
-        ha.ld = g->ld;
-        ha.t_col = t_col;
-        ha.n_t = g->dnns[t.tower].layers.back().out + (g->cfg.kind == MAMDR_GRAPH_AUTOINT ? 3 * ATT_OUT : 0);
-        ha.w = g->params + t.head_w;
-        ha.gb = g->params + t.head_gb;
-        ha.y = g->y;
-        ha.rows = sc.rows;
-        ha.rows_pad = sc.rp;
-        ha.dlogit = g->dlogit;
-        ha.rowloss = g->rowloss;
-        ha.extra = g->extra;
-        ha.gate_scale = 1.0f;
-        ha.thresholds = g->thresholds;
-        ha.hist = d_hist;
-        ha.pred_out = d_pred_out ? d_pred_out + row_base : nullptr;
-        GLAUNCH(k_graph_head, dim3(sc.rp / 4), dim3(256), 0, g->stream, ha);
-        GLAUNCH(k_graph_loss, dim3(1), dim3(256), 0, g->stream, g->rowloss, sc.rows, g->params + g->dm_off,
-                           g->cfg.n_domain * g->emb, g->cfg.l2_emb, g->frozen_sumsq, g->eval_acc, 1,
-                           g->extra ? g->params + g->lin_d_off : nullptr, g->cfg.n_domain, g->cfg.l2_linear);
+        launch_head(g, t, sc, t_col, d_hist, d_pred_out ? d_pred_out + row_base : nullptr);
+        launch_loss(g, sc, g->eval_acc, true);
     }
     GLAUNCH(k_graph_scale, dim3(1), dim3(1), 0, g->stream, g->eval_acc, 1.0f / (float)n_batches);
     GHIP(hipMemcpyAsync(d_loss_out, g->eval_acc, sizeof(float), hipMemcpyDeviceToDevice, g->stream));

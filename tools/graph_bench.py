@@ -96,8 +96,6 @@ for cfg_name in TOWERS + tuple(n for n in (ONLY or ()) if n not in TOWERS):
     if HIDDEN is not None:
         cfg["model"]["hidden_dim"] = HIDDEN
     ds = MultiDomainDataset(cfg["dataset"])
-    if os.environ.get("MAMDR_GRAPH_DIAG_REPLAY"):      # stream capture needs a stream of its own (not the legacy default one)
-        torch.cuda.set_stream(torch.cuda.Stream())
     model = cli.build_model(cfg, ds)
     eng = model.model
     D = ds.n_domain

@@ -11,7 +11,9 @@ Keras model:
     K.batch_get_value(vars)     -> get_weights / weights      (maml.py:189-194)
     SetVarOp(vars)(values)      -> set_weights                (utils/tool.py:36-45)
 
-plus the outer-update primitives on flat vectors.  No CPU fallback exists.
+plus the outer-update primitives on flat vectors (`FlatVectorOps`).  `DeviceEngine` holds what `TowerEngine` and
+`graph_engine.GraphEngine` do alike over their two entry-point families; `keras_names` is the one table of Keras
+variable names behind the reference's name filters.  No CPU fallback exists.
 """
 import ctypes as C
 
@@ -174,24 +176,267 @@ class FlatVectorOps(object):
         L.check(self.lib.mamdr_pcgrad_project(_ptr(final), _ptr(aux), offs, rows, cols, n, self._s()))
 
 
-class TowerEngine(FlatVectorOps):
-    def __init__(self, n_user, n_item, n_domain, batch_size, dropout=0.5, emb_trainable=False,
-                 tower="mlp", emb_dim=128, hidden=(256, 128, 64), l2_emb=1e-5, device=None,
-                 dropout_seed=1024, l2_linear=1e-5, uncertainty_weight=False, tower_tile=None, adam_beta1=0.9, adam_beta2=0.999):
-        """tower_tile: rows per tower workgroup (mamdr_set_tower_tile: 0 automatic, 4, 16); None = automatic, except for an
-        engine built on a lane of a parallel.LaneGroup of four or more lanes, which takes 16 (it shares the CUs with the
-        other lanes' launches).  adam_beta1 / adam_beta2: the compiled Adam's betas (tf.train.AdamOptimizer's defaults)."""
+# Keras variable names of the step engine's segments, for the reference's substring filters (maml.py:153-179)
+KERAS_NAMES = {"Ws0": "kernel_shared_0", "Ws1": "kernel_shared_1", "Ws2": "kernel_shared_2",
+               "bs0": "bias_shared_0", "bs1": "bias_shared_1", "bs2": "bias_shared_2",
+               "Wd0": "kernel_specific_0", "Wd1": "kernel_specific_1", "Wd2": "kernel_specific_2",
+               "bd0": "bias_specific_0", "bd1": "bias_specific_1", "bd2": "bias_specific_2",
+               "pn_gamma_shared": "gamma_shared", "pn_beta_shared": "beta_shared",
+               "pn_gamma_spec": "gamma_specific", "pn_beta_spec": "beta_specific",
+               "wo": "dense/kernel", "gb": "dense/bias",
+               # deepctr's embedding layers: "sparse_emb_<feature>", the 1-d linear ones "linear...sparse_emb_<feature>"
+               "user_emb": "sparse_emb_uid", "item_emb": "sparse_emb_pid", "domain_emb": "sparse_emb_domain",
+               "lin_user": "linear0sparse_emb_uid", "lin_item": "linear0sparse_emb_pid",
+               "lin_domain": "linear0sparse_emb_domain"}
+
+
+def keras_names(kind, dense=None, segments=()):
+    """{segment: Keras variable name} (a segment that is not listed keeps its own name).  dense None: the step engine's
+    towers, the step Star form among them.  kind "star" with dense "star" / "dense": model_zoo/Star's layers on the
+    generic-layer engine and in the plain-DNN form -- the shared / specific names for any layer count, auxiliary_net/*,
+    batch_normalization/*; with dense "dense" the numbered Keras Dense layers behind `segments` (output unit last).  Every
+    other kind of the generic-layer engine: its tensor names."""
+    if dense is None:
+        return KERAS_NAMES
+    if kind != "star":
+        return {}
+    names = dict(KERAS_NAMES)
+    names.update({"user_emb": "user_emb/embeddings", "item_emb": "item_emb/embeddings", "domain_emb": "domain_emb/embeddings",
+                  "aux_W": "auxiliary_net/kernel_specific", "aux_b": "auxiliary_net/bias_specific",
+                  "bn_gamma": "batch_normalization/gamma", "bn_beta": "batch_normalization/beta"})
+    for l in range(4):
+        names["Ws%d" % l], names["bs%d" % l] = "kernel_shared_%d" % l, "bias_shared_%d" % l
+        names["Wd%d" % l], names["bd%d" % l] = "kernel_specific_%d" % l, "bias_specific_%d" % l
+    if dense == "dense":
+        n = len([s for s in segments if s in ("W0", "W1", "W2", "W3")])
+        for l in range(n):
+            stem = "dense" if l == 0 else "dense_%d" % l
+            names["W%d" % l], names["b%d" % l] = stem + "/kernel", stem + "/bias"
+        names["wo"], names["gb"] = "dense_%d/kernel" % n, "dense_%d/bias" % n
+    return names
+
+
+def keras_name(kind, dense, segments, segment):
+    """Keras variable name of one segment, for the reference's substring filters (maml.py:153-179)."""
+    return keras_names(kind, dense, segments).get(segment, segment)
+
+
+class DeviceEngine(FlatVectorOps):
+    """what the two engines do alike over their entry-point families (`mamdr_*`, `mamdr_graph_*`: the same signatures,
+    _lib.SIGNATURES): device and stream, the bound state vectors and aux buffer, tables and split columns, train_steps with
+    the moving-average accumulate pass, evaluate, the accumulator and the counters.  A subclass names its family (PREFIX,
+    GRAPH), creates its context between `_open` and `_bind_buffers`, and says how `keras_names` is keyed."""
+    PREFIX, GRAPH = None, False
+    SHARED_CALLS = ("destroy", "bind_state", "aux_count", "bind_aux", "bind_table", "bind_domain_data", "train_steps_n",
+                    "eval_domain", "bind_accumulator", "set_counters", "optimizer_reset")
+
+    def _open(self, device, n_user, n_item, n_domain, batch_size, dropout_seed, emb_trainable):
         self.lib = L.load()
         if not torch.cuda.is_available():
-            raise RuntimeError("TowerEngine needs a HIP device (no CPU fallback for the MAMDR hot path)")
+            raise RuntimeError("%s needs a HIP device (no CPU fallback for the MAMDR hot path)" % type(self).__name__)
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         torch.cuda.set_device(self.device)
         self.stream = torch.cuda.current_stream(self.device)
         self.n_user, self.n_item, self.n_domain = int(n_user), int(n_item), int(n_domain)
         self.batch_size = int(batch_size)
         self.dropout_seed = int(dropout_seed) & 0xFFFFFFFF
+        self.emb_trainable = bool(emb_trainable)
+        # the family's entry points, resolved once (train_steps runs inside the benchmark's timed region)
+        for name in self.SHARED_CALLS:
+            setattr(self, "_c_" + name, getattr(self.lib, self.PREFIX + name))
+
+    def _check(self, code):
+        return L.check(code, graph=self.GRAPH)
+
+    def _bind_buffers(self, aux_ones):
+        """live state: weights + Adam slots (one set for the whole run); the non-trainable state of a norm layer
+        (zeros, `aux_ones` ones from offset `aux_ones`: the moving variances); the evaluation's read-back buffers."""
+        self._weights = self.new_vector()
+        self._adam_m = self.new_vector()
+        self._adam_v = self.new_vector()
+        self._check(self._c_bind_state(self.ctx, _ptr(self._weights), _ptr(self._adam_m), _ptr(self._adam_v)))
+        self.aux = None
+        n_aux = int(self._c_aux_count(self.ctx))
+        if n_aux:
+            self.aux = torch.zeros(n_aux, dtype=torch.float32, device=self.device)
+            self.aux[aux_ones:2 * aux_ones] = 1.0
+            self._check(self._c_bind_aux(self.ctx, _ptr(self.aux)))
+        self.tables = {}
+        self.data = {}          # (domain, split) -> dict of device columns
         self._acc = None
         self._ema = None            # set_moving_average
+        self._hist = torch.zeros(2 * 501, dtype=torch.int32, device=self.device)
+        self._loss1 = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    @property
+    def weights(self):
+        return self._weights
+
+    @property
+    def adam_m(self):
+        return self._adam_m
+
+    @property
+    def adam_v(self):
+        return self._adam_v
+
+    def close(self):
+        if getattr(self, "ctx", None):
+            torch.cuda.synchronize(self.device)
+            self._c_destroy(self.ctx)
+            self.ctx = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # ------------------------------------------------------------ flat vectors
+    def new_vector(self, like=None, meta=False):
+        if like is not None:
+            return like.clone()
+        return torch.zeros(self.n_meta if meta else self.n_params, dtype=torch.float32, device=self.device)
+
+    def keras_name(self, segment):
+        return keras_name(*self.keras_key(), segment)
+
+    def pack(self, named):
+        """numpy dict {segment name: array} -> flat device vector (padding zero)."""
+        host = np.zeros(self.n_params, np.float32)
+        for name, (off, cnt) in self.segments.items():
+            a = np.asarray(named[name], np.float32).ravel()
+            if a.size != cnt:
+                raise ValueError("segment %s has %d elements, expected %d" % (name, a.size, cnt))
+            host[off:off + cnt] = a
+        return torch.from_numpy(host).to(self.device)
+
+    def unpack(self, vec):
+        host = vec.detach().cpu().numpy()
+        return {name: host[off:off + cnt].copy() for name, (off, cnt) in self.segments.items()}
+
+    def aux_state(self):
+        """PartitionedNorm (the step Star tower, the pn forms): {mov_mean, mov_var [D,384], steps [D]} as numpy (partitioned_norm.py:71-87)."""
+        if self.aux is None:
+            return {}
+        h = self.aux.cpu().numpy()
+        dx = self.n_domain * 384
+        return {"mov_mean": h[0:dx].reshape(self.n_domain, 384).copy(),
+                "mov_var": h[dx:2 * dx].reshape(self.n_domain, 384).copy(),
+                "biased_mean": h[2 * dx:3 * dx].reshape(self.n_domain, 384).copy(),
+                "biased_var": h[3 * dx:4 * dx].reshape(self.n_domain, 384).copy(),
+                "steps": h[4 * dx:4 * dx + self.n_domain].copy()}
+
+    # ------------------------------------------------------------ binding
+    def bind_table(self, name, rows):
+        """frozen pretrained table (deepctr.py:104-116), numpy [n, emb_dim] fp32."""
+        seg = {"user_emb": L.SEG_USER_EMB, "item_emb": L.SEG_ITEM_EMB}[name]
+        t = torch.from_numpy(np.ascontiguousarray(rows, np.float32)).to(self.device)
+        self.tables[name] = t
+        self._check(self._c_bind_table(self.ctx, seg, _ptr(t), t.shape[0]))
+
+    def bind_domain_data(self, domain, split, uid, pid, dom, label):
+        split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
+        uid = np.ascontiguousarray(uid, np.int32)
+        pid = np.ascontiguousarray(pid, np.int32)
+        dom = np.ascontiguousarray(dom, np.int32)
+        if uid.size:
+            if uid.min() < 0 or uid.max() >= self.n_user or pid.min() < 0 or pid.max() >= self.n_item \
+                    or dom.min() < 0 or dom.max() >= self.n_domain:
+                raise ValueError("domain %d %s: id out of range" % (domain, split))
+        cols = {
+            "uid": torch.from_numpy(uid).to(self.device),
+            "pid": torch.from_numpy(pid).to(self.device),
+            "domain": torch.from_numpy(dom).to(self.device),
+            "label": torch.from_numpy(np.ascontiguousarray(label, np.float32)).to(self.device),
+        }
+        self.data[(domain, split)] = cols
+        self._check(self._c_bind_domain_data(self.ctx, domain, split_id, _ptr(cols["uid"]), _ptr(cols["pid"]),
+                                             _ptr(cols["domain"]), _ptr(cols["label"]), uid.shape[0]))
+
+    def n_rows(self, domain, split):
+        return int(self.data[(domain, split)]["uid"].shape[0])
+
+    # ------------------------------------------------------------ the hot path
+    def train_steps(self, domain, perm=None, first_step=0, n_steps=None, lr=1e-3, optimizer="adam",
+                    loss_out=None, batch_size=None, pass_rows=None):
+        """n_steps x train_on_batch on one domain, device-side. perm: int32 device tensor or None.
+        pass_rows: the pass covers only that many positions (perm then lists that many rows of the split) --
+        the take / skip sub-datasets of the meta-train / meta-val split."""
+        bs = batch_size or self.batch_size
+        n = self.n_rows(domain, "train") if pass_rows is None else int(pass_rows)
+        if n_steps is None:
+            n_steps = -(-n // bs) - first_step
+        optimizer, lr = self._compiled(optimizer, lr)
+        opt = {"adam": L.OPT_ADAM, "sgd": L.OPT_SGD, "accumulate": L.OPT_ACCUMULATE}[optimizer]
+        rows = -1 if pass_rows is None else n
+        if optimizer == "accumulate" and self._ema is not None:
+            # average_meta_grad == "moving_mean": every meta batch updates the accumulator's moving average
+            # (maml.py:219-220) -- one step at a time into a scratch gradient, then mamdr_moving_average
+            ema = self._ema
+            if loss_out is not None:
+                raise ValueError("accumulate passes under average_meta_grad = moving_mean report no per-step loss")
+            for s in range(first_step, first_step + n_steps):
+                ema["scratch"].zero_()
+                self._check(self._c_train_steps_n(self.ctx, domain, _ptr(perm), rows, s, 1, bs, self.dropout_seed, opt,
+                                                  float(lr), _ptr(None)))
+                ema["step"] += 1
+                decay = np.float32(1.0 - ema["momentum"])
+                denom = np.float32(1.0) - np.power(np.float32(1.0) - decay, np.float32(ema["step"]), dtype=np.float32)
+                L.check(self.lib.mamdr_moving_average(_ptr(self._acc), _ptr(ema["biased"]), _ptr(ema["scratch"]),
+                                                      float(decay), float(denom), self._acc.numel(), self._s()))
+            return n_steps
+        self._check(self._c_train_steps_n(self.ctx, domain, _ptr(perm), rows, first_step, n_steps, bs, self.dropout_seed,
+                                          opt, float(lr), _ptr(loss_out)))
+        return n_steps
+
+    def evaluate(self, domain, split, want_preds=False):
+        """model.evaluate(data, steps=n_step) -> (loss, auc[, preds]); syncs to read back."""
+        n = self.n_rows(domain, split)
+        preds = torch.empty(n, dtype=torch.float32, device=self.device) if want_preds else None
+        split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
+        self._check(self._c_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1),
+                                        _ptr(self._hist), _ptr(preds)))
+        hist = self._hist.cpu().numpy().astype(np.int64)
+        loss = float(self._loss1.cpu().numpy()[0])
+        auc, _ = auc_from_histogram(hist)
+        if want_preds:
+            return loss, auc, hist.reshape(2, 501), preds.cpu().numpy()
+        return loss, auc
+
+    def bind_accumulator(self, acc):
+        """meta-gradient accumulator of the MAML / MLDG / PCGrad meta passes (maml.py:202); optimizer="accumulate" adds
+        to it (or, after set_moving_average, moves it towards every batch's gradient)."""
+        self._acc = acc
+        self._check(self._c_bind_accumulator(self.ctx, _ptr(acc if self._ema is None else self._ema["scratch"])))
+
+    def set_moving_average(self, momentum):
+        """average_meta_grad == "moving_mean" (maml.py:219-220): accumulate passes keep TF 1.12's zero-debiased
+        moving average of the batch gradients in the bound accumulator.  Its hidden state (`biased`, `local_step`)
+        lives as long as the engine, like the hidden variables of the reference's accumulator."""
+        self._ema = {"momentum": float(momentum), "step": 0, "biased": self.new_vector(), "scratch": self.new_vector()}
+        if self._acc is not None:
+            self.bind_accumulator(self._acc)
+
+    def set_counters(self, optimizer_steps, dropout_steps):
+        """restore the Adam step count (with TF's running beta powers) and the dropout stream's position
+        (mamdr_set_counters): a run resumed from saved weights / slots written into the bound vectors."""
+        self._check(self._c_set_counters(self.ctx, int(optimizer_steps), int(dropout_steps)))
+
+    def optimizer_reset(self):
+        self._check(self._c_optimizer_reset(self.ctx))
+
+
+class TowerEngine(DeviceEngine):
+    PREFIX, KERAS_NAMES = "mamdr_", KERAS_NAMES
+
+    def __init__(self, n_user, n_item, n_domain, batch_size, dropout=0.5, emb_trainable=False,
+                 tower="mlp", emb_dim=128, hidden=(256, 128, 64), l2_emb=1e-5, device=None,
+                 dropout_seed=1024, l2_linear=1e-5, uncertainty_weight=False, tower_tile=None, adam_beta1=0.9, adam_beta2=0.999):
+        """tower_tile: rows per tower workgroup (mamdr_set_tower_tile: 0 automatic, 4, 16); None = automatic, except for an
+        engine built on a lane of a parallel.LaneGroup of four or more lanes, which takes 16 (it shares the CUs with the
+        other lanes' launches).  adam_beta1 / adam_beta2: the compiled Adam's betas (tf.train.AdamOptimizer's defaults)."""
+        self._open(device, n_user, n_item, n_domain, batch_size, dropout_seed, emb_trainable)
         tower_id = {"mlp": L.TOWER_MLP, "deepfm": L.TOWER_DEEPFM, "star": L.TOWER_STAR, "wdl": L.TOWER_WDL,
                     "pnn": L.TOWER_PNN, "nfm": L.TOWER_NFM}[tower]
         max_batch = (self.batch_size + 15) // 16 * 16
@@ -210,7 +455,6 @@ class TowerEngine(FlatVectorOps):
             tower_tile = 16 if (group is not None and group.n >= 4 and tower in ("mlp", "deepfm", "wdl")) else 0
         if tower_tile:
             self.set_tower_tile(tower_tile)
-        self.emb_trainable = bool(emb_trainable)
         self.tower = tower
         self.n_params = int(self.lib.mamdr_param_count(self.ctx))
         # theta / phi vectors cover the META prefix only (all of it except for the Star tower)
@@ -221,23 +465,8 @@ class TowerEngine(FlatVectorOps):
             L.check(self.lib.mamdr_param_segment(self.ctx, seg, C.byref(off), C.byref(cnt)))
             if cnt.value:
                 self.segments[name] = (off.value, cnt.value)
-        # live state: weights + Adam slots (one set for the whole run)
-        self._weights = self.new_vector()
-        self._adam_m = self.new_vector()
-        self._adam_v = self.new_vector()
-        L.check(self.lib.mamdr_bind_state(self.ctx, _ptr(self._weights), _ptr(self._adam_m), _ptr(self._adam_v)))
-        # non-trainable model state (Star: PartitionedNorm moving statistics, initial mean 0 / variance 1)
-        self.aux = None
-        n_aux = int(self.lib.mamdr_aux_count(self.ctx))
-        if n_aux:
-            self.aux = torch.zeros(n_aux, dtype=torch.float32, device=self.device)
-            dx = self.n_domain * 3 * emb_dim
-            self.aux[dx:2 * dx] = 1.0
-            L.check(self.lib.mamdr_bind_aux(self.ctx, _ptr(self.aux)))
-        self.tables = {}
-        self.data = {}          # (domain, split) -> dict of device columns
-        self._hist = torch.zeros(2 * 501, dtype=torch.int32, device=self.device)
-        self._loss1 = torch.zeros(1, dtype=torch.float32, device=self.device)
+        # (Star: PartitionedNorm's moving statistics, initial mean 0 / variance 1 per domain)
+        self._bind_buffers(self.n_domain * 3 * emb_dim)
 
     # The live state is only handed out synchronised: with trainable tables the library advances rows that
     # no batch touched lazily (mamdr_sync_tables in include/mamdr_hip.h); every read or replacement of the
@@ -260,69 +489,19 @@ class TowerEngine(FlatVectorOps):
         self.sync()
         return self._adam_v
 
-    def close(self):
-        if getattr(self, "ctx", None):
-            torch.cuda.synchronize(self.device)
-            self.lib.mamdr_destroy(self.ctx)
-            self.ctx = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # ------------------------------------------------------------ flat vectors
-    def new_vector(self, like=None, meta=False):
-        if like is not None:
-            return like.clone()
-        return torch.zeros(self.n_meta if meta else self.n_params, dtype=torch.float32, device=self.device)
-
-    # Keras variable names of the segments, for the reference's substring filters (maml.py:153-179)
-    KERAS_NAMES = {"Ws0": "kernel_shared_0", "Ws1": "kernel_shared_1", "Ws2": "kernel_shared_2",
-                   "bs0": "bias_shared_0", "bs1": "bias_shared_1", "bs2": "bias_shared_2",
-                   "Wd0": "kernel_specific_0", "Wd1": "kernel_specific_1", "Wd2": "kernel_specific_2",
-                   "bd0": "bias_specific_0", "bd1": "bias_specific_1", "bd2": "bias_specific_2",
-                   "pn_gamma_shared": "gamma_shared", "pn_beta_shared": "beta_shared",
-                   "pn_gamma_spec": "gamma_specific", "pn_beta_spec": "beta_specific",
-                   "wo": "dense/kernel", "gb": "dense/bias",
-                   # deepctr's embedding layers: "sparse_emb_<feature>", the 1-d linear ones "linear...sparse_emb_<feature>"
-                   "user_emb": "sparse_emb_uid", "item_emb": "sparse_emb_pid", "domain_emb": "sparse_emb_domain",
-                   "lin_user": "linear0sparse_emb_uid", "lin_item": "linear0sparse_emb_pid",
-                   "lin_domain": "linear0sparse_emb_domain"}
-
-    def keras_name(self, segment):
-        return self.KERAS_NAMES.get(segment, segment)
-
-    def aux_state(self):
-        """Star: {mov_mean, mov_var [D,384], steps [D]} as numpy (partitioned_norm.py:71-87)."""
-        if self.aux is None:
-            return {}
-        h = self.aux.cpu().numpy()
-        dx = self.n_domain * 384
-        return {"mov_mean": h[0:dx].reshape(self.n_domain, 384).copy(),
-                "mov_var": h[dx:2 * dx].reshape(self.n_domain, 384).copy(),
-                "biased_mean": h[2 * dx:3 * dx].reshape(self.n_domain, 384).copy(),
-                "biased_var": h[3 * dx:4 * dx].reshape(self.n_domain, 384).copy(),
-                "steps": h[4 * dx:4 * dx + self.n_domain].copy()}
+    def keras_key(self):
+        return self.tower, None, ()
 
     def pack(self, named):
-        """numpy dict {segment name: array} -> flat device vector (padding zero).  PNN: deepctr's first kernel
-        [387, 256] is given as ONE tensor "W0"; its last three rows (the inner products') live in segment "W0x"."""
-        host = np.zeros(self.n_params, np.float32)
+        """PNN: deepctr's first kernel [387, 256] is given as ONE tensor "W0"; its last three rows (the inner products')
+        live in segment "W0x"."""
         if "W0x" in self.segments and "W0x" not in named:
             w0 = np.asarray(named["W0"], np.float32).reshape(-1, 256)
             named = dict(named, W0=w0[:384], W0x=w0[384:])
-        for name, (off, cnt) in self.segments.items():
-            a = np.asarray(named[name], np.float32).ravel()
-            if a.size != cnt:
-                raise ValueError("segment %s has %d elements, expected %d" % (name, a.size, cnt))
-            host[off:off + cnt] = a
-        return torch.from_numpy(host).to(self.device)
+        return DeviceEngine.pack(self, named)
 
     def unpack(self, vec):
-        host = vec.detach().cpu().numpy()
-        out = {name: host[off:off + cnt].copy() for name, (off, cnt) in self.segments.items()}
+        out = DeviceEngine.unpack(self, vec)
         if "W0x" in out:           # PNN: the caller's view is deepctr's one kernel [387, 256]
             out["W0"] = np.concatenate([out["W0"], out.pop("W0x")])
         return out
@@ -377,69 +556,6 @@ class TowerEngine(FlatVectorOps):
             L.check(rows)
         return rows
 
-    # ------------------------------------------------------------ binding
-    def bind_table(self, name, rows):
-        """frozen pretrained table (deepctr.py:104-116), numpy [n, 128] fp32."""
-        seg = {"user_emb": L.SEG_USER_EMB, "item_emb": L.SEG_ITEM_EMB}[name]
-        t = torch.from_numpy(np.ascontiguousarray(rows, np.float32)).to(self.device)
-        self.tables[name] = t
-        L.check(self.lib.mamdr_bind_table(self.ctx, seg, _ptr(t), t.shape[0]))
-
-    def bind_domain_data(self, domain, split, uid, pid, dom, label):
-        split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
-        uid = np.ascontiguousarray(uid, np.int32)
-        pid = np.ascontiguousarray(pid, np.int32)
-        dom = np.ascontiguousarray(dom, np.int32)
-        if uid.size:
-            if uid.min() < 0 or uid.max() >= self.n_user or pid.min() < 0 or pid.max() >= self.n_item \
-                    or dom.min() < 0 or dom.max() >= self.n_domain:
-                raise ValueError("domain %d %s: id out of range" % (domain, split))
-        cols = {
-            "uid": torch.from_numpy(uid).to(self.device),
-            "pid": torch.from_numpy(pid).to(self.device),
-            "domain": torch.from_numpy(dom).to(self.device),
-            "label": torch.from_numpy(np.ascontiguousarray(label, np.float32)).to(self.device),
-        }
-        self.data[(domain, split)] = cols
-        L.check(self.lib.mamdr_bind_domain_data(self.ctx, domain, split_id, _ptr(cols["uid"]), _ptr(cols["pid"]),
-                                                _ptr(cols["domain"]), _ptr(cols["label"]), uid.shape[0]))
-
-    def n_rows(self, domain, split):
-        return int(self.data[(domain, split)]["uid"].shape[0])
-
-    # ------------------------------------------------------------ the hot path
-    def train_steps(self, domain, perm=None, first_step=0, n_steps=None, lr=1e-3, optimizer="adam",
-                    loss_out=None, batch_size=None, pass_rows=None):
-        """n_steps x train_on_batch on one domain, device-side. perm: int32 device tensor or None.
-        pass_rows: the pass covers only that many positions (perm then lists that many rows of the split) --
-        the take / skip sub-datasets of the meta-train / meta-val split."""
-        bs = batch_size or self.batch_size
-        n = self.n_rows(domain, "train") if pass_rows is None else int(pass_rows)
-        if n_steps is None:
-            n_steps = -(-n // bs) - first_step
-        optimizer, lr = self._compiled(optimizer, lr)
-        opt = {"adam": L.OPT_ADAM, "sgd": L.OPT_SGD, "accumulate": L.OPT_ACCUMULATE}[optimizer]
-        if optimizer == "accumulate" and self._ema is not None:
-            # average_meta_grad == "moving_mean": every meta batch updates the accumulator's moving average
-            # (maml.py:219-220) -- one step at a time into a scratch gradient, then mamdr_moving_average
-            ema = self._ema
-            if loss_out is not None:
-                raise ValueError("accumulate passes under average_meta_grad = moving_mean report no per-step loss")
-            for s in range(first_step, first_step + n_steps):
-                ema["scratch"].zero_()
-                L.check(self.lib.mamdr_train_steps_n(self.ctx, domain, _ptr(perm), -1 if pass_rows is None else n,
-                                                     s, 1, bs, self.dropout_seed, opt, float(lr), _ptr(None)))
-                ema["step"] += 1
-                decay = np.float32(1.0 - ema["momentum"])
-                denom = np.float32(1.0) - np.power(np.float32(1.0) - decay, np.float32(ema["step"]), dtype=np.float32)
-                L.check(self.lib.mamdr_moving_average(_ptr(self._acc), _ptr(ema["biased"]), _ptr(ema["scratch"]),
-                                                      float(decay), float(denom), self._acc.numel(), self._s()))
-            return n_steps
-        L.check(self.lib.mamdr_train_steps_n(self.ctx, domain, _ptr(perm), -1 if pass_rows is None else n,
-                                             first_step, n_steps, bs, self.dropout_seed, opt, float(lr),
-                                             _ptr(loss_out)))
-        return n_steps
-
     def dr_advance(self, phi, merged, theta, gamma, method="plus", assign_model=True):
         """FlatVectorOps.dr_advance on the context's live weights (mamdr_dr_advance_live): the library synchronises them
         itself, and a domain-table step the fused step path left pending is materialised inside the same launch."""
@@ -463,20 +579,6 @@ class TowerEngine(FlatVectorOps):
         rows = (C.c_int64 * n)(*[(-1 if len(p) < 3 or p[2] is None else int(p[2])) for p in passes])
         L.check(self.lib.mamdr_pregather_passes(self.ctx, n, doms, perms, rows, int(batch_size or self.batch_size)))
 
-    def evaluate(self, domain, split, want_preds=False):
-        """model.evaluate(data, steps=n_step) -> (loss, auc[, preds]); syncs to read back."""
-        n = self.n_rows(domain, split)
-        preds = torch.empty(n, dtype=torch.float32, device=self.device) if want_preds else None
-        split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
-        L.check(self.lib.mamdr_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1),
-                                           _ptr(self._hist), _ptr(preds)))
-        hist = self._hist.cpu().numpy().astype(np.int64)
-        loss = float(self._loss1.cpu().numpy()[0])
-        auc, _ = auc_from_histogram(hist)
-        if want_preds:
-            return loss, auc, hist.reshape(2, 501), preds.cpu().numpy()
-        return loss, auc
-
     def gather(self, domain, split, perm=None, first_row=0, n_rows=None, out=None):
         n = self.n_rows(domain, split) if n_rows is None else n_rows
         if out is None:
@@ -484,28 +586,6 @@ class TowerEngine(FlatVectorOps):
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         L.check(self.lib.mamdr_gather_rows(self.ctx, domain, split_id, _ptr(perm), first_row, n, _ptr(out)))
         return out
-
-    def bind_accumulator(self, acc):
-        """meta-gradient accumulator of the MAML meta pass (maml.py:202); optimizer="accumulate" adds to it
-        (or, after set_moving_average, moves it towards every batch's gradient)."""
-        self._acc = acc
-        L.check(self.lib.mamdr_bind_accumulator(self.ctx, _ptr(acc if self._ema is None else self._ema["scratch"])))
-
-    def set_moving_average(self, momentum):
-        """average_meta_grad == "moving_mean" (maml.py:219-220): accumulate passes keep TF 1.12's zero-debiased
-        moving average of the batch gradients in the bound accumulator.  Its hidden state (`biased`, `local_step`)
-        lives as long as the engine, like the hidden variables of the reference's accumulator."""
-        self._ema = {"momentum": float(momentum), "step": 0, "biased": self.new_vector(), "scratch": self.new_vector()}
-        if self._acc is not None:
-            self.bind_accumulator(self._acc)
-
-    def set_counters(self, optimizer_steps, dropout_steps):
-        """restore the Adam step count (with TF's running beta powers) and the dropout stream's position
-        (mamdr_set_counters): a run resumed from saved weights / slots written into the bound vectors."""
-        L.check(self.lib.mamdr_set_counters(self.ctx, int(optimizer_steps), int(dropout_steps)))
-
-    def optimizer_reset(self):
-        L.check(self.lib.mamdr_optimizer_reset(self.ctx))
 
     def step_kernel_names(self, batch=None):
         """names of the kernels behind profile_read's FWD_BWD / WGRAD / UPDATE slots for a step of `batch` rows."""

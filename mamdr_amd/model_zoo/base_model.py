@@ -50,6 +50,54 @@ class BaseModel(object):
     def train(self):
         raise NotImplementedError
 
+    # ------------------------------------------------------------------ build_model's shared steps
+    def pretrained_tables(self):
+        """(user, item) tables of the dataset when train.load_pretrain_emb is set, else (None, None)."""
+        if not self.train_config["load_pretrain_emb"]:
+            return None, None
+        user, item = self.dataset.user_emb, self.dataset.item_emb
+        if user is None:
+            raise ValueError("load_pretrain_emb is set but the dataset has no pretrained tables")
+        for what, table in (("user", user), ("item", item)):
+            if table is not None and table.shape[1] != self.model_config["user_dim"]:
+                raise ValueError("the pretrained %s table is %d wide, model.user_dim says %d (synthetic data: "
+                                 "dataset.synthetic_emb_dim)" % (what, table.shape[1], self.model_config["user_dim"]))
+        return user, item
+
+    def construct_engine(self, r):
+        """the engine of a deepctr.Route: the HIP engines -- looked up in their modules now --, or the injected factory:
+        itself, or the attribute of it the route names."""
+        tc = self.train_config
+        # deepctr.py:104-116: `trainable=emb_trainable` reaches SparseFeat only on the pretrained branch; without
+        # pretrained tables the column is built with deepctr's default (trainable) WHATEVER emb_trainable says
+        self.tables_trainable = bool(tc["emb_trainable"]) or not bool(tc["load_pretrain_emb"])
+        factory = self.engine_factory
+        if factory is None:
+            from .. import engine, graph_engine
+            factory = graph_engine.GraphEngine if r.engine == "graph" else engine.TowerEngine
+        elif r.offer:
+            factory = getattr(factory, r.offer)
+        return factory(*r.args, self.n_uid, self.n_pid, self.n_domain, self.batch_size, emb_trainable=self.tables_trainable,
+                       **r.kwargs)
+
+    def bind_engine(self, eng, tensors, where):
+        """frozen tables, the three splits' columns, the initial weights, the compiled optimiser."""
+        tc = self.train_config
+        if not self.tables_trainable:
+            eng.bind_table("user_emb", tensors["user_emb"])
+            eng.bind_table("item_emb", tensors["item_emb"])
+        for split, store in (("train", self.dataset.train_dataset), ("val", self.dataset.val_dataset),
+                             ("test", self.dataset.test_dataset)):
+            for d, v in store.items():
+                c = v["data"]
+                eng.bind_domain_data(d, split, c["uid"], c["pid"], c["domain"], c["label"])
+        eng.set_weights(eng.pack(tensors))
+        self.optimizer = tc["optimizer"]
+        eng.compile(self.optimizer)      # "adam" -> tf.train.AdamOptimizer(learning_rate); a Keras name otherwise (deepctr.py:54-57)
+        if tc["loss"] != "binary_crossentropy":
+            raise NotImplementedError("loss '%s': only binary_crossentropy is %s" % (tc["loss"], where))
+        return eng
+
     # ------------------------------------------------------------------ step / eval primitives
     def fit_domain(self, idx, max_steps=0, optimizer="adam", lr=None, trace=None, phase="fit"):
         """model.fit(iter, steps_per_epoch=n_step) / n_step x train_on_batch on one domain."""

@@ -10,14 +10,14 @@ Keras Adam per domain, lr 1e-3 and epsilon 1e-7 whatever `learning_rate` says, z
 with plain SGD at `learning_rate` (:143-146); Keras EarlyStopping(val_AUC, min_delta=1e-4) + best-only checkpoint.  Initial tensors: deepctr's initialisers (glorot normal DNN kernels, glorot uniform gate / head kernels, zero biases,
 N(0, 1e-4^2) domain table, pretrained constants for the user / item tables) from a numpy stream seeded with dataset.seed.
 """
+import os
 import random
 
 import numpy as np
 
 from .base_model import BaseModel
-from .deepctr import check_emb_width, glorot_normal
-
-KINDS = ("shared_bottom", "mmoe", "ple")
+from .deepctr import MTL_KINDS as KINDS
+from .deepctr import glorot_normal, route
 
 
 def tensor_plan(kind, n_domain, emb_dim, expert_hidden, tower_hidden, gate_hidden, num_experts, shared_expert_num,
@@ -80,50 +80,23 @@ class DeepMTLCTR(BaseModel):
         raise ValueError("model: {} not found".format(name))
 
     def build_model(self):
-        kind = self.tower_kind()
-        mc, tc = self.model_config, self.train_config
-        if not (mc["user_dim"] == mc["item_dim"] == mc["domain_dim"]):
-            raise ValueError("user_dim, item_dim and domain_dim must be equal")
-        if kind == "ple" and mc.get("num_levels", 1) != 1:
-            raise NotImplementedError("ple with num_levels = %r: the reference's configs all use one level" % mc.get("num_levels"))
-        factory = self.engine_factory
-        if factory is None:
-            check_emb_width(kind, mc["user_dim"], False)
-            from ..graph_engine import GraphEngine
-            factory = GraphEngine
-        self.tables_trainable = bool(tc["emb_trainable"]) or not bool(tc["load_pretrain_emb"])
-        gate = tuple(mc.get("gate_dnn_hidden_units", ())) if kind != "shared_bottom" else ()
-        shape = dict(expert_hidden=tuple(mc["hidden_dim"]), tower_hidden=tuple(mc["tower_hidden_dim"]), gate_hidden=gate,
-                     num_experts=int(mc.get("num_experts", 0)), shared_expert_num=int(mc.get("shared_expert_num", 0)),
-                     specific_expert_num=int(mc.get("specific_expert_num", 0)))
-        eng = factory(kind, self.n_uid, self.n_pid, self.n_domain, self.batch_size, dropout=mc.get("dropout", 0.0),
-                      emb_trainable=self.tables_trainable, emb_dim=mc["user_dim"], **shape)
+        """route (always the generic-layer engine), construct, draw the initial tensors, bind."""
+        mc = self.model_config
+        user, item = self.pretrained_tables()
+        r = self.route = route(self.tower_kind(), mc, self.batch_size, self.engine_factory, os.environ)
+        eng = self.construct_engine(r)
         self.init_rs = np.random.RandomState(self.dataset.seed)
-        pre = bool(tc["load_pretrain_emb"])
-        if pre and self.dataset.user_emb is None:
-            raise ValueError("load_pretrain_emb is set but the dataset has no pretrained tables")
-        self.plan = tensor_plan(kind, self.n_domain, mc["user_dim"], **shape)
-        tensors = initial_tensors(self.init_rs, self.plan, mc["user_dim"])
+        E, shape = mc["user_dim"], {k: v for k, v in r.kwargs.items() if k not in ("dropout", "emb_dim")}
+        self.plan = tensor_plan(r.kind, self.n_domain, E, **shape)
+        tensors = initial_tensors(self.init_rs, self.plan, E)
         # deep_mtl_ctr.py:108-121: pretrained constants when load_pretrain_emb, deepctr's N(0, 1e-4^2) otherwise
-        E = mc["user_dim"]
-        user = self.dataset.user_emb if pre else (self.init_rs.standard_normal((self.n_uid, E)) * 1e-4).astype(np.float32)
-        item = self.dataset.item_emb if pre else (self.init_rs.standard_normal((self.n_pid, E)) * 1e-4).astype(np.float32)
+        if user is None:
+            user = (self.init_rs.standard_normal((self.n_uid, E)) * 1e-4).astype(np.float32)
+            item = (self.init_rs.standard_normal((self.n_pid, E)) * 1e-4).astype(np.float32)
+        tensors["user_emb"], tensors["item_emb"] = user, item
         if self.tables_trainable:
-            tensors["user_emb"], tensors["item_emb"] = user, item
             self.plan = [("user_emb", (self.n_uid, E)), ("item_emb", (self.n_pid, E))] + self.plan
-        else:
-            eng.bind_table("user_emb", user)
-            eng.bind_table("item_emb", item)
-        for split, store in (("train", self.dataset.train_dataset), ("val", self.dataset.val_dataset),
-                             ("test", self.dataset.test_dataset)):
-            for d, v in store.items():
-                c = v["data"]
-                eng.bind_domain_data(d, split, c["uid"], c["pid"], c["domain"], c["label"])
-        eng.set_weights(eng.pack(tensors))
-        eng.compile(tc["optimizer"])     # "adam" -> tf.train.AdamOptimizer(learning_rate); a Keras name otherwise (deep_mtl_ctr.py:53-56)
-        if tc["loss"] != "binary_crossentropy":
-            raise NotImplementedError("loss '%s': only binary_crossentropy is built" % tc["loss"])
-        return eng
+        return self.bind_engine(eng, tensors, "built")
 
     def separate_train_val_test(self, init_parms=True):
         """deep_mtl_ctr.py:128-187.  init_parms: `compile(optimizer=self.train_config['optimizer'])` with the string

@@ -8,11 +8,14 @@ tables and the FM second-order term to the logit (deepctr.py:36-38, SURVEY A.8);
 bi-interaction of the three fields) and `pnn` (deepctr.py:44-46: DNN over the fields and their pairwise inner
 products) and `ccpm` (deepctr.py:41-43: convolutions over the field axis) run on the generic-layer engine
 (`GraphEngine`, csrc/graph_engine.hip), and so does `autoint` (deepctr.py:37-40: three multi-head self-attention
-layers over the fields beside the DNN).  Initial tensors follow the reference's initialisers (glorot normal for the
+layers over the fields beside the DNN).  `route` is the one place that decides which engine a config runs on -- for this
+model, Star and DeepMTLCTR -- and `build_model` is route, construct, draw the initial tensors, bind.  Initial tensors follow the reference's initialisers (glorot normal for the
 kernels, zeros for biases, N(0, 1e-4^2) for the domain table and for user/item tables
 without pretraining, constants from the pretrained tables otherwise) drawn from a numpy
 stream seeded with dataset.seed -- TF's own streams are not reproducible.
 """
+import collections
+import os
 import random
 
 import numpy as np
@@ -20,6 +23,8 @@ import numpy as np
 from .base_model import BaseModel
 
 GRAPH_TOWERS = ("nfm", "pnn", "ccpm", "autoint")
+MTL_KINDS = ("shared_bottom", "mmoe", "ple")
+REFERENCE_HIDDEN = (256, 128, 64)
 # embedding widths (user_dim == item_dim == domain_dim) of the mlp / wdl / deepfm towers: the step kernels are built for
 # 128, the generic-layer engine's gather / FM / table kernels for these (mamdr_graph_create checks the same set)
 EMB_WIDTHS = (32, 64, 128, 256)
@@ -37,15 +42,100 @@ def check_emb_width(tower, emb_dim, any_width):
         raise ValueError("user_dim %r: the '%s' tower takes an embedding width in %r" % (emb_dim, tower, EMB_WIDTHS))
 
 
-def glorot_normal(rs, fan_in, fan_out, shape):
-    """Keras glorot_normal: truncated normal (2 sigma), stddev = sqrt(2 / (fan_in + fan_out))."""
-    std = np.sqrt(2.0 / (fan_in + fan_out))
+# engine: "step" (engine.TowerEngine) or "graph" (graph_engine.GraphEngine); kind: the tower / kind the engine is built as;
+# args, kwargs: the constructor call's leading positional argument and the keyword arguments the config decides; offer: the
+# attribute of an injected factory that serves the route (None: the factory itself -- TowerEngine-style for a step route,
+# GraphEngine-style for the multi-task kinds)
+Route = collections.namedtuple("Route", "engine kind args kwargs offer")
+
+
+def route(tower, mc, batch_size, factory, environ, star_form=None):
+    """Which engine a config runs on, and how it is constructed -- every such decision, once.
+
+    tower: the registry's name (DeepCTR / Star / DeepMTLCTR.tower_kind); mc: model_config; factory: None (the HIP
+    engines) or the injected factory, whose `graph` / `star_graph` attributes say what it offers beside the step-style
+    call; star_form: Star's {norm, dense, auxiliary_dim, plain}.
+
+        shared_bottom / mmoe / ple                          graph
+        ccpm / autoint                                      graph
+        pnn / nfm                                           step at hidden_dim [256, 128, 64], width 128 and batches of up to
+                                                            2,048 rows (every reference config); graph beyond either limit,
+                                                            under MAMDR_PNN_ENGINE=graph / MAMDR_NFM_ENGINE=graph (the parity
+                                                            twins, one switch per tower) and on an injected factory
+        mlp / wdl / deepfm                                  step at [256, 128, 64] and width 128, else graph (1 - 4 layers of
+                                                            multiples of 64, a width of EMB_WIDTHS); an injected factory is
+                                                            always called step-style, with `hidden=` and `emb_dim=`
+        star, plain form (norm none, dense dense, no aux)   as mlp, without dropout and regularisers
+        star, pn + star, no aux, [256, 128, 64]             step; MAMDR_STAR_ENGINE=graph: graph (the parity twin)
+        star, every other form                              graph -- where the factory offers it, else what Star raised
+    """
+    E, hidden, injected = mc["user_dim"], tuple(mc["hidden_dim"]), factory is not None
+    if not (mc["user_dim"] == mc["item_dim"] == mc["domain_dim"]):
+        raise ValueError("user_dim, item_dim and domain_dim must be equal")
+    if tower in MTL_KINDS:                  # deep_mtl_ctr.py:25-49
+        if tower == "ple" and mc.get("num_levels", 1) != 1:
+            raise NotImplementedError("ple with num_levels = %r: the reference's configs all use one level" % mc.get("num_levels"))
+        if not injected:
+            check_emb_width(tower, E, False)
+        gate = tuple(mc.get("gate_dnn_hidden_units", ())) if tower != "shared_bottom" else ()
+        return Route("graph", tower, (tower,), dict(
+            dropout=mc.get("dropout", 0.0), emb_dim=E, expert_hidden=hidden, tower_hidden=tuple(mc["tower_hidden_dim"]),
+            gate_hidden=gate, num_experts=int(mc.get("num_experts", 0)), shared_expert_num=int(mc.get("shared_expert_num", 0)),
+            specific_expert_num=int(mc.get("specific_expert_num", 0))), None)
+    kw = dict(dropout=mc.get("dropout", 0.0), emb_dim=E)
+    if star_form is not None:               # star.py:74-95 attaches no regulariser to any layer and builds no Dropout layer
+        kw["dropout"] = 0.0
+        if star_form["plain"]:
+            tower = "mlp"
+            kw.update(l2_emb=0.0, l2_linear=0.0)
+    if "uncertainty_weight" in mc["name"]:     # run.py:49-50: the weighted loss joins the compiled model
+        kw["uncertainty_weight"] = True
+    if not 1 <= len(hidden) <= 4:
+        raise ValueError("hidden_dim %r: the '%s' tower takes 1 to 4 hidden layers" % (mc["hidden_dim"], tower))
+    reference_shape = hidden == REFERENCE_HIDDEN and E == 128
+    any_width = False
+    if tower == "star":
+        step_form = (star_form["norm"], star_form["dense"], star_form["auxiliary_dim"], hidden) == ("pn", "star", 0, REFERENCE_HIDDEN)
+        graph = (not injected or hasattr(factory, "star_graph")) and not (
+            step_form and environ.get("MAMDR_STAR_ENGINE", "step") != "graph")
+        if graph:
+            kw.update(norm=star_form["norm"], dense=star_form["dense"], auxiliary_dim=star_form["auxiliary_dim"])
+        elif len(hidden) != 3:
+            raise ValueError("hidden_dim %r: the Star tower's kernels are built for three hidden layers (the reference's "
+                             "configs all have [256, 128, 64])" % (mc["hidden_dim"],))
+    elif tower == "pnn":
+        graph = injected or batch_size > 2048 or not reference_shape or environ.get("MAMDR_PNN_ENGINE", "step") == "graph"
+    elif tower == "nfm":
+        graph = injected or batch_size > 2048 or not reference_shape or environ.get("MAMDR_NFM_ENGINE", "step") == "graph"
+    elif tower in GRAPH_TOWERS:
+        graph = True
+    else:                                   # mlp / wdl / deepfm
+        graph, any_width = not reference_shape and not injected, True
+    if not injected:                        # (an injected factory -- the tests' CPU stand-in -- takes any width and shape)
+        check_emb_width(tower, E, any_width)
+        if graph and tower not in GRAPH_TOWERS and any(h <= 0 or h % 64 for h in hidden):
+            raise ValueError("hidden_dim %r: layer widths must be multiples of 64" % (mc["hidden_dim"],))
+    elif graph and tower in GRAPH_TOWERS and getattr(factory, "graph", None) is None:
+        raise NotImplementedError("the injected engine factory has no '%s' tower" % tower)
+    if graph:
+        return Route("graph", tower, (tower,), dict(kw, expert_hidden=hidden, tower_hidden=()),
+                     "star_graph" if tower == "star" else "graph")
+    return Route("step", tower, (), dict(kw, tower=tower, hidden=hidden), None)
+
+
+def truncated_normal(rs, shape):
+    """standard normal draws, redrawn where they lie beyond 2 sigma (Keras' TruncatedNormal)."""
     x = rs.standard_normal(shape)
     bad = np.abs(x) > 2.0
     while bad.any():
         x[bad] = rs.standard_normal(int(bad.sum()))
         bad = np.abs(x) > 2.0
-    return (x * std).astype(np.float32)
+    return x
+
+
+def glorot_normal(rs, fan_in, fan_out, shape):
+    """Keras glorot_normal: truncated normal (2 sigma), stddev = sqrt(2 / (fan_in + fan_out))."""
+    return (truncated_normal(rs, shape) * np.sqrt(2.0 / (fan_in + fan_out))).astype(np.float32)
 
 
 def initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, user_emb=None, item_emb=None):
@@ -94,129 +184,25 @@ class DeepCTR(BaseModel):
             raise ValueError("model: {} not found".format(name))
         return tower
 
-    def build_model(self):
-        tower = self.tower_kind()
-        mc, tc = self.model_config, self.train_config
-        if not (mc["user_dim"] == mc["item_dim"] == mc["domain_dim"]):
-            raise ValueError("user_dim, item_dim and domain_dim must be equal")
-        n_hidden = len(mc["hidden_dim"])
-        if not 1 <= n_hidden <= 4:
-            raise ValueError("hidden_dim %r: the '%s' tower takes 1 to 4 hidden layers" % (mc["hidden_dim"], tower))
-        # mlp / wdl / deepfm with a hidden_dim other than the reference configs' [256, 128, 64] (deepctr.py:26-49 passes any
-        # list through as dnn_hidden_units): the step kernels are built for that one shape, the generic-layer engine takes
-        # 1 - 4 layers of widths that are multiples of 64 (MAMDR_GRAPH_MLP / WDL / DEEPFM, round 5)
-        # Star forms beyond the step kernels' one (star.py:70-96: bn, the mixed forms, the auxiliary network, any hidden_dim) run
-        # on the generic-layer engine as kind "star" (MAMDR_GRAPH_STAR); MAMDR_STAR_ENGINE=graph sends the step form there too
-        star_graph = self.star_graph_kwargs() if tower == "star" else None
-        if tower == "star" and star_graph is None and n_hidden != 3:
-            raise ValueError("hidden_dim %r: the Star tower's kernels are built for three hidden layers (the reference's "
-                             "configs all have [256, 128, 64])" % (mc["hidden_dim"],))
-        # ... and so does a user_dim other than the reference configs' 128 (deepctr.py:95-102 hands the three dims to
-        # SparseFeat(embedding_dim=...)), whatever hidden_dim is: the generic-layer engine takes the widths of EMB_WIDTHS
-        plain = tower not in GRAPH_TOWERS and tower != "star"
-        self.graph_dnn = plain and (tuple(mc["hidden_dim"]) != (256, 128, 64) or mc["user_dim"] != 128)
-        if tc["load_pretrain_emb"]:
-            for what, table in (("user", self.dataset.user_emb), ("item", self.dataset.item_emb)):
-                if table is not None and table.shape[1] != mc["user_dim"]:
-                    raise ValueError("the pretrained %s table is %d wide, model.user_dim says %d (synthetic data: "
-                                     "dataset.synthetic_emb_dim)" % (what, table.shape[1], mc["user_dim"]))
-        factory = self.engine_factory
-        if factory is None:           # (an injected factory -- the tests' CPU stand-in -- takes any width)
-            check_emb_width(tower, mc["user_dim"], plain)
-        # PNN and NFM on the step kernels (round 4: MAMDR_TOWER_PNN = the mlp tower + the inner products' three rows of the
-        # first kernel; MAMDR_TOWER_NFM = WDL's linear tables + the DNN on the bi-interaction in the domain field's place;
-        # both on k_tower4's FM instances): batches of up to 2,048 rows and hidden_dim [256, 128, 64] -- every reference
-        # config; anything else, and MAMDR_PNN_ENGINE / MAMDR_NFM_ENGINE=graph (the parity twins), runs them on the
-        # generic-layer engine
-        import os
-        self.step_pnn = (tower in ("pnn", "nfm") and factory is None and self.batch_size <= 2048 and
-                         tuple(mc["hidden_dim"]) == (256, 128, 64) and mc["user_dim"] == 128 and
-                         os.environ.get("MAMDR_PNN_ENGINE", "step") != "graph" and
-                         os.environ.get("MAMDR_%s_ENGINE" % tower.upper(), "step") != "graph")
-        if self.step_pnn:
-            from ..engine import TowerEngine
-            factory = TowerEngine
-        elif star_graph is not None:
-            if factory is None:
-                if any(h <= 0 or h % 64 for h in mc["hidden_dim"]):
-                    raise ValueError("hidden_dim %r: layer widths must be multiples of 64" % (mc["hidden_dim"],))
-                from ..graph_engine import GraphEngine
-                factory = GraphEngine
-            else:
-                factory = factory.star_graph
-        elif self.graph_dnn:
-            if factory is None:       # (an injected factory -- the tests' CPU stand-in -- takes `hidden` itself)
-                if any(h <= 0 or h % 64 for h in mc["hidden_dim"]):
-                    raise ValueError("hidden_dim %r: layer widths must be multiples of 64" % (mc["hidden_dim"],))
-                from ..graph_engine import GraphEngine
-                factory = GraphEngine
-            else:
-                self.graph_dnn = False
-        elif tower in GRAPH_TOWERS:       # generic-layer engine; an injected factory offers it as `.graph` (tests)
-            if factory is not None:
-                factory = getattr(factory, "graph", None)
-                if factory is None:
-                    raise NotImplementedError("the injected engine factory has no '%s' tower" % tower)
-            else:
-                from ..graph_engine import GraphEngine
-                factory = GraphEngine
-        elif factory is None:
-            from ..engine import TowerEngine
-            factory = TowerEngine
-        kw = dict(self.engine_kwargs())
-        if "uncertainty_weight" in mc["name"]:     # run.py:49-50: the weighted loss joins the compiled model
-            kw["uncertainty_weight"] = True
-        # deepctr.py:104-116: `trainable=emb_trainable` reaches SparseFeat only on the pretrained branch; without
-        # pretrained tables the column is built with deepctr's default (trainable) WHATEVER emb_trainable says
-        self.tables_trainable = bool(tc["emb_trainable"]) or not bool(tc["load_pretrain_emb"])
-        if star_graph is not None:
-            kw.update(star_graph)
-        if (tower in GRAPH_TOWERS and not self.step_pnn) or self.graph_dnn or star_graph is not None:
-            eng = factory(tower, self.n_uid, self.n_pid, self.n_domain, self.batch_size, expert_hidden=tuple(mc["hidden_dim"]),
-                          tower_hidden=(), dropout=self.dropout_rate(), emb_trainable=self.tables_trainable,
-                          emb_dim=mc["user_dim"], **kw)
-        else:
-            eng = factory(self.n_uid, self.n_pid, self.n_domain, self.batch_size, dropout=self.dropout_rate(),
-                          emb_trainable=self.tables_trainable, tower=tower, emb_dim=mc["user_dim"],
-                          hidden=tuple(mc["hidden_dim"]), **kw)
-        self.tower = tower
-        self.init_rs = np.random.RandomState(self.dataset.seed)
-        pre = bool(tc["load_pretrain_emb"])
-        self.pretrained = (self.dataset.user_emb, self.dataset.item_emb) if pre else (None, None)
-        if pre and self.pretrained[0] is None:
-            raise ValueError("load_pretrain_emb is set but the dataset has no pretrained tables")
-        tensors = self.draw_initial_tensors()
-        if not self.tables_trainable:
-            eng.bind_table("user_emb", tensors["user_emb"])
-            eng.bind_table("item_emb", tensors["item_emb"])
-        for split, store in (("train", self.dataset.train_dataset), ("val", self.dataset.val_dataset),
-                             ("test", self.dataset.test_dataset)):
-            for d, v in store.items():
-                c = v["data"]
-                eng.bind_domain_data(d, split, c["uid"], c["pid"], c["domain"], c["label"])
-        eng.set_weights(eng.pack(tensors))
-        self.optimizer = tc["optimizer"]
-        eng.compile(self.optimizer)      # "adam" -> tf.train.AdamOptimizer(learning_rate); a Keras name otherwise (deepctr.py:54-57)
-        if tc["loss"] != "binary_crossentropy":
-            raise NotImplementedError("loss '%s': only binary_crossentropy is on the hot path" % tc["loss"])
-        return eng
-
-    def star_graph_kwargs(self):
-        """Star: the generic-layer form's keyword arguments, None for every tower that does not run there as kind "star"."""
+    def star_form(self):
+        """Star: {norm, dense, auxiliary_dim, plain} of the config; None for every other model."""
         return None
 
-    def engine_kwargs(self):
-        """extra keyword arguments of the engine (subclasses: Star's plain-DNN form has no regularisers)."""
-        return {}
-
-    def dropout_rate(self):
-        return self.model_config.get("dropout", 0.0)
+    def build_model(self):
+        """route, construct, draw the initial tensors, bind."""
+        self.pretrained = self.pretrained_tables()
+        self.form = self.star_form()
+        r = self.route = route(self.tower_kind(), self.model_config, self.batch_size, self.engine_factory, os.environ, self.form)
+        self.tower = r.kind
+        eng = self.construct_engine(r)
+        self.init_rs = np.random.RandomState(self.dataset.seed)
+        return self.bind_engine(eng, self.draw_initial_tensors(), "on the hot path")
 
     def draw_initial_tensors(self):
         mc = self.model_config
         t = initial_tensors(self.init_rs, self.n_uid, self.n_pid, self.n_domain, mc["user_dim"],
                             tuple(mc["hidden_dim"]), self.pretrained[0], self.pretrained[1])
-        tower = getattr(self, "tower", None)
+        tower = self.tower
         if tower in GRAPH_TOWERS:         # first kernel: NFM on the 128 interaction columns, PNN on the fields + 3 inner products,
             E, h0 = mc["user_dim"], mc["hidden_dim"][0]       # CCPM on the [128 x 4] convolution features
             in_dim = {"nfm": E, "pnn": 3 * E + 3, "ccpm": 4 * E, "autoint": 3 * E}[tower]
@@ -224,12 +210,7 @@ class DeepCTR(BaseModel):
             if tower == "autoint":        # InteractingLayer: W_Query | W_key | W_Value | W_Res, TruncatedNormal(stddev 0.05) each
                 d_in = E
                 for l in range(3):
-                    w = self.init_rs.standard_normal((d_in, 128))
-                    bad = np.abs(w) > 2.0
-                    while bad.any():
-                        w[bad] = self.init_rs.standard_normal(int(bad.sum()))
-                        bad = np.abs(w) > 2.0
-                    t["att%d_w" % l] = (w * 0.05).astype(np.float32)
+                    t["att%d_w" % l] = (truncated_normal(self.init_rs, (d_in, 128)) * 0.05).astype(np.float32)
                     d_in = 32
                 h_last = mc["hidden_dim"][-1]
                 t["wo"] = glorot_normal(self.init_rs, 96 + h_last, 1, (96 + h_last, 1))

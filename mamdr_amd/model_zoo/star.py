@@ -11,6 +11,7 @@ hidden layer per width (`dense: "star"` StarFCN, `dense: "dense"` Keras Dense) -
     everything else: bn, the mixed forms, auxiliary_net,      `GraphEngine("star", norm=, dense=, auxiliary_dim=)`
     1 - 4 hidden layers of multiples of 64                    (csrc/graph_engine.hip, MAMDR_GRAPH_STAR)
 
+`Star.star_form` reads and checks these keys once per build; `deepctr.route` picks the engine from the form.
 `auxiliary_net: true` needs `auxiliary_dim == hidden_dim[-1]` (Keras' Add).  `bn` keeps one pair of moving statistics whose
 shape the several-process / several-lane synchronisation does not know: it raises there.  An injected engine factory (the
 tests' CPU stand-ins) gets the generic-layer forms only if it offers them as `factory.star_graph`.  The
@@ -20,8 +21,11 @@ unless pretrained (star.py:113-127), glorot-uniform kernels (fans of the 3-d spe
 the domain axis, as Keras computes them), zero biases, gamma one / beta zero; no regularisers, no
 dropout.  Numerics: `TowerEngine(tower="star")` (csrc/star_kernels.hip).
 """
+import functools
+
 import numpy as np
 
+from ..engine import keras_name
 from .deepctr import DeepCTR
 
 
@@ -31,39 +35,14 @@ def glorot_uniform(rs, shape, fan_in, fan_out):
 
 
 def initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, user_emb=None, item_emb=None):
-    t = {}
-    t["user_emb"] = user_emb if user_emb is not None else rs.uniform(-0.05, 0.05, (n_user, emb_dim)).astype(np.float32)
-    t["item_emb"] = item_emb if item_emb is not None else rs.uniform(-0.05, 0.05, (n_item, emb_dim)).astype(np.float32)
-    t["domain_emb"] = rs.uniform(-0.05, 0.05, (n_domain, emb_dim)).astype(np.float32)
-    dims = (3 * emb_dim,) + tuple(hidden)
-    t["pn_gamma_shared"] = np.ones(dims[0], np.float32)
-    t["pn_beta_shared"] = np.zeros(dims[0], np.float32)
-    t["pn_gamma_spec"] = np.ones((n_domain, dims[0]), np.float32)
-    t["pn_beta_spec"] = np.zeros((n_domain, dims[0]), np.float32)
-    for l in range(3):
-        t["Wd%d" % l] = glorot_uniform(rs, (n_domain, dims[l], dims[l + 1]), dims[l] * n_domain, dims[l + 1] * n_domain)
-        t["bd%d" % l] = np.zeros((n_domain, dims[l + 1]), np.float32)
-        t["Ws%d" % l] = glorot_uniform(rs, (dims[l], dims[l + 1]), dims[l], dims[l + 1])
-        t["bs%d" % l] = np.zeros(dims[l + 1], np.float32)
-    t["wo"] = glorot_uniform(rs, (dims[3], 1), dims[3], 1)
-    t["gb"] = np.zeros(1, np.float32)
-    return t
+    """the step kernels' form: PartitionedNorm + StarFCN, no auxiliary network."""
+    return forms_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, "pn", "star", 0, user_emb, item_emb)
 
 
 def dense_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, user_emb=None, item_emb=None):
     """star.py:84-86,95 with `dense: "dense"`: Keras Dense layers (glorot-uniform kernels, zero biases) on the concatenated
     embeddings, Dense(1, sigmoid) on top -- in the mlp tower's segment names (the output unit's kernel / bias = wo / gb)."""
-    t = {}
-    t["user_emb"] = user_emb if user_emb is not None else rs.uniform(-0.05, 0.05, (n_user, emb_dim)).astype(np.float32)
-    t["item_emb"] = item_emb if item_emb is not None else rs.uniform(-0.05, 0.05, (n_item, emb_dim)).astype(np.float32)
-    t["domain_emb"] = rs.uniform(-0.05, 0.05, (n_domain, emb_dim)).astype(np.float32)
-    dims = (3 * emb_dim,) + tuple(hidden)
-    for l in range(len(hidden)):
-        t["W%d" % l] = glorot_uniform(rs, (dims[l], dims[l + 1]), dims[l], dims[l + 1])
-        t["b%d" % l] = np.zeros(dims[l + 1], np.float32)
-    t["wo"] = glorot_uniform(rs, (dims[-1], 1), dims[-1], 1)
-    t["gb"] = np.zeros(1, np.float32)
-    return t
+    return forms_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, "none", "dense", 0, user_emb, item_emb)
 
 
 def forms_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, norm, dense, auxiliary_dim, user_emb=None,
@@ -105,81 +84,46 @@ def forms_initial_tensors(rs, n_user, n_item, n_domain, emb_dim, hidden, norm, d
 class Star(DeepCTR):
     NORMS, DENSES = ("none", "pn", "bn"), ("dense", "star")
 
-    def plain_dnn(self):
-        mc = self.model_config
-        return mc.get("norm") == "none" and mc.get("dense") == "dense" and not mc.get("auxiliary_net")
-
-    def has_star_graph(self):
-        """the generic-layer Star forms exist: on the HIP engine, or on an injected factory that offers `star_graph`."""
-        return self.engine_factory is None or hasattr(self.engine_factory, "star_graph")
-
     def tower_kind(self):
+        return "star"
+
+    def star_form(self):
+        """{norm, dense, auxiliary_dim, plain} of the config, checked against what the engines (or the injected factory's
+        `star_graph`) build: the one place that reads the family's keys."""
         mc = self.model_config
-        if mc.get("auxiliary_net"):
-            if not self.has_star_graph():
+        norm, dense, aux = mc.get("norm"), mc.get("dense"), bool(mc.get("auxiliary_net"))
+        offered = self.engine_factory is None or hasattr(self.engine_factory, "star_graph")
+        if aux:
+            if not offered:
                 raise NotImplementedError("auxiliary_net (model_zoo/Star/auxiliary_net.py) is not built")
             if mc.get("auxiliary_dim") != mc["hidden_dim"][-1]:
                 raise ValueError("auxiliary_net: auxiliary_dim %r != hidden_dim[-1] %r (star.py:92-93 adds the two outputs)"
                                  % (mc.get("auxiliary_dim"), mc["hidden_dim"][-1]))
-        if self.plain_dnn():
-            return "mlp"
-        if mc.get("norm") != "pn" or mc.get("dense") != "star":
-            if not self.has_star_graph():
+        plain = norm == "none" and dense == "dense" and not aux
+        if not plain and (norm != "pn" or dense != "star"):
+            if not offered:
                 raise NotImplementedError("Star with norm=%r dense=%r: built are the PartitionedNorm + StarFCN form of the BASELINE "
-                                          "configs and the plain form (norm none, dense dense)" % (mc.get("norm"), mc.get("dense")))
-            if mc.get("norm") not in self.NORMS or mc.get("dense") not in self.DENSES:
+                                          "configs and the plain form (norm none, dense dense)" % (norm, dense))
+            if norm not in self.NORMS or dense not in self.DENSES:
                 raise ValueError("Star with norm=%r dense=%r: norm is one of %r, dense one of %r"
-                                 % (mc.get("norm"), mc.get("dense"), self.NORMS, self.DENSES))
-        return "star"
-
-    def star_graph_kwargs(self):
-        """keyword arguments of `GraphEngine("star", ...)` when this config runs there, else None (step kernels / mlp engines)."""
-        mc = self.model_config
-        if self.plain_dnn() or not self.has_star_graph():
-            return None
-        import os
-        aux = bool(mc.get("auxiliary_net"))
-        step_form = (mc.get("norm") == "pn" and mc.get("dense") == "star" and not aux and
-                     tuple(mc["hidden_dim"]) == (256, 128, 64))
-        if step_form and os.environ.get("MAMDR_STAR_ENGINE", "step") != "graph":
-            return None
-        if mc.get("norm") == "bn":
+                                 % (norm, dense, self.NORMS, self.DENSES))
             from .. import parallel
-            if parallel.world()[1] > 1:
+            if norm == "bn" and parallel.world()[1] > 1:
                 raise NotImplementedError("Star with norm 'bn' under several processes or lanes: BatchNormalization keeps ONE pair "
                                           "of moving statistics [384], not the per-domain state the tail synchronisation "
                                           "of parallel.py combines")
-        return dict(norm=mc.get("norm"), dense=mc.get("dense"), auxiliary_dim=int(mc["auxiliary_dim"]) if aux else 0)
-
-    def engine_kwargs(self):
-        # star.py:74-95 attaches no regulariser to any layer and has no dropout
-        return dict(l2_emb=0.0, l2_linear=0.0) if self.plain_dnn() else {}
-
-    def dropout_rate(self):
-        return 0.0                  # (star.py builds no Dropout layer, whatever the config says)
+        return dict(norm=norm, dense=dense, auxiliary_dim=int(mc["auxiliary_dim"]) if aux else 0, plain=plain)
 
     def build_model(self):
         eng = super(Star, self).build_model()
-        self.star_form = self.star_graph_kwargs()
-        if self.plain_dnn():
-            # Keras names of star.py's layers (for the substring filters of maml.py:153-179): Embedding layers named after
-            # their attribute, Dense layers numbered in creation order, the output unit last
-            n = len(self.model_config["hidden_dim"])
-            names = {"user_emb": "user_emb/embeddings", "item_emb": "item_emb/embeddings", "domain_emb": "domain_emb/embeddings",
-                     "wo": "dense_%d/kernel" % n, "gb": "dense_%d/bias" % n}
-            for l in range(n):
-                stem = "dense" if l == 0 else "dense_%d" % l
-                names["W%d" % l], names["b%d" % l] = stem + "/kernel", stem + "/bias"
-            eng.keras_name = lambda segment: names.get(segment, segment)
+        if self.form["plain"]:
+            # Keras names of star.py's layers (for the substring filters of maml.py:153-179) on whichever mlp engine runs
+            # the form: Embedding layers named after their attribute, Dense layers numbered in creation order
+            # (set on the instance: an injected factory's engine has a keras_name of its own)
+            eng.keras_name = functools.partial(keras_name, "star", "dense", eng.segments)
         return eng
 
     def draw_initial_tensors(self):
-        mc = self.model_config
-        form = self.star_graph_kwargs()
-        if form is not None:
-            return forms_initial_tensors(self.init_rs, self.n_uid, self.n_pid, self.n_domain, mc["user_dim"],
-                                         tuple(mc["hidden_dim"]), form["norm"], form["dense"], form["auxiliary_dim"],
-                                         self.pretrained[0], self.pretrained[1])
-        make = dense_initial_tensors if self.plain_dnn() else initial_tensors
-        return make(self.init_rs, self.n_uid, self.n_pid, self.n_domain, mc["user_dim"],
-                    tuple(mc["hidden_dim"]), self.pretrained[0], self.pretrained[1])
+        mc, f = self.model_config, self.form
+        return forms_initial_tensors(self.init_rs, self.n_uid, self.n_pid, self.n_domain, mc["user_dim"], tuple(mc["hidden_dim"]),
+                                     f["norm"], f["dense"], f["auxiliary_dim"], self.pretrained[0], self.pretrained[1])

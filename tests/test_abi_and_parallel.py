@@ -102,7 +102,7 @@ def test_environment_switch_registry_is_complete():
             src = open(f, errors="replace").read()
             for pat in pats:
                 read.update(re.findall(pat, src))
-    read = {n for n in read if not n.endswith("_")} | {"MAMDR_NFM_ENGINE"}     # ("MAMDR_%s_ENGINE" % tower: pnn, nfm)
+    read = {n for n in read if not n.endswith("_")}
     missing = sorted(n for n in read if n not in exact and not n.startswith(prefixes))
     assert not missing, "environment switches read but not in csrc/env_registry.h: %s" % missing
     # an unknown name is counted (and reported on stderr) by a fresh process; a known one and a prefixed one are not

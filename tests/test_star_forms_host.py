@@ -194,3 +194,24 @@ def test_epochs_on_the_stand_in_carry_aux_through_best_state(tmp_path, name):
     with np.load(base.checkpoint_path if base.checkpoint_path.endswith(".npz") else base.checkpoint_path + ".npz") as z:
         assert z["aux"].shape[0] == eng.aux.numel() and np.array_equal(z["aux"], saved.numpy())
         assert "aux_W" in list(z["segment_names"])
+
+
+@pytest.mark.parametrize("hidden", [(256, 128, 64), (64,), (128, 64, 64, 64)])
+@pytest.mark.parametrize("pretrained", [False, True])
+def test_the_two_named_initialisers_are_members_of_the_family(hidden, pretrained):
+    """`initial_tensors` (pn + star) and `dense_initial_tensors` (none + dense) draw what `forms_initial_tensors` draws for
+    their form from the same stream: the same keys in the same order, dtypes and bits."""
+    from mamdr_amd.model_zoo import star
+    tables = {}
+    if pretrained:
+        rs = np.random.RandomState(5)
+        tables = dict(user_emb=rs.standard_normal((30, 128)).astype(np.float32),
+                      item_emb=rs.standard_normal((20, 128)).astype(np.float32))
+    for make, norm, dense in ((star.initial_tensors, "pn", "star"), (star.dense_initial_tensors, "none", "dense")):
+        if make is star.initial_tensors and len(hidden) != 3:
+            continue                                            # (the step kernels' form has three layers)
+        a = make(np.random.RandomState(11), 30, 20, 3, 128, hidden, **tables)
+        b = star.forms_initial_tensors(np.random.RandomState(11), 30, 20, 3, 128, hidden, norm, dense, 0, **tables)
+        assert list(a) == list(b)
+        for k in a:
+            assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and np.array_equal(a[k], b[k]), k

@@ -29,10 +29,7 @@ namespace mamdr {
 
 constexpr int FZ_THREADS = 512;
 constexpr int FZ_WAVES = 8;
-#ifndef MAMDR_FZ_RING
-#define MAMDR_FZ_RING 32
-#endif
-constexpr int FZ_RING = MAMDR_FZ_RING;       // slots (of 4 batch rows) in flight per wave (diagnostic builds may override)
+constexpr int FZ_RING = 32;                   // slots (of 4 batch rows) in flight per wave
 constexpr int FZ_SBLK = DM_PARTS;                   // S workgroups = 8-column blocks of dz1 (the optimiser step of their
                                               // 128 x 8 block of W0[256:384] is the long part: 2 elements per thread)
 constexpr int FZ_SC = 8;                      // columns per S workgroup
@@ -42,55 +39,20 @@ constexpr int FZ_T1 = (H1 / 16) * (H2 / 32);          // 64 tiles of dW1
 constexpr int FZ_T2 = (H2 / 16) * (H3 / 32);          // 16 tiles of dW2
 constexpr int FZ_TILES = FZ_T0 + FZ_T1 + FZ_T2;       // 208
 
-#ifdef MAMDR_STAMPS   // diagnostic build only (tools/stamp_fused.py)
-#define FZSTAMP(k)                                                                            \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 8 + (k)] = t_;                \
-    } while (0)
-#define FZREAL(k)                                                                             \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");       \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 8 + (k)] = t_;                \
-    } while (0)
-#else
-#define FZSTAMP(k) do { } while (0)
-#define FZREAL(k) do { } while (0)
-#endif
+// cycle / device-wide counter stamps of wave 0 (diagnostic build only, tools/stamp_fused.py)
+#define FZSTAMP(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 8 + (k)])
+#define FZREAL(k) MAMDR_STAMP(MAMDR_REALTIME, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 8 + (k)])
 
-__device__ __forceinline__ void fz_opt(const FusedArgs& a, float g, float& p, float& m, float& v) {
-    if (a.optimizer == 0) {
-        m = m + (g - m) * a.omb1;
-        v = v + (g * g - v) * a.omb2;
-        p = p - (m * a.alpha) / (sqrtf(v) + a.eps);
-    } else if (a.optimizer == 1) {
-        p = p - g * a.alpha;
-    } else {
-        m = m + g;
-    }
-}
-
-#ifdef FZ_SC1_STORES          // diagnostic builds: write-through parameter stores
-#define FZ_ST(ptr, val) __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#else
-#define FZ_ST(ptr, val) (*(ptr) = (val))
-#endif
 __device__ __forceinline__ void fz_store(const FusedArgs& a, int e, float p, float m, float v) {
     if (a.optimizer == 2) {
-        FZ_ST(&a.m[e], m);
+        a.m[e] = m;
         return;
     }
     if (a.optimizer == 0) {
-        FZ_ST(&a.m[e], m);
-        FZ_ST(&a.v[e], v);
+        a.m[e] = m;
+        a.v[e] = v;
     }
-    FZ_ST(&a.p[e], p);
+    a.p[e] = p;
 }
 
 // this wave's share of the 4-row slots [0, n_slots): contiguous, in wave order
@@ -125,14 +87,9 @@ __device__ __forceinline__ void fz_dense(const float* __restrict__ A, int lda, c
     f32x2 rb[FZ_RING];
 #pragma unroll
     for (int u = 0; u < FZ_RING; ++u) {
-#ifdef FZ_ABLATE_LOADS       // diagnostic builds only
-        ra[u] = (float)(u + lane);
-        rb[u] = (f32x2){(float)u, (float)lane};
-#else
         const int idx = min(u, last);
         ra[u] = (arow + idx * astep)[aoff];
         rb[u] = *reinterpret_cast<const f32x2*>(brow + idx * bstep + boff);
-#endif
     }
     __builtin_amdgcn_sched_barrier(0);
     const int passes = (n + FZ_RING - 1) / FZ_RING;
@@ -143,11 +100,9 @@ __device__ __forceinline__ void fz_dense(const float* __restrict__ A, int lda, c
             acc[0] = MAMDR_MFMA16(ra[u], rb[u][0], acc[0]);
             acc[1] = MAMDR_MFMA16(ra[u], rb[u][1], acc[1]);
             if (CSUM) csum += rb[u];
-#ifndef FZ_ABLATE_LOADS
             const int idx = min(base + u + FZ_RING, last);
             ra[u] = (arow + idx * astep)[aoff];
             rb[u] = *reinterpret_cast<const f32x2*>(brow + idx * bstep + boff);
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -302,15 +257,15 @@ __device__ __forceinline__ void fz_tile_body(const FusedArgs& a, int t, float* l
 #pragma unroll
     for (int ww = 1; ww < FZ_WAVES; ++ww) g += lds[(ww * 16 + em) * 32 + en];
     float p = p0, m = m0, v = v0;
-    fz_opt(a, g, p, m, v);
+    opt_step(a, g, p, m, v);
     fz_store(a, e, p, m, v);
     if (a.wT && a.optimizer != 2) {          // k_tower4's transposed copies of W1 / W2
         if (gemm == 2) {
             const int row = (e - a.L.w2) / H3, col = (e - a.L.w2) - row * H3;
-            FZ_ST(&a.wT[W2T_OFF + col * H2 + row], p);
+            a.wT[W2T_OFF + col * H2 + row] = p;
         } else if (gemm == 1) {
             const int row = (e - a.L.w1) / H2, col = (e - a.L.w1) - row * H2;
-            FZ_ST(&a.wT[W1T_OFF + col * H1 + row], p);
+            a.wT[W1T_OFF + col * H1 + row] = p;
         }
     }
     if (bias_tile && tid < 32) {
@@ -318,7 +273,7 @@ __device__ __forceinline__ void fz_tile_body(const FusedArgs& a, int t, float* l
 #pragma unroll
         for (int ww = 1; ww < FZ_WAVES; ++ww) gb_ += lds[FZ_CS + ww * 32 + tid];
         float bp = bp0, bm = bm0, bv = bv0;
-        fz_opt(a, gb_, bp, bm, bv);
+        opt_step(a, gb_, bp, bm, bv);
         fz_store(a, be, bp, bm, bv);
     }
     FZSTAMP(4);
@@ -413,7 +368,7 @@ __device__ __forceinline__ void fz_s_body(const FusedArgs& a, int blk, float* ld
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             float pc = p[k], mc = m[k], vc = v[k];
-            fz_opt(a, g[k], pc, mc, vc);
+            opt_step(a, g[k], pc, mc, vc);
             p[k] = pc;
             m[k] = mc;
             v[k] = vc;
@@ -450,7 +405,7 @@ __device__ __forceinline__ void fz_s_body(const FusedArgs& a, int blk, float* ld
             for (int d = 0; d < 16; ++d) g += t[d];
         }
         float p = bp0, m = bm0, v = bv0;
-        fz_opt(a, g, p, m, v);
+        opt_step(a, g, p, m, v);
         if (tid < FZ_SC) fz_store(a, be0, p, m, v);
     }
     FZSTAMP(4);
@@ -524,7 +479,7 @@ __device__ __forceinline__ void fz_out_body(const FusedArgs& a, int ob, float* l
         for (int ww = 1; ww < FZ_WAVES; ++ww) g += lds[ww * 32 + tid];
         const int e = a.L.wo + 32 * ob + tid;
         float p = a.p[e], m = a.optimizer == 1 ? 0.f : a.m[e], v = a.optimizer == 0 ? a.v[e] : 0.f;
-        fz_opt(a, g, p, m, v);
+        opt_step(a, g, p, m, v);
         fz_store(a, e, p, m, v);
     } else if (tid == 64 && ob == 0) {
         float g = lds[256];
@@ -532,7 +487,7 @@ __device__ __forceinline__ void fz_out_body(const FusedArgs& a, int ob, float* l
         for (int ww = 1; ww < FZ_WAVES; ++ww) g += lds[256 + ww];
         const int e = a.L.gb;
         float p = a.p[e], m = a.optimizer == 1 ? 0.f : a.m[e], v = a.optimizer == 0 ? a.v[e] : 0.f;
-        fz_opt(a, g, p, m, v);
+        opt_step(a, g, p, m, v);
         fz_store(a, e, p, m, v);
     }
     FZSTAMP(4);
@@ -637,11 +592,9 @@ __device__ __forceinline__ void pass_prep_row(const P& a, const float* user_tab,
     it = it < 0 ? 0 : (it >= n_item ? n_item - 1 : it);
     const float* row = lane < 32 ? user_tab + (size_t)u * EMB + 4 * lane : item_tab + (size_t)it * EMB + 4 * (lane - 32);
     const f32x4 v = *reinterpret_cast<const f32x4*>(row);
-#ifdef MAMDR_PREP_PLAIN_STORES      // (A/B: plain stores, so that the rows may stay in the infinity cache for the towers)
-    *reinterpret_cast<f32x4*>(xpre + (size_t)i * (2 * EMB) + 4 * lane) = v;
-#else
+    // (nontemporal: with plain stores, so that the rows might stay in the infinity cache for the towers, the headline workload
+    // ran at 42.6 K instead of 44.3 K domain-steps/s -- profiles/r04_prep_store_ab.txt; variant since removed)
     __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(xpre + (size_t)i * (2 * EMB) + 4 * lane));
-#endif
     if (lane == 0) {
         int d = a.dom[src];
         pdom[i] = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);

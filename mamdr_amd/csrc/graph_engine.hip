@@ -638,6 +638,8 @@ struct GradSink {
     int optimizer;
     float alpha, omb1, omb2, eps;
 };
+// (opt_step's arithmetic, mamdr_device.h, with the SGD test first.  It stays a copy: with opt_step's order of the tests
+// k_graph_tail, k_graph_adam and k_graph_fm_bwd<256> compile to different code -- profiles/step_kernels_refactor.txt)
 __device__ __forceinline__ void opt_elem(const int optimizer, const float g, float& p, float& m, float& v, const float alpha,
                                          const float omb1, const float omb2, const float eps) {
     if (optimizer == MAMDR_OPT_SGD) {

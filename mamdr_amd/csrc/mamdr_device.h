@@ -119,11 +119,76 @@ __device__ __forceinline__ uint32_t mamdr_dropout_u32(uint32_t key, uint32_t ele
     return fmix32(key + 0x9E3779B9u * elem);
 }
 
-#ifdef MAMDR_ABLATE_MFMA   // diagnostic builds only: keep the operands live, skip the matrix op
-#define MAMDR_MFMA16(a, b, c) ((c) + (f32x4){(a), (b), (a), (b)})
-#else
 #define MAMDR_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#endif
 #define MAMDR_MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
+
+// ---- small helpers every step-kernel source uses
+template <int N> struct VecT;
+template <> struct VecT<4> { typedef f32x4 type; };
+template <> struct VecT<2> { typedef f32x2 type; };
+template <> struct VecT<1> { typedef float type; };
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Workspace stores (activations, gradients, gradient slabs): WRITE-THROUGH (agent-scope relaxed atomic store =
+// global_store ... sc1).  With plain stores the 3.7 MB a step of k_tower4 writes sit dirty in the eight L2s until the
+// kernel ends and are written back between that kernel and k_wgrad_adam: 3.6 us from the tower's last workgroup to the
+// next kernel's first one, 1.5 us with no stores at all, 2.2 us with write-through stores (tools/stamp_wall.py;
+// nontemporal stores: 2.6 us; plain-, nontemporal- and no-store variants since removed).  The next kernel reads these
+// rows from other XCDs anyway.  4-byte pieces only (wider vectors are stored piecewise).
+__device__ __forceinline__ void ws_store1(float* p, float v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename V>
+__device__ __forceinline__ void ws_store(float* p, const V& v) {
+    if constexpr (sizeof(V) == 4) {
+        ws_store1(p, v);
+    } else {
+#pragma unroll
+        for (int t = 0; t < (int)(sizeof(V) / 4); ++t) ws_store1(p + t, v[t]);
+    }
+}
+
+// The plain optimiser step of one element.  TF1 ApplyAdam: m += (g - m)(1-b1); v += (g^2 - v)(1-b2);
+// p -= (m * alpha) / (sqrt(v) + eps), alpha = lr sqrt(1-b2^t)/(1-b1^t) from the host.  SGD: p -= g alpha.
+// Accumulate only: `m` is the meta-gradient accumulator, p and v are untouched.
+// (It contracts, or not, as the including translation unit is compiled.  The sites that fix their roundings -- dm_apply1,
+// adam_zero_step, emb_bodies.h's adam_elem -- keep arithmetic of their own.)
+__device__ __forceinline__ void opt_step(const int optimizer, const float g, float& p, float& m, float& v, const float alpha,
+                                         const float omb1, const float omb2, const float eps) {
+    if (optimizer == 0) {             // MAMDR_OPT_ADAM
+        m = m + (g - m) * omb1;
+        v = v + (g * g - v) * omb2;
+        p = p - (m * alpha) / (sqrtf(v) + eps);
+    } else if (optimizer == 1) {      // MAMDR_OPT_SGD
+        p = p - g * alpha;
+    } else {                          // MAMDR_OPT_ACCUMULATE
+        m = m + g;
+    }
+}
+// (the same with the hyperparameters taken from the launch's argument block)
+template <typename Args>
+__device__ __forceinline__ void opt_step(const Args& a, const float g, float& p, float& m, float& v) {
+    opt_step(a.optimizer, g, p, m, v, a.alpha, a.omb1, a.omb2, a.eps);
+}
+
+// Diagnostic build only (-DMAMDR_STAMPS; tools/stamp_*.py): one counter stamp into a buffer nothing else reads.  `counter`
+// is MAMDR_CYCLES (s_memtime, the XCD's cycle counter) or MAMDR_REALTIME (s_memrealtime: one 100 MHz counter for the whole
+// device, comparable across XCDs and kernels); the stamp goes to `slot` where `cond` holds.  The production library has
+// no stamp code.
+#ifdef MAMDR_STAMPS
+#define MAMDR_CYCLES "s_memtime"
+#define MAMDR_REALTIME "s_memrealtime"
+#define MAMDR_STAMP(counter, cond, slot)                                                      \
+    do {                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        unsigned long long t_;                                                                \
+        asm volatile(counter " %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");            \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        if (cond) (slot) = t_;                                                                \
+    } while (0)
+#else
+#define MAMDR_STAMP(counter, cond, slot) do { } while (0)
+#endif
 
 }  // namespace mamdr

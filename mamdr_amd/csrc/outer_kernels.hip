@@ -185,10 +185,7 @@ struct ApplyAcc {     // dst += acc [/ divisor] * scale; acc = 0
 struct AdamApply {    // TF1 ApplyAdam on a flat vector (outer optimiser of MAML)
     float* p; float* m; float* v; const float* g; float gscale, alpha, omb1, omb2, eps;
     __device__ __forceinline__ void step(float& pp, float& mm, float& vv, float gg) const {
-        gg = gg * gscale;
-        mm = mm + (gg - mm) * omb1;
-        vv = vv + (gg * gg - vv) * omb2;
-        pp = pp - (mm * alpha) / (sqrtf(vv) + eps);
+        opt_step(0, gg * gscale, pp, mm, vv, alpha, omb1, omb2, eps);
     }
     __device__ __forceinline__ void vec(int64_t i) const {
         f32x4 pp = reinterpret_cast<f32x4*>(p)[i], mm = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];

@@ -29,8 +29,6 @@
 namespace mamdr {
 
 namespace {
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 // One Adam step of an element whose gradient is exactly zero (the Star slices of the domains a batch does not carry):
 // explicit roundings, shared by the per-step sweep and by k_star_catchup's replay -- the same bits either way.
 // (square root and reciprocal on the hardware units, v_sqrt_f32 / v_rcp_f32, 1 ulp, as emb_bodies.h's adam_elem: the

@@ -43,29 +43,6 @@ static_assert(LDS_FLOATS * 4 <= 65536, "stay under the 64 KiB dynamic-LDS defaul
 
 size_t tower_lds_bytes() { return LDS_FLOATS * sizeof(float); }
 
-template <int N> struct VecT;
-template <> struct VecT<4> { typedef f32x4 type; };
-template <> struct VecT<2> { typedef f32x2 type; };
-template <> struct VecT<1> { typedef float type; };
-
-// Workspace stores (activations, gradients, gradient slabs): write-through (agent-scope relaxed atomic store =
-// global_store ... sc1) under -DMAMDR_WS_SC1 -- see tower4_kernels.hip: dirty lines left in the L2s are written back
-// BETWEEN the kernels.  4-byte pieces only (wider vectors are stored piecewise).
-#ifdef MAMDR_WS_PLAIN
-#define WS_STORE1(ptr, val) (*(ptr) = (val))
-#else
-#define WS_STORE1(ptr, val) __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#endif
-template <typename V>
-__device__ __forceinline__ void ws_store(float* p, const V& v) {
-    if constexpr (sizeof(V) == 4) {
-        WS_STORE1(p, v);
-    } else {
-#pragma unroll
-        for (int t = 0; t < (int)(sizeof(V) / 4); ++t) WS_STORE1(p + t, v[t]);
-    }
-}
-
 constexpr int TOWER_THREADS = 512;   // 8 waves = 2 per SIMD: one wave's epilogue / waits overlap the other's MFMAs
 
 template <int TPW>
@@ -189,9 +166,7 @@ __device__ __forceinline__ void fwd_layer(FwdW<K, N, PF, NW>& fw, const float* _
             const f32x4 a_next = *reinterpret_cast<const f32x4*>(ap + 16 * (c0 + u + 1));
             __builtin_amdgcn_sched_barrier(0);
             mfma_fwd_chunk<TPW>(acc, odd, a_cur, fw.b[u]);
-#ifndef MAMDR_ABLATE_LOADS   // diagnostic builds only: time the loop without its weight stream
             load_b_rows<TPW>(fw.b[u], wp + (size_t)(16 * (c0 + u + PF)) * N, N);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             a_cur = a_next;
         }
@@ -217,12 +192,10 @@ __device__ __forceinline__ void fwd_layer(FwdW<K, N, PF, NW>& fw, const float* _
             float z = acc[t][r];
             if constexpr (Extra::on) z += extra(row, ncol + t);
             z = fmaxf(z, 0.0f);
-#ifndef MAMDR_ABLATE_HASH
             if (TRAIN && use_dropout) {
                 const uint32_t u = mamdr_dropout_u32(key, (uint32_t)(row0 + row) * (uint32_t)N + (uint32_t)(ncol + t));
                 z = (u >= thresh) ? z * scale : 0.0f;
             }
-#endif
             h[t] = z;
         }
         V v;
@@ -233,9 +206,7 @@ __device__ __forceinline__ void fwd_layer(FwdW<K, N, PF, NW>& fw, const float* _
             for (int t = 0; t < TPW; ++t) v[t] = h[t];
         }
         *reinterpret_cast<V*>(Os + row * LDO + ncol) = v;
-#ifndef MAMDR_ABLATE_STORES
         if (TRAIN) ws_store<V>(gout + (size_t)row * ACT_LD + ncol, v);
-#endif
     }
 }
 
@@ -326,9 +297,7 @@ __device__ __forceinline__ void bwd_layer(BwdW<K, N, LDW, PF, NW>& bw, const flo
             const f32x4 n1 = *reinterpret_cast<const f32x4*>(ap + 32 * (c0 + u + 1) + 4);
             __builtin_amdgcn_sched_barrier(0);
             mfma_bwd_chunk<TPW>(acc, odd, a0, a1, bw.b[u]);
-#ifndef MAMDR_ABLATE_LOADS
             bw.load(u, c0 + u + PF, wp);
-#endif
             __builtin_amdgcn_sched_barrier(0);
             a0 = n0;
             a1 = n1;
@@ -354,8 +323,6 @@ __device__ __forceinline__ void bwd_layer(BwdW<K, N, LDW, PF, NW>& bw, const flo
 #pragma unroll
         for (int r = 0; r < 4; ++r) epi(4 * kq + r, nbase + 16 * t + j, acc[t][r]);
 }
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // row bookkeeping + embedding gather of one 16-row tile into LDS (and optionally global)
 // perm[position of row tid & 15], requested by every lane before anything else (see k_tower: loads retire in order)
@@ -503,37 +470,12 @@ __device__ __forceinline__ void gather_tile(const TowerArgs& a, float* smem, int
     __syncthreads();
 }
 
-// Diagnostic build only (-DMAMDR_STAMPS, tools/stamp_tower.py): per-phase s_memtime stamps
-// of wave 0 into a buffer nothing else reads.  The production library has no stamp code.
-#ifdef MAMDR_STAMPS
-#define STAMP(k)                                                                              \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 16 + (k)] = t_;               \
-    } while (0)
-#else
-#define STAMP(k) do { } while (0)
-#endif
+// per-phase cycle stamps of wave 0 (diagnostic build only, tools/stamp_tower.py)
+#define STAMP(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 16 + (k)])
 
-// ring depths: forward in 16-deep chunks, backward in 32-deep chunks
-// ring depths in chunks (diagnostic builds may override them)
-#ifndef MAMDR_PF0
-#define MAMDR_PF0 4
-#endif
-#ifndef MAMDR_PF1
-#define MAMDR_PF1 4
-#endif
-#ifndef MAMDR_PF2
-#define MAMDR_PF2 4
-#endif
-#ifndef MAMDR_PFB1
-#define MAMDR_PFB1 2
-#endif
-constexpr int PF0 = MAMDR_PF0, PF1 = MAMDR_PF1, PF2 = MAMDR_PF2;
-constexpr int PFB2 = 2, PFB1 = MAMDR_PFB1, PFB0 = 4;
+// ring depths in chunks: forward in 16-deep chunks, backward in 32-deep chunks
+constexpr int PF0 = 4, PF1 = 4, PF2 = 4;
+constexpr int PFB2 = 2, PFB1 = 2, PFB0 = 4;
 
 // DX: the user / item tables are trainable, so every row also needs d loss / d [user | item]
 // embedding = dz1 . W0[0:256, :]^T (the frozen-table path replaces that contraction by linearity).
@@ -777,9 +719,7 @@ __global__ __launch_bounds__(TOWER_THREADS) void k_tower(const int32_t* __restri
                                      [&](int row, int col, float v) {
             const float d = (hs[row * H2_LD + col] > 0.f) ? v * scale : 0.f;
             dzs[row * H2_LD + col] = d;
-#ifndef MAMDR_ABLATE_STORES
-            WS_STORE1(&dz_t[(size_t)row * DZ_LD + H1 + col], d);
-#endif
+            ws_store1(&dz_t[(size_t)row * DZ_LD + H1 + col], d);
         });
     }
     STAMP(7);
@@ -793,9 +733,7 @@ __global__ __launch_bounds__(TOWER_THREADS) void k_tower(const int32_t* __restri
         bwd_layer<H2, H1, H2, H2_LD>(bw1, P + a.L.w1, smem + DZ2S_OFF, []() {}, [&](int row, int col, float v) {
             const float d = (hs[row * H1_LD + col] > 0.f) ? v * scale : 0.f;
             if (DX) dzs[row * H1_LD + col] = d;
-#ifndef MAMDR_ABLATE_STORES
-            WS_STORE1(&dz_t[(size_t)row * DZ_LD + col], d);
-#endif
+            ws_store1(&dz_t[(size_t)row * DZ_LD + col], d);
         });
     }
     STAMP(8);
@@ -1049,19 +987,7 @@ __device__ __forceinline__ void wgrad_rows(const WgradArgs& g, const TileDesc& t
 constexpr int W0DOM_FLOAT4 = EMB * H1 / 4;               // rows 256..383 of W0
 constexpr int W0DOM_COPY_WGS = W0DOM_FLOAT4 / 256;        // 32
 
-
-#ifdef MAMDR_STAMPS
-#define WSTAMP(k)                                                                             \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (g.stamps && threadIdx.x == 0 && blockIdx.x < 1024) g.stamps[blockIdx.x * 8 + (k)] = t_; \
-    } while (0)
-#else
-#define WSTAMP(k) do { } while (0)
-#endif
+#define WSTAMP(k) MAMDR_STAMP(MAMDR_CYCLES, g.stamps && threadIdx.x == 0 && blockIdx.x < 1024, g.stamps[blockIdx.x * 8 + (k)])
 
 // ---- 64x64 tiles of acts^T dz: the four waves own the 2x2 32x32 quadrants of the tile and share the
 // operands through LDS.  Rows are staged in chunks of 32 (16-B global loads, 16 lanes per 256-B row slice,
@@ -1123,7 +1049,7 @@ __device__ __forceinline__ void wgrad_big(const WgradArgs& g, const TileDesc& t,
                  (size_t)(wm * 32) * t.dst_ld + wn * 32;
     const int rb4 = 4 * (lane >> 5);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) WS_STORE1(&dst[(size_t)((r & 3) + 8 * (r >> 2) + rb4) * t.dst_ld + c], acc[r]);
+    for (int r = 0; r < 16; ++r) ws_store1(&dst[(size_t)((r & 3) + 8 * (r >> 2) + rb4) * t.dst_ld + c], acc[r]);
     WSTAMP(3);
     WSTAMP(4);
 }
@@ -1208,7 +1134,7 @@ __device__ __forceinline__ void wgrad_body(const WgradArgs& g, const int bid, fl
         const int row = e >> 5, col = e & 31;
         if (row < t.m_valid && col < t.n_valid) {
             const float v = ((red[e] + red[1024 + e]) + red[2048 + e]) + red[3072 + e];
-            WS_STORE1(&slab[t.dst_off + row * t.dst_ld + col], v);
+            ws_store1(&slab[t.dst_off + row * t.dst_ld + col], v);
         }
     }
     WSTAMP(4);
@@ -1282,13 +1208,12 @@ void launch_wgrad(const WgradArgs& a, hipStream_t s, const GatherPf* pf) {
     MAMDR_LAUNCH(k_wgrad, dim3(wgrad_blocks(a)), dim3(256), 0, s, WGRAD_EARLY_ARGS(a), a);
 }
 
-// sum of one float4 / float over the gradient slabs IN SLAB ORDER.  Round 5: ALL of up to 16 slabs' loads in flight at once (the
-// slabs were written a moment ago by k_wgrad on other XCDs: every dependent batch of loads is a ~2 K-cycle trip to the
-// infinity cache -- the timeline of k_update showed 5 K cycles for the two batches of eight; round 2's rolled loop paid one
-// trip per slab); the additions run in slab order as before (bit-identical)
+// sum of one float4 / float over the gradient slabs IN SLAB ORDER, eight slabs' loads in flight (round 2's rolled loop paid
+// one dependent round trip per slab: 4 at 1024 rows, 16 at 4096); the additions run in slab order as before (bit-identical)
 __device__ __forceinline__ f32x4 slab_sum4(const float* slabs, int n_groups, int slab_ld, size_t e) {
-    // (float4: eight slabs' loads in flight -- sixteen would cost the kernel half its occupancy: 113 instead of 62 VGPRs, and the
-    // kernel is bound by how many requests the chip keeps in flight, not by this thread's trips: measured on Amazon-6)
+    // (float4: eight slabs' loads in flight in the WIDE form too -- sixteen would cost the kernel half its occupancy: 113 instead
+    // of 62 VGPRs, and the kernel is bound by how many requests the chip keeps in flight, not by this thread's trips: measured
+    // on Amazon-6)
     f32x4 g = *reinterpret_cast<const f32x4*>(slabs + e);
     for (int s0 = 1; s0 < n_groups; s0 += 8) {
         f32x4 t[8];
@@ -1301,35 +1226,37 @@ __device__ __forceinline__ f32x4 slab_sum4(const float* slabs, int n_groups, int
     }
     return g;
 }
+template <bool WIDE>
 __device__ __forceinline__ float slab_sum1(const float* slabs, int n_groups, int slab_ld, size_t e) {
-    float t[16];
+    if constexpr (WIDE) {
+        // Round 5: ALL of up to 16 slabs' loads in flight at once (the slabs were written a moment ago by k_wgrad on other
+        // XCDs: every dependent batch of loads is a ~2 K-cycle trip to the infinity cache -- the timeline of k_update showed
+        // 5 K cycles for the two batches of eight)
+        float t[16];
 #pragma unroll
-    for (int k = 0; k < 16; ++k)
-        if (k < n_groups) t[k] = slabs[(size_t)k * slab_ld + e];
-    float g = t[0];
+        for (int k = 0; k < 16; ++k)
+            if (k < n_groups) t[k] = slabs[(size_t)k * slab_ld + e];
+        float g = t[0];
 #pragma unroll
-    for (int k = 1; k < 16; ++k)
-        if (k < n_groups) g += t[k];
-    for (int s0 = 16; s0 < n_groups; ++s0) g += slabs[(size_t)s0 * slab_ld + e];
-    return g;
-}
-
-// ------------------------------------------------------------------ slab reduce + optimiser
-// TF1 ApplyAdam: m += (g - m)(1-b1); v += (g^2 - v)(1-b2);
-// p -= (m * alpha) / (sqrt(v) + eps), alpha = lr sqrt(1-b2^t)/(1-b1^t) from the host.
-// optimizer 2 = accumulate only: `m` points at the meta-gradient accumulator, p and v are untouched
-__device__ __forceinline__ void optimizer_step(const UpdateArgs& u, float g, float& p, float& m, float& v) {
-    if (u.optimizer == 0) {
-        m = m + (g - m) * u.omb1;
-        v = v + (g * g - v) * u.omb2;
-        p = p - (m * u.alpha) / (sqrtf(v) + u.eps);
-    } else if (u.optimizer == 1) {
-        p = p - g * u.alpha;
+        for (int k = 1; k < 16; ++k)
+            if (k < n_groups) g += t[k];
+        for (int s0 = 16; s0 < n_groups; ++s0) g += slabs[(size_t)s0 * slab_ld + e];
+        return g;
     } else {
-        m = m + g;
+        float g = slabs[e];
+        for (int s0 = 1; s0 < n_groups; s0 += 8) {
+            float t[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) t[k] = slabs[(size_t)min(s0 + k, n_groups - 1) * slab_ld + e];
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if (s0 + k < n_groups) g += t[k];
+        }
+        return g;
     }
 }
 
+// ------------------------------------------------------------------ slab reduce + optimiser (opt_step, mamdr_device.h)
 // four consecutive elements e..e+3 of the dense block (e a multiple of 4) with gradient sum gsum: the linear
 // domain table's regulariser, the optimiser, and the transposed copies k_tower4's backward layers read
 __device__ __forceinline__ void apply_vec4(const UpdateArgs& u, size_t e, f32x4 gsum, f32x4 p, f32x4 m, f32x4 v) {
@@ -1338,7 +1265,7 @@ __device__ __forceinline__ void apply_vec4(const UpdateArgs& u, size_t e, f32x4 
         float pc = p[c], mc = m[c], vc = v[c];
         const int ec = (int)e + c;
         if (ec >= u.ld_off && ec < u.ld_off + u.ld_count) gsum[c] += u.two_l2_lin * pc;
-        optimizer_step(u, gsum[c], pc, mc, vc);
+        opt_step(u, gsum[c], pc, mc, vc);
         p[c] = pc;
         m[c] = mc;
         v[c] = vc;
@@ -1370,11 +1297,10 @@ __device__ __forceinline__ void apply_vec4(const UpdateArgs& u, size_t e, f32x4 
     }
 }
 
-__device__ __forceinline__ void apply_vec4(const UpdateArgs& u, size_t e, f32x4 gsum) {
-    apply_vec4(u, e, gsum, *reinterpret_cast<const f32x4*>(u.p + e), *reinterpret_cast<const f32x4*>(u.m + e),
-               *reinterpret_cast<const f32x4*>(u.v + e));
-}
-
+// The bodies below exist in two forms.  WIDE (round 5) keeps every operand of a workgroup in flight at once -- 113 VGPRs,
+// four waves per SIMD; the narrow form (rounds 2 - 4) has 62 VGPRs, eight waves per SIMD, and serves steps of up to 8 row
+// groups and k_update_lin (see k_update for what each costs where).
+//
 // dW0[256:384, :] by linearity.  Those rows of x are the domain-embedding row of the sample's domain, the same
 // vector for every sample of a domain, so  sum_b x[b][256 + r] dz1[b][c] = sum_d Dm[d][r] S[d][c]  with
 // S = onehot(domain)^T dz1 -- which k_wgrad computes anyway for the domain-table gradient.  8 of the 34 64x64
@@ -1382,64 +1308,79 @@ __device__ __forceinline__ void apply_vec4(const UpdateArgs& u, size_t e, f32x4 
 // S[:, 8 columns] is summed over the slabs into LDS once, thread (r, half) then owns W0[256 + r][c0 + 4 half .. +3].
 constexpr int W0LIN_COLS = 8;
 constexpr int W0LIN_WGS = H1 / W0LIN_COLS;      // 32
+template <bool WIDE>
 __device__ __forceinline__ void update_w0dom_linear(const UpdateArgs& u, int wg, float* s_l) {
     const int tid = threadIdx.x, c0 = wg * W0LIN_COLS;
     const int r = tid >> 1, half = tid & 1;
-    // this thread's parameters and slots, and the first eight domains' embedding values of row r, are requested
+    // this thread's parameters and slots, and the first domains' embedding values of row r, are requested
     // before the S block is reduced
     const size_t e = (size_t)u.w0_off + (size_t)(2 * EMB + r) * H1 + c0 + 4 * half;
     const f32x4 p0 = *reinterpret_cast<const f32x4*>(u.p + e);
     const f32x4 m0 = *reinterpret_cast<const f32x4*>(u.m + e);
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(u.v + e);
-    // (round 5: the first 32 domains' values of this thread's table column are requested up front, beside the S block's slab
-    // loads -- the 8-at-a-time prefetch paid one trip to the infinity cache per eight domains: 12.2 K cycles per workgroup)
-    float x[32];
+    // (WIDE, round 5: the first 32 domains' values of this thread's table column are requested up front, beside the S block's
+    // slab loads -- the narrow form's 8-at-a-time prefetch paid one trip to the infinity cache per eight domains: 12.2 K cycles
+    // per workgroup)
+    constexpr int NX = WIDE ? 32 : 8;
+    float x[NX];
 #pragma unroll
-    for (int k = 0; k < 32; ++k) x[k] = u.dm_copy[min(k, u.n_domain - 1) * EMB + r];
+    for (int k = 0; k < NX; ++k) x[k] = u.dm_copy[min(k, u.n_domain - 1) * EMB + r];
     for (int idx = tid; idx < u.n_domain * W0LIN_COLS; idx += 256) {
         const int d = idx / W0LIN_COLS, cc = idx - d * W0LIN_COLS;
-        s_l[idx] = slab_sum1(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s_off + (size_t)d * H1 + c0 + cc);
+        s_l[idx] = slab_sum1<WIDE>(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s_off + (size_t)d * H1 + c0 + cc);
     }
     __syncthreads();
     f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if constexpr (WIDE) {
 #pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        if (k < u.n_domain) {
-            const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + k * W0LIN_COLS + 4 * half);
+        for (int k = 0; k < 32; ++k) {
+            if (k < u.n_domain) {
+                const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + k * W0LIN_COLS + 4 * half);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) g[q] = fmaf(x[k], sv[q], g[q]);
+                for (int q = 0; q < 4; ++q) g[q] = fmaf(x[k], sv[q], g[q]);
+            }
         }
-    }
-    for (int d = 32; d < u.n_domain; ++d) {              // (33 .. 64 domains)
-        const float xd = u.dm_copy[d * EMB + r];
-        const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + d * W0LIN_COLS + 4 * half);
+        for (int d = 32; d < u.n_domain; ++d) {              // (33 .. 64 domains)
+            const float xd = u.dm_copy[d * EMB + r];
+            const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + d * W0LIN_COLS + 4 * half);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) g[q] = fmaf(xd, sv[q], g[q]);
+            for (int q = 0; q < 4; ++q) g[q] = fmaf(xd, sv[q], g[q]);
+        }
+    } else {
+        for (int d0 = 0; d0 < u.n_domain; d0 += 8) {
+            float xn[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) xn[k] = u.dm_copy[min(d0 + 8 + k, u.n_domain - 1) * EMB + r];   // next eight
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                if (d0 + k < u.n_domain) {
+                    const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + (d0 + k) * W0LIN_COLS + 4 * half);
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) g[q] = fmaf(x[k], sv[q], g[q]);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) x[k] = xn[k];
+        }
     }
     apply_vec4(u, e, g, p0, m0, v0);
 }
 
-#ifdef MAMDR_STAMPS
-#define USTAMP(k)                                                                             \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (u.stamps && threadIdx.x == 0 && bx < 1024) u.stamps[bx * 4 + (k)] = t_;            \
+// (cycle stamps: the WIDE form only)
+#define USTAMP(k)                                                                                                      \
+    do {                                                                                                               \
+        if constexpr (WIDE) MAMDR_STAMP(MAMDR_CYCLES, u.stamps && threadIdx.x == 0 && bx < 1024, u.stamps[bx * 4 + (k)]); \
     } while (0)
-#else
-#define USTAMP(k) do { } while (0)
-#endif
 
 constexpr int DM_CBLOCKS = 8;       // column blocks of the domain table's update: 16 columns per workgroup
+template <bool WIDE>
 __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bx, float* s_l) {
     USTAMP(0);
     const int n_vec_wgs = (u.count4 - u.dm_count / 4 + 255) / 256;
     // the workgroups with the longest dependent chain come first in the grid
     const int n_lin_wgs = u.dm_copy ? W0LIN_WGS : 0;
     if (bx < n_lin_wgs) {
-        update_w0dom_linear(u, bx, s_l);
+        update_w0dom_linear<WIDE>(u, bx, s_l);
         USTAMP(2);
         return;
     }
@@ -1472,37 +1413,45 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bx, f
     if (d >= u.dm_count / EMB) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     constexpr int PER_WAVE = EMB / DM_CBLOCKS / 4;
-    // (round 5: the wave's four elements' parameters, slots, W0 snapshot rows and S2 sums are requested BEFORE the S row's slab
-    // sums are waited for -- one trip instead of five; round 4 tried the same while the 32 linearity workgroups were the
-    // kernel's long pole and saw no change)
     float pe[PER_WAVE], me[PER_WAVE], ve[PER_WAVE];
     f32x4 wve[PER_WAVE];
+    // (WIDE, round 5: the wave's four elements are requested BEFORE the S row's slab sums are waited for -- one trip instead of
+    // five; round 4 tried the same while the 32 linearity workgroups were the kernel's long pole and saw no change.  The
+    // narrow form requests each where it is used: hoisted, k_update_lin was slower on Amazon-6, 7.55 -> 8.0+ us)
+    if constexpr (WIDE) {
 #pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) {
-        const int c = c0 + w * PER_WAVE + i, el = d * EMB + c;
-        pe[i] = u.p[el];
-        me[i] = u.m[el];
-        ve[i] = u.v[el];
-        wve[i] = *reinterpret_cast<const f32x4*>(u.w0dom_copy + (size_t)c * H1 + 4 * lane);
+        for (int i = 0; i < PER_WAVE; ++i) {
+            const int c = c0 + w * PER_WAVE + i, el = d * EMB + c;
+            pe[i] = u.p[el];
+            me[i] = u.m[el];
+            ve[i] = u.v[el];
+            wve[i] = *reinterpret_cast<const f32x4*>(u.w0dom_copy + (size_t)c * H1 + 4 * lane);
+        }
     }
-    s_l[threadIdx.x] = slab_sum1(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s_off + (size_t)d * H1 + threadIdx.x);
+    s_l[threadIdx.x] = slab_sum1<WIDE>(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s_off + (size_t)d * H1 + threadIdx.x);
     __syncthreads();
     USTAMP(1);
     const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + 4 * lane);
 #pragma unroll
     for (int i = 0; i < PER_WAVE; ++i) {
         const int c = c0 + w * PER_WAVE + i, el = d * EMB + c;
+        if constexpr (!WIDE) {      // (narrow: requested where they are used, see above)
+            pe[i] = u.p[el];
+            me[i] = u.m[el];
+            ve[i] = u.v[el];
+            wve[i] = *reinterpret_cast<const f32x4*>(u.w0dom_copy + (size_t)c * H1 + 4 * lane);
+        }
         float p = pe[i], m = me[i], v = ve[i];
         const f32x4 wv = wve[i];
         // (DeepFM's S2 sums stay in the loop: hoisted with the rest they made k_update_lin slower on Amazon-6, 7.55 -> 8.05 us)
-        const float g2 = u.s2_off ? slab_sum1(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s2_off + el) : 0.f;
+        const float g2 = u.s2_off ? slab_sum1<WIDE>(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s2_off + el) : 0.f;
         float g = fmaf(sv[3], wv[3], fmaf(sv[2], wv[2], fmaf(sv[1], wv[1], sv[0] * wv[0])));
         for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
         if (lane == 0) {
             if (u.no_sdm) g = 0.f;
             if (u.s2_off) g += g2;
             g += u.two_l2 * p;
-            optimizer_step(u, g, p, m, v);
+            opt_step(u, g, p, m, v);
             if (u.optimizer == 2) {
                 u.m[el] = m;
                 continue;
@@ -1516,138 +1465,7 @@ __device__ __forceinline__ void update_body(const UpdateArgs& u, const int bx, f
     }
     USTAMP(2);
 }
-
-// ---- the NARROW forms (rounds 2 - 4; 62 VGPRs, eight waves per SIMD): up to 8 row groups, k_update_lin.  Sum of one float4 / float over the gradient slabs IN SLAB ORDER, eight slabs' loads in flight (the rolled
-// loop paid one dependent round trip per slab: 4 at 1024 rows, 16 at 4096)
-__device__ __forceinline__ f32x4 slab_sum4_n(const float* slabs, int n_groups, int slab_ld, size_t e) {
-    f32x4 g = *reinterpret_cast<const f32x4*>(slabs + e);
-    for (int s0 = 1; s0 < n_groups; s0 += 8) {
-        f32x4 t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            t[k] = *reinterpret_cast<const f32x4*>(slabs + (size_t)min(s0 + k, n_groups - 1) * slab_ld + e);
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (s0 + k < n_groups) g += t[k];
-    }
-    return g;
-}
-__device__ __forceinline__ float slab_sum1_n(const float* slabs, int n_groups, int slab_ld, size_t e) {
-    float g = slabs[e];
-    for (int s0 = 1; s0 < n_groups; s0 += 8) {
-        float t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = slabs[(size_t)min(s0 + k, n_groups - 1) * slab_ld + e];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (s0 + k < n_groups) g += t[k];
-    }
-    return g;
-}
-
-// dW0[256:384, :] by linearity.  Those rows of x are the domain-embedding row of the sample's domain, the same
-// vector for every sample of a domain, so  sum_b x[b][256 + r] dz1[b][c] = sum_d Dm[d][r] S[d][c]  with
-// S = onehot(domain)^T dz1 -- which k_wgrad computes anyway for the domain-table gradient.  8 of the 34 64x64
-// tiles of k_wgrad (24 % of its MFMA work) become D fmas per element here.  One workgroup per 8 columns:
-// S[:, 8 columns] is summed over the slabs into LDS once, thread (r, half) then owns W0[256 + r][c0 + 4 half .. +3].
-__device__ __forceinline__ void update_w0dom_linear_n(const UpdateArgs& u, int wg, float* s_l) {
-    const int tid = threadIdx.x, c0 = wg * W0LIN_COLS;
-    const int r = tid >> 1, half = tid & 1;
-    // this thread's parameters and slots, and the first eight domains' embedding values of row r, are requested
-    // before the S block is reduced
-    const size_t e = (size_t)u.w0_off + (size_t)(2 * EMB + r) * H1 + c0 + 4 * half;
-    const f32x4 p0 = *reinterpret_cast<const f32x4*>(u.p + e);
-    const f32x4 m0 = *reinterpret_cast<const f32x4*>(u.m + e);
-    const f32x4 v0 = *reinterpret_cast<const f32x4*>(u.v + e);
-    float x[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) x[k] = u.dm_copy[min(k, u.n_domain - 1) * EMB + r];
-    for (int idx = tid; idx < u.n_domain * W0LIN_COLS; idx += 256) {
-        const int d = idx / W0LIN_COLS, cc = idx - d * W0LIN_COLS;
-        s_l[idx] = slab_sum1_n(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s_off + (size_t)d * H1 + c0 + cc);
-    }
-    __syncthreads();
-    f32x4 g = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int d0 = 0; d0 < u.n_domain; d0 += 8) {
-        float xn[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) xn[k] = u.dm_copy[min(d0 + 8 + k, u.n_domain - 1) * EMB + r];   // next eight
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            if (d0 + k < u.n_domain) {
-                const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + (d0 + k) * W0LIN_COLS + 4 * half);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) g[q] = fmaf(x[k], sv[q], g[q]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) x[k] = xn[k];
-    }
-    apply_vec4(u, e, g, p0, m0, v0);
-}
-
-__device__ __forceinline__ void update_body_n(const UpdateArgs& u, const int bx, float* s_l) {
-    const int n_vec_wgs = (u.count4 - u.dm_count / 4 + 255) / 256;
-    // the workgroups with the longest dependent chain come first in the grid
-    const int n_lin_wgs = u.dm_copy ? W0LIN_WGS : 0;
-    if (bx < n_lin_wgs) {
-        update_w0dom_linear_n(u, bx, s_l);
-        return;
-    }
-    const int bid = bx - n_lin_wgs;
-    if (bid < n_vec_wgs) {
-        // dense weights behind the domain table: float4 per thread
-        const int e4 = u.dm_count / 4 + bid * 256 + threadIdx.x;
-        if (e4 >= u.count4) return;
-        const size_t e = (size_t)e4 * 4;
-        // (rows 256..383 of W0 have no tiles when their gradient comes from S: update_w0dom_linear_n)
-        if (u.dm_copy && (int)e >= u.w0_off + 2 * EMB * H1 && (int)e < u.w0_off + XDIM * H1) return;
-        // (parameters and slots are requested before the slab sum is waited for: one round of misses, not two)
-        const f32x4 p0 = *reinterpret_cast<const f32x4*>(u.p + e);
-        const f32x4 m0 = *reinterpret_cast<const f32x4*>(u.m + e);
-        const f32x4 v0 = *reinterpret_cast<const f32x4*>(u.v + e);
-        apply_vec4(u, e, slab_sum4_n(u.slabs, u.n_groups, u.slab_ld, e), p0, m0, v0);
-        return;
-    }
-    // domain table, one workgroup per (domain d, 16 columns c):
-    //   g[d][c] = sum_k S[d][k] * W0[256 + c][k] + 2 l2 p,   S = onehot(domain)^T dz1 summed over the slabs
-    // S[d][:] is summed over the slabs ONCE per workgroup (thread k owns element k; LDS), then every wave contracts it with
-    // four rows of the W0 snapshot.  (One wave per element re-summed the 16 slabs of S[d][:] for each of its 128 columns:
-    // 960 workgroups x 16 KB on Taobao-30.)  Same orders as that form -- slabs in sequence, four fmas per lane, the
-    // xor tree over the lanes: bit-identical.
-    const int blk = bid - n_vec_wgs;
-    const int d = blk / DM_CBLOCKS, c0 = (blk - d * DM_CBLOCKS) * (EMB / DM_CBLOCKS);
-    if (d >= u.dm_count / EMB) return;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    s_l[threadIdx.x] = slab_sum1_n(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s_off + (size_t)d * H1 + threadIdx.x);
-    __syncthreads();
-    const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + 4 * lane);
-    constexpr int PER_WAVE = EMB / DM_CBLOCKS / 4;
-#pragma unroll
-    for (int i = 0; i < PER_WAVE; ++i) {
-        const int c = c0 + w * PER_WAVE + i, el = d * EMB + c;
-        float p = u.p[el], m = u.m[el], v = u.v[el];
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(u.w0dom_copy + (size_t)c * H1 + 4 * lane);
-        const float g2 = u.s2_off ? slab_sum1_n(u.slabs, u.n_groups, u.slab_ld, (size_t)u.s2_off + el) : 0.f;
-        float g = fmaf(sv[3], wv[3], fmaf(sv[2], wv[2], fmaf(sv[1], wv[1], sv[0] * wv[0])));
-        for (int o = 32; o > 0; o >>= 1) g += __shfl_xor(g, o);
-        if (lane == 0) {
-            if (u.no_sdm) g = 0.f;
-            if (u.s2_off) g += g2;
-            g += u.two_l2 * p;
-            optimizer_step(u, g, p, m, v);
-            if (u.optimizer == 2) {
-                u.m[el] = m;
-                continue;
-            }
-            if (u.optimizer == 0) {
-                u.m[el] = m;
-                u.v[el] = v;
-            }
-            u.p[el] = p;
-        }
-    }
-}
+#undef USTAMP
 #define UPDATE_EARLY_PARAMS                                                                                            \
     float *__restrict__ k_p, float *__restrict__ k_m, float *__restrict__ k_v, const float *__restrict__ k_slabs,      \
         const int k_n_groups, const int k_slab_ld, const int k_count4, const int k_dm_count, const int k_optimizer
@@ -1663,8 +1481,7 @@ template <bool WIDE>
 __global__ __launch_bounds__(256) void k_update(UPDATE_EARLY_PARAMS, const UpdateArgs u0) {
     __shared__ __attribute__((aligned(16))) float s_l[64 * W0LIN_COLS];     // n_domain <= 64
     UPDATE_EARLY_APPLY(u, u0);
-    if constexpr (WIDE) update_body(u, (int)blockIdx.x, s_l);
-    else update_body_n(u, (int)blockIdx.x, s_l);
+    update_body<WIDE>(u, (int)blockIdx.x, s_l);
 }
 // rider workgroup rb (4 waves = 4 tiles of the next step's tower, all = rb mod 8): see GatherPf
 __device__ __forceinline__ void gather_prefetch_body(const GatherPf& p, const int rb) {
@@ -1698,7 +1515,7 @@ __global__ __launch_bounds__(256) void k_update_lin(UPDATE_EARLY_PARAMS, const U
     UPDATE_EARLY_APPLY(u, u0);
     const int bid = (int)blockIdx.x;
     if (bid < 2 * n_cu) emb_catchup_body(nc, bid % n_cu, bid / n_cu);
-    else if (bid < 2 * n_cu + n_update) update_body_n(u, bid - 2 * n_cu, s_l);
+    else if (bid < 2 * n_cu + n_update) update_body<false>(u, bid - 2 * n_cu, s_l);
     else lin_sweep_body(e, bid - 2 * n_cu - n_update, n_lin);
 }
 static int update_blocks(const UpdateArgs& a) {

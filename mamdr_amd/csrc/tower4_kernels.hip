@@ -30,10 +30,7 @@ constexpr int T4_ROWS = 4;
 constexpr int T4_THREADS = 512;
 constexpr int T4_WAVES = 8;
 constexpr int T4_PF = 8;                 // k rows in flight per wave (first layer, input-gradient layer)
-#ifndef MAMDR_T4_DEEP
-#define MAMDR_T4_DEEP 8
-#endif
-constexpr int T4_DEEP = MAMDR_T4_DEEP;   // ring depth of the short layers (diagnostic builds may override it)
+constexpr int T4_DEEP = 8;               // ring depth of the short layers (see T4W for what 32 measured)
 
 // LDS map (floats).  dz_l overwrites h_l in place (the gate is read by the thread that writes the gradient); the
 // split-k partials of the 256-column contractions share a slot between waves w and w + 4 (t4_put), so that everything
@@ -62,30 +59,12 @@ static_assert(T4_WAVES * T4_ROWS * H2 <= T4_RED_FLOATS, "one slot per wave up to
 
 size_t tower4_lds_bytes(bool w1l) { return (w1l ? T4_LDS_FLOATS_W1L : T4_LDS_FLOATS) * sizeof(float); }
 
-// Workspace stores of the activations / gradients: WRITE-THROUGH (agent-scope relaxed atomic store = global_store
-// ... sc1).  With plain stores the 3.7 MB a step writes sit dirty in the eight L2s until the kernel ends and are
-// written back between this kernel and k_wgrad_adam: 3.6 us from the tower's last workgroup to the next kernel's
-// first one, 1.5 us with no stores at all, 2.2 us with write-through stores (tools/stamp_wall.py; -DT4_NT_STORES,
-// nontemporal: 2.6 us).  The next kernel reads these rows from other XCDs anyway.
-#ifdef T4_ABLATE_STORES        // diagnostic builds
-#define T4_WS_STORE(ptr, val) do { } while (0)
-#elif defined(T4_NT_STORES)
-#define T4_WS_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#elif defined(T4_PLAIN_STORES)
-#define T4_WS_STORE(ptr, val) (*(ptr) = (val))
-#else
-#define T4_WS_STORE(ptr, val) __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#endif
+// (workspace stores of the activations / gradients are write-through: ws_store1, mamdr_device.h)
 #define MAMDR_MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_4x4x1f32((a), (b), (c), 4, 0, 0)
-
-template <int V> struct Vec4T;
-template <> struct Vec4T<4> { typedef f32x4 type; };
-template <> struct Vec4T<2> { typedef f32x2 type; };
-template <> struct Vec4T<1> { typedef float type; };
 
 template <int V>
 __device__ __forceinline__ void t4_load(float (&b)[V], const float* __restrict__ p) {
-    typedef typename Vec4T<V>::type T;
+    typedef typename VecT<V>::type T;
 
     const T v = *reinterpret_cast<const T*>(p);
     if constexpr (V == 1) {
@@ -106,11 +85,6 @@ struct T4W {
     static constexpr int V = N / 64;
     static constexpr int KW = K / T4_WAVES;
     static constexpr int PF = KW < DEPTH ? KW : DEPTH;
-#ifdef T4_ABLATE_W1          // diagnostic build: layer 1 / its backward without their weight streams
-    static constexpr bool LOADS = !((K == H1 && N == H2) || (K == H2 && N == H1));
-#else
-    static constexpr bool LOADS = true;
-#endif
     float b[PF][V];
     static __device__ __forceinline__ const float* wptr(const float* __restrict__ W) {
         return W + (size_t)((threadIdx.x >> 6) * KW) * N + V * (threadIdx.x & 63);
@@ -118,10 +92,7 @@ struct T4W {
     __device__ __forceinline__ void prefetch(const float* __restrict__ W) {
         const float* wp = wptr(W);
 #pragma unroll
-        for (int u = 0; u < PF; ++u) {
-            if constexpr (LOADS) t4_load<V>(b[u], wp + (size_t)u * N);
-            else for (int t = 0; t < V; ++t) b[u][t] = 1.0f;
-        }
+        for (int u = 0; u < PF; ++u) t4_load<V>(b[u], wp + (size_t)u * N);
         __builtin_amdgcn_sched_barrier(0);
     }
     // the same ring from the UNtransposed matrix Wn [N][K] (W = Wn^T): b[u][t] = Wn[V lane + t][w KW + u] -- for each of
@@ -149,7 +120,7 @@ struct T4W {
 // own partial (p_w + p_{w+4}) -- and t4_sum adds the four slots in order.
 template <int N, int V, bool STRIDED>
 __device__ __forceinline__ void t4_put(const f32x4 (&acc)[V], float* red) {
-    typedef typename Vec4T<V>::type T;
+    typedef typename VecT<V>::type T;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     constexpr bool PAIRED = N > H2;
     float* slot = red + ((PAIRED ? (w & 3) : w) * T4_ROWS) * N;
@@ -210,7 +181,7 @@ __device__ __forceinline__ void t4_contract(T4W<K, N, DEPTH>& tw, const float* _
             for (int u = 0; u < 4; ++u) {
 #pragma unroll
                 for (int t = 0; t < V; ++t) acc[t] = MAMDR_MFMA4(a4[u], tw.b[q + u][t], acc[t]);
-                if constexpr (T4W<K, N, DEPTH>::LOADS) t4_load<V>(tw.b[q + u], wp + (size_t)(k0 + q + u + PF) * N);
+                t4_load<V>(tw.b[q + u], wp + (size_t)(k0 + q + u + PF) * N);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -386,40 +357,11 @@ __device__ __forceinline__ float t4_sum(const float* red, int row, int col) {
     return s;
 }
 
-#ifdef MAMDR_STAMPS   // diagnostic build only (tools/stamp_tower.py)
-#define T4STAMP(k)                                                                            \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 16 + (k)] = t_;               \
-    } while (0)
-// the same stamp by the first lane of wave 4 (rows 256.. of the stamp buffer)
-#define T4STAMP_W4(k)                                                                         \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.stamps && threadIdx.x == 256) a.stamps[(blockIdx.x + 256) * 16 + (k)] = t_;     \
-    } while (0)
-// wall-clock stamp (s_memrealtime: one 100 MHz counter for the whole device, comparable across XCDs and kernels)
-#define T4REAL(k)                                                                             \
-    do {                                                                                      \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        unsigned long long t_;                                                                \
-        asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");       \
-        __builtin_amdgcn_sched_barrier(0);                                                    \
-        if (a.stamps && threadIdx.x == 0) a.stamps[blockIdx.x * 16 + (k)] = t_;               \
-    } while (0)
-#else
-#define T4STAMP(k) do { } while (0)
-#define T4STAMP_W4(k) do { } while (0)
-#define T4REAL(k) do { } while (0)
-#endif
-
-__device__ __forceinline__ int t4_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// stamps (diagnostic build only, tools/stamp_tower.py): cycle stamps by the first lane of wave 0 and of wave 4 (rows 256..
+// of the stamp buffer), and the device-wide counter
+#define T4STAMP(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 16 + (k)])
+#define T4STAMP_W4(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 256, a.stamps[(blockIdx.x + 256) * 16 + (k)])
+#define T4REAL(k) MAMDR_STAMP(MAMDR_REALTIME, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 16 + (k)])
 
 // DX: trainable user / item tables -> d loss / d [user | item] row = dz1 . W0[0:256,:]^T through the
 // transposed copy W0T (kept current by k_update), row ids + representatives for the table update.
@@ -493,13 +435,10 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     __builtin_amdgcn_sched_barrier(0);
     const bool l0_dom_only = FM && a.deepfm == 4;      // NFM: rows 0..255 of W0 are zero and meet nothing the DNN reads
     w0.prefetch(k_w0, l0_dom_only);
-    // (the snapshot of W0[256:384] for k_wgrad_adam is taken at the END of the kernel since round 5: here, its load -> store
-    // dependency put an `s_waitcnt vmcnt(0)` into the last wave's prologue -- one full round trip for everything that wave
-    // had requested, in front of its bias loads and W1-image requests -- and the whole workgroup waited for that wave at the
-    // bookkeeping barrier)
-#ifdef MAMDR_T4_SNAP_EARLY
-    if (FUSED_OK) tower_snapshots(a, T4_THREADS, n_tiles);
-#endif
+    // (the snapshot of W0[256:384] for k_wgrad_adam is taken at the END of the kernel since round 5: here (variant since
+    // removed), its load -> store dependency put an `s_waitcnt vmcnt(0)` into the last wave's prologue -- one full round trip
+    // for everything that wave had requested, in front of its bias loads and W1-image requests -- and the whole workgroup
+    // waited for that wave at the bookkeeping barrier)
     const bool dmw = FUSED_OK && a.dm_snap_out != nullptr;       // k_wgrad_adam path: domain-table duty (DmStep)
     // (the pending domain row is requested AFTER the bookkeeping, also with a pre-gathered pass: asked for here, from
     // the caller's expected domain, its loads -- misses to HBM -- delayed the x rows by 1.5 K cycles; measured)
@@ -546,9 +485,9 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
             if (src < 0) src = 0;
             if (src >= a.n_rows_split) src = a.n_rows_split - 1;
         }
-        rowi[tid] = t4_clamp(a.uid[src], 0, a.n_user - 1);
-        rowi[4 + tid] = t4_clamp(a.pid[src], 0, a.n_item - 1);
-        rowi[8 + tid] = t4_clamp(a.dom[src], 0, a.n_domain - 1);
+        rowi[tid] = clampi(a.uid[src], 0, a.n_user - 1);
+        rowi[4 + tid] = clampi(a.pid[src], 0, a.n_item - 1);
+        rowi[8 + tid] = clampi(a.dom[src], 0, a.n_domain - 1);
         rowi[12 + tid] = valid ? 1 : 0;
         rowf[tid] = a.label[src];
     }
@@ -730,7 +669,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
                 h = (u >= a.drop_thresh) ? h * scale : 0.f;
             }
             smem[T4_H1 + row * T4_H1LD + ecol] = h;
-            T4_WS_STORE(&acts_t[(size_t)row * ACT_LD + XDIM + ecol], h);
+            ws_store1(&acts_t[(size_t)row * ACT_LD + XDIM + ecol], h);
         }
     }
     __syncthreads();
@@ -753,7 +692,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
             h = (u >= a.drop_thresh) ? h * scale : 0.f;
         }
         smem[T4_H2 + row * T4_H2LD + col] = h;
-        T4_WS_STORE(&acts_t[(size_t)row * ACT_LD + XDIM + H1 + col], h);
+        ws_store1(&acts_t[(size_t)row * ACT_LD + XDIM + H1 + col], h);
     }
     __syncthreads();
 
@@ -778,7 +717,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
             const uint32_t u = mamdr_dropout_u32(key, (uint32_t)(r0 + row) * (uint32_t)H3 + (uint32_t)col);
             h = (u >= a.drop_thresh) ? h * scale : 0.f;
         }
-        T4_WS_STORE(&acts_t[(size_t)row * ACT_LD + XDIM + H1 + H2 + col], h);
+        ws_store1(&acts_t[(size_t)row * ACT_LD + XDIM + H1 + H2 + col], h);
         float s = h * wor;
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
         float logit = s + gbr;
@@ -818,7 +757,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
         }
         const float d = (h > 0.f) ? (dl * wor) * scale : 0.f;
         smem[T4_DZ3 + row * T4_H3LD + col] = d;
-        T4_WS_STORE(&dz_t[(size_t)row * DZ_LD + H1 + H2 + col], d);
+        ws_store1(&dz_t[(size_t)row * DZ_LD + H1 + H2 + col], d);
     }
     __syncthreads();
     if (tid == 0) a.loss_part[tile] = (rowf[4] + rowf[5]) + (rowf[6] + rowf[7]);
@@ -837,7 +776,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
         const float v = t4_sum<H2>(red, row, col);
         const float d = (smem[T4_H2 + row * T4_H2LD + col] > 0.f) ? v * scale : 0.f;
         smem[T4_DZ2 + row * T4_H2LD + col] = d;
-        T4_WS_STORE(&dz_t[(size_t)row * DZ_LD + H1 + col], d);
+        ws_store1(&dz_t[(size_t)row * DZ_LD + H1 + col], d);
     }
     __syncthreads();
     T4STAMP(8);
@@ -851,7 +790,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
         const int row = erow2 + 2 * rr;
         const float v = t4_sum<H1>(red, row, ecol);
         const float d = (smem[T4_H1 + row * T4_H1LD + ecol] > 0.f) ? v * scale : 0.f;
-        T4_WS_STORE(&dz_t[(size_t)row * DZ_LD + ecol], d);
+        ws_store1(&dz_t[(size_t)row * DZ_LD + ecol], d);
         if (DX || nfm) smem[T4_DZ1 + row * T4_H1LD + ecol] = d;
         dip[rr][0] = d * wx0;
         dip[rr][1] = d * wx1;
@@ -859,9 +798,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     }
     T4STAMP(9);
     T4REAL(11);
-#ifndef MAMDR_T4_SNAP_EARLY
     if (FUSED_OK) tower_snapshots(a, T4_THREADS, n_tiles);      // (W0's rows are L2-resident by now: layer 0 streamed them)
-#endif
     if (pnn) {
         // d loss / d ip[row][j] = sum_c dz1[row][c] W0x[j][c]: wave sums, then the row's four waves (rows erow2, erow2 + 2
         // belong to waves 4 erow2 .. 4 erow2 + 3) through LDS in wave order; the inner products' chain rule then gives the

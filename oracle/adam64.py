@@ -18,7 +18,7 @@ Rounding sequences of the sites and the bars they imply (u = 2^-24, first order 
         |v - v*| <= 0.5 ulp(v*) + 3 u (g^2 + |v|) omb2
   (hardware-rcp sites form m, v with one fma: fewer roundings, same bar.)
 
-  parameter, IEEE sites (fz_opt, optimizer_step, dm_apply, opt_apply, opt_elem, AdamApply):
+  parameter, IEEE sites (opt_step -- k_wgrad_adam, k_update, AdamApply --, dm_apply, opt_apply, opt_elem):
         delta = fl(fl(m alpha) / fl(fl(sqrt v) + eps))  -- four roundings of relative size <= u: K = 4
   (the issue that introduced this module proposed K = 3; the addition of eps is a fourth rounding, and its error is not
   absorbed by any other: a delta with the three others exact but fl(s + eps) off by half an ulp sits 1 u out.)

@@ -8,14 +8,17 @@
 //                    activation columns, 8-byte loads of the 32 gradient columns) and feeds two
 //                    v_mfma_f32_16x16x4_f32 per slot; the 8 partial tiles are summed through LDS in wave order
 //                    (fixed order: bitwise reproducible); thread (m, n) then applies TF1 Adam / SGD / accumulate
-//                    to element (m, n) and keeps k_tower4's transposed W1 / W2 copies current.
-//   S workgroups     8 workgroups, one per 32 columns of dz1: S = onehot(domain)^T dz1 for their columns (the
+//                    to element (m, n) and keeps k_tower4's transposed W2 copy current (W1's too, unless the context
+//                    can only ever launch the W1-image towers, which do not read it).
+//   S workgroups     32 workgroups, one per 8 columns of dz1: S = onehot(domain)^T dz1 for their columns (the
 //                    same contraction with a synthesised A operand), from which follow, by linearity (the rows
 //                    256..383 of x are the domain-embedding row of the sample's domain):
 //                      db0[c]        = sum_d S[d][c]
 //                      dW0[256+r][c] = sum_d Dm[d][r] S[d][c]          (stepped here)
 //                      pdm[blk][d][r] = sum_{c in blk} S[d][c] W0[256+r][c]   (partial domain-table gradient)
-//                    against PRE-update snapshots of Dm and W0[256:384] made by the tower kernel of the step.
+//                    against the PRE-update Dm (the snapshot the tower kernel of the step leaves) and the PRE-update
+//                    W0[256:384, its 8 columns], which the workgroup reads from the live parameters before it steps
+//                    that very block itself (no other workgroup writes it: no snapshot).
 //   domain table     g = sum_blk pdm[blk] + 2 l2 Dm: applied by the NEXT step's tower kernel (DmStep, mamdr_kernels.h);
 //                    k_dm_finish materialises the last step of a call.
 //
@@ -259,11 +262,11 @@ __device__ __forceinline__ void fz_tile_body(const FusedArgs& a, int t, float* l
     float p = p0, m = m0, v = v0;
     opt_step(a, g, p, m, v);
     fz_store(a, e, p, m, v);
-    if (a.wT && a.optimizer != 2) {          // k_tower4's transposed copies of W1 / W2
+    if (a.wT && a.optimizer != 2) {          // k_tower4's transposed copies of W2 and, where a tower can read it, W1
         if (gemm == 2) {
             const int row = (e - a.L.w2) / H3, col = (e - a.L.w2) - row * H3;
             a.wT[W2T_OFF + col * H2 + row] = p;
-        } else if (gemm == 1) {
+        } else if (gemm == 1 && !a.w1t_unread) {
             const int row = (e - a.L.w1) / H2, col = (e - a.L.w1) - row * H2;
             a.wT[W1T_OFF + col * H1 + row] = p;
         }
@@ -307,11 +310,14 @@ __device__ __forceinline__ void fz_s_body(const FusedArgs& a, int blk, float* ld
     const f32x2 p0 = *reinterpret_cast<const f32x2*>(a.p + e0);
     const f32x2 m0 = a.optimizer == 1 ? (f32x2){0.f, 0.f} : *reinterpret_cast<const f32x2*>(a.m + e0);
     const f32x2 v0 = a.optimizer == 0 ? *reinterpret_cast<const f32x2*>(a.v + e0) : (f32x2){0.f, 0.f};
-    // pre-update W0[256 + c'][c0 .. c0 + 7] for the partial domain-table gradient: thread (c' = tid & 127, dq = tid >> 7)
+    // pre-update W0[256 + c'][c0 .. c0 + 7] for the partial domain-table gradient: thread (c' = tid & 127, dq = tid >> 7).
+    // Read from the live parameters: this 128 x 8 block is the one THIS workgroup steps in part (a), nobody else in the
+    // launch writes it, and the values are in registers two barriers before the first store
     const int cp = tid & 127, dq = tid >> 7;
     f32x4 wsn[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) wsn[k] = *reinterpret_cast<const f32x4*>(a.w0dom_snap + (size_t)cp * H1 + c0 + 4 * k);
+    for (int k = 0; k < 2; ++k)
+        wsn[k] = *reinterpret_cast<const f32x4*>(a.p + a.L.w0 + (size_t)(2 * EMB + cp) * H1 + c0 + 4 * k);
     // Dm[d][r] (pre-update) of every (padded) domain: requested before the contraction too
     float xd[64];
 #pragma unroll
@@ -383,7 +389,7 @@ __device__ __forceinline__ void fz_s_body(const FusedArgs& a, int blk, float* ld
             *reinterpret_cast<f32x2*>(a.p + e0) = p;
         }
     }
-    // (b) pdm[blk][d][c'] = sum_k S[d][k] W0[256 + c'][c0 + k]   (W0: pre-update snapshot)
+    // (b) pdm[blk][d][c'] = sum_k S[d][k] W0[256 + c'][c0 + k]   (W0: the pre-update values in wsn)
     for (int d = dq; d < 16 * MT; d += 4) {
         const f32x4 s0v = *reinterpret_cast<const f32x4*>(sb + d * FZ_SC);
         const f32x4 s1v = *reinterpret_cast<const f32x4*>(sb + d * FZ_SC + 4);

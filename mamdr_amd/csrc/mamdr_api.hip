@@ -100,7 +100,7 @@ struct mamdr_ctx {
     float* acts = nullptr;
     float* dz = nullptr;
     float* dlogit = nullptr;
-    float* w0dom_copy = nullptr;
+    float* w0dom_copy = nullptr;    // slab path only: k_wgrad's pre-update snapshot of W0[256:384, :] for k_update
     float* dm_copy = nullptr;       // pre-update snapshot of the domain table (dW0[256:384] by linearity)
     bool lin_w0dom = false;         // k_wgrad carries no tiles for W0[256:384]: k_update rebuilds that gradient from S
     float* wT = nullptr;            // transposed W1 / W2 (k_tower4)
@@ -138,6 +138,10 @@ struct mamdr_ctx {
     // the transposed copies in wT hold the live W1 / W2 (/ W0[0:256]): true after a call whose steps kept them current,
     // false once the live state may have been replaced from outside (sync_tables) or stepped without them
     bool wT_valid = false;
+    // ... except W1T in a context none of whose tower launches can read it (w1t_unread_now: every k_tower4 grid takes the
+    // W1 image): k_wgrad_adam skips those 128 KB of strided stores per step.  A function of the context's configuration;
+    // mamdr_set_tower_tile, which can change it, drops wT_valid
+    bool w1t_unread = false;
     bool w2_direct_ok = true;       // MAMDR_NO_W2_DIRECT=1: always build the copies at the start of a call (k_transpose_w)
     bool dm_finish_each = false;    // MAMDR_DM_EACH=1: materialise after every step (k_dm_finish per step; A/B measurements)
     int tower_tile = 0;             // 0 auto, 4 / 16 forced (env MAMDR_TOWER_TILE)
@@ -512,6 +516,13 @@ static bool takes_fused_path(const mamdr_ctx* c, int64_t batch) { return c->fuse
 static bool takes_tower4(const mamdr_ctx* c, int64_t rows_pad) {
     return !c->star && c->tower_tile != 16 && (c->tower_tile == 4 || rows_pad <= c->tower4_max_rows);
 }
+// every k_tower4 launch this context can make reads W1 from its LDS image: the largest batch that tower takes (tile 4
+// forced: any batch the context accepts) still fits one round of workgroups
+static bool w1t_unread_now(const mamdr_ctx* c) {
+    if (!c->fused || c->tower_tile == 16) return false;
+    const int64_t max4 = c->tower_tile == 4 ? c->rows_pad_max : std::min<int64_t>(c->tower4_max_rows, c->rows_pad_max);
+    return tower4_never_streams(max4, c->t4_no_w1l);
+}
 // row groups of k_wgrad (= gradient slabs) of a step and the rows of each (measured: 1024 rows, 8 groups of 128: 31.0 us /
 // step vs 32.0 with 4 of 256; batches of <= 512 rows keep 256-row groups: one or two slabs)
 static int wgrad_groups(int rows_pad, int* rpg) {
@@ -581,8 +592,8 @@ static void plan_call(mamdr_ctx* c, CallPlan& P) {
     P.pre = fused && c->use_pre && P.pre_n > 0;
     // the transposed copies: built at the start of the call unless the previous call's steps left them current (no
     // sync_tables since).  On the k_wgrad_adam path with the W1 image (k_tower4<.., W1L, PRE>) only W2T is read, and only
-    // the call's FIRST tower can find it stale -- k_wgrad_adam rewrites every copy with the step -- so that tower reads W2
-    // itself (w2_direct: 32 B runs of 128 rows, four loads per lane) and nothing is transposed at all
+    // the call's FIRST tower can find it stale -- k_wgrad_adam rewrites every copy a tower can read with the step -- so
+    // that tower reads W2 itself (w2_direct: 32 B runs of 128 rows, four loads per lane) and nothing is transposed at all
     P.build_wT = P.need_wT && !c->wT_valid;
     if (P.build_wT && P.pre && c->w2_direct_ok && !accumulate && !c->t4_no_w1l && c->tower_tile != 16 && tower4_w1l_ready() &&
         tower4_takes_w1l(first_rows, c->t4_no_w1l)) {
@@ -909,7 +920,6 @@ static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
     float* const dense_m = (optimizer == MAMDR_OPT_ACCUMULATE ? c->accum : c->adam_m) + c->table_floats;
     TowerArgs ta;
     fill_step_tower(c, P, row_base, rows, ta);
-    ta.w0dom_snap = c->w0dom_copy;
     c->dm_cur ^= 1;
     ta.dms = dm_pending;                       // the previous step of this call (snap == null: none)
     ta.dm_hint = P.domain;
@@ -940,10 +950,10 @@ static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
     fa.v = c->adam_v + c->table_floats;
     fa.L = c->L;
     fa.n_domain = c->cfg.n_domain;
-    fa.w0dom_snap = c->w0dom_copy;
     fa.dm_snap = c->dmsnap[c->dm_cur];         // p plane: the domain table as this step's forward pass saw it
     fa.pdm = c->pdm;
     fa.wT = (P.need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
+    fa.w1t_unread = c->w1t_unread ? 1 : 0;
     fa.optimizer = optimizer;
     fa.alpha = alpha;
     fa.omb1 = P.omb1;
@@ -1331,6 +1341,7 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
             if (const char* de = getenv("MAMDR_NO_W2_DIRECT")) c->w2_direct_ok = atoi(de) == 0;
             if (const char* pe = getenv("MAMDR_NO_PREGATHER")) c->use_pre = atoi(pe) == 0;
         }
+        c->w1t_unread = w1t_unread_now(c);
     }
     if (const char* ev = getenv("MAMDR_NO_TAILFUSE")) c->tail_fuse = atoi(ev) == 0;
     ALLOC(c->slabs, (size_t)WGRAD_MAX_GROUPS * c->slab_ld * sizeof(float));
@@ -2064,6 +2075,8 @@ int mamdr_set_tower_tile(mamdr_ctx* c, int32_t rows) {
     if (rows != c->tower_tile) {
         c->tower_tile = rows;
         c->pg.clear();          // (passes gathered ahead were laid out for the step path of the old choice)
+        c->w1t_unread = w1t_unread_now(c);
+        c->wT_valid = false;    // (W1T may have been left alone under the old choice)
     }
     return MAMDR_OK;
 }

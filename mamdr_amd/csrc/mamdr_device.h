@@ -136,6 +136,11 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 // next kernel's first one, 1.5 us with no stores at all, 2.2 us with write-through stores (tools/stamp_wall.py;
 // nontemporal stores: 2.6 us; plain-, nontemporal- and no-store variants since removed).  The next kernel reads these
 // rows from other XCDs anyway.  4-byte pieces only (wider vectors are stored piecewise).
+// The OPPOSITE boundary keeps plain stores: k_wgrad_adam leaves ~2 MB of parameters and slots dirty, yet the next tower's
+// first workgroup starts 1.3 - 1.4 us after its last one ends.  Written through (4-byte pieces, or 16-byte pieces staged
+// through LDS) that gap is 1.1 - 1.3 us, but k_wgrad_adam itself takes about 1.7 us longer -- its last stores are
+// acknowledged by memory, not by the L2 -- and the headline drops from 44.8 K to 42.6 K domain-steps/s
+// (profiles/ab_param_handoff.txt; both variants removed).
 __device__ __forceinline__ void ws_store1(float* p, float v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -147,11 +147,8 @@ struct TowerArgs {
     // divided by var^2, var = dense[uw_off] (the batch's domain); -1 = off
     int uw_off;
     const float* wT;           // k_tower4 only: transposed W1 / W2 copies
-    // k_wgrad_adam path: the tower also snapshots W0[256:384, :] and the domain table (it only READS the weights;
-    // the fused kernel steps them while other workgroups still need the pre-update values); null otherwise
-    float* w0dom_snap;
-    // domain table (see DmStep): the pending step to apply on the fly, the live rows workgroup d < n_domain writes
-    // back, and the snapshot [3][n_domain][EMB] of (p, m, v) as this step's forward pass saw them
+    // k_wgrad_adam path, domain table (see DmStep): the pending step to apply on the fly, the live rows workgroup
+    // d < n_domain writes back, and the snapshot [3][n_domain][EMB] of (p, m, v) as this step's forward pass saw them
     // pre-gathered pass (k_pass_prep; frozen tables on the k_wgrad_adam path): row i of this launch reads its
     // [user | item] embedding rows, domain and label at xpre[i], pdom[i], plabel[i] -- no chain of dependent loads
     const float* xpre;         // [rows][2 EMB], null = gather through perm / uid / pid
@@ -247,18 +244,6 @@ struct UpdateArgs {
 #endif
 };
 
-// pre-update snapshot of W0[256:384, :] for k_wgrad_adam, by the LAST wave of every tower workgroup (it is not on
-// the row bookkeeping's critical path): float4 i for i in this workgroup's share
-__device__ __forceinline__ void tower_snapshots(const TowerArgs& a, int n_threads, int n_tiles) {
-    if (a.w0dom_snap == nullptr) return;
-    const int st = (int)threadIdx.x - (n_threads - 64);
-    if (st < 0) return;
-    const int total = EMB * H1 / 4;
-    const int per = (total + n_tiles - 1) / n_tiles;
-    const int i0 = (int)blockIdx.x * per, i1 = min(i0 + per, total);
-    const f32x4* w0dom = reinterpret_cast<const f32x4*>(a.dense + a.L.w0 + 2 * EMB * H1);
-    for (int i = i0 + st; i < i1; i += 64) reinterpret_cast<f32x4*>(a.w0dom_snap)[i] = w0dom[i];
-}
 // ---- the tile workgroups' domain-table duty (DmStep).  Everything is requested at kernel start, beside the weight
 // prefetch, from the domain the caller expects (dm_hint: per-domain datasets carry one domain per batch), so the
 // round trip to the partials hides behind the row bookkeeping's own dependent loads:
@@ -484,10 +469,10 @@ struct FusedArgs {
     float* v;
     DenseLayout L;
     int n_domain;
-    const float* w0dom_snap;   // pre-update W0[256:384, :] and domain table (tower_snapshots)
-    const float* dm_snap;
+    const float* dm_snap;      // pre-update domain table (the tower's dm_snap_out)
     float* pdm;                // [8][n_domain][EMB] partial domain-table gradients
     float* wT;                 // nullable: k_tower4's transposed W1 / W2 copies
+    int w1t_unread;            // no tower launch of this context reads W1T (tower4_never_streams): only W2T is kept current
     int optimizer;             // 0 adam, 1 sgd, 2 accumulate
     float alpha, omb1, omb2, eps, two_l2;
     const float* loss_part;    // loss of the step (optional)
@@ -600,6 +585,9 @@ int launch_tower4_train(const TowerArgs& a, hipStream_t s);
 // the W1-image instance of the pre-gathered tower can run (its LDS limit was granted): grids of up to one tile per CU
 bool tower4_w1l_ready();
 bool tower4_takes_w1l(int64_t rows, int no_w1l);      // launch_tower4_train's choice of the W1-image instance for a batch
+// no launch of the frozen-table mlp k_tower4 of up to max_rows rows, pre-gathered or not, can be a streaming instance
+// (the only reader of W1T): every such grid fits one round of workgroups and both W1-image instances have their LDS limit
+bool tower4_never_streams(int64_t max_rows, int no_w1l);
 void launch_transpose_w(const float* dense, const DenseLayout& L, float* wT, hipStream_t s);
 struct EvalFinishArgs {
     const float* loss_part;

@@ -495,7 +495,6 @@ __global__ __launch_bounds__(TOWER_THREADS) void k_tower(const int32_t* __restri
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int tile = blockIdx.x;
-    const int n_tiles = (int)gridDim.x;
     const int r0 = tile * TILE_ROWS;
     int* rowi = reinterpret_cast<int*>(smem + ROWI_OFF);
     // [0,16) label, [16,32) DeepFM fm + linear term, [32,40) per-wave loss, [48,64) DeepFM dlogit
@@ -534,7 +533,6 @@ __global__ __launch_bounds__(TOWER_THREADS) void k_tower(const int32_t* __restri
     if (!pre && k_perm) perm_src = k_perm[k_row_base + min(r0 + (int)(threadIdx.x & (TILE_ROWS - 1)), max(k_rows - 1, 0))];
     __builtin_amdgcn_sched_barrier(0);
     fw0.prefetch(k_w0, k_b0);
-    if (FUSED_OK) tower_snapshots(a, TOWER_THREADS, n_tiles);
     const bool dmw = FUSED_OK && a.dm_snap_out != nullptr;   // k_wgrad_adam path: domain-table duty (DmStep)
     const f32x2 wo_reg = *reinterpret_cast<const f32x2*>(P + a.L.wo + (tid & 31) * 2);
     const float gb_reg = P[a.L.gb];
@@ -800,7 +798,7 @@ void launch_tower_train(const TowerArgs& a, hipStream_t s) {
         MAMDR_LAUNCH((k_tower<true, 384, false>), grid, block, lds, s, a.perm, a.row_base, a.dense + a.L.w0, a.dense + a.L.b0, a.rows, a);
     } else if (a.dxe) {
         MAMDR_LAUNCH((k_tower<true, 256, false>), grid, block, lds, s, a.perm, a.row_base, a.dense + a.L.w0, a.dense + a.L.b0, a.rows, a);
-    } else if (a.xpre || a.dm_snap_out || a.dms.snap || a.w0dom_snap) {
+    } else if (a.xpre || a.dm_snap_out || a.dms.snap) {
         MAMDR_LAUNCH((k_tower<true, 0, false, true>), grid, block, lds, s, a.perm, a.row_base, a.dense + a.L.w0, a.dense + a.L.b0, a.rows, a);
     } else {
         MAMDR_LAUNCH((k_tower<true, 0, false>), grid, block, lds, s, a.perm, a.row_base, a.dense + a.L.w0, a.dense + a.L.b0, a.rows, a);

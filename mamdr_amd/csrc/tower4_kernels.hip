@@ -798,7 +798,6 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     }
     T4STAMP(9);
     T4REAL(11);
-    if (FUSED_OK) tower_snapshots(a, T4_THREADS, n_tiles);      // (W0's rows are L2-resident by now: layer 0 streamed them)
     if (pnn) {
         // d loss / d ip[row][j] = sum_c dz1[row][c] W0x[j][c]: wave sums, then the row's four waves (rows erow2, erow2 + 2
         // belong to waves 4 erow2 .. 4 erow2 + 3) through LDS in wave order; the inner products' chain rule then gives the
@@ -960,6 +959,9 @@ static int t4_cu_count() {
 bool tower4_takes_w1l(int64_t rows, int no_w1l) {
     const int64_t tiles = ((rows + TILE_ROWS - 1) / TILE_ROWS) * (TILE_ROWS / T4_ROWS);
     return !no_w1l && tiles <= t4_cu_count();
+}
+bool tower4_never_streams(int64_t max_rows, int no_w1l) {
+    return tower4_takes_w1l(max_rows, no_w1l) && tower4_w1l_ready() && t4_w1l_raised<false, false, false, false>();
 }
 int launch_tower4_train(const TowerArgs& a, hipStream_t s) {
     const int tiles = ((a.rows + TILE_ROWS - 1) / TILE_ROWS) * (TILE_ROWS / T4_ROWS);   // cover rows_pad

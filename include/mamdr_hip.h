@@ -322,12 +322,30 @@ int mamdr_profile_enable(mamdr_ctx* ctx, int32_t enable);
  * none (that call then gathers as before).  The permutations and the bound columns must not change in between.  At
  * most 16 passes per hint (more: the first 16); everywhere else this is a no-op.  Same rows, same bits.  No reference
  * counterpart: the reference's tf.data iterator re-reads the csv files on every pass (utils/dataset.py:20-38).
- * mamdr_pregather_hits: how many calls found their pass gathered; mamdr_pregather_launches: how many hints led to a
- * gather launch (k_pass_prep_multi) -- both for tests and reports. */
+ * mamdr_pregather_hits: how many calls found their pass gathered; mamdr_pregather_launches: how many hints had their
+ * window gathered ahead of its calls (by one k_pass_prep_multi launch, or by riders, see below) -- both for tests and
+ * reports.
+ *
+ * mamdr_pregather_ahead announces the window AFTER the current one: the list mamdr_pregather_passes will be called with
+ * once the caller has run `spread_steps` more steps of the k_wgrad_adam path.  On a device with more CUs than a
+ * k_wgrad_adam launch has workgroups, every such step then carries a few rider workgroups that gather the next slice of
+ * that window into a second set of the pass buffer; the later mamdr_pregather_passes with the same list (same domains,
+ * permutation pointers, rows and batch, in the same order) adopts that set and launches k_pass_prep_multi only over the
+ * positions the riders did not reach (no launch if there are none).  Any other list, a call that matches no announced
+ * pass, mamdr_bind_table, mamdr_bind_domain_data and mamdr_set_tower_tile drop the announcement, and the next hint
+ * gathers as without it.  A hint only: nothing happens where mamdr_pregather_passes does nothing, in a profiled context
+ * (every kernel is timed on its own there), with spread_steps <= 0 or MAMDR_NO_PREGATHER_RIDE=1, or on a device without
+ * idle CUs.  The permutations must be on the device when the hint is given.  Same rows, same bits.
+ * mamdr_pregather_rider_rows / _remainder_rows: positions (rows and padding rows) gathered by riders / by the launches
+ * over what they did not reach.  (Added within ABI 19: new entry points only, no structure or existing call changed.) */
 int mamdr_pregather_passes(mamdr_ctx* ctx, int32_t n_passes, const int32_t* h_domains, const int32_t* const* h_d_perms,
                            const int64_t* h_pass_rows, int32_t batch);
+int mamdr_pregather_ahead(mamdr_ctx* ctx, int32_t n_passes, const int32_t* h_domains, const int32_t* const* h_d_perms,
+                          const int64_t* h_pass_rows, int32_t batch, int64_t spread_steps);
 int64_t mamdr_pregather_hits(const mamdr_ctx* ctx);
 int64_t mamdr_pregather_launches(const mamdr_ctx* ctx);
+int64_t mamdr_pregather_rider_rows(const mamdr_ctx* ctx);
+int64_t mamdr_pregather_remainder_rows(const mamdr_ctx* ctx);
 /* which kernels a training step of `batch` rows launches (for reports; no reference counterpart):
  *   0  tower -> k_wgrad (split-K slabs) -> k_update
  *   1  [k_pass_prep once per call] tower -> k_wgrad_adam (weight gradients + optimiser step in one launch;

@@ -93,6 +93,9 @@ SIGNATURES = {
     "mamdr_pregather_passes": (_I32, [_VP, _I32, _VP, _VP, _VP, _I32]),
     "mamdr_pregather_hits": (_I64, [_VP]),
     "mamdr_pregather_launches": (_I64, [_VP]),
+    "mamdr_pregather_ahead": (_I32, [_VP, _I32, _VP, _VP, _VP, _I32, _I64]),
+    "mamdr_pregather_rider_rows": (_I64, [_VP]),
+    "mamdr_pregather_remainder_rows": (_I64, [_VP]),
     "mamdr_sync_tables": (C.c_int, [_VP]),
     "mamdr_bind_accumulator": (C.c_int, [_VP, _VP]),
     "mamdr_bind_table": (C.c_int, [_VP, C.c_int, _VP, _I64]),

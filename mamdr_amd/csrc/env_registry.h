@@ -29,6 +29,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_T4_NO_W1L", "lib", "1: k_tower4 without the W1 image in LDS (diagnostic)"},
     {"MAMDR_NO_W2_DIRECT", "lib", "1: k_transpose_w opens a call instead of the W2-in-place tower instance"},
     {"MAMDR_NO_PREGATHER", "lib,bench", "1: no k_pass_prep; the tower gathers its rows itself"},
+    {"MAMDR_NO_PREGATHER_RIDE", "lib", "1: no rider workgroups in k_wgrad_adam; every pass window is gathered by k_pass_prep_multi (same bits)"},
     {"MAMDR_STAR_DENSE_SLICES", "lib", "1: every per-domain Star slice swept every step (diagnostic; same bits)"},
     // ---- library, generic-layer engine (read at mamdr_graph_create)
     {"MAMDR_GRAPH_NO_DEFER", "lib", "1: a pair of weight-gradient launches per layer instead of the queued flat grid"},

@@ -41,6 +41,8 @@ constexpr int FZ_T0 = (2 * EMB / 16) * (H1 / 32);     // 128 tiles of dW0[0:256,
 constexpr int FZ_T1 = (H1 / 16) * (H2 / 32);          // 64 tiles of dW1
 constexpr int FZ_T2 = (H2 / 16) * (H3 / 32);          // 16 tiles of dW2
 constexpr int FZ_TILES = FZ_T0 + FZ_T1 + FZ_T2;       // 208
+// the launch's own workgroups (riders sit behind them)
+__host__ __device__ constexpr int fz_own_wgs(bool with_loss) { return FZ_SBLK + FZ_TILES + FZ_OUTB + (with_loss ? 1 : 0); }
 
 // cycle / device-wide counter stamps of wave 0 (diagnostic build only, tools/stamp_fused.py)
 #define FZSTAMP(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 8 + (k)])
@@ -525,7 +527,109 @@ __device__ __forceinline__ void fz_loss_body(const FusedArgs& a, float* lds) {
     }
 }
 
-// grid: [0, 32) S workgroups (the longest chains first), [32, 240) tiles, 240 / 241 output unit, 242 loss (optional)
+// ---- the pieces of one pre-gathered position (k_pass_prep / k_pass_prep_multi: pass_prep_row, one wave per position;
+// the riders below: fz_ride_body).  Position i < n of a pass is row src of the split: perm[pos] (or pos), clamped ...
+template <typename P>
+__device__ __forceinline__ void prep_ids(const P& a, int n_user, int n_item, int64_t pos, int64_t& src, int& u, int& it) {
+    src = a.perm ? (int64_t)a.perm[pos] : pos;
+    src = src < 0 ? 0 : (src >= a.n_rows_split ? a.n_rows_split - 1 : src);
+    u = a.uid[src];
+    it = a.pid[src];
+    u = u < 0 ? 0 : (u >= n_user ? n_user - 1 : u);
+    it = it < 0 ? 0 : (it >= n_item ? n_item - 1 : it);
+}
+// ... lane l copies float4 l of its 1-KB [user | item] row ...
+__device__ __forceinline__ const f32x4* prep_src(const float* user_tab, const float* item_tab, int u, int it, int lane) {
+    return reinterpret_cast<const f32x4*>(lane < 32 ? user_tab + (size_t)u * EMB + 4 * lane : item_tab + (size_t)it * EMB + 4 * (lane - 32));
+}
+__device__ __forceinline__ void prep_store_row(float* xpre, int64_t i, int lane, f32x4 v) {
+    // (nontemporal: with plain stores, so that the rows might stay in the infinity cache for the towers, the headline workload
+    // ran at 42.6 K instead of 44.3 K domain-steps/s -- profiles/r04_prep_store_ab.txt; variant since removed)
+    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(xpre + (size_t)i * (2 * EMB) + 4 * lane));
+}
+// ... and one lane writes its domain (clamped) and label
+template <typename P>
+__device__ __forceinline__ void prep_meta(const P& a, int n_domain, int64_t src, int32_t* pdom, float* plabel, int64_t i) {
+    const int d = a.dom[src];
+    pdom[i] = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
+    plabel[i] = a.label[src];
+}
+// Positions n .. n + 15 are 16 more rows: k_wgrad_adam contracts whole 16-row tiles counted from EVERY step's own first row
+// (against zero gradients for the padding rows, but 0 x garbage must stay 0); with a batch size that is no multiple of
+// 16 the last step's tile ends up to 15 rows past the call's last row, wherever that row sits
+// (and carry the pass's domain: a tower tile compares all of its rows' domains with the caller's)
+__device__ __forceinline__ void prep_pad_row(float* xpre, int64_t i, int lane) {
+    *reinterpret_cast<f32x4*>(xpre + (size_t)i * (2 * EMB) + 4 * lane) = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+template <typename P>
+__device__ __forceinline__ void prep_pad_meta(const P& a, int32_t* pdom, float* plabel, int64_t i) {
+    pdom[i] = a.pad_dom;
+    plabel[i] = 0.f;
+}
+
+// ---- rider workgroup r: positions [64 r, 64 r + 64) of the launch's slice of the NEXT pass window (RideArgs,
+// mamdr_kernels.h).  It must not become the launch's longest workgroup, so the dependent trips are taken once for all of its
+// positions: thread t resolves position t (perm -> ids, and writes the position's domain and label), the ids cross one
+// barrier through LDS, then every wave issues the row loads of its 8 positions back to back and stores them.
+// position q of the slice -> its row in the pass buffer (< 0: beyond the slice)
+__device__ __forceinline__ int64_t ride_row(const RideArgs& g, int q) {
+    if (q < g.seg[0].count) return g.seg[0].out_off + g.seg[0].first + q;
+    q -= g.seg[0].count;
+    if (q < g.seg[1].count) return g.seg[1].out_off + g.seg[1].first + q;
+    return -1;
+}
+// thread-level part of position `first + q` of a segment -> the user id (< 0: a padding row), the item id
+__device__ __forceinline__ void ride_resolve(const RideArgs& g, const RideArgs::Seg& s, int n_domain, int q, int& u, int& it) {
+    const int64_t i = (int64_t)s.first + q;
+    if (i < s.n) {
+        int64_t src;
+        prep_ids(s, g.n_user, g.n_item, i, src, u, it);
+        prep_meta(s, n_domain, src, g.pdom + s.out_off, g.plabel + s.out_off, i);
+    } else {
+        prep_pad_meta(s, g.pdom + s.out_off, g.plabel + s.out_off, i);
+        u = -1;
+        it = 0;
+    }
+}
+__device__ __forceinline__ void fz_ride_body(const FusedArgs& a, int r, float* lds) {
+    const RideArgs& g = a.ride;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int* ids = reinterpret_cast<int*>(lds);                 // [FZ_RIDE_ROWS][2]
+    if (tid < FZ_RIDE_ROWS) {
+        const int q = r * FZ_RIDE_ROWS + tid;
+        int u = -1, it = 0;
+        if (q < g.seg[0].count) ride_resolve(g, g.seg[0], a.n_domain, q, u, it);
+        else if (q - g.seg[0].count < g.seg[1].count) ride_resolve(g, g.seg[1], a.n_domain, q - g.seg[0].count, u, it);
+        *reinterpret_cast<int2*>(ids + 2 * tid) = make_int2(u, it);
+    }
+    FZSTAMP(1);
+    FZSTAMP(2);
+    __syncthreads();
+    FZSTAMP(3);
+    constexpr int PER = FZ_RIDE_ROWS / FZ_WAVES;            // 8 positions per wave
+    f32x4 v[PER];
+    int us[PER];
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int2 id = *reinterpret_cast<const int2*>(ids + 2 * (w * PER + k));
+        us[k] = __builtin_amdgcn_readfirstlane(id.x);       // wave-uniform: the row pointers stay scalar
+        const int it = __builtin_amdgcn_readfirstlane(id.y);
+        // (a padding row and a position beyond the slice load row 0 for nothing: no branch between the eight requests)
+        v[k] = *prep_src(g.user_tab, g.item_tab, max(us[k], 0), it, lane);
+    }
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int64_t row = ride_row(g, r * FZ_RIDE_ROWS + w * PER + k);        // uniform
+        if (row < 0) continue;
+        if (us[k] >= 0) prep_store_row(g.xpre, row, lane, v[k]);
+        else prep_pad_row(g.xpre, row, lane);
+    }
+    FZSTAMP(4);
+}
+
+// grid: [0, 32) S workgroups (the longest chains first), [32, 240) tiles, 240 / 241 output unit, 242 loss (optional),
+// then the riders (optional)
 __global__ __launch_bounds__(FZ_THREADS) void k_wgrad_adam(const FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = (int)blockIdx.x;
@@ -534,12 +638,15 @@ __global__ __launch_bounds__(FZ_THREADS) void k_wgrad_adam(const FusedArgs a) {
     if (b < FZ_SBLK) fz_s_body(a, b, lds);
     else if (b < FZ_SBLK + FZ_TILES) fz_tile_body(a, b - FZ_SBLK, lds);
     else if (b < FZ_SBLK + FZ_TILES + FZ_OUTB) fz_out_body(a, b - FZ_SBLK - FZ_TILES, lds);
-    else fz_loss_body(a, lds);
+    else if (b < fz_own_wgs(a.loss_out != nullptr)) fz_loss_body(a, lds);
+    else fz_ride_body(a, b - fz_own_wgs(a.loss_out != nullptr), lds);
     FZREAL(6);
 }
 
+int wgrad_adam_own_wgs(bool with_loss) { return fz_own_wgs(with_loss); }
+
 void launch_wgrad_adam(const FusedArgs& a, hipStream_t s) {
-    const int grid = FZ_SBLK + FZ_TILES + FZ_OUTB + (a.loss_out ? 1 : 0);
+    const int grid = fz_own_wgs(a.loss_out != nullptr) + a.ride.n_wg;
     const size_t lds = (size_t)fz_lds_floats(a.n_domain) * sizeof(float);
     if (lds > 65536) {          // 49..64 domains: 72 KB of partial S tiles (raised once: thread-safe static initialiser, to the
                                 // size of the largest domain count this path takes)
@@ -578,34 +685,18 @@ __device__ __forceinline__ void pass_prep_row(const P& a, const float* user_tab,
                                               int n_domain, int64_t pos0, float* xpre, int32_t* pdom, float* plabel, int64_t i) {
     const int lane = threadIdx.x & 63;
     if (i >= a.n) {
-        // 16 more rows: k_wgrad_adam contracts whole 16-row tiles counted from EVERY step's own first row (against
-        // zero gradients for the padding rows, but 0 x garbage must stay 0); with a batch size that is no multiple of
-        // 16 the last step's tile ends up to 15 rows past the call's last row, wherever that row sits
-        // (and carry the pass's domain: a tower tile compares all of its rows' domains with the caller's)
-        if (i < a.n + 16) {
-            *reinterpret_cast<f32x4*>(xpre + (size_t)i * (2 * EMB) + 4 * lane) = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (lane == 0) {
-                pdom[i] = a.pad_dom;
-                plabel[i] = 0.f;
-            }
+        if (i < a.n + PREP_PAD) {
+            prep_pad_row(xpre, i, lane);
+            if (lane == 0) prep_pad_meta(a, pdom, plabel, i);
         }
         return;
     }
-    int64_t src = a.perm ? (int64_t)a.perm[pos0 + i] : pos0 + i;
-    src = src < 0 ? 0 : (src >= a.n_rows_split ? a.n_rows_split - 1 : src);
-    int u = a.uid[src], it = a.pid[src];
-    u = u < 0 ? 0 : (u >= n_user ? n_user - 1 : u);
-    it = it < 0 ? 0 : (it >= n_item ? n_item - 1 : it);
-    const float* row = lane < 32 ? user_tab + (size_t)u * EMB + 4 * lane : item_tab + (size_t)it * EMB + 4 * (lane - 32);
-    const f32x4 v = *reinterpret_cast<const f32x4*>(row);
-    // (nontemporal: with plain stores, so that the rows might stay in the infinity cache for the towers, the headline workload
-    // ran at 42.6 K instead of 44.3 K domain-steps/s -- profiles/r04_prep_store_ab.txt; variant since removed)
-    __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(xpre + (size_t)i * (2 * EMB) + 4 * lane));
-    if (lane == 0) {
-        int d = a.dom[src];
-        pdom[i] = d < 0 ? 0 : (d >= n_domain ? n_domain - 1 : d);
-        plabel[i] = a.label[src];
-    }
+    int64_t src;
+    int u, it;
+    prep_ids(a, n_user, n_item, pos0 + i, src, u, it);
+    const f32x4 v = *prep_src(user_tab, item_tab, u, it, lane);
+    prep_store_row(xpre, i, lane, v);
+    if (lane == 0) prep_meta(a, n_domain, src, pdom, plabel, i);
 }
 __global__ __launch_bounds__(256) void k_pass_prep(const PassPrepArgs a) {
     if ((int)blockIdx.x >= a.n_prep_wgs) {       // the call's transposed weight copies (k_transpose_w) in the same launch
@@ -622,7 +713,7 @@ __global__ __launch_bounds__(256) void k_pass_prep_multi(const PassPrepMultiArgs
     const int wg0 = k ? a.wg_end[k - 1] : 0;
     const PassPrepMultiArgs::Pass& p = a.p[k];
     pass_prep_row(p, a.user_tab, a.item_tab, a.n_user, a.n_item, a.n_domain, (int64_t)0, a.xpre + (size_t)p.out_off * (2 * EMB),
-                  a.pdom + p.out_off, a.plabel + p.out_off, (int64_t)((int)blockIdx.x - wg0) * 4 + (threadIdx.x >> 6));
+                  a.pdom + p.out_off, a.plabel + p.out_off, p.i0 + (int64_t)((int)blockIdx.x - wg0) * 4 + (threadIdx.x >> 6));
 }
 void launch_pass_prep_multi(const PassPrepMultiArgs& a, hipStream_t s) {
     if (a.n_pass <= 0) return;

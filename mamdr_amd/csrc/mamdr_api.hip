@@ -126,7 +126,26 @@ struct mamdr_ctx {
     std::vector<PgEntry> pg;
     size_t pg_pos = 0;
     int64_t pg_hits = 0;            // calls served from an entry (mamdr_pregather_hits)
-    int64_t pg_launches = 0;        // hints that launched k_pass_prep_multi (mamdr_pregather_launches)
+    int64_t pg_launches = 0;        // hints whose window was gathered ahead of its calls (mamdr_pregather_launches)
+    // the second set of the pass buffer: the window announced by mamdr_pregather_ahead is gathered here, slice by slice, by
+    // the riders of k_wgrad_adam while the steps of the current window read the first set; mamdr_pregather_passes with the
+    // same pass list swaps the sets and launches k_pass_prep_multi over what the riders did not reach.  Each set has its
+    // own capacity and growing one never frees the other
+    float* xpre_ahead = nullptr;
+    int32_t* pdom_ahead = nullptr;
+    float* plabel_ahead = nullptr;
+    int64_t pre_cap_ahead = 0;
+    struct Ahead {
+        bool on = false;
+        std::vector<PgEntry> list;      // the announced passes, laid out as mamdr_pregather_passes lays them out
+        std::vector<int64_t> rows;      // ... their row counts (the planner's view)
+        PassPrepMultiArgs args;         // ... and their columns
+        PrePlanCursor cur;              // first position no rider gathered yet
+    } ahead;
+    int n_cu = 0;                   // CUs of the device: k_wgrad_adam's riders fill what its own workgroups leave idle
+    bool ride_on = true;            // MAMDR_NO_PREGATHER_RIDE=1: no riders (mamdr_pregather_ahead does nothing)
+    int64_t pg_rider_rows = 0;      // positions gathered by riders / by the remainder launches of adopted windows
+    int64_t pg_remainder_rows = 0;
     bool use_pre = true;            // MAMDR_NO_PREGATHER=1: the towers gather through perm / uid / pid every step
     float* dmsnap[2] = {nullptr, nullptr};
     int dm_cur = 0;
@@ -512,6 +531,15 @@ static int rows_at(int64_t pass_rows, int64_t row_base, int batch) { return (int
 // one path per call (the pending domain-table step lives across the steps of a call): k_wgrad_adam for batches up to
 // fused_max_batch rows (measured: 27.3 vs 29.5 us / step at 1,024 rows, a tie at 4,096), k_wgrad -> slabs -> k_update above
 static bool takes_fused_path(const mamdr_ctx* c, int64_t batch) { return c->fused && pad_rows(batch) <= c->fused_max_batch; }
+// forget every pass gathered ahead of its call, and the window the riders are working on
+static void drop_pregathered(mamdr_ctx* c) {
+    c->pg.clear();
+    c->ahead.on = false;
+}
+// rider workgroups a k_wgrad_adam launch can carry: the CUs its own workgroups leave idle (none on a smaller part)
+static int ride_wgs(const mamdr_ctx* c, bool with_loss) {
+    return std::max(0, std::min(FZ_RIDE_CAP, c->n_cu - wgrad_adam_own_wgs(with_loss)));
+}
 // small steps run the 4-row-tile tower (all CUs busy), the others the 16-row one (the only one of the Star tower)
 static bool takes_tower4(const mamdr_ctx* c, int64_t rows_pad) {
     return !c->star && c->tower_tile != 16 && (c->tower_tile == 4 || rows_pad <= c->tower4_max_rows);
@@ -618,7 +646,7 @@ static void plan_call(mamdr_ctx* c, CallPlan& P) {
                 break;
             }
         }
-        if (!P.pre_cached) c->pg.clear();
+        if (!P.pre_cached) drop_pregathered(c);
     }
     // Star tower: a batch carries one domain, so D - 1 of the D slices of every per-domain tensor see a zero gradient
     // and only decay -- TF1's dense Adam still moves them every step (star_kernels.hip).  Inside a call those steps are
@@ -908,6 +936,41 @@ static int run_step_tower(mamdr_ctx* c, const TowerArgs& ta, bool use4, int64_t 
     return MAMDR_OK;
 }
 
+// the riders of one k_wgrad_adam launch: the next slice of the announced window (pregather_plan.h), one rider per
+// FZ_RIDE_ROWS positions, into the ahead set of the pass buffer
+static void attach_riders(mamdr_ctx* c, FusedArgs& fa) {
+    mamdr_ctx::Ahead& h = c->ahead;
+    const int riders = ride_wgs(c, fa.loss_out != nullptr);
+    if (riders <= 0) return;
+    const PrePlanSlice sl = pre_plan_next(h.rows.data(), (int)h.rows.size(), h.cur, (int64_t)riders * FZ_RIDE_ROWS);
+    if (sl.count() <= 0) return;
+    RideArgs& g = fa.ride;
+    g.user_tab = c->user_tab;
+    g.item_tab = c->item_tab;
+    g.xpre = c->xpre_ahead;
+    g.pdom = c->pdom_ahead;
+    g.plabel = c->plabel_ahead;
+    g.n_user = c->cfg.n_user;
+    g.n_item = c->cfg.n_item;
+    g.n_wg = (int)((sl.count() + FZ_RIDE_ROWS - 1) / FZ_RIDE_ROWS);
+    for (int k = 0; k < sl.n_seg; ++k) {
+        const PassPrepMultiArgs::Pass& p = h.args.p[sl.seg[k].pass];
+        RideArgs::Seg& q = g.seg[k];
+        q.uid = p.uid;
+        q.pid = p.pid;
+        q.dom = p.dom;
+        q.label = p.label;
+        q.perm = p.perm;
+        q.out_off = p.out_off;
+        q.n = (int)p.n;                          // (a split holds at most 2^31 - 1 rows: mamdr_bind_domain_data)
+        q.n_rows_split = (int)p.n_rows_split;
+        q.first = (int)sl.seg[k].first;
+        q.count = (int)sl.seg[k].count;
+        q.pad_dom = p.pad_dom;
+    }
+    c->pg_rider_rows += sl.count();
+}
+
 // ---- k_wgrad_adam path (frozen-table mlp): tower + weight gradients and optimiser step in one launch; the domain table's
 // step stays pending (DmStep): the next step's tower kernel applies it
 static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
@@ -968,6 +1031,9 @@ static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
 #ifdef MAMDR_STAMPS
     fa.stamps = c->stamps ? c->stamps + 65536 + (c->global_step & 1) * 4096 : nullptr;
 #endif
+    // riders: the next slice of the window announced by mamdr_pregather_ahead (not in a profiled run: it times every kernel
+    // on its own, k_pass_prep_multi among them)
+    if (c->ahead.on && !c->profile) attach_riders(c, fa);
     {
         Prof p(c, MAMDR_KERNEL_WGRAD);
         launch_wgrad_adam(fa, c->stream);
@@ -1324,6 +1390,7 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
                 n_cu <= 0)
                 n_cu = 256;
+            c->n_cu = n_cu;
             const int one_round = std::min(2048, std::max(256, 4 * n_cu));
             c->fused_max_batch = one_round;
             if (cfg->tower == MAMDR_TOWER_MLP && !cfg->emb_trainable) c->tower4_max_rows = one_round;
@@ -1340,6 +1407,7 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
             if (const char* de = getenv("MAMDR_DM_CALL")) c->dm_finish_call = atoi(de) != 0;
             if (const char* de = getenv("MAMDR_NO_W2_DIRECT")) c->w2_direct_ok = atoi(de) == 0;
             if (const char* pe = getenv("MAMDR_NO_PREGATHER")) c->use_pre = atoi(pe) == 0;
+            if (const char* pe = getenv("MAMDR_NO_PREGATHER_RIDE")) c->ride_on = atoi(pe) == 0;
         }
         c->w1t_unread = w1t_unread_now(c);
     }
@@ -1382,7 +1450,7 @@ int mamdr_destroy(mamdr_ctx* c) {
             (void)hipEventDestroy(p.b);
         }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
-    void* ptrs[] = {c->urow_alt, c->irow_alt, c->map_u_alt, c->map_i_alt, c->acts, c->dz, c->dlogit, c->w0dom_copy, c->dm_copy, c->wT, c->dxe, c->urow, c->irow, c->map_u, c->map_i, c->gbuf_u, c->gbuf_i, c->hasdup_u, c->hasdup_i, c->last_u, c->last_i, c->alpha_log, c->star_alpha, c->pdm, c->dmsnap[0], c->dmsnap[1], c->xpre, c->pdom, c->plabel, c->fmq, c->ipbuf, c->glin_u, c->glin_i, c->eff, c->pn, c->star_part, c->star_sums, c->star_dmpart, c->domrow, c->loss_part, c->eval_part, c->slabs,
+    void* ptrs[] = {c->urow_alt, c->irow_alt, c->map_u_alt, c->map_i_alt, c->acts, c->dz, c->dlogit, c->w0dom_copy, c->dm_copy, c->wT, c->dxe, c->urow, c->irow, c->map_u, c->map_i, c->gbuf_u, c->gbuf_i, c->hasdup_u, c->hasdup_i, c->last_u, c->last_i, c->alpha_log, c->star_alpha, c->pdm, c->dmsnap[0], c->dmsnap[1], c->xpre, c->pdom, c->plabel, c->xpre_ahead, c->pdom_ahead, c->plabel_ahead, c->fmq, c->ipbuf, c->glin_u, c->glin_i, c->eff, c->pn, c->star_part, c->star_sums, c->star_dmpart, c->domrow, c->loss_part, c->eval_part, c->slabs,
                     c->tiles, c->thresholds, c->frozen_sumsq, c->sumsq_partials};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -1563,7 +1631,7 @@ int mamdr_bind_table(mamdr_ctx* c, int seg, const float* d_rows, int64_t n_rows)
     if (check_ctx(c)) return MAMDR_EINVAL;
     if (c->cfg.emb_trainable) return fail(MAMDR_ESTATE, "tables are trainable: they live in the flat vector");
     if (!d_rows || ((uintptr_t)d_rows & 15)) return fail(MAMDR_EINVAL, "table pointer null or not 16-byte aligned");
-    c->pg.clear();              // rows gathered ahead of their calls came from the old table
+    drop_pregathered(c);        // rows gathered ahead of their calls came from the old table
     if (seg == MAMDR_SEG_USER_EMB) {
         if (n_rows != c->cfg.n_user) return fail(MAMDR_EINVAL, "user table has %lld rows, config says %d", (long long)n_rows, c->cfg.n_user);
         c->user_tab = d_rows;
@@ -1592,7 +1660,7 @@ int mamdr_bind_domain_data(mamdr_ctx* c, int domain, int split, const int32_t* d
     d->dom = d_domain;
     d->label = d_label;
     d->n = n_rows;
-    c->pg.clear();              // (a pass gathered ahead of its call may have come from the old columns)
+    drop_pregathered(c);        // (a pass gathered ahead of its call may have come from the old columns)
     const int64_t tiles = (n_rows + TILE_ROWS - 1) / TILE_ROWS;
     if (tiles > c->eval_part_cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1604,36 +1672,37 @@ int mamdr_bind_domain_data(mamdr_ctx* c, int domain, int split, const int32_t* d
     return MAMDR_OK;
 }
 
-// the pass buffer holds at least `rows` positions (contents are lost when it grows)
+// a set of the pass buffer holds at least `rows` positions (its contents are lost when it grows; the other set stays)
+static int grow_pass_set(float*& xpre, int32_t*& pdom, float*& plabel, int64_t& have, int64_t rows) {
+    if (rows <= have) return MAMDR_OK;
+    const int64_t cap = rows + rows / 4 + 1024;
+    if (xpre) { (void)hipFree(xpre); (void)hipFree(pdom); (void)hipFree(plabel); }
+    xpre = nullptr; pdom = nullptr; plabel = nullptr; have = 0;
+    HIP_TRY(hipMalloc((void**)&xpre, (size_t)cap * 2 * EMB * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&pdom, (size_t)cap * sizeof(int32_t)));
+    HIP_TRY(hipMalloc((void**)&plabel, (size_t)cap * sizeof(float)));
+    have = cap;
+    return MAMDR_OK;
+}
+// the current set: what was gathered ahead is dropped with it
 static int grow_pass_buffer(mamdr_ctx* c, int64_t rows) {
     if (rows <= c->pre_cap) return MAMDR_OK;
-    const int64_t cap = rows + rows / 4 + 1024;
-    c->pg.clear();
-    if (c->xpre) { (void)hipFree(c->xpre); (void)hipFree(c->pdom); (void)hipFree(c->plabel); }
-    c->xpre = nullptr; c->pdom = nullptr; c->plabel = nullptr; c->pre_cap = 0;
-    HIP_TRY(hipMalloc((void**)&c->xpre, (size_t)cap * 2 * EMB * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&c->pdom, (size_t)cap * sizeof(int32_t)));
-    HIP_TRY(hipMalloc((void**)&c->plabel, (size_t)cap * sizeof(float)));
-    c->pre_cap = cap;
-    return MAMDR_OK;
+    drop_pregathered(c);
+    return grow_pass_set(c->xpre, c->pdom, c->plabel, c->pre_cap, rows);
 }
 
 int64_t mamdr_pregather_hits(const mamdr_ctx* c) { return c ? c->pg_hits : 0; }
 int64_t mamdr_pregather_launches(const mamdr_ctx* c) { return c ? c->pg_launches : 0; }
+int64_t mamdr_pregather_rider_rows(const mamdr_ctx* c) { return c ? c->pg_rider_rows : 0; }
+int64_t mamdr_pregather_remainder_rows(const mamdr_ctx* c) { return c ? c->pg_remainder_rows : 0; }
 
-int mamdr_pregather_passes(mamdr_ctx* c, int32_t n_passes, const int32_t* h_domains, const int32_t* const* h_d_perms,
-                           const int64_t* h_pass_rows, int32_t batch) {
-    if (check_ctx(c)) return MAMDR_EINVAL;
-    if (ready(c)) return MAMDR_ESTATE;
-    if (n_passes < 0 || (n_passes > 0 && !h_domains)) return fail(MAMDR_EINVAL, "pregather: bad pass list");
-    c->pg.clear();
-    c->pg_pos = 0;
-    // a hint: it only has an effect where a call would gather its pass itself (frozen tables, k_wgrad_adam path)
-    if (n_passes == 0 || batch <= 0 || batch > c->cfg.max_batch || !c->use_pre || !takes_fused_path(c, batch))
-        return MAMDR_OK;
-    if (n_passes > PREP_MAX_PASSES) n_passes = PREP_MAX_PASSES;      // the later ones gather themselves
-    PassPrepMultiArgs a;
+// a pass list as both hints lay it out: pass k's n + 16 positions at row off (a multiple of 4) of a set of the pass buffer,
+// one workgroup of k_pass_prep_multi per 4 positions.  -> the rows the set must hold
+static int lay_out_passes(mamdr_ctx* c, int32_t n_passes, const int32_t* h_domains, const int32_t* const* h_d_perms,
+                          const int64_t* h_pass_rows, int32_t batch, PassPrepMultiArgs& a, std::vector<mamdr_ctx::PgEntry>& list,
+                          int64_t& total) {
     memset(&a, 0, sizeof(a));
+    list.clear();
     int64_t off = 0;
     int wgs = 0;
     for (int k = 0; k < n_passes; ++k) {
@@ -1653,34 +1722,104 @@ int mamdr_pregather_passes(mamdr_ctx* c, int32_t n_passes, const int32_t* h_doma
         p.n_rows_split = d->n;
         p.out_off = off;
         p.pad_dom = h_domains[k];
-        const int64_t w = n > 0 ? (n + 16 + 3) / 4 : 0;      // (an empty pass has no steps: nothing to gather)
+        const int64_t w = n > 0 ? (n + PREP_PAD + 3) / 4 : 0;      // (an empty pass has no steps: nothing to gather)
         wgs += (int)w;
         a.wg_end[k] = wgs;
-        c->pg.push_back(mamdr_ctx::PgEntry{h_domains[k], p.perm, n, off, batch});
+        list.push_back(mamdr_ctx::PgEntry{h_domains[k], p.perm, n, off, batch});
         off += 4 * w;
     }
     a.n_pass = n_passes;
-    if (wgs == 0) return MAMDR_OK;
-    {
-        std::vector<mamdr_ctx::PgEntry> keep = c->pg;      // (growing the buffer drops the entries of the OLD buffer)
-        if (int rc = grow_pass_buffer(c, off)) return rc;
-        c->pg = keep;
-    }
     a.user_tab = c->user_tab;
     a.item_tab = c->item_tab;
     a.n_user = c->cfg.n_user;
     a.n_item = c->cfg.n_item;
     a.n_domain = c->cfg.n_domain;
+    total = off;
+    return MAMDR_OK;
+}
+// where a hint has an effect: where a call would gather its pass itself (frozen tables, k_wgrad_adam path)
+static bool pregather_applies(const mamdr_ctx* c, int32_t n_passes, int32_t batch) {
+    return n_passes > 0 && batch > 0 && batch <= c->cfg.max_batch && c->use_pre && takes_fused_path(c, batch);
+}
+
+int mamdr_pregather_passes(mamdr_ctx* c, int32_t n_passes, const int32_t* h_domains, const int32_t* const* h_d_perms,
+                           const int64_t* h_pass_rows, int32_t batch) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (ready(c)) return MAMDR_ESTATE;
+    if (n_passes < 0 || (n_passes > 0 && !h_domains)) return fail(MAMDR_EINVAL, "pregather: bad pass list");
+    const bool had_ahead = c->ahead.on;
+    drop_pregathered(c);
+    c->pg_pos = 0;
+    if (!pregather_applies(c, n_passes, batch)) return MAMDR_OK;
+    if (n_passes > PREP_MAX_PASSES) n_passes = PREP_MAX_PASSES;      // the later ones gather themselves
+    PassPrepMultiArgs a;
+    std::vector<mamdr_ctx::PgEntry> list;
+    int64_t total = 0;
+    if (int rc = lay_out_passes(c, n_passes, h_domains, h_d_perms, h_pass_rows, batch, a, list, total)) return rc;
+    if (total == 0) {
+        c->pg = list;
+        return MAMDR_OK;
+    }
+    // the window announced by mamdr_pregather_ahead: its set takes over and only what the riders did not reach is gathered now
+    mamdr_ctx::Ahead& h = c->ahead;
+    bool adopt = had_ahead && h.list.size() == list.size();
+    for (size_t k = 0; adopt && k < list.size(); ++k)
+        adopt = h.list[k].domain == list[k].domain && h.list[k].perm == list[k].perm && h.list[k].n == list[k].n &&
+                h.list[k].batch == list[k].batch;
+    if (adopt) {
+        std::swap(c->xpre, c->xpre_ahead);
+        std::swap(c->pdom, c->pdom_ahead);
+        std::swap(c->plabel, c->plabel_ahead);
+        std::swap(c->pre_cap, c->pre_cap_ahead);
+        pre_plan_settle(h.rows.data(), n_passes, h.cur);
+        int wgs = 0;
+        int64_t left = 0;
+        for (int k = 0; k < n_passes; ++k) {
+            const int64_t from = k < h.cur.pass ? pre_plan_positions(h.rows[k]) : (k == h.cur.pass ? h.cur.pos : 0);
+            const int64_t todo = pre_plan_positions(h.rows[k]) - from;
+            a.p[k].i0 = from;
+            wgs += (int)((todo + 3) / 4);
+            a.wg_end[k] = wgs;
+            left += todo;
+        }
+        if (left == 0) a.n_pass = 0;
+        c->pg_remainder_rows += left;
+    } else if (int rc = grow_pass_buffer(c, total)) {
+        return rc;
+    }
+    c->pg = list;
     a.xpre = c->xpre;
     a.pdom = c->pdom;
     a.plabel = c->plabel;
-    prof_break(c);
-    {
+    c->pg_launches++;
+    if (a.n_pass > 0) {              // (0: the riders gathered the whole window)
+        prof_break(c);
         Prof p(c, MAMDR_KERNEL_AUX);
         launch_pass_prep_multi(a, c->stream);
-        c->pg_launches++;
     }
     HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_pregather_ahead(mamdr_ctx* c, int32_t n_passes, const int32_t* h_domains, const int32_t* const* h_d_perms,
+                          const int64_t* h_pass_rows, int32_t batch, int64_t spread_steps) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (ready(c)) return MAMDR_ESTATE;
+    if (n_passes < 0 || (n_passes > 0 && !h_domains)) return fail(MAMDR_EINVAL, "pregather: bad pass list");
+    mamdr_ctx::Ahead& h = c->ahead;
+    h.on = false;
+    // a hint about a hint: nothing where mamdr_pregather_passes does nothing, nothing without riders or steps to carry them
+    if (!pregather_applies(c, n_passes, batch) || spread_steps <= 0 || !c->ride_on || c->profile || ride_wgs(c, false) <= 0)
+        return MAMDR_OK;
+    if (n_passes > PREP_MAX_PASSES) n_passes = PREP_MAX_PASSES;
+    int64_t total = 0;
+    if (int rc = lay_out_passes(c, n_passes, h_domains, h_d_perms, h_pass_rows, batch, h.args, h.list, total)) return rc;
+    if (total == 0) return MAMDR_OK;
+    if (int rc = grow_pass_set(c->xpre_ahead, c->pdom_ahead, c->plabel_ahead, c->pre_cap_ahead, total)) return rc;
+    h.rows.clear();
+    for (const mamdr_ctx::PgEntry& e : h.list) h.rows.push_back(e.n);
+    h.cur = PrePlanCursor();
+    h.on = true;
     return MAMDR_OK;
 }
 
@@ -2074,7 +2213,7 @@ int mamdr_set_tower_tile(mamdr_ctx* c, int32_t rows) {
     if (rows == 16 && (c->pnn || c->nfm)) return fail(MAMDR_EINVAL, "the pnn / nfm towers exist as four-row tiles only");
     if (rows != c->tower_tile) {
         c->tower_tile = rows;
-        c->pg.clear();          // (passes gathered ahead were laid out for the step path of the old choice)
+        drop_pregathered(c);    // (passes gathered ahead were laid out for the step path of the old choice)
         c->w1t_unread = w1t_unread_now(c);
         c->wT_valid = false;    // (W1T may have been left alone under the old choice)
     }

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "mamdr_device.h"
+#include "pregather_plan.h"
 
 namespace mamdr {
 
@@ -455,6 +456,30 @@ __device__ __forceinline__ void dm_tile_writer(const TowerArgs& a, int tile, int
     }
 }
 
+// Riders of k_wgrad_adam: the launch's own 242 / 243 workgroups leave CUs of a larger part idle for its whole span, and
+// up to that many rider workgroups gather a slice of the NEXT pass window there (mamdr_pregather_ahead) -- what
+// k_pass_prep_multi would write, bit for bit, into the pass-buffer set that window will adopt.  A rider owns FZ_RIDE_ROWS
+// consecutive positions of the slice; the slice is at most two segments of one pass each (pregather_plan.h).
+constexpr int FZ_RIDE_ROWS = 64;      // positions per rider and launch (8 rows per wave: 8 float4 loads in flight per lane)
+constexpr int FZ_RIDE_CAP = 32;       // riders per launch, at most (and never more than the CUs the launch leaves idle)
+struct RideArgs {
+    const float* user_tab;
+    const float* item_tab;
+    float* xpre;               // the ahead set of the pass buffer
+    int32_t* pdom;
+    float* plabel;
+    int n_user, n_item;
+    int n_wg;                  // rider workgroups of this launch
+    struct Seg {               // positions [first, first + count) of a pass of n rows (+ 16 padding rows) at row out_off
+        const int32_t* uid;
+        const int32_t* pid;
+        const int32_t* dom;
+        const float* label;
+        const int32_t* perm;   // nullable
+        int64_t out_off;
+        int n, n_rows_split, first, count, pad_dom;
+    } seg[2];
+};
 // k_wgrad_adam (fused_kernels.hip): weight gradients + optimiser step of the dense block in one launch
 struct FusedArgs {
     const float* acts;         // [rows_pad][ACT_LD]
@@ -480,11 +505,13 @@ struct FusedArgs {
     const float* frozen_sumsq;
     float l2_emb;
     float* loss_out;
+    RideArgs ride;             // rider workgroups behind the launch's own (n_wg == 0: none)
 #ifdef MAMDR_STAMPS
     unsigned long long* stamps; // diagnostic build only: [workgroups][8] s_memtime stamps of wave 0
 #endif
 };
 void launch_wgrad_adam(const FusedArgs& a, hipStream_t s);
+int wgrad_adam_own_wgs(bool with_loss);      // workgroups of a launch before its riders
 // positions [pos0, pos0 + n) of a pass resolved once per mamdr_train_steps call: src = perm[pos] (or pos), clamped;
 // xpre[i] = [user row | item row] of src, pdom[i] / plabel[i] its domain (clamped) and label
 struct PassPrepArgs {
@@ -526,6 +553,7 @@ struct PassPrepMultiArgs {
         const float* label;
         const int32_t* perm;   // nullable
         int64_t n, n_rows_split, out_off;
+        int64_t i0;            // first position of the launch in this pass (what riders gathered before it is skipped)
         int pad_dom;
     } p[PREP_MAX_PASSES];
 };

@@ -579,6 +579,18 @@ class TowerEngine(DeviceEngine):
         rows = (C.c_int64 * n)(*[(-1 if len(p) < 3 or p[2] is None else int(p[2])) for p in passes])
         L.check(self.lib.mamdr_pregather_passes(self.ctx, n, doms, perms, rows, int(batch_size or self.batch_size)))
 
+    def pregather_ahead(self, passes, batch_size=None, spread_steps=0):
+        """hint (mamdr_pregather_ahead): `passes` is the window AFTER the current one -- the list the next `pregather`
+        will get, once `spread_steps` more steps of the fused path have run.  Rider workgroups of those steps gather it
+        meanwhile; `pregather` with the same list only gathers what they did not reach.  Same rows, same bits; a no-op
+        wherever `pregather` is one, and on a device without idle CUs."""
+        n = len(passes)
+        doms = (C.c_int32 * n)(*[int(p[0]) for p in passes])
+        perms = (C.c_void_p * n)(*[(p[1].data_ptr() if p[1] is not None else None) for p in passes])
+        rows = (C.c_int64 * n)(*[(-1 if len(p) < 3 or p[2] is None else int(p[2])) for p in passes])
+        L.check(self.lib.mamdr_pregather_ahead(self.ctx, n, doms, perms, rows, int(batch_size or self.batch_size),
+                                               int(spread_steps)))
+
     def gather(self, domain, split, perm=None, first_row=0, n_rows=None, out=None):
         n = self.n_rows(domain, split) if n_rows is None else n_rows
         if out is None:

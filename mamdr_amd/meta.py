@@ -34,7 +34,13 @@ class PassWindow(object):
     mamdr_pregather_passes).  Needs a perm_fn that can show its next permutations without consuming them
     (plan.EpochShuffles.peek); anything else -- and any engine without the hint -- runs as before.  A window holds at
     most `max_passes` passes and `budget_rows` rows (1 KB each: the gathered rows should still sit in the 256 MB
-    infinity cache when their steps read them).  Results do not depend on it (same rows, same bits)."""
+    infinity cache when their steps read them).
+
+    A loop that also knows what it will announce AFTERWARDS (`then`: the later announcements of the epoch, in order)
+    lets the engine work on the window after the current one while the current one's steps run (engine.pregather_ahead
+    -> mamdr_pregather_ahead: rider workgroups in the step launches); that window is cut by the same rule, so the hint
+    it later gets as the current window is the list the engine already holds.  Results do not depend on any of it (same
+    rows, same bits)."""
 
     def __init__(self, eng, perm_fn, batch_size, budget_rows=96 * 1024, max_passes=16):
         self.eng, self.perm_fn, self.batch_size = eng, perm_fn, batch_size
@@ -43,33 +49,58 @@ class PassWindow(object):
         self.on = hasattr(perm_fn, "peek") and hasattr(eng, "pregather") and not os.environ.get("MAMDR_NO_PASS_WINDOW")
         if os.environ.get("MAMDR_PASS_WINDOW_ROWS"):          # (A/B measurements of the window size)
             self.budget = int(os.environ["MAMDR_PASS_WINDOW_ROWS"])
-        self.todo, self.left = [], 0
+        self.todo, self.left, self.then = [], 0, []
 
-    def announce(self, domains):
+    def announce(self, domains, then=()):
         self.todo, self.left = list(domains), 0
+        self.then = [list(g) for g in then]
+
+    def _cut(self, todo):
+        """how many of the passes in `todo` the next window takes"""
+        take, rows = 0, 0
+        while take < len(todo) and take < self.max_passes:
+            n = self.eng.n_rows(todo[take], "train")
+            if take and rows + n > self.budget:
+                break
+            rows += n
+            take += 1
+        return take
 
     def step(self):
         """right before every announced pass"""
         if not self.on:
             return
         if self.left == 0 and self.todo:
-            take, rows = 0, 0
-            while take < len(self.todo) and take < self.max_passes:
-                n = self.eng.n_rows(self.todo[take], "train")
-                if take and rows + n > self.budget:
-                    break
-                rows += n
-                take += 1
+            take = self._cut(self.todo)
             chunk, self.todo = self.todo[:take], self.todo[take:]
-            perms = self.perm_fn.peek(chunk)
+            # the window after this one: the rest of this announcement, or else the next announcement that has passes
+            # (a window of one pass is never hinted, see below: nothing to work ahead on)
+            after = next((g for g in [self.todo] + self.then if g), [])
+            after = after[:self._cut(after)]
+            ahead = hasattr(self.eng, "pregather_ahead") and take > 1 and len(after) > 1
+            perms = self.perm_fn.peek(chunk + after) if ahead else None
+            if perms is None:
+                ahead, perms = False, self.perm_fn.peek(chunk)
             if perms is None:          # the loop is not following the announced order: no hint
                 self.on = False
                 return
             # (a window of one pass is what the call does by itself: an empty hint, so that no entry of an earlier
             # window -- same device buffer, other contents two epochs later -- can ever be taken for this pass)
             self.eng.pregather(list(zip(chunk, perms)) if take > 1 else [], self.batch_size)
+            if ahead:
+                steps = sum(-(-self.eng.n_rows(d, "train") // self.batch_size) for d in chunk)
+                self.eng.pregather_ahead(list(zip(after, perms[take:])), self.batch_size, spread_steps=steps)
             self.left = take
         self.left = max(self.left - 1, 0)
+
+
+def dr_announcements(dr, domain_regulation_step=0):
+    """what dr_query announces to its PassWindow for every (query, support) of a plan, in order"""
+    # (a query pass capped to `domain_regulation_step` steps runs over the first few batches of its shuffle only: announced,
+    # ALL of the query domain's rows would be gathered once per support domain and evict useful rows from the window --
+    # ADVICE r04; no hint then, every call gathers exactly the rows its steps read)
+    capped = bool(domain_regulation_step and domain_regulation_step > 0)
+    return [[] if capped else [x for j in support for x in (j, query)] for query, support in dr]
 
 
 def run_pass(eng, d, perm_fn, batch_size, lr, trace, phase, max_steps=0, optimizer="adam", window=None):
@@ -264,20 +295,18 @@ def pcgrad_epoch(eng, outer, cur, aux, seq, aux_plan, perm_fn, batch_size, lr, m
 
 
 def dr_query(eng, theta, phi, query, support, perm_fn, batch_size, lr, meta_lr, trace, merged,
-             merged_method="plus", domain_regulation_step=0, batch_variant=False, sample_num=None, acc=None, pw=None):
+             merged_method="plus", domain_regulation_step=0, batch_variant=False, sample_num=None, acc=None, pw=None,
+             then=()):
     """DR for one query domain (mamdr.py:60-108): phi is updated in place.  Reads theta
-    (fixed during DR) and writes only phi -- the unit that shards across GPUs."""
+    (fixed during DR) and writes only phi -- the unit that shards across GPUs.
+    then: what the caller will announce to `pw` after this query (dr_announcements of the queries that follow)."""
     eng.merge(merged, theta, phi, merged_method)
     if batch_variant:
         acc.zero_()
     assigned = False
     if pw is None:
         pw = PassWindow(eng, perm_fn, batch_size)
-    # (a query pass capped to `domain_regulation_step` steps runs over the first few batches of its shuffle only: announced,
-    # ALL of the query domain's rows would be gathered once per support domain and evict useful rows from the window --
-    # ADVICE r04; no hint then, every call gathers exactly the rows its steps read)
-    capped = bool(domain_regulation_step and domain_regulation_step > 0)
-    pw.announce([] if capped else [x for j in support for x in (j, query)])
+    pw.announce(dr_announcements([(query, support)], domain_regulation_step)[0], then)
     for k, j in enumerate(support):
         if not assigned:
             eng.assign_meta(merged)
@@ -314,7 +343,9 @@ def mamdr_epoch(eng, theta, phis, plan, perm_fn, batch_size, lr, meta_lr, merged
     pw = PassWindow(eng, perm_fn, batch_size)
     # DN phase (mamdr.py:48-57)
     eng.assign_meta(theta)
-    pw.announce(plan["seq"])
+    # (the finetune passes between the queries are announced to nobody: the DR windows then start from scratch)
+    later = [] if finetune_every_epoch else dr_announcements(plan["dr"], domain_regulation_step)
+    pw.announce(plan["seq"], later)
     for d in plan["seq"]:
         pw.step()
         run_pass(eng, d, perm_fn, batch_size, lr, trace, "dn")
@@ -322,9 +353,9 @@ def mamdr_epoch(eng, theta, phis, plan, perm_fn, batch_size, lr, meta_lr, merged
     # DR phase (mamdr.py:59-108)
     merged = scratch if scratch is not None else torch.empty_like(theta)
     acc = torch.zeros_like(theta) if batch_variant else None
-    for query, support in plan["dr"]:
+    for k, (query, support) in enumerate(plan["dr"]):
         dr_query(eng, theta, phis[query], query, support, perm_fn, batch_size, lr, meta_lr, trace, merged,
-                 merged_method, domain_regulation_step, batch_variant, sample_num, acc, pw)
+                 merged_method, domain_regulation_step, batch_variant, sample_num, acc, pw, later[k + 1:])
         if finetune_every_epoch:
             finetune_query(eng, theta, phis[query], query, perm_fn, batch_size, lr, trace, merged, merged_method)
     return trace

@@ -816,7 +816,8 @@ class BalancedMAMDR(object):
             wire += self.tail.floats() * 4
         eng.assign_meta(theta)
         pw = meta.PassWindow(eng, perm_fn, batch_size)
-        pw.announce(local["seq"])
+        later = [] if finetune_every_epoch else meta.dr_announcements(local["dr"], domain_regulation_step)
+        pw.announce(local["seq"], later)
         for d in local["seq"]:
             pw.step()
             meta.run_pass(eng, d, perm_fn, batch_size, lr, trace, "dn")
@@ -846,9 +847,9 @@ class BalancedMAMDR(object):
                 all_reduce(self.delta)
                 wire += self.P * 4
         eng.interp(theta, self.delta, self.zero, meta_lr)
-        for query, support in local["dr"]:
+        for k, (query, support) in enumerate(local["dr"]):
             meta.dr_query(eng, theta, self.phis[query], query, support, perm_fn, batch_size, lr, meta_lr, trace,
-                          self.merged, merged_method, domain_regulation_step, batch_variant, sample_num, acc)
+                          self.merged, merged_method, domain_regulation_step, batch_variant, sample_num, acc, pw, later[k + 1:])
             if finetune_every_epoch:
                 meta.finetune_query(eng, theta, self.phis[query], query, perm_fn, batch_size, lr, trace, self.merged,
                                     merged_method)

@@ -241,6 +241,37 @@ int mamdr_eval_domain(mamdr_ctx* ctx, int domain, int split, int32_t batch, floa
 int mamdr_gather_rows(mamdr_ctx* ctx, int domain, int split, const int32_t* d_perm,
                       int64_t first_row, int64_t n_rows, float* d_out);
 
+/* Top-K item recommendation from the live weights of an mlp / wdl / deepfm tower.  NO REFERENCE COUNTERPART: the
+ * reference's pipeline ends at per-domain loss and AUC (base_model.py:111-144); this scores (query, candidate) pairs
+ * with the same tower in inference mode (dropout off, no regularisers) and ranks them on the device.
+ *   n_query, d_uid, d_domain   the queries: user and domain of each
+ *   d_cand, n_cand             candidate item ids, DISTINCT (not checked) and inside [0, n_item) (ids outside are clamped:
+ *                              range-check on the host); NULL: every item 0 .. n_item - 1, n_cand ignored
+ *   d_excl_off, d_excl_ids     optional CSR, both or neither: query q never gets the ids d_excl_ids[d_excl_off[q] ..
+ *                              d_excl_off[q + 1]), which are ascending
+ *   k                          1 .. 128
+ *   d_ids_out, d_scores_out    [n_query][k]: the k best candidates by logit, descending; equal logits by ascending item
+ *                              id (the id, not the position in d_cand); a NaN logit ranks behind every number; the score
+ *                              is sigmoid(logit) as mamdr_eval_domain's d_pred_out computes it.  A query with fewer than
+ *                              k candidates left ends in id -1 / score 0
+ *   d_scores_all               optional [n_query][n_cand]: sigmoid(logit) of every pair in d_cand order, 0 for an
+ *                              excluded pair
+ * The first layer separates by field -- z0 = (u.W0[0:128] + d.W0[256:384] + b0) + i.W0[128:256] -- so the query term is
+ * formed once per query, the item term once per candidate and call, and layers 1 and 2 + the head per pair: 82,048 flop
+ * per pair against the full tower's 360,576.  A pair's logit is the same bits wherever it sits in the call: full or
+ * remainder tile, any chunking (MAMDR_REC_CHUNK), any neighbouring queries.
+ * Reads the state only: weights, Adam slots, step and dropout counters and gathered pass windows are unchanged; lagging
+ * table rows and a pending domain-table step are brought up to date first (as mamdr_sync_tables).  The workspace is the
+ * context's, allocated on first use.
+ * MAMDR_EINVAL: null / unaligned required pointer, k outside 1..128, n_query <= 0, n_cand <= 0 with a list given;
+ * MAMDR_ESTATE: state or frozen tables not bound; MAMDR_ENOTBUILT: the star / pnn / nfm towers (their first layer does not
+ * separate this way).  (Added within ABI 19: a new entry point only, no structure or existing call changed.) */
+int mamdr_recommend(mamdr_ctx* ctx, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain,
+                    const int32_t* d_cand, int64_t n_cand,
+                    const int64_t* d_excl_off, const int32_t* d_excl_ids,
+                    int32_t k, int32_t* d_ids_out, float* d_scores_out,
+                    float* d_scores_all);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

@@ -24,6 +24,7 @@ SOURCES = [
     ("star_kernels.hip", []),
     ("outer_kernels.hip", ["-ffp-contract=off"]),
     ("graph_engine.hip", []),
+    ("recommend_kernels.hip", []),
     ("mamdr_api.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]

@@ -99,9 +99,11 @@ def n_lanes(config):
     return max(1, int(os.environ.get("MAMDR_LANES") or config["train"].get("lanes", 1) or 1))
 
 
-def main(config, engine_factory=None, on_model=None):
+def main(config, engine_factory=None, on_model=None, recommend=None, recommend_out=None):
     """run.py:71-89.  on_model(model) (optional) sees the built, wrapped model before training starts (tests attach
-    their recorders there)."""
+    their recorders there).  recommend = K (not an option of the reference's run.py): once the pipeline has ended, rank 0 /
+    lane 0 ranks every domain's catalogue for its test users with the weights the run finished with and writes the top K
+    (recommend.report) to recommend_out, by default under train.result_save_path."""
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
     name = config["model"]["name"]
@@ -125,11 +127,11 @@ def main(config, engine_factory=None, on_model=None):
         # (train.lane_sum_block: a test knob -- a one-process run of N * L lanes that adds up in the order of N processes of L
         # lanes, the bit-for-bit reference of the composed run: tests/test_abi_and_parallel.py)
         return parallel.LaneGroup(lanes, outer=(rank, world), sum_block=config["train"].get("lane_sum_block")).run(
-            lambda lane: _run(config, dataset, engine_factory, on_model, rank * lanes + lane))[0]
-    return _run(config, dataset, engine_factory, on_model, rank)
+            lambda lane: _run(config, dataset, engine_factory, on_model, rank * lanes + lane, recommend, recommend_out))[0]
+    return _run(config, dataset, engine_factory, on_model, rank, recommend, recommend_out)
 
 
-def _run(config, dataset, engine_factory, on_model, rank):
+def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recommend_out=None):
     name = config["model"]["name"]
     model = build_model(config, dataset, engine_factory)
     if on_model is not None:
@@ -146,6 +148,9 @@ def _run(config, dataset, engine_factory, on_model, rank):
         avg_loss, avg_auc, domain_loss, domain_auc = model.separate_train_val_test(init_parms=False)
     if rank == 0:
         model.save_result(avg_loss, avg_auc, domain_loss, domain_auc)
+        if recommend:
+            from . import recommend as rec
+            rec.report(model, int(recommend), recommend_out)
     return avg_loss, avg_auc, domain_loss, domain_auc
 
 
@@ -154,9 +159,16 @@ def cli(argv=None):
     parser.add_argument("--config", type=str, help="Train config file", required=True)
     # (not an option of the reference's run.py: the sharded epoch on one GPU, see n_lanes)
     parser.add_argument("--lanes", type=int, default=None, help="run the sharded epoch on this many lanes of one process (train.lanes)")
+    # (not options of the reference's run.py either: its pipeline ends at loss and AUC)
+    parser.add_argument("--recommend", type=int, default=None, metavar="K",
+                        help="after the run: top-K items per domain for its test users, with HitRate / Recall / NDCG @K")
+    parser.add_argument("--recommend-out", type=str, default=None, metavar="FILE",
+                        help=".npz the recommendations go to (default: under train.result_save_path)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
     if args.lanes is not None:
         config["train"]["lanes"] = args.lanes
-    return main(config)
+    if args.recommend is None:
+        return main(config)
+    return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

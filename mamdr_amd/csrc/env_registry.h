@@ -31,6 +31,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_NO_PREGATHER", "lib,bench", "1: no k_pass_prep; the tower gathers its rows itself"},
     {"MAMDR_NO_PREGATHER_RIDE", "lib", "1: no rider workgroups in k_wgrad_adam; every pass window is gathered by k_pass_prep_multi (same bits)"},
     {"MAMDR_STAR_DENSE_SLICES", "lib", "1: every per-domain Star slice swept every step (diagnostic; same bits)"},
+    {"MAMDR_REC_CHUNK", "lib,tests", "candidates per pass of mamdr_recommend's phases (default 16384; rounded up to 64; tests: several chunks at tiny sizes; same bits)"},
     // ---- library, generic-layer engine (read at mamdr_graph_create)
     {"MAMDR_GRAPH_NO_DEFER", "lib", "1: a pair of weight-gradient launches per layer instead of the queued flat grid"},
     {"MAMDR_GRAPH_TILE32_BELOW", "lib", "row count below which the 32 x 32 GEMM tile is used (0: 64 x 64 everywhere)"},

@@ -212,6 +212,14 @@ struct mamdr_ctx {
     float* thresholds = nullptr;
     float* frozen_sumsq = nullptr;  // [4] user, item table; DeepFM linear user, item table
     float* sumsq_partials = nullptr;
+    // mamdr_recommend's workspace (RecArgs, mamdr_kernels.h): allocated on first use for chunks of up to rec_cap candidates
+    int rec_chunk = 16384;          // candidates per pass (MAMDR_REC_CHUNK)
+    int rec_cap = 0;
+    float* rec_P = nullptr;
+    float* rec_lin = nullptr;
+    float* rec_q = nullptr;         // q0 | qud | qs
+    unsigned long long* rec_part = nullptr;
+    unsigned long long* rec_best = nullptr;
 #ifdef MAMDR_STAMPS
     unsigned long long* stamps = nullptr;
 #endif
@@ -1412,6 +1420,8 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
         c->w1t_unread = w1t_unread_now(c);
     }
     if (const char* ev = getenv("MAMDR_NO_TAILFUSE")) c->tail_fuse = atoi(ev) == 0;
+    if (const char* ev = getenv("MAMDR_REC_CHUNK"))
+        if (atoi(ev) > 0) c->rec_chunk = (int)std::min<int64_t>(((int64_t)atoi(ev) + REC_TILE - 1) / REC_TILE * REC_TILE, 1 << 20);
     ALLOC(c->slabs, (size_t)WGRAD_MAX_GROUPS * c->slab_ld * sizeof(float));
     ALLOC(c->tiles, tiles.size() * sizeof(TileDesc));
     ALLOC(c->thresholds, sizeof(thr));
@@ -1451,6 +1461,7 @@ int mamdr_destroy(mamdr_ctx* c) {
         }
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     void* ptrs[] = {c->urow_alt, c->irow_alt, c->map_u_alt, c->map_i_alt, c->acts, c->dz, c->dlogit, c->w0dom_copy, c->dm_copy, c->wT, c->dxe, c->urow, c->irow, c->map_u, c->map_i, c->gbuf_u, c->gbuf_i, c->hasdup_u, c->hasdup_i, c->last_u, c->last_i, c->alpha_log, c->star_alpha, c->pdm, c->dmsnap[0], c->dmsnap[1], c->xpre, c->pdom, c->plabel, c->xpre_ahead, c->pdom_ahead, c->plabel_ahead, c->fmq, c->ipbuf, c->glin_u, c->glin_i, c->eff, c->pn, c->star_part, c->star_sums, c->star_dmpart, c->domrow, c->loss_part, c->eval_part, c->slabs,
+                    c->rec_P, c->rec_lin, c->rec_q, c->rec_part, c->rec_best,
                     c->tiles, c->thresholds, c->frozen_sumsq, c->sumsq_partials};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -2006,6 +2017,98 @@ int mamdr_gather_rows(mamdr_ctx* c, int domain, int split, const int32_t* d_perm
     {
         Prof p(c, MAMDR_KERNEL_GATHER);
         launch_gather(ta, d_out, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+// ---- top-K retrieval (recommend_kernels.hip)
+static int grow_rec_workspace(mamdr_ctx* c, int chunk) {
+    if (chunk <= c->rec_cap) return MAMDR_OK;
+    void* old[] = {c->rec_P, c->rec_lin, c->rec_part};
+    for (void* p : old)
+        if (p) (void)hipFree(p);
+    c->rec_P = c->rec_lin = nullptr;
+    c->rec_part = nullptr;
+    c->rec_cap = 0;
+    HIP_TRY(hipMalloc((void**)&c->rec_P, (size_t)chunk * H1 * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&c->rec_lin, (size_t)chunk * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&c->rec_part, (size_t)REC_QBLOCK * chunk * sizeof(unsigned long long)));
+    if (!c->rec_q) HIP_TRY(hipMalloc((void**)&c->rec_q, (size_t)REC_QBLOCK * (H1 + EMB + 4) * sizeof(float)));
+    if (!c->rec_best) HIP_TRY(hipMalloc((void**)&c->rec_best, (size_t)REC_QBLOCK * REC_KMAX * sizeof(unsigned long long)));
+    c->rec_cap = chunk;
+    return MAMDR_OK;
+}
+
+int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain, const int32_t* d_cand,
+                    int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
+                    float* d_scores_out, float* d_scores_all) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->star || c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend: the %s tower is not built for retrieval (its first layer does not separate "
+                                     "into a query and an item term); mlp, wdl and deepfm are", c->star ? "star" : (c->pnn ? "pnn" : "nfm"));
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "mamdr_recommend: n_query %d must be positive", n_query);
+    if (k < 1 || k > REC_KMAX) return fail(MAMDR_EINVAL, "mamdr_recommend: k %d outside [1, %d]", k, REC_KMAX);
+    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "mamdr_recommend: n_cand %lld with a candidate list given", (long long)n_cand);
+    if (!d_uid || !d_domain || !d_ids_out || !d_scores_out) return fail(MAMDR_EINVAL, "mamdr_recommend: null uid / domain / output pointer");
+    if ((((uintptr_t)d_uid | (uintptr_t)d_domain | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_ids_out |
+          (uintptr_t)d_scores_out | (uintptr_t)d_scores_all) & 3) || ((uintptr_t)d_excl_off & 7))
+        return fail(MAMDR_EINVAL, "mamdr_recommend: a pointer is not aligned to its element size");
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return fail(MAMDR_EINVAL, "mamdr_recommend: the exclusion lists need both their offsets and their ids");
+    if (ready(c)) return MAMDR_ESTATE;
+    if (!d_cand) n_cand = c->cfg.n_item;
+    sync_tables(c);              // lagging table rows, a pending domain-table step: as mamdr_eval_domain
+    prof_break(c);
+    const int chunk = (int)std::min<int64_t>(c->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
+    if (int e = grow_rec_workspace(c, chunk)) return e;
+    RecArgs a;
+    memset(&a, 0, sizeof(a));
+    a.user_tab = c->cfg.emb_trainable ? c->params : c->user_tab;
+    a.item_tab = c->cfg.emb_trainable ? c->params + (size_t)c->cfg.n_user * EMB : c->item_tab;
+    a.dense = c->params + c->table_floats;
+    a.L = c->L;
+    a.n_user = c->cfg.n_user;
+    a.n_item = c->cfg.n_item;
+    a.n_domain = c->cfg.n_domain;
+    a.mode = c->deepfm ? (c->cfg.tower == MAMDR_TOWER_WDL ? 2 : 1) : 0;
+    if (c->deepfm && c->cfg.emb_trainable) {
+        a.lin_user = c->params + c->lin_user_off;
+        a.lin_item = c->params + c->lin_item_off;
+    }
+    a.cand = d_cand;
+    a.n_cand = n_cand;
+    a.excl_ids = d_excl_ids;
+    a.k = k;
+    a.kt = std::min<int>(k, REC_TILE);
+    a.tiles_cap = c->rec_cap / REC_TILE;
+    a.P = c->rec_P;
+    a.lin_i = c->rec_lin;
+    a.q0 = c->rec_q;
+    a.qud = c->rec_q + (size_t)REC_QBLOCK * H1;
+    a.qs = a.qud + (size_t)REC_QBLOCK * EMB;
+    a.part = c->rec_part;
+    a.best = c->rec_best;
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        a.n_query = std::min<int32_t>(REC_QBLOCK, n_query - qb);
+        a.uid = d_uid + qb;
+        a.dom = d_domain + qb;
+        a.excl_off = d_excl_off ? d_excl_off + qb : nullptr;
+        a.ids_out = d_ids_out + (size_t)qb * k;
+        a.scores_out = d_scores_out + (size_t)qb * k;
+        a.scores_all = d_scores_all ? d_scores_all + (size_t)qb * n_cand : nullptr;
+        launch_rec_query_proj(a, c->stream);
+        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
+            a.c_base = c0;
+            a.n_chunk = (int)std::min<int64_t>(chunk, n_cand - c0);
+            a.tiles = (a.n_chunk + REC_TILE - 1) / REC_TILE;
+            a.first_chunk = c0 == 0;
+            a.last_chunk = c0 + chunk >= n_cand;
+            launch_rec_item_proj(a, c->stream);
+            if (!launch_rec_score(a, c->stream))
+                return fail(MAMDR_EHIP, "mamdr_recommend: k_rec_score was refused its LDS limit (hipFuncSetAttribute)");
+            launch_rec_merge(a, c->stream);
+        }
     }
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;

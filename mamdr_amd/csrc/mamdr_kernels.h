@@ -824,4 +824,47 @@ struct PcgArgs {
 };
 void launch_pcgrad(const PcgArgs& a, hipStream_t s);
 
+// recommend_kernels.hip: top-K retrieval (mamdr_recommend).  One RecArgs describes a block of queries x a chunk of
+// candidates; the query-side pointers (uid, dom, excl_off, the outputs) are already offset to the block's first query.
+constexpr int REC_TILE = 64;          // candidates per workgroup of k_rec_score (chunks are multiples of it)
+constexpr int REC_KMAX = 128;         // largest K
+constexpr int REC_QBLOCK = 256;       // queries per pass over the candidates (sizes the workspace)
+struct RecArgs {
+    const float* user_tab;
+    const float* item_tab;
+    const float* dense;
+    DenseLayout L;
+    int n_user, n_item, n_domain;
+    int mode;                  // 0 mlp, 1 deepfm (linear tables + FM term), 2 wdl (linear tables)
+    const float* lin_user;     // null = frozen at their zero initialisation
+    const float* lin_item;
+    const int32_t* uid;        // [n_query]
+    const int32_t* dom;
+    int n_query;
+    const int32_t* cand;       // [n_cand], null: candidate at position p is item p
+    int64_t n_cand, c_base;    // the chunk covers positions [c_base, c_base + n_chunk)
+    int n_chunk;
+    const int64_t* excl_off;   // nullable CSR: the ids excluded for query q are excl_ids[excl_off[q] .. excl_off[q + 1]), ascending
+    const int32_t* excl_ids;
+    int k, kt;                 // K; entries kept per tile = min(K, REC_TILE)
+    int tiles, tiles_cap;      // tiles of this chunk / stride of `part` per query
+    int first_chunk, last_chunk;
+    // workspace (owned by the context)
+    float* P;                  // [chunk][H1] item term of layer 0
+    float* lin_i;              // [chunk] lin_item[cand] (wdl / deepfm)
+    float* q0;                 // [REC_QBLOCK][H1] query term of layer 0 (+ b0)
+    float* qud;                // [REC_QBLOCK][EMB] deepfm: u + d
+    float* qs;                 // [REC_QBLOCK][2] u . d (deepfm) | lin_user + lin_domain
+    unsigned long long* part;  // [REC_QBLOCK][tiles_cap][kt] per-tile lists, descending
+    unsigned long long* best;  // [REC_QBLOCK][REC_KMAX] running best of the call
+    // outputs
+    int32_t* ids_out;          // [n_query][k]
+    float* scores_out;
+    float* scores_all;         // nullable [n_query][n_cand]
+};
+void launch_rec_item_proj(const RecArgs& a, hipStream_t s);
+void launch_rec_query_proj(const RecArgs& a, hipStream_t s);
+bool launch_rec_score(const RecArgs& a, hipStream_t s);        // false: its LDS limit was refused, nothing launched
+void launch_rec_merge(const RecArgs& a, hipStream_t s);
+
 }  // namespace mamdr

@@ -1,0 +1,338 @@
+// Top-K item retrieval from a trained mlp / wdl / deepfm tower (mamdr_recommend, include/mamdr_hip.h).  No reference
+// counterpart: the reference's pipeline ends at per-domain loss and AUC.
+//
+// The tower's first layer separates by field,
+//     z0 = (u . W0[0:128] + d . W0[256:384] + b0) + i . W0[128:256],
+// so the query term is formed once per query (k_rec_query_proj), the item term once per candidate and call
+// (k_rec_item_proj, shared by every query), and only layers 1 and 2 (256 -> 128 -> 64) and the head remain per
+// (query, candidate) pair (k_rec_score): 2 (256 x 128 + 128 x 64 + 64) = 82,048 flop per pair instead of the full tower's
+// 360,576, and no [u | i | d] row is ever materialised.  One launch per phase: the kernel boundary is the hand-off.
+//
+// Determinism: every contraction has ONE reduction order per output element -- k ascending inside the MFMA chains, fixed
+// shuffle trees elsewhere -- and no operand depends on where a pair sits in the grid: a pair's logit is the same bits in a
+// full tile and in the remainder tile, under any chunking, beside any other query.
+//
+// Ranking: one 64-bit key per pair, (order-preserving bits of the logit << 32) | ~id: descending key order = descending
+// logit, equal logits by ascending item id, a NaN logit behind every number; key 0 = no entry (excluded pair, padding).
+// Keys of distinct ids are distinct, so the top K of a query is one well-defined list whatever the tiles and chunks.
+#include "mamdr_kernels.h"
+
+namespace mamdr {
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int REC_THREADS = 256;
+constexpr int IP_ROWS = 32;                   // candidates per workgroup of k_rec_item_proj
+constexpr int XS_LD = EMB + 4;                // LDS row strides: 4 floats of padding keep the 16-B operand reads of 16
+constexpr int H0_LD = H1 + 4;                 // consecutive rows on disjoint banks
+constexpr int H1_LD = H2 + 4;
+constexpr int H2_LD = H3 + 4;
+// k_rec_score's LDS (floats): h0 [64][260]; behind the barrier that ends layer 1, h1 [64][132] and h2 [64][68] reuse it
+constexpr int SC_H1_OFF = 0;
+constexpr int SC_H2_OFF = REC_TILE * H1_LD;                   // 8,448
+constexpr int SC_KEY_OFF = SC_H2_OFF + REC_TILE * H2_LD;      // 12,800: 64 keys (8-byte aligned)
+constexpr int SC_UD_OFF = REC_TILE * H0_LD;                   // 16,640: deepfm's u + d of the query
+constexpr int SC_FLOATS = SC_UD_OFF + EMB;
+static_assert(SC_KEY_OFF + 2 * REC_TILE <= SC_UD_OFF && (SC_KEY_OFF % 2) == 0, "keys inside the h0 region");
+
+__device__ __forceinline__ float rec_sigmoid(float logit) {          // as the evaluation's tower computes it
+    if (logit >= 0.f) return 1.0f / (1.0f + __expf(-logit));
+    const float ez = __expf(logit);
+    return ez / (1.0f + ez);
+}
+__device__ __forceinline__ u64 rec_key(float logit, int id) {
+    const uint32_t b = __float_as_uint(logit);
+    uint32_t hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    if (logit != logit) hi = 1u;                  // below -inf (0x007fffff), above "no entry"
+    return ((u64)hi << 32) | (u64)(~(uint32_t)id);
+}
+__device__ __forceinline__ float rec_key_logit(u64 key) {
+    const uint32_t hi = (uint32_t)(key >> 32);
+    if (hi == 1u) return __uint_as_float(0x7fc00000u);
+    return __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);
+}
+__device__ __forceinline__ int rec_cand_id(const RecArgs& a, int pos) {      // pos < n_chunk
+    const int id = a.cand ? a.cand[a.c_base + pos] : (int)(a.c_base + pos);
+    return clampi(id, 0, a.n_item - 1);
+}
+
+// ---- P[c, 0:256] = I[cand[c]] . W0[128:256, :] for the chunk's candidates: 32 gathered rows per workgroup in LDS, wave w
+// owns columns [64 w, 64 w + 64) as two 32 x 32 x 2 fp32 MFMA chains over k = 0 .. 127
+__global__ __launch_bounds__(REC_THREADS) void k_rec_item_proj(const RecArgs a) {
+    __shared__ float xs[IP_ROWS * XS_LD];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r0 = blockIdx.x * IP_ROWS;
+#pragma unroll
+    for (int t = 0; t < IP_ROWS * (EMB / 4) / REC_THREADS; ++t) {
+        const int e = tid + REC_THREADS * t, r = e >> 5, c4 = e & 31, pos = r0 + r;
+        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+        if (pos < a.n_chunk) v = *reinterpret_cast<const f32x4*>(a.item_tab + (size_t)rec_cand_id(a, pos) * EMB + 4 * c4);
+        *reinterpret_cast<f32x4*>(xs + r * XS_LD + 4 * c4) = v;
+    }
+    if (a.mode != 0 && tid < IP_ROWS && r0 + tid < a.n_chunk)
+        a.lin_i[r0 + tid] = a.lin_item ? a.lin_item[rec_cand_id(a, r0 + tid)] : 0.f;
+    __syncthreads();
+    const float* __restrict__ W = a.dense + a.L.w0 + EMB * H1;
+    const int c = lane & 31, h = lane >> 5;
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+    // the MFMA's two k slots carry k = 8 g + j and 8 g + 4 + j (j = 0 .. 3): one 16-B LDS read feeds four MFMAs
+#pragma unroll 4
+    for (int g = 0; g < EMB / 8; ++g) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(xs + c * XS_LD + 8 * g + 4 * h);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float* wr = W + (size_t)(8 * g + 4 * h + j) * H1 + 64 * w + c;
+            acc0 = MAMDR_MFMA32(av[j], wr[0], acc0);
+            acc1 = MAMDR_MFMA32(av[j], wr[32], acc1);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int pos = r0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (pos < a.n_chunk) {
+            a.P[(size_t)pos * H1 + 64 * w + c] = acc0[r];
+            a.P[(size_t)pos * H1 + 64 * w + 32 + c] = acc1[r];
+        }
+    }
+}
+
+// ---- q0[q, 0:256] = U[uid] . W0[0:128] + Dm[dom] . W0[256:384] + b0, one workgroup per query, thread n owns column n (one
+// fma chain, k ascending); deepfm: u + d and u . d; wdl / deepfm: lin_user[uid] + lin_domain[dom]
+__global__ __launch_bounds__(REC_THREADS) void k_rec_query_proj(const RecArgs a) {
+    __shared__ float us[EMB], ds[EMB], red[2];
+    const int tid = threadIdx.x, q = blockIdx.x;
+    const int uid = clampi(a.uid[q], 0, a.n_user - 1), dom = clampi(a.dom[q], 0, a.n_domain - 1);
+    if (tid < EMB) us[tid] = a.user_tab[(size_t)uid * EMB + tid];
+    else ds[tid - EMB] = a.dense[a.L.dm + dom * EMB + tid - EMB];
+    __syncthreads();
+    const float* __restrict__ W0 = a.dense + a.L.w0;
+    float acc = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < EMB; ++k) acc = fmaf(us[k], W0[(size_t)k * H1 + tid], acc);
+#pragma unroll 8
+    for (int k = 0; k < EMB; ++k) acc = fmaf(ds[k], W0[(size_t)(2 * EMB + k) * H1 + tid], acc);
+    a.q0[(size_t)q * H1 + tid] = acc + a.dense[a.L.b0 + tid];
+    if (a.mode == 1) {
+        float p = 0.f;
+        if (tid < EMB) {
+            a.qud[(size_t)q * EMB + tid] = us[tid] + ds[tid];
+            p = us[tid] * ds[tid];
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) p += __shfl_xor(p, m);
+        if (tid < EMB && (tid & 63) == 0) red[tid >> 6] = p;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        a.qs[2 * q] = a.mode == 1 ? red[0] + red[1] : 0.f;
+        a.qs[2 * q + 1] = a.mode != 0 ? (a.lin_user ? a.lin_user[uid] : 0.f) + a.dense[a.L.ld + dom] : 0.f;
+    }
+}
+
+// descending bitonic sort of one key per lane of a wave
+__device__ __forceinline__ u64 rec_wave_sort(u64 key, int lane) {
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const uint32_t olo = __shfl_xor((uint32_t)key, j), ohi = __shfl_xor((uint32_t)(key >> 32), j);
+            const u64 other = ((u64)ohi << 32) | olo;
+            const bool take_max = ((lane & j) == 0) == ((lane & k) == 0);
+            key = take_max ? (key > other ? key : other) : (key < other ? key : other);
+        }
+    }
+    return key;
+}
+
+// ---- one (query, 64 candidates) tile: h0 = relu(q0[q] + P[c]) staged in LDS, layers 1 and 2 on fp32 MFMA with bias + relu
+// between them, the head (wo, gb, then the wdl / deepfm extras), the optional dense score matrix and the tile's partial
+// top-K.  Layer 1: wave w owns columns [32 w, 32 w + 32) of both 32-row halves (each weight element fetched once per
+// tile); layer 2: wave w owns the 32 x 32 quadrant (w >> 1, w & 1).
+__global__ __launch_bounds__(REC_THREADS) void k_rec_score(const RecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tile = blockIdx.x, q = blockIdx.y;
+    const int p0 = tile * REC_TILE;
+    const float* __restrict__ dense = a.dense;
+    {
+        const int c4 = tid & 63;
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(a.q0 + (size_t)q * H1 + 4 * c4);
+#pragma unroll 4
+        for (int t = 0; t < REC_TILE * (H1 / 4) / REC_THREADS; ++t) {
+            const int r = (tid >> 6) + 4 * t, pos = p0 + r;
+            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (pos < a.n_chunk) {
+                const f32x4 pv = *reinterpret_cast<const f32x4*>(a.P + (size_t)pos * H1 + 4 * c4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fmaxf(qv[e] + pv[e], 0.f);
+            }
+            *reinterpret_cast<f32x4*>(smem + r * H0_LD + 4 * c4) = v;
+        }
+        if (a.mode == 1 && tid < EMB) smem[SC_UD_OFF + tid] = a.qud[(size_t)q * EMB + tid];
+    }
+    __syncthreads();
+    const int c = lane & 31, h = lane >> 5;
+    {
+        const float* __restrict__ W1 = dense + a.L.w1;
+        f32x16 acc0, acc1;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+#pragma unroll 4
+        for (int g = 0; g < H1 / 8; ++g) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(smem + c * H0_LD + 8 * g + 4 * h);
+            const f32x4 a1 = *reinterpret_cast<const f32x4*>(smem + (32 + c) * H0_LD + 8 * g + 4 * h);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float b = W1[(size_t)(8 * g + 4 * h + j) * H2 + 32 * w + c];
+                acc0 = MAMDR_MFMA32(a0[j], b, acc0);
+                acc1 = MAMDR_MFMA32(a1[j], b, acc1);
+            }
+        }
+        const float bias = dense[a.L.b1 + 32 * w + c];
+        __syncthreads();                          // every wave is done with h0: h1 takes its place
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+            smem[SC_H1_OFF + row * H1_LD + 32 * w + c] = fmaxf(acc0[r] + bias, 0.f);
+            smem[SC_H1_OFF + (32 + row) * H1_LD + 32 * w + c] = fmaxf(acc1[r] + bias, 0.f);
+        }
+    }
+    __syncthreads();
+    {
+        const float* __restrict__ W2 = dense + a.L.w2;
+        const int rb = w >> 1, cb = w & 1;
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll 4
+        for (int g = 0; g < H2 / 8; ++g) {
+            const f32x4 av = *reinterpret_cast<const f32x4*>(smem + SC_H1_OFF + (32 * rb + c) * H1_LD + 8 * g + 4 * h);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = MAMDR_MFMA32(av[j], W2[(size_t)(8 * g + 4 * h + j) * H3 + 32 * cb + c], acc);
+        }
+        const float bias = dense[a.L.b2 + 32 * cb + c];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = 32 * rb + (r & 3) + 8 * (r >> 2) + 4 * h;
+            smem[SC_H2_OFF + row * H2_LD + 32 * cb + c] = fmaxf(acc[r] + bias, 0.f);
+        }
+    }
+    __syncthreads();
+    // ---- head: four lanes per pair, 16 hidden units (and 32 elements of deepfm's i . (u + d)) each, a two-step xor tree
+    u64* keys = reinterpret_cast<u64*>(smem + SC_KEY_OFF);
+    {
+        const int row = tid >> 2, part = tid & 3, pos = p0 + row;
+        const bool in = pos < a.n_chunk;
+        const int id = in ? rec_cand_id(a, pos) : 0;
+        const float* wo = dense + a.L.wo + 16 * part;
+        const float* hr = smem + SC_H2_OFF + row * H2_LD + 16 * part;
+        float s = 0.f;
+#pragma unroll
+        for (int n = 0; n < 16; ++n) s = fmaf(hr[n], wo[n], s);
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        float logit = s + dense[a.L.gb];
+        if (a.mode != 0) {
+            float fm = 0.f;
+            if (a.mode == 1) {
+                const float* ir = a.item_tab + (size_t)id * EMB + 32 * part;
+                const float* ud = smem + SC_UD_OFF + 32 * part;
+#pragma unroll
+                for (int k4 = 0; k4 < 8; ++k4) {
+                    const f32x4 iv = *reinterpret_cast<const f32x4*>(ir + 4 * k4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) fm = fmaf(iv[e], ud[4 * k4 + e], fm);
+                }
+                fm += __shfl_xor(fm, 1);
+                fm += __shfl_xor(fm, 2);
+                fm += a.qs[2 * q];
+            }
+            const float lin = a.qs[2 * q + 1] + (in ? a.lin_i[pos] : 0.f);
+            logit += fm + lin;
+        }
+        logit += 0.f;                             // -0 -> +0: equal logits are equal keys
+        if (part == 0) {
+            bool valid = in;
+            if (valid && a.excl_off) {            // the query's excluded ids, ascending
+                int64_t lo = a.excl_off[q], hi = a.excl_off[q + 1];
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (a.excl_ids[mid] < id) lo = mid + 1; else hi = mid;
+                }
+                if (lo < a.excl_off[q + 1] && a.excl_ids[lo] == id) valid = false;
+            }
+            if (in && a.scores_all) a.scores_all[(size_t)q * a.n_cand + a.c_base + pos] = valid ? rec_sigmoid(logit) : 0.f;
+            keys[row] = valid ? rec_key(logit, id) : 0ull;
+        }
+    }
+    __syncthreads();
+    if (w == 0) {
+        const u64 key = rec_wave_sort(keys[lane], lane);
+        if (lane < a.kt) a.part[((size_t)q * a.tiles_cap + tile) * a.kt + lane] = key;
+    }
+}
+
+// ---- one workgroup per query: the chunk's per-tile lists merged into the query's running best 128 (kept across the
+// chunks of a call), 128 keys per round through a 256-key bitonic sort in LDS; a round none of whose keys beats the
+// current K-th is skipped.  The last chunk writes the call's outputs.
+__global__ __launch_bounds__(REC_THREADS) void k_rec_merge(const RecArgs a) {
+    __shared__ u64 buf[2 * REC_KMAX];
+    const int t = threadIdx.x, q = blockIdx.x;
+    u64* best = a.best + (size_t)q * REC_KMAX;
+    buf[t] = (t < REC_KMAX && !a.first_chunk) ? best[t] : 0ull;
+    __syncthreads();
+    const u64* list = a.part + (size_t)q * a.tiles_cap * a.kt;
+    const int n = a.tiles * a.kt;
+    for (int base = 0; base < n; base += REC_KMAX) {
+        const u64 key = (t < REC_KMAX && base + t < n) ? list[base + t] : 0ull;
+        const u64 kth = buf[a.k - 1];
+        if (!__syncthreads_or(key > kth)) continue;
+        if (t < REC_KMAX) buf[REC_KMAX + t] = key;
+        __syncthreads();
+        for (int k = 2; k <= 2 * REC_KMAX; k <<= 1) {
+            for (int j = k >> 1; j > 0; j >>= 1) {
+                const int o = t ^ j;
+                if (o > t) {
+                    const u64 x = buf[t], y = buf[o];
+                    if (((t & k) == 0) ? x < y : x > y) {
+                        buf[t] = y;
+                        buf[o] = x;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+    if (t < REC_KMAX) best[t] = buf[t];
+    if (a.last_chunk && t < a.k) {
+        const u64 key = buf[t];
+        a.ids_out[(size_t)q * a.k + t] = key ? (int32_t)~(uint32_t)key : -1;
+        a.scores_out[(size_t)q * a.k + t] = key ? rec_sigmoid(rec_key_logit(key)) : 0.f;
+    }
+}
+
+}  // namespace
+
+void launch_rec_item_proj(const RecArgs& a, hipStream_t s) {
+    MAMDR_LAUNCH(k_rec_item_proj, dim3((a.n_chunk + IP_ROWS - 1) / IP_ROWS), dim3(REC_THREADS), 0, s, a);
+}
+void launch_rec_query_proj(const RecArgs& a, hipStream_t s) {
+    MAMDR_LAUNCH(k_rec_query_proj, dim3(a.n_query), dim3(REC_THREADS), 0, s, a);
+}
+// -> false: the 66 KB of LDS were refused (hipFuncSetAttribute), nothing was launched
+bool launch_rec_score(const RecArgs& a, hipStream_t s) {
+    static const bool raised = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rec_score),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)(SC_FLOATS * sizeof(float))) == hipSuccess;
+    if (!raised) return false;
+    MAMDR_LAUNCH(k_rec_score, dim3(a.tiles, a.n_query), dim3(REC_THREADS), SC_FLOATS * sizeof(float), s, a);
+    return true;
+}
+void launch_rec_merge(const RecArgs& a, hipStream_t s) {
+    MAMDR_LAUNCH(k_rec_merge, dim3(a.n_query), dim3(REC_THREADS), 0, s, a);
+}
+
+}  // namespace mamdr

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .recommend import exclusion_csr
 
 
 def _ptr(t):
@@ -598,6 +599,43 @@ class TowerEngine(DeviceEngine):
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         L.check(self.lib.mamdr_gather_rows(self.ctx, domain, split_id, _ptr(perm), first_row, n, _ptr(out)))
         return out
+
+    def recommend(self, uids, domains, k, candidates=None, exclude=None, want_scores=False):
+        """top-K items for the queries (uids[q], domains[q]) from the live weights (mamdr_recommend: mlp / wdl / deepfm; no
+        reference counterpart).  candidates: distinct item ids (None: the whole item table); exclude: one array of item ids
+        per query that must not be returned (any order, duplicates allowed).  -> (ids [Q, k] int32, scores [Q, k] float32
+        [, all_scores [Q, n_cand]]) as numpy: by logit descending, equal logits by ascending id, scores = sigmoid(logit);
+        a query with fewer than k candidates left ends in id -1 / score 0; all_scores holds 0 for an excluded pair."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        dom = np.array(np.broadcast_to(np.asarray(domains), uid.shape), np.int32)          # (a writable copy)
+        nq = int(uid.shape[0])
+        if nq and (uid.min() < 0 or uid.max() >= self.n_user or dom.min() < 0 or dom.max() >= self.n_domain):
+            raise ValueError("recommend: user or domain id out of range")
+        cand = None
+        n_cand = self.n_item
+        if candidates is not None:
+            cand = np.ascontiguousarray(np.asarray(candidates).ravel(), np.int32)
+            n_cand = int(cand.shape[0])
+            if n_cand and (cand.min() < 0 or cand.max() >= self.n_item):
+                raise ValueError("recommend: candidate id out of range")
+            if np.unique(cand).shape[0] != n_cand:
+                raise ValueError("recommend: candidate ids must be distinct")
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusion_csr(exclude, nq)
+            if ids.size and ids.max() >= self.n_item:
+                raise ValueError("recommend: excluded item id out of range")
+            ids = ids if ids.size else np.zeros(1, np.int32)       # (a non-null pointer for an all-empty list)
+        dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
+        d_uid, d_dom, d_cand, d_off, d_ids = dev(uid), dev(dom), dev(cand), dev(off), dev(ids)
+        kk = max(int(k), 1)
+        out_ids = torch.empty((max(nq, 1), kk), dtype=torch.int32, device=self.device)
+        out_scores = torch.empty((max(nq, 1), kk), dtype=torch.float32, device=self.device)
+        all_scores = torch.empty((max(nq, 1), max(n_cand, 1)), dtype=torch.float32, device=self.device) if want_scores else None
+        L.check(self.lib.mamdr_recommend(self.ctx, nq, _ptr(d_uid), _ptr(d_dom), _ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids),
+                                         int(k), _ptr(out_ids), _ptr(out_scores), _ptr(all_scores)))
+        res = (out_ids.cpu().numpy()[:nq, :int(k)], out_scores.cpu().numpy()[:nq, :int(k)])
+        return res + (all_scores.cpu().numpy()[:nq, :n_cand],) if want_scores else res
 
     def step_kernel_names(self, batch=None):
         """names of the kernels behind profile_read's FWD_BWD / WGRAD / UPDATE slots for a step of `batch` rows."""

@@ -116,5 +116,9 @@ class GraphEngine(DeviceEngine):
         self._check(self.lib.mamdr_graph_task_ranges(self.ctx, int(domain), *[C.byref(x) for x in v]))
         return [(v[0].value, v[1].value), (v[2].value, v[3].value)]
 
+    def recommend(self, *args, **kwargs):
+        raise NotImplementedError("recommend: the generic-layer towers (kind '%s') are not built for retrieval; the step engine's "
+                                  "mlp / wdl / deepfm towers at width 128, hidden [256, 128, 64] are (TowerEngine.recommend)" % self.kind)
+
     def set_adam_eps(self, eps):
         self._check(self.lib.mamdr_graph_set_adam_eps(self.ctx, float(eps)))

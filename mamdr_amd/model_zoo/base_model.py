@@ -109,6 +109,30 @@ class BaseModel(object):
         """model.evaluate(d['data'], steps=d['n_step']) -> (loss, auc)."""
         return self.model.evaluate(idx, mode)
 
+    # ------------------------------------------------------------------ retrieval (no reference counterpart)
+    def recommend(self, domain, k, users=None, exclude_seen=True):
+        """top-k items of `domain`'s catalogue -- the distinct pids of its three splits -- for `users` (default: the distinct
+        uids of its test split) from the live weights.  exclude_seen: a user never gets an item it has in the domain's train
+        or val split.  -> {"users" [Q], "ids" [Q, k] (-1 behind a short list), "scores" [Q, k], "catalogue": its size}."""
+        cols = [s[domain]["data"] for s in (self.dataset.train_dataset, self.dataset.val_dataset, self.dataset.test_dataset)
+                if domain in s]
+        catalogue = np.unique(np.concatenate([np.asarray(c["pid"], np.int64) for c in cols]))
+        if users is None:
+            users = np.unique(np.asarray(self.dataset.test_dataset[domain]["data"]["uid"], np.int64))
+        users = np.asarray(users, np.int64).ravel()
+        exclude = None
+        if exclude_seen:
+            seen = {}
+            for store in (self.dataset.train_dataset, self.dataset.val_dataset):
+                if domain in store:
+                    c = store[domain]["data"]
+                    for u, p in zip(np.asarray(c["uid"]).tolist(), np.asarray(c["pid"]).tolist()):
+                        seen.setdefault(u, []).append(p)
+            exclude = [seen.get(int(u), ()) for u in users]
+        ids, scores = self.model.recommend(users, np.full(users.shape, domain, np.int64), k, candidates=catalogue,
+                                           exclude=exclude)[:2]
+        return {"users": users, "ids": ids, "scores": scores, "catalogue": int(catalogue.shape[0])}
+
     # ------------------------------------------------------------------ finetune / separate training
     def separate_train_val_test(self, init_parms=True):
         """base_model.py:41-109.  init_parms=False is the finetune stage: plain SGD with

@@ -1,0 +1,142 @@
+"""pairs/s of mamdr_recommend beside the only way to score the same (user, item, domain) pairs without it:
+mamdr_eval_domain with d_pred_out over a bound split that holds those triples (one full 384 -> 256 -> 128 -> 64 -> 1
+forward per row).  Taobao-10-shaped synthetic data (23,778 users, 6,932 items, 10 domains), frozen tables, the mlp tower
+by default.
+
+    python tools/recommend_bench.py [--tower mlp|wdl|deepfm] [--queries 512] [--k 10] [--reps 5] [--out profiles/recommend_bench.txt]
+
+Method (device time): each leg runs in a child process of its own under `timeout -k 10`; inside it two warm-up calls, then
+`reps` calls between two HIP events recorded on the engine's stream; the figure is elapsed / reps.  The recommend leg's
+time covers all of its launches (query term, item term, scoring, merge); the eval leg's covers k_tower<eval> and its
+loss / regulariser tail, as a caller of mamdr_eval_domain pays them.  Neither covers uploads or read-backs.  The recommend
+leg also checks, for 8 of the queries, that both paths score the same pairs alike.  Nothing is tuned per leg: default
+chunk, default tile sizes, the same queries and the whole item table as candidates.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def build(tower, batch):
+    import torch  # noqa: F401
+    from mamdr_amd import synthetic
+    from mamdr_amd.engine import TowerEngine
+    spec = synthetic.SHAPES["taobao10"]
+    rs = np.random.RandomState(7)
+    n_user, n_item, n_domain = spec["n_user"], spec["n_item"], spec["n_domain"]
+    eng = TowerEngine(n_user, n_item, n_domain, batch, dropout=0.0, emb_trainable=False, tower=tower)
+    eng.bind_table("user_emb", (rs.standard_normal((n_user, 128)) * 0.1).astype(np.float32))
+    eng.bind_table("item_emb", (rs.standard_normal((n_item, 128)) * 0.1).astype(np.float32))
+    scale = {"domain_emb": 0.05, "W0": 0.06, "W1": 0.07, "W2": 0.1, "wo": 0.17, "gb": 0.0}
+    named = {n: (rs.standard_normal(cnt) * scale.get(n, 0.05)).astype(np.float32) for n, (off, cnt) in eng.segments.items()}
+    eng.set_weights(eng.pack(named))
+    return eng, n_user, n_item, n_domain
+
+
+def timed(eng, call, reps):
+    import torch
+    for _ in range(2):
+        call()
+    torch.cuda.synchronize(eng.device)
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(eng.stream)
+    for _ in range(reps):
+        call()
+    b.record(eng.stream)
+    torch.cuda.synchronize(eng.device)
+    return a.elapsed_time(b) / reps
+
+
+def eval_preds(eng, uid, pid, dom, reps=0):
+    """mamdr_eval_domain with d_pred_out over a split holding the triples -> (preds, ms per call or None)."""
+    import torch
+    from mamdr_amd import _lib as L
+    eng.bind_domain_data(0, "test", uid, pid, dom, np.zeros(uid.shape[0], np.float32))
+    preds = torch.empty(uid.shape[0], dtype=torch.float32, device=eng.device)
+    p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+
+    def call():
+        L.check(eng.lib.mamdr_eval_domain(eng.ctx, 0, L.SPLIT_TEST, eng.eval_batch, p(eng._loss1), p(eng._hist), p(preds)))
+    ms = timed(eng, call, reps) if reps else (call(), None)[1]
+    torch.cuda.synchronize(eng.device)
+    return preds.cpu().numpy(), ms
+
+
+def leg(args):
+    import torch
+    from mamdr_amd import _lib as L
+    eng, n_user, n_item, n_domain = build(args.tower, 1024)
+    rs = np.random.RandomState(3)
+    uids = rs.choice(n_user, args.queries, replace=False).astype(np.int32)
+    doms = (uids % n_domain).astype(np.int32)
+    pairs = int(args.queries) * n_item
+    res = {"leg": args.leg, "tower": args.tower, "queries": int(args.queries), "items": n_item, "pairs": pairs, "k": args.k,
+           "device": torch.cuda.get_device_name(eng.device), "reps": args.reps}
+    if args.leg == "recommend":
+        d_uid, d_dom = torch.from_numpy(uids).to(eng.device), torch.from_numpy(doms).to(eng.device)
+        out_i = torch.empty((args.queries, args.k), dtype=torch.int32, device=eng.device)
+        out_s = torch.empty((args.queries, args.k), dtype=torch.float32, device=eng.device)
+        p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+
+        def call():
+            L.check(eng.lib.mamdr_recommend(eng.ctx, args.queries, p(d_uid), p(d_dom), None, 0, None, None, args.k, p(out_i),
+                                            p(out_s), None))
+        res["ms"] = timed(eng, call, args.reps)
+        # both paths score the same pairs alike (8 queries)
+        _, _, dense = eng.recommend(uids[:8], doms[:8], args.k, want_scores=True)
+        preds, _ = eval_preds(eng, np.repeat(uids[:8], n_item), np.tile(np.arange(n_item, dtype=np.int32), 8), np.repeat(doms[:8], n_item))
+        res["max_abs_diff_vs_eval"] = float(np.abs(dense.ravel() - preds).max())
+    else:
+        _, res["ms"] = eval_preds(eng, np.repeat(uids, n_item), np.tile(np.arange(n_item, dtype=np.int32), args.queries),
+                                  np.repeat(doms, n_item), reps=args.reps)
+    res["pairs_per_s"] = pairs / (res["ms"] * 1e-3)
+    eng.close()
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tower", default="mlp", choices=["mlp", "wdl", "deepfm"])
+    ap.add_argument("--queries", type=int, default=512)
+    ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--leg", default=None, choices=["recommend", "eval"])
+    ap.add_argument("--leg-timeout", type=int, default=240)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recommend_bench.txt"))
+    args = ap.parse_args()
+    if args.leg:
+        return leg(args)
+    got = {}
+    for name in ("recommend", "eval"):          # one child per leg, each under its own time limit; a failed leg ends the run
+        cmd = ["timeout", "-k", "10", str(args.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", name,
+               "--tower", args.tower, "--queries", str(args.queries), "--k", str(args.k), "--reps", str(args.reps)]
+        run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
+        lines = [l for l in run.stdout.splitlines() if l.startswith("RESULT ")]
+        if run.returncode != 0 or not lines:
+            sys.stderr.write(run.stdout[-2000:] + run.stderr[-4000:])
+            raise SystemExit("leg %s failed (exit %d): nothing further is started" % (name, run.returncode))
+        got[name] = json.loads(lines[-1][7:])
+    r, e = got["recommend"], got["eval"]
+    ratio = r["pairs_per_s"] / e["pairs_per_s"]
+    text = ("%s  %s  tower %s  %d queries x %d items = %d pairs, K %d, %d reps (HIP events, 2 warm-up calls, a process per leg)\n"
+            "  mamdr_recommend                 %9.3f ms / call  %8.1f M pairs/s  (max |score - eval path's| over 8 queries: %.2e)\n"
+            "  mamdr_eval_domain + d_pred_out  %9.3f ms / call  %8.1f M pairs/s\n"
+            "  recommend / eval throughput     %.2fx  (flop per pair: 82,048 / 360,576 = 0.23)\n" % (
+                time.strftime("%Y-%m-%d"), r["device"], args.tower, r["queries"], r["items"], r["pairs"], r["k"], r["reps"],
+                r["ms"], r["pairs_per_s"] / 1e6, r["max_abs_diff_vs_eval"], e["ms"], e["pairs_per_s"] / 1e6, ratio))
+    print(text)
+    with open(args.out, "a") as f:
+        f.write(text)
+
+
+if __name__ == "__main__":
+    main()

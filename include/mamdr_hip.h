@@ -272,6 +272,43 @@ int mamdr_recommend(mamdr_ctx* ctx, int32_t n_query, const int32_t* d_uid, const
                     int32_t k, int32_t* d_ids_out, float* d_scores_out,
                     float* d_scores_all);
 
+/* Per-user grouped AUC (GAUC, Zhou et al., DIN, KDD 2018) of one split's predictions.  NO REFERENCE COUNTERPART: the
+ * reference reports one 500-threshold AUC per domain (base_model.py:111-144) and nothing per user.  Stateless, any stream.
+ * Definition.  For one split of one domain, group the rows by uid.  For a group u with r_u rows, P_u of them positive
+ * (label != 0, as the eval histogram classifies) and N_u negative:
+ *   T_u = 2 * #{(p, n): s_p > s_n} + #{(p, n): s_p == s_n} over positive rows p and negative rows n of the group.  It is
+ *   an integer.  AUC_u = T_u / (2 * P_u * N_u), the Mann-Whitney statistic with ties counted half.
+ *   Predictions compare as IEEE floats, with three rules.  -0 equals +0.  A NaN is below every number, -inf included.
+ *   Two NaNs are equal.
+ *   A group is valid when P_u > 0 and N_u > 0.
+ *   GAUC = sum_valid r_u * AUC_u / sum_valid r_u.
+ *   Report beside it n_groups, n_valid and rows_valid = sum_valid r_u.
+ *   When no group is valid, GAUC is reported as 0.0 with n_valid = 0.  This is the convention of
+ *   recommend.ranking_metrics.
+ * Arguments (device pointers; mamdr_amd/gauc.py: group_plan builds the grouping on the host):
+ *   d_pred, d_label [n]        predictions and labels in file order
+ *   d_order [n]                row indices grouped by uid (an index outside [0, n) is clamped: check on the host)
+ *   d_group_off [n_groups + 1] positions into d_order, ascending from 0 to n; n_groups <= n
+ *   d_tile_group, d_tile_first [n_tiles], both or neither: EVERY group of more than 64 rows is covered exactly once by
+ *                              tiles (group, first position into d_order) of up to 256 consecutive positions (not
+ *                              checked: a larger group without tiles reports T_u = P_u = 0); groups of up to 64 rows
+ *                              need none
+ *   d_T, d_P                   optional [n_groups]: T_u (uint64) and P_u (uint32) of every group, valid or not
+ *   d_result [4]               doubles: num = sum_valid r_u * AUC_u (GAUC = num / rows_valid), rows_valid, n_valid,
+ *                              n_groups -- the three counts are exact integers
+ * T_u and P_u are exact integers; the fp64 sum runs over one fixed tree per n_groups, so d_result is the same bits from
+ * run to run, under any permutation of the rows (with the plan of the permuted rows) and for any order of a group's
+ * members inside d_order.  No floating-point atomics.  Nothing synchronises the device; the only memory written is the
+ * outputs (a missing d_T / d_P and the tree's partial sums live in a stream-ordered allocation of the call,
+ * hipMallocAsync / hipFreeAsync on `stream`).
+ * MAMDR_EINVAL, before any device call: a null d_result, d_group_off, or (n > 0) d_pred / d_label / d_order; n < 0 or
+ * beyond int32; n_groups < 0 or > n; n_tiles < 0; a tile list given with n_tiles = 0, or n_tiles > 0 without both lists.
+ * (Added within ABI 19: a new entry point only, no structure or existing call changed.) */
+int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_order, int64_t n,
+                    const int64_t* d_group_off, int64_t n_groups,
+                    const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
+                    uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

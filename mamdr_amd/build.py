@@ -25,6 +25,9 @@ SOURCES = [
     ("outer_kernels.hip", ["-ffp-contract=off"]),
     ("graph_engine.hip", []),
     ("recommend_kernels.hip", []),
+    # gauc_kernels: the fp64 terms are a division, a multiplication and additions as the host definition computes them
+    # -> no fma fusion; its register / LDS / scratch report: profiles/gauc_bench.txt
+    ("gauc_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
     ("mamdr_api.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]

@@ -103,7 +103,8 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     """run.py:71-89.  on_model(model) (optional) sees the built, wrapped model before training starts (tests attach
     their recorders there).  recommend = K (not an option of the reference's run.py): once the pipeline has ended, rank 0 /
     lane 0 ranks every domain's catalogue for its test users with the weights the run finished with and writes the top K
-    (recommend.report) to recommend_out, by default under train.result_save_path."""
+    (recommend.report) to recommend_out, by default under train.result_save_path.  train.report_gauc (run.py --gauc; not a
+    key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py)."""
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
     name = config["model"]["name"]
@@ -111,6 +112,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     if (world > 1 or lanes > 1) and not ("meta" in name and ("mamdr" in name or "domain_negotiation" in name or "reptile" in name)):
         raise NotImplementedError("multi-process / multi-lane runs shard the MAMDR (DN + DR), Domain Negotiation and Reptile "
                                   "wrappers only; got '%s'" % name)
+    if config["train"].get("report_gauc") and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.report_gauc (run.py --gauc): the per-user grouped AUC is not gathered across processes "
+                                  "or lanes (parallel.gather_domain_scalars carries loss and AUC only); run it with one "
+                                  "process and train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
     if lanes > 1:
         # (under N processes the lanes of every rank are a slice of ONE world of N * lanes participants: a rank's DR queries
@@ -164,11 +169,15 @@ def cli(argv=None):
                         help="after the run: top-K items per domain for its test users, with HitRate / Recall / NDCG @K")
     parser.add_argument("--recommend-out", type=str, default=None, metavar="FILE",
                         help=".npz the recommendations go to (default: under train.result_save_path)")
+    parser.add_argument("--gauc", action="store_true",
+                        help="also report the impression-weighted per-user AUC (GAUC) of every evaluation (train.report_gauc)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
     if args.lanes is not None:
         config["train"]["lanes"] = args.lanes
+    if args.gauc:
+        config["train"]["report_gauc"] = True
     if args.recommend is None:
         return main(config)
     return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

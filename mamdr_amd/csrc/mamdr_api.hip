@@ -2114,6 +2114,63 @@ int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const i
     return MAMDR_OK;
 }
 
+// ---- per-user grouped AUC (gauc_kernels.hip): stateless, like the outer updates
+int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_order, int64_t n, const int64_t* d_group_off,
+                    int64_t n_groups, const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
+                    uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream) {
+    if (!d_result || !d_group_off) return fail(MAMDR_EINVAL, "mamdr_group_auc: null result / group offsets pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_group_auc: n %lld outside [0, 2^31)", (long long)n);
+    if (n_groups < 0 || n_groups > n)
+        return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld groups for %lld rows", (long long)n_groups, (long long)n);
+    if (n > 0 && (!d_pred || !d_label || !d_order)) return fail(MAMDR_EINVAL, "mamdr_group_auc: null pred / label / order pointer");
+    if (n_tiles < 0 || n_tiles > n) return fail(MAMDR_EINVAL, "mamdr_group_auc: n_tiles %lld for %lld rows", (long long)n_tiles, (long long)n);
+    if (n_tiles == 0 && (d_tile_group || d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: a tile list given without tiles");
+    if (n_tiles > 0 && (!d_tile_group || !d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld tiles need both of their lists", (long long)n_tiles);
+    if ((((uintptr_t)d_pred | (uintptr_t)d_label | (uintptr_t)d_order | (uintptr_t)d_tile_group | (uintptr_t)d_P) & 3) ||
+        (((uintptr_t)d_group_off | (uintptr_t)d_tile_first | (uintptr_t)d_T | (uintptr_t)d_result) & 7))
+        return fail(MAMDR_EINVAL, "mamdr_group_auc: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    GaucArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.order = d_order;
+    a.group_off = d_group_off;
+    a.tile_group = d_tile_group;
+    a.tile_first = d_tile_first;
+    a.n = n;
+    a.n_groups = n_groups;
+    a.n_tiles = n_tiles;
+    a.n_parts = gauc_parts(n_groups);
+    a.result = d_result;
+    // the call's own scratch, ordered on its stream: [T if not given | partial sums | P if not given]
+    const size_t t_bytes = d_T ? 0 : (size_t)n_groups * sizeof(uint64_t);
+    const size_t part_bytes = (size_t)a.n_parts * (sizeof(double) + 2 * sizeof(uint64_t));
+    const size_t p_bytes = d_P ? 0 : (size_t)n_groups * sizeof(uint32_t);
+    char* ws = nullptr;
+    if (t_bytes + part_bytes + p_bytes) HIP_TRY(hipMallocAsync((void**)&ws, t_bytes + part_bytes + p_bytes, s));
+    a.T = d_T ? reinterpret_cast<unsigned long long*>(d_T) : reinterpret_cast<unsigned long long*>(ws);
+    a.part_num = reinterpret_cast<double*>(ws + t_bytes);
+    a.part_rows = reinterpret_cast<unsigned long long*>(a.part_num + a.n_parts);
+    a.part_valid = a.part_rows + a.n_parts;
+    a.P = d_P ? d_P : reinterpret_cast<uint32_t*>(ws + t_bytes + part_bytes);
+    hipError_t e = hipSuccess;
+    if (n_groups > 0) {
+        e = hipMemsetAsync(a.T, 0, (size_t)n_groups * sizeof(uint64_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(a.P, 0, (size_t)n_groups * sizeof(uint32_t), s);
+    }
+    if (e == hipSuccess) {
+        launch_gauc(a, s);
+        e = hipGetLastError();
+    }
+    if (ws) {
+        const hipError_t ef = hipFreeAsync(ws, s);
+        if (e == hipSuccess) e = ef;
+    }
+    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_group_auc: %s", hipGetErrorString(e));
+    return MAMDR_OK;
+}
+
 // ---- outer updates
 static int check_vec(const void* p, const char* name) {
     if (!p) return fail(MAMDR_EINVAL, "%s is null", name);

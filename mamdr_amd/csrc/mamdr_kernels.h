@@ -867,4 +867,26 @@ void launch_rec_query_proj(const RecArgs& a, hipStream_t s);
 bool launch_rec_score(const RecArgs& a, hipStream_t s);        // false: its LDS limit was refused, nothing launched
 void launch_rec_merge(const RecArgs& a, hipStream_t s);
 
+// gauc_kernels.hip: per-user grouped AUC of one split's predictions (mamdr_group_auc)
+constexpr int GAUC_SMALL = 64;        // groups of up to this many rows: one wave each (k_gauc_small)
+constexpr int GAUC_TILE = 256;        // larger groups: positions per workgroup of k_gauc_tiles
+struct GaucArgs {
+    const float* pred;             // [n] in file order
+    const float* label;            // [n]
+    const int32_t* order;          // [n] row indices, grouped
+    const int64_t* group_off;      // [n_groups + 1] into order
+    const int32_t* tile_group;     // [n_tiles]
+    const int64_t* tile_first;     // [n_tiles] first position (into order) of the tile
+    int64_t n, n_groups, n_tiles;
+    unsigned long long* T;         // [n_groups], zeroed by the call
+    uint32_t* P;                   // [n_groups], zeroed by the call
+    double* part_num;              // [n_parts] partial sums of k_gauc_terms' blocks
+    unsigned long long* part_rows;
+    unsigned long long* part_valid;
+    int64_t n_parts;
+    double* result;                // [4] num, rows_valid, n_valid, n_groups
+};
+int64_t gauc_parts(int64_t n_groups);
+void launch_gauc(const GaucArgs& a, hipStream_t s);
+
 }  // namespace mamdr

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import gauc
 from .recommend import exclusion_csr
 
 
@@ -264,6 +265,7 @@ class DeviceEngine(FlatVectorOps):
             self._check(self._c_bind_aux(self.ctx, _ptr(self.aux)))
         self.tables = {}
         self.data = {}          # (domain, split) -> dict of device columns
+        self._gauc_plans = {}   # (domain, split) -> the split's grouping by uid on the device (group_auc_plan)
         self._acc = None
         self._ema = None            # set_moving_average
         self._hist = torch.zeros(2 * 501, dtype=torch.int32, device=self.device)
@@ -352,6 +354,7 @@ class DeviceEngine(FlatVectorOps):
             "label": torch.from_numpy(np.ascontiguousarray(label, np.float32)).to(self.device),
         }
         self.data[(domain, split)] = cols
+        self._gauc_plans.pop((domain, split), None)         # (the grouping by uid of the rows bound before)
         self._check(self._c_bind_domain_data(self.ctx, domain, split_id, _ptr(cols["uid"]), _ptr(cols["pid"]),
                                              _ptr(cols["domain"]), _ptr(cols["label"]), uid.shape[0]))
 
@@ -391,19 +394,69 @@ class DeviceEngine(FlatVectorOps):
                                           opt, float(lr), _ptr(loss_out)))
         return n_steps
 
-    def evaluate(self, domain, split, want_preds=False):
-        """model.evaluate(data, steps=n_step) -> (loss, auc[, preds]); syncs to read back."""
+    def evaluate(self, domain, split, want_preds=False, want_gauc=False):
+        """model.evaluate(data, steps=n_step) -> (loss, auc[, hist, preds][, gauc report]); syncs to read back.
+        want_gauc (no reference counterpart): the predictions stay on the device, mamdr_group_auc runs behind the evaluation
+        on the engine's stream over the split's uid groups, and gauc.finish's report dict ends the tuple."""
         n = self.n_rows(domain, split)
-        preds = torch.empty(n, dtype=torch.float32, device=self.device) if want_preds else None
+        preds = torch.empty(n, dtype=torch.float32, device=self.device) if (want_preds or want_gauc) else None
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         self._check(self._c_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1),
                                         _ptr(self._hist), _ptr(preds)))
+        if want_gauc:
+            res4 = self._group_auc_launch(preds, self.data[(domain, split)]["label"], self.group_auc_plan(domain, split))
         hist = self._hist.cpu().numpy().astype(np.int64)
         loss = float(self._loss1.cpu().numpy()[0])
         auc, _ = auc_from_histogram(hist)
+        out = (loss, auc)
         if want_preds:
-            return loss, auc, hist.reshape(2, 501), preds.cpu().numpy()
-        return loss, auc
+            out += (hist.reshape(2, 501), preds.cpu().numpy())
+        if want_gauc:
+            out += (gauc.finish(*res4.cpu().numpy().tolist()),)
+        return out
+
+    # ------------------------------------------------------------ per-user grouped AUC (no reference counterpart)
+    def group_auc_plan(self, domain, split):
+        """the device copy of gauc.group_plan over the bound split's uid column: built at first use, uploaded once, dropped
+        when bind_domain_data replaces the split."""
+        plan = self._gauc_plans.get((domain, split))
+        if plan is None:
+            plan = self.upload_group_plan(gauc.group_plan(self.data[(domain, split)]["uid"].cpu().numpy()))
+            self._gauc_plans[(domain, split)] = plan
+        return plan
+
+    def upload_group_plan(self, plan):
+        """gauc.GroupPlan of numpy arrays -> the same of device tensors."""
+        return gauc.GroupPlan(*[torch.from_numpy(np.ascontiguousarray(a, t)).to(self.device) for a, t in
+                                zip(plan, (np.int32, np.int64, np.int32, np.int64))])
+
+    def _group_auc_launch(self, preds, labels, plan, T=None, P=None):
+        """mamdr_group_auc on the engine's stream -> the device tensor of its four results (nothing is read back)."""
+        res4 = torch.empty(4, dtype=torch.float64, device=self.device)
+        n_tiles = int(plan.tile_group.shape[0])
+        L.check(self.lib.mamdr_group_auc(_ptr(preds), _ptr(labels), _ptr(plan.order), int(plan.order.shape[0]),
+                                         _ptr(plan.group_off), int(plan.group_off.shape[0]) - 1,
+                                         _ptr(plan.tile_group if n_tiles else None), _ptr(plan.tile_first if n_tiles else None),
+                                         n_tiles, _ptr(T), _ptr(P), _ptr(res4), self._s()))
+        return res4
+
+    def group_auc(self, preds, labels, plan, want_groups=False):
+        """GAUC (gauc.py's definition) of device tensors preds / labels [n] fp32 under `plan` (gauc.GroupPlan of device
+        tensors: upload_group_plan, group_auc_plan) -> gauc.finish's report; want_groups adds "T" (uint64) and "P" (uint32)
+        per group as numpy."""
+        n = int(plan.order.shape[0])
+        if preds.numel() != n or labels.numel() != n or preds.dtype != torch.float32 or labels.dtype != torch.float32:
+            raise ValueError("group_auc: preds and labels must be fp32 device tensors of the plan's %d rows" % n)
+        G = int(plan.group_off.shape[0]) - 1
+        T = P = None
+        if want_groups:
+            # (torch has no uint64 / uint32 arithmetic: int64 / int32 storage, reinterpreted on the host)
+            T = torch.empty(max(G, 1), dtype=torch.int64, device=self.device)
+            P = torch.empty(max(G, 1), dtype=torch.int32, device=self.device)
+        rep = gauc.finish(*self._group_auc_launch(preds, labels, plan, T, P).cpu().numpy().tolist())
+        if want_groups:
+            rep.update(T=T.cpu().numpy()[:G].view(np.uint64), P=P.cpu().numpy()[:G].view(np.uint32))
+        return rep
 
     def bind_accumulator(self, acc):
         """meta-gradient accumulator of the MAML / MLDG / PCGrad meta passes (maml.py:202); optimizer="accumulate" adds

@@ -41,6 +41,7 @@ class BaseModel(object):
         sizes = {d: v["n_data"] for d, v in dataset.train_dataset.items()}
         self.shuffler = mplan.PassShuffler(sizes, dataset.shuffle_buffer_size, dataset.seed,
                                            shuffle=getattr(dataset, "shuffle_train", True))
+        self.gauc_reports = {}        # train.report_gauc: {(mode, domain): gauc.finish's report of the latest evaluation}
         self.model = self.build_model()
         self._build_early_stop()
 
@@ -106,8 +107,15 @@ class BaseModel(object):
                              phase, max_steps, optimizer)
 
     def evaluate_domain(self, idx, mode):
-        """model.evaluate(d['data'], steps=d['n_step']) -> (loss, auc)."""
-        return self.model.evaluate(idx, mode)
+        """model.evaluate(d['data'], steps=d['n_step']) -> (loss, auc).  Under train.report_gauc (not a key of the
+        reference's configs) the evaluation also yields the split's per-user grouped AUC (gauc.py) -- of whatever weights the
+        caller has installed: the merged per-domain ones under MAMDR / DN, the finetuned ones in the finetune stage --,
+        remembered per (mode, domain) for _summarise / save_result."""
+        if not self.train_config.get("report_gauc"):
+            return self.model.evaluate(idx, mode)
+        loss, auc, report = self.model.evaluate(idx, mode, want_gauc=True)
+        self.gauc_reports[(mode, idx)] = report
+        return loss, auc
 
     # ------------------------------------------------------------------ retrieval (no reference counterpart)
     def recommend(self, domain, k, users=None, exclude_seen=True):
@@ -213,7 +221,17 @@ class BaseModel(object):
         self._format_print_domain_metric("AUC", domain_auc)
         print("Overall {} Loss: {}, AUC: {}, Weighted AUC: {}".format(mode, avg_loss, avg_auc,
                                                                      self._weighted_auc(mode, domain_auc)))
+        if self.train_config.get("report_gauc"):
+            domain_gauc = {d: self.gauc_reports[(mode, d)]["gauc"] for d in domain_auc if (mode, d) in self.gauc_reports}
+            self._format_print_domain_metric("GAUC", domain_gauc)
+            print("Overall {} GAUC: {}, Weighted GAUC: {}".format(mode, *self._gauc_summary(mode, domain_gauc)))
         return avg_loss, avg_auc, domain_loss, domain_auc
+
+    def _gauc_summary(self, mode, domains):
+        """(plain mean over the domains with a valid user, sum rows_valid_d * gauc_d / sum rows_valid_d) of the remembered
+        reports of `mode`."""
+        from .. import gauc
+        return gauc.summarise({d: self.gauc_reports[(mode, d)] for d in domains})
 
     def _format_print_domain_metric(self, name, domain_metric):
         print("{}: ".format(name))
@@ -268,8 +286,13 @@ class BaseModel(object):
         with open(osp.join(result_path, "config.json.example"), "w") as f:
             json.dump(self.config, f)
         with open(osp.join(result_path, "result.json"), "w") as f:
-            json.dump({"avg_loss": avg_loss, "avg_auc": avg_auc, "domain_loss": domain_loss,
-                       "domain_auc": domain_auc}, f)
+            result = {"avg_loss": avg_loss, "avg_auc": avg_auc, "domain_loss": domain_loss, "domain_auc": domain_auc}
+            if self.train_config.get("report_gauc"):         # the test evaluations behind domain_auc
+                reps = {d: self.gauc_reports[("test", d)] for d in domain_auc if ("test", d) in self.gauc_reports}
+                result["avg_gauc"], result["weighted_gauc"] = self._gauc_summary("test", reps)
+                result["domain_gauc"] = {d: r["gauc"] for d, r in reps.items()}
+                result["domain_gauc_users"] = {d: r["n_valid"] for d, r in reps.items()}
+            json.dump(result, f)
         self.save_model(osp.join(result_path, "model_parameters.npz"))
         return result_path
 

@@ -264,13 +264,36 @@ int mamdr_gather_rows(mamdr_ctx* ctx, int domain, int split, const int32_t* d_pe
  * table rows and a pending domain-table step are brought up to date first (as mamdr_sync_tables).  The workspace is the
  * context's, allocated on first use.
  * MAMDR_EINVAL: null / unaligned required pointer, k outside 1..128, n_query <= 0, n_cand <= 0 with a list given;
- * MAMDR_ESTATE: state or frozen tables not bound; MAMDR_ENOTBUILT: the star / pnn / nfm towers (their first layer does not
- * separate this way).  (Added within ABI 19: a new entry point only, no structure or existing call changed.) */
+ * MAMDR_ESTATE: state or frozen tables not bound; MAMDR_ENOTBUILT: the pnn / nfm towers (their first layer does not
+ * separate this way) and the star tower, whose first layer separates for one domain at a time only: its item term depends
+ * on the domain, so a call that mixes domains stays refused and the single-domain call declared next serves it.  (Added
+ * within ABI 19: a new entry point only, no structure or existing call changed.) */
 int mamdr_recommend(mamdr_ctx* ctx, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain,
                     const int32_t* d_cand, int64_t n_cand,
                     const int64_t* d_excl_off, const int32_t* d_excl_ids,
                     int32_t k, int32_t* d_ids_out, float* d_scores_out,
                     float* d_scores_all);
+
+/* Top-K item recommendation with every query of the call in ONE domain, from the live weights of an mlp / wdl / deepfm /
+ * star tower.  NO REFERENCE COUNTERPART, as mamdr_recommend.  `domain` is a host integer; every other argument, the
+ * ranking keys, the tie and NaN rules, the -1 / 0 padding, d_scores_all, the chunking (MAMDR_REC_CHUNK) and the "same bits
+ * wherever the pair sits" guarantee are mamdr_recommend's; on mlp / wdl / deepfm the outputs are the bytes of
+ * mamdr_recommend with d_domain[q] = domain for every q.
+ * Star: in inference PartitionedNorm with domain d's moving statistics is a per-column affine xn = x * scale_d + shift_d
+ * and layer 0 a plain matmul with K0_d = Ws0 * Wd0[d], b0_d = bs0 + bd0[d] (partitioned_norm.py:143-165,
+ * star_fcn.py:105-110), so z0 = (xn_u.K0_d[0:128] + xn_dm.K0_d[256:384] + b0_d) + xn_i.K0_d[128:256]: the same query term /
+ * item term / per-pair split, on the effective dense block and PartitionedNorm workspace that mamdr_eval_domain builds for
+ * the domain.  The scores are mamdr_eval_domain's d_pred_out of the same (user, item, domain) triples up to fp32
+ * summation order.
+ * Reads the state only, as mamdr_recommend (lazily replayed per-domain slices are brought up to date first); the effective
+ * block and the PartitionedNorm workspace it overwrites are rebuilt by every training and evaluation call before use.
+ * MAMDR_EINVAL: domain outside [0, n_domain), and mamdr_recommend's cases; MAMDR_ESTATE: as mamdr_recommend;
+ * MAMDR_ENOTBUILT: the pnn / nfm towers.  (Added within ABI 19: a new entry point only, no structure or existing call
+ * changed.) */
+int mamdr_recommend_domain(mamdr_ctx* ctx, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                           const int32_t* d_cand, int64_t n_cand,
+                           const int64_t* d_excl_off, const int32_t* d_excl_ids,
+                           int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all);
 
 /* Per-user grouped AUC (GAUC, Zhou et al., DIN, KDD 2018) of one split's predictions.  NO REFERENCE COUNTERPART: the
  * reference reports one 500-threshold AUC per domain (base_model.py:111-144) and nothing per user.  Stateless, any stream.

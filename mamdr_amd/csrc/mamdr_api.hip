@@ -2040,25 +2040,24 @@ static int grow_rec_workspace(mamdr_ctx* c, int chunk) {
     return MAMDR_OK;
 }
 
-int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain, const int32_t* d_cand,
-                    int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
-                    float* d_scores_out, float* d_scores_all) {
-    if (check_ctx(c)) return MAMDR_EINVAL;
-    if (c->star || c->pnn || c->nfm)
-        return fail(MAMDR_ENOTBUILT, "mamdr_recommend: the %s tower is not built for retrieval (its first layer does not separate "
-                                     "into a query and an item term); mlp, wdl and deepfm are", c->star ? "star" : (c->pnn ? "pnn" : "nfm"));
-    if (n_query <= 0) return fail(MAMDR_EINVAL, "mamdr_recommend: n_query %d must be positive", n_query);
-    if (k < 1 || k > REC_KMAX) return fail(MAMDR_EINVAL, "mamdr_recommend: k %d outside [1, %d]", k, REC_KMAX);
-    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "mamdr_recommend: n_cand %lld with a candidate list given", (long long)n_cand);
-    if (!d_uid || !d_domain || !d_ids_out || !d_scores_out) return fail(MAMDR_EINVAL, "mamdr_recommend: null uid / domain / output pointer");
+// the body of both entry points: `domain` < 0 = mamdr_recommend (query q in d_domain[q]), otherwise every query in `domain`
+static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                          const int32_t* d_domain, const int32_t* d_cand, int64_t n_cand, const int64_t* d_excl_off,
+                          const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    const bool per_query = domain < 0;
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (k < 1 || k > REC_KMAX) return fail(MAMDR_EINVAL, "%s: k %d outside [1, %d]", fn, k, REC_KMAX);
+    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
+    if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
+        return fail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
     if ((((uintptr_t)d_uid | (uintptr_t)d_domain | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_ids_out |
           (uintptr_t)d_scores_out | (uintptr_t)d_scores_all) & 3) || ((uintptr_t)d_excl_off & 7))
-        return fail(MAMDR_EINVAL, "mamdr_recommend: a pointer is not aligned to its element size");
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
     if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
-        return fail(MAMDR_EINVAL, "mamdr_recommend: the exclusion lists need both their offsets and their ids");
+        return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
     if (ready(c)) return MAMDR_ESTATE;
     if (!d_cand) n_cand = c->cfg.n_item;
-    sync_tables(c);              // lagging table rows, a pending domain-table step: as mamdr_eval_domain
+    sync_tables(c);              // lagging table rows and lazily replayed per-domain slices: as mamdr_eval_domain
     prof_break(c);
     const int chunk = (int)std::min<int64_t>(c->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
     if (int e = grow_rec_workspace(c, chunk)) return e;
@@ -2068,6 +2067,26 @@ int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const i
     a.item_tab = c->cfg.emb_trainable ? c->params + (size_t)c->cfg.n_user * EMB : c->item_tab;
     a.dense = c->params + c->table_floats;
     a.L = c->L;
+    a.dom_all = per_query ? -1 : domain;
+    if (c->star) {
+        // inference in `domain`: its moving statistics and merged kernels, exactly as mamdr_eval_domain prepares them.
+        // c->eff / c->pn are the training step's workspaces too: star_step rebuilds both at step 0 of every call
+        StarPrepArgs pa;
+        memset(&pa, 0, sizeof(pa));
+        pa.blk = c->params + c->table_floats;
+        pa.SL = c->SL;
+        pa.L = c->L;
+        pa.n_domain = c->cfg.n_domain;
+        pa.d = domain;
+        pa.eff = c->eff;
+        pa.pn = c->pn;
+        pa.aux = c->aux;
+        pa.AL = c->AL;
+        pa.train = 0;
+        launch_star_prep(pa, c->stream);
+        a.dense = c->eff;
+        a.pn = c->pn;
+    }
     a.n_user = c->cfg.n_user;
     a.n_item = c->cfg.n_item;
     a.n_domain = c->cfg.n_domain;
@@ -2092,7 +2111,7 @@ int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const i
     for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
         a.n_query = std::min<int32_t>(REC_QBLOCK, n_query - qb);
         a.uid = d_uid + qb;
-        a.dom = d_domain + qb;
+        a.dom = per_query ? d_domain + qb : nullptr;
         a.excl_off = d_excl_off ? d_excl_off + qb : nullptr;
         a.ids_out = d_ids_out + (size_t)qb * k;
         a.scores_out = d_scores_out + (size_t)qb * k;
@@ -2106,12 +2125,40 @@ int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const i
             a.last_chunk = c0 + chunk >= n_cand;
             launch_rec_item_proj(a, c->stream);
             if (!launch_rec_score(a, c->stream))
-                return fail(MAMDR_EHIP, "mamdr_recommend: k_rec_score was refused its LDS limit (hipFuncSetAttribute)");
+                return fail(MAMDR_EHIP, "%s: k_rec_score was refused its LDS limit (hipFuncSetAttribute)", fn);
             launch_rec_merge(a, c->stream);
         }
     }
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;
+}
+
+int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain, const int32_t* d_cand,
+                    int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
+                    float* d_scores_out, float* d_scores_all) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->star)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend: the star tower is not built for retrieval with a domain per query (its "
+                                     "first layer separates into a query and an item term per domain only: "
+                                     "mamdr_recommend_domain); mlp, wdl and deepfm are");
+    if (c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend: the %s tower is not built for retrieval (its first layer does not separate "
+                                     "into a query and an item term); mlp, wdl and deepfm are", c->pnn ? "pnn" : "nfm");
+    return recommend_body(c, "mamdr_recommend", -1, n_query, d_uid, d_domain, d_cand, n_cand, d_excl_off, d_excl_ids, k,
+                          d_ids_out, d_scores_out, d_scores_all);
+}
+
+int mamdr_recommend_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
+                           int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k,
+                           int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend_domain: the %s tower is not built for retrieval (its first layer does not "
+                                     "separate into a query and an item term); mlp, wdl, deepfm and star are", c->pnn ? "pnn" : "nfm");
+    if (domain < 0 || domain >= c->cfg.n_domain)
+        return fail(MAMDR_EINVAL, "mamdr_recommend_domain: domain %d outside [0, %d)", domain, c->cfg.n_domain);
+    return recommend_body(c, "mamdr_recommend_domain", domain, n_query, d_uid, nullptr, d_cand, n_cand, d_excl_off, d_excl_ids,
+                          k, d_ids_out, d_scores_out, d_scores_all);
 }
 
 // ---- per-user grouped AUC (gauc_kernels.hip): stateless, like the outer updates

@@ -824,7 +824,7 @@ struct PcgArgs {
 };
 void launch_pcgrad(const PcgArgs& a, hipStream_t s);
 
-// recommend_kernels.hip: top-K retrieval (mamdr_recommend).  One RecArgs describes a block of queries x a chunk of
+// recommend_kernels.hip: top-K retrieval (mamdr_recommend, mamdr_recommend_domain).  One RecArgs describes a block of queries x a chunk of
 // candidates; the query-side pointers (uid, dom, excl_off, the outputs) are already offset to the block's first query.
 constexpr int REC_TILE = 64;          // candidates per workgroup of k_rec_score (chunks are multiples of it)
 constexpr int REC_KMAX = 128;         // largest K
@@ -840,6 +840,9 @@ struct RecArgs {
     const float* lin_item;
     const int32_t* uid;        // [n_query]
     const int32_t* dom;
+    int dom_all;               // -1: query q is in domain dom[q]; otherwise every query is in this domain and dom may be null
+    const float* pn;           // Star: PartitionedNorm's workspace of domain dom_all (scale | shift | ... | xdom, k_star_prep
+                               // with train = 0) and `dense` the effective block of that domain; null otherwise
     int n_query;
     const int32_t* cand;       // [n_cand], null: candidate at position p is item p
     int64_t n_cand, c_base;    // the chunk covers positions [c_base, c_base + n_chunk)

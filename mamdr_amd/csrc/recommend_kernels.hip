@@ -1,5 +1,6 @@
-// Top-K item retrieval from a trained mlp / wdl / deepfm tower (mamdr_recommend, include/mamdr_hip.h).  No reference
-// counterpart: the reference's pipeline ends at per-domain loss and AUC.
+// Top-K item retrieval from a trained mlp / wdl / deepfm tower (mamdr_recommend) and, one domain per call, from those and
+// the Star tower (mamdr_recommend_domain; include/mamdr_hip.h).  No reference counterpart: the reference's pipeline ends at
+// per-domain loss and AUC.
 //
 // The tower's first layer separates by field,
 //     z0 = (u . W0[0:128] + d . W0[256:384] + b0) + i . W0[128:256],
@@ -7,6 +8,11 @@
 // (k_rec_item_proj, shared by every query), and only layers 1 and 2 (256 -> 128 -> 64) and the head remain per
 // (query, candidate) pair (k_rec_score): 2 (256 x 128 + 128 x 64 + 64) = 82,048 flop per pair instead of the full tower's
 // 360,576, and no [u | i | d] row is ever materialised.  One launch per phase: the kernel boundary is the hand-off.
+//
+// Star (RecArgs::pn set, one domain d per call): in inference PartitionedNorm is the per-column affine
+// xn = x * scale_d + shift_d and layer 0 a plain matmul with K0_d = Ws0 * Wd0[d], b0_d = bs0 + bd0[d], so the same split
+// holds on the normalised rows with the effective dense block k_star_prep (train = 0) wrote: the affine is applied where
+// a row is staged, with the tower gather's separately rounded multiply and add, and everything behind is unchanged.
 //
 // Determinism: every contraction has ONE reduction order per output element -- k ascending inside the MFMA chains, fixed
 // shuffle trees elsewhere -- and no operand depends on where a pair sits in the grid: a pair's logit is the same bits in a
@@ -63,11 +69,23 @@ __global__ __launch_bounds__(REC_THREADS) void k_rec_item_proj(const RecArgs a) 
     __shared__ float xs[IP_ROWS * XS_LD];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int r0 = blockIdx.x * IP_ROWS;
+    // Star: the item columns' affine of PartitionedNorm; a thread stages one column quad (tid & 31) of every row it touches
+    f32x4 sc = (f32x4){1.f, 1.f, 1.f, 1.f}, sh = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (a.pn) {
+        sc = *reinterpret_cast<const f32x4*>(a.pn + EMB + 4 * (tid & 31));
+        sh = *reinterpret_cast<const f32x4*>(a.pn + XDIM + EMB + 4 * (tid & 31));
+    }
 #pragma unroll
     for (int t = 0; t < IP_ROWS * (EMB / 4) / REC_THREADS; ++t) {
         const int e = tid + REC_THREADS * t, r = e >> 5, c4 = e & 31, pos = r0 + r;
         f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (pos < a.n_chunk) v = *reinterpret_cast<const f32x4*>(a.item_tab + (size_t)rec_cand_id(a, pos) * EMB + 4 * c4);
+        if (pos < a.n_chunk) {
+            v = *reinterpret_cast<const f32x4*>(a.item_tab + (size_t)rec_cand_id(a, pos) * EMB + 4 * c4);
+            if (a.pn) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = __fadd_rn(__fmul_rn(v[k], sc[k]), sh[k]);
+            }
+        }
         *reinterpret_cast<f32x4*>(xs + r * XS_LD + 4 * c4) = v;
     }
     if (a.mode != 0 && tid < IP_ROWS && r0 + tid < a.n_chunk)
@@ -100,13 +118,19 @@ __global__ __launch_bounds__(REC_THREADS) void k_rec_item_proj(const RecArgs a) 
 }
 
 // ---- q0[q, 0:256] = U[uid] . W0[0:128] + Dm[dom] . W0[256:384] + b0, one workgroup per query, thread n owns column n (one
-// fma chain, k ascending); deepfm: u + d and u . d; wdl / deepfm: lin_user[uid] + lin_domain[dom]
+// fma chain, k ascending); deepfm: u + d and u . d; wdl / deepfm: lin_user[uid] + lin_domain[dom].  Star: the user row takes
+// PartitionedNorm's affine of columns [0, 128) and the domain part is the normalised domain row k_star_prep left behind
 __global__ __launch_bounds__(REC_THREADS) void k_rec_query_proj(const RecArgs a) {
     __shared__ float us[EMB], ds[EMB], red[2];
     const int tid = threadIdx.x, q = blockIdx.x;
-    const int uid = clampi(a.uid[q], 0, a.n_user - 1), dom = clampi(a.dom[q], 0, a.n_domain - 1);
-    if (tid < EMB) us[tid] = a.user_tab[(size_t)uid * EMB + tid];
-    else ds[tid - EMB] = a.dense[a.L.dm + dom * EMB + tid - EMB];
+    const int uid = clampi(a.uid[q], 0, a.n_user - 1), dom = clampi(a.dom_all >= 0 ? a.dom_all : a.dom[q], 0, a.n_domain - 1);
+    if (tid < EMB) {
+        float x = a.user_tab[(size_t)uid * EMB + tid];
+        if (a.pn) x = __fadd_rn(__fmul_rn(x, a.pn[tid]), a.pn[XDIM + tid]);
+        us[tid] = x;
+    } else {
+        ds[tid - EMB] = a.pn ? a.pn[PN_XDOM_OFF + tid - EMB] : a.dense[a.L.dm + dom * EMB + tid - EMB];
+    }
     __syncthreads();
     const float* __restrict__ W0 = a.dense + a.L.w0;
     float acc = 0.f;

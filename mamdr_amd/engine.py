@@ -661,8 +661,24 @@ class TowerEngine(DeviceEngine):
         a query with fewer than k candidates left ends in id -1 / score 0; all_scores holds 0 for an excluded pair."""
         uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
         dom = np.array(np.broadcast_to(np.asarray(domains), uid.shape), np.int32)          # (a writable copy)
+        if uid.size and (dom.min() < 0 or dom.max() >= self.n_domain):
+            raise ValueError("recommend: user or domain id out of range")
+        return self._recommend(uid, dom, None, k, candidates, exclude, want_scores)
+
+    def recommend_domain(self, uids, domain, k, candidates=None, exclude=None, want_scores=False):
+        """`recommend` with every query in the one domain `domain` (mamdr_recommend_domain: mlp / wdl / deepfm, whose
+        results are `recommend`'s with a constant domain vector, byte for byte, and star, which retrieves through this call
+        only: its item term depends on the domain).  Same arguments otherwise, same return contract."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
+            raise ValueError("recommend_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
+        return self._recommend(uid, None, int(domain), k, candidates, exclude, want_scores)
+
+    def _recommend(self, uid, dom, domain, k, candidates, exclude, want_scores):
+        """the marshalling of both retrieval calls: dom [Q] int32 per query (mamdr_recommend) or None and the host integer
+        `domain` (mamdr_recommend_domain).  Every range check runs before the launch."""
         nq = int(uid.shape[0])
-        if nq and (uid.min() < 0 or uid.max() >= self.n_user or dom.min() < 0 or dom.max() >= self.n_domain):
+        if nq and (uid.min() < 0 or uid.max() >= self.n_user):
             raise ValueError("recommend: user or domain id out of range")
         cand = None
         n_cand = self.n_item
@@ -685,8 +701,11 @@ class TowerEngine(DeviceEngine):
         out_ids = torch.empty((max(nq, 1), kk), dtype=torch.int32, device=self.device)
         out_scores = torch.empty((max(nq, 1), kk), dtype=torch.float32, device=self.device)
         all_scores = torch.empty((max(nq, 1), max(n_cand, 1)), dtype=torch.float32, device=self.device) if want_scores else None
-        L.check(self.lib.mamdr_recommend(self.ctx, nq, _ptr(d_uid), _ptr(d_dom), _ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids),
-                                         int(k), _ptr(out_ids), _ptr(out_scores), _ptr(all_scores)))
+        tail = (_ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids), int(k), _ptr(out_ids), _ptr(out_scores), _ptr(all_scores))
+        if domain is None:
+            L.check(self.lib.mamdr_recommend(self.ctx, nq, _ptr(d_uid), _ptr(d_dom), *tail))
+        else:
+            L.check(self.lib.mamdr_recommend_domain(self.ctx, domain, nq, _ptr(d_uid), *tail))
         res = (out_ids.cpu().numpy()[:nq, :int(k)], out_scores.cpu().numpy()[:nq, :int(k)])
         return res + (all_scores.cpu().numpy()[:nq, :n_cand],) if want_scores else res
 

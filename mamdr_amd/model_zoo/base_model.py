@@ -137,8 +137,13 @@ class BaseModel(object):
                     for u, p in zip(np.asarray(c["uid"]).tolist(), np.asarray(c["pid"]).tolist()):
                         seen.setdefault(u, []).append(p)
             exclude = [seen.get(int(u), ()) for u in users]
-        ids, scores = self.model.recommend(users, np.full(users.shape, domain, np.int64), k, candidates=catalogue,
-                                           exclude=exclude)[:2]
+        # one domain per call: the engine's single-domain retrieval where it has one (the only one the Star tower has)
+        single = getattr(self.model, "recommend_domain", None)
+        if single is not None:
+            ids, scores = single(users, int(domain), k, candidates=catalogue, exclude=exclude)[:2]
+        else:
+            ids, scores = self.model.recommend(users, np.full(users.shape, domain, np.int64), k, candidates=catalogue,
+                                               exclude=exclude)[:2]
         return {"users": users, "ids": ids, "scores": scores, "catalogue": int(catalogue.shape[0])}
 
     # ------------------------------------------------------------------ finetune / separate training

@@ -1,9 +1,10 @@
 """pairs/s of mamdr_recommend beside the only way to score the same (user, item, domain) pairs without it:
 mamdr_eval_domain with d_pred_out over a bound split that holds those triples (one full 384 -> 256 -> 128 -> 64 -> 1
 forward per row).  Taobao-10-shaped synthetic data (23,778 users, 6,932 items, 10 domains), frozen tables, the mlp tower
-by default.
+by default.  --tower star: every query in domain 0 through mamdr_recommend_domain (the Star tower retrieves one domain per
+call), the eval leg over the same triples as domain 0's split.
 
-    python tools/recommend_bench.py [--tower mlp|wdl|deepfm] [--queries 512] [--k 10] [--reps 5] [--out profiles/recommend_bench.txt]
+    python tools/recommend_bench.py [--tower mlp|wdl|deepfm|star] [--queries 512] [--k 10] [--reps 5] [--out profiles/recommend_bench.txt]
 
 Method (device time): each leg runs in a child process of its own under `timeout -k 10`; inside it two warm-up calls, then
 `reps` calls between two HIP events recorded on the engine's stream; the figure is elapsed / reps.  The recommend leg's
@@ -37,7 +38,11 @@ def build(tower, batch):
     eng.bind_table("user_emb", (rs.standard_normal((n_user, 128)) * 0.1).astype(np.float32))
     eng.bind_table("item_emb", (rs.standard_normal((n_item, 128)) * 0.1).astype(np.float32))
     scale = {"domain_emb": 0.05, "W0": 0.06, "W1": 0.07, "W2": 0.1, "wo": 0.17, "gb": 0.0}
+    scale.update({"Ws0": 0.06, "Ws1": 0.07, "Ws2": 0.1})
     named = {n: (rs.standard_normal(cnt) * scale.get(n, 0.05)).astype(np.float32) for n, (off, cnt) in eng.segments.items()}
+    for n in named:             # Star: PartitionedNorm's gammas and the per-domain kernel factors around one
+        if n.startswith("pn_gamma") or n.startswith("Wd"):
+            named[n] = (1.0 + 0.2 * rs.standard_normal(named[n].shape)).astype(np.float32)
     eng.set_weights(eng.pack(named))
     return eng, n_user, n_item, n_domain
 
@@ -77,7 +82,8 @@ def leg(args):
     eng, n_user, n_item, n_domain = build(args.tower, 1024)
     rs = np.random.RandomState(3)
     uids = rs.choice(n_user, args.queries, replace=False).astype(np.int32)
-    doms = (uids % n_domain).astype(np.int32)
+    star = args.tower == "star"
+    doms = np.zeros_like(uids) if star else (uids % n_domain).astype(np.int32)
     pairs = int(args.queries) * n_item
     res = {"leg": args.leg, "tower": args.tower, "queries": int(args.queries), "items": n_item, "pairs": pairs, "k": args.k,
            "device": torch.cuda.get_device_name(eng.device), "reps": args.reps}
@@ -88,11 +94,18 @@ def leg(args):
         p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
 
         def call():
-            L.check(eng.lib.mamdr_recommend(eng.ctx, args.queries, p(d_uid), p(d_dom), None, 0, None, None, args.k, p(out_i),
-                                            p(out_s), None))
+            if star:
+                L.check(eng.lib.mamdr_recommend_domain(eng.ctx, 0, args.queries, p(d_uid), None, 0, None, None, args.k,
+                                                       p(out_i), p(out_s), None))
+            else:
+                L.check(eng.lib.mamdr_recommend(eng.ctx, args.queries, p(d_uid), p(d_dom), None, 0, None, None, args.k,
+                                                p(out_i), p(out_s), None))
         res["ms"] = timed(eng, call, args.reps)
         # both paths score the same pairs alike (8 queries)
-        _, _, dense = eng.recommend(uids[:8], doms[:8], args.k, want_scores=True)
+        if star:
+            _, _, dense = eng.recommend_domain(uids[:8], 0, args.k, want_scores=True)
+        else:
+            _, _, dense = eng.recommend(uids[:8], doms[:8], args.k, want_scores=True)
         preds, _ = eval_preds(eng, np.repeat(uids[:8], n_item), np.tile(np.arange(n_item, dtype=np.int32), 8), np.repeat(doms[:8], n_item))
         res["max_abs_diff_vs_eval"] = float(np.abs(dense.ravel() - preds).max())
     else:
@@ -105,7 +118,7 @@ def leg(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--tower", default="mlp", choices=["mlp", "wdl", "deepfm"])
+    ap.add_argument("--tower", default="mlp", choices=["mlp", "wdl", "deepfm", "star"])
     ap.add_argument("--queries", type=int, default=512)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
@@ -128,10 +141,11 @@ def main():
     r, e = got["recommend"], got["eval"]
     ratio = r["pairs_per_s"] / e["pairs_per_s"]
     text = ("%s  %s  tower %s  %d queries x %d items = %d pairs, K %d, %d reps (HIP events, 2 warm-up calls, a process per leg)\n"
-            "  mamdr_recommend                 %9.3f ms / call  %8.1f M pairs/s  (max |score - eval path's| over 8 queries: %.2e)\n"
+            "  %-30s  %9.3f ms / call  %8.1f M pairs/s  (max |score - eval path's| over 8 queries: %.2e)\n"
             "  mamdr_eval_domain + d_pred_out  %9.3f ms / call  %8.1f M pairs/s\n"
             "  recommend / eval throughput     %.2fx  (flop per pair: 82,048 / 360,576 = 0.23)\n" % (
                 time.strftime("%Y-%m-%d"), r["device"], args.tower, r["queries"], r["items"], r["pairs"], r["k"], r["reps"],
+                "mamdr_recommend_domain (d = 0)" if args.tower == "star" else "mamdr_recommend",
                 r["ms"], r["pairs_per_s"] / 1e6, r["max_abs_diff_vs_eval"], e["ms"], e["pairs_per_s"] / 1e6, ratio))
     print(text)
     with open(args.out, "a") as f:

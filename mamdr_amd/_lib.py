@@ -121,6 +121,7 @@ SIGNATURES = {
     "mamdr_shuffle_perm": (C.c_int, [_I64, _I64, _U64, _VP]),
     "mamdr_shuffle_perms": (C.c_int, [_I32, _VP, _I64, _VP, _VP]),
     "mamdr_step_path": (C.c_int, [_VP, _I32]),
+    "mamdr_fused_flags": (C.c_int, [_VP]),
     "mamdr_dropout_steps": (_I64, [_VP]),
     "mamdr_set_tower_tile": (C.c_int, [_VP, _I32]),
     "mamdr_tower_tile": (C.c_int, [_VP, _I32]),

@@ -8,8 +8,9 @@
 //                    activation columns, 8-byte loads of the 32 gradient columns) and feeds two
 //                    v_mfma_f32_16x16x4_f32 per slot; the 8 partial tiles are summed through LDS in wave order
 //                    (fixed order: bitwise reproducible); thread (m, n) then applies TF1 Adam / SGD / accumulate
-//                    to element (m, n) and keeps k_tower4's transposed W2 copy current (W1's too, unless the context
-//                    can only ever launch the W1-image towers, which do not read it).
+//                    to element (m, n) and keeps k_tower4's transposed copies of W1 and W2 current, each only where a
+//                    tower of the context can read it (the W1-image towers do not read W1T; the call's towers that
+//                    read W2 in place do not read W2T).
 //   S workgroups     32 workgroups, one per 8 columns of dz1: S = onehot(domain)^T dz1 for their columns (the
 //                    same contraction with a synthesised A operand), from which follow, by linearity (the rows
 //                    256..383 of x are the domain-embedding row of the sample's domain):
@@ -27,20 +28,18 @@
 #include <hip/hip_ext.h>
 
 #include "mamdr_kernels.h"
+#include "wgrad_adam_deal.h"
 
 namespace mamdr {
 
 constexpr int FZ_THREADS = 512;
 constexpr int FZ_WAVES = 8;
 constexpr int FZ_RING = 32;                   // slots (of 4 batch rows) in flight per wave
-constexpr int FZ_SBLK = DM_PARTS;                   // S workgroups = 8-column blocks of dz1 (the optimiser step of their
-                                              // 128 x 8 block of W0[256:384] is the long part: 2 elements per thread)
-constexpr int FZ_SC = 8;                      // columns per S workgroup
+// FZ_SBLK S workgroups (the optimiser step of their 128 x 8 block of W0[256:384] is the long part: 2 elements per
+// thread), FZ_SC columns each, and the FZ_TILES = FZ_T0 + FZ_T1 + FZ_T2 tiles: wgrad_adam_deal.h, which deals them
+static_assert(FZ_SBLK == DM_PARTS && FZ_DEAL_EMB == EMB && FZ_DEAL_H1 == H1 && FZ_DEAL_H2 == H2 && FZ_DEAL_H3 == H3,
+              "wgrad_adam_deal.h deals the tower of mamdr_device.h");
 constexpr int FZ_OUTB = 2;                    // output-unit workgroups = 32-column blocks of h3
-constexpr int FZ_T0 = (2 * EMB / 16) * (H1 / 32);     // 128 tiles of dW0[0:256, :]
-constexpr int FZ_T1 = (H1 / 16) * (H2 / 32);          // 64 tiles of dW1
-constexpr int FZ_T2 = (H2 / 16) * (H3 / 32);          // 16 tiles of dW2
-constexpr int FZ_TILES = FZ_T0 + FZ_T1 + FZ_T2;       // 208
 // the launch's own workgroups (riders sit behind them)
 __host__ __device__ constexpr int fz_own_wgs(bool with_loss) { return FZ_SBLK + FZ_TILES + FZ_OUTB + (with_loss ? 1 : 0); }
 
@@ -185,40 +184,34 @@ static int fz_lds_floats(int n_domain) {
 __device__ __forceinline__ void fz_tile_body(const FusedArgs& a, int t, float* lds) {
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, kq = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);         // wave-uniform: shares and trip counts stay scalar
-    // tile -> operands / destination.  Workgroup b runs on XCD b % 8 (round-robin dispatch; a speed assumption
-    // only), and the 8 L2s do not share data: the tiles are dealt so that XCD x = (xb, xa) only reads a quarter of
-    // the activation columns (xa) and a half of the gradient columns (xb) of every matrix -- 12.7 MB leave the
-    // infinity cache per launch at 1,024 rows instead of 24 MB with one gradient block per XCD.
-    const int x = t & 7, xa = x & 3, xb = x >> 2, li = t >> 3;      // li: 0..25 inside the XCD
+    // tile -> operands / destination (fz_tile, wgrad_adam_deal.h).  The workgroups of one residue mod 8 share an XCD
+    // (round-robin dispatch; a speed assumption only) and the 8 L2s share no data: residue (xa, xb) reads a quarter of the
+    // activation columns and a half of the gradient columns of every matrix, 12 cold 128-B lines per batch row and XCD --
+    // by this geometry 12 x 1,024 x 8 lines = 12.6 MB of operands cross the fabric per launch at 1,024 rows, instead of
+    // 24 MB with one gradient block per XCD.  (The counter of the L2s' fabric-side reads gives 126,273 requests of 128 B =
+    // 16.2 MB for EVERYTHING the launch reads, parameters and slots included: profiles/ab_wgrad_adam_s_placement.txt.)
+    const FzTile ft = fz_tile(t);
+    const int gemm = ft.gemm, ablk = ft.ablk, bblk = ft.bblk;
     const float* A;
-    int lda, b_off, dst, ldn, ablk, gemm;
-    if (li < 16) {
-        gemm = 0;
-        ablk = 4 * xa + (li & 3);
-        const int bblk = 4 * xb + (li >> 2);
+    int lda, b_off, dst, ldn;
+    if (gemm == 0) {
         A = a.xa + 16 * ablk;
         lda = a.xa_ld;
         b_off = 32 * bblk;
         ldn = H1;
         dst = a.L.w0 + 16 * ablk * H1 + 32 * bblk;
-    } else if (li < 24) {
-        gemm = 1;
-        const int u = li - 16;
-        ablk = 4 * xa + (u & 3);
-        const int bblk = 2 * xb + (u >> 2);
+    } else if (gemm == 1) {
         A = a.acts + XDIM + 16 * ablk;
         lda = ACT_LD;
         b_off = H1 + 32 * bblk;
         ldn = H2;
         dst = a.L.w1 + 16 * ablk * H2 + 32 * bblk;
     } else {
-        gemm = 2;
-        ablk = 2 * xa + (li - 24);
         A = a.acts + XDIM + H1 + 16 * ablk;
         lda = ACT_LD;
-        b_off = H1 + H2 + 32 * xb;
+        b_off = H1 + H2 + 32 * bblk;
         ldn = H3;
-        dst = a.L.w2 + 16 * ablk * H3 + 32 * xb;
+        dst = a.L.w2 + 16 * ablk * H3 + 32 * bblk;
     }
     // this thread's parameter and slots: requested before the contraction
     const int em = tid >> 5, en = tid & 31;
@@ -264,11 +257,11 @@ __device__ __forceinline__ void fz_tile_body(const FusedArgs& a, int t, float* l
     float p = p0, m = m0, v = v0;
     opt_step(a, g, p, m, v);
     fz_store(a, e, p, m, v);
-    if (a.wT && a.optimizer != 2) {          // k_tower4's transposed copies of W2 and, where a tower can read it, W1
-        if (gemm == 2) {
+    if (a.wT && a.optimizer != 2) {          // k_tower4's transposed copies of W2 and W1, each where a tower can read it
+        if (gemm == 2 && !(a.flags & FZ_F_W2T_UNREAD)) {
             const int row = (e - a.L.w2) / H3, col = (e - a.L.w2) - row * H3;
             a.wT[W2T_OFF + col * H2 + row] = p;
-        } else if (gemm == 1 && !a.w1t_unread) {
+        } else if (gemm == 1 && !(a.flags & FZ_F_W1T_UNREAD)) {
             const int row = (e - a.L.w1) / H2, col = (e - a.L.w1) - row * H2;
             a.wT[W1T_OFF + col * H1 + row] = p;
         }
@@ -628,14 +621,18 @@ __device__ __forceinline__ void fz_ride_body(const FusedArgs& a, int r, float* l
     FZSTAMP(4);
 }
 
-// grid: [0, 32) S workgroups (the longest chains first), [32, 240) tiles, 240 / 241 output unit, 242 loss (optional),
-// then the riders (optional)
+// grid: [0, 32) S workgroups (the longest chains first; workgroup b takes the column block fz_s_block(b) of dz1, one that
+// lies in the dz1 lines the tiles of its residue b & 7 -- its XCD -- read anyway: under blk = b half of them were the
+// only readers of 1,024 lines on their XCD, +17 % cold lines for every XCD), [32, 240) tiles (tile t has the residue of
+// its workgroup 32 + t: fz_tile), 240 / 241 output unit, 242 loss (optional), then the riders (optional).
+// Which workgroup computes which block is all the dealing decides: every value and summation order is a function of the
+// block.
 __global__ __launch_bounds__(FZ_THREADS) void k_wgrad_adam(const FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = (int)blockIdx.x;
     FZSTAMP(0);
     FZREAL(5);
-    if (b < FZ_SBLK) fz_s_body(a, b, lds);
+    if (b < FZ_SBLK) fz_s_body(a, fz_s_block(b, (a.flags & FZ_F_S_INORDER) != 0), lds);
     else if (b < FZ_SBLK + FZ_TILES) fz_tile_body(a, b - FZ_SBLK, lds);
     else if (b < FZ_SBLK + FZ_TILES + FZ_OUTB) fz_out_body(a, b - FZ_SBLK - FZ_TILES, lds);
     else if (b < fz_own_wgs(a.loss_out != nullptr)) fz_loss_body(a, lds);

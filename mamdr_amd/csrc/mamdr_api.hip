@@ -161,6 +161,12 @@ struct mamdr_ctx {
     // W1 image): k_wgrad_adam skips those 128 KB of strided stores per step.  A function of the context's configuration;
     // mamdr_set_tower_tile, which can change it, drops wT_valid
     bool w1t_unread = false;
+    // ... and W2T in a context every training call of which runs pre-gathered on the k_wgrad_adam path with the W1 image
+    // (w2t_unread_now): every tower then reads W2 in place (k_tower4<.., W2D>), k_wgrad_adam skips those 32 KB of
+    // strided stores per step, and the copies are never built or called current (MAMDR_NO_W2_DIRECT=1: built and kept)
+    bool w2t_unread = false;
+    int fused_flags = -1;           // FZ_F_* of the latest k_wgrad_adam launch (mamdr_fused_flags)
+    bool fz_s_inorder = false;      // MAMDR_FZ_S_INORDER=1: k_wgrad_adam's S workgroups take their column blocks in grid order
     bool w2_direct_ok = true;       // MAMDR_NO_W2_DIRECT=1: always build the copies at the start of a call (k_transpose_w)
     bool dm_finish_each = false;    // MAMDR_DM_EACH=1: materialise after every step (k_dm_finish per step; A/B measurements)
     int tower_tile = 0;             // 0 auto, 4 / 16 forced (env MAMDR_TOWER_TILE)
@@ -559,6 +565,11 @@ static bool w1t_unread_now(const mamdr_ctx* c) {
     const int64_t max4 = c->tower_tile == 4 ? c->rows_pad_max : std::min<int64_t>(c->tower4_max_rows, c->rows_pad_max);
     return tower4_never_streams(max4, c->t4_no_w1l);
 }
+// ... and every training call takes the k_wgrad_adam path over a pre-gathered pass, so that each of those launches can
+// be the instance that reads W2 in place: no batch the context accepts goes to the slab path (whose towers read W2T)
+static bool w2t_unread_now(const mamdr_ctx* c) {
+    return w1t_unread_now(c) && c->w2_direct_ok && c->use_pre && takes_fused_path(c, c->rows_pad_max);
+}
 // row groups of k_wgrad (= gradient slabs) of a step and the rows of each (measured: 1024 rows, 8 groups of 128: 31.0 us /
 // step vs 32.0 with 4 of 256; batches of <= 512 rows keep 256-row groups: one or two slabs)
 static int wgrad_groups(int rows_pad, int* rpg) {
@@ -608,6 +619,7 @@ struct CallPlan {
     bool need_wT = false;       // a step of the call runs k_tower4, which reads the transposed W1 / W2 copies
     bool build_wT = false;      // ... which are built at the start of the call
     bool w2_direct = false;     // ... or not: the call's first tower reads W2 in place
+    bool w2_all = false;        // ... as every tower of the call does (w2t_unread_now): the W2 copy is left alone
     bool star_lazy = false;     // Star: the other domains' slices are replayed by k_star_catchup, not stepped every step
 };
 
@@ -635,6 +647,13 @@ static void plan_call(mamdr_ctx* c, CallPlan& P) {
         tower4_takes_w1l(first_rows, c->t4_no_w1l)) {
         P.build_wT = false;
         P.w2_direct = true;
+    }
+    // ... and in a context all of whose towers are W1-image instances over pre-gathered rows (w2t_unread_now) EVERY tower
+    // of the call reads W2 in place, whether the copies are current or not and in accumulate calls too: nothing is built,
+    // k_wgrad_adam leaves W2T alone as it does W1T, and the call leaves the copies stale (wT_valid, mamdr_train_steps_n)
+    if (P.need_wT && P.pre && c->w2t_unread) {
+        P.build_wT = false;
+        P.w2_direct = P.w2_all = true;
     }
     // ... and a call whose FIRST step runs the 16-row tower (which reads no copy) needs none built either: k_update
     // rewrites the copy of every element it steps, so they are current from the call's second step on -- before the
@@ -1004,7 +1023,7 @@ static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
     ta.dm_live_m = dense_m + c->L.dm;
     ta.dm_live_v = c->adam_v + c->table_floats + c->L.dm;
     ta.dm_snap_out = c->dmsnap[c->dm_cur];
-    ta.w2_direct = (P.w2_direct && s == 0) ? 1 : 0;
+    ta.w2_direct = (P.w2_direct && (s == 0 || P.w2_all) && use4) ? 1 : 0;
     if (int rc = run_step_tower(c, ta, use4, s)) return rc;
     FusedArgs fa;
     memset(&fa, 0, sizeof(fa));
@@ -1024,7 +1043,8 @@ static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
     fa.dm_snap = c->dmsnap[c->dm_cur];         // p plane: the domain table as this step's forward pass saw it
     fa.pdm = c->pdm;
     fa.wT = (P.need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
-    fa.w1t_unread = c->w1t_unread ? 1 : 0;
+    fa.flags = (c->w1t_unread ? FZ_F_W1T_UNREAD : 0) | (P.w2_all ? FZ_F_W2T_UNREAD : 0) | (c->fz_s_inorder ? FZ_F_S_INORDER : 0);
+    c->fused_flags = fa.flags;
     fa.optimizer = optimizer;
     fa.alpha = alpha;
     fa.omb1 = P.omb1;
@@ -1416,8 +1436,10 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
             if (const char* de = getenv("MAMDR_NO_W2_DIRECT")) c->w2_direct_ok = atoi(de) == 0;
             if (const char* pe = getenv("MAMDR_NO_PREGATHER")) c->use_pre = atoi(pe) == 0;
             if (const char* pe = getenv("MAMDR_NO_PREGATHER_RIDE")) c->ride_on = atoi(pe) == 0;
+            if (const char* se = getenv("MAMDR_FZ_S_INORDER")) c->fz_s_inorder = atoi(se) != 0;
         }
         c->w1t_unread = w1t_unread_now(c);
+        c->w2t_unread = w2t_unread_now(c);
     }
     if (const char* ev = getenv("MAMDR_NO_TAILFUSE")) c->tail_fuse = atoi(ev) == 0;
     if (const char* ev = getenv("MAMDR_REC_CHUNK"))
@@ -1915,7 +1937,8 @@ int mamdr_train_steps_n(mamdr_ctx* c, int domain, const int32_t* d_perm, int64_t
     }
     // (what the call's steps leave behind: k_wgrad_adam / k_update keep the copies of what they step current when the
     // call uses them; steps without them make them stale; accumulate steps change no weight)
-    if (optimizer != MAMDR_OPT_ACCUMULATE) c->wT_valid = P.need_wT;
+    if (P.w2_all) c->wT_valid = false;         // (W2T is not kept: a later call that reads it builds it)
+    else if (optimizer != MAMDR_OPT_ACCUMULATE) c->wT_valid = P.need_wT;
     else if (P.build_wT) c->wT_valid = true;
     for (int64_t s = 0; s < n_steps; ++s) {
         // the reported loss carries l2 * sum(table^2) over EVERY row: bring lagging rows up to date first
@@ -2413,6 +2436,7 @@ int mamdr_debug_set_stamps(mamdr_ctx* c, unsigned long long* d_stamps) {
 int64_t mamdr_dropout_steps(const mamdr_ctx* c) { return c ? (int64_t)c->global_step : 0; }
 
 int mamdr_step_path(const mamdr_ctx* c, int32_t batch) { return c && takes_fused_path(c, batch) ? 1 : 0; }
+int mamdr_fused_flags(const mamdr_ctx* c) { return c ? c->fused_flags : -1; }
 
 int mamdr_set_tower_tile(mamdr_ctx* c, int32_t rows) {
     if (check_ctx(c)) return MAMDR_EINVAL;
@@ -2422,7 +2446,8 @@ int mamdr_set_tower_tile(mamdr_ctx* c, int32_t rows) {
         c->tower_tile = rows;
         drop_pregathered(c);    // (passes gathered ahead were laid out for the step path of the old choice)
         c->w1t_unread = w1t_unread_now(c);
-        c->wT_valid = false;    // (W1T may have been left alone under the old choice)
+        c->w2t_unread = w2t_unread_now(c);
+        c->wT_valid = false;    // (W1T / W2T may have been left alone under the old choice)
     }
     return MAMDR_OK;
 }

@@ -156,7 +156,8 @@ struct TowerArgs {
     const int32_t* pdom;
     const float* plabel;
     int no_w1l;                // k_tower4: keep streaming W1 / W1^T (MAMDR_T4_NO_W1L=1, diagnostic)
-    int w2_direct;             // k_tower4<.., W1L, PRE>: the backward pass reads W2 itself instead of the copy W2T (the first
+    int w2_direct;             // k_tower4<.., W1L, PRE>: the backward pass reads W2 itself instead of the copy W2T (every
+                               // tower of a call where all of them can -- CallPlan::w2_all -- otherwise the first
                                // step of a call whose copies are stale)
     DmStep dms;
     int dm_hint;               // the domain the caller expects every row of the batch to carry (the pass's domain)
@@ -481,6 +482,9 @@ struct RideArgs {
     } seg[2];
 };
 // k_wgrad_adam (fused_kernels.hip): weight gradients + optimiser step of the dense block in one launch
+constexpr int FZ_F_W1T_UNREAD = 1;     // no tower launch of this context reads W1T (tower4_never_streams): W1T is left alone
+constexpr int FZ_F_W2T_UNREAD = 2;     // every tower of this call reads W2 in place (k_tower4<.., W2D>): W2T is left alone too
+constexpr int FZ_F_S_INORDER = 4;      // MAMDR_FZ_S_INORDER=1: S workgroup b takes column block b (A/B switch; same bits)
 struct FusedArgs {
     const float* acts;         // [rows_pad][ACT_LD]
     const float* dz;           // [rows_pad][DZ_LD]
@@ -497,7 +501,8 @@ struct FusedArgs {
     const float* dm_snap;      // pre-update domain table (the tower's dm_snap_out)
     float* pdm;                // [8][n_domain][EMB] partial domain-table gradients
     float* wT;                 // nullable: k_tower4's transposed W1 / W2 copies
-    int w1t_unread;            // no tower launch of this context reads W1T (tower4_never_streams): only W2T is kept current
+    int flags;                 // FZ_F_* below (ONE word next to wT: the kernel fetches both with its first argument loads;
+                               // as words of their own the compiler fetched them where they are used, behind the barrier)
     int optimizer;             // 0 adam, 1 sgd, 2 accumulate
     float alpha, omb1, omb2, eps, two_l2;
     const float* loss_part;    // loss of the step (optional)

@@ -25,7 +25,8 @@ perm = torch.from_numpy(engine.shuffle_perm(n, 10000, 1)).to(eng.device)
 for _ in range(5):
     eng.train_steps(d, perm=perm, first_step=0, n_steps=3)
 torch.cuda.synchronize()
-ws = stamps.cpu().numpy()[65536:65536 + 8 * 242].reshape(242, 8)[:, :5].astype(np.float64)
+raw = stamps.cpu().numpy()[65536:65536 + 8 * 242].reshape(242, 8).astype(np.float64)
+ws = raw[:, :5]
 t0 = ws[:, 0].min()
 print("k_wgrad_adam stamps (cycles relative to the first workgroup's start): start | contraction begins | ends | barrier passed | done")
 for name, sl in (("S workgroups", slice(0, 32)), ("tiles", slice(32, 240)), ("output unit", slice(240, 242))):
@@ -34,3 +35,18 @@ for name, sl in (("S workgroups", slice(0, 32)), ("tiles", slice(32, 240)), ("ou
         name, len(w), np.round(np.median(w, axis=0)).astype(int).tolist(), np.round(w.max(axis=0)).astype(int).tolist(),
         np.median(ws[sl][:, 4] - ws[sl][:, 0]), (ws[sl][:, 4] - ws[sl][:, 0]).max()))
 print("  (phases: prologue | contraction | wait at the barrier | reduce + optimiser step)")
+# The S workgroups in two classes: workgroup b's column block under blk = b lies in the half of dz1 that the tiles of its
+# residue b & 7 (its XCD) read -- b >> 4 == (b & 7) >> 2 -- or in the other half, where b is its XCD's only reader of those
+# lines.  (The classes are sets of workgroups: under the XCD-aware dealing, the default, every block is in the right half.)
+# Lifetimes in the CU's own cycles; ends on the device-wide 100 MHz clock, relative to the launch's first workgroup.
+b_ = np.arange(32)
+home = (b_ >> 4) == ((b_ & 7) >> 2)
+r0 = raw[:, 5].min()
+print("placement (MAMDR_FZ_S_INORDER=%s): lifetime cycles median / max | end on the device-wide clock, 10 ns, median / max" %
+      os.environ.get("MAMDR_FZ_S_INORDER", "0"))
+for name, idx in (("S, block b on the reading XCD", b_[home]), ("S, block b on another XCD", b_[~home]), ("tiles", np.arange(32, 240))):
+    life = raw[idx, 4] - raw[idx, 0]
+    end = raw[idx, 6] - r0
+    print("  %-30s n=%3d  lifetime %6d / %6d | end %4d / %4d" % (name, len(idx), np.median(life), life.max(), np.median(end), end.max()))
+late = np.argsort(raw[:32, 6])[::-1][:8]
+print("  the 8 S workgroups that end last: %s" % ", ".join("b=%d%s" % (b, "" if home[b] else "*") for b in late), "(*: block b on another XCD)")

@@ -445,7 +445,9 @@ int64_t mamdr_pregather_remainder_rows(const mamdr_ctx* ctx);
 int mamdr_step_path(const mamdr_ctx* ctx, int32_t batch);
 /* how the context's latest k_wgrad_adam launch ran (for reports and tests; -1: none yet): bit 0 = it left W1^T alone (no
  * tower of the context reads it), bit 1 = it left W2^T alone (every tower of its call read W2 in place: no transposed copy
- * was built either), bit 2 = its S workgroups took their column blocks in grid order (MAMDR_FZ_S_INORDER=1) */
+ * was built either), bit 2 = its S workgroups took their column blocks in grid order (MAMDR_FZ_S_INORDER=1), bit 3 = its
+ * workgroups were dealt their blocks by residue, every XCD the same mix, instead of by matrix (MAMDR_FZ_DEAL_RESIDUE=1, and
+ * implied by bit 2) */
 int mamdr_fused_flags(const mamdr_ctx* ctx);
 /* rows per tower workgroup from the next call on: 0 = the library's choice (4-row tiles while the grid fits the CUs in one
  * round: ONE chain of steps then has every CU busy), 4 or 16 forced.  16 is the choice of a context that SHARES the

@@ -30,6 +30,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_NO_W2_DIRECT", "lib", "1: k_transpose_w opens a call instead of the W2-in-place tower instance"},
     {"MAMDR_NO_PREGATHER", "lib,bench", "1: no k_pass_prep; the tower gathers its rows itself"},
     {"MAMDR_NO_PREGATHER_RIDE", "lib", "1: no rider workgroups in k_wgrad_adam; every pass window is gathered by k_pass_prep_multi (same bits)"},
+    {"MAMDR_FZ_DEAL_RESIDUE", "lib", "1: k_wgrad_adam deals every XCD the same mix of S blocks and tiles of all three matrices instead of one rectangle of one matrix (A/B switch; same bits)"},
     {"MAMDR_FZ_S_INORDER", "lib", "1: S workgroup b of k_wgrad_adam takes column block b of dz1 instead of one its XCD's tiles read (A/B switch; same bits)"},
     {"MAMDR_STAR_DENSE_SLICES", "lib", "1: every per-domain Star slice swept every step (diagnostic; same bits)"},
     {"MAMDR_REC_CHUNK", "lib,tests", "candidates per pass of mamdr_recommend's phases (default 16384; rounded up to 64; tests: several chunks at tiny sizes; same bits)"},

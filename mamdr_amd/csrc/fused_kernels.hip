@@ -39,9 +39,11 @@ constexpr int FZ_RING = 32;                   // slots (of 4 batch rows) in flig
 // thread), FZ_SC columns each, and the FZ_TILES = FZ_T0 + FZ_T1 + FZ_T2 tiles: wgrad_adam_deal.h, which deals them
 static_assert(FZ_SBLK == DM_PARTS && FZ_DEAL_EMB == EMB && FZ_DEAL_H1 == H1 && FZ_DEAL_H2 == H2 && FZ_DEAL_H3 == H3,
               "wgrad_adam_deal.h deals the tower of mamdr_device.h");
-constexpr int FZ_OUTB = 2;                    // output-unit workgroups = 32-column blocks of h3
-// the launch's own workgroups (riders sit behind them)
-__host__ __device__ constexpr int fz_own_wgs(bool with_loss) { return FZ_SBLK + FZ_TILES + FZ_OUTB + (with_loss ? 1 : 0); }
+// the launch's own workgroups (riders sit behind them): the FZ_OWN dealt ones (FZ_OUTB output-unit workgroups last) + the loss
+static_assert(FZ_OUTB == 2 && FZ_OWN == FZ_SBLK + FZ_TILES + FZ_OUTB, "two output-unit workgroups of 32 columns of h3");
+__host__ __device__ constexpr int fz_own_wgs(bool with_loss) { return FZ_OWN + (with_loss ? 1 : 0); }
+// both dealings (wgrad_adam_deal.h) in constant memory: one 8-byte scalar load, indexed by the workgroup id alone
+__constant__ const FzDealTable c_fz_deal = fz_deal_table_make();
 
 // cycle / device-wide counter stamps of wave 0 (diagnostic build only, tools/stamp_fused.py)
 #define FZSTAMP(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 8 + (k)])
@@ -181,16 +183,15 @@ static int fz_lds_floats(int n_domain) {
     return s > FZ_LDS_TILE ? s : FZ_LDS_TILE;
 }
 
-__device__ __forceinline__ void fz_tile_body(const FusedArgs& a, int t, float* lds) {
+__device__ __forceinline__ void fz_tile_body(const FusedArgs& a, const FzTile ft, float* lds) {
     const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, kq = lane >> 4;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);         // wave-uniform: shares and trip counts stay scalar
-    // tile -> operands / destination (fz_tile, wgrad_adam_deal.h).  The workgroups of one residue mod 8 share an XCD
-    // (round-robin dispatch; a speed assumption only) and the 8 L2s share no data: residue (xa, xb) reads a quarter of the
-    // activation columns and a half of the gradient columns of every matrix, 12 cold 128-B lines per batch row and XCD --
-    // by this geometry 12 x 1,024 x 8 lines = 12.6 MB of operands cross the fabric per launch at 1,024 rows, instead of
-    // 24 MB with one gradient block per XCD.  (The counter of the L2s' fabric-side reads gives 126,273 requests of 128 B =
-    // 16.2 MB for EVERYTHING the launch reads, parameters and slots included: profiles/ab_wgrad_adam_s_placement.txt.)
-    const FzTile ft = fz_tile(t);
+    // tile -> operands / destination (the dealing: wgrad_adam_deal.h).  The workgroups of one residue mod 8 share an XCD
+    // (round-robin dispatch; a speed assumption only) and the 8 L2s share no data: dealt by matrix, a residue's tiles form
+    // one rectangle of one weight matrix and read 7 - 10 cold 128-B lines per batch row, 69 over the chip = 9.0 MB of
+    // operands across the fabric per launch at 1,024 rows (the residue dealing: 12 - 13 lines, 98 = 12.8 MB; one gradient
+    // block per XCD: 24 MB).  (The counters of the L2s' fabric-side reads, which hold EVERYTHING the launch reads,
+    // parameters and slots included: profiles/ab_wgrad_adam_xcd_lines.txt.)
     const int gemm = ft.gemm, ablk = ft.ablk, bblk = ft.bblk;
     const float* A;
     int lda, b_off, dst, ldn;
@@ -621,20 +622,24 @@ __device__ __forceinline__ void fz_ride_body(const FusedArgs& a, int r, float* l
     FZSTAMP(4);
 }
 
-// grid: [0, 32) S workgroups (the longest chains first; workgroup b takes the column block fz_s_block(b) of dz1, one that
-// lies in the dz1 lines the tiles of its residue b & 7 -- its XCD -- read anyway: under blk = b half of them were the
-// only readers of 1,024 lines on their XCD, +17 % cold lines for every XCD), [32, 240) tiles (tile t has the residue of
-// its workgroup 32 + t: fz_tile), 240 / 241 output unit, 242 loss (optional), then the riders (optional).
-// Which workgroup computes which block is all the dealing decides: every value and summation order is a function of the
-// block.
+// grid: [0, FZ_OWN) the dealt workgroups -- 32 S workgroups, 208 tiles, 2 output-unit workgroups --, 242 loss (optional),
+// then the riders (optional).  Which of the dealt workgroups computes which block is all the dealing decides
+// (wgrad_adam_deal.h): every value and summation order is a function of the block.  By default the table of the dealing by
+// matrix says it, under FZ_F_DEAL_RESIDUE the residue dealing ([0, 32) S workgroups, workgroup b taking the column block
+// fz_s_block(b) of dz1; [32, 240) tiles, tile t with the residue of its workgroup 32 + t: fz_tile; 240 / 241 output unit).
+// Both roles are one entry of a table in constant memory, requested first, with the argument loads: the index is the
+// workgroup id, and the flag word selects between two registers.
 __global__ __launch_bounds__(FZ_THREADS) void k_wgrad_adam(const FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = (int)blockIdx.x;
+    const int2 dealt = *reinterpret_cast<const int2*>(c_fz_deal.code[min(b, FZ_OWN - 1)]);
     FZSTAMP(0);
     FZREAL(5);
-    if (b < FZ_SBLK) fz_s_body(a, fz_s_block(b, (a.flags & FZ_F_S_INORDER) != 0), lds);
-    else if (b < FZ_SBLK + FZ_TILES) fz_tile_body(a, b - FZ_SBLK, lds);
-    else if (b < FZ_SBLK + FZ_TILES + FZ_OUTB) fz_out_body(a, b - FZ_SBLK - FZ_TILES, lds);
+    const int code = (a.flags & FZ_F_DEAL_RESIDUE) ? dealt.y : dealt.x;
+    const int role = b < FZ_OWN ? fz_code_role(code) : -1;
+    if (role == FZ_ROLE_S) fz_s_body(a, (a.flags & FZ_F_S_INORDER) ? b : fz_code_x(code), lds);
+    else if (role >= 0 && role < 3) fz_tile_body(a, FzTile{role, fz_code_x(code), fz_code_y(code)}, lds);
+    else if (role == FZ_ROLE_OUT) fz_out_body(a, fz_code_x(code), lds);
     else if (b < fz_own_wgs(a.loss_out != nullptr)) fz_loss_body(a, lds);
     else fz_ride_body(a, b - fz_own_wgs(a.loss_out != nullptr), lds);
     FZREAL(6);

@@ -167,6 +167,7 @@ struct mamdr_ctx {
     bool w2t_unread = false;
     int fused_flags = -1;           // FZ_F_* of the latest k_wgrad_adam launch (mamdr_fused_flags)
     bool fz_s_inorder = false;      // MAMDR_FZ_S_INORDER=1: k_wgrad_adam's S workgroups take their column blocks in grid order
+    bool fz_deal_residue = false;   // MAMDR_FZ_DEAL_RESIDUE=1 (implied by the switch above): the residue dealing, not the one by matrix
     bool w2_direct_ok = true;       // MAMDR_NO_W2_DIRECT=1: always build the copies at the start of a call (k_transpose_w)
     bool dm_finish_each = false;    // MAMDR_DM_EACH=1: materialise after every step (k_dm_finish per step; A/B measurements)
     int tower_tile = 0;             // 0 auto, 4 / 16 forced (env MAMDR_TOWER_TILE)
@@ -1043,7 +1044,8 @@ static int fused_step(mamdr_ctx* c, const CallPlan& P, int64_t s, float alpha) {
     fa.dm_snap = c->dmsnap[c->dm_cur];         // p plane: the domain table as this step's forward pass saw it
     fa.pdm = c->pdm;
     fa.wT = (P.need_wT && optimizer != MAMDR_OPT_ACCUMULATE) ? c->wT : nullptr;
-    fa.flags = (c->w1t_unread ? FZ_F_W1T_UNREAD : 0) | (P.w2_all ? FZ_F_W2T_UNREAD : 0) | (c->fz_s_inorder ? FZ_F_S_INORDER : 0);
+    fa.flags = (c->w1t_unread ? FZ_F_W1T_UNREAD : 0) | (P.w2_all ? FZ_F_W2T_UNREAD : 0) | (c->fz_s_inorder ? FZ_F_S_INORDER : 0) |
+               (c->fz_deal_residue || c->fz_s_inorder ? FZ_F_DEAL_RESIDUE : 0);
     c->fused_flags = fa.flags;
     fa.optimizer = optimizer;
     fa.alpha = alpha;
@@ -1437,6 +1439,7 @@ int mamdr_create(const mamdr_config* cfg, void* stream, mamdr_ctx** out) {
             if (const char* pe = getenv("MAMDR_NO_PREGATHER")) c->use_pre = atoi(pe) == 0;
             if (const char* pe = getenv("MAMDR_NO_PREGATHER_RIDE")) c->ride_on = atoi(pe) == 0;
             if (const char* se = getenv("MAMDR_FZ_S_INORDER")) c->fz_s_inorder = atoi(se) != 0;
+            if (const char* se = getenv("MAMDR_FZ_DEAL_RESIDUE")) c->fz_deal_residue = atoi(se) != 0;
         }
         c->w1t_unread = w1t_unread_now(c);
         c->w2t_unread = w2t_unread_now(c);

@@ -485,6 +485,8 @@ struct RideArgs {
 constexpr int FZ_F_W1T_UNREAD = 1;     // no tower launch of this context reads W1T (tower4_never_streams): W1T is left alone
 constexpr int FZ_F_W2T_UNREAD = 2;     // every tower of this call reads W2 in place (k_tower4<.., W2D>): W2T is left alone too
 constexpr int FZ_F_S_INORDER = 4;      // MAMDR_FZ_S_INORDER=1: S workgroup b takes column block b (A/B switch; same bits)
+constexpr int FZ_F_DEAL_RESIDUE = 8;   // MAMDR_FZ_DEAL_RESIDUE=1 (or FZ_F_S_INORDER): the residue dealing of wgrad_adam_deal.h instead of
+                                       // the dealing by matrix (A/B switch; same bits)
 struct FusedArgs {
     const float* acts;         // [rows_pad][ACT_LD]
     const float* dz;           // [rows_pad][DZ_LD]

@@ -2,10 +2,14 @@
 
 Used by __graft_entry__.build().  The shared library lands next to this file
 (mamdr_amd/libmamdr_hip.so): git-ignored, but it travels to the GPU box.
+
+Diagnostic variants (extra -D flags on every compile) come from the same SOURCES and COMMON:
+python -m mamdr_amd.build --variant <name> <flags...>, which tools/build_variant.sh wraps.
 """
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -28,9 +32,14 @@ SOURCES = [
     # gauc_kernels: the fp64 terms are a division, a multiplication and additions as the host definition computes them
     # -> no fma fusion; its register / LDS / scratch report: profiles/gauc_bench.txt
     ("gauc_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
+    # host code only: the step engine's C ABI (map: csrc/step_ctx.h)
     ("mamdr_api.hip", []),
+    ("step_context.hip", []),
+    ("step_queries.hip", []),
+    ("step_stateless.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]
+JOBS = 16       # compiles at a time, at most
 
 
 def _hipcc():
@@ -47,33 +56,57 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=True):
-    os.makedirs(BUILD, exist_ok=True)
+def build(force=False, verbose=True, out=OUT, build_dir=BUILD, extra_flags=()):
+    """Compile SOURCES with COMMON (+ each file's own flags + extra_flags) into build_dir and link them into `out`."""
+    os.makedirs(build_dir, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "mamdr_hip.h"))
-    objs = []
+    objs, todo = [], []
     for src, extra in SOURCES:
         s = os.path.join(CSRC, src)
-        o = os.path.join(BUILD, src.replace(".hip", ".o"))
+        o = os.path.join(build_dir, src.replace(".hip", ".o"))
         objs.append(o)
-        cmd = [hipcc] + COMMON + extra + ["-c", s, "-o", o]
+        cmd = [hipcc] + COMMON + extra + list(extra_flags) + ["-c", s, "-o", o]
         # a change of flags rebuilds too: the command line is kept next to the object
         stamp = o + ".cmd"
         same_cmd = os.path.exists(stamp) and open(stamp).read() == " ".join(cmd)
         if force or not same_cmd or _stale(o, [s] + headers):
-            if verbose:
-                print(" ".join(cmd), flush=True)
-            subprocess.check_call(cmd)
-            with open(stamp, "w") as f:
-                f.write(" ".join(cmd))
-    if force or _stale(OUT, objs):
-        cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", OUT] + objs
+            todo.append((cmd, stamp))
+
+    def compile_one(job):
+        cmd, stamp = job
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)
-    return OUT
+        with open(stamp, "w") as f:
+            f.write(" ".join(cmd))
+
+    with ThreadPoolExecutor(max_workers=JOBS) as pool:
+        list(pool.map(compile_one, todo))
+    if force or _stale(out, objs):
+        cmd = [hipcc, "-shared", "-fPIC", "--offload-arch=gfx950", "-o", out] + objs
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return out
+
+
+def build_variant(name, flags, force=False, verbose=True):
+    """A diagnostic build of the same sources with extra flags on every compile: build/variants/lib<name>.so (load it with
+    MAMDR_LIB_PATH); its objects live in build/variants/<name>/."""
+    vdir = os.path.join(BUILD, "variants")
+    return build(force=force, verbose=verbose, out=os.path.join(vdir, "lib%s.so" % name),
+                 build_dir=os.path.join(vdir, name), extra_flags=flags)
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv)
+    argv = sys.argv[1:]
+    force = "--force" in argv
+    if "--variant" in argv:      # python -m mamdr_amd.build --variant <name> <flags...>   (tools/build_variant.sh)
+        rest = [a for a in argv[argv.index("--variant") + 1:] if a != "--force"]
+        if not rest:
+            sys.exit("usage: python -m mamdr_amd.build --variant <name> <flags...>")
+        print("built", os.path.relpath(build_variant(rest[0], rest[1:], force=force)))
+    else:
+        build(force=force)

@@ -3,8 +3,10 @@
 // by its JSON files only, run.py:20-33); the defaults are what the parity tests and bench.py run.
 //   * mamdr_env_switches() (include/mamdr_hip.h) hands the table out ("NAME\twho reads it\teffect\n" ...): DESIGN.md
 //     section 10 points here, and tests/test_abi_and_parallel.py checks that every MAMDR_* name any source file reads is listed.
-//   * mamdr_create and mamdr_graph_create scan the environment once per process and WARN on stderr about any MAMDR_*
-//     name that is not in the table (a misspelt switch used to be silently ignored: VERDICT r05 weak #11).
+//   * the scan for unknown names runs ONCE PER PROCESS (env_warn_unknown, step_context.hip: a function-local static), at
+//     the first mamdr_create or mamdr_graph_create, not per context: it WARNS on stderr about any MAMDR_* name of the
+//     environment that is not in the table (a misspelt switch used to be silently ignored: VERDICT r05 weak #11); a name set
+//     after that first create is not looked at again.
 #pragma once
 
 namespace mamdr {

@@ -55,8 +55,8 @@
 //   a step         mamdr_graph_train_steps_n: step_ctx, advance_optimizer, open_sink, launch_gather, task_forward, launch_head,
 //                  launch_loss, task_backward, finish_grads, star_chain, table_step, adam_step; mamdr_graph_eval_domain shares
 //                  step_ctx / launch_gather / task_forward / launch_head / launch_loss.  Nothing in a step allocates.
-//   a context      mamdr_graph_create: validate_config, layout_one_task (layout_star / layout_single) or layout_multi_task,
-//                  alloc_workspace; every device pointer comes from dev_alloc and is freed from its record (mamdr_graph::allocs)
+//   a context      mamdr_graph_create: validate_config, read_switches, layout_one_task (layout_star / layout_single) or
+//                  layout_multi_task, alloc_workspace; every device pointer is freed from the record it came from (mamdr_graph::dev)
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -69,6 +69,7 @@
 
 #include "../../include/mamdr_hip.h"
 #include "mamdr_kernels.h"
+#include "host_common.h"
 
 // every kernel launch of this engine goes through here: the count is what tools/graph_bench.py reports as launches per step
 static std::atomic<long long> g_graph_launches{0};      // (contexts may be driven from several host threads: lanes)
@@ -82,19 +83,10 @@ using namespace mamdr;
 
 namespace {
 
-thread_local char g_gerr[512] = "";
-int gfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_gerr, sizeof(g_gerr), fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define GHIP(expr)                                                                              \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return gfail(MAMDR_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+thread_local ErrBuf g_gerr;     // mamdr_graph_last_error
+template <typename... A>
+int gfail(int code, const char* fmt, A... a) { return g_gerr.fail(code, fmt, a...); }
+#define GHIP(expr) MAMDR_HIP_TRY(g_gerr, expr, #expr)
 
 constexpr int GT = 64;      // output tile (rows and columns)
 constexpr int GK = 16;      // reduction depth per staged tile
@@ -1813,13 +1805,6 @@ struct Task {
     std::vector<int> path;              // dnns on the path: mix..., gate, tower
     int g_col = 0, m_col = 0, n_cols = 0;
 };
-struct SplitData {
-    const int32_t *uid = nullptr, *pid = nullptr, *dom = nullptr;
-    const float* label = nullptr;
-    int64_t n = 0;
-    bool bound = false;     // an empty split (n = 0) is bound too
-};
-
 }  // namespace
 
 struct mamdr_graph {
@@ -1870,8 +1855,7 @@ struct mamdr_graph {
     float b1p = 1.f, b2p = 1.f;
     uint32_t global_step = 0;
     // workspace
-    std::vector<void*> allocs;  // every device allocation of this context (dev_alloc): what mamdr_graph_destroy frees
-    hipError_t alloc_err = hipSuccess;
+    DevAllocs dev;              // every device allocation of this context: what mamdr_graph_destroy frees
     int rows_pad_max = 0, ld = 0;
     float *act = nullptr, *dact = nullptr, *grad = nullptr, *dlogit = nullptr, *rowloss = nullptr, *y = nullptr;
     float* wpart = nullptr;     // split-K partial products of one weight gradient (launch_wgrad)
@@ -3136,24 +3120,16 @@ int layout_multi_task(mamdr_graph* g) {
     return max_cols;
 }
 
-// every device allocation of a context goes through here: mamdr_graph_destroy frees what this recorded (after the first
-// failure nothing more is allocated; alloc_workspace reports it)
-template <typename T>
-void dev_alloc(mamdr_graph* g, T** p, size_t count) {
-    if (g->alloc_err != hipSuccess) return;
-    g->alloc_err = hipMalloc((void**)p, count * sizeof(T));
-    if (g->alloc_err == hipSuccess) g->allocs.push_back(*p);
-}
+// every device allocation of a context goes through its record (DevAllocs, host_common.h): mamdr_graph_destroy frees what
+// it holds (after the first failure nothing more is allocated; reported below)
 hipError_t alloc_workspace(mamdr_graph* g) {
     const mamdr_graph_config& cfg = g->cfg;
     float thr[500];
-    thr[0] = (float)(0.0 - 1e-7);
-    for (int i = 0; i < 498; ++i) thr[i + 1] = (float)((double)(i + 1) * 1.0 / (double)(500 - 1));
-    thr[499] = (float)(1.0 + 1e-7);
+    auc_thresholds(thr);
     const size_t rp = (size_t)g->rows_pad_max, n_grad = (size_t)(g->n_params - g->table_floats);
-    dev_alloc(g, &g->act, rp * g->ld);
-    dev_alloc(g, &g->dact, rp * g->ld);
-    dev_alloc(g, &g->grad, n_grad);
+    g->dev.alloc(&g->act, rp * g->ld);
+    g->dev.alloc(&g->dact, rp * g->ld);
+    g->dev.alloc(&g->grad, n_grad);
     size_t max_w = (size_t)EMB * ATT_P;
     for (const Dnn& d : g->dnns)
         for (const Layer& L : d.layers) max_w = std::max(max_w, (size_t)L.in * L.out);
@@ -3169,58 +3145,58 @@ hipError_t alloc_workspace(mamdr_graph* g) {
         g->wpart_floats = std::max(g->wpart_floats, 8 * max_path);
     }
     g->wpart_floats += 16 * (size_t)XDIM * cfg.auxiliary_dim;       // Star: the auxiliary kernel's splits
-    dev_alloc(g, &g->wpart, g->wpart_floats);
+    g->dev.alloc(&g->wpart, g->wpart_floats);
     if (g->stab.n) {
-        dev_alloc(g, &g->eff, 4 * (size_t)g->stab.first4[g->stab.n]);
-        dev_alloc(g, &g->deff, 4 * (size_t)g->stab.first4[g->stab.n]);
+        g->dev.alloc(&g->eff, 4 * (size_t)g->stab.first4[g->stab.n]);
+        g->dev.alloc(&g->deff, 4 * (size_t)g->stab.first4[g->stab.n]);
     }
     if (cfg.star_norm) {
-        dev_alloc(g, &g->spart, (rp + SN_ROWS - 1) / SN_ROWS * 2 * XDIM);
-        dev_alloc(g, &g->pnv, (size_t)3 * XDIM);
+        g->dev.alloc(&g->spart, (rp + SN_ROWS - 1) / SN_ROWS * 2 * XDIM);
+        g->dev.alloc(&g->pnv, (size_t)3 * XDIM);
     }
     size_t max_mix = 0;
     for (const Task& t : g->tasks) max_mix = std::max(max_mix, t.mix.size());
     if (g->gated && max_mix > 1) {
         g->dxpart_floats = max_mix * rp * (size_t)(g->tables ? XDIM : EMB);
-        dev_alloc(g, &g->dxpart, g->dxpart_floats);
+        g->dev.alloc(&g->dxpart, g->dxpart_floats);
     }
     if (g->tables) {
-        dev_alloc(g, &g->urow, rp);
-        dev_alloc(g, &g->irow, rp);
-        dev_alloc(g, &g->hasdup_u, rp);
-        dev_alloc(g, &g->hasdup_i, rp);
-        dev_alloc(g, &g->map_u, (size_t)cfg.n_user);
-        dev_alloc(g, &g->map_i, (size_t)cfg.n_item);
-        dev_alloc(g, &g->gbuf_u, rp * g->emb);
-        dev_alloc(g, &g->gbuf_i, rp * g->emb);
+        g->dev.alloc(&g->urow, rp);
+        g->dev.alloc(&g->irow, rp);
+        g->dev.alloc(&g->hasdup_u, rp);
+        g->dev.alloc(&g->hasdup_i, rp);
+        g->dev.alloc(&g->map_u, (size_t)cfg.n_user);
+        g->dev.alloc(&g->map_i, (size_t)cfg.n_item);
+        g->dev.alloc(&g->gbuf_u, rp * g->emb);
+        g->dev.alloc(&g->gbuf_i, rp * g->emb);
     }
-    dev_alloc(g, &g->dlogit, rp);
-    dev_alloc(g, &g->rowloss, rp);
-    dev_alloc(g, &g->y, rp);
-    dev_alloc(g, &g->domrow, rp);
-    dev_alloc(g, &g->thresholds, (size_t)500);
-    dev_alloc(g, &g->frozen_sumsq, (size_t)4);
-    dev_alloc(g, &g->sumsq_partials, (size_t)1024);
-    dev_alloc(g, &g->eval_acc, (size_t)4);
+    g->dev.alloc(&g->dlogit, rp);
+    g->dev.alloc(&g->rowloss, rp);
+    g->dev.alloc(&g->y, rp);
+    g->dev.alloc(&g->domrow, rp);
+    g->dev.alloc(&g->thresholds, (size_t)500);
+    g->dev.alloc(&g->frozen_sumsq, (size_t)4);
+    g->dev.alloc(&g->sumsq_partials, (size_t)1024);
+    g->dev.alloc(&g->eval_acc, (size_t)4);
     if (cfg.kind == MAMDR_GRAPH_AUTOINT) {
-        dev_alloc(g, &g->xt, rp * XDIM);
-        dev_alloc(g, &g->dxt, rp * XDIM);
+        g->dev.alloc(&g->xt, rp * XDIM);
+        g->dev.alloc(&g->dxt, rp * XDIM);
         for (int l = 0; l < 3; ++l) {
-            dev_alloc(g, &g->attP[l], 3 * rp * ATT_P);
-            dev_alloc(g, &g->attdP[l], 3 * rp * ATT_P);
-            dev_alloc(g, &g->attA[l], rp * 36);
-            dev_alloc(g, &g->attY[l], 3 * rp * ATT_OUT);
-            dev_alloc(g, &g->attdY[l], 3 * rp * ATT_OUT);
+            g->dev.alloc(&g->attP[l], 3 * rp * ATT_P);
+            g->dev.alloc(&g->attdP[l], 3 * rp * ATT_P);
+            g->dev.alloc(&g->attA[l], rp * 36);
+            g->dev.alloc(&g->attY[l], 3 * rp * ATT_OUT);
+            g->dev.alloc(&g->attdY[l], 3 * rp * ATT_OUT);
         }
     }
     if (g->has_lin) {
-        dev_alloc(g, &g->extra, rp);
+        g->dev.alloc(&g->extra, rp);
         if (g->tables) {
-            dev_alloc(g, &g->glin_u, rp);
-            dev_alloc(g, &g->glin_i, rp);
+            g->dev.alloc(&g->glin_u, rp);
+            g->dev.alloc(&g->glin_i, rp);
         }
     }
-    hipError_t e = g->alloc_err;
+    hipError_t e = g->dev.err;
     if (e == hipSuccess) e = hipMemsetAsync(g->grad, 0, n_grad * sizeof(float), g->stream);
     if (g->tables && e == hipSuccess) {
         e = hipMemsetAsync(g->hasdup_u, 0, rp * sizeof(int32_t), g->stream);
@@ -3237,11 +3213,21 @@ hipError_t alloc_workspace(mamdr_graph* g) {
     return e;
 }
 
+// every environment switch of this engine (env_registry.h), read at mamdr_graph_create
+void read_switches(mamdr_graph* g) {
+    if (const char* ev = getenv("MAMDR_GRAPH_NO_DEFER")) g->defer_w = atoi(ev) == 0;
+    {
+        const char* ev = getenv("MAMDR_GRAPH_TILE32_BELOW");
+        g_tile32_below.store(ev ? atoi(ev) : TILE32_BELOW_DEFAULT, std::memory_order_relaxed);
+    }
+    if (const char* ev = getenv("MAMDR_GRAPH_NO_TAIL_OPT")) g->tail_opt = atoi(ev) == 0;
+}
+
 }  // namespace
 
 extern "C" {
 
-const char* mamdr_graph_last_error(void) { return g_gerr; }
+const char* mamdr_graph_last_error(void) { return g_gerr.text; }
 
 int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph** out) {
     if (!cfg || !out) return gfail(MAMDR_EINVAL, "null argument");
@@ -3262,12 +3248,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
     }
     g->emb = cfg->emb_dim;
     g->stream = (hipStream_t)stream;
-    if (const char* ev = getenv("MAMDR_GRAPH_NO_DEFER")) g->defer_w = atoi(ev) == 0;
-    {
-        const char* ev = getenv("MAMDR_GRAPH_TILE32_BELOW");
-        g_tile32_below.store(ev ? atoi(ev) : TILE32_BELOW_DEFAULT, std::memory_order_relaxed);
-    }
-    if (const char* ev = getenv("MAMDR_GRAPH_NO_TAIL_OPT")) g->tail_opt = atoi(ev) == 0;
+    read_switches(g);
     g->sink.p = nullptr;
     g->gated = cfg->kind == MAMDR_GRAPH_MMOE || cfg->kind == MAMDR_GRAPH_PLE;
     g->single = cfg->kind >= MAMDR_GRAPH_NFM;
@@ -3302,7 +3283,7 @@ int mamdr_graph_create(const mamdr_graph_config* cfg, void* stream, mamdr_graph*
 int mamdr_graph_destroy(mamdr_graph* g) {
     if (!g) return MAMDR_OK;
     (void)hipStreamSynchronize(g->stream);
-    for (void* p : g->allocs) (void)hipFree(p);
+    g->dev.free_all();
     delete g;
     return MAMDR_OK;
 }
@@ -3336,8 +3317,7 @@ int mamdr_graph_task_ranges(const mamdr_graph* g, int domain, int64_t* shared_of
 
 int mamdr_graph_bind_state(mamdr_graph* g, float* d_params, float* d_m, float* d_v) {
     if (check(g)) return MAMDR_EINVAL;
-    if (!d_params || !d_m || !d_v) return gfail(MAMDR_EINVAL, "null state pointer");
-    if (((uintptr_t)d_params | (uintptr_t)d_m | (uintptr_t)d_v) & 15) return gfail(MAMDR_EINVAL, "state pointers must be 16-byte aligned");
+    if (const int rc = check_state_ptrs(g_gerr, d_params, d_m, d_v)) return rc;
     g->params = d_params;
     g->adam_m = d_m;
     g->adam_v = d_v;
@@ -3356,22 +3336,14 @@ int mamdr_graph_optimizer_reset(mamdr_graph* g) {
     g->b1p = g->b2p = 1.f;
     return MAMDR_OK;
 }
-// the counterpart of mamdr_set_counters for the generic-layer engine: TF's running beta powers for `optimizer_steps` steps
+// the counterpart of mamdr_set_counters for the generic-layer engine: TF's running beta powers after `optimizer_steps` steps
 // (one optimizer object for all D compiled models: deep_mtl_ctr.py:52-55) and the position of the dropout stream
 int mamdr_graph_set_counters(mamdr_graph* g, int64_t optimizer_steps, int64_t dropout_steps) {
     if (check(g)) return MAMDR_EINVAL;
     if (optimizer_steps < 0 || optimizer_steps > (int64_t)0x7ffffff0 || dropout_steps < 0 || dropout_steps > (int64_t)0xffffffffLL)
         return gfail(MAMDR_EINVAL, "mamdr_graph_set_counters(%lld, %lld): out of range", (long long)optimizer_steps, (long long)dropout_steps);
     g->adam_t = optimizer_steps;
-    float b1 = 1.f, b2 = 1.f;
-    for (int64_t t = 0; t < optimizer_steps; ++t) {       // (stops where both products stop changing: mamdr_set_counters)
-        const float n1 = b1 * g->cfg.adam_beta1, n2 = b2 * g->cfg.adam_beta2;
-        if (n1 == b1 && n2 == b2) break;
-        b1 = n1;
-        b2 = n2;
-    }
-    g->b1p = b1;
-    g->b2p = b2;
+    tf_beta_powers(g->cfg.adam_beta1, g->cfg.adam_beta2, optimizer_steps, &g->b1p, &g->b2p);
     g->global_step = (uint32_t)dropout_steps;
     return MAMDR_OK;
 }
@@ -3396,19 +3368,10 @@ int64_t mamdr_graph_dropout_steps(const mamdr_graph* g) { return g ? (int64_t)g-
 
 int mamdr_graph_bind_table(mamdr_graph* g, int seg, const float* d_rows, int64_t n_rows) {
     if (check(g)) return MAMDR_EINVAL;
-    if (g->tables) return gfail(MAMDR_ESTATE, "tables are trainable: they live in the flat vector");
-    if (!d_rows || ((uintptr_t)d_rows & 15)) return gfail(MAMDR_EINVAL, "table pointer null or not 16-byte aligned");
-    if (seg == MAMDR_SEG_USER_EMB) {
-        if (n_rows != g->cfg.n_user) return gfail(MAMDR_EINVAL, "user table has %lld rows, config says %d", (long long)n_rows, g->cfg.n_user);
-        g->user_tab = d_rows;
-        launch_sumsq(d_rows, n_rows * g->emb, g->sumsq_partials, g->frozen_sumsq + 0, g->stream);
-    } else if (seg == MAMDR_SEG_ITEM_EMB) {
-        if (n_rows != g->cfg.n_item) return gfail(MAMDR_EINVAL, "item table has %lld rows, config says %d", (long long)n_rows, g->cfg.n_item);
-        g->item_tab = d_rows;
-        launch_sumsq(d_rows, n_rows * g->emb, g->sumsq_partials, g->frozen_sumsq + 1, g->stream);
-    } else {
-        return gfail(MAMDR_EINVAL, "segment %d is not a bindable table", seg);
-    }
+    if (const int rc = check_bind_table(g_gerr, g->tables, seg, d_rows, n_rows, g->cfg.n_user, g->cfg.n_item)) return rc;
+    const int item = seg == MAMDR_SEG_ITEM_EMB;
+    (item ? g->item_tab : g->user_tab) = d_rows;
+    launch_sumsq(d_rows, n_rows * g->emb, g->sumsq_partials, g->frozen_sumsq + item, g->stream);
     GHIP(hipGetLastError());
     return MAMDR_OK;
 }
@@ -3416,17 +3379,7 @@ int mamdr_graph_bind_table(mamdr_graph* g, int seg, const float* d_rows, int64_t
 int mamdr_graph_bind_domain_data(mamdr_graph* g, int domain, int split, const int32_t* d_uid, const int32_t* d_pid,
                                  const int32_t* d_domain, const float* d_label, int64_t n_rows) {
     if (check(g)) return MAMDR_EINVAL;
-    SplitData* d = split_of(g, domain, split);
-    if (!d) return gfail(MAMDR_EINVAL, "domain %d / split %d out of range", domain, split);
-    if (n_rows < 0 || n_rows > 0x7fffffff) return gfail(MAMDR_EINVAL, "n_rows out of range");
-    if (n_rows > 0 && (!d_uid || !d_pid || !d_domain || !d_label)) return gfail(MAMDR_EINVAL, "null column pointer");
-    d->bound = true;
-    d->uid = d_uid;
-    d->pid = d_pid;
-    d->dom = d_domain;
-    d->label = d_label;
-    d->n = n_rows;
-    return MAMDR_OK;
+    return bind_columns(g_gerr, split_of(g, domain, split), domain, split, d_uid, d_pid, d_domain, d_label, n_rows);
 }
 
 int mamdr_graph_train_steps(mamdr_graph* g, int domain, const int32_t* d_perm, int64_t first_step, int64_t n_steps,
@@ -3440,21 +3393,11 @@ int mamdr_graph_train_steps_n(mamdr_graph* g, int domain, const int32_t* d_perm,
     if (check(g)) return MAMDR_EINVAL;
     if (ready(g)) return MAMDR_ESTATE;
     SplitData* d = split_of(g, domain, MAMDR_SPLIT_TRAIN);
-    if (!d || !d->bound) return gfail(MAMDR_ESTATE, "train split of domain %d is not bound", domain);
-    if (batch <= 0 || batch > g->cfg.max_batch) return gfail(MAMDR_EINVAL, "batch %d outside (0, max_batch=%d]", batch, g->cfg.max_batch);
-    if (optimizer != MAMDR_OPT_ADAM && optimizer != MAMDR_OPT_SGD && optimizer != MAMDR_OPT_ACCUMULATE)
-        return gfail(MAMDR_EINVAL, "unknown optimizer %d", optimizer);
-    if (optimizer == MAMDR_OPT_ACCUMULATE && !g->accum)
-        return gfail(MAMDR_ESTATE, "MAMDR_OPT_ACCUMULATE needs mamdr_graph_bind_accumulator first");
-    if (first_step < 0 || n_steps < 0) return gfail(MAMDR_EINVAL, "negative step range");
-    if (pass_rows < 0) pass_rows = d->n;                 // the whole split
-    if (pass_rows > d->n) return gfail(MAMDR_EINVAL, "pass of %lld rows exceeds the %lld rows of domain %d",
-                                       (long long)pass_rows, (long long)d->n, domain);
+    if (const int rc = check_train_call(g_gerr, d, domain, batch, g->cfg.max_batch, optimizer, g->accum,
+                                        "mamdr_graph_bind_accumulator", first_step, n_steps, &pass_rows))
+        return rc;
     if (pass_rows < d->n && !d_perm) return gfail(MAMDR_EINVAL, "a pass over part of a split needs its permutation");
-    const int64_t pass_steps = (pass_rows + batch - 1) / batch;
-    if (first_step + n_steps > pass_steps)
-        return gfail(MAMDR_EINVAL, "steps [%lld,%lld) exceed the %lld batches of domain %d", (long long)first_step,
-                     (long long)(first_step + n_steps), (long long)pass_steps, domain);
+    if (const int rc = check_step_range(g_gerr, domain, pass_rows, batch, first_step, n_steps)) return rc;
     if (n_steps == 0) return MAMDR_OK;
     const Task& t = g->tasks[g->single ? 0 : domain];
     for (int64_t s = 0; s < n_steps; ++s) {

@@ -1,4 +1,4 @@
-// Internal launch interface between the C ABI (mamdr_api.hip) and the kernel
+// Internal launch interface between the C ABI (mamdr_api.hip, step_*.hip) and the kernel
 // translation units.  Not part of the public boundary (include/mamdr_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,11 +19,11 @@ struct OptArgsLite {
 };
 constexpr int32_t EMB_UNTOUCHED = 0x7fffffff;
 
-// Profiling (mamdr_api.hip: Prof): while a timed launch is being issued, g_prof_stop is the event the launch
+// Profiling (step_ctx.h: Prof): while a timed launch is being issued, g_prof_stop is the event the launch
 // carries as its OWN stop event (hipExtLaunchKernelGGL: recorded by the kernel's completion, no marker packet
 // between the kernels).  A kernel's time is then its stop event minus the stop event of the kernel before it.
 extern thread_local hipEvent_t g_prof_stop;
-int env_warn_unknown();          // mamdr_api.hip: MAMDR_* names of the environment missing from env_registry.h, reported once
+int env_warn_unknown();          // step_context.hip: MAMDR_* names of the environment missing from env_registry.h, reported once
 #define MAMDR_LAUNCH(kernel, grid, block, lds, stream, ...)                                               \
     do {                                                                                                  \
         if (::mamdr::g_prof_stop) {                                                                       \

@@ -1,0 +1,269 @@
+// C ABI of libmamdr_hip.so, the queries of a step-kernel context: evaluation of a split, the gathered input rows, top-K
+// retrieval, and the (stateless) per-user grouped AUC of any evaluation's predictions.
+#include <algorithm>
+
+#include "step_ctx.h"
+
+extern "C" {
+
+int mamdr_eval_domain(mamdr_ctx* c, int domain, int split, int32_t batch, float* d_loss_out, uint32_t* d_hist,
+                      float* d_pred_out) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (ready(c)) return MAMDR_ESTATE;
+    SplitData* d = split_of(c, domain, split);
+    if (!d || !d->bound) return fail(MAMDR_ESTATE, "split %d of domain %d is not bound", split, domain);
+    if (!d_loss_out || !d_hist) return fail(MAMDR_EINVAL, "null output pointer");
+    sync_tables(c);
+    if (batch <= 0 || batch % TILE_ROWS != 0) return fail(MAMDR_EINVAL, "eval batch must be a positive multiple of %d", TILE_ROWS);
+    if (d->n <= 0) return fail(MAMDR_EINVAL, "split %d of domain %d is empty", split, domain);
+    HIP_TRY(hipMemsetAsync(d_hist, 0, 2 * 501 * sizeof(uint32_t), c->stream));
+    TowerArgs ta;
+    fill_tower_common(c, *d, ta);
+    ta.perm = nullptr;
+    ta.row_base = 0;
+    ta.rows = (int)d->n;
+    ta.batch = batch;
+    ta.loss_part = c->eval_part;
+    ta.hist = d_hist;
+    ta.pred_out = d_pred_out;
+    if (c->star) {
+        // inference: domain `domain`'s moving statistics and merged kernels (partitioned_norm.py:143-165)
+        StarPrepArgs pa;
+        fill_star_prep(c, domain, pa);
+        launch_star_prep(pa, c->stream);
+        ta.dense = c->eff;
+        ta.pn_aff = c->pn;
+    }
+    {
+        Prof p(c, MAMDR_KERNEL_EVAL);
+        launch_tower_eval(ta, c->stream);
+    }
+    if (c->cfg.emb_trainable) refresh_table_sumsq(c);
+    EvalFinishArgs fa;
+    fa.loss_part = c->eval_part;
+    fa.n_rows = d->n;
+    fa.batch = batch;
+    fa.dense = c->params + c->table_floats;
+    fa.dm_count = c->star ? 0 : c->cfg.n_domain * EMB;
+    fa.l2_emb = c->star ? 0.f : c->cfg.l2_emb;
+    fa.frozen_sumsq = c->frozen_sumsq;
+    fa.ld_off = c->L.ld;
+    fa.ld_count = c->L.ld_count;
+    fa.l2_lin = c->cfg.l2_linear;
+    fa.loss_out = d_loss_out;
+    launch_eval_finish(fa, c->stream);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_gather_rows(mamdr_ctx* c, int domain, int split, const int32_t* d_perm, int64_t first_row,
+                      int64_t n_rows, float* d_out) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (ready(c)) return MAMDR_ESTATE;
+    SplitData* d = split_of(c, domain, split);
+    if (!d || !d->bound) return fail(MAMDR_ESTATE, "split %d of domain %d is not bound", split, domain);
+    if (!d_out) return fail(MAMDR_EINVAL, "null output pointer");
+    if (first_row < 0 || n_rows < 0 || first_row + n_rows > d->n) return fail(MAMDR_EINVAL, "row range outside the split");
+    if (n_rows == 0) return MAMDR_OK;
+    sync_tables(c);
+    TowerArgs ta;
+    fill_tower_common(c, *d, ta);
+    ta.perm = d_perm;
+    ta.row_base = first_row;
+    ta.rows = (int)n_rows;
+    {
+        Prof p(c, MAMDR_KERNEL_GATHER);
+        launch_gather(ta, d_out, c->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+// ---- top-K retrieval (recommend_kernels.hip)
+static int grow_rec_workspace(mamdr_ctx* c, int chunk) {
+    if (chunk <= c->rec_cap) return MAMDR_OK;
+    c->dev.release(c->rec_P);
+    c->dev.release(c->rec_lin);
+    c->dev.release(c->rec_part);
+    c->rec_P = c->rec_lin = nullptr;
+    c->rec_part = nullptr;
+    c->rec_cap = 0;
+    c->dev.alloc(&c->rec_P, (size_t)chunk * H1);
+    c->dev.alloc(&c->rec_lin, (size_t)chunk);
+    c->dev.alloc(&c->rec_part, (size_t)REC_QBLOCK * chunk);
+    if (!c->rec_q) c->dev.alloc(&c->rec_q, (size_t)REC_QBLOCK * (H1 + EMB + 4));
+    if (!c->rec_best) c->dev.alloc(&c->rec_best, (size_t)REC_QBLOCK * REC_KMAX);
+    if (const int rc = c->dev.check(g_err)) return rc;
+    c->rec_cap = chunk;
+    return MAMDR_OK;
+}
+
+// the body of both entry points: `domain` < 0 = mamdr_recommend (query q in d_domain[q]), otherwise every query in `domain`
+static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                          const int32_t* d_domain, const int32_t* d_cand, int64_t n_cand, const int64_t* d_excl_off,
+                          const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    const bool per_query = domain < 0;
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (k < 1 || k > REC_KMAX) return fail(MAMDR_EINVAL, "%s: k %d outside [1, %d]", fn, k, REC_KMAX);
+    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
+    if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
+        return fail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
+    if ((((uintptr_t)d_uid | (uintptr_t)d_domain | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_ids_out |
+          (uintptr_t)d_scores_out | (uintptr_t)d_scores_all) & 3) || ((uintptr_t)d_excl_off & 7))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
+    if (ready(c)) return MAMDR_ESTATE;
+    if (!d_cand) n_cand = c->cfg.n_item;
+    sync_tables(c);              // lagging table rows and lazily replayed per-domain slices: as mamdr_eval_domain
+    prof_break(c);
+    const int chunk = (int)std::min<int64_t>(c->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
+    if (int e = grow_rec_workspace(c, chunk)) return e;
+    RecArgs a;
+    memset(&a, 0, sizeof(a));
+    a.user_tab = c->cfg.emb_trainable ? c->params : c->user_tab;
+    a.item_tab = c->cfg.emb_trainable ? c->params + (size_t)c->cfg.n_user * EMB : c->item_tab;
+    a.dense = c->params + c->table_floats;
+    a.L = c->L;
+    a.dom_all = per_query ? -1 : domain;
+    if (c->star) {
+        // inference in `domain`: its moving statistics and merged kernels, exactly as mamdr_eval_domain prepares them.
+        // c->eff / c->pn are the training step's workspaces too: star_step rebuilds both at step 0 of every call
+        StarPrepArgs pa;
+        fill_star_prep(c, domain, pa);
+        launch_star_prep(pa, c->stream);
+        a.dense = c->eff;
+        a.pn = c->pn;
+    }
+    a.n_user = c->cfg.n_user;
+    a.n_item = c->cfg.n_item;
+    a.n_domain = c->cfg.n_domain;
+    a.mode = c->deepfm ? (c->cfg.tower == MAMDR_TOWER_WDL ? 2 : 1) : 0;
+    if (c->deepfm && c->cfg.emb_trainable) {
+        a.lin_user = c->params + c->lin_user_off;
+        a.lin_item = c->params + c->lin_item_off;
+    }
+    a.cand = d_cand;
+    a.n_cand = n_cand;
+    a.excl_ids = d_excl_ids;
+    a.k = k;
+    a.kt = std::min<int>(k, REC_TILE);
+    a.tiles_cap = c->rec_cap / REC_TILE;
+    a.P = c->rec_P;
+    a.lin_i = c->rec_lin;
+    a.q0 = c->rec_q;
+    a.qud = c->rec_q + (size_t)REC_QBLOCK * H1;
+    a.qs = a.qud + (size_t)REC_QBLOCK * EMB;
+    a.part = c->rec_part;
+    a.best = c->rec_best;
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        a.n_query = std::min<int32_t>(REC_QBLOCK, n_query - qb);
+        a.uid = d_uid + qb;
+        a.dom = per_query ? d_domain + qb : nullptr;
+        a.excl_off = d_excl_off ? d_excl_off + qb : nullptr;
+        a.ids_out = d_ids_out + (size_t)qb * k;
+        a.scores_out = d_scores_out + (size_t)qb * k;
+        a.scores_all = d_scores_all ? d_scores_all + (size_t)qb * n_cand : nullptr;
+        launch_rec_query_proj(a, c->stream);
+        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
+            a.c_base = c0;
+            a.n_chunk = (int)std::min<int64_t>(chunk, n_cand - c0);
+            a.tiles = (a.n_chunk + REC_TILE - 1) / REC_TILE;
+            a.first_chunk = c0 == 0;
+            a.last_chunk = c0 + chunk >= n_cand;
+            launch_rec_item_proj(a, c->stream);
+            if (!launch_rec_score(a, c->stream))
+                return fail(MAMDR_EHIP, "%s: k_rec_score was refused its LDS limit (hipFuncSetAttribute)", fn);
+            launch_rec_merge(a, c->stream);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_recommend(mamdr_ctx* c, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain, const int32_t* d_cand,
+                    int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
+                    float* d_scores_out, float* d_scores_all) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->star)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend: the star tower is not built for retrieval with a domain per query (its "
+                                     "first layer separates into a query and an item term per domain only: "
+                                     "mamdr_recommend_domain); mlp, wdl and deepfm are");
+    if (c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend: the %s tower is not built for retrieval (its first layer does not separate "
+                                     "into a query and an item term); mlp, wdl and deepfm are", c->pnn ? "pnn" : "nfm");
+    return recommend_body(c, "mamdr_recommend", -1, n_query, d_uid, d_domain, d_cand, n_cand, d_excl_off, d_excl_ids, k,
+                          d_ids_out, d_scores_out, d_scores_all);
+}
+
+int mamdr_recommend_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
+                           int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k,
+                           int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_recommend_domain: the %s tower is not built for retrieval (its first layer does not "
+                                     "separate into a query and an item term); mlp, wdl, deepfm and star are", c->pnn ? "pnn" : "nfm");
+    if (domain < 0 || domain >= c->cfg.n_domain)
+        return fail(MAMDR_EINVAL, "mamdr_recommend_domain: domain %d outside [0, %d)", domain, c->cfg.n_domain);
+    return recommend_body(c, "mamdr_recommend_domain", domain, n_query, d_uid, nullptr, d_cand, n_cand, d_excl_off, d_excl_ids,
+                          k, d_ids_out, d_scores_out, d_scores_all);
+}
+
+// ---- per-user grouped AUC (gauc_kernels.hip): stateless, like the outer updates
+int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_order, int64_t n, const int64_t* d_group_off,
+                    int64_t n_groups, const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
+                    uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream) {
+    if (!d_result || !d_group_off) return fail(MAMDR_EINVAL, "mamdr_group_auc: null result / group offsets pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_group_auc: n %lld outside [0, 2^31)", (long long)n);
+    if (n_groups < 0 || n_groups > n)
+        return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld groups for %lld rows", (long long)n_groups, (long long)n);
+    if (n > 0 && (!d_pred || !d_label || !d_order)) return fail(MAMDR_EINVAL, "mamdr_group_auc: null pred / label / order pointer");
+    if (n_tiles < 0 || n_tiles > n) return fail(MAMDR_EINVAL, "mamdr_group_auc: n_tiles %lld for %lld rows", (long long)n_tiles, (long long)n);
+    if (n_tiles == 0 && (d_tile_group || d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: a tile list given without tiles");
+    if (n_tiles > 0 && (!d_tile_group || !d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld tiles need both of their lists", (long long)n_tiles);
+    if ((((uintptr_t)d_pred | (uintptr_t)d_label | (uintptr_t)d_order | (uintptr_t)d_tile_group | (uintptr_t)d_P) & 3) ||
+        (((uintptr_t)d_group_off | (uintptr_t)d_tile_first | (uintptr_t)d_T | (uintptr_t)d_result) & 7))
+        return fail(MAMDR_EINVAL, "mamdr_group_auc: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    GaucArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.order = d_order;
+    a.group_off = d_group_off;
+    a.tile_group = d_tile_group;
+    a.tile_first = d_tile_first;
+    a.n = n;
+    a.n_groups = n_groups;
+    a.n_tiles = n_tiles;
+    a.n_parts = gauc_parts(n_groups);
+    a.result = d_result;
+    // the call's own scratch, ordered on its stream: [T if not given | partial sums | P if not given]
+    const size_t t_bytes = d_T ? 0 : (size_t)n_groups * sizeof(uint64_t);
+    const size_t part_bytes = (size_t)a.n_parts * (sizeof(double) + 2 * sizeof(uint64_t));
+    const size_t p_bytes = d_P ? 0 : (size_t)n_groups * sizeof(uint32_t);
+    char* ws = nullptr;
+    if (t_bytes + part_bytes + p_bytes) HIP_TRY(hipMallocAsync((void**)&ws, t_bytes + part_bytes + p_bytes, s));
+    a.T = d_T ? reinterpret_cast<unsigned long long*>(d_T) : reinterpret_cast<unsigned long long*>(ws);
+    a.part_num = reinterpret_cast<double*>(ws + t_bytes);
+    a.part_rows = reinterpret_cast<unsigned long long*>(a.part_num + a.n_parts);
+    a.part_valid = a.part_rows + a.n_parts;
+    a.P = d_P ? d_P : reinterpret_cast<uint32_t*>(ws + t_bytes + part_bytes);
+    hipError_t e = hipSuccess;
+    if (n_groups > 0) {
+        e = hipMemsetAsync(a.T, 0, (size_t)n_groups * sizeof(uint64_t), s);
+        if (e == hipSuccess) e = hipMemsetAsync(a.P, 0, (size_t)n_groups * sizeof(uint32_t), s);
+    }
+    if (e == hipSuccess) {
+        launch_gauc(a, s);
+        e = hipGetLastError();
+    }
+    if (ws) {
+        const hipError_t ef = hipFreeAsync(ws, s);
+        if (e == hipSuccess) e = ef;
+    }
+    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_group_auc: %s", hipGetErrorString(e));
+    return MAMDR_OK;
+}
+
+}  // extern "C"

@@ -4,8 +4,8 @@ element (tests/test_gpu_optimizer.py), with the bar that says how far a site may
 Host scalars.  The library forms them on the host in fp32, one rounding per operation, and so does `scalars` here:
     omb   = fl(1 - beta)                                    (mamdr_api.hip, graph_engine.hip: omb1 / omb2)
     b1p_t = fl(b1p_{t-1} * beta1), b2p_t likewise           (TF's running beta1_power / beta2_power variables)
-    alpha = fl(fl(lr * fl(sqrt(fl(1 - b2p)))) / fl(1 - b1p))  (mamdr_api.hip `step_alpha`, graph_engine.hip `alpha`,
-                                                            mamdr_adam_apply)
+    alpha = fl(fl(lr * fl(sqrt(fl(1 - b2p)))) / fl(1 - b1p))  (mamdr_api.hip `adam_alpha`, graph_engine.hip `alpha`,
+                                                            mamdr_adam_apply in step_stateless.hip)
 Everything after that is evaluated exactly (float64; the few products lose nothing that matters at the bar):
     m* = m + (g - m) omb1,   v* = v + (g^2 - v) omb2,   p* = p - delta*,   delta* = m* alpha / (sqrt(v*) + eps)
 

@@ -295,6 +295,51 @@ int mamdr_recommend_domain(mamdr_ctx* ctx, int32_t domain, int32_t n_query, cons
                            const int64_t* d_excl_off, const int32_t* d_excl_ids,
                            int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all);
 
+/* Exact ranks of target items among a candidate list, every query of the call in ONE domain, from the live weights of an
+ * mlp / wdl / deepfm / star tower.  NO REFERENCE COUNTERPART, as mamdr_recommend.  Where mamdr_recommend_domain returns the
+ * first k <= 128 positions of a query's ordering, this call returns, for chosen (query, target) pairs, the position
+ * itself -- one integer per pair, from which MRR, mean percentile rank and HitRate / Recall / NDCG at any K follow.
+ *   domain, n_query, d_uid, d_cand, n_cand, d_excl_off, d_excl_ids
+ *                              mamdr_recommend_domain's, with the same checks and errors
+ *   d_tgt_off [n_query + 1], d_tgt_ids
+ *                              CSR of target items per query: offsets ascending from 0 (checked: the call reads them back,
+ *                              its one synchronisation of the context's stream); the ids of a query ascending and
+ *                              distinct, inside [0, n_item) (ids outside are clamped: range-check on the host).  A query
+ *                              may have no targets; so may the whole call, which then produces d_live_out only
+ *   d_rank_out [n targets]     int32, see Rank
+ *   d_score_out                optional [n targets], see Score
+ *   d_live_out [n_query]       int32, see Live
+ * key(q, x) is the 64-bit ranking key of the top-K calls: (order-preserving bits of the logit << 32) | ~id, so a larger
+ * key is a higher logit or an equal logit and a smaller item id; -0 counts as +0; a NaN logit is behind every number.
+ * A candidate c is live for q when it is not in q's exclusion list.
+ * Rank.  d_rank_out[j], for target j = (q, t), is #{ c in candidates, live for q : key(q, c) > key(q, t) }: the number
+ *   of live candidates that order strictly before the pair.  It is defined for any target id, whether or not t is among
+ *   the candidates or excluded for q: the caller decides what an unlisted target means.  The target never counts itself:
+ *   equal ids give equal keys, the target's key being the bits the candidate pass computes for the same pair.
+ * Score.  d_score_out[j] = sigmoid(logit(q, t)), the bits d_scores_all of mamdr_recommend_domain holds for that pair.
+ * Live.  d_live_out[q] is the number of live candidates of q.  A NaN-scored candidate is live.
+ * Link to top-K.  For t among the candidates and live, and k <= 128: t is at position r of mamdr_recommend_domain's list
+ *   exactly when its rank is r < k.
+ * Two phases per block of 256 queries: the target keys (the targets' item term, then 64 consecutive targets per
+ * workgroup through the layers and the head of the scoring tile), then the scoring tiles of the top-K calls with a
+ * counting ending instead of the sort -- popcount(ballot(key > target key)) per (tile, target), added with an integer
+ * atomic.  No merge pass.
+ * Determinism: all counts are integers and there is no floating-point atomic: the outputs are the same bits from run to
+ * run and under any MAMDR_REC_CHUNK.
+ * Reads the state only, as mamdr_recommend_domain: tables and lazily replayed slices are brought up to date first, the star
+ * tower's effective block and PartitionedNorm workspace are built for `domain` in inference mode; weights, Adam slots,
+ * counters and gathered windows are untouched.  The call zeroes d_rank_out and d_live_out itself, on the context's stream;
+ * the target keys live in a workspace of the context, grown on demand.
+ * MAMDR_EINVAL: mamdr_recommend_domain's cases; a null d_tgt_off, d_rank_out or d_live_out; d_tgt_ids null while targets
+ * exist; offsets that do not start at 0 or descend; a misaligned pointer.  MAMDR_ESTATE: as mamdr_recommend;
+ * MAMDR_ENOTBUILT: the pnn / nfm towers.  (Added within ABI 19: a new entry point only, no structure or existing call
+ * changed.) */
+int mamdr_rank_domain(mamdr_ctx* ctx, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                      const int32_t* d_cand, int64_t n_cand,
+                      const int64_t* d_excl_off, const int32_t* d_excl_ids,
+                      const int64_t* d_tgt_off, const int32_t* d_tgt_ids,
+                      int32_t* d_rank_out, float* d_score_out, int32_t* d_live_out);
+
 /* Per-user grouped AUC (GAUC, Zhou et al., DIN, KDD 2018) of one split's predictions.  NO REFERENCE COUNTERPART: the
  * reference reports one 500-threshold AUC per domain (base_model.py:111-144) and nothing per user.  Stateless, any stream.
  * Definition.  For one split of one domain, group the rows by uid.  For a group u with r_u rows, P_u of them positive

@@ -106,6 +106,7 @@ SIGNATURES = {
     "mamdr_gather_rows": (C.c_int, [_VP, C.c_int, C.c_int, _VP, _I64, _I64, _VP]),
     "mamdr_recommend": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
     "mamdr_recommend_domain": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mamdr_rank_domain": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mamdr_group_auc": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
     "mamdr_interp": (C.c_int, [_VP, _VP, _VP, _F, _I64, _VP]),
     "mamdr_moving_average": (C.c_int, [_VP, _VP, _VP, _F, _F, _I64, _VP]),

@@ -28,7 +28,8 @@ SOURCES = [
     ("star_kernels.hip", []),
     ("outer_kernels.hip", ["-ffp-contract=off"]),
     ("graph_engine.hip", []),
-    ("recommend_kernels.hip", []),
+    # recommend_kernels: its register / LDS / scratch report: profiles/rank_bench.txt
+    ("recommend_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
     # gauc_kernels: the fp64 terms are a division, a multiplication and additions as the host definition computes them
     # -> no fma fusion; its register / LDS / scratch report: profiles/gauc_bench.txt
     ("gauc_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),

@@ -10,6 +10,8 @@ Dispatch is by substring of config.model.name, in the reference's order (run.py:
 Every tower name of the reference's registries is built (run.py:37-47; deepctr.py:24-50: mlp wdl nfm autoint ccpm pnn
 deepfm; deep_mtl_ctr.py:25-49: shared_bottom mmoe ple; star); Star in every form of star.py:70-96 -- norm none / pn / bn, dense dense / star, auxiliary_net); what is not (ple with more than one
 level, uncertainty weighting on the multi-task towers) raises NotImplementedError naming why.
+Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, and
+--rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report).
 """
 import argparse
 import json
@@ -104,7 +106,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     their recorders there).  recommend = K (not an option of the reference's run.py): once the pipeline has ended, rank 0 /
     lane 0 ranks every domain's catalogue for its test users with the weights the run finished with and writes the top K
     (recommend.report) to recommend_out, by default under train.result_save_path.  train.report_gauc (run.py --gauc; not a
-    key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py)."""
+    key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.rank_eval = [K,
+    ...] (run.py --rank-eval; not a key of the reference's configs either): once the pipeline has ended, the exact rank of every
+    test positive in its domain's whole catalogue, with MRR, mean percentile and HitRate / Recall / NDCG at those K
+    (recommend.rank_report), written under train.result_save_path."""
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
     name = config["model"]["name"]
@@ -116,6 +121,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
         raise NotImplementedError("train.report_gauc (run.py --gauc): the per-user grouped AUC is not gathered across processes "
                                   "or lanes (parallel.gather_domain_scalars carries loss and AUC only); run it with one "
                                   "process and train.lanes = 1")
+    if config["train"].get("rank_eval") and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
+                                  "(the best phi_d slots are current only on their owners); run it with one process and "
+                                  "train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
     if lanes > 1:
         # (under N processes the lanes of every rank are a slice of ONE world of N * lanes participants: a rank's DR queries
@@ -153,9 +162,11 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
         avg_loss, avg_auc, domain_loss, domain_auc = model.separate_train_val_test(init_parms=False)
     if rank == 0:
         model.save_result(avg_loss, avg_auc, domain_loss, domain_auc)
+        from . import recommend as rec
         if recommend:
-            from . import recommend as rec
             rec.report(model, int(recommend), recommend_out)
+        if config["train"].get("rank_eval"):
+            rec.rank_report(model, config["train"]["rank_eval"])
     return avg_loss, avg_auc, domain_loss, domain_auc
 
 
@@ -171,6 +182,9 @@ def cli(argv=None):
                         help=".npz the recommendations go to (default: under train.result_save_path)")
     parser.add_argument("--gauc", action="store_true",
                         help="also report the impression-weighted per-user AUC (GAUC) of every evaluation (train.report_gauc)")
+    parser.add_argument("--rank-eval", type=str, default=None, nargs="?", const="10,50,200", metavar="KS",
+                        help="after the run: the exact rank of every test positive in its domain's whole catalogue, with MRR, mean "
+                             "percentile and HitRate / Recall / NDCG at the comma list KS (default 10,50,200) (train.rank_eval)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -178,6 +192,8 @@ def cli(argv=None):
         config["train"]["lanes"] = args.lanes
     if args.gauc:
         config["train"]["report_gauc"] = True
+    if args.rank_eval is not None:
+        config["train"]["rank_eval"] = [int(k) for k in args.rank_eval.split(",")]
     if args.recommend is None:
         return main(config)
     return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

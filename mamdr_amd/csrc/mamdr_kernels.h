@@ -831,7 +831,7 @@ struct PcgArgs {
 };
 void launch_pcgrad(const PcgArgs& a, hipStream_t s);
 
-// recommend_kernels.hip: top-K retrieval (mamdr_recommend, mamdr_recommend_domain).  One RecArgs describes a block of queries x a chunk of
+// recommend_kernels.hip: top-K retrieval (mamdr_recommend, mamdr_recommend_domain) and exact ranks (mamdr_rank_domain).  One RecArgs describes a block of queries x a chunk of
 // candidates; the query-side pointers (uid, dom, excl_off, the outputs) are already offset to the block's first query.
 constexpr int REC_TILE = 64;          // candidates per workgroup of k_rec_score (chunks are multiples of it)
 constexpr int REC_KMAX = 128;         // largest K
@@ -871,11 +871,21 @@ struct RecArgs {
     int32_t* ids_out;          // [n_query][k]
     float* scores_out;
     float* scores_all;         // nullable [n_query][n_cand]
+    // mamdr_rank_domain only (null / unused on the top-K path): positions j into the call's flat target list
+    const int64_t* tgt_off;    // [n_query + 1] CSR of the block's queries: query q owns targets [tgt_off[q], tgt_off[q + 1])
+    unsigned long long* tkey;  // [n targets of the call] workspace: key(q, t), written by k_rec_pair, read by the counting tiles
+    float* tscore_out;         // nullable [n targets]: sigmoid(logit(q, t))
+    int32_t* rank_out;         // [n targets], zeroed by the call
+    int32_t* live_out;         // [n_query] of the block, zeroed by the call
 };
 void launch_rec_item_proj(const RecArgs& a, hipStream_t s);
 void launch_rec_query_proj(const RecArgs& a, hipStream_t s);
 bool launch_rec_score(const RecArgs& a, hipStream_t s);        // false: its LDS limit was refused, nothing launched
 void launch_rec_merge(const RecArgs& a, hipStream_t s);
+// mamdr_rank_domain: the pair tiles over targets [c_base, c_base + n_chunk) (cand = the target ids, P / lin_i their item
+// terms) and the counting ending of k_rec_score; false as launch_rec_score
+bool launch_rec_pair(const RecArgs& a, hipStream_t s);
+bool launch_rec_count(const RecArgs& a, hipStream_t s);
 
 // gauc_kernels.hip: per-user grouped AUC of one split's predictions (mamdr_group_auc)
 constexpr int GAUC_SMALL = 64;        // groups of up to this many rows: one wave each (k_gauc_small)

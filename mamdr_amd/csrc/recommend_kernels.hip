@@ -21,6 +21,12 @@
 // Ranking: one 64-bit key per pair, (order-preserving bits of the logit << 32) | ~id: descending key order = descending
 // logit, equal logits by ascending item id, a NaN logit behind every number; key 0 = no entry (excluded pair, padding).
 // Keys of distinct ids are distinct, so the top K of a query is one well-defined list whatever the tiles and chunks.
+//
+// Exact ranks (mamdr_rank_domain): the same phases with a counting ending.  The targets' keys first -- their item term
+// (k_rec_item_proj over the flat target list), then k_rec_pair, 64 (query, target) pairs per workgroup through the layers
+// and the head of the scoring tile, so a target's key is the bits the grid computes for the same pair --, then
+// k_rec_score<REC_EPI_COUNT>: a tile counts its keys above each target key of its query by ballot + popcount and adds the
+// count with one integer atomic.  No sort, no merge; integers only, so the sums do not depend on the tiles' order.
 #include "mamdr_kernels.h"
 
 namespace mamdr {
@@ -171,32 +177,14 @@ __device__ __forceinline__ u64 rec_wave_sort(u64 key, int lane) {
     return key;
 }
 
-// ---- one (query, 64 candidates) tile: h0 = relu(q0[q] + P[c]) staged in LDS, layers 1 and 2 on fp32 MFMA with bias + relu
-// between them, the head (wo, gb, then the wdl / deepfm extras), the optional dense score matrix and the tile's partial
-// top-K.  Layer 1: wave w owns columns [32 w, 32 w + 32) of both 32-row halves (each weight element fetched once per
-// tile); layer 2: wave w owns the 32 x 32 quadrant (w >> 1, w & 1).
-__global__ __launch_bounds__(REC_THREADS) void k_rec_score(const RecArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int tile = blockIdx.x, q = blockIdx.y;
-    const int p0 = tile * REC_TILE;
+// ---- layers 1 and 2 of a 64-row tile whose h0 [64][260] the caller has staged in LDS (entered before the barrier that
+// publishes h0, left behind the barrier that publishes h2 [64][68]): fp32 MFMA with bias + relu between them.  Layer 1:
+// wave w owns columns [32 w, 32 w + 32) of both 32-row halves (each weight element fetched once per tile); layer 2: wave w
+// owns the 32 x 32 quadrant (w >> 1, w & 1).  Rows never meet: a row's h2 depends on its own h0 and the weights only, so
+// the grid tile (k_rec_score) and the pair tile (k_rec_pair) give one pair the same bits.
+__device__ __forceinline__ void rec_layers12(const RecArgs& a, float* smem, int tid) {
     const float* __restrict__ dense = a.dense;
-    {
-        const int c4 = tid & 63;
-        const f32x4 qv = *reinterpret_cast<const f32x4*>(a.q0 + (size_t)q * H1 + 4 * c4);
-#pragma unroll 4
-        for (int t = 0; t < REC_TILE * (H1 / 4) / REC_THREADS; ++t) {
-            const int r = (tid >> 6) + 4 * t, pos = p0 + r;
-            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (pos < a.n_chunk) {
-                const f32x4 pv = *reinterpret_cast<const f32x4*>(a.P + (size_t)pos * H1 + 4 * c4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(qv[e] + pv[e], 0.f);
-            }
-            *reinterpret_cast<f32x4*>(smem + r * H0_LD + 4 * c4) = v;
-        }
-        if (a.mode == 1 && tid < EMB) smem[SC_UD_OFF + tid] = a.qud[(size_t)q * EMB + tid];
-    }
+    const int lane = tid & 63, w = tid >> 6;
     __syncthreads();
     const int c = lane & 31, h = lane >> 5;
     {
@@ -245,39 +233,81 @@ __global__ __launch_bounds__(REC_THREADS) void k_rec_score(const RecArgs a) {
         }
     }
     __syncthreads();
-    // ---- head: four lanes per pair, 16 hidden units (and 32 elements of deepfm's i . (u + d)) each, a two-step xor tree
+}
+
+// ---- the head of one pair (tile row `row`, item `id`, position `pos` of the chunk when `in`) of query q: four lanes per
+// pair (part = 0 .. 3), 16 hidden units (and 32 elements of deepfm's i . (u + d)) each, a two-step xor tree; then wo, gb
+// and the wdl / deepfm extras.  `ud` is the query's u + d -- the tile's LDS copy or a.qud's row: the same values, the same
+// fma order.  Every lane of the four returns the logit
+__device__ __forceinline__ float rec_head(const RecArgs& a, const float* smem, int row, int part, bool in, int id, int pos,
+                                          int q, const float* ud) {
+    const float* __restrict__ dense = a.dense;
+    const float* wo = dense + a.L.wo + 16 * part;
+    const float* hr = smem + SC_H2_OFF + row * H2_LD + 16 * part;
+    float s = 0.f;
+#pragma unroll
+    for (int n = 0; n < 16; ++n) s = fmaf(hr[n], wo[n], s);
+    s += __shfl_xor(s, 1);
+    s += __shfl_xor(s, 2);
+    float logit = s + dense[a.L.gb];
+    if (a.mode != 0) {
+        float fm = 0.f;
+        if (a.mode == 1) {
+            const float* ir = a.item_tab + (size_t)id * EMB + 32 * part;
+            ud += 32 * part;
+#pragma unroll
+            for (int k4 = 0; k4 < 8; ++k4) {
+                const f32x4 iv = *reinterpret_cast<const f32x4*>(ir + 4 * k4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) fm = fmaf(iv[e], ud[4 * k4 + e], fm);
+            }
+            fm += __shfl_xor(fm, 1);
+            fm += __shfl_xor(fm, 2);
+            fm += a.qs[2 * q];
+        }
+        const float lin = a.qs[2 * q + 1] + (in ? a.lin_i[pos] : 0.f);
+        logit += fm + lin;
+    }
+    logit += 0.f;                                 // -0 -> +0: equal logits are equal keys
+    return logit;
+}
+
+// ---- one (query, 64 candidates) tile: h0 = relu(q0[q] + P[c]) staged in LDS, layers 1 and 2 (rec_layers12), the head
+// (rec_head), the optional dense score matrix, the tile's 64 keys in LDS (0 = excluded pair or padding) and one of two
+// endings.  REC_EPI_TOPK: the tile's partial top-K (mamdr_recommend, mamdr_recommend_domain).  REC_EPI_COUNT
+// (mamdr_rank_domain): lane l of every wave holds key l; wave w takes the query's targets tgt_off[q] + w, + 4, ... and adds
+// popcount(ballot(key_l > tkey[j])) to rank_out[j]; wave 0 adds the tile's live candidates to live_out[q].  Integer atomics
+// only: the sums are the same whatever the order the tiles arrive in.
+enum { REC_EPI_TOPK = 0, REC_EPI_COUNT = 1 };
+template <int EPI>
+__global__ __launch_bounds__(REC_THREADS) void k_rec_score(const RecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int tile = blockIdx.x, q = blockIdx.y;
+    const int p0 = tile * REC_TILE;
+    {
+        const int c4 = tid & 63;
+        const f32x4 qv = *reinterpret_cast<const f32x4*>(a.q0 + (size_t)q * H1 + 4 * c4);
+#pragma unroll 4
+        for (int t = 0; t < REC_TILE * (H1 / 4) / REC_THREADS; ++t) {
+            const int r = (tid >> 6) + 4 * t, pos = p0 + r;
+            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (pos < a.n_chunk) {
+                const f32x4 pv = *reinterpret_cast<const f32x4*>(a.P + (size_t)pos * H1 + 4 * c4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fmaxf(qv[e] + pv[e], 0.f);
+            }
+            *reinterpret_cast<f32x4*>(smem + r * H0_LD + 4 * c4) = v;
+        }
+        if (a.mode == 1 && tid < EMB) smem[SC_UD_OFF + tid] = a.qud[(size_t)q * EMB + tid];
+    }
+    rec_layers12(a, smem, tid);
     u64* keys = reinterpret_cast<u64*>(smem + SC_KEY_OFF);
     {
         const int row = tid >> 2, part = tid & 3, pos = p0 + row;
         const bool in = pos < a.n_chunk;
         const int id = in ? rec_cand_id(a, pos) : 0;
-        const float* wo = dense + a.L.wo + 16 * part;
-        const float* hr = smem + SC_H2_OFF + row * H2_LD + 16 * part;
-        float s = 0.f;
-#pragma unroll
-        for (int n = 0; n < 16; ++n) s = fmaf(hr[n], wo[n], s);
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        float logit = s + dense[a.L.gb];
-        if (a.mode != 0) {
-            float fm = 0.f;
-            if (a.mode == 1) {
-                const float* ir = a.item_tab + (size_t)id * EMB + 32 * part;
-                const float* ud = smem + SC_UD_OFF + 32 * part;
-#pragma unroll
-                for (int k4 = 0; k4 < 8; ++k4) {
-                    const f32x4 iv = *reinterpret_cast<const f32x4*>(ir + 4 * k4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) fm = fmaf(iv[e], ud[4 * k4 + e], fm);
-                }
-                fm += __shfl_xor(fm, 1);
-                fm += __shfl_xor(fm, 2);
-                fm += a.qs[2 * q];
-            }
-            const float lin = a.qs[2 * q + 1] + (in ? a.lin_i[pos] : 0.f);
-            logit += fm + lin;
-        }
-        logit += 0.f;                             // -0 -> +0: equal logits are equal keys
+        const float logit = rec_head(a, smem, row, part, in, id, pos, q, smem + SC_UD_OFF);
         if (part == 0) {
             bool valid = in;
             if (valid && a.excl_off) {            // the query's excluded ids, ascending
@@ -293,9 +323,72 @@ __global__ __launch_bounds__(REC_THREADS) void k_rec_score(const RecArgs a) {
         }
     }
     __syncthreads();
-    if (w == 0) {
-        const u64 key = rec_wave_sort(keys[lane], lane);
-        if (lane < a.kt) a.part[((size_t)q * a.tiles_cap + tile) * a.kt + lane] = key;
+    if (EPI == REC_EPI_TOPK) {
+        if (w == 0) {
+            const u64 key = rec_wave_sort(keys[lane], lane);
+            if (lane < a.kt) a.part[((size_t)q * a.tiles_cap + tile) * a.kt + lane] = key;
+        }
+    } else {
+        const u64 key = keys[lane];
+        if (w == 0) {
+            const int live = __popcll(__ballot(key != 0ull));
+            if (lane == 0 && live) atomicAdd(a.live_out + q, live);
+        }
+        const int64_t t1 = a.tgt_off[q + 1];
+        for (int64_t j = a.tgt_off[q] + w; j < t1; j += REC_THREADS / 64) {
+            const int cnt = __popcll(__ballot(key > a.tkey[j]));      // (a key of 0 is above no target: tkey >= 1 << 32)
+            if (lane == 0 && cnt) atomicAdd(a.rank_out + j, cnt);
+        }
+    }
+}
+
+// ---- the pair form of the scoring tile (mamdr_rank_domain's target pre-pass): 64 consecutive positions of the flat target
+// list per workgroup, row r = target j = c_base + p0 + r of the query that a binary search of j in tgt_off finds (queries
+// without targets are stepped over).  h0 = relu(q0[q_r] + P[r]) with P the targets' item term (k_rec_item_proj over
+// cand = tgt_ids), then rec_layers12 and rec_head as the grid tile runs them: tkey[j] is the key the grid computes for the
+// pair (q_r, tgt_ids[j]), whether or not the item is a candidate or excluded; score_out[j] = sigmoid of the same logit.
+__global__ __launch_bounds__(REC_THREADS) void k_rec_pair(const RecArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    int* rowq = reinterpret_cast<int*>(smem + SC_UD_OFF);          // [64] the rows' queries (the u + d slot is free here)
+    const int tid = threadIdx.x;
+    const int p0 = blockIdx.x * REC_TILE;
+    if (tid < REC_TILE) {
+        int lo = 0;
+        if (p0 + tid < a.n_chunk) {
+            const int64_t j = a.c_base + p0 + tid;
+            int hi = a.n_query - 1;                                // first q with tgt_off[q + 1] > j
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (a.tgt_off[mid + 1] <= j) lo = mid + 1; else hi = mid;
+            }
+        }
+        rowq[tid] = lo;
+    }
+    __syncthreads();
+    {
+        const int c4 = tid & 63;
+#pragma unroll 4
+        for (int t = 0; t < REC_TILE * (H1 / 4) / REC_THREADS; ++t) {
+            const int r = (tid >> 6) + 4 * t, pos = p0 + r;
+            f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
+            if (pos < a.n_chunk) {
+                const f32x4 qv = *reinterpret_cast<const f32x4*>(a.q0 + (size_t)rowq[r] * H1 + 4 * c4);
+                const f32x4 pv = *reinterpret_cast<const f32x4*>(a.P + (size_t)pos * H1 + 4 * c4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = fmaxf(qv[e] + pv[e], 0.f);
+            }
+            *reinterpret_cast<f32x4*>(smem + r * H0_LD + 4 * c4) = v;
+        }
+    }
+    const int row = tid >> 2, part = tid & 3, pos = p0 + row;
+    const int q = rowq[row];                                       // (read before layer 1's barriers; nothing overwrites it)
+    rec_layers12(a, smem, tid);
+    const bool in = pos < a.n_chunk;
+    const int id = in ? rec_cand_id(a, pos) : 0;
+    const float logit = rec_head(a, smem, row, part, in, id, pos, q, a.qud + (size_t)q * EMB);
+    if (part == 0 && in) {
+        a.tkey[a.c_base + pos] = rec_key(logit, id);
+        if (a.tscore_out) a.tscore_out[a.c_base + pos] = rec_sigmoid(logit);
     }
 }
 
@@ -347,12 +440,27 @@ void launch_rec_query_proj(const RecArgs& a, hipStream_t s) {
     MAMDR_LAUNCH(k_rec_query_proj, dim3(a.n_query), dim3(REC_THREADS), 0, s, a);
 }
 // -> false: the 66 KB of LDS were refused (hipFuncSetAttribute), nothing was launched
+template <typename K>
+static bool raise_lds(K kernel) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(SC_FLOATS * sizeof(float))) == hipSuccess;
+}
 bool launch_rec_score(const RecArgs& a, hipStream_t s) {
-    static const bool raised = hipFuncSetAttribute(reinterpret_cast<const void*>(k_rec_score),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)(SC_FLOATS * sizeof(float))) == hipSuccess;
+    static const bool raised = raise_lds(k_rec_score<REC_EPI_TOPK>);
     if (!raised) return false;
-    MAMDR_LAUNCH(k_rec_score, dim3(a.tiles, a.n_query), dim3(REC_THREADS), SC_FLOATS * sizeof(float), s, a);
+    MAMDR_LAUNCH(k_rec_score<REC_EPI_TOPK>, dim3(a.tiles, a.n_query), dim3(REC_THREADS), SC_FLOATS * sizeof(float), s, a);
+    return true;
+}
+bool launch_rec_count(const RecArgs& a, hipStream_t s) {
+    static const bool raised = raise_lds(k_rec_score<REC_EPI_COUNT>);
+    if (!raised) return false;
+    MAMDR_LAUNCH(k_rec_score<REC_EPI_COUNT>, dim3(a.tiles, a.n_query), dim3(REC_THREADS), SC_FLOATS * sizeof(float), s, a);
+    return true;
+}
+bool launch_rec_pair(const RecArgs& a, hipStream_t s) {
+    static const bool raised = raise_lds(k_rec_pair);
+    if (!raised) return false;
+    MAMDR_LAUNCH(k_rec_pair, dim3((a.n_chunk + REC_TILE - 1) / REC_TILE), dim3(REC_THREADS), SC_FLOATS * sizeof(float), s, a);
     return true;
 }
 void launch_rec_merge(const RecArgs& a, hipStream_t s) {

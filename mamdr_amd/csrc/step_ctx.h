@@ -200,7 +200,7 @@ struct mamdr_ctx {
     float* frozen_sumsq = nullptr;  // [4] user, item table; DeepFM linear user, item table
     float* sumsq_partials = nullptr;
     DevAllocs dev;                  // every device allocation of this context, the buffers grown on demand too: what mamdr_destroy frees
-    // mamdr_recommend's workspace (RecArgs, mamdr_kernels.h): allocated on first use for chunks of up to rec_cap candidates
+    // the retrieval calls' workspace (RecArgs, mamdr_kernels.h): allocated on first use for chunks of up to rec_cap candidates
     int rec_chunk = 16384;          // candidates per pass (MAMDR_REC_CHUNK)
     int rec_cap = 0;
     float* rec_P = nullptr;
@@ -208,6 +208,8 @@ struct mamdr_ctx {
     float* rec_q = nullptr;         // q0 | qud | qs
     unsigned long long* rec_part = nullptr;
     unsigned long long* rec_best = nullptr;
+    unsigned long long* rec_tkey = nullptr;      // mamdr_rank_domain: the call's target keys, grown on demand
+    int64_t rec_tkey_cap = 0;
 #ifdef MAMDR_STAMPS
     unsigned long long* stamps = nullptr;
 #endif

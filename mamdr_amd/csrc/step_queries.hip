@@ -1,5 +1,5 @@
 // C ABI of libmamdr_hip.so, the queries of a step-kernel context: evaluation of a split, the gathered input rows, top-K
-// retrieval, and the (stateless) per-user grouped AUC of any evaluation's predictions.
+// retrieval, the exact ranks of target items, and the (stateless) per-user grouped AUC of any evaluation's predictions.
 #include <algorithm>
 
 #include "step_ctx.h"
@@ -98,28 +98,16 @@ static int grow_rec_workspace(mamdr_ctx* c, int chunk) {
     return MAMDR_OK;
 }
 
-// the body of both entry points: `domain` < 0 = mamdr_recommend (query q in d_domain[q]), otherwise every query in `domain`
-static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t n_query, const int32_t* d_uid,
-                          const int32_t* d_domain, const int32_t* d_cand, int64_t n_cand, const int64_t* d_excl_off,
-                          const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+// what both retrieval bodies do between their argument checks and their launches: tables brought up to date, the workspace
+// for `chunk` candidates per pass, and the RecArgs fields that do not change inside the call
+static int rec_prepare(mamdr_ctx* c, int32_t domain, const int32_t* d_cand, int64_t& n_cand, const int32_t* d_excl_ids,
+                       RecArgs& a, int& chunk) {
     const bool per_query = domain < 0;
-    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
-    if (k < 1 || k > REC_KMAX) return fail(MAMDR_EINVAL, "%s: k %d outside [1, %d]", fn, k, REC_KMAX);
-    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
-    if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
-        return fail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
-    if ((((uintptr_t)d_uid | (uintptr_t)d_domain | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_ids_out |
-          (uintptr_t)d_scores_out | (uintptr_t)d_scores_all) & 3) || ((uintptr_t)d_excl_off & 7))
-        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
-    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
-        return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
-    if (ready(c)) return MAMDR_ESTATE;
     if (!d_cand) n_cand = c->cfg.n_item;
     sync_tables(c);              // lagging table rows and lazily replayed per-domain slices: as mamdr_eval_domain
     prof_break(c);
-    const int chunk = (int)std::min<int64_t>(c->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
+    chunk = (int)std::min<int64_t>(c->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
     if (int e = grow_rec_workspace(c, chunk)) return e;
-    RecArgs a;
     memset(&a, 0, sizeof(a));
     a.user_tab = c->cfg.emb_trainable ? c->params : c->user_tab;
     a.item_tab = c->cfg.emb_trainable ? c->params + (size_t)c->cfg.n_user * EMB : c->item_tab;
@@ -146,8 +134,6 @@ static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t 
     a.cand = d_cand;
     a.n_cand = n_cand;
     a.excl_ids = d_excl_ids;
-    a.k = k;
-    a.kt = std::min<int>(k, REC_TILE);
     a.tiles_cap = c->rec_cap / REC_TILE;
     a.P = c->rec_P;
     a.lin_i = c->rec_lin;
@@ -156,6 +142,30 @@ static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t 
     a.qs = a.qud + (size_t)REC_QBLOCK * EMB;
     a.part = c->rec_part;
     a.best = c->rec_best;
+    return MAMDR_OK;
+}
+
+// the body of both entry points: `domain` < 0 = mamdr_recommend (query q in d_domain[q]), otherwise every query in `domain`
+static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                          const int32_t* d_domain, const int32_t* d_cand, int64_t n_cand, const int64_t* d_excl_off,
+                          const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    const bool per_query = domain < 0;
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (k < 1 || k > REC_KMAX) return fail(MAMDR_EINVAL, "%s: k %d outside [1, %d]", fn, k, REC_KMAX);
+    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
+    if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
+        return fail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
+    if ((((uintptr_t)d_uid | (uintptr_t)d_domain | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_ids_out |
+          (uintptr_t)d_scores_out | (uintptr_t)d_scores_all) & 3) || ((uintptr_t)d_excl_off & 7))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
+    if (ready(c)) return MAMDR_ESTATE;
+    RecArgs a;
+    int chunk;
+    if (int e = rec_prepare(c, domain, d_cand, n_cand, d_excl_ids, a, chunk)) return e;
+    a.k = k;
+    a.kt = std::min<int>(k, REC_TILE);
     for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
         a.n_query = std::min<int32_t>(REC_QBLOCK, n_query - qb);
         a.uid = d_uid + qb;
@@ -207,6 +217,83 @@ int mamdr_recommend_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const 
         return fail(MAMDR_EINVAL, "mamdr_recommend_domain: domain %d outside [0, %d)", domain, c->cfg.n_domain);
     return recommend_body(c, "mamdr_recommend_domain", domain, n_query, d_uid, nullptr, d_cand, n_cand, d_excl_off, d_excl_ids,
                           k, d_ids_out, d_scores_out, d_scores_all);
+}
+
+// ---- exact ranks of target items among a candidate list: the retrieval phases with the counting ending
+int mamdr_rank_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
+                      int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, const int64_t* d_tgt_off,
+                      const int32_t* d_tgt_ids, int32_t* d_rank_out, float* d_score_out, int32_t* d_live_out) {
+    const char* fn = "mamdr_rank_domain";
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_rank_domain: the %s tower is not built for retrieval (its first layer does not "
+                                     "separate into a query and an item term); mlp, wdl, deepfm and star are", c->pnn ? "pnn" : "nfm");
+    if (domain < 0 || domain >= c->cfg.n_domain)
+        return fail(MAMDR_EINVAL, "mamdr_rank_domain: domain %d outside [0, %d)", domain, c->cfg.n_domain);
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
+    if (!d_uid || !d_tgt_off || !d_rank_out || !d_live_out)
+        return fail(MAMDR_EINVAL, "%s: null uid / target offsets / rank / live output pointer", fn);
+    if ((((uintptr_t)d_uid | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_tgt_ids | (uintptr_t)d_rank_out |
+          (uintptr_t)d_score_out | (uintptr_t)d_live_out) & 3) || (((uintptr_t)d_excl_off | (uintptr_t)d_tgt_off) & 7))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
+    if (ready(c)) return MAMDR_ESTATE;
+    // the target offsets size the pre-pass and the key workspace: read back once (the call's one synchronisation of the
+    // context's stream) and held to their contract here, so that no kernel indexes past the target list
+    std::vector<int64_t> off((size_t)n_query + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), d_tgt_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (off[0] != 0) return fail(MAMDR_EINVAL, "%s: the target offsets start at %lld, not 0", fn, (long long)off[0]);
+    for (int32_t q = 0; q < n_query; ++q)
+        if (off[q + 1] < off[q]) return fail(MAMDR_EINVAL, "%s: the target offsets descend at query %d", fn, q);
+    const int64_t n_tgt = off[n_query];
+    if (n_tgt > 0 && !d_tgt_ids) return fail(MAMDR_EINVAL, "%s: %lld targets without their ids", fn, (long long)n_tgt);
+    RecArgs a;
+    int chunk;
+    if (int e = rec_prepare(c, domain, d_cand, n_cand, d_excl_ids, a, chunk)) return e;
+    if (n_tgt > c->rec_tkey_cap) {
+        c->dev.release(c->rec_tkey);
+        c->rec_tkey = nullptr;
+        c->rec_tkey_cap = 0;
+        c->dev.alloc(&c->rec_tkey, (size_t)n_tgt);
+        if (const int rc = c->dev.check(g_err)) return rc;
+        c->rec_tkey_cap = n_tgt;
+    }
+    a.tkey = c->rec_tkey;
+    a.tscore_out = d_score_out;
+    a.rank_out = d_rank_out;
+    if (n_tgt > 0) HIP_TRY(hipMemsetAsync(d_rank_out, 0, (size_t)n_tgt * sizeof(int32_t), c->stream));
+    HIP_TRY(hipMemsetAsync(d_live_out, 0, (size_t)n_query * sizeof(int32_t), c->stream));
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        a.n_query = std::min<int32_t>(REC_QBLOCK, n_query - qb);
+        a.uid = d_uid + qb;
+        a.excl_off = d_excl_off ? d_excl_off + qb : nullptr;
+        a.tgt_off = d_tgt_off + qb;
+        a.live_out = d_live_out + qb;
+        launch_rec_query_proj(a, c->stream);
+        // the block's target keys first: the item term of the flat target list, then the pair tiles
+        a.cand = d_tgt_ids;
+        for (int64_t t0 = off[qb]; t0 < off[qb + a.n_query]; t0 += c->rec_cap) {
+            a.c_base = t0;
+            a.n_chunk = (int)std::min<int64_t>(c->rec_cap, off[qb + a.n_query] - t0);
+            launch_rec_item_proj(a, c->stream);
+            if (!launch_rec_pair(a, c->stream))
+                return fail(MAMDR_EHIP, "%s: k_rec_pair was refused its LDS limit (hipFuncSetAttribute)", fn);
+        }
+        a.cand = d_cand;
+        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
+            a.c_base = c0;
+            a.n_chunk = (int)std::min<int64_t>(chunk, n_cand - c0);
+            a.tiles = (a.n_chunk + REC_TILE - 1) / REC_TILE;
+            launch_rec_item_proj(a, c->stream);
+            if (!launch_rec_count(a, c->stream))
+                return fail(MAMDR_EHIP, "%s: k_rec_score was refused its LDS limit (hipFuncSetAttribute)", fn);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
 }
 
 // ---- per-user grouped AUC (gauc_kernels.hip): stateless, like the outer updates

@@ -674,9 +674,9 @@ class TowerEngine(DeviceEngine):
             raise ValueError("recommend_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
         return self._recommend(uid, None, int(domain), k, candidates, exclude, want_scores)
 
-    def _recommend(self, uid, dom, domain, k, candidates, exclude, want_scores):
-        """the marshalling of both retrieval calls: dom [Q] int32 per query (mamdr_recommend) or None and the host integer
-        `domain` (mamdr_recommend_domain).  Every range check runs before the launch."""
+    def _retrieval_inputs(self, uid, candidates, exclude):
+        """the host arrays and range checks every retrieval call shares -> (n_query, candidates int32 or None, n_cand,
+        exclusion offsets, exclusion ids), the CSR None when nothing is excluded."""
         nq = int(uid.shape[0])
         if nq and (uid.min() < 0 or uid.max() >= self.n_user):
             raise ValueError("recommend: user or domain id out of range")
@@ -695,6 +695,48 @@ class TowerEngine(DeviceEngine):
             if ids.size and ids.max() >= self.n_item:
                 raise ValueError("recommend: excluded item id out of range")
             ids = ids if ids.size else np.zeros(1, np.int32)       # (a non-null pointer for an all-empty list)
+        return nq, cand, n_cand, off, ids
+
+    def rank_domain(self, uids, domain, targets, candidates=None, exclude=None, want_scores=False):
+        """exact ranks (mamdr_rank_domain) of `targets` -- one array of item ids per query, any order, duplicates allowed: made
+        ascending and distinct as `exclude` is -- among the candidates, every query in the one domain `domain`, from the
+        live weights.  candidates / exclude: as recommend_domain.  -> {"offsets" [Q + 1] int64, "ids" [T] int32 (the targets'
+        CSR), "ranks" [T] int32: the live candidates that order strictly before the pair (higher logit, or equal logit and
+        smaller id), "listed" [T] bool: the target is a candidate and not excluded for its query (only then is its rank its
+        0-based position in the query's ordering), "live" [Q] int32: live candidates per query [, "scores" [T]: sigmoid(logit)
+        of the pair]} as numpy.  Every range check runs before the launch."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
+            raise ValueError("rank_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
+        nq, cand, n_cand, off, ids = self._retrieval_inputs(uid, candidates, exclude)
+        t_off, t_ids = exclusion_csr(targets, nq, "targets")
+        if t_ids.size and t_ids.max() >= self.n_item:
+            raise ValueError("rank_domain: target item id out of range")
+        n_tgt = int(t_ids.shape[0])
+        in_cand = np.ones(n_tgt, bool) if cand is None else np.isin(t_ids, cand)
+        listed = in_cand.copy()
+        if off is not None:
+            for q in range(nq):
+                sl = slice(t_off[q], t_off[q + 1])
+                listed[sl] &= ~np.isin(t_ids[sl], ids[off[q]:off[q + 1]])
+        dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
+        d_uid, d_cand, d_off, d_ids, d_toff = dev(uid), dev(cand), dev(off), dev(ids), dev(t_off)
+        d_tids = dev(t_ids if n_tgt else np.zeros(1, np.int32))
+        ranks = torch.empty(max(n_tgt, 1), dtype=torch.int32, device=self.device)
+        live = torch.empty(max(nq, 1), dtype=torch.int32, device=self.device)
+        scores = torch.empty(max(n_tgt, 1), dtype=torch.float32, device=self.device) if want_scores else None
+        L.check(self.lib.mamdr_rank_domain(self.ctx, int(domain), nq, _ptr(d_uid), _ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids),
+                                           _ptr(d_toff), _ptr(d_tids), _ptr(ranks), _ptr(scores), _ptr(live)))
+        res = {"offsets": t_off, "ids": t_ids, "ranks": ranks.cpu().numpy()[:n_tgt], "listed": listed,
+               "live": live.cpu().numpy()[:nq]}
+        if want_scores:
+            res["scores"] = scores.cpu().numpy()[:n_tgt]
+        return res
+
+    def _recommend(self, uid, dom, domain, k, candidates, exclude, want_scores):
+        """the marshalling of both retrieval calls: dom [Q] int32 per query (mamdr_recommend) or None and the host integer
+        `domain` (mamdr_recommend_domain).  Every range check runs before the launch."""
+        nq, cand, n_cand, off, ids = self._retrieval_inputs(uid, candidates, exclude)
         dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
         d_uid, d_dom, d_cand, d_off, d_ids = dev(uid), dev(dom), dev(cand), dev(off), dev(ids)
         kk = max(int(k), 1)

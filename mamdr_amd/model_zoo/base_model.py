@@ -118,10 +118,10 @@ class BaseModel(object):
         return loss, auc
 
     # ------------------------------------------------------------------ retrieval (no reference counterpart)
-    def recommend(self, domain, k, users=None, exclude_seen=True):
-        """top-k items of `domain`'s catalogue -- the distinct pids of its three splits -- for `users` (default: the distinct
-        uids of its test split) from the live weights.  exclude_seen: a user never gets an item it has in the domain's train
-        or val split.  -> {"users" [Q], "ids" [Q, k] (-1 behind a short list), "scores" [Q, k], "catalogue": its size}."""
+    def _retrieval_problem(self, domain, users, exclude_seen):
+        """what `recommend` and `rank_eval` ask of `domain` -> (catalogue: the distinct pids of its three splits; users:
+        the given ones, by default the distinct uids of its test split; exclude: per user the items it has in the domain's
+        train or val split, None when exclude_seen is off)."""
         cols = [s[domain]["data"] for s in (self.dataset.train_dataset, self.dataset.val_dataset, self.dataset.test_dataset)
                 if domain in s]
         catalogue = np.unique(np.concatenate([np.asarray(c["pid"], np.int64) for c in cols]))
@@ -137,6 +137,13 @@ class BaseModel(object):
                     for u, p in zip(np.asarray(c["uid"]).tolist(), np.asarray(c["pid"]).tolist()):
                         seen.setdefault(u, []).append(p)
             exclude = [seen.get(int(u), ()) for u in users]
+        return catalogue, users, exclude
+
+    def recommend(self, domain, k, users=None, exclude_seen=True):
+        """top-k items of `domain`'s catalogue -- the distinct pids of its three splits -- for `users` (default: the distinct
+        uids of its test split) from the live weights.  exclude_seen: a user never gets an item it has in the domain's train
+        or val split.  -> {"users" [Q], "ids" [Q, k] (-1 behind a short list), "scores" [Q, k], "catalogue": its size}."""
+        catalogue, users, exclude = self._retrieval_problem(domain, users, exclude_seen)
         # one domain per call: the engine's single-domain retrieval where it has one (the only one the Star tower has)
         single = getattr(self.model, "recommend_domain", None)
         if single is not None:
@@ -145,6 +152,19 @@ class BaseModel(object):
             ids, scores = self.model.recommend(users, np.full(users.shape, domain, np.int64), k, candidates=catalogue,
                                                exclude=exclude)[:2]
         return {"users": users, "ids": ids, "scores": scores, "catalogue": int(catalogue.shape[0])}
+
+    def rank_eval(self, domain, users=None, exclude_seen=True):
+        """the exact rank, in `domain`'s whole catalogue, of every held-out positive -- the label-1 items of its test split --
+        of `users` (default: the distinct uids of its test split) from the live weights (the engine's rank_domain:
+        mamdr_rank_domain).  exclude_seen: the items a user has in the domain's train or val split are not candidates.
+        -> the engine's dict ("offsets", "ids", "ranks", "listed", "live") plus "users" [Q], "catalogue" (the candidate ids)
+        and "n_positives" [Q] (the distinct positives of each user)."""
+        from .. import recommend as rec
+        catalogue, users, exclude = self._retrieval_problem(domain, users, exclude_seen)
+        positives = rec.split_positives(self.dataset, domain, users)
+        res = dict(self.model.rank_domain(users, int(domain), positives, candidates=catalogue, exclude=exclude))
+        res.update(users=users, catalogue=catalogue, n_positives=np.diff(res["offsets"]).astype(np.int64))
+        return res
 
     # ------------------------------------------------------------------ finetune / separate training
     def separate_train_val_test(self, init_parms=True):

@@ -107,6 +107,20 @@ class SpecificBase(MAML):
             domain_loss, domain_auc = parallel.gather_domain_scalars(local, self.n_domain, self.model.device)
         return self.base_model._summarise(mode, domain_loss, domain_auc)
 
+    def rank_eval(self, domain, users=None, exclude_seen=True):
+        """BaseModel.rank_eval under domain `domain`'s own weights: with best weights kept, the best theta (+|*) phi_domain is
+        installed for the call -- what val_and_test("test") scores the domain with -- and the previous live flat vector is
+        put back afterwards, bit for bit.  Before the first snapshot the live weights are ranked, as `recommend` does.  A
+        finetune run is ranked with the un-finetuned best merged weights: the per-domain finetuned models are not kept."""
+        if self.best_shared_weights is None or not self.best_domain_weights or domain not in self.best_domain_weights:
+            return self.base_model.rank_eval(domain, users, exclude_seen)
+        live = self.model.get_weights().clone()
+        self._set_model_meta_parms(self._merge_weights(self.best_shared_weights, self.best_domain_weights[domain]))
+        try:
+            return self.base_model.rank_eval(domain, users, exclude_seen)
+        finally:
+            self.model.set_weights(live)
+
     def separate_train_val_test(self, init_parms=True):
         if init_parms:
             return self.base_model.separate_train_val_test(init_parms=True)

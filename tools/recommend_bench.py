@@ -5,6 +5,13 @@ by default.  --tower star: every query in domain 0 through mamdr_recommend_domai
 call), the eval leg over the same triples as domain 0's split.
 
     python tools/recommend_bench.py [--tower mlp|wdl|deepfm|star] [--queries 512] [--k 10] [--reps 5] [--out profiles/recommend_bench.txt]
+    python tools/recommend_bench.py --rank [--tower mlp|star] [--targets 3] [--out profiles/rank_bench.txt]
+
+--rank: mamdr_rank_domain (exact ranks of `targets` random items per query among the whole item table, every query in domain
+0) beside (b) mamdr_recommend_domain(k) over the same queries and (c) what a caller without it must do: recommend_domain with
+the dense [queries, items] score matrix, its read-back and a numpy ranking per target -- (a) and (b) in device time by the
+method below, (c) in wall time (two warm-up rounds, `reps` rounds).  The rank leg also checks the link to top-K on 8 queries;
+the host leg counts the (query, target, tile) triples whose count is not zero -- the integer atomics of a call.
 
 Method (device time): each leg runs in a child process of its own under `timeout -k 10`; inside it two warm-up calls, then
 `reps` calls between two HIP events recorded on the engine's stream; the figure is elapsed / reps.  The recommend leg's
@@ -82,12 +89,57 @@ def leg(args):
     eng, n_user, n_item, n_domain = build(args.tower, 1024)
     rs = np.random.RandomState(3)
     uids = rs.choice(n_user, args.queries, replace=False).astype(np.int32)
-    star = args.tower == "star"
+    star = args.tower == "star" or args.rank          # (--rank: every leg in domain 0 through the single-domain calls)
     doms = np.zeros_like(uids) if star else (uids % n_domain).astype(np.int32)
     pairs = int(args.queries) * n_item
     res = {"leg": args.leg, "tower": args.tower, "queries": int(args.queries), "items": n_item, "pairs": pairs, "k": args.k,
            "device": torch.cuda.get_device_name(eng.device), "reps": args.reps}
-    if args.leg == "recommend":
+    if args.leg in ("rank", "host"):
+        targets = [rs.choice(n_item, args.targets, replace=False) for _ in range(args.queries)]
+        res["targets"] = args.targets
+    if args.leg == "rank":
+        from mamdr_amd.recommend import exclusion_csr
+        t_off, t_ids = exclusion_csr(targets, args.queries, "targets")
+        d_uid, d_off, d_ids = (torch.from_numpy(x).to(eng.device) for x in (uids, t_off, t_ids))
+        ranks = torch.empty(t_ids.size, dtype=torch.int32, device=eng.device)
+        live = torch.empty(args.queries, dtype=torch.int32, device=eng.device)
+        p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+
+        def call():
+            L.check(eng.lib.mamdr_rank_domain(eng.ctx, 0, args.queries, p(d_uid), None, 0, None, None, p(d_off), p(d_ids),
+                                              p(ranks), None, p(live)))
+        res["ms"] = timed(eng, call, args.reps)
+        # the link to top-K (8 queries): a target of rank r < 128 is the r-th id of recommend_domain's list
+        top = eng.recommend_domain(uids[:8], 0, 128)[0]
+        got = ranks.cpu().numpy()
+        for q in range(8):
+            for j in range(t_off[q], t_off[q + 1]):
+                assert (top[q, got[j]] == t_ids[j]) if got[j] < 128 else (t_ids[j] not in top[q]), (q, j)
+        assert live.cpu().numpy().tolist() == [n_item] * args.queries
+        res["mean_rank"] = float(got.mean())
+    elif args.leg == "host":
+        tiles = -(-n_item // 64)
+        ids = np.arange(n_item)
+
+        def round_trip():
+            dense = eng.recommend_domain(uids, 0, args.k, want_scores=True)[2]
+            out, atomics = [], 0
+            for q in range(args.queries):
+                row = dense[q]
+                for t in np.unique(targets[q]):
+                    before = (row > row[t]) | ((row == row[t]) & (ids < t))
+                    out.append(int(before.sum()))
+                    atomics += int(np.add.reduceat(before, np.arange(0, n_item, 64)).astype(bool).sum())
+            return out, atomics
+        for _ in range(2):
+            round_trip()
+        t0 = time.perf_counter()
+        for _ in range(args.reps):
+            _, atomics = round_trip()
+        res["ms"] = (time.perf_counter() - t0) / args.reps * 1e3
+        res["rank_atomics"], res["rank_atomics_bound"] = atomics, args.queries * args.targets * tiles
+        res["live_atomics"] = args.queries * tiles
+    elif args.leg == "recommend":
         d_uid, d_dom = torch.from_numpy(uids).to(eng.device), torch.from_numpy(doms).to(eng.device)
         out_i = torch.empty((args.queries, args.k), dtype=torch.int32, device=eng.device)
         out_s = torch.empty((args.queries, args.k), dtype=torch.float32, device=eng.device)
@@ -122,22 +174,48 @@ def main():
     ap.add_argument("--queries", type=int, default=512)
     ap.add_argument("--k", type=int, default=10)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--leg", default=None, choices=["recommend", "eval"])
+    ap.add_argument("--leg", default=None, choices=["recommend", "eval", "rank", "host"])
+    ap.add_argument("--rank", action="store_true", help="the mamdr_rank_domain comparison (module docstring)")
+    ap.add_argument("--targets", type=int, default=3)
     ap.add_argument("--leg-timeout", type=int, default=240)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recommend_bench.txt"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "rank_bench.txt" if args.rank else "recommend_bench.txt")
     if args.leg:
         return leg(args)
     got = {}
-    for name in ("recommend", "eval"):          # one child per leg, each under its own time limit; a failed leg ends the run
+    # one child per leg, each under its own time limit; a failed leg ends the run
+    for name in (("rank", "recommend", "host") if args.rank else ("recommend", "eval")):
         cmd = ["timeout", "-k", "10", str(args.leg_timeout), sys.executable, os.path.abspath(__file__), "--leg", name,
-               "--tower", args.tower, "--queries", str(args.queries), "--k", str(args.k), "--reps", str(args.reps)]
+               "--tower", args.tower, "--queries", str(args.queries), "--k", str(args.k), "--reps", str(args.reps),
+               "--targets", str(args.targets)] + (["--rank"] if args.rank else [])
         run = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True)
         lines = [l for l in run.stdout.splitlines() if l.startswith("RESULT ")]
         if run.returncode != 0 or not lines:
             sys.stderr.write(run.stdout[-2000:] + run.stderr[-4000:])
             raise SystemExit("leg %s failed (exit %d): nothing further is started" % (name, run.returncode))
         got[name] = json.loads(lines[-1][7:])
+    if args.rank:
+        a, b, c = got["rank"], got["recommend"], got["host"]
+        tiles = -(-a["items"] // 64)
+        text = ("%s  %s  tower %s  %d queries x %d items, %d targets per query, domain 0, %d reps (a, b: HIP events, 2 warm-up "
+                "calls; c: wall time, 2 warm-up rounds; a process per leg)\n"
+                "  a  mamdr_rank_domain                              %9.3f ms / call  (mean rank %.1f; link to top-128 checked on 8 queries)\n"
+                "  b  mamdr_recommend_domain(k = %d)                 %9.3f ms / call   a / b = %.3f\n"
+                "  c  recommend_domain(want_scores) + read-back + numpy ranks  %9.3f ms / round (wall)\n"
+                "  tiles: pre-pass %d pair tiles, grid %d x %d = %d scoring tiles (pre-pass share %.4f)\n"
+                "  integer atomics per call: ranks %d of at most %d (queries x targets x tiles, zero counts skipped; counted on "
+                "the host from the score matrix), live counts %d\n" % (
+                    time.strftime("%Y-%m-%d"), a["device"], args.tower, a["queries"], a["items"], a["targets"], a["reps"],
+                    a["ms"], a["mean_rank"], b["k"], b["ms"], a["ms"] / b["ms"], c["ms"],
+                    -(-a["queries"] * a["targets"] // 64), tiles, a["queries"], tiles * a["queries"],
+                    -(-a["queries"] * a["targets"] // 64) / float(tiles * a["queries"]),
+                    c["rank_atomics"], c["rank_atomics_bound"], c["live_atomics"]))
+        print(text)
+        with open(args.out, "a") as f:
+            f.write(text)
+        return
     r, e = got["recommend"], got["eval"]
     ratio = r["pairs_per_s"] / e["pairs_per_s"]
     text = ("%s  %s  tower %s  %d queries x %d items = %d pairs, K %d, %d reps (HIP events, 2 warm-up calls, a process per leg)\n"

@@ -377,6 +377,36 @@ int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_
                     const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
                     uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream);
 
+/* Gram matrices of up to MAMDR_GRAM_MAX_VEC flat fp32 vectors over column ranges, in fp64 -- the reduction behind the
+ * domain-conflict report (the cosines between the domains' gradients).  NO REFERENCE COUNTERPART: the reference argues
+ * that domains conflict and never measures it.  Stateless, any stream, no synchronisation, no allocation: the workspace
+ * is the caller's.
+ *   d_vecs, stride, n_vec, n_cols   vector i is d_vecs + i * stride, n_cols floats long; stride >= n_cols; n_vec in
+ *                                   [1, MAMDR_GRAM_MAX_VEC]; d_vecs 4-byte aligned (nothing wider is assumed)
+ *   h_off, h_count [n_range]        HOST arrays: range r is columns [h_off[r], h_off[r] + h_count[r]) inside [0, n_cols).
+ *                                   Ranges may overlap, may be empty and may start at any element
+ *   d_work, work_doubles            workspace of at least mamdr_gram_work(n_vec, h_off, h_count, n_range) doubles
+ *   d_out [n_range][n_vec][n_vec]   out[r][i][j] = sum over k in range r of (double) v_i[k] * (double) v_j[k]; the full
+ *                                   matrix is written, out[r][i][j] and out[r][j][i] are the same bits; an empty range
+ *                                   gives zeros
+ * Arithmetic.  Every product is formed in fp64 from the two fp32 values (48 significant bits: exact) and accumulated in
+ * fp64, on the f64 matrix cores.  No floating-point atomics.
+ * Reduction order.  Range r is cut, from ITS first column, into slabs of MAMDR_GRAM_SLAB columns; every slab's partial
+ * matrix goes to d_work; a second launch adds a range's partials in ascending slab order.  Inside a slab the order of k
+ * per output element is fixed.  The bits of d_out therefore depend on the values and the range table alone -- not on
+ * stride, on where the buffers sit, on their alignment or on the grid --, and a range of an overlapping request gets the
+ * bits it gets when asked for alone.  NaN and Inf propagate as IEEE: they reach their own vector's row and column only.
+ * MAMDR_EINVAL, with the argument named and nothing launched: n_vec outside [1, MAMDR_GRAM_MAX_VEC]; stride < n_cols; a
+ * range that is negative or leaves [0, n_cols); a null pointer; d_vecs not 4-byte, d_work or d_out not 8-byte aligned;
+ * work_doubles below mamdr_gram_work's answer.  mamdr_gram_work returns MAMDR_EINVAL for a bad n_vec or range table.
+ * (Added within ABI 19: new entry points only, no structure or existing call changed.) */
+#define MAMDR_GRAM_SLAB 16384
+#define MAMDR_GRAM_MAX_VEC 32
+int64_t mamdr_gram_work(int32_t n_vec, const int64_t* h_off, const int64_t* h_count, int32_t n_range);
+int mamdr_gram(const float* d_vecs, int64_t stride, int32_t n_vec, int64_t n_cols,
+               const int64_t* h_off, const int64_t* h_count, int32_t n_range,
+               double* d_work, int64_t work_doubles, double* d_out, void* stream);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

@@ -15,6 +15,7 @@ TOWER_MLP, TOWER_DEEPFM, TOWER_STAR, TOWER_WDL, TOWER_PNN, TOWER_NFM = 0, 1, 2, 
 SPLIT_TRAIN, SPLIT_VAL, SPLIT_TEST = 0, 1, 2
 OPT_ADAM, OPT_SGD, OPT_ACCUMULATE = 0, 1, 2
 MERGE_PLUS, MERGE_TIMES = 0, 1
+GRAM_SLAB, GRAM_MAX_VEC = 16384, 32         # MAMDR_GRAM_SLAB, MAMDR_GRAM_MAX_VEC (mamdr_gram)
 (SEG_USER_EMB, SEG_ITEM_EMB, SEG_DOMAIN_EMB, SEG_W0, SEG_W1, SEG_W2, SEG_B0, SEG_B1, SEG_B2, SEG_WO,
  SEG_GB, SEG_LIN_USER, SEG_LIN_ITEM, SEG_LIN_DOMAIN) = range(14)
 SEG_NAMES = ("user_emb", "item_emb", "domain_emb", "W0", "W1", "W2", "b0", "b1", "b2", "wo", "gb",
@@ -108,6 +109,8 @@ SIGNATURES = {
     "mamdr_recommend_domain": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
     "mamdr_rank_domain": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "mamdr_group_auc": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "mamdr_gram_work": (_I64, [_I32, _VP, _VP, _I32]),
+    "mamdr_gram": (C.c_int, [_VP, _I64, _I32, _I64, _VP, _VP, _I32, _VP, _I64, _VP, _VP]),
     "mamdr_interp": (C.c_int, [_VP, _VP, _VP, _F, _I64, _VP]),
     "mamdr_moving_average": (C.c_int, [_VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mamdr_merge": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP]),

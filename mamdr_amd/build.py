@@ -33,6 +33,8 @@ SOURCES = [
     # gauc_kernels: the fp64 terms are a division, a multiplication and additions as the host definition computes them
     # -> no fma fusion; its register / LDS / scratch report: profiles/gauc_bench.txt
     ("gauc_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
+    # gram_kernels: its register / LDS / scratch report: profiles/conflict_bench.txt
+    ("gram_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)
     ("mamdr_api.hip", []),
     ("step_context.hip", []),

@@ -11,10 +11,12 @@ Every tower name of the reference's registries is built (run.py:37-47; deepctr.p
 deepfm; deep_mtl_ctr.py:25-49: shared_bottom mmoe ple; star); Star in every form of star.py:70-96 -- norm none / pn / bn, dense dense / star, auxiliary_net); what is not (ple with more than one
 level, uncertainty weighting on the multi-task towers) raises NotImplementedError naming why.
 Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, and
---rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report).
+--rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report), and
+--conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report).
 """
 import argparse
 import json
+import os
 
 DEEP_CTR_LIST = ["mlp", "wdl", "nfm", "autoint", "ccpm", "pnn", "deepfm"]
 MTL_DEEP_CTR_LIST = ["shared_bottom", "mmoe", "ple"]
@@ -109,7 +111,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.rank_eval = [K,
     ...] (run.py --rank-eval; not a key of the reference's configs either): once the pipeline has ended, the exact rank of every
     test positive in its domain's whole catalogue, with MRR, mean percentile and HitRate / Recall / NDCG at those K
-    (recommend.rank_report), written under train.result_save_path."""
+    (recommend.rank_report), written under train.result_save_path.  train.conflict = N (run.py --conflict [N]; no key of the
+    reference's configs): once the pipeline has ended, the domain-conflict report (conflict.report) over N batches per domain
+    (0: whole passes), written to train.conflict_out or under train.result_save_path; result.json gains conflict_rate_all,
+    mean_cosine_all, conflict_rate_meta and mean_cosine_meta."""
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
     name = config["model"]["name"]
@@ -125,6 +130,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
         raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
                                   "(the best phi_d slots are current only on their owners); run it with one process and "
                                   "train.lanes = 1")
+    if config["train"].get("conflict") is not None and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.conflict (run.py --conflict): the domain-conflict report is not computed across processes "
+                                  "or lanes (one engine measures every domain's gradient at one point); run it with one process "
+                                  "and train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
     if lanes > 1:
         # (under N processes the lanes of every rank are a slice of ONE world of N * lanes participants: a rank's DR queries
@@ -161,12 +170,21 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
         print("Finetune: ")
         avg_loss, avg_auc, domain_loss, domain_auc = model.separate_train_val_test(init_parms=False)
     if rank == 0:
-        model.save_result(avg_loss, avg_auc, domain_loss, domain_auc)
+        saved = model.save_result(avg_loss, avg_auc, domain_loss, domain_auc)
         from . import recommend as rec
         if recommend:
             rec.report(model, int(recommend), recommend_out)
         if config["train"].get("rank_eval"):
             rec.rank_report(model, config["train"]["rank_eval"])
+        if config["train"].get("conflict") is not None:
+            from . import conflict
+            _, res = conflict.report(model, int(config["train"]["conflict"]), config["train"].get("conflict_out"))
+            path = os.path.join(saved, "result.json")        # (written by save_result above: the report runs after it)
+            with open(path) as f:
+                result = json.load(f)
+            result.update(conflict.headline(res))
+            with open(path, "w") as f:
+                json.dump(result, f)
     return avg_loss, avg_auc, domain_loss, domain_auc
 
 
@@ -185,6 +203,12 @@ def cli(argv=None):
     parser.add_argument("--rank-eval", type=str, default=None, nargs="?", const="10,50,200", metavar="KS",
                         help="after the run: the exact rank of every test positive in its domain's whole catalogue, with MRR, mean "
                              "percentile and HitRate / Recall / NDCG at the comma list KS (default 10,50,200) (train.rank_eval)")
+    parser.add_argument("--conflict", type=int, default=None, nargs="?", const=8, metavar="N",
+                        help="after the run: the domain-conflict report -- cosines between the domains' gradients over N batches "
+                             "per domain (default 8; 0: whole passes), per tensor, with the share of conflicting pairs "
+                             "(train.conflict)")
+    parser.add_argument("--conflict-out", type=str, default=None, metavar="FILE",
+                        help=".npz the domain-conflict report goes to (default: under train.result_save_path)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -194,6 +218,12 @@ def cli(argv=None):
         config["train"]["report_gauc"] = True
     if args.rank_eval is not None:
         config["train"]["rank_eval"] = [int(k) for k in args.rank_eval.split(",")]
+    if args.conflict is not None:
+        if args.conflict < 0:
+            parser.error("--conflict N: N batches per domain, 0 for whole passes")
+        config["train"]["conflict"] = args.conflict
+    if args.conflict_out is not None:
+        config["train"]["conflict_out"] = args.conflict_out
     if args.recommend is None:
         return main(config)
     return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

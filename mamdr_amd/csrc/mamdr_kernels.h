@@ -909,4 +909,22 @@ struct GaucArgs {
 int64_t gauc_parts(int64_t n_groups);
 void launch_gauc(const GaucArgs& a, hipStream_t s);
 
+// gram_kernels.hip: fp64 Gram matrices of up to GRAM_MAX_VEC flat vectors over column ranges (mamdr_gram).  One GramArgs
+// describes a batch of up to GRAM_MAX_RANGES ranges: two launches
+constexpr int GRAM_SLAB = 16384;      // columns per workgroup of k_gram_slab (= MAMDR_GRAM_SLAB)
+constexpr int GRAM_MAX_VEC = 32;
+constexpr int GRAM_MAX_RANGES = 64;
+struct GramArgs {
+    const float* vecs;             // vector i = vecs + i * stride
+    int64_t stride;
+    int n_vec, n_range;            // ranges of this batch
+    int64_t off[GRAM_MAX_RANGES], count[GRAM_MAX_RANGES];
+    int64_t first[GRAM_MAX_RANGES + 1];    // slabs of the batch before range r; first[n_range] = all of them
+    double* work;                  // [slabs of the call][n_vec][n_vec]
+    int64_t work_first;            // slabs of the call before this batch
+    double* out;                   // [ranges of the call][n_vec][n_vec]
+    int64_t out_first;             // ranges of the call before this batch
+};
+void launch_gram(const GramArgs& a, hipStream_t s);
+
 }  // namespace mamdr

@@ -5,7 +5,7 @@
 //   mamdr_api.hip       the training call: its decisions, CallPlan / plan_call, the three step functions, the pre-gather
 //                       entry points, mamdr_train_steps(_n)
 //   step_queries.hip    mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain), mamdr_group_auc
-//   step_stateless.hip  the outer updates, mamdr_adam_apply, mamdr_pcgrad_project, mamdr_copy, the shuffle
+//   step_stateless.hip  the outer updates, mamdr_adam_apply, mamdr_pcgrad_project, mamdr_copy, mamdr_gram, the shuffle
 // Helpers that one file uses stay static in it.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 // C ABI of libmamdr_hip.so, the entry points that hold no state of their own: the outer updates of the meta loops (the one
-// that advances a context's live weights among them), Adam on a caller's vectors, the PCGrad projection, the copy and the
-// host-side shuffle order.
+// that advances a context's live weights among them), Adam on a caller's vectors, the PCGrad projection, the copy, the fp64
+// Gram matrices (mamdr_gram) and the host-side shuffle order.
 #include <cmath>
 
 #include "step_ctx.h"
@@ -145,6 +145,66 @@ int mamdr_copy(float* d_dst, const float* d_src, int64_t n, void* stream) {
     if (n < 0) return fail(MAMDR_EINVAL, "negative length");
     if (n == 0) return MAMDR_OK;
     HIP_TRY(hipMemcpyAsync(d_dst, d_src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return MAMDR_OK;
+}
+
+// ---- fp64 Gram matrices of flat vectors over column ranges (gram_kernels.hip)
+static_assert(MAMDR_GRAM_SLAB == GRAM_SLAB && MAMDR_GRAM_MAX_VEC == GRAM_MAX_VEC, "include/mamdr_hip.h and mamdr_kernels.h agree");
+// the checks mamdr_gram_work and mamdr_gram share (n_cols < 0: the vectors' length is not known); *slabs = slabs of all ranges
+static int gram_check(const char* fn, int32_t n_vec, int64_t n_cols, const int64_t* h_off, const int64_t* h_count,
+                      int32_t n_range, int64_t* slabs) {
+    if (n_vec < 1 || n_vec > GRAM_MAX_VEC) return fail(MAMDR_EINVAL, "%s: n_vec %d outside [1, %d]", fn, n_vec, GRAM_MAX_VEC);
+    if (n_range < 0 || (n_range > 0 && (!h_off || !h_count)))
+        return fail(MAMDR_EINVAL, "%s: n_range %d / null h_off or h_count", fn, n_range);
+    *slabs = 0;
+    for (int32_t r = 0; r < n_range; ++r) {
+        if (h_off[r] < 0 || h_count[r] < 0 || h_count[r] > INT64_MAX - h_off[r] || (n_cols >= 0 && h_off[r] + h_count[r] > n_cols))
+            return fail(MAMDR_EINVAL, "%s: range %d (h_off %lld, h_count %lld) is negative or outside the %lld columns", fn, r,
+                        (long long)h_off[r], (long long)h_count[r], (long long)n_cols);
+        *slabs += (h_count[r] + GRAM_SLAB - 1) / GRAM_SLAB;
+    }
+    return MAMDR_OK;
+}
+int64_t mamdr_gram_work(int32_t n_vec, const int64_t* h_off, const int64_t* h_count, int32_t n_range) {
+    int64_t slabs = 0;
+    if (const int rc = gram_check("mamdr_gram_work", n_vec, -1, h_off, h_count, n_range, &slabs)) return rc;
+    return slabs * n_vec * n_vec;
+}
+int mamdr_gram(const float* d_vecs, int64_t stride, int32_t n_vec, int64_t n_cols, const int64_t* h_off, const int64_t* h_count,
+               int32_t n_range, double* d_work, int64_t work_doubles, double* d_out, void* stream) {
+    const char* fn = "mamdr_gram";
+    if (n_cols < 0 || stride < n_cols) return fail(MAMDR_EINVAL, "%s: n_cols %lld negative or above stride %lld", fn, (long long)n_cols, (long long)stride);
+    int64_t slabs = 0;
+    if (const int rc = gram_check(fn, n_vec, n_cols, h_off, h_count, n_range, &slabs)) return rc;
+    if (n_range == 0) return MAMDR_OK;
+    if (!d_out || ((uintptr_t)d_out & 7)) return fail(MAMDR_EINVAL, "%s: d_out is null or not 8-byte aligned", fn);
+    if (slabs > 0) {
+        if (!d_vecs || ((uintptr_t)d_vecs & 3)) return fail(MAMDR_EINVAL, "%s: d_vecs is null or not 4-byte aligned", fn);
+        if (work_doubles < slabs * n_vec * n_vec)
+            return fail(MAMDR_EINVAL, "%s: work_doubles %lld below the %lld of mamdr_gram_work", fn, (long long)work_doubles,
+                        (long long)(slabs * n_vec * n_vec));
+        if (!d_work || ((uintptr_t)d_work & 7)) return fail(MAMDR_EINVAL, "%s: d_work is null or not 8-byte aligned", fn);
+        if (slabs > 0x7fffffff) return fail(MAMDR_EINVAL, "%s: %lld slabs exceed one grid", fn, (long long)slabs);
+    }
+    GramArgs a;
+    memset(&a, 0, sizeof(a));
+    a.vecs = d_vecs;
+    a.stride = stride;
+    a.n_vec = n_vec;
+    a.work = d_work;
+    a.out = d_out;
+    for (int32_t r0 = 0; r0 < n_range; r0 += GRAM_MAX_RANGES) {
+        a.n_range = std::min<int32_t>(GRAM_MAX_RANGES, n_range - r0);
+        a.out_first = r0;
+        for (int r = 0; r < a.n_range; ++r) {
+            a.off[r] = h_off[r0 + r];
+            a.count[r] = h_count[r0 + r];
+            a.first[r + 1] = a.first[r] + (a.count[r] + GRAM_SLAB - 1) / GRAM_SLAB;
+        }
+        launch_gram(a, (hipStream_t)stream);
+        a.work_first += a.first[a.n_range];
+    }
+    HIP_TRY(hipGetLastError());
     return MAMDR_OK;
 }
 

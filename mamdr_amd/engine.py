@@ -177,6 +177,37 @@ class FlatVectorOps(object):
         cols = (C.c_int32 * n)(*[t[2] for t in tensors])
         L.check(self.lib.mamdr_pcgrad_project(_ptr(final), _ptr(aux), offs, rows, cols, n, self._s()))
 
+    # ---- fp64 Gram matrices of flat vectors (mamdr_gram; no reference counterpart)
+    _gram_work = None       # the slab partials' workspace: kept by the engine, grown on demand
+
+    def gram(self, vecs, ranges):
+        """fp64 Gram matrices of the rows of `vecs` -- a 2-D fp32 device tensor [D, n], D <= 32, unit stride along a row,
+        any stride between rows -- over `ranges` = [(offset, count)] inside [0, n): overlapping, empty and unaligned ranges
+        are fine.  -> float64 device tensor [len(ranges), D, D], out[r, i, j] = sum_k double(v_i[k]) * double(v_j[k]) over
+        range r: symmetric bit for bit, and the same bits for the same values and ranges wherever the rows sit
+        (include/mamdr_hip.h: mamdr_gram).  Nothing is read back."""
+        if vecs.dim() != 2 or vecs.dtype != torch.float32 or not vecs.is_cuda or (vecs.shape[1] > 1 and vecs.stride(1) != 1):
+            raise ValueError("gram: vecs must be a 2-D fp32 device tensor with unit stride along its rows")
+        D, n = int(vecs.shape[0]), int(vecs.shape[1])
+        stride = int(vecs.stride(0)) if D > 1 else n
+        if not 1 <= D <= L.GRAM_MAX_VEC or stride < n:
+            raise ValueError("gram: %d vectors (1 to %d), row stride %d for %d columns" % (D, L.GRAM_MAX_VEC, stride, n))
+        R = len(ranges)
+        offs = (C.c_int64 * max(R, 1))(*[int(r[0]) for r in ranges])
+        cnts = (C.c_int64 * max(R, 1))(*[int(r[1]) for r in ranges])
+        for o, c in zip(offs[:R], cnts[:R]):
+            if o < 0 or c < 0 or o + c > n:
+                raise ValueError("gram: range [%d, %d) outside the %d columns" % (o, o + c, n))
+        need = int(self.lib.mamdr_gram_work(D, offs, cnts, R))
+        if need < 0:
+            L.check(need)
+        if self._gram_work is None or self._gram_work.numel() < need:
+            self._gram_work = torch.empty(max(need, 1), dtype=torch.float64, device=vecs.device)
+        out = torch.empty((R, D, D), dtype=torch.float64, device=vecs.device)
+        L.check(self.lib.mamdr_gram(_ptr(vecs), stride, D, n, offs, cnts, R, _ptr(self._gram_work), self._gram_work.numel(),
+                                    _ptr(out), self._s()))
+        return out
+
 
 # Keras variable names of the step engine's segments, for the reference's substring filters (maml.py:153-179)
 KERAS_NAMES = {"Ws0": "kernel_shared_0", "Ws1": "kernel_shared_1", "Ws2": "kernel_shared_2",
@@ -480,6 +511,64 @@ class DeviceEngine(FlatVectorOps):
     def optimizer_reset(self):
         self._check(self._c_optimizer_reset(self.ctx))
 
+    # ------------------------------------------------------------ per-domain gradients (no reference counterpart)
+    def counters(self):
+        """(Adam steps taken, position of the dropout stream): what set_counters restores."""
+        return (int(getattr(self.lib, self.PREFIX + "optimizer_steps")(self.ctx)),
+                int(getattr(self.lib, self.PREFIX + "dropout_steps")(self.ctx)))
+
+    def domain_gradients(self, domains, n_batches=None, out=None):
+        """the gradient of the total loss (L2 terms included, dropout off) at the live weights, one row per domain: row j of
+        the result [len(domains), n_params] is the SUM over the first `n_batches` batches (None: the whole pass) of
+        domains[j]'s train split, in file order -- exactly what that many MAMDR_OPT_ACCUMULATE steps add to a zeroed
+        accumulator, plain sums even after set_moving_average.  -> (rows: fp32 device tensor, a view of `out` when given;
+        steps: the batches behind each row).  `out`: a 2-D fp32 device tensor of that shape whose rows start 16-byte
+        aligned (the result of an earlier call serves); it is zeroed here.
+        Everything else stays as it was: weights, Adam slots, the Adam step count with its beta powers, the dropout stream's
+        position (accumulate steps advance it: put back with set_counters), the aux buffer (a norm layer's moving
+        statistics), the bound accumulator and the moving average's hidden state.  On the step engine a window of passes
+        gathered ahead (`pregather`) is gathered again afterwards: the accumulate calls are not part of it."""
+        domains = [int(d) for d in domains]
+        stride = (self.n_params + 3) // 4 * 4           # every row is an accumulator: 16-byte aligned
+        if out is None:
+            out = torch.empty((max(len(domains), 1), stride), dtype=torch.float32, device=self.device)[:len(domains), :self.n_params]
+        elif (out.dim() != 2 or tuple(out.shape) != (len(domains), self.n_params) or out.dtype != torch.float32 or
+              (self.n_params > 1 and out.stride(1) != 1) or out.data_ptr() % 16 or (len(domains) > 1 and out.stride(0) % 4)):
+            raise ValueError("domain_gradients: out must be an fp32 device tensor [%d, %d] with 16-byte aligned rows"
+                             % (len(domains), self.n_params))
+        steps = []
+        for d in domains:
+            total = -(-self.n_rows(d, "train") // self.batch_size)
+            steps.append(total if n_batches is None else min(int(n_batches), total))
+        opt_steps, drop_steps = self.counters()
+        aux = self.aux.clone() if self.aux is not None else None
+        acc, ema = self._acc, self._ema
+        self._ema = None                                # plain sums: the moving average and its hidden state stay out of it
+        try:
+            for j, d in enumerate(domains):
+                row = out[j]
+                row.zero_()
+                self._acc = row
+                self._check(self._c_bind_accumulator(self.ctx, _ptr(row)))
+                if steps[j]:
+                    self.train_steps(d, n_steps=steps[j], optimizer="accumulate")
+        finally:
+            self._ema, self._acc = ema, acc
+            if acc is not None:
+                self.bind_accumulator(acc)
+            elif self.GRAPH:
+                self._check(self._c_bind_accumulator(self.ctx, _ptr(None)))        # none was bound: none is now
+            else:
+                self._grad_rows = out       # (the step engine cannot unbind: the last row stays bound, and alive)
+            if aux is not None:
+                self.aux.copy_(aux)
+            self.set_counters(opt_steps, drop_steps)
+            self._after_domain_gradients()
+        return out, np.asarray(steps, np.int64)
+
+    def _after_domain_gradients(self):
+        pass
+
 
 class TowerEngine(DeviceEngine):
     PREFIX, KERAS_NAMES = "mamdr_", KERAS_NAMES
@@ -625,6 +714,7 @@ class TowerEngine(DeviceEngine):
         None[, pass_rows])] -- in this order; where a call would gather its pass's rows itself (frozen tables, fused
         step path) the library gathers them all in one launch now.  Same rows, same bits; a no-op elsewhere."""
         n = len(passes)
+        self._window = (list(passes), batch_size) if n else None       # (keeps the permutations alive: _after_domain_gradients)
         if n == 0:                 # forget an earlier hint
             L.check(self.lib.mamdr_pregather_passes(self.ctx, 0, None, None, None, int(batch_size or self.batch_size)))
             return
@@ -632,6 +722,14 @@ class TowerEngine(DeviceEngine):
         perms = (C.c_void_p * n)(*[(p[1].data_ptr() if p[1] is not None else None) for p in passes])
         rows = (C.c_int64 * n)(*[(-1 if len(p) < 3 or p[2] is None else int(p[2])) for p in passes])
         L.check(self.lib.mamdr_pregather_passes(self.ctx, n, doms, perms, rows, int(batch_size or self.batch_size)))
+
+    _window = None
+
+    def _after_domain_gradients(self):
+        """the accumulate calls of domain_gradients are no part of an announced window and made the library drop it: the
+        window is announced -- and gathered -- again, so the passes that follow find their rows as before."""
+        if self._window is not None:
+            self.pregather(*self._window)
 
     def pregather_ahead(self, passes, batch_size=None, spread_steps=0):
         """hint (mamdr_pregather_ahead): `passes` is the window AFTER the current one -- the list the next `pregather`

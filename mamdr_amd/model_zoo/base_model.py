@@ -166,6 +166,14 @@ class BaseModel(object):
         res.update(users=users, catalogue=catalogue, n_positives=np.diff(res["offsets"]).astype(np.int64))
         return res
 
+    # ------------------------------------------------------------------ domain conflict (no reference counterpart)
+    def domain_conflict(self, n_batches=None):
+        """conflict.measure at the live weights: one gradient per train domain over its first `n_batches` batches (None or 0:
+        whole passes), their fp64 Gram matrices over the whole flat vector, the meta range and every tensor, the cosines
+        and their summaries.  The engine's state is left as it was (engine.domain_gradients)."""
+        from .. import conflict
+        return conflict.measure(self.model, sorted(self.dataset.train_dataset), n_batches)
+
     # ------------------------------------------------------------------ finetune / separate training
     def separate_train_val_test(self, init_parms=True):
         """base_model.py:41-109.  init_parms=False is the finetune stage: plain SGD with

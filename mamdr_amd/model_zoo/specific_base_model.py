@@ -121,6 +121,20 @@ class SpecificBase(MAML):
         finally:
             self.model.set_weights(live)
 
+    def domain_conflict(self, n_batches=None):
+        """BaseModel.domain_conflict at the best theta ALONE -- the shared point that Domain Negotiation negotiates, without
+        any domain's phi_d: it is assigned to the meta parameters for the call and the previous live flat vector is put
+        back afterwards, bit for bit (as rank_eval does with theta (+|*) phi_d).  Before the first snapshot the live weights
+        are measured."""
+        if self.best_shared_weights is None:
+            return self.base_model.domain_conflict(n_batches)
+        live = self.model.get_weights().clone()
+        self._set_model_meta_parms(self.best_shared_weights.clone())
+        try:
+            return self.base_model.domain_conflict(n_batches)
+        finally:
+            self.model.set_weights(live)
+
     def separate_train_val_test(self, init_parms=True):
         if init_parms:
             return self.base_model.separate_train_val_test(init_parms=True)

@@ -18,6 +18,7 @@ Both carry l2_reg_embedding 1e-5 on the three tables.  Tensor names follow oracl
 """
 import numpy as np
 
+from . import rng
 from . import tower as T
 
 F32 = np.float32
@@ -67,20 +68,22 @@ def forward(P, kind, uid, pid, dom, masks=None, keep_scale=F32(1)):
     return T.sigmoid(logit), hs, x
 
 
-def reg_loss(P, kind, frozen_sumsq=None):
-    r = T.reg_loss(P, frozen_sumsq, False)
+def reg_loss(P, kind, frozen_sumsq=None, l2=None):
+    """l2 = (l2_emb, l2_linear) as oracle/tower.reg_loss; None: deepctr's defaults."""
+    r = T.reg_loss(P, frozen_sumsq, False, l2)
     if kind == "nfm":
+        l2_lin = T.L2_LIN if l2 is None else F32(l2[1])
         for n in ("lin_user", "lin_item", "lin_domain"):
-            r = F32(r + T.L2_LIN * T.table_sumsq(P[n]))
+            r = F32(r + l2_lin * T.table_sumsq(P[n]))
     return F32(r)
 
 
-def loss_and_grads(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, frozen_sumsq=None, uncertainty=False):
+def loss_and_grads(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, frozen_sumsq=None, uncertainty=False, l2=None):
     """uncertainty (model_zoo/uncertainty_weight/weighted_loss.py:30-43, as oracle/tower.loss_and_grads): loss =
     mean(BCE) / var^2 + log var + regularisers, var = log_var[domain of the batch's first row]."""
     B = uid.shape[0]
     E = P["domain_emb"].shape[1]
-    keep_scale = F32(1.0 / (1.0 - rate)) if masks is not None else F32(1)
+    keep_scale = rng.keep_scale(rate) if masks is not None else F32(1)
     p, hs, x = forward(P, kind, uid, pid, dom, masks, keep_scale)
     y = label.astype(F32)
     mean_bce = F32(np.mean(T.bce_per_row(p, y), dtype=np.float64))
@@ -91,12 +94,12 @@ def loss_and_grads(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, fr
         d0 = int(dom[0])
         var = P["log_var"][d0]
         w = F32(F32(1) / F32(var * var))
-        loss = F32(w * mean_bce) + F32(np.log(var, dtype=F32)) + reg_loss(P, kind, frozen_sumsq)
+        loss = F32(w * mean_bce) + F32(np.log(var, dtype=F32)) + reg_loss(P, kind, frozen_sumsq, l2)
         dlogit = (dlogit * w).astype(F32)
         g["log_var"] = np.zeros_like(P["log_var"])
         g["log_var"][d0] = F32(F32(-2) * mean_bce / F32(var * var * var)) + F32(F32(1) / var)
     else:
-        loss = mean_bce + reg_loss(P, kind, frozen_sumsq)
+        loss = mean_bce + reg_loss(P, kind, frozen_sumsq, l2)
     g["wo"] = (hs[3].T @ dlogit[:, None]).astype(F32)
     g["gb"] = np.array([np.sum(dlogit, dtype=np.float64)], F32)
     dh = (dlogit[:, None] * P["wo"][:, 0][None, :]).astype(F32)
@@ -108,7 +111,7 @@ def loss_and_grads(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, fr
     u, i, d = x[:, :E], x[:, E:2 * E], x[:, 2 * E:]
     if kind == "nfm":
         dx = np.concatenate([dh * (i + d), dh * (u + d), dh * (u + i)], axis=1).astype(F32)
-        two_l2_lin = F32(2) * T.L2_LIN
+        two_l2_lin = F32(2) * (T.L2_LIN if l2 is None else F32(l2[1]))
         gl = np.bincount(dom, weights=dlogit.astype(np.float64), minlength=P["lin_domain"].shape[0])
         g["lin_domain"] = (gl.astype(F32) + two_l2_lin * P["lin_domain"]).astype(F32)
         if emb_trainable:
@@ -123,7 +126,7 @@ def loss_and_grads(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, fr
         dx[:, E:2 * E] += dip[:, 0:1] * u + dip[:, 2:3] * d
         dx[:, 2 * E:] += dip[:, 1:2] * u + dip[:, 2:3] * i
         dx = dx.astype(F32)
-    two_l2 = F32(2) * T.L2_EMB
+    two_l2 = F32(2) * (T.L2_EMB if l2 is None else F32(l2[0]))
     onehot = (dom[:, None] == np.arange(P["domain_emb"].shape[0])[None, :]).astype(np.float64)
     g["domain_emb"] = ((onehot.T @ dx[:, 2 * E:].astype(np.float64)).astype(F32) + two_l2 * P["domain_emb"]).astype(F32)
     if emb_trainable:
@@ -140,8 +143,11 @@ class OracleNet(T.OracleModel):
     """OracleModel with the NFM / PNN forward and gradients (same optimiser, weights in / out, passes)."""
 
     def __init__(self, params, kind, emb_trainable=False, dropout=0.5, lr=1e-3, hidden=(256, 128, 64), dropout_seed=1024,
-                 uncertainty=False):
+                 uncertainty=False, l2=None):
         T.OracleModel.__init__(self, params, emb_trainable, dropout, lr, hidden, dropout_seed, "mlp", False)
+        if l2 is not None:          # (l2_emb, l2_linear); None: deepctr's defaults, the constants of oracle/tower.py
+            self.l2 = (F32(l2[0]), F32(l2[1]))
+            self.l2_emb, self.l2_linear = float(l2[0]), float(l2[1])
         self.kind = kind
         self.conv = kind in ("ccpm", "autoint")
         self.uncertainty = bool(uncertainty)
@@ -155,10 +161,10 @@ class OracleNet(T.OracleModel):
         masks = T.train_masks(self.seed, self.step, B, self.hidden, self.rate) if self.rate > 0 else None
         if self.conv:
             loss, g, _ = loss_and_grads_conv(self.params, self.kind, uid, pid, dom, label, masks, self.rate, self.emb_trainable,
-                                             self.frozen_sumsq(), self.uncertainty)
+                                             self.frozen_sumsq(), self.uncertainty, self.l2)
         else:
             loss, g, _ = loss_and_grads(self.params, self.kind, uid, pid, dom, label, masks, self.rate, self.emb_trainable,
-                                        self.frozen_sumsq(), self.uncertainty)
+                                        self.frozen_sumsq(), self.uncertainty, self.l2)
         if self.use_sgd:
             self.opt.sgd(self.params, g, self.lr)
         else:
@@ -171,10 +177,10 @@ class OracleNet(T.OracleModel):
         total loss at the current weights added to `acc`, learning phase 0 (dropout off), no update."""
         if self.conv:
             _, g, _ = loss_and_grads_conv(self.params, self.kind, uid, pid, dom, label, None, 0.0, self.emb_trainable,
-                                          self.frozen_sumsq(), self.uncertainty)
+                                          self.frozen_sumsq(), self.uncertainty, self.l2)
         else:
             _, g, _ = loss_and_grads(self.params, self.kind, uid, pid, dom, label, None, 0.0, self.emb_trainable,
-                                     self.frozen_sumsq(), self.uncertainty)
+                                     self.frozen_sumsq(), self.uncertainty, self.l2)
         if getattr(self, "moving_average", None) is not None:
             from . import outer
             ma = self.moving_average
@@ -188,7 +194,7 @@ class OracleNet(T.OracleModel):
 
     def evaluate(self, data, batch_size):
         n = data["uid"].shape[0]
-        reg = reg_loss(self.params, "nfm" if self.conv else self.kind, self.frozen_sumsq())
+        reg = reg_loss(self.params, "nfm" if self.conv else self.kind, self.frozen_sumsq(), self.l2)
         batch_losses, preds = [], np.empty(n, F32)
         for s in range(0, n, batch_size):
             sl = slice(s, min(n, s + batch_size))
@@ -354,10 +360,11 @@ def forward_conv(P, kind, uid, pid, dom, masks=None, keep_scale=F32(1)):
     return T.sigmoid(logit), c
 
 
-def loss_and_grads_conv(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, frozen_sumsq=None, uncertainty=False):
+def loss_and_grads_conv(P, kind, uid, pid, dom, label, masks, rate, emb_trainable, frozen_sumsq=None, uncertainty=False,
+                        l2=None):
     B = uid.shape[0]
     E = P["domain_emb"].shape[1]
-    keep_scale = F32(1.0 / (1.0 - rate)) if masks is not None else F32(1)
+    keep_scale = rng.keep_scale(rate) if masks is not None else F32(1)
     p, c = forward_conv(P, kind, uid, pid, dom, masks, keep_scale)
     y = label.astype(F32)
     mean_bce = F32(np.mean(T.bce_per_row(p, y), dtype=np.float64))
@@ -368,12 +375,12 @@ def loss_and_grads_conv(P, kind, uid, pid, dom, label, masks, rate, emb_trainabl
         d0 = int(dom[0])
         var = P["log_var"][d0]
         w = F32(F32(1) / F32(var * var))
-        loss = F32(w * mean_bce) + F32(np.log(var, dtype=F32)) + reg_loss(P, "nfm", frozen_sumsq)
+        loss = F32(w * mean_bce) + F32(np.log(var, dtype=F32)) + reg_loss(P, "nfm", frozen_sumsq, l2)
         dlogit = (dlogit * w).astype(F32)
         g["log_var"] = np.zeros_like(P["log_var"])
         g["log_var"][d0] = F32(F32(-2) * mean_bce / F32(var * var * var)) + F32(F32(1) / var)
     else:
-        loss = mean_bce + reg_loss(P, "nfm", frozen_sumsq)
+        loss = mean_bce + reg_loss(P, "nfm", frozen_sumsq, l2)
     g["wo"] = (c["top"].T @ dlogit[:, None]).astype(F32)
     g["gb"] = np.array([np.sum(dlogit, dtype=np.float64)], F32)
     dtop = (dlogit[:, None] * P["wo"][:, 0][None, :]).astype(F32)
@@ -392,10 +399,10 @@ def loss_and_grads_conv(P, kind, uid, pid, dom, label, masks, rate, emb_trainabl
         for l in range(ATT_LAYERS - 1, -1, -1):
             dX, g["att%d_w" % l] = att_layer_backward(P["att%d_w" % l], c["att"][l], dX)
         dx = (dx + dX.reshape(B, 3 * E)).astype(F32)
-    two_l2_lin = F32(2) * T.L2_LIN
+    two_l2_lin = F32(2) * (T.L2_LIN if l2 is None else F32(l2[1]))
     gl = np.bincount(dom, weights=dlogit.astype(np.float64), minlength=P["lin_domain"].shape[0])
     g["lin_domain"] = (gl.astype(F32) + two_l2_lin * P["lin_domain"]).astype(F32)
-    two_l2 = F32(2) * T.L2_EMB
+    two_l2 = F32(2) * (T.L2_EMB if l2 is None else F32(l2[0]))
     onehot = (dom[:, None] == np.arange(P["domain_emb"].shape[0])[None, :]).astype(np.float64)
     g["domain_emb"] = ((onehot.T @ dx[:, 2 * E:].astype(np.float64)).astype(F32) + two_l2 * P["domain_emb"]).astype(F32)
     if emb_trainable:

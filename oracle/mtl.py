@@ -182,13 +182,14 @@ def train_masks(spec, seed, step, n_rows, rate):
     return {n: rng.dropout_mask(seed, step, k, n_rows, shapes[n][1], rate) for n, k in ids.items()}
 
 
-def loss_and_grads(P, spec, d, uid, pid, dom, label, masks, rate, emb_trainable, frozen_sumsq=None):
-    """one batch of task d: total loss (mean BCE + regularisers) and the gradients of every tensor on the path."""
+def loss_and_grads(P, spec, d, uid, pid, dom, label, masks, rate, emb_trainable, frozen_sumsq=None, l2=None):
+    """one batch of task d: total loss (mean BCE + regularisers) and the gradients of every tensor on the path.
+    l2 = (l2_emb, l2_linear) as oracle/tower.reg_loss (these towers have no linear tables); None: deepctr's defaults."""
     B = uid.shape[0]
-    keep_scale = F32(1.0 / (1.0 - rate)) if masks is not None else F32(1)
+    keep_scale = rng.keep_scale(rate) if masks is not None else F32(1)
     p, c = forward(P, spec, d, uid, pid, dom, masks, keep_scale)
     y = label.astype(F32)
-    loss = F32(np.mean(T.bce_per_row(p, y), dtype=np.float64)) + T.reg_loss(P, frozen_sumsq)
+    loss = F32(np.mean(T.bce_per_row(p, y), dtype=np.float64)) + T.reg_loss(P, frozen_sumsq, False, l2)
     inside = ((p >= T.EPS_CLIP) & (p <= F32(1) - T.EPS_CLIP)).astype(F32)
     dlogit = ((p - y) * inside / F32(B)).astype(F32)
     g = {}
@@ -215,7 +216,7 @@ def loss_and_grads(P, spec, d, uid, pid, dom, label, masks, rate, emb_trainable,
         e = mix[0]
         dx = (dx + dnn_backward(P, e, spec.expert_hidden, c["x"], c["experts"][e][1], dm, keep_scale, g)).astype(F32)
     E = spec.emb_dim
-    two_l2 = F32(2) * T.L2_EMB
+    two_l2 = F32(2) * (T.L2_EMB if l2 is None else F32(l2[0]))
     onehot = (dom[:, None] == np.arange(spec.D)[None, :]).astype(np.float64)
     g["domain_emb"] = ((onehot.T @ dx[:, 2 * E:3 * E].astype(np.float64)).astype(F32) + two_l2 * P["domain_emb"]).astype(F32)
     if emb_trainable:
@@ -231,7 +232,7 @@ def loss_and_grads(P, spec, d, uid, pid, dom, label, masks, rate, emb_trainable,
 class OracleMTL(object):
     """stand-in for the D compiled Keras models over one set of variables and ONE Adam optimizer object."""
 
-    def __init__(self, params, spec, emb_trainable=False, dropout=0.5, lr=1e-4, dropout_seed=1024):
+    def __init__(self, params, spec, emb_trainable=False, dropout=0.5, lr=1e-4, dropout_seed=1024, l2=None):
         self.params, self.spec = params, spec
         self.emb_trainable = emb_trainable
         self.names = [n for n, _ in spec.tensors(emb_trainable, params["user_emb"].shape[0], params["item_emb"].shape[0])]
@@ -242,6 +243,7 @@ class OracleMTL(object):
         self.step = 0
         self.use_sgd = False
         self._frozen = None
+        self.l2 = None if l2 is None else (F32(l2[0]), F32(l2[1]))
 
     def get_flat(self):
         return T.flatten(self.params, self.names)
@@ -261,7 +263,7 @@ class OracleMTL(object):
         B = uid.shape[0]
         masks = train_masks(self.spec, self.seed, self.step, B, self.rate) if self.rate > 0 else None
         loss, g, _ = loss_and_grads(self.params, self.spec, d, uid, pid, dom, label, masks, self.rate,
-                                    self.emb_trainable, self.frozen_sumsq())
+                                    self.emb_trainable, self.frozen_sumsq(), self.l2)
         if self.use_sgd:
             for n, gr in g.items():
                 self.params[n] -= (gr * F32(self.lr)).astype(F32)
@@ -294,7 +296,7 @@ class OracleMTL(object):
     def evaluate(self, d, data, batch_size):
         """domain_model_dict[d].evaluate (deep_mtl_ctr.py:207): mean over batches of the batch-mean loss (+ reg)."""
         n = data["uid"].shape[0]
-        reg = T.reg_loss(self.params, self.frozen_sumsq())
+        reg = T.reg_loss(self.params, self.frozen_sumsq(), False, self.l2)
         batch_losses, preds = [], np.empty(n, F32)
         for s in range(0, n, batch_size):
             sl = slice(s, min(n, s + batch_size))

@@ -7,6 +7,11 @@ arithmetic:
 
 * dropout keep-mask: one 32-bit hash per (seed, step, layer, row, col)
   -- mirrors mamdr_amd/csrc/mamdr_device.h `mamdr_dropout_u32`.
+* dropout scalars: the rate crosses the C ABI as a `float` (mamdr_config.dropout), so the threshold and the keep
+  scale are derived HERE from `np.float32(rate)`, in double, as mamdr_train_steps_n / mamdr_graph_train_steps_n
+  derive them: threshold = trunc(float32(rate) * 2^32) clamped to uint32, keep scale = float32(1 / (1 - float32(rate))).
+  For a rate float32 holds exactly (0.5, 0.25, 0.75) this is what the Python double gives; for 0.1 it is 429496736,
+  not int(0.1 * 2^32) = 429496729.
 * shuffle buffer: tf.data `shuffle(buffer_size)` semantics
   (utils/dataset.py:27-37: shuffle_buffer_size=10000, reshuffled every pass),
   driven by splitmix64 -- mirrors mamdr_amd/csrc/mamdr_host.cpp
@@ -49,10 +54,20 @@ def dropout_u32(seed, step, layer, n_rows, n_cols):
         return fmix32(key + np.uint32(GOLDEN) * e)
 
 
+def abi_rate(rate):
+    """the rate the library receives: the config's value rounded to float32, as a Python double."""
+    return float(np.float32(rate))
+
+
 def dropout_threshold(rate):
     """keep iff u >= threshold; P(keep) = 1 - rate."""
-    t = int(float(rate) * 4294967296.0)
+    t = int(abi_rate(rate) * 4294967296.0)
     return np.uint32(min(max(t, 0), 0xFFFFFFFF))
+
+
+def keep_scale(rate):
+    """1 / P(keep) as the float32 the kernels multiply by."""
+    return np.float32(1.0 / (1.0 - abi_rate(rate)))
 
 
 def dropout_mask(seed, step, layer, n_rows, n_cols, rate):

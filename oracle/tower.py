@@ -190,7 +190,7 @@ def loss_and_grads(params, uid, pid, dom, label, masks, rate, emb_trainable, fro
     uncertainty (weighted_loss.py:30-43): loss = mean(BCE / var^2 + log var) + regularisers with
     var = log_var[domain of the batch's first row]."""
     B = uid.shape[0]
-    keep_scale = F32(1.0 / (1.0 - rate)) if masks is not None else F32(1)
+    keep_scale = rng.keep_scale(rate) if masks is not None else F32(1)
     p, hs = forward(params, uid, pid, dom, masks, keep_scale, deepfm)
     y = label.astype(F32)
     mean_bce = F32(np.mean(bce_per_row(p, y), dtype=np.float64))

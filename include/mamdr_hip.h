@@ -340,6 +340,54 @@ int mamdr_rank_domain(mamdr_ctx* ctx, int32_t domain, int32_t n_query, const int
                       const int64_t* d_tgt_off, const int32_t* d_tgt_ids,
                       int32_t* d_rank_out, float* d_score_out, int32_t* d_live_out);
 
+/* Per-query candidate slates scored and ordered, every query of the call in ONE domain, from the live weights of an mlp /
+ * wdl / deepfm / star tower.  NO REFERENCE COUNTERPART, as mamdr_recommend.  The three calls above share one candidate list
+ * among all queries of a call; here every query brings its own list -- the ranking stage behind a retrieval stage, and the
+ * sampled-negatives evaluation protocol (each held-out positive among N sampled items) -- and the work is one pair per
+ * entry, sum of the slates' lengths, not n_query x |union of the slates|.
+ *   domain, n_query, d_uid     mamdr_rank_domain's
+ *   d_slate_off [n_query + 1]  int64 offsets ascending from 0 (checked: the call reads them back, its one synchronisation of
+ *                              the context's stream)
+ *   d_slate_ids [n entries]    the item ids of slate q at [d_slate_off[q], d_slate_off[q + 1]), in any order, DISTINCT within
+ *                              a slate (not checked) and inside [0, n_item) (ids outside are clamped: range-check on the
+ *                              host).  A slate may be empty; so may the whole call, which then returns MAMDR_OK and writes
+ *                              nothing
+ *   d_pos_out [n entries]      int32, see Position
+ *   d_score_out                optional [n entries], see Score
+ *   d_order_out                optional [n entries] int32, see Order
+ * key(q, x) is the 64-bit ranking key of the family: (order-preserving bits of the logit << 32) | ~id, so a larger key is
+ * a higher logit or an equal logit and a smaller item id; -0 counts as +0; a NaN logit is behind every number.
+ * Position.  d_pos_out[j], for entry j of slate q, is the number of entries of the same slate whose key is strictly
+ *   greater.  With distinct ids the positions of a slate of L entries are a permutation of 0 .. L - 1.
+ * Score.  d_score_out[j] = sigmoid(logit) of the pair: the bits mamdr_rank_domain's d_score_out and
+ *   mamdr_recommend_domain's d_scores_all hold for that (user, item, domain).
+ * Order.  d_order_out[d_slate_off[q] + d_pos_out[j]] = j - d_slate_off[q]: the slate-local index of the entry at each
+ *   position.  The call fills the array with -1 first; with distinct ids no -1 remains.  Duplicate ids share a position:
+ *   which of them claims the slot is unspecified, and the slots nobody claims keep -1.
+ * Per block of 256 queries: the query terms, then -- a workspace's worth of entries at a time -- mamdr_rank_domain's target
+ * pre-pass over the block's entries (the entries' item term, then 64 consecutive entries per workgroup through the layers
+ * and the head of the scoring tile: the keys are the bits the grid computes for the same pair), then k_slate_order: one
+ * wave per slate of up to 64 entries, one workgroup per 256 entries of a longer slate with the slate's keys staged through
+ * LDS 1,024 at a time; every entry counts the keys of its slate above its own.  That is O(L^2) integer compares per
+ * slate, ON PURPOSE: slates are short (tens to a few thousand entries); ordering a whole catalogue stays
+ * mamdr_rank_domain's job.  An item that sits in several slates has its item term formed once per slate.  The grid of the
+ * longer slates' launch is ceil(longest slate of the block / 256) x the block's queries, and workgroups without entries leave
+ * at once: a block whose slates are of very unequal lengths launches many that do no work.
+ * Determinism: the ordering uses integers only and no atomics, every output word is written by one thread; the bits do not
+ * depend on MAMDR_REC_CHUNK, on neighbouring queries, or on the order of the entries inside a slate.
+ * Reads the state only, as mamdr_rank_domain: tables and lazily replayed slices are brought up to date first, the star
+ * tower's effective block and PartitionedNorm workspace are built for `domain` in inference mode; weights, Adam slots,
+ * counters and gathered windows are untouched.  The keys live in a workspace of the context, grown on demand.
+ * Under mamdr_profile_enable the call's phases land in three slots: the entries' item term in MAMDR_KERNEL_GATHER, the pair
+ * tiles in MAMDR_KERNEL_EVAL and k_slate_order in MAMDR_KERNEL_AUX (the query terms are not timed).
+ * MAMDR_EINVAL: a null d_uid, d_slate_off or d_pos_out; d_slate_ids null while entries exist; a misaligned pointer; domain
+ * outside [0, n_domain); n_query <= 0; offsets that do not start at 0 or descend, or a slate of more than 2^31 - 1 entries.
+ * MAMDR_ESTATE: as mamdr_recommend; MAMDR_ENOTBUILT: the pnn / nfm towers.  (Added within ABI 19: a new entry point only,
+ * no structure or existing call changed.) */
+int mamdr_rank_slates(mamdr_ctx* ctx, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                      const int64_t* d_slate_off, const int32_t* d_slate_ids,
+                      float* d_score_out, int32_t* d_pos_out, int32_t* d_order_out);
+
 /* Per-user grouped AUC (GAUC, Zhou et al., DIN, KDD 2018) of one split's predictions.  NO REFERENCE COUNTERPART: the
  * reference reports one 500-threshold AUC per domain (base_model.py:111-144) and nothing per user.  Stateless, any stream.
  * Definition.  For one split of one domain, group the rows by uid.  For a group u with r_u rows, P_u of them positive

@@ -11,7 +11,9 @@ Every tower name of the reference's registries is built (run.py:37-47; deepctr.p
 deepfm; deep_mtl_ctr.py:25-49: shared_bottom mmoe ple; star); Star in every form of star.py:70-96 -- norm none / pn / bn, dense dense / star, auxiliary_net); what is not (ple with more than one
 level, uncertainty weighting on the multi-task towers) raises NotImplementedError naming why.
 Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, and
---rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report), and
+--rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report),
+--sampled-eval [N] with --sampled-eval-ks KS (train.sampled_eval, train.sampled_eval_ks, train.sampled_eval_seed: every held-out
+positive ranked among N sampled items the user never interacted with, recommend.sampled_report), and
 --conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report).
 """
 import argparse
@@ -111,7 +113,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.rank_eval = [K,
     ...] (run.py --rank-eval; not a key of the reference's configs either): once the pipeline has ended, the exact rank of every
     test positive in its domain's whole catalogue, with MRR, mean percentile and HitRate / Recall / NDCG at those K
-    (recommend.rank_report), written under train.result_save_path.  train.conflict = N (run.py --conflict [N]; no key of the
+    (recommend.rank_report), written under train.result_save_path.  train.sampled_eval = N (run.py --sampled-eval [N]; no key
+    of the reference's configs): once the pipeline has ended, the sampled-negatives protocol -- every test positive ranked
+    among N sampled negatives (seed train.sampled_eval_seed, default 0), MRR and HitRate / NDCG at train.sampled_eval_ks
+    (default [10]) (recommend.sampled_report) --, written under train.result_save_path.  train.conflict = N (run.py --conflict [N]; no key of the
     reference's configs): once the pipeline has ended, the domain-conflict report (conflict.report) over N batches per domain
     (0: whole passes), written to train.conflict_out or under train.result_save_path; result.json gains conflict_rate_all,
     mean_cosine_all, conflict_rate_meta and mean_cosine_meta."""
@@ -129,6 +134,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     if config["train"].get("rank_eval") and (world > 1 or lanes > 1):
         raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
                                   "(the best phi_d slots are current only on their owners); run it with one process and "
+                                  "train.lanes = 1")
+    if config["train"].get("sampled_eval") and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.sampled_eval (run.py --sampled-eval): the slates are not ranked across processes or "
+                                  "lanes (the best phi_d slots are current only on their owners); run it with one process and "
                                   "train.lanes = 1")
     if config["train"].get("conflict") is not None and (world > 1 or lanes > 1):
         raise NotImplementedError("train.conflict (run.py --conflict): the domain-conflict report is not computed across processes "
@@ -176,6 +185,9 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
             rec.report(model, int(recommend), recommend_out)
         if config["train"].get("rank_eval"):
             rec.rank_report(model, config["train"]["rank_eval"])
+        if config["train"].get("sampled_eval"):
+            rec.sampled_report(model, int(config["train"]["sampled_eval"]), config["train"].get("sampled_eval_ks", [10]),
+                               seed=int(config["train"].get("sampled_eval_seed", 0)))
         if config["train"].get("conflict") is not None:
             from . import conflict
             _, res = conflict.report(model, int(config["train"]["conflict"]), config["train"].get("conflict_out"))
@@ -203,6 +215,11 @@ def cli(argv=None):
     parser.add_argument("--rank-eval", type=str, default=None, nargs="?", const="10,50,200", metavar="KS",
                         help="after the run: the exact rank of every test positive in its domain's whole catalogue, with MRR, mean "
                              "percentile and HitRate / Recall / NDCG at the comma list KS (default 10,50,200) (train.rank_eval)")
+    parser.add_argument("--sampled-eval", type=int, default=None, nargs="?", const=99, metavar="N",
+                        help="after the run: every test positive ranked among N sampled items its user never interacted with "
+                             "(default 99), with MRR and HitRate / NDCG at --sampled-eval-ks (train.sampled_eval)")
+    parser.add_argument("--sampled-eval-ks", type=str, default=None, metavar="KS",
+                        help="the comma list of K for --sampled-eval (default 10) (train.sampled_eval_ks)")
     parser.add_argument("--conflict", type=int, default=None, nargs="?", const=8, metavar="N",
                         help="after the run: the domain-conflict report -- cosines between the domains' gradients over N batches "
                              "per domain (default 8; 0: whole passes), per tensor, with the share of conflicting pairs "
@@ -218,6 +235,14 @@ def cli(argv=None):
         config["train"]["report_gauc"] = True
     if args.rank_eval is not None:
         config["train"]["rank_eval"] = [int(k) for k in args.rank_eval.split(",")]
+    if args.sampled_eval is not None:
+        if args.sampled_eval < 1:
+            parser.error("--sampled-eval N: N negatives per positive, at least 1")
+        config["train"]["sampled_eval"] = args.sampled_eval
+    if args.sampled_eval_ks is not None:
+        if not config["train"].get("sampled_eval"):
+            parser.error("--sampled-eval-ks KS needs --sampled-eval [N] (or train.sampled_eval in the config)")
+        config["train"]["sampled_eval_ks"] = [int(k) for k in args.sampled_eval_ks.split(",")]
     if args.conflict is not None:
         if args.conflict < 0:
             parser.error("--conflict N: N batches per domain, 0 for whole passes")

@@ -831,7 +831,7 @@ struct PcgArgs {
 };
 void launch_pcgrad(const PcgArgs& a, hipStream_t s);
 
-// recommend_kernels.hip: top-K retrieval (mamdr_recommend, mamdr_recommend_domain) and exact ranks (mamdr_rank_domain).  One RecArgs describes a block of queries x a chunk of
+// recommend_kernels.hip: top-K retrieval (mamdr_recommend, mamdr_recommend_domain), exact ranks (mamdr_rank_domain) and per-query slates (mamdr_rank_slates).  One RecArgs describes a block of queries x a chunk of
 // candidates; the query-side pointers (uid, dom, excl_off, the outputs) are already offset to the block's first query.
 constexpr int REC_TILE = 64;          // candidates per workgroup of k_rec_score (chunks are multiples of it)
 constexpr int REC_KMAX = 128;         // largest K
@@ -871,7 +871,8 @@ struct RecArgs {
     int32_t* ids_out;          // [n_query][k]
     float* scores_out;
     float* scores_all;         // nullable [n_query][n_cand]
-    // mamdr_rank_domain only (null / unused on the top-K path): positions j into the call's flat target list
+    // mamdr_rank_domain and mamdr_rank_slates (null / unused on the top-K path): positions j into the call's flat target list
+    // (mamdr_rank_slates: the slates' entries are the targets; rank_out and live_out stay unused)
     const int64_t* tgt_off;    // [n_query + 1] CSR of the block's queries: query q owns targets [tgt_off[q], tgt_off[q + 1])
     unsigned long long* tkey;  // [n targets of the call] workspace: key(q, t), written by k_rec_pair, read by the counting tiles
     float* tscore_out;         // nullable [n targets]: sigmoid(logit(q, t))
@@ -886,6 +887,22 @@ void launch_rec_merge(const RecArgs& a, hipStream_t s);
 // terms) and the counting ending of k_rec_score; false as launch_rec_score
 bool launch_rec_pair(const RecArgs& a, hipStream_t s);
 bool launch_rec_count(const RecArgs& a, hipStream_t s);
+// mamdr_rank_slates: the order inside each slate of a block of queries, from the keys k_rec_pair left in `tkey`.  Offsets
+// and positions j are the call's (absolute); `off` is already offset to the block's first query
+constexpr int SLATE_WAVE = 64;        // slates of up to this many entries: one wave each
+constexpr int SLATE_TILE = 256;       // longer slates: entries per workgroup
+constexpr int SLATE_STAGE = 1024;     // ... keys of the slate staged in LDS per round
+struct SlateArgs {
+    const int64_t* off;                 // [n_query + 1] slate q owns entries [off[q], off[q + 1])
+    const unsigned long long* tkey;     // [entries of the call] key(q, x) of every entry
+    int32_t* pos_out;                   // [entries of the call] keys of the same slate that are greater
+    int32_t* order_out;                 // nullable [entries of the call], filled with -1 by the call: order[off[q] + pos[j]] = j - off[q]
+    int n_query;
+};
+// max_len: the longest slate of the block; any_short: some slate has 1 .. SLATE_WAVE entries (both from the offsets the
+// call read back): the launches a block does not need are left out.  The long form's grid is ceil(max_len / SLATE_TILE) x
+// n_query: workgroups of shorter slates and behind a slate's end leave at once
+void launch_slate_order(const SlateArgs& a, int64_t max_len, bool any_short, hipStream_t s);
 
 // gauc_kernels.hip: per-user grouped AUC of one split's predictions (mamdr_group_auc)
 constexpr int GAUC_SMALL = 64;        // groups of up to this many rows: one wave each (k_gauc_small)

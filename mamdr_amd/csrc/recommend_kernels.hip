@@ -431,7 +431,83 @@ __global__ __launch_bounds__(REC_THREADS) void k_rec_merge(const RecArgs a) {
     }
 }
 
+// ---- the order inside each slate (mamdr_rank_slates): pos[j] = the keys of j's slate that are greater than key j, and,
+// when asked for, the inverse permutation.  O(L^2) compares per slate, on purpose: slates are short, and ordering a whole
+// catalogue is mamdr_rank_domain's job.  Integers only, no atomics: every output word has one writer (slates of distinct
+// ids have distinct keys, so their positions are a permutation and no two entries claim one slot of `order`).
+//   LONG = false: slates of 1 .. SLATE_WAVE entries, one wave per query of the block (wave w of workgroup b: query 4 b + w;
+//     other lengths are stepped over).  Lane l holds key l, 0 behind the slate's end -- below every key, keys being at
+//     least 1 << 32 --, and key i reaches every lane as two lane reads with a wave-uniform index.
+//   LONG = true: longer slates, one workgroup per (SLATE_TILE entries, query) (workgroups of other slates and behind a
+//     slate's end leave at once).  The slate's keys pass through LDS SLATE_STAGE at a time; every thread compares its own
+//     key with each staged key: all lanes read one address, a broadcast without bank conflicts.
+template <bool LONG>
+__global__ __launch_bounds__(REC_THREADS) void k_slate_order(const SlateArgs a) {
+    const int tid = threadIdx.x;
+    if (!LONG) {
+        const int lane = tid & 63;
+        const int q = __builtin_amdgcn_readfirstlane(blockIdx.x * (REC_THREADS / 64) + (tid >> 6));
+        if (q >= a.n_query) return;
+        const int64_t o0 = a.off[q];
+        const int64_t len = a.off[q + 1] - o0;
+        if (len < 1 || len > SLATE_WAVE) return;
+        const int L = __builtin_amdgcn_readfirstlane((int)len);
+        const u64 key = lane < L ? a.tkey[o0 + lane] : 0ull;
+        const int klo = (int)(uint32_t)key, khi = (int)(uint32_t)(key >> 32);
+        int cnt = 0;
+        for (int i = 0; i < L; ++i) {
+            const u64 other = ((u64)(uint32_t)__builtin_amdgcn_readlane(khi, i) << 32) |
+                              (u64)(uint32_t)__builtin_amdgcn_readlane(klo, i);
+            cnt += other > key ? 1 : 0;
+        }
+        if (lane < L) {
+            a.pos_out[o0 + lane] = cnt;
+            if (a.order_out) a.order_out[o0 + cnt] = lane;
+        }
+    } else {
+        __shared__ u64 sk[SLATE_STAGE];
+        const int q = blockIdx.y;
+        const int64_t o0 = a.off[q];
+        const int64_t len = a.off[q + 1] - o0;
+        const int64_t e0 = (int64_t)blockIdx.x * SLATE_TILE;
+        if (len <= SLATE_WAVE || e0 >= len) return;              // (uniform over the workgroup: before any barrier)
+        const int64_t e = e0 + tid;
+        const bool in = e < len;
+        const u64 key = in ? a.tkey[o0 + e] : ~0ull;
+        int cnt = 0;
+        for (int64_t s0 = 0; s0 < len; s0 += SLATE_STAGE) {
+            const int n = (int)(len - s0 < SLATE_STAGE ? len - s0 : SLATE_STAGE);
+            if (s0) __syncthreads();                             // every thread is done with the stage before
+#pragma unroll
+            for (int t = 0; t < SLATE_STAGE / REC_THREADS; ++t) {
+                const int i = tid + REC_THREADS * t;
+                if (i < n) sk[i] = a.tkey[o0 + s0 + i];
+            }
+            __syncthreads();
+#pragma unroll 8
+            for (int i = 0; i < n; ++i) cnt += sk[i] > key ? 1 : 0;
+        }
+        if (in) {
+            a.pos_out[o0 + e] = cnt;
+            if (a.order_out) a.order_out[o0 + cnt] = (int32_t)e;
+        }
+    }
+}
+
 }  // namespace
+
+void launch_slate_order(const SlateArgs& a, int64_t max_len, bool any_short, hipStream_t s) {
+    // (the block's LAST launch carries a profiling scope's stop event: the slot times both)
+    const bool any_long = max_len > SLATE_WAVE;
+    if (any_short) {
+        const dim3 grid((a.n_query + REC_THREADS / 64 - 1) / (REC_THREADS / 64));
+        if (any_long) hipLaunchKernelGGL(k_slate_order<false>, grid, dim3(REC_THREADS), 0, s, a);
+        else MAMDR_LAUNCH(k_slate_order<false>, grid, dim3(REC_THREADS), 0, s, a);
+    }
+    if (any_long)
+        MAMDR_LAUNCH(k_slate_order<true>, dim3((unsigned)((max_len + SLATE_TILE - 1) / SLATE_TILE), a.n_query), dim3(REC_THREADS),
+                     0, s, a);
+}
 
 void launch_rec_item_proj(const RecArgs& a, hipStream_t s) {
     MAMDR_LAUNCH(k_rec_item_proj, dim3((a.n_chunk + IP_ROWS - 1) / IP_ROWS), dim3(REC_THREADS), 0, s, a);

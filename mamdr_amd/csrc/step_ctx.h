@@ -4,7 +4,8 @@
 //                       slots, tile setters
 //   mamdr_api.hip       the training call: its decisions, CallPlan / plan_call, the three step functions, the pre-gather
 //                       entry points, mamdr_train_steps(_n)
-//   step_queries.hip    mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain), mamdr_group_auc
+//   step_queries.hip    mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain), mamdr_rank_domain, mamdr_rank_slates,
+//                       mamdr_group_auc
 //   step_stateless.hip  the outer updates, mamdr_adam_apply, mamdr_pcgrad_project, mamdr_copy, mamdr_gram, the shuffle
 // Helpers that one file uses stay static in it.
 #pragma once
@@ -208,7 +209,7 @@ struct mamdr_ctx {
     float* rec_q = nullptr;         // q0 | qud | qs
     unsigned long long* rec_part = nullptr;
     unsigned long long* rec_best = nullptr;
-    unsigned long long* rec_tkey = nullptr;      // mamdr_rank_domain: the call's target keys, grown on demand
+    unsigned long long* rec_tkey = nullptr;      // mamdr_rank_domain / mamdr_rank_slates: the call's target / entry keys, grown on demand
     int64_t rec_tkey_cap = 0;
 #ifdef MAMDR_STAMPS
     unsigned long long* stamps = nullptr;

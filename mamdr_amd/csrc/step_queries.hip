@@ -1,5 +1,6 @@
 // C ABI of libmamdr_hip.so, the queries of a step-kernel context: evaluation of a split, the gathered input rows, top-K
-// retrieval, the exact ranks of target items, and the (stateless) per-user grouped AUC of any evaluation's predictions.
+// retrieval, the exact ranks of target items, per-query candidate slates, and the (stateless) per-user grouped AUC of any
+// evaluation's predictions.
 #include <algorithm>
 
 #include "step_ctx.h"
@@ -219,6 +220,32 @@ int mamdr_recommend_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const 
                           k, d_ids_out, d_scores_out, d_scores_all);
 }
 
+// the CSR offsets of a call's targets / slate entries (`what` names them in the errors) size its launches and its key
+// workspace: read back once (the call's one synchronisation of the context's stream) and held to their contract here, so
+// that no kernel indexes past the list
+static int read_offsets(mamdr_ctx* c, const char* fn, const char* what, const int64_t* d_off, int32_t n_query,
+                        std::vector<int64_t>& off) {
+    off.resize((size_t)n_query + 1);
+    HIP_TRY(hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (off[0] != 0) return fail(MAMDR_EINVAL, "%s: the %s offsets start at %lld, not 0", fn, what, (long long)off[0]);
+    for (int32_t q = 0; q < n_query; ++q)
+        if (off[q + 1] < off[q]) return fail(MAMDR_EINVAL, "%s: the %s offsets descend at query %d", fn, what, q);
+    return MAMDR_OK;
+}
+
+// the key workspace (k_rec_pair's tkey) for n keys
+static int grow_rec_tkey(mamdr_ctx* c, int64_t n) {
+    if (n <= c->rec_tkey_cap) return MAMDR_OK;
+    c->dev.release(c->rec_tkey);
+    c->rec_tkey = nullptr;
+    c->rec_tkey_cap = 0;
+    c->dev.alloc(&c->rec_tkey, (size_t)n);
+    if (const int rc = c->dev.check(g_err)) return rc;
+    c->rec_tkey_cap = n;
+    return MAMDR_OK;
+}
+
 // ---- exact ranks of target items among a candidate list: the retrieval phases with the counting ending
 int mamdr_rank_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
                       int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, const int64_t* d_tgt_off,
@@ -240,27 +267,14 @@ int mamdr_rank_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32
     if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
         return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
     if (ready(c)) return MAMDR_ESTATE;
-    // the target offsets size the pre-pass and the key workspace: read back once (the call's one synchronisation of the
-    // context's stream) and held to their contract here, so that no kernel indexes past the target list
-    std::vector<int64_t> off((size_t)n_query + 1);
-    HIP_TRY(hipMemcpyAsync(off.data(), d_tgt_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (off[0] != 0) return fail(MAMDR_EINVAL, "%s: the target offsets start at %lld, not 0", fn, (long long)off[0]);
-    for (int32_t q = 0; q < n_query; ++q)
-        if (off[q + 1] < off[q]) return fail(MAMDR_EINVAL, "%s: the target offsets descend at query %d", fn, q);
+    std::vector<int64_t> off;
+    if (int e = read_offsets(c, fn, "target", d_tgt_off, n_query, off)) return e;
     const int64_t n_tgt = off[n_query];
     if (n_tgt > 0 && !d_tgt_ids) return fail(MAMDR_EINVAL, "%s: %lld targets without their ids", fn, (long long)n_tgt);
     RecArgs a;
     int chunk;
     if (int e = rec_prepare(c, domain, d_cand, n_cand, d_excl_ids, a, chunk)) return e;
-    if (n_tgt > c->rec_tkey_cap) {
-        c->dev.release(c->rec_tkey);
-        c->rec_tkey = nullptr;
-        c->rec_tkey_cap = 0;
-        c->dev.alloc(&c->rec_tkey, (size_t)n_tgt);
-        if (const int rc = c->dev.check(g_err)) return rc;
-        c->rec_tkey_cap = n_tgt;
-    }
+    if (int e = grow_rec_tkey(c, n_tgt)) return e;
     a.tkey = c->rec_tkey;
     a.tscore_out = d_score_out;
     a.rank_out = d_rank_out;
@@ -292,6 +306,78 @@ int mamdr_rank_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32
                 return fail(MAMDR_EHIP, "%s: k_rec_score was refused its LDS limit (hipFuncSetAttribute)", fn);
         }
     }
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+// ---- per-query candidate slates: mamdr_rank_domain's target pre-pass over the slates' entries, then the order inside
+// each slate (k_slate_order).  No candidate pass: a slate is ranked against itself
+int mamdr_rank_slates(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32_t* d_uid, const int64_t* d_slate_off,
+                      const int32_t* d_slate_ids, float* d_score_out, int32_t* d_pos_out, int32_t* d_order_out) {
+    const char* fn = "mamdr_rank_slates";
+    if (check_ctx(c)) return MAMDR_EINVAL;
+    if (c->pnn || c->nfm)
+        return fail(MAMDR_ENOTBUILT, "mamdr_rank_slates: the %s tower is not built for retrieval (its first layer does not "
+                                     "separate into a query and an item term); mlp, wdl, deepfm and star are", c->pnn ? "pnn" : "nfm");
+    if (domain < 0 || domain >= c->cfg.n_domain)
+        return fail(MAMDR_EINVAL, "mamdr_rank_slates: domain %d outside [0, %d)", domain, c->cfg.n_domain);
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (!d_uid || !d_slate_off || !d_pos_out) return fail(MAMDR_EINVAL, "%s: null uid / slate offsets / position output pointer", fn);
+    if ((((uintptr_t)d_uid | (uintptr_t)d_slate_ids | (uintptr_t)d_score_out | (uintptr_t)d_pos_out | (uintptr_t)d_order_out) & 3) ||
+        ((uintptr_t)d_slate_off & 7))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if (ready(c)) return MAMDR_ESTATE;
+    std::vector<int64_t> off;
+    if (int e = read_offsets(c, fn, "slate", d_slate_off, n_query, off)) return e;
+    for (int32_t q = 0; q < n_query; ++q)
+        if (off[q + 1] - off[q] > INT32_MAX)
+            return fail(MAMDR_EINVAL, "%s: slate %d has %lld entries: positions are int32", fn, q, (long long)(off[q + 1] - off[q]));
+    int64_t n_ent = off[n_query];
+    if (n_ent == 0) return MAMDR_OK;
+    if (!d_slate_ids) return fail(MAMDR_EINVAL, "%s: %lld entries without their ids", fn, (long long)n_ent);
+    RecArgs a;
+    int chunk;
+    if (int e = rec_prepare(c, domain, d_slate_ids, n_ent, nullptr, a, chunk)) return e;
+    if (int e = grow_rec_tkey(c, n_ent)) return e;
+    a.tkey = c->rec_tkey;
+    a.tscore_out = d_score_out;
+    SlateArgs sa;
+    sa.tkey = c->rec_tkey;
+    sa.pos_out = d_pos_out;
+    sa.order_out = d_order_out;
+    if (d_order_out) HIP_TRY(hipMemsetAsync(d_order_out, 0xff, (size_t)n_ent * sizeof(int32_t), c->stream));
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        a.n_query = std::min<int32_t>(REC_QBLOCK, n_query - qb);
+        if (off[qb + a.n_query] == off[qb]) continue;           // a block of empty slates
+        a.uid = d_uid + qb;
+        a.tgt_off = d_slate_off + qb;
+        launch_rec_query_proj(a, c->stream);
+        prof_break(c);
+        // the block's keys: the item term of its entries, a workspace's worth at a time, then the pair tiles
+        for (int64_t t0 = off[qb]; t0 < off[qb + a.n_query]; t0 += c->rec_cap) {
+            a.c_base = t0;
+            a.n_chunk = (int)std::min<int64_t>(c->rec_cap, off[qb + a.n_query] - t0);
+            {
+                Prof p(c, MAMDR_KERNEL_GATHER);
+                launch_rec_item_proj(a, c->stream);
+            }
+            Prof p(c, MAMDR_KERNEL_EVAL);
+            if (!launch_rec_pair(a, c->stream))
+                return fail(MAMDR_EHIP, "%s: k_rec_pair was refused its LDS limit (hipFuncSetAttribute)", fn);
+        }
+        int64_t max_len = 0;
+        bool any_short = false;
+        for (int32_t q = qb; q < qb + a.n_query; ++q) {
+            const int64_t len = off[q + 1] - off[q];
+            max_len = std::max(max_len, len);
+            any_short = any_short || (len >= 1 && len <= SLATE_WAVE);
+        }
+        sa.off = d_slate_off + qb;
+        sa.n_query = a.n_query;
+        Prof p(c, MAMDR_KERNEL_AUX);
+        launch_slate_order(sa, max_len, any_short, c->stream);
+    }
+    prof_break(c);
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;
 }

@@ -22,7 +22,7 @@ import torch
 
 from . import _lib as L
 from . import gauc
-from .recommend import exclusion_csr
+from .recommend import exclusion_csr, slates_csr
 
 
 def _ptr(t):
@@ -829,6 +829,42 @@ class TowerEngine(DeviceEngine):
                "live": live.cpu().numpy()[:nq]}
         if want_scores:
             res["scores"] = scores.cpu().numpy()[:n_tgt]
+        return res
+
+    def rank_slates(self, uids, domain, slates, want_order=False):
+        """every query's own candidate slate scored and ordered (mamdr_rank_slates): `slates` is one array of DISTINCT item
+        ids per query, kept in the caller's order (a slate may be empty), every query in the one domain `domain`, from the
+        live weights.  -> {"offsets" [Q + 1] int64, "ids" [E] int32 (the slates' CSR), "scores" [E] float32: sigmoid(logit)
+        of the pair -- the bits rank_domain and recommend_domain give it --, "pos" [E] int32: the entries of the same slate
+        that order strictly before the entry (higher logit, or equal logit and smaller id), a permutation of 0 .. L - 1 per
+        slate [, "order" [E] int32: order[offsets[q] + pos[j]] = j - offsets[q], the slate-local index of the entry at each
+        position]} as numpy.  Every check runs before the launch: the work is sum of the slates' lengths pairs, and
+        O(L^2) integer compares per slate -- a whole catalogue is rank_domain's job."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
+            raise ValueError("rank_slates: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
+        nq = int(uid.shape[0])
+        off, ids = slates_csr(slates, nq)
+        if nq and (uid.min() < 0 or uid.max() >= self.n_user):
+            raise ValueError("rank_slates: user id out of range")
+        if ids.size and ids.max() >= self.n_item:
+            raise ValueError("rank_slates: item id out of range")
+        n_ent = int(ids.shape[0])
+        res = {"offsets": off, "ids": ids}
+        if nq == 0 or n_ent == 0:
+            res.update(scores=np.zeros(0, np.float32), pos=np.zeros(0, np.int32))
+            if want_order:
+                res["order"] = np.zeros(0, np.int32)
+            return res
+        d_uid, d_off, d_ids = (torch.from_numpy(a).to(self.device) for a in (uid, off, ids))
+        scores = torch.empty(n_ent, dtype=torch.float32, device=self.device)
+        pos = torch.empty(n_ent, dtype=torch.int32, device=self.device)
+        order = torch.empty(n_ent, dtype=torch.int32, device=self.device) if want_order else None
+        L.check(self.lib.mamdr_rank_slates(self.ctx, int(domain), nq, _ptr(d_uid), _ptr(d_off), _ptr(d_ids), _ptr(scores),
+                                           _ptr(pos), _ptr(order)))
+        res.update(scores=scores.cpu().numpy(), pos=pos.cpu().numpy())
+        if want_order:
+            res["order"] = order.cpu().numpy()
         return res
 
     def _recommend(self, uid, dom, domain, k, candidates, exclude, want_scores):

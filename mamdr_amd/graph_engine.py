@@ -130,5 +130,10 @@ class GraphEngine(DeviceEngine):
                                   "engine's mlp / wdl / deepfm / star towers at width 128, hidden [256, 128, 64] are "
                                   "(TowerEngine.rank_domain)" % self.kind)
 
+    def rank_slates(self, *args, **kwargs):
+        raise NotImplementedError("rank_slates: the generic-layer towers (kind '%s') are not built for retrieval; the step "
+                                  "engine's mlp / wdl / deepfm / star towers at width 128, hidden [256, 128, 64] are "
+                                  "(TowerEngine.rank_slates)" % self.kind)
+
     def set_adam_eps(self, eps):
         self._check(self.lib.mamdr_graph_set_adam_eps(self.ctx, float(eps)))

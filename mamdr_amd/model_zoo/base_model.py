@@ -119,7 +119,7 @@ class BaseModel(object):
 
     # ------------------------------------------------------------------ retrieval (no reference counterpart)
     def _retrieval_problem(self, domain, users, exclude_seen):
-        """what `recommend` and `rank_eval` ask of `domain` -> (catalogue: the distinct pids of its three splits; users:
+        """what `recommend`, `rank_eval` and `sampled_eval` ask of `domain` -> (catalogue: the distinct pids of its three splits; users:
         the given ones, by default the distinct uids of its test split; exclude: per user the items it has in the domain's
         train or val split, None when exclude_seen is off)."""
         cols = [s[domain]["data"] for s in (self.dataset.train_dataset, self.dataset.val_dataset, self.dataset.test_dataset)
@@ -164,6 +164,51 @@ class BaseModel(object):
         positives = rec.split_positives(self.dataset, domain, users)
         res = dict(self.model.rank_domain(users, int(domain), positives, candidates=catalogue, exclude=exclude))
         res.update(users=users, catalogue=catalogue, n_positives=np.diff(res["offsets"]).astype(np.int64))
+        return res
+
+    def rerank(self, domain, users, slates):
+        """every user's own candidate slate -- `slates`: one array of distinct item ids per user, in the caller's order --
+        scored and ordered in `domain` from the live weights (the engine's rank_slates: mamdr_rank_slates) -> the engine's
+        dict ("offsets", "ids", "scores", "pos") plus "users" [Q]."""
+        users = np.asarray(users, np.int64).ravel()
+        res = dict(self.model.rank_slates(users, int(domain), slates))
+        res["users"] = users
+        return res
+
+    def sampled_eval(self, domain, n_neg, seed=0, users=None, exclude_seen=True):
+        """the sampled-negatives protocol on `domain`: one slate per distinct (user, positive) pair of its test split (label
+        1; `users`: default the distinct uids of that split) -- entry 0 the positive, behind it `n_neg` negatives drawn
+        uniformly without replacement (recommend.sample_negatives, `seed`) from the domain's catalogue (_retrieval_problem's)
+        without the user's train / val items (exclude_seen) and without ANY of the user's test positives.  A user with fewer
+        free items than n_neg gets all of them: such slates are evaluated and counted in "n_short".
+        -> `rerank`'s dict ("users" [S]: the user of each slate) plus "positives" [S], "rank" [S] (pos of entry 0: the
+        negatives that order before the positive), "slate_len" [S] and "n_short"."""
+        from .. import recommend as rec
+        catalogue, users, exclude = self._retrieval_problem(domain, users, exclude_seen)
+        positives = [np.unique(p) for p in rec.split_positives(self.dataset, domain, users)]
+        n_pos = np.asarray([p.size for p in positives], np.int64)
+        forbid = [np.concatenate([np.asarray(exclude[q] if exclude is not None else (), np.int64).ravel(), p])
+                  for q, p in enumerate(positives)]
+        f_len = np.asarray([f.size for f in forbid], np.int64)
+        by_slate = np.repeat(np.arange(users.size), n_pos)          # slate -> index of its user
+        slate_users = users[by_slate]
+        slate_pos = np.concatenate(positives + [np.zeros(0, np.int64)])
+        # the users' forbidden lists, once per slate of the user
+        f_start = np.concatenate([[0], np.cumsum(f_len)])[:-1]
+        f_off = np.concatenate([[0], np.cumsum(f_len[by_slate])]).astype(np.int64)
+        f_all = np.concatenate(forbid + [np.zeros(0, np.int64)])
+        f_ids = f_all[np.repeat(f_start[by_slate] - f_off[:-1], f_len[by_slate]) + np.arange(f_off[-1])]
+        n_off, n_ids = rec.sample_negatives(catalogue, f_off, f_ids, n_neg, seed)
+        n_slate = slate_pos.size
+        off = n_off + np.arange(n_slate + 1)
+        ids = np.empty(int(off[-1]), np.int64)
+        is_pos = np.zeros(ids.size, bool)
+        is_pos[off[:-1]] = True
+        ids[is_pos], ids[~is_pos] = slate_pos, n_ids
+        res = self.rerank(domain, slate_users, np.split(ids, off[1:-1]) if n_slate else [])
+        slate_len = np.diff(off)
+        res.update(positives=slate_pos, rank=res["pos"][off[:-1]], slate_len=slate_len,
+                   n_short=int((slate_len < int(n_neg) + 1).sum()))
         return res
 
     # ------------------------------------------------------------------ domain conflict (no reference counterpart)

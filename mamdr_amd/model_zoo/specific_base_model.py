@@ -6,6 +6,8 @@ host deep copies (specific_base_model.py:44-62); the finetune stage restarts eve
 its best merged weights with plain SGD, lr 0.001 hard-coded (specific_base_model.py:99-162,
 :120 -- the reference's comment says Adam, the code says GradientDescent).
 """
+import contextlib
+
 from .. import parallel
 from .maml import MAML
 
@@ -107,19 +109,33 @@ class SpecificBase(MAML):
             domain_loss, domain_auc = parallel.gather_domain_scalars(local, self.n_domain, self.model.device)
         return self.base_model._summarise(mode, domain_loss, domain_auc)
 
+    @contextlib.contextmanager
+    def _best_of_domain(self, domain):
+        """for the body: with best weights kept, the best theta (+|*) phi_domain installed -- what val_and_test("test") scores
+        the domain with --, and the previous live flat vector put back afterwards, bit for bit; before the first snapshot
+        the live weights stay."""
+        if self.best_shared_weights is None or not self.best_domain_weights or domain not in self.best_domain_weights:
+            yield
+            return
+        live = self.model.get_weights().clone()
+        self._set_model_meta_parms(self._merge_weights(self.best_shared_weights, self.best_domain_weights[domain]))
+        try:
+            yield
+        finally:
+            self.model.set_weights(live)
+
     def rank_eval(self, domain, users=None, exclude_seen=True):
         """BaseModel.rank_eval under domain `domain`'s own weights: with best weights kept, the best theta (+|*) phi_domain is
         installed for the call -- what val_and_test("test") scores the domain with -- and the previous live flat vector is
         put back afterwards, bit for bit.  Before the first snapshot the live weights are ranked, as `recommend` does.  A
         finetune run is ranked with the un-finetuned best merged weights: the per-domain finetuned models are not kept."""
-        if self.best_shared_weights is None or not self.best_domain_weights or domain not in self.best_domain_weights:
+        with self._best_of_domain(domain):
             return self.base_model.rank_eval(domain, users, exclude_seen)
-        live = self.model.get_weights().clone()
-        self._set_model_meta_parms(self._merge_weights(self.best_shared_weights, self.best_domain_weights[domain]))
-        try:
-            return self.base_model.rank_eval(domain, users, exclude_seen)
-        finally:
-            self.model.set_weights(live)
+
+    def sampled_eval(self, domain, n_neg, seed=0, users=None, exclude_seen=True):
+        """BaseModel.sampled_eval under domain `domain`'s own weights, installed and put back as rank_eval does."""
+        with self._best_of_domain(domain):
+            return self.base_model.sampled_eval(domain, n_neg, seed, users, exclude_seen)
 
     def domain_conflict(self, n_batches=None):
         """BaseModel.domain_conflict at the best theta ALONE -- the shared point that Domain Negotiation negotiates, without

@@ -1,5 +1,6 @@
-"""Host side of top-K retrieval (`mamdr_recommend`, include/mamdr_hip.h) and of the exact full-catalogue ranks
-(`mamdr_rank_domain`): the exclusion and target lists' CSR form, ranking metrics from top-K lists (`ranking_metrics`) and from
+"""Host side of top-K retrieval (`mamdr_recommend`, include/mamdr_hip.h), of the exact full-catalogue ranks
+(`mamdr_rank_domain`) and of per-query slates (`mamdr_rank_slates`: `slates_csr`, `sample_negatives`, `sampled_report` behind
+`run.py --sampled-eval N`): the exclusion and target lists' CSR form, ranking metrics from top-K lists (`ranking_metrics`) and from
 ranks (`rank_metrics`), and the per-domain reports behind `run.py --recommend K` and `run.py --rank-eval KS`.  Pure numpy.  The reference has no counterpart: its pipeline
 ends at per-domain loss and AUC (base_model.py:111-144).
 """
@@ -21,6 +22,92 @@ def exclusion_csr(exclude, n_query, what="exclude"):
     if ids.size and (ids.min() < 0 or ids.max() > np.iinfo(np.int32).max):
         raise ValueError("%s: item id out of range" % what)
     return off, ids.astype(np.int32)
+
+
+def slates_csr(slates, n_query):
+    """`slates` -- one array of item ids per query, DISTINCT inside a slate, a slate may be empty or None -- as the CSR
+    `mamdr_rank_slates` takes: (offsets int64 [n_query + 1], ids int32), every slate in the caller's order."""
+    if len(slates) != n_query:
+        raise ValueError("slates lists %d queries, the call has %d" % (len(slates), n_query))
+    rows = [np.asarray(e if e is not None else (), np.int64).ravel() for e in slates]
+    off = np.zeros(n_query + 1, np.int64)
+    np.cumsum([r.size for r in rows], out=off[1:])
+    ids = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+    if ids.size and (ids.min() < 0 or ids.max() > np.iinfo(np.int32).max):
+        raise ValueError("slates: item id out of range")
+    if ids.size:
+        q = np.repeat(np.arange(n_query), np.diff(off))
+        o = np.lexsort((ids, q))
+        same = (ids[o][1:] == ids[o][:-1]) & (q[o][1:] == q[o][:-1])
+        if same.any():
+            raise ValueError("slates: item %d is listed twice in the slate of query %d" % (
+                ids[o][1:][same][0], q[o][1:][same][0]))
+    return off, ids.astype(np.int32)
+
+
+SAMPLE_ROUNDS = 16      # vectorised rejection rounds of sample_negatives before the per-slate completion
+
+
+def sample_negatives(catalogue, forbid_off, forbid_ids, n_neg, seed):
+    """`n_neg` items per slate, drawn uniformly without replacement from `catalogue` (item ids; taken as a set) minus the
+    slate's forbidden ids forbid_ids[forbid_off[s] : forbid_off[s + 1]] (any order, duplicates and ids outside the catalogue
+    allowed).  A slate with fewer free items than n_neg gets all of them.  -> (offsets int64 [S + 1], ids int64): slate s's
+    draws at ids[offsets[s] : offsets[s + 1]], min(n_neg, free) of them.  A function of its arguments only: the stream is
+    numpy's RandomState(seed), whose values are frozen.
+    Vectorised rejection over all slates at once: every open position draws a catalogue index; a draw that is forbidden or
+    equals another position of its slate is drawn again in the next round (of two equal positions the first stays).  The
+    procedure never looks at an item's value except to compare it, so every free item is as likely as any other and every
+    set of the right size equally likely.  Slates still open after SAMPLE_ROUNDS rounds -- those that take nearly all of
+    their free items -- are completed one by one from their explicit free set."""
+    cat = np.unique(np.asarray(catalogue, np.int64).ravel())
+    off = np.asarray(forbid_off, np.int64).ravel()
+    fid = np.asarray(forbid_ids, np.int64).ravel()
+    n_slate, n_cat, n_neg = off.size - 1, int(cat.size), int(n_neg)
+    if n_slate < 0 or n_neg < 0 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != fid.size:
+        raise ValueError("sample_negatives: forbid_off [S + 1] ascending from 0 to len(forbid_ids), n_neg >= 0")
+    # the forbidden (slate, catalogue index) pairs as sorted distinct keys slate * n_cat + index
+    keys = np.zeros(0, np.int64)
+    if fid.size and n_cat:
+        idx = np.minimum(np.searchsorted(cat, fid), n_cat - 1)
+        hit = cat[idx] == fid
+        keys = np.unique(np.repeat(np.arange(n_slate, dtype=np.int64), np.diff(off))[hit] * n_cat + idx[hit])
+    n_forbid = np.bincount(keys // max(n_cat, 1), minlength=n_slate)[:n_slate] if n_slate else np.zeros(0, np.int64)
+    want = np.minimum(n_neg, n_cat - n_forbid).astype(np.int64)
+    rs = np.random.RandomState(int(seed))
+    draws = np.zeros((n_slate, n_neg), np.int32)          # (catalogue indices; the sentinels below reach n_cat + n_neg)
+    col = np.arange(n_neg, dtype=np.int32)[None, :]
+    todo = np.flatnonzero(want > 0)
+    redraw = col < want[todo][:, None]
+    for _ in range(SAMPLE_ROUNDS):
+        if not todo.size:
+            break
+        active = col < want[todo][:, None]
+        d = draws[todo]
+        d[redraw] = rs.randint(0, n_cat, size=int(redraw.sum()))
+        bad = np.zeros_like(active)
+        if keys.size:
+            k = todo[:, None] * n_cat + d.astype(np.int64)
+            bad = keys[np.minimum(np.searchsorted(keys, k), keys.size - 1)] == k
+        # equal positions of a slate: a stable sort per row (positions behind the slate's end under distinct sentinels)
+        # brings them together in position order; all but the first are drawn again
+        v = np.where(active, d, np.int32(n_cat) + col)
+        o = np.argsort(v, axis=1, kind="stable")
+        vs = np.take_along_axis(v, o, 1)
+        dup_sorted = np.zeros_like(active)
+        dup_sorted[:, 1:] = vs[:, 1:] == vs[:, :-1]
+        dup = np.zeros_like(active)
+        np.put_along_axis(dup, o, dup_sorted, 1)
+        redraw = (bad | dup) & active
+        draws[todo] = d
+        open_ = redraw.any(1)
+        todo, redraw = todo[open_], redraw[open_]
+    for s in todo.tolist():                       # (ascending: the stream's order is part of the function)
+        lo, hi = np.searchsorted(keys, [s * n_cat, (s + 1) * n_cat])
+        free = np.setdiff1d(np.arange(n_cat, dtype=np.int64), keys[lo:hi] - s * n_cat, assume_unique=True)
+        draws[s, :want[s]] = rs.choice(free, int(want[s]), replace=False)
+    out_off = np.zeros(n_slate + 1, np.int64)
+    np.cumsum(want, out=out_off[1:])
+    return out_off, cat[draws[col < want[:, None]]] if n_cat else np.zeros(0, np.int64)
 
 
 def ranking_metrics(ids, positives):
@@ -157,4 +244,42 @@ def rank_report(model, ks, out_path=None):
     os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
     np.savez(out_path, **arrays)
     print("Ranks written to {}".format(out_path))
+    return out_path, metrics
+
+
+def sampled_report(model, n_neg, ks, seed=0, out_path=None):
+    """`run.py --sampled-eval N`: the sampled-negatives protocol -- for every domain, each (user, positive) pair of its test
+    split ranked among N items the user never interacted with (model.sampled_eval; under the wrappers that keep a phi_d per
+    domain, the best theta (+|*) phi_d of THAT domain) --, with MRR and HitRate / NDCG at every K of `ks` averaged over
+    the pairs (rank_metrics with one slate per query), written to ONE .npz -- domains, ks, n_neg, seed, per domain d users_d /
+    positives_d / rank_d [S], offsets_d [S + 1], ids_d / scores_d / pos_d [E]; n_short [n domains], mrr / mean_percentile
+    [n domains], hit_rate / recall / ndcg [n domains, len(ks)] -- and printed, one line per domain.
+    -> (path, {domain: metrics})."""
+    ks, n_neg, seed = [int(k) for k in ks], int(n_neg), int(seed)
+    domains = sorted(model.dataset.test_dataset)
+    arrays = {"domains": np.asarray(domains, np.int64), "ks": np.asarray(ks, np.int64), "n_neg": np.asarray(n_neg, np.int64),
+              "seed": np.asarray(seed, np.int64)}
+    metrics = {}
+    print("Sampled eval ({} negatives per positive, seed {}): ".format(n_neg, seed))
+    for d in domains:
+        r = model.sampled_eval(d, n_neg, seed=seed)
+        n_slate = r["rank"].shape[0]
+        m = rank_metrics(np.arange(n_slate + 1), r["rank"], np.ones(n_slate, bool), r["slate_len"], np.ones(n_slate, np.int64), ks)
+        m["n_short"] = int(r["n_short"])
+        metrics[d] = m
+        for name in ("users", "positives", "offsets", "ids", "scores", "pos", "rank"):
+            arrays["%s_%d" % (name, d)] = r[name]
+        print("{}: MRR {:.4f} {} ({} pairs, {} short slates; random ranking: {})".format(
+            d, m["mrr"],
+            " ".join("HitRate@{k} {:.4f} NDCG@{k} {:.4f}".format(m["hit_rate"][i], m["ndcg"][i], k=k) for i, k in enumerate(ks)),
+            m["n_eval"], m["n_short"],
+            " ".join("HitRate@{} {:.4f}".format(k, min(1.0, float(k) / (n_neg + 1))) for k in ks)))
+    for name in ("mrr", "mean_percentile", "hit_rate", "recall", "ndcg"):
+        arrays[name] = np.asarray([metrics[d][name] for d in domains], np.float64)
+    arrays["n_short"] = np.asarray([metrics[d]["n_short"] for d in domains], np.int64)
+    if out_path is None:
+        out_path = os.path.join(model.result_path, "sampled_eval_neg%d.npz" % n_neg)
+    os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
+    np.savez(out_path, **arrays)
+    print("Sampled evaluation written to {}".format(out_path))
     return out_path, metrics

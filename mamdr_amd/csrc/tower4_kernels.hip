@@ -13,7 +13,9 @@
 // (fixed order, no atomics).  The backward layers use transposed copies of W1 / W2 kept
 // current by k_update, so they stream rows exactly like the forward layers.  With one workgroup per CU
 // (grids of up to 256 tiles, W1L) W1 is brought into LDS ONCE by LDS-DMA while the gather's misses are
-// outstanding and feeds both layer 1 and its backward contraction (see t4_w1_request).  The dropout
+// outstanding and feeds both layer 1 and its backward contraction (see t4_w1_request).  On a pre-gathered pass (PRE)
+// every wave fetches the 4 x 128 B of x its own first layer-0 segment contracts and, with the domain-table step pending
+// on a one-domain tile (`same`), starts layer 0 by itself: no workgroup barrier runs before layer 0's own.  The dropout
 // stream, loss, and workspace layout are identical to k_tower; results differ only by fp32
 // summation order.  Replaces the same reference call sites (model_zoo/mamdr.py:54,86,97).
 #include <hip/hip_ext.h>
@@ -38,8 +40,11 @@ constexpr int T4_DEEP = 8;               // ring depth of the short layers (see 
 // Row strides of the four activation tiles: + 4 floats, so that the A fragment reads of a contraction -- lane l reads
 // 16 B of row l & 3 -- fall into four different bank groups (unpadded, every stride is a multiple of 32 banks and the
 // four rows collide: SQ_LDS_BANK_CONFLICT 2.9 K cycles per CU and launch at 1,024 rows).
+// x tile on a pre-gathered pass: columns [32 w, 32 w + 32) of the four rows are written AND read by wave w alone (wave
+// fence, no barrier); so are the domain columns [256 + 16 w, 256 + 16 w + 16) when the wave finishes them itself (midseg).
+// Without `same` the domain columns come from other waves, between the two barriers of the gather.
 constexpr int T4_XLD = XDIM + 4, T4_H1LD = H1 + 4, T4_H2LD = H2 + 4, T4_H3LD = H3 + 4;
-constexpr int T4_XS = 0;                               // [4][384 + 4]
+constexpr int T4_XS = 0;                               // [4][384 + 4]  (PRE: per-wave column slices, see above)
 constexpr int T4_H1 = T4_XS + T4_ROWS * T4_XLD;        // [4][256 + 4]  h1, then dz1 (trainable tables: input of the dx contraction)
 constexpr int T4_H2 = T4_H1 + T4_ROWS * T4_H1LD;       // [4][128 + 4]  h2, then dz2
 constexpr int T4_DZ3 = T4_H2 + T4_ROWS * T4_H2LD;      // [4][64 + 4]
@@ -413,8 +418,10 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     // whatever is requested ahead of it (weights, domain-table partials) would be waited for together with it.
     // Every lane loads (a clamped position): a divergent branch around a load drains all loads at its end.
     int perm_src = 0;
-    // pre-gathered pass (k_pass_prep): the tile's four [user | item] rows, domains and labels sit at known addresses;
-    // every lane loads (clamped rows; lanes 256.. repeat rows 0..3), no dependent chain
+    // pre-gathered pass (k_pass_prep): the tile's four [user | item] rows, domains and labels sit at known addresses.
+    // Wave w fetches exactly the slice its first layer-0 segment contracts -- columns [32 w, 32 w + 32) of the four rows,
+    // 4 x 128 B: lane l takes row (l >> 3) & 3, 16-B chunk l & 7 -- so layer 0 needs no other wave's loads.  Every lane
+    // loads (clamped rows; lanes 32..63 repeat lanes 0..31), no dependent chain
     // (the k_wgrad_adam path's duties -- pre-gathered passes, the pending domain-table step, the W0 snapshot -- exist
     // for the frozen-table mlp tower only: compiled out of the DX / FM instances, see k_tower)
     constexpr bool FUSED_OK = !DX && !FM;
@@ -423,8 +430,8 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     int pre_dom = 0;
     float pre_lab = 0.f;
     if (pre) {
-        const int rr = min(r0 + ((tid >> 6) & 3), max(k_rows - 1, 0));
-        xv = *reinterpret_cast<const f32x4*>(k_xpre + (size_t)rr * (2 * EMB) + 4 * (tid & 63));
+        const int rr = min(r0 + ((lane >> 3) & 3), max(k_rows - 1, 0));
+        xv = *reinterpret_cast<const f32x4*>(k_xpre + (size_t)rr * (2 * EMB) + 32 * w + 4 * (lane & 7));
         const int rb = min(r0 + (tid & 3), max(k_rows - 1, 0));
         pre_dom = k_pdom[rb];
         pre_lab = k_plabel[rb];
@@ -463,6 +470,15 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
 
     // ---- row bookkeeping + embedding gather (4 rows x 96 float4)
     if (pre) {
+        // the wave's own slice of the x tile (rows beyond the batch: zero); read back by this wave only (t4_contract_l0's
+        // first segment), so a wave-level fence orders the other lanes' reads behind these stores -- no workgroup barrier
+        const int row = (lane >> 3) & 3;
+        if (r0 + row >= a.rows) xv = (f32x4){0.f, 0.f, 0.f, 0.f};
+        *reinterpret_cast<f32x4*>(smem + T4_XS + row * T4_XLD + 32 * w + 4 * (lane & 7)) = xv;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        // (first read behind a workgroup barrier: the one in front of the gather without `same`, layer 0's otherwise)
         if (tid < T4_ROWS) {
             const bool valid = (r0 + tid) < a.rows;
             rowi[tid] = 0;
@@ -470,11 +486,6 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
             rowi[8 + tid] = pre_dom;
             rowi[12 + tid] = valid ? 1 : 0;
             rowf[tid] = pre_lab;
-        }
-        if (tid < 256) {
-            const int row = tid >> 6;
-            if (r0 + row >= a.rows) xv = (f32x4){0.f, 0.f, 0.f, 0.f};
-            *reinterpret_cast<f32x4*>(smem + T4_XS + row * T4_XLD + 4 * (tid & 63)) = xv;
         }
     } else if (tid < T4_ROWS) {
         const bool valid = (r0 + tid) < a.rows;
@@ -491,11 +502,22 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
         rowi[12 + tid] = valid ? 1 : 0;
         rowf[tid] = a.label[src];
     }
-    __syncthreads();
     // domain-table step still pending (DmStep): the domain rows as that step leaves them.  `same`: one domain per tile
     // AND the one the caller announced (the addresses were formed from it); otherwise every lane works alone.
     const bool pend = FUSED_OK && a.dms.snap != nullptr;
-    const bool same = pend && rowi[8] == a.dm_hint && rowi[9] == rowi[8] && rowi[10] == rowi[8] && rowi[11] == rowi[8];
+    bool same;
+    if (pre) {
+        // every wave holds the four rows' domains (padding rows: the clamped row's) in its lanes 0..3 -- what rowi[8..11]
+        // get -- so the decision needs no LDS and no barrier.  With `same` no workgroup barrier runs before layer 0:
+        // the wave reads only its own x slice and the domain columns it finishes itself (midseg)
+        const int d0 = __builtin_amdgcn_readlane(pre_dom, 0), d1 = __builtin_amdgcn_readlane(pre_dom, 1);
+        const int d2 = __builtin_amdgcn_readlane(pre_dom, 2), d3 = __builtin_amdgcn_readlane(pre_dom, 3);
+        same = pend && d0 == a.dm_hint && d1 == d0 && d2 == d0 && d3 == d0;
+        if (!same) __syncthreads();        // (uniform) the gather below reads rowi
+    } else {
+        __syncthreads();
+        same = pend && rowi[8] == a.dm_hint && rowi[9] == rowi[8] && rowi[10] == rowi[8] && rowi[11] == rowi[8];
+    }
     T4STAMP(12);
     T4STAMP_W4(0);
     // (requested only now, beside the table rows: at kernel start these loads -- misses all the way to HBM, the
@@ -527,7 +549,8 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     // for the image as well -- it is requested only now)
     if (W1L && !pre) t4_w1_request<32>(k_w1, w1s, 32 * __builtin_amdgcn_readfirstlane(w));
     T4STAMP_W4(2);
-    __syncthreads();
+    // gather-end barrier: the tile's columns come from other waves -- not so on a pre-gathered pass with `same`
+    if (!(pre && same)) __syncthreads();   // (uniform)
     const bool pnn = FM && a.deepfm == 3;              // (uniform) the inner products of the field pairs feed three more rows of W0
     float wx0 = 0.f, wx1 = 0.f, wx2 = 0.f;             // ... rows a.L.wx + {0, 1, 2} H1, this thread's column
     if (FM && !pnn) {
@@ -608,7 +631,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
                            dm_apply1(a.dms, dm_wave_sum(dmt.r), p, m, v);
                            if (lane < 16) {
 #pragma unroll
-                               for (int rr = 0; rr < T4_ROWS; ++rr) smem[T4_XS + rr * T4_XLD + 2 * EMB + c] = rowi[12 + rr] ? p : 0.f;
+                               for (int rr = 0; rr < T4_ROWS; ++rr) smem[T4_XS + rr * T4_XLD + 2 * EMB + c] = r0 + rr < a.rows ? p : 0.f;
                            }
                        }
                        T4STAMP(14);

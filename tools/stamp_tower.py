@@ -56,13 +56,15 @@ names = ["w0 prefetch+gather", "L0 fwd", "L1 fwd (incl. barrier)", "L2 fwd", "ba
 full = allst[:tiles * 16].reshape(tiles, 16).astype(np.float64)
 if full[:, 12].min() > 0:
     g0 = full[:, 0]
-    print("  gather detail (cycles after kernel start, median): bookkeeping barrier passed %.0f | pair sums staged %.0f | "
-          "pending barrier passed %.0f | domain rows finished %.0f | gather done %.0f" % tuple(
-              np.median(full[:, k] - g0) for k in (12, 13, 14, 15, 1)))
+    # (pre-gathered pass: stamp 12 = wave 0 has stored its x slice; the bookkeeping barrier only runs without `same`)
+    print("  gather detail (cycles after kernel start, median): wave 0 has its x slice / bookkeeping barrier passed %.0f | "
+          "midseg entered %.0f | domain columns finished %.0f | domain rows written back %.0f | wave 0 begins layer 0 %.0f | "
+          "layer 0 ends %.0f" % tuple(np.median(full[:, k] - g0) for k in (12, 13, 14, 15, 1, 2)))
 w4 = allst[256 * 16:(256 + tiles) * 16].reshape(tiles, 16).astype(np.float64)
 if w4[:, 0].min() > 0:
-    print("  wave 4 (cycles after kernel start, median): after the bookkeeping barrier %.0f | partials requested %.0f | "
-          "at the gather-end barrier %.0f" % tuple(np.median(w4[:, k] - full[:, 0]) for k in (0, 1, 2)))
+    # (pre-gathered pass with `same`: no gather-end barrier runs, stamp 2 of wave 4 is where it begins layer 0)
+    print("  wave 4 (cycles after kernel start, median): has its x slice / after the bookkeeping barrier %.0f | partials "
+          "requested %.0f | at the gather-end barrier / begins layer 0 %.0f" % tuple(np.median(w4[:, k] - full[:, 0]) for k in (0, 1, 2)))
 dif = np.diff(st, axis=1)
 tot = st[:, 9] - st[:, 0]
 print("tiles %d; total cycles median %.0f (min %.0f max %.0f); s_memtime ticks = shader cycles" % (tiles, np.median(tot), tot.min(), tot.max()))

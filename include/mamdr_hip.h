@@ -425,6 +425,50 @@ int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_
                     const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
                     uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream);
 
+/* Exact AUC, average precision and equal-mass calibration bins of one split's predictions.  NO REFERENCE COUNTERPART: every
+ * AUC the reference prints is AUC(num_thresholds=500), a trapezoid over 500 evenly spaced thresholds
+ * (base_model.py:111-144), which stays the metric of parity and early stopping.  Stateless, any stream.
+ * Definition.  Per row:
+ *   key is GAUC's order-preserving 32-bit key: NaN is lowest and equals NaN, -0 equals +0.
+ *   positive is label != 0.
+ *   The composite is (uint64) key << 1 | positive.
+ * Sort the composites ascending.  Equal composites are indistinguishable, so the sorted array is unique.  Inside a run of
+ * equal keys the negatives come first.  For sorted position i:
+ *   rs(i) is the first position of i's run of equal keys.
+ *   cp(i) is the number of positives at positions < i.
+ *   cn(i) = i - cp(i).
+ * Arguments (device pointers; nothing is read back by the call):
+ *   d_pred, d_label [n]   fp32 predictions and labels in file order, 0 <= n < 2^31; read only
+ *   n_bins                1 .. MAMDR_EXACT_MAX_BINS
+ *   d_counts [5]          int64 words T, P, N, n_runs, n_nan:
+ *                         T = sum_{i positive} (cn(rs(i)) + cn(i)).  This is 2 * #{s_p > s_n} + #{s_p == s_n}, the integer
+ *                         mamdr_group_auc's definition gives for the whole split as one group.  n_runs is the number of
+ *                         distinct keys, n_nan the number of NaN predictions.
+ *                         AUC = T / (2 * P * N); when P * N == 0 it is 0.0 with valid = 0 (recommend.ranking_metrics'
+ *                         convention)
+ *   d_ap [1]              one double, sum_{i positive} (double)(P - cp(rs(i))) / (double)(n - rs(i)).  Average precision
+ *                         is that sum divided by P, 0.0 when P = 0: scikit-learn's step-wise definition, each positive
+ *                         contributes the precision at its own threshold
+ *   d_bins [3][n_bins]    int64, with every row of a run in bin floor(rs(i) * n_bins / n) (64-bit arithmetic): rows,
+ *                         positives, and the sum of predictions in Q32 fixed point, floor(clamp(p, 0, 1) * 2^32 + 0.5)
+ *                         evaluated in fp64, where it is exact.  A NaN prediction adds 0 and is counted in n_nan.  A tie
+ *                         run is never split across bins: bins may come out EMPTY or UNEQUAL (predictions quantised to
+ *                         fewer values than bins leave most bins empty)
+ *   d_sorted_out [n]      optional int64: the sorted composites (the last sort pass writes them here)
+ * Determinism.  All outputs are the same bits from run to run and under any permutation of the rows.  Every integer is
+ * exact (integer atomics commute; the bin sums are fixed-point for that reason); each AP term is one division, and their
+ * sum runs over one fixed tree per n that depends on the sorted array alone.  No floating-point atomics.
+ * The sort is a least-significant-digit radix sort, the scans are three launches each; the kernel boundary is the only
+ * hand-off between workgroups (csrc/exact_kernels.hip).  Nothing synchronises the device; the only memory written is the
+ * outputs and a stream-ordered allocation of the call (hipMallocAsync / hipFreeAsync on `stream`) of about 17 bytes per row.
+ * n = 0 writes zeros and returns MAMDR_OK.
+ * MAMDR_EINVAL, before any device call: a null d_counts, d_ap, d_bins, or (n > 0) d_pred / d_label; a pointer that is not
+ * aligned to its element size; n < 0 or n >= 2^31; n_bins outside 1 .. MAMDR_EXACT_MAX_BINS.
+ * (Added within ABI 19: a new entry point only, no structure or existing call changed.) */
+#define MAMDR_EXACT_MAX_BINS 4096
+int mamdr_exact_metrics(const float* d_pred, const float* d_label, int64_t n, int32_t n_bins,
+                        int64_t* d_counts, double* d_ap, int64_t* d_bins, int64_t* d_sorted_out, void* stream);
+
 /* Gram matrices of up to MAMDR_GRAM_MAX_VEC flat fp32 vectors over column ranges, in fp64 -- the reduction behind the
  * domain-conflict report (the cosines between the domains' gradients).  NO REFERENCE COUNTERPART: the reference argues
  * that domains conflict and never measures it.  Stateless, any stream, no synchronisation, no allocation: the workspace

@@ -33,6 +33,9 @@ SOURCES = [
     # gauc_kernels: the fp64 terms are a division, a multiplication and additions as the host definition computes them
     # -> no fma fusion; its register / LDS / scratch report: profiles/gauc_bench.txt
     ("gauc_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
+    # exact_kernels: the AP term is the host definition's one division -> no fma fusion; its register / LDS / scratch
+    # report: profiles/exact_metrics_bench.txt
+    ("exact_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
     # gram_kernels: its register / LDS / scratch report: profiles/conflict_bench.txt
     ("gram_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)

@@ -10,7 +10,7 @@ Dispatch is by substring of config.model.name, in the reference's order (run.py:
 Every tower name of the reference's registries is built (run.py:37-47; deepctr.py:24-50: mlp wdl nfm autoint ccpm pnn
 deepfm; deep_mtl_ctr.py:25-49: shared_bottom mmoe ple; star); Star in every form of star.py:70-96 -- norm none / pn / bn, dense dense / star, auxiliary_net); what is not (ple with more than one
 level, uncertainty weighting on the multi-task towers) raises NotImplementedError naming why.
-Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, and
+Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, --exact-metrics, and
 --rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report),
 --sampled-eval [N] with --sampled-eval-ks KS (train.sampled_eval, train.sampled_eval_ks, train.sampled_eval_seed: every held-out
 positive ranked among N sampled items the user never interacted with, recommend.sampled_report), and
@@ -110,7 +110,9 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     their recorders there).  recommend = K (not an option of the reference's run.py): once the pipeline has ended, rank 0 /
     lane 0 ranks every domain's catalogue for its test users with the weights the run finished with and writes the top K
     (recommend.report) to recommend_out, by default under train.result_save_path.  train.report_gauc (run.py --gauc; not a
-    key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.rank_eval = [K,
+    key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.report_exact = B
+    (run.py --exact-metrics [B]; not a key of the reference's configs): every evaluation also reports the exact AUC, the average
+    precision and the calibration over B equal-mass bins (exact.py).  train.rank_eval = [K,
     ...] (run.py --rank-eval; not a key of the reference's configs either): once the pipeline has ended, the exact rank of every
     test positive in its domain's whole catalogue, with MRR, mean percentile and HitRate / Recall / NDCG at those K
     (recommend.rank_report), written under train.result_save_path.  train.sampled_eval = N (run.py --sampled-eval [N]; no key
@@ -131,6 +133,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
         raise NotImplementedError("train.report_gauc (run.py --gauc): the per-user grouped AUC is not gathered across processes "
                                   "or lanes (parallel.gather_domain_scalars carries loss and AUC only); run it with one "
                                   "process and train.lanes = 1")
+    if config["train"].get("report_exact") and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.report_exact (run.py --exact-metrics): the exact AUC, average precision and calibration "
+                                  "are not gathered across processes or lanes (parallel.gather_domain_scalars carries loss and "
+                                  "AUC only); run it with one process and train.lanes = 1")
     if config["train"].get("rank_eval") and (world > 1 or lanes > 1):
         raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
                                   "(the best phi_d slots are current only on their owners); run it with one process and "
@@ -212,6 +218,9 @@ def cli(argv=None):
                         help=".npz the recommendations go to (default: under train.result_save_path)")
     parser.add_argument("--gauc", action="store_true",
                         help="also report the impression-weighted per-user AUC (GAUC) of every evaluation (train.report_gauc)")
+    parser.add_argument("--exact-metrics", type=int, default=None, nargs="?", const=20, metavar="B",
+                        help="also report the exact (tie-aware Mann-Whitney) AUC, the average precision and the calibration "
+                             "over B equal-mass bins (default 20) of every evaluation (train.report_exact)")
     parser.add_argument("--rank-eval", type=str, default=None, nargs="?", const="10,50,200", metavar="KS",
                         help="after the run: the exact rank of every test positive in its domain's whole catalogue, with MRR, mean "
                              "percentile and HitRate / Recall / NDCG at the comma list KS (default 10,50,200) (train.rank_eval)")
@@ -233,6 +242,10 @@ def cli(argv=None):
         config["train"]["lanes"] = args.lanes
     if args.gauc:
         config["train"]["report_gauc"] = True
+    if args.exact_metrics is not None:
+        if not 1 <= args.exact_metrics <= 4096:
+            parser.error("--exact-metrics B: B calibration bins, 1 .. 4096")
+        config["train"]["report_exact"] = args.exact_metrics
     if args.rank_eval is not None:
         config["train"]["rank_eval"] = [int(k) for k in args.rank_eval.split(",")]
     if args.sampled_eval is not None:

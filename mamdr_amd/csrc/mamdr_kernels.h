@@ -926,6 +926,27 @@ struct GaucArgs {
 int64_t gauc_parts(int64_t n_groups);
 void launch_gauc(const GaucArgs& a, hipStream_t s);
 
+// exact_kernels.hip: exact AUC, average precision and equal-mass calibration bins of one split (mamdr_exact_metrics).
+// (mamdr_amd/exact.py carries the same four tile constants for the tests)
+constexpr int EXACT_RADIX_BITS = 8;           // digit width of the sort: 5 passes over the 33-bit composites
+constexpr int EXACT_SORT_TILE = 2048;         // composites per workgroup of k_exact_hist / k_exact_scatter
+constexpr int EXACT_SCAN_TILE = 512;          // elements per workgroup of the device-wide scans
+constexpr int EXACT_METRIC_TILE = 1024;       // sorted positions per workgroup of k_exact_runs / k_exact_metrics
+constexpr int EXACT_MAX_BINS = 4096;          // (= MAMDR_EXACT_MAX_BINS)
+struct ExactArgs {
+    const float* pred;                 // [n] in file order
+    const float* label;                // [n]
+    int64_t n;
+    int n_bins;
+    unsigned long long* counts;        // [5] T, P, N, n_runs, n_nan; zeroed by the call
+    double* ap;                        // [1]
+    unsigned long long* bins;          // [3][n_bins] rows, positives, Q32 prediction sums; zeroed by the call
+    unsigned long long* sorted_out;    // nullable [n]: the last pass scatters here
+    char* ws;                          // exact_workspace_bytes(n) bytes, 16-byte aligned
+};
+size_t exact_workspace_bytes(int64_t n);
+void launch_exact(const ExactArgs& a, hipStream_t s);      // n > 0
+
 // gram_kernels.hip: fp64 Gram matrices of up to GRAM_MAX_VEC flat vectors over column ranges (mamdr_gram).  One GramArgs
 // describes a batch of up to GRAM_MAX_RANGES ranges: two launches
 constexpr int GRAM_SLAB = 16384;      // columns per workgroup of k_gram_slab (= MAMDR_GRAM_SLAB)

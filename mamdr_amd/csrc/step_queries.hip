@@ -439,4 +439,40 @@ int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_
     return MAMDR_OK;
 }
 
+// ---- exact AUC, average precision and calibration bins of one split (exact_kernels.hip): stateless as well
+int mamdr_exact_metrics(const float* d_pred, const float* d_label, int64_t n, int32_t n_bins, int64_t* d_counts, double* d_ap,
+                        int64_t* d_bins, int64_t* d_sorted_out, void* stream) {
+    if (!d_counts || !d_ap || !d_bins) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: null counts / ap / bins pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: n %lld outside [0, 2^31)", (long long)n);
+    if (n_bins < 1 || n_bins > MAMDR_EXACT_MAX_BINS)
+        return fail(MAMDR_EINVAL, "mamdr_exact_metrics: n_bins %d outside 1..%d", (int)n_bins, MAMDR_EXACT_MAX_BINS);
+    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: null pred / label pointer");
+    if ((((uintptr_t)d_pred | (uintptr_t)d_label) & 3) ||
+        (((uintptr_t)d_counts | (uintptr_t)d_ap | (uintptr_t)d_bins | (uintptr_t)d_sorted_out) & 7))
+        return fail(MAMDR_EINVAL, "mamdr_exact_metrics: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    ExactArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.n = n;
+    a.n_bins = n_bins;
+    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    a.ap = d_ap;
+    a.bins = reinterpret_cast<unsigned long long*>(d_bins);
+    a.sorted_out = reinterpret_cast<unsigned long long*>(d_sorted_out);
+    HIP_TRY(hipMemsetAsync(d_counts, 0, 5 * sizeof(int64_t), s));
+    HIP_TRY(hipMemsetAsync(d_ap, 0, sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(d_bins, 0, 3 * (size_t)n_bins * sizeof(int64_t), s));
+    if (n == 0) return MAMDR_OK;
+    // the call's own scratch, ordered on its stream
+    HIP_TRY(hipMallocAsync((void**)&a.ws, exact_workspace_bytes(n), s));
+    launch_exact(a, s);
+    hipError_t e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(a.ws, s);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_exact_metrics: %s", hipGetErrorString(e));
+    return MAMDR_OK;
+}
+
 }  // extern "C"

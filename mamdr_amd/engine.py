@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import exact
 from . import gauc
 from .recommend import exclusion_csr, slates_csr
 
@@ -425,17 +426,22 @@ class DeviceEngine(FlatVectorOps):
                                           opt, float(lr), _ptr(loss_out)))
         return n_steps
 
-    def evaluate(self, domain, split, want_preds=False, want_gauc=False):
-        """model.evaluate(data, steps=n_step) -> (loss, auc[, hist, preds][, gauc report]); syncs to read back.
-        want_gauc (no reference counterpart): the predictions stay on the device, mamdr_group_auc runs behind the evaluation
-        on the engine's stream over the split's uid groups, and gauc.finish's report dict ends the tuple."""
+    def evaluate(self, domain, split, want_preds=False, want_gauc=False, want_exact=0):
+        """model.evaluate(data, steps=n_step) -> (loss, auc[, hist, preds][, gauc report][, exact report]); syncs to read
+        back.  want_gauc (no reference counterpart): the predictions stay on the device, mamdr_group_auc runs behind the
+        evaluation on the engine's stream over the split's uid groups, and gauc.finish's report dict ends the tuple.
+        want_exact = B > 0 (no reference counterpart either): mamdr_exact_metrics runs behind the evaluation likewise, with B
+        calibration bins, and exact.finish's report dict ends the tuple, after GAUC's when both are asked for."""
         n = self.n_rows(domain, split)
-        preds = torch.empty(n, dtype=torch.float32, device=self.device) if (want_preds or want_gauc) else None
+        want_exact = int(want_exact or 0)
+        preds = torch.empty(n, dtype=torch.float32, device=self.device) if (want_preds or want_gauc or want_exact) else None
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         self._check(self._c_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1),
                                         _ptr(self._hist), _ptr(preds)))
         if want_gauc:
             res4 = self._group_auc_launch(preds, self.data[(domain, split)]["label"], self.group_auc_plan(domain, split))
+        if want_exact:
+            exact_out = self._exact_launch(preds, self.data[(domain, split)]["label"], want_exact)
         hist = self._hist.cpu().numpy().astype(np.int64)
         loss = float(self._loss1.cpu().numpy()[0])
         auc, _ = auc_from_histogram(hist)
@@ -444,7 +450,36 @@ class DeviceEngine(FlatVectorOps):
             out += (hist.reshape(2, 501), preds.cpu().numpy())
         if want_gauc:
             out += (gauc.finish(*res4.cpu().numpy().tolist()),)
+        if want_exact:
+            out += (exact.finish(*[t.cpu().numpy() for t in exact_out[:3]]),)
         return out
+
+    # ------------------------------------------------------------ exact AUC / AP / calibration (no reference counterpart)
+    def _exact_launch(self, preds, labels, n_bins, want_sorted=False):
+        """mamdr_exact_metrics on the engine's stream -> the device tensors (counts [5] int64, ap_sum [1] fp64, bins [3,
+        n_bins] int64, sorted composites [n] int64 or None); nothing is read back."""
+        n, n_bins = int(preds.numel()), int(n_bins)
+        if not 1 <= n_bins <= exact.MAX_BINS:
+            raise ValueError("exact metrics: n_bins %d outside 1..%d" % (n_bins, exact.MAX_BINS))
+        counts = torch.empty(5, dtype=torch.int64, device=self.device)
+        ap = torch.empty(1, dtype=torch.float64, device=self.device)
+        bins = torch.empty((3, n_bins), dtype=torch.int64, device=self.device)
+        out = torch.empty(n, dtype=torch.int64, device=self.device) if want_sorted else None
+        L.check(self.lib.mamdr_exact_metrics(_ptr(preds if n else None), _ptr(labels if n else None), n, n_bins, _ptr(counts),
+                                             _ptr(ap), _ptr(bins), _ptr(out if n else None), self._s()))
+        return counts, ap, bins, out
+
+    def exact_metrics(self, preds, labels, n_bins, want_sorted=False):
+        """exact AUC, average precision and calibration (exact.py's definition) of device tensors preds / labels [n] fp32
+        -> exact.finish's report; want_sorted adds "sorted", the sorted composites (int64 numpy)."""
+        if preds.numel() != labels.numel() or preds.dtype != torch.float32 or labels.dtype != torch.float32 \
+                or preds.device != self.device or labels.device != self.device:
+            raise ValueError("exact_metrics: preds and labels must be fp32 tensors of one length on the engine's device")
+        counts, ap, bins, out = self._exact_launch(preds.contiguous(), labels.contiguous(), n_bins, want_sorted)
+        rep = exact.finish(counts.cpu().numpy(), ap.cpu().numpy()[0], bins.cpu().numpy())
+        if want_sorted:
+            rep["sorted"] = out.cpu().numpy()
+        return rep
 
     # ------------------------------------------------------------ per-user grouped AUC (no reference counterpart)
     def group_auc_plan(self, domain, split):

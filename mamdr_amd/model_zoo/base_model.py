@@ -42,6 +42,7 @@ class BaseModel(object):
         self.shuffler = mplan.PassShuffler(sizes, dataset.shuffle_buffer_size, dataset.seed,
                                            shuffle=getattr(dataset, "shuffle_train", True))
         self.gauc_reports = {}        # train.report_gauc: {(mode, domain): gauc.finish's report of the latest evaluation}
+        self.exact_reports = {}       # train.report_exact: {(mode, domain): exact.finish's report of the latest evaluation}
         self.model = self.build_model()
         self._build_early_stop()
 
@@ -110,12 +111,20 @@ class BaseModel(object):
         """model.evaluate(d['data'], steps=d['n_step']) -> (loss, auc).  Under train.report_gauc (not a key of the
         reference's configs) the evaluation also yields the split's per-user grouped AUC (gauc.py) -- of whatever weights the
         caller has installed: the merged per-domain ones under MAMDR / DN, the finetuned ones in the finetune stage --,
-        remembered per (mode, domain) for _summarise / save_result."""
-        if not self.train_config.get("report_gauc"):
-            return self.model.evaluate(idx, mode)
-        loss, auc, report = self.model.evaluate(idx, mode, want_gauc=True)
-        self.gauc_reports[(mode, idx)] = report
-        return loss, auc
+        remembered per (mode, domain) for _summarise / save_result.  Under train.report_exact = B (not a key of the
+        reference's configs either) it yields the exact AUC, average precision and B-bin calibration of the split (exact.py),
+        remembered likewise; early stopping, checkpoints and finetune decisions stay on the 500-threshold AUC."""
+        want = {}
+        if self.train_config.get("report_gauc"):
+            want["want_gauc"] = True
+        if self.train_config.get("report_exact"):
+            want["want_exact"] = int(self.train_config["report_exact"])
+        out = self.model.evaluate(idx, mode, **want)          # (an engine sees a keyword only when its key is set)
+        for key, store in (("want_exact", self.exact_reports), ("want_gauc", self.gauc_reports)):      # from the tuple's end
+            if key in want:
+                store[(mode, idx)] = out[-1]
+                out = out[:-1]
+        return out
 
     # ------------------------------------------------------------------ retrieval (no reference counterpart)
     def _retrieval_problem(self, domain, users, exclude_seen):
@@ -303,6 +312,13 @@ class BaseModel(object):
             domain_gauc = {d: self.gauc_reports[(mode, d)]["gauc"] for d in domain_auc if (mode, d) in self.gauc_reports}
             self._format_print_domain_metric("GAUC", domain_gauc)
             print("Overall {} GAUC: {}, Weighted GAUC: {}".format(mode, *self._gauc_summary(mode, domain_gauc)))
+        if self.train_config.get("report_exact"):
+            from .. import exact
+            reps = {d: self.exact_reports[(mode, d)] for d in domain_auc if (mode, d) in self.exact_reports}
+            overall = exact.summarise(reps)
+            for name, key in (("Exact AUC", "auc"), ("AP", "ap"), ("ECE", "ece")):
+                self._format_print_domain_metric(name, {d: r[key] for d, r in reps.items()})
+                print("Overall {} {}: {}, Weighted {}: {}".format(mode, name, overall[key][0], name, overall[key][1]))
         return avg_loss, avg_auc, domain_loss, domain_auc
 
     def _gauc_summary(self, mode, domains):
@@ -370,6 +386,17 @@ class BaseModel(object):
                 result["avg_gauc"], result["weighted_gauc"] = self._gauc_summary("test", reps)
                 result["domain_gauc"] = {d: r["gauc"] for d, r in reps.items()}
                 result["domain_gauc_users"] = {d: r["n_valid"] for d, r in reps.items()}
+            if self.train_config.get("report_exact"):        # likewise
+                from .. import exact
+                reps = {d: self.exact_reports[("test", d)] for d in domain_auc if ("test", d) in self.exact_reports}
+                result["avg_auc_exact"], result["weighted_auc_exact"] = exact.summarise(reps)["auc"]
+                result["domain_auc_exact"] = {d: r["auc"] for d, r in reps.items()}
+                for key in ("ap", "ece", "pcoc"):
+                    result["domain_" + key] = {d: r[key] for d, r in reps.items()}
+                # the calibration bins behind ece / pcoc: [domains][n_bins], the rows of `domains` in its order
+                np.savez(osp.join(result_path, "exact_metrics.npz"), domains=np.array(list(reps), np.int64),
+                         **{k: np.array([r[k] for r in reps.values()]).reshape(len(reps), -1)
+                            for k in ("bin_rows", "bin_positives", "bin_pred_sum")})
             json.dump(result, f)
         self.save_model(osp.join(result_path, "model_parameters.npz"))
         return result_path

@@ -469,6 +469,56 @@ int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_
 int mamdr_exact_metrics(const float* d_pred, const float* d_label, int64_t n, int32_t n_bins,
                         int64_t* d_counts, double* d_ap, int64_t* d_bins, int64_t* d_sorted_out, void* stream);
 
+/* Bootstrap replicates of the exact AUC's integers: the statistic of mamdr_exact_metrics under integer resampling weights,
+ * n_rep times over, for standard errors, confidence intervals and paired comparisons of the exact AUC
+ * (mamdr_amd/bootstrap.py: finish, paired).  NO REFERENCE COUNTERPART: every figure the reference reports is a point estimate.
+ * Stateless, any stream.
+ * Row order.  key is GAUC's order-preserving 32-bit key: NaN is lowest and equals NaN, -0 equals +0.  positive is
+ * label != 0.  The sorted order is ascending in (key, positive, row index): inside a run of equal keys the negatives come
+ * first, as in mamdr_exact_metrics, and equal (key, positive) pairs order by row index, which makes the sorted array unique.
+ * Unit.  unit(i) = d_unit ? (uint32) d_unit[i] : (uint32) i, with i the row's index in file order.  Passing the split's uid
+ * column resamples users (the cluster bootstrap: a user's rows are correlated); NULL resamples rows.
+ * Weight.  For replicate b = 1 .. n_rep: w(b, i) = poisson1(u32(b, unit(i))).
+ *   u32(b, x) = the high 32 bits of mix64(mix64(seed + 0x9E3779B97F4A7C15 * (uint64) b) ^ (uint64) x).
+ *   mix64 is the splitmix64 finaliser: z ^= z >> 30, z *= 0xBF58476D1CE4E5B9, z ^= z >> 27, z *= 0x94D049BB133111EB,
+ *   z ^= z >> 31.  All arithmetic is mod 2^64.
+ *   poisson1(u) = the number of k >= 0 with u >= MAMDR_BOOT_THR[k], where THR[k] = floor(2^32 * sum_{j <= k} e^-1 / j!),
+ *   listed up to and including the first k where it reaches 2^32 - 1: a Poisson(1) draw to 32 bits, at most
+ *   MAMDR_BOOT_WMAX.
+ *   Replicate 0 is the unweighted statistic: w(0, .) = 1.
+ * Outputs (device pointers; nothing is read back by the call), arrays [n_rep + 1], slot b for replicate b:
+ *   d_P[b] = sum_{positive i} w(b, i).
+ *   d_N[b] = sum_{negative i} w(b, i).
+ *   d_T[b] = sum_{positive i} w(b, i) * (Cn_b(rs(i)) + Cn_b(i)), with Cn_b(j) the weight of negatives at sorted positions < j
+ *   and rs(i) the first position of i's run of equal keys.  That is 2 * #{s_p > s_n} + #{s_p == s_n} with every pair counted
+ *   w_p * w_n times: mamdr_exact_metrics' T under weights.  Slot 0 is therefore exactly mamdr_exact_metrics' (T, P, N).
+ *   AUC_b = T_b / (2 * P_b * N_b) is formed on the host in fp64.  A replicate with P_b * N_b = 0 is invalid; it is
+ *   reported, not hidden.
+ * Bounds.  0 <= n < 2^27: a replicate's weights add up to S <= n * MAMDR_BOOT_WMAX < 2^27 * 13 < 2^31, P_b + N_b = S gives
+ * 2 * P_b * N_b <= S^2 / 2 < 2^61, and T_b <= 2 * P_b * N_b: every word fits 64 bits, every partial sum 32.
+ * 0 <= n_rep <= 65,535.  n = 0 writes zeros and returns MAMDR_OK.
+ * Determinism.  Every output word is an exact integer: integer atomics commute, and there is no floating-point arithmetic
+ * on the device at all.  The bits depend on (values, file order or unit ids, seed) alone, not on grid, tiling or chunking.
+ * With d_unit = NULL the replicates do depend on file order, which is inherent to resampling rows; slot 0 does not.
+ * Two calls with the same seed, labels and units give every row the same weights: their d_P and d_N are identical and
+ * their replicates are paired.
+ * The sort is mamdr_exact_metrics' radix sort on a wider word; the weights are recomputed where they are used, never
+ * stored (csrc/bootstrap_kernels.hip).  Nothing synchronises the device; the only memory written is the outputs and a
+ * stream-ordered allocation of the call (hipMallocAsync / hipFreeAsync on `stream`): about 17 bytes per row and 12 bytes
+ * per (tile of 1,024 rows, replicate), the latter bounded by 64 MiB -- more replicates than fit run in chunks.
+ * mamdr_auc_bootstrap_bounded is the same call with that bound given in 32-bit words (> 0; the tests force the chunking
+ * with it): the outputs do not depend on it.
+ * MAMDR_EINVAL, before any device call: a null d_T, d_P, d_N, or (n > 0) d_pred / d_label; a pointer that is not aligned
+ * to its element size; n < 0 or n >= 2^27; n_rep < 0 or n_rep > 65,535; part_words <= 0.
+ * (Added within ABI 19: a new entry point only, no structure or existing call changed.) */
+#define MAMDR_BOOT_WMAX 13
+#define MAMDR_BOOT_THR {1580030168u, 3160060337u, 3950075421u, 4213413783u, 4279248373u, 4292415291u, 4294609777u, \
+                        4294923276u, 4294962463u, 4294966817u, 4294967252u, 4294967292u, 4294967295u}
+int mamdr_auc_bootstrap(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
+                        uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, void* stream);
+int mamdr_auc_bootstrap_bounded(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
+                                uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, int64_t part_words, void* stream);
+
 /* Gram matrices of up to MAMDR_GRAM_MAX_VEC flat fp32 vectors over column ranges, in fp64 -- the reduction behind the
  * domain-conflict report (the cosines between the domains' gradients).  NO REFERENCE COUNTERPART: the reference argues
  * that domains conflict and never measures it.  Stateless, any stream, no synchronisation, no allocation: the workspace

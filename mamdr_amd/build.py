@@ -36,6 +36,8 @@ SOURCES = [
     # exact_kernels: the AP term is the host definition's one division -> no fma fusion; its register / LDS / scratch
     # report: profiles/exact_metrics_bench.txt
     ("exact_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
+    # bootstrap_kernels: integers only; its register / LDS / scratch report: profiles/auc_bootstrap.txt
+    ("bootstrap_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
     # gram_kernels: its register / LDS / scratch report: profiles/conflict_bench.txt
     ("gram_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)

@@ -10,7 +10,8 @@ Dispatch is by substring of config.model.name, in the reference's order (run.py:
 Every tower name of the reference's registries is built (run.py:37-47; deepctr.py:24-50: mlp wdl nfm autoint ccpm pnn
 deepfm; deep_mtl_ctr.py:25-49: shared_bottom mmoe ple; star); Star in every form of star.py:70-96 -- norm none / pn / bn, dense dense / star, auxiliary_net); what is not (ple with more than one
 level, uncertainty weighting on the multi-task towers) raises NotImplementedError naming why.
-Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, --exact-metrics, and
+Not options of the reference's run.py: --lanes, --recommend K (top-K lists per domain, recommend.report), --gauc, --exact-metrics,
+--auc-ci [B] with --auc-ci-unit and --auc-ci-seed (train.report_auc_ci: bootstrap intervals of the exact AUC, bootstrap.py), and
 --rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report),
 --sampled-eval [N] with --sampled-eval-ks KS (train.sampled_eval, train.sampled_eval_ks, train.sampled_eval_seed: every held-out
 positive ranked among N sampled items the user never interacted with, recommend.sampled_report), and
@@ -112,7 +113,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     (recommend.report) to recommend_out, by default under train.result_save_path.  train.report_gauc (run.py --gauc; not a
     key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.report_exact = B
     (run.py --exact-metrics [B]; not a key of the reference's configs): every evaluation also reports the exact AUC, the average
-    precision and the calibration over B equal-mass bins (exact.py).  train.rank_eval = [K,
+    precision and the calibration over B equal-mass bins (exact.py).  train.report_auc_ci = B (run.py --auc-ci [B]; not a key
+    of the reference's configs): every evaluation also draws B bootstrap replicates of the exact AUC, resampling
+    train.auc_ci_unit = "user" (default) or "row" under train.auc_ci_seed (default 0), and reports its standard error and
+    percentile interval (bootstrap.py); the test evaluation's replicates go to auc_bootstrap.npz.  train.rank_eval = [K,
     ...] (run.py --rank-eval; not a key of the reference's configs either): once the pipeline has ended, the exact rank of every
     test positive in its domain's whole catalogue, with MRR, mean percentile and HitRate / Recall / NDCG at those K
     (recommend.rank_report), written under train.result_save_path.  train.sampled_eval = N (run.py --sampled-eval [N]; no key
@@ -137,6 +141,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
         raise NotImplementedError("train.report_exact (run.py --exact-metrics): the exact AUC, average precision and calibration "
                                   "are not gathered across processes or lanes (parallel.gather_domain_scalars carries loss and "
                                   "AUC only); run it with one process and train.lanes = 1")
+    if config["train"].get("report_auc_ci") and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.report_auc_ci (run.py --auc-ci): the bootstrap replicates of the exact AUC are not "
+                                  "gathered across processes or lanes (parallel.gather_domain_scalars carries loss and AUC "
+                                  "only); run it with one process and train.lanes = 1")
     if config["train"].get("rank_eval") and (world > 1 or lanes > 1):
         raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
                                   "(the best phi_d slots are current only on their owners); run it with one process and "
@@ -221,6 +229,13 @@ def cli(argv=None):
     parser.add_argument("--exact-metrics", type=int, default=None, nargs="?", const=20, metavar="B",
                         help="also report the exact (tie-aware Mann-Whitney) AUC, the average precision and the calibration "
                              "over B equal-mass bins (default 20) of every evaluation (train.report_exact)")
+    parser.add_argument("--auc-ci", type=int, default=None, nargs="?", const=1000, metavar="B",
+                        help="also report the standard error and the 95 %% percentile interval of the exact AUC of every "
+                             "evaluation from B bootstrap replicates (default 1000, 1 .. 65535) (train.report_auc_ci)")
+    parser.add_argument("--auc-ci-unit", type=str, default=None, choices=("row", "user"),
+                        help="what --auc-ci resamples: users (default; a user's rows are correlated) or rows (train.auc_ci_unit)")
+    parser.add_argument("--auc-ci-seed", type=int, default=None, metavar="S",
+                        help="the seed of --auc-ci's resampling weights (default 0) (train.auc_ci_seed)")
     parser.add_argument("--rank-eval", type=str, default=None, nargs="?", const="10,50,200", metavar="KS",
                         help="after the run: the exact rank of every test positive in its domain's whole catalogue, with MRR, mean "
                              "percentile and HitRate / Recall / NDCG at the comma list KS (default 10,50,200) (train.rank_eval)")
@@ -246,6 +261,18 @@ def cli(argv=None):
         if not 1 <= args.exact_metrics <= 4096:
             parser.error("--exact-metrics B: B calibration bins, 1 .. 4096")
         config["train"]["report_exact"] = args.exact_metrics
+    if args.auc_ci is not None:
+        if not 1 <= args.auc_ci <= 65535:
+            parser.error("--auc-ci B: B bootstrap replicates, 1 .. 65535")
+        config["train"]["report_auc_ci"] = args.auc_ci
+    for flag, value, key in (("--auc-ci-unit", args.auc_ci_unit, "auc_ci_unit"), ("--auc-ci-seed", args.auc_ci_seed, "auc_ci_seed")):
+        if value is not None:
+            if not config["train"].get("report_auc_ci"):
+                parser.error("%s needs --auc-ci [B] (or train.report_auc_ci in the config)" % flag)
+            config["train"][key] = value
+    if args.auc_ci is not None:          # the flag's defaults, spelled out in the saved config
+        config["train"].setdefault("auc_ci_unit", "user")
+        config["train"].setdefault("auc_ci_seed", 0)
     if args.rank_eval is not None:
         config["train"]["rank_eval"] = [int(k) for k in args.rank_eval.split(",")]
     if args.sampled_eval is not None:

@@ -13,6 +13,9 @@
 //                             popcount(peers & lanes below), the wave's running count per digit lives in LDS; thread d
 //                             then turns the four waves' counts of digit d into their start offsets.
 //            Pass 0 forms the composites from pred / label on the fly; the last pass writes d_sorted_out when it is given.
+//            The same five passes sort mamdr_auc_bootstrap's wider word, key << 32 | positive << 31 | row, on its upper
+//            33 bits (launch_exact_sort with `rows`: every digit sits 31 bits higher, pass 0 forms that word).  The sort is
+//            stable and starts from file order, so the rows ascend inside equal (key, positive) pairs.
 //   scan     the device-wide scans are the three-launch form -- k_scan_sums (tile totals), the scan of the totals (the
 //            same two kernels again while they do not fit one tile), k_scan_apply (exclusive scan in place with the tile's
 //            carry) -- over a combine operator: AddU32 for the histograms, RunOp for the sorted array.
@@ -62,6 +65,7 @@ struct SortPass {
     uint32_t* hist;              // [RADIX][n_tiles]; counts, then (scanned in place) start offsets
     int64_t n, n_tiles;
     int shift;
+    int rows;                    // pass 0 forms key << 32 | positive << 31 | row (bootstrap_kernels.hip), not key << 1 | positive
 };
 
 // order-preserving key (gauc_kernels.hip's, a third copy of the few lines): NaN -> 0, -inf -> 0x007fffff, -0 and +0 ->
@@ -75,7 +79,8 @@ __device__ __forceinline__ uint32_t exact_key(float s) {
 
 __device__ __forceinline__ u64 exact_load(const SortPass& p, int64_t i) {
     if (p.src) return p.src[i];
-    return ((u64)exact_key(p.pred[i]) << 1) | (p.label[i] != 0.f ? 1ull : 0ull);
+    const u64 key = exact_key(p.pred[i]), positive = p.label[i] != 0.f ? 1ull : 0ull;
+    return p.rows ? ((key << 32) | (positive << 31) | (u64)i) : ((key << 1) | positive);
 }
 
 __global__ __launch_bounds__(THREADS) void k_exact_hist(const SortPass p) {
@@ -460,10 +465,11 @@ __global__ __launch_bounds__(THREADS) void k_exact_finish(const MetricPass m) {
     }
 }
 
-// the call's workspace: two composite buffers, the histograms, the tiles' runs and AP partials, the scans' upper levels
+// the call's workspace: two composite buffers, the histograms (the sort's part, which leads), the tiles' runs and AP
+// partials, the scans' upper levels
 struct ExactLayout {
     int64_t sort_tiles, metric_tiles;
-    size_t buf_a, buf_b, hist, hist_work, runs, runs_work, ap_part, bytes;
+    size_t buf_a, buf_b, hist, hist_work, sort_bytes, runs, runs_work, ap_part, bytes;
 };
 ExactLayout exact_layout(int64_t n) {
     ExactLayout l;
@@ -479,6 +485,7 @@ ExactLayout exact_layout(int64_t n) {
     l.buf_b = take((size_t)n * sizeof(u64));
     l.hist = take((size_t)RADIX * l.sort_tiles * sizeof(uint32_t));
     l.hist_work = take((size_t)scan_work((int64_t)RADIX * l.sort_tiles) * sizeof(uint32_t));
+    l.sort_bytes = at;
     l.runs = take((size_t)l.metric_tiles * sizeof(ExactRun));
     l.runs_work = take((size_t)scan_work(l.metric_tiles) * sizeof(ExactRun));
     l.ap_part = take((size_t)l.metric_tiles * sizeof(double));
@@ -489,8 +496,9 @@ ExactLayout exact_layout(int64_t n) {
 }  // namespace
 
 size_t exact_workspace_bytes(int64_t n) { return exact_layout(n).bytes; }
+size_t exact_sort_workspace_bytes(int64_t n) { return exact_layout(n).sort_bytes; }
 
-void launch_exact(const ExactArgs& a, hipStream_t s) {
+const unsigned long long* launch_exact_sort(const ExactSortArgs& a, hipStream_t s) {
     const ExactLayout l = exact_layout(a.n);
     u64* buf_a = reinterpret_cast<u64*>(a.ws + l.buf_a);
     u64* buf_b = reinterpret_cast<u64*>(a.ws + l.buf_b);
@@ -500,17 +508,31 @@ void launch_exact(const ExactArgs& a, hipStream_t s) {
     p.hist = reinterpret_cast<uint32_t*>(a.ws + l.hist);
     p.n = a.n;
     p.n_tiles = l.sort_tiles;
+    p.rows = a.rows;
     const u64* sorted = nullptr;
     for (int pass = 0; pass < PASSES; ++pass) {      // pred / label -> a -> b -> a -> b -> a (or the caller's array)
         p.src = pass == 0 ? nullptr : ((pass & 1) ? buf_a : buf_b);
         p.dst = (pass & 1) ? buf_b : buf_a;
         if (pass == PASSES - 1 && a.sorted_out) p.dst = a.sorted_out;
-        p.shift = pass * EXACT_RADIX_BITS;
+        p.shift = (a.rows ? 31 : 0) + pass * EXACT_RADIX_BITS;
         MAMDR_LAUNCH(k_exact_hist, dim3((unsigned)l.sort_tiles), dim3(THREADS), 0, s, p);
         scan_exclusive<AddU32>(p.hist, (int64_t)RADIX * l.sort_tiles, reinterpret_cast<uint32_t*>(a.ws + l.hist_work), s);
         MAMDR_LAUNCH(k_exact_scatter, dim3((unsigned)l.sort_tiles), dim3(THREADS), 0, s, p);
         sorted = p.dst;
     }
+    return sorted;
+}
+
+void launch_exact(const ExactArgs& a, hipStream_t s) {
+    const ExactLayout l = exact_layout(a.n);
+    ExactSortArgs sort;
+    sort.pred = a.pred;
+    sort.label = a.label;
+    sort.n = a.n;
+    sort.rows = 0;
+    sort.sorted_out = a.sorted_out;
+    sort.ws = a.ws;
+    const u64* sorted = launch_exact_sort(sort, s);
     MetricPass m;
     m.sorted = sorted;
     m.runs = reinterpret_cast<ExactRun*>(a.ws + l.runs);

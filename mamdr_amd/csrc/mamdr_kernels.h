@@ -946,6 +946,41 @@ struct ExactArgs {
 };
 size_t exact_workspace_bytes(int64_t n);
 void launch_exact(const ExactArgs& a, hipStream_t s);      // n > 0
+// the chain's radix sort on its own (launch_exact's first phase; bootstrap_kernels.hip sorts its wider word with it)
+struct ExactSortArgs {
+    const float* pred;                 // [n] in file order
+    const float* label;                // [n]
+    int64_t n;
+    int rows;                          // 0: the composites key << 1 | positive, sorted on bits 0 .. 32;
+                                       // 1: the words key << 32 | positive << 31 | row (n <= 2^31), sorted on bits 31 .. 63
+    unsigned long long* sorted_out;    // nullable [n]: the last pass scatters here
+    char* ws;                          // exact_sort_workspace_bytes(n) bytes, 16-byte aligned (the head of launch_exact's)
+};
+size_t exact_sort_workspace_bytes(int64_t n);
+const unsigned long long* launch_exact_sort(const ExactSortArgs& a, hipStream_t s);      // n > 0 -> the sorted array
+
+// bootstrap_kernels.hip: Poisson-bootstrap replicates of the exact AUC's integers (mamdr_auc_bootstrap).
+// (mamdr_amd/bootstrap.py carries the same constants for the tests)
+constexpr int BOOT_TILE = 1024;               // sorted positions per wave: 16 consecutive ones per lane, in registers
+constexpr int BOOT_GROUP = 16;                // replicates per workgroup: 4 waves x 4 replicates in turn
+constexpr int64_t BOOT_PART_WORDS = 1 << 24;  // 32-bit words of per-(tile, replicate) partials at a time (64 MiB): more
+                                              // replicates than fit run in chunks
+struct BootArgs {
+    const float* pred;                 // [n] in file order
+    const float* label;                // [n]
+    const int32_t* unit;               // nullable [n]: the resampling unit of a row; null = the row itself
+    int64_t n;
+    int n_rep;
+    uint64_t seed;
+    unsigned long long* T;             // [n_rep + 1], zeroed by the call
+    long long* P;                      // [n_rep + 1]
+    long long* N;                      // [n_rep + 1]
+    int64_t part_words;                // BOOT_PART_WORDS, or a test's smaller bound
+    char* ws;                          // boot_workspace_bytes(n, n_rep, part_words) bytes, 16-byte aligned
+};
+int boot_chunk(int64_t n, int n_rep, int64_t part_words);       // replicate slots per chunk, a multiple of BOOT_GROUP
+size_t boot_workspace_bytes(int64_t n, int n_rep, int64_t part_words);
+void launch_boot(const BootArgs& a, hipStream_t s);        // n > 0
 
 // gram_kernels.hip: fp64 Gram matrices of up to GRAM_MAX_VEC flat vectors over column ranges (mamdr_gram).  One GramArgs
 // describes a batch of up to GRAM_MAX_RANGES ranges: two launches

@@ -475,4 +475,49 @@ int mamdr_exact_metrics(const float* d_pred, const float* d_label, int64_t n, in
     return MAMDR_OK;
 }
 
+// ---- bootstrap replicates of the exact AUC's integers (bootstrap_kernels.hip): stateless as well
+int mamdr_auc_bootstrap_bounded(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
+                                uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, int64_t part_words, void* stream) {
+    if (!d_T || !d_P || !d_N) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: null T / P / N pointer");
+    if (n < 0 || n >= ((int64_t)1 << 27)) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: n %lld outside [0, 2^27)", (long long)n);
+    if (n_rep < 0 || n_rep > 65535) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: n_rep %d outside 0..65535", (int)n_rep);
+    if (part_words <= 0) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: part_words %lld is not positive", (long long)part_words);
+    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: null pred / label pointer");
+    if ((((uintptr_t)d_pred | (uintptr_t)d_label | (uintptr_t)d_unit) & 3) || (((uintptr_t)d_T | (uintptr_t)d_P | (uintptr_t)d_N) & 7))
+        return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t out_bytes = ((size_t)n_rep + 1) * sizeof(uint64_t);
+    HIP_TRY(hipMemsetAsync(d_T, 0, out_bytes, s));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_P, 0, out_bytes, s));
+        HIP_TRY(hipMemsetAsync(d_N, 0, out_bytes, s));
+        return MAMDR_OK;
+    }
+    BootArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.unit = d_unit;
+    a.n = n;
+    a.n_rep = n_rep;
+    a.seed = seed;
+    a.T = reinterpret_cast<unsigned long long*>(d_T);
+    a.P = reinterpret_cast<long long*>(d_P);
+    a.N = reinterpret_cast<long long*>(d_N);
+    a.part_words = part_words;
+    // the call's own scratch, ordered on its stream
+    HIP_TRY(hipMallocAsync((void**)&a.ws, boot_workspace_bytes(n, n_rep, part_words), s));
+    launch_boot(a, s);
+    hipError_t e = hipGetLastError();
+    const hipError_t ef = hipFreeAsync(a.ws, s);
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_auc_bootstrap: %s", hipGetErrorString(e));
+    return MAMDR_OK;
+}
+
+int mamdr_auc_bootstrap(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
+                        uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, void* stream) {
+    return mamdr_auc_bootstrap_bounded(d_pred, d_label, d_unit, n, n_rep, seed, d_T, d_P, d_N, BOOT_PART_WORDS, stream);
+}
+
 }  // extern "C"

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import bootstrap
 from . import exact
 from . import gauc
 from .recommend import exclusion_csr, slates_csr
@@ -426,15 +427,23 @@ class DeviceEngine(FlatVectorOps):
                                           opt, float(lr), _ptr(loss_out)))
         return n_steps
 
-    def evaluate(self, domain, split, want_preds=False, want_gauc=False, want_exact=0):
-        """model.evaluate(data, steps=n_step) -> (loss, auc[, hist, preds][, gauc report][, exact report]); syncs to read
-        back.  want_gauc (no reference counterpart): the predictions stay on the device, mamdr_group_auc runs behind the
+    def evaluate(self, domain, split, want_preds=False, want_gauc=False, want_exact=0, want_ci=None):
+        """model.evaluate(data, steps=n_step) -> (loss, auc[, hist, preds][, gauc report][, exact report][, ci report]); syncs
+        to read back.  want_gauc (no reference counterpart): the predictions stay on the device, mamdr_group_auc runs behind the
         evaluation on the engine's stream over the split's uid groups, and gauc.finish's report dict ends the tuple.
         want_exact = B > 0 (no reference counterpart either): mamdr_exact_metrics runs behind the evaluation likewise, with B
-        calibration bins, and exact.finish's report dict ends the tuple, after GAUC's when both are asked for."""
+        calibration bins, and exact.finish's report dict ends the tuple, after GAUC's when both are asked for.
+        want_ci = (n_rep, seed, "row" | "user") (no reference counterpart either): mamdr_auc_bootstrap runs behind the
+        evaluation likewise -- "user" resamples the bound split's uid column, "row" its rows --, and bootstrap.finish's report
+        dict ends the tuple, after GAUC's and exact's."""
         n = self.n_rows(domain, split)
         want_exact = int(want_exact or 0)
-        preds = torch.empty(n, dtype=torch.float32, device=self.device) if (want_preds or want_gauc or want_exact) else None
+        if want_ci is not None:
+            n_rep, ci_seed, ci_unit = want_ci
+            if ci_unit not in ("row", "user"):
+                raise ValueError("want_ci: the unit is 'row' or 'user', got %r" % (ci_unit,))
+        preds = torch.empty(n, dtype=torch.float32, device=self.device) \
+            if (want_preds or want_gauc or want_exact or want_ci is not None) else None
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         self._check(self._c_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1),
                                         _ptr(self._hist), _ptr(preds)))
@@ -442,6 +451,9 @@ class DeviceEngine(FlatVectorOps):
             res4 = self._group_auc_launch(preds, self.data[(domain, split)]["label"], self.group_auc_plan(domain, split))
         if want_exact:
             exact_out = self._exact_launch(preds, self.data[(domain, split)]["label"], want_exact)
+        if want_ci is not None:
+            cols = self.data[(domain, split)]
+            ci_out = self._bootstrap_launch(preds, cols["label"], n_rep, ci_seed, cols["uid"] if ci_unit == "user" else None)
         hist = self._hist.cpu().numpy().astype(np.int64)
         loss = float(self._loss1.cpu().numpy()[0])
         auc, _ = auc_from_histogram(hist)
@@ -452,7 +464,36 @@ class DeviceEngine(FlatVectorOps):
             out += (gauc.finish(*res4.cpu().numpy().tolist()),)
         if want_exact:
             out += (exact.finish(*[t.cpu().numpy() for t in exact_out[:3]]),)
+        if want_ci is not None:
+            out += (bootstrap.finish(*[t.cpu().numpy() for t in ci_out]),)
         return out
+
+    # ------------------------------------------------------------ bootstrap replicates of the exact AUC (no reference counterpart)
+    def _bootstrap_launch(self, preds, labels, n_rep, seed, unit=None, part_words=None):
+        """mamdr_auc_bootstrap on the engine's stream -> the device tensors (T, P, N), int64 [n_rep + 1] each (T holds
+        uint64 words); nothing is read back.  part_words (tests): mamdr_auc_bootstrap_bounded with that workspace bound."""
+        n, n_rep = int(preds.numel()), int(n_rep)
+        bootstrap.check_sizes(n, n_rep)
+        T, P, N = [torch.empty(n_rep + 1, dtype=torch.int64, device=self.device) for _ in range(3)]
+        args = (_ptr(preds if n else None), _ptr(labels if n else None), _ptr(unit if n else None), n, n_rep,
+                int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(T), _ptr(P), _ptr(N))
+        if part_words is None:
+            L.check(self.lib.mamdr_auc_bootstrap(*args, self._s()))
+        else:
+            L.check(self.lib.mamdr_auc_bootstrap_bounded(*args, int(part_words), self._s()))
+        return T, P, N
+
+    def auc_bootstrap(self, preds, labels, n_rep, seed=0, unit=None, level=0.95):
+        """bootstrap replicates of the exact AUC (bootstrap.py's definition) of device tensors preds / labels [n] fp32 and,
+        optionally, unit [n] int32 (the resampling unit of every row; None resamples rows) -> bootstrap.finish's report."""
+        if preds.numel() != labels.numel() or preds.dtype != torch.float32 or labels.dtype != torch.float32 \
+                or preds.device != self.device or labels.device != self.device:
+            raise ValueError("auc_bootstrap: preds and labels must be fp32 tensors of one length on the engine's device")
+        if unit is not None and (unit.numel() != preds.numel() or unit.dtype != torch.int32 or unit.device != self.device):
+            raise ValueError("auc_bootstrap: unit must be an int32 tensor of the predictions' length on the engine's device")
+        T, P, N = self._bootstrap_launch(preds.contiguous(), labels.contiguous(), n_rep, seed,
+                                         unit.contiguous() if unit is not None else None)
+        return bootstrap.finish(T.cpu().numpy().view(np.uint64), P.cpu().numpy(), N.cpu().numpy(), level)
 
     # ------------------------------------------------------------ exact AUC / AP / calibration (no reference counterpart)
     def _exact_launch(self, preds, labels, n_bins, want_sorted=False):

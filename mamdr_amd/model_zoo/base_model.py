@@ -43,6 +43,7 @@ class BaseModel(object):
                                            shuffle=getattr(dataset, "shuffle_train", True))
         self.gauc_reports = {}        # train.report_gauc: {(mode, domain): gauc.finish's report of the latest evaluation}
         self.exact_reports = {}       # train.report_exact: {(mode, domain): exact.finish's report of the latest evaluation}
+        self.ci_reports = {}          # train.report_auc_ci: {(mode, domain): bootstrap.finish's report of the latest evaluation}
         self.model = self.build_model()
         self._build_early_stop()
 
@@ -113,18 +114,33 @@ class BaseModel(object):
         caller has installed: the merged per-domain ones under MAMDR / DN, the finetuned ones in the finetune stage --,
         remembered per (mode, domain) for _summarise / save_result.  Under train.report_exact = B (not a key of the
         reference's configs either) it yields the exact AUC, average precision and B-bin calibration of the split (exact.py),
-        remembered likewise; early stopping, checkpoints and finetune decisions stay on the 500-threshold AUC."""
+        remembered likewise; early stopping, checkpoints and finetune decisions stay on the 500-threshold AUC.  Under
+        train.report_auc_ci = B (not a key of the reference's configs either) it yields B bootstrap replicates of the exact
+        AUC (bootstrap.py; train.auc_ci_unit "user" | "row", train.auc_ci_seed), remembered likewise; it decides nothing either."""
         want = {}
         if self.train_config.get("report_gauc"):
             want["want_gauc"] = True
         if self.train_config.get("report_exact"):
             want["want_exact"] = int(self.train_config["report_exact"])
+        if self.train_config.get("report_auc_ci"):
+            want["want_ci"] = self._auc_ci_request()
         out = self.model.evaluate(idx, mode, **want)          # (an engine sees a keyword only when its key is set)
-        for key, store in (("want_exact", self.exact_reports), ("want_gauc", self.gauc_reports)):      # from the tuple's end
+        for key, store in (("want_ci", self.ci_reports), ("want_exact", self.exact_reports),
+                           ("want_gauc", self.gauc_reports)):      # from the tuple's end
             if key in want:
                 store[(mode, idx)] = out[-1]
                 out = out[:-1]
         return out
+
+    def _auc_ci_request(self):
+        """train.report_auc_ci / auc_ci_seed / auc_ci_unit -> the engines' want_ci = (n_rep, seed, "row" | "user")."""
+        tc = self.train_config
+        n_rep, unit = int(tc["report_auc_ci"]), tc.get("auc_ci_unit", "user")
+        if not 1 <= n_rep <= 65535:
+            raise ValueError("train.report_auc_ci %d outside 1..65535" % n_rep)
+        if unit not in ("row", "user"):
+            raise ValueError("train.auc_ci_unit is 'row' or 'user', got %r" % (unit,))
+        return n_rep, int(tc.get("auc_ci_seed", 0)), unit
 
     # ------------------------------------------------------------------ retrieval (no reference counterpart)
     def _retrieval_problem(self, domain, users, exclude_seen):
@@ -319,6 +335,14 @@ class BaseModel(object):
             for name, key in (("Exact AUC", "auc"), ("AP", "ap"), ("ECE", "ece")):
                 self._format_print_domain_metric(name, {d: r[key] for d, r in reps.items()})
                 print("Overall {} {}: {}, Weighted {}: {}".format(mode, name, overall[key][0], name, overall[key][1]))
+        if self.train_config.get("report_auc_ci"):
+            n_rep, seed, unit = self._auc_ci_request()
+            print("Exact AUC, {} bootstrap replicates by {} (seed {}): estimate [95 % interval] standard error, valid".format(
+                n_rep, unit, seed))
+            for d in domain_auc:
+                if (mode, d) in self.ci_reports:
+                    r = self.ci_reports[(mode, d)]
+                    print("{}: {} [{}, {}] {}, {}".format(d, r["auc"], r["ci_lo"], r["ci_hi"], r["se"], r["n_valid"]))
         return avg_loss, avg_auc, domain_loss, domain_auc
 
     def _gauc_summary(self, mode, domains):
@@ -397,6 +421,17 @@ class BaseModel(object):
                 np.savez(osp.join(result_path, "exact_metrics.npz"), domains=np.array(list(reps), np.int64),
                          **{k: np.array([r[k] for r in reps.values()]).reshape(len(reps), -1)
                             for k in ("bin_rows", "bin_positives", "bin_pred_sum")})
+            if self.train_config.get("report_auc_ci"):       # likewise
+                from .. import bootstrap
+                reps = {d: self.ci_reports[("test", d)] for d in domain_auc if ("test", d) in self.ci_reports}
+                result.update(bootstrap.summarise(reps))
+                # what bootstrap.paired needs to compare two runs: per domain d the replicates and their integers
+                n_rep, seed, unit = self._auc_ci_request()
+                arrays = {"n_rep": np.int64(n_rep), "seed": np.uint64(seed & 0xFFFFFFFFFFFFFFFF), "unit": np.array(unit)}
+                for d, r in reps.items():
+                    for k in ("replicates", "T", "P", "N"):
+                        arrays["%s_%s" % (k, d)] = r[k]
+                np.savez(osp.join(result_path, "auc_bootstrap.npz"), **arrays)
             json.dump(result, f)
         self.save_model(osp.join(result_path, "model_parameters.npz"))
         return result_path

@@ -44,6 +44,7 @@ SOURCES = [
     ("mamdr_api.hip", []),
     ("step_context.hip", []),
     ("step_queries.hip", []),
+    ("eval_metrics.hip", []),
     ("step_stateless.hip", []),
 ]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function"]

@@ -110,13 +110,11 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     """run.py:71-89.  on_model(model) (optional) sees the built, wrapped model before training starts (tests attach
     their recorders there).  recommend = K (not an option of the reference's run.py): once the pipeline has ended, rank 0 /
     lane 0 ranks every domain's catalogue for its test users with the weights the run finished with and writes the top K
-    (recommend.report) to recommend_out, by default under train.result_save_path.  train.report_gauc (run.py --gauc; not a
-    key of the reference's configs): every evaluation also reports the per-user grouped AUC (gauc.py).  train.report_exact = B
-    (run.py --exact-metrics [B]; not a key of the reference's configs): every evaluation also reports the exact AUC, the average
-    precision and the calibration over B equal-mass bins (exact.py).  train.report_auc_ci = B (run.py --auc-ci [B]; not a key
-    of the reference's configs): every evaluation also draws B bootstrap replicates of the exact AUC, resampling
-    train.auc_ci_unit = "user" (default) or "row" under train.auc_ci_seed (default 0), and reports its standard error and
-    percentile interval (bootstrap.py); the test evaluation's replicates go to auc_bootstrap.npz.  train.rank_eval = [K,
+    (recommend.report) to recommend_out, by default under train.result_save_path.  train.report_gauc, train.report_exact
+    = B and train.report_auc_ci = B (run.py --gauc, --exact-metrics [B], --auc-ci [B]; no keys of the reference's configs):
+    every evaluation also yields the reports of reports.EVAL_REPORTS -- the per-user grouped AUC (gauc.py); the exact AUC,
+    average precision and calibration over B equal-mass bins (exact.py); B bootstrap replicates of the exact AUC by
+    train.auc_ci_unit = "user" (default) or "row" under train.auc_ci_seed (default 0) (bootstrap.py).  train.rank_eval = [K,
     ...] (run.py --rank-eval; not a key of the reference's configs either): once the pipeline has ended, the exact rank of every
     test positive in its domain's whole catalogue, with MRR, mean percentile and HitRate / Recall / NDCG at those K
     (recommend.rank_report), written under train.result_save_path.  train.sampled_eval = N (run.py --sampled-eval [N]; no key
@@ -126,6 +124,7 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     reference's configs): once the pipeline has ended, the domain-conflict report (conflict.report) over N batches per domain
     (0: whole passes), written to train.conflict_out or under train.result_save_path; result.json gains conflict_rate_all,
     mean_cosine_all, conflict_rate_meta and mean_cosine_meta."""
+    from .reports import EVAL_REPORTS
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
     name = config["model"]["name"]
@@ -133,18 +132,11 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     if (world > 1 or lanes > 1) and not ("meta" in name and ("mamdr" in name or "domain_negotiation" in name or "reptile" in name)):
         raise NotImplementedError("multi-process / multi-lane runs shard the MAMDR (DN + DR), Domain Negotiation and Reptile "
                                   "wrappers only; got '%s'" % name)
-    if config["train"].get("report_gauc") and (world > 1 or lanes > 1):
-        raise NotImplementedError("train.report_gauc (run.py --gauc): the per-user grouped AUC is not gathered across processes "
-                                  "or lanes (parallel.gather_domain_scalars carries loss and AUC only); run it with one "
-                                  "process and train.lanes = 1")
-    if config["train"].get("report_exact") and (world > 1 or lanes > 1):
-        raise NotImplementedError("train.report_exact (run.py --exact-metrics): the exact AUC, average precision and calibration "
-                                  "are not gathered across processes or lanes (parallel.gather_domain_scalars carries loss and "
-                                  "AUC only); run it with one process and train.lanes = 1")
-    if config["train"].get("report_auc_ci") and (world > 1 or lanes > 1):
-        raise NotImplementedError("train.report_auc_ci (run.py --auc-ci): the bootstrap replicates of the exact AUC are not "
-                                  "gathered across processes or lanes (parallel.gather_domain_scalars carries loss and AUC "
-                                  "only); run it with one process and train.lanes = 1")
+    for e in EVAL_REPORTS:
+        if config["train"].get(e.config_key) and (world > 1 or lanes > 1):
+            raise NotImplementedError("train.%s (run.py %s): %s not gathered across processes or lanes "
+                                      "(parallel.gather_domain_scalars carries loss and AUC only); run it with one process and "
+                                      "train.lanes = 1" % (e.config_key, e.flag, e.refusal))
     if config["train"].get("rank_eval") and (world > 1 or lanes > 1):
         raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
                                   "(the best phi_d slots are current only on their owners); run it with one process and "

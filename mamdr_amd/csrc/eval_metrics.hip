@@ -1,0 +1,141 @@
+// C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics and
+// mamdr_auc_bootstrap(_bounded).  Stateless, like the outer updates: no context, the caller's stream.  Host code only.
+#include "step_ctx.h"
+
+// a call's own scratch, ordered on its stream: `bytes` are allocated (nothing for 0), `run(ws)` launches and returns its
+// first HIP error, the scratch is freed -> MAMDR_OK, or MAMDR_EHIP with the first error of (allocation, run, free) behind `fn`
+template <typename F>
+static int with_scratch(const char* fn, size_t bytes, hipStream_t s, F run) {
+    char* ws = nullptr;
+    hipError_t e = bytes ? hipMallocAsync((void**)&ws, bytes, s) : hipSuccess;
+    if (e == hipSuccess) e = run(ws);
+    const hipError_t ef = ws ? hipFreeAsync(ws, s) : hipSuccess;
+    if (e == hipSuccess) e = ef;
+    if (e != hipSuccess) return fail(MAMDR_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    return MAMDR_OK;
+}
+
+extern "C" {
+
+// ---- per-user grouped AUC (gauc_kernels.hip)
+int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_order, int64_t n, const int64_t* d_group_off,
+                    int64_t n_groups, const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
+                    uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream) {
+    if (!d_result || !d_group_off) return fail(MAMDR_EINVAL, "mamdr_group_auc: null result / group offsets pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_group_auc: n %lld outside [0, 2^31)", (long long)n);
+    if (n_groups < 0 || n_groups > n)
+        return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld groups for %lld rows", (long long)n_groups, (long long)n);
+    if (n > 0 && (!d_pred || !d_label || !d_order)) return fail(MAMDR_EINVAL, "mamdr_group_auc: null pred / label / order pointer");
+    if (n_tiles < 0 || n_tiles > n) return fail(MAMDR_EINVAL, "mamdr_group_auc: n_tiles %lld for %lld rows", (long long)n_tiles, (long long)n);
+    if (n_tiles == 0 && (d_tile_group || d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: a tile list given without tiles");
+    if (n_tiles > 0 && (!d_tile_group || !d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld tiles need both of their lists", (long long)n_tiles);
+    if (misaligned(3, d_pred, d_label, d_order, d_tile_group, d_P) || misaligned(7, d_group_off, d_tile_first, d_T, d_result))
+        return fail(MAMDR_EINVAL, "mamdr_group_auc: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    GaucArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.order = d_order;
+    a.group_off = d_group_off;
+    a.tile_group = d_tile_group;
+    a.tile_first = d_tile_first;
+    a.n = n;
+    a.n_groups = n_groups;
+    a.n_tiles = n_tiles;
+    a.n_parts = gauc_parts(n_groups);
+    a.result = d_result;
+    // the scratch: [T if not given | partial sums | P if not given]
+    const size_t t_bytes = d_T ? 0 : (size_t)n_groups * sizeof(uint64_t);
+    const size_t part_bytes = (size_t)a.n_parts * (sizeof(double) + 2 * sizeof(uint64_t));
+    const size_t p_bytes = d_P ? 0 : (size_t)n_groups * sizeof(uint32_t);
+    return with_scratch("mamdr_group_auc", t_bytes + part_bytes + p_bytes, s, [&](char* ws) {
+        a.T = d_T ? reinterpret_cast<unsigned long long*>(d_T) : reinterpret_cast<unsigned long long*>(ws);
+        a.part_num = reinterpret_cast<double*>(ws + t_bytes);
+        a.part_rows = reinterpret_cast<unsigned long long*>(a.part_num + a.n_parts);
+        a.part_valid = a.part_rows + a.n_parts;
+        a.P = d_P ? d_P : reinterpret_cast<uint32_t*>(ws + t_bytes + part_bytes);
+        if (n_groups > 0) {
+            if (hipError_t e = hipMemsetAsync(a.T, 0, (size_t)n_groups * sizeof(uint64_t), s)) return e;
+            if (hipError_t e = hipMemsetAsync(a.P, 0, (size_t)n_groups * sizeof(uint32_t), s)) return e;
+        }
+        launch_gauc(a, s);
+        return hipGetLastError();
+    });
+}
+
+// ---- exact AUC, average precision and calibration bins of one split (exact_kernels.hip)
+int mamdr_exact_metrics(const float* d_pred, const float* d_label, int64_t n, int32_t n_bins, int64_t* d_counts, double* d_ap,
+                        int64_t* d_bins, int64_t* d_sorted_out, void* stream) {
+    if (!d_counts || !d_ap || !d_bins) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: null counts / ap / bins pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: n %lld outside [0, 2^31)", (long long)n);
+    if (n_bins < 1 || n_bins > MAMDR_EXACT_MAX_BINS)
+        return fail(MAMDR_EINVAL, "mamdr_exact_metrics: n_bins %d outside 1..%d", (int)n_bins, MAMDR_EXACT_MAX_BINS);
+    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: null pred / label pointer");
+    if (misaligned(3, d_pred, d_label) || misaligned(7, d_counts, d_ap, d_bins, d_sorted_out))
+        return fail(MAMDR_EINVAL, "mamdr_exact_metrics: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    ExactArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.n = n;
+    a.n_bins = n_bins;
+    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
+    a.ap = d_ap;
+    a.bins = reinterpret_cast<unsigned long long*>(d_bins);
+    a.sorted_out = reinterpret_cast<unsigned long long*>(d_sorted_out);
+    HIP_TRY(hipMemsetAsync(d_counts, 0, 5 * sizeof(int64_t), s));
+    HIP_TRY(hipMemsetAsync(d_ap, 0, sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(d_bins, 0, 3 * (size_t)n_bins * sizeof(int64_t), s));
+    if (n == 0) return MAMDR_OK;
+    return with_scratch("mamdr_exact_metrics", exact_workspace_bytes(n), s, [&](char* ws) {
+        a.ws = ws;
+        launch_exact(a, s);
+        return hipGetLastError();
+    });
+}
+
+// ---- bootstrap replicates of the exact AUC's integers (bootstrap_kernels.hip)
+int mamdr_auc_bootstrap_bounded(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
+                                uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, int64_t part_words, void* stream) {
+    if (!d_T || !d_P || !d_N) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: null T / P / N pointer");
+    if (n < 0 || n >= ((int64_t)1 << 27)) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: n %lld outside [0, 2^27)", (long long)n);
+    if (n_rep < 0 || n_rep > 65535) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: n_rep %d outside 0..65535", (int)n_rep);
+    if (part_words <= 0) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: part_words %lld is not positive", (long long)part_words);
+    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: null pred / label pointer");
+    if (misaligned(3, d_pred, d_label, d_unit) || misaligned(7, d_T, d_P, d_N))
+        return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t out_bytes = ((size_t)n_rep + 1) * sizeof(uint64_t);
+    HIP_TRY(hipMemsetAsync(d_T, 0, out_bytes, s));
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_P, 0, out_bytes, s));
+        HIP_TRY(hipMemsetAsync(d_N, 0, out_bytes, s));
+        return MAMDR_OK;
+    }
+    BootArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.unit = d_unit;
+    a.n = n;
+    a.n_rep = n_rep;
+    a.seed = seed;
+    a.T = reinterpret_cast<unsigned long long*>(d_T);
+    a.P = reinterpret_cast<long long*>(d_P);
+    a.N = reinterpret_cast<long long*>(d_N);
+    a.part_words = part_words;
+    return with_scratch("mamdr_auc_bootstrap", boot_workspace_bytes(n, n_rep, part_words), s, [&](char* ws) {
+        a.ws = ws;
+        launch_boot(a, s);
+        return hipGetLastError();
+    });
+}
+
+int mamdr_auc_bootstrap(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
+                        uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, void* stream) {
+    return mamdr_auc_bootstrap_bounded(d_pred, d_label, d_unit, n, n_rep, seed, d_T, d_P, d_N, BOOT_PART_WORDS, stream);
+}
+
+}  // extern "C"

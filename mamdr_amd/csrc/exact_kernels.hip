@@ -68,18 +68,10 @@ struct SortPass {
     int rows;                    // pass 0 forms key << 32 | positive << 31 | row (bootstrap_kernels.hip), not key << 1 | positive
 };
 
-// order-preserving key (gauc_kernels.hip's, a third copy of the few lines): NaN -> 0, -inf -> 0x007fffff, -0 and +0 ->
-// 0x80000000, +inf -> 0xff800000
-__device__ __forceinline__ uint32_t exact_key(float s) {
-    if (s != s) return 0u;
-    if (s == 0.f) return 0x80000000u;
-    const uint32_t b = __float_as_uint(s);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
+// (key: score_key, mamdr_kernels.h)
 __device__ __forceinline__ u64 exact_load(const SortPass& p, int64_t i) {
     if (p.src) return p.src[i];
-    const u64 key = exact_key(p.pred[i]), positive = p.label[i] != 0.f ? 1ull : 0ull;
+    const u64 key = score_key(p.pred[i]), positive = p.label[i] != 0.f ? 1ull : 0ull;
     return p.rows ? ((key << 32) | (positive << 31) | (u64)i) : ((key << 1) | positive);
 }
 

@@ -45,20 +45,12 @@ constexpr int TERMS_PER_BLOCK = GAUC_THREADS * TERMS_PER_THREAD;       // 2,048 
 static_assert(GAUC_TILE == GAUC_THREADS, "one thread per tile position");
 static_assert(GAUC_SMALL == 64, "one lane per row of a small group");
 
-// order-preserving key of the definition's comparison (a second copy of recommend_kernels.hip's few lines, with the
-// definition's -0 == +0): NaN -> 0, -inf -> 0x007fffff, -0 and +0 -> 0x80000000, +inf -> 0xff800000
-__device__ __forceinline__ uint32_t gauc_key(float s) {
-    if (s != s) return 0u;
-    if (s == 0.f) return 0x80000000u;
-    const uint32_t b = __float_as_uint(s);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// (key, is-positive) of the row at position `pos` of `order`; a row index outside the split is clamped into it
+// (key, is-positive) of the row at position `pos` of `order`, the key being score_key (mamdr_kernels.h): the definition's
+// comparison; a row index outside the split is clamped into it
 __device__ __forceinline__ uint32_t gauc_row(const GaucArgs& a, int64_t pos, bool& positive) {
     const int row = clampi(a.order[pos], 0, (int)(a.n - 1));
     positive = a.label[row] != 0.f;
-    return gauc_key(a.pred[row]);
+    return score_key(a.pred[row]);
 }
 
 __global__ __launch_bounds__(GAUC_THREADS) void k_gauc_small(const GaucArgs a) {

@@ -101,6 +101,11 @@ inline void tf_beta_powers(float beta1, float beta2, int64_t steps, float* b1p, 
 }
 
 // ---- argument checks of both C ABIs (MAMDR_OK or the code that `err` now explains)
+// whether one of the pointers is not aligned to its element size, `mask` = that size - 1 (3, 7); a null pointer is aligned
+template <typename... P>
+inline bool misaligned(uintptr_t mask, const P*... ptrs) {
+    return ((... | (uintptr_t)ptrs) & mask) != 0;
+}
 inline int check_state_ptrs(ErrBuf& err, const float* p, const float* m, const float* v) {
     if (!p || !m || !v) return err.fail(MAMDR_EINVAL, "null state pointer");
     if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) return err.fail(MAMDR_EINVAL, "state pointers must be 16-byte aligned");

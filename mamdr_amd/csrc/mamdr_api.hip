@@ -5,7 +5,7 @@
 // global inner-step counter that indexes the dropout stream, and a private
 // workspace sized for max_batch.  Everything numeric runs in the kernels of
 // step_kernels.hip / outer_kernels.hip on the context's stream.  The context itself, the queries and the stateless
-// entry points live in step_context.hip, step_queries.hip and step_stateless.hip (map: step_ctx.h).
+// entry points live in step_context.hip, step_queries.hip, eval_metrics.hip and step_stateless.hip (map: step_ctx.h).
 #include <algorithm>
 #include <cmath>
 

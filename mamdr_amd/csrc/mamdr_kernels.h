@@ -904,6 +904,16 @@ struct SlateArgs {
 // n_query: workgroups of shorter slates and behind a slate's end leave at once
 void launch_slate_order(const SlateArgs& a, int64_t max_len, bool any_short, hipStream_t s);
 
+// the order-preserving 32-bit key of a prediction, as mamdr_group_auc, mamdr_exact_metrics and mamdr_auc_bootstrap compare
+// scores (gauc_kernels.hip, exact_kernels.hip): NaN -> 0, below everything and equal to NaN; -0 and +0 -> 0x80000000; every
+// other value ordered as its float (-inf -> 0x007fffff, +inf -> 0xff800000)
+__device__ __forceinline__ uint32_t score_key(float s) {
+    if (s != s) return 0u;
+    if (s == 0.f) return 0x80000000u;
+    const uint32_t b = __float_as_uint(s);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
 // gauc_kernels.hip: per-user grouped AUC of one split's predictions (mamdr_group_auc)
 constexpr int GAUC_SMALL = 64;        // groups of up to this many rows: one wave each (k_gauc_small)
 constexpr int GAUC_TILE = 256;        // larger groups: positions per workgroup of k_gauc_tiles

@@ -1,11 +1,13 @@
 // Internal header of the step engine's host side: the context (mamdr_ctx), the profiling slots (Prof) and the few helpers
-// that cross its four files --
+// that cross its five files --
 //   step_context.hip    the context: create / destroy, counts, segments, bindings, counters, environment table, profiling
 //                       slots, tile setters
 //   mamdr_api.hip       the training call: its decisions, CallPlan / plan_call, the three step functions, the pre-gather
 //                       entry points, mamdr_train_steps(_n)
-//   step_queries.hip    mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain), mamdr_rank_domain, mamdr_rank_slates,
-//                       mamdr_group_auc
+//   step_queries.hip    the queries of a context: mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain),
+//                       mamdr_rank_domain, mamdr_rank_slates
+//   eval_metrics.hip    the metrics of an evaluation's predictions, no context: mamdr_group_auc, mamdr_exact_metrics,
+//                       mamdr_auc_bootstrap(_bounded)
 //   step_stateless.hip  the outer updates, mamdr_adam_apply, mamdr_pcgrad_project, mamdr_copy, mamdr_gram, the shuffle
 // Helpers that one file uses stay static in it.
 #pragma once
@@ -20,7 +22,7 @@
 #include "mamdr_kernels.h"
 #include "host_common.h"
 
-using namespace mamdr;       // (this header is private to the four host files above, each of which works in that namespace)
+using namespace mamdr;       // (this header is private to the five host files above, each of which works in that namespace)
 
 // mamdr_last_error's text (step_context.hip).  Like g_prof_stop it keeps default visibility, inside namespace mamdr: a hidden
 // extern thread_local is reached through a weak init symbol that is absent for a constant-initialised object

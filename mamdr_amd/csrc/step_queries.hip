@@ -1,6 +1,6 @@
-// C ABI of libmamdr_hip.so, the queries of a step-kernel context: evaluation of a split, the gathered input rows, top-K
-// retrieval, the exact ranks of target items, per-query candidate slates, and the (stateless) per-user grouped AUC of any
-// evaluation's predictions.
+// C ABI of libmamdr_hip.so, the queries of a step-kernel context: evaluation of a split (mamdr_eval_domain), the gathered
+// input rows (mamdr_gather_rows), top-K retrieval (mamdr_recommend(_domain)), the exact ranks of target items
+// (mamdr_rank_domain) and per-query candidate slates (mamdr_rank_slates).  (The metrics of predictions: eval_metrics.hip.)
 #include <algorithm>
 
 #include "step_ctx.h"
@@ -156,8 +156,7 @@ static int recommend_body(mamdr_ctx* c, const char* fn, int32_t domain, int32_t 
     if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
     if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
         return fail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
-    if ((((uintptr_t)d_uid | (uintptr_t)d_domain | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_ids_out |
-          (uintptr_t)d_scores_out | (uintptr_t)d_scores_all) & 3) || ((uintptr_t)d_excl_off & 7))
+    if (misaligned(3, d_uid, d_domain, d_cand, d_excl_ids, d_ids_out, d_scores_out, d_scores_all) || misaligned(7, d_excl_off))
         return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
     if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
         return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
@@ -261,8 +260,7 @@ int mamdr_rank_domain(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32
     if (d_cand && n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
     if (!d_uid || !d_tgt_off || !d_rank_out || !d_live_out)
         return fail(MAMDR_EINVAL, "%s: null uid / target offsets / rank / live output pointer", fn);
-    if ((((uintptr_t)d_uid | (uintptr_t)d_cand | (uintptr_t)d_excl_ids | (uintptr_t)d_tgt_ids | (uintptr_t)d_rank_out |
-          (uintptr_t)d_score_out | (uintptr_t)d_live_out) & 3) || (((uintptr_t)d_excl_off | (uintptr_t)d_tgt_off) & 7))
+    if (misaligned(3, d_uid, d_cand, d_excl_ids, d_tgt_ids, d_rank_out, d_score_out, d_live_out) || misaligned(7, d_excl_off, d_tgt_off))
         return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
     if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
         return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
@@ -323,8 +321,7 @@ int mamdr_rank_slates(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32
         return fail(MAMDR_EINVAL, "mamdr_rank_slates: domain %d outside [0, %d)", domain, c->cfg.n_domain);
     if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
     if (!d_uid || !d_slate_off || !d_pos_out) return fail(MAMDR_EINVAL, "%s: null uid / slate offsets / position output pointer", fn);
-    if ((((uintptr_t)d_uid | (uintptr_t)d_slate_ids | (uintptr_t)d_score_out | (uintptr_t)d_pos_out | (uintptr_t)d_order_out) & 3) ||
-        ((uintptr_t)d_slate_off & 7))
+    if (misaligned(3, d_uid, d_slate_ids, d_score_out, d_pos_out, d_order_out) || misaligned(7, d_slate_off))
         return fail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
     if (ready(c)) return MAMDR_ESTATE;
     std::vector<int64_t> off;
@@ -380,144 +377,6 @@ int mamdr_rank_slates(mamdr_ctx* c, int32_t domain, int32_t n_query, const int32
     prof_break(c);
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;
-}
-
-// ---- per-user grouped AUC (gauc_kernels.hip): stateless, like the outer updates
-int mamdr_group_auc(const float* d_pred, const float* d_label, const int32_t* d_order, int64_t n, const int64_t* d_group_off,
-                    int64_t n_groups, const int32_t* d_tile_group, const int64_t* d_tile_first, int64_t n_tiles,
-                    uint64_t* d_T, uint32_t* d_P, double* d_result, void* stream) {
-    if (!d_result || !d_group_off) return fail(MAMDR_EINVAL, "mamdr_group_auc: null result / group offsets pointer");
-    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_group_auc: n %lld outside [0, 2^31)", (long long)n);
-    if (n_groups < 0 || n_groups > n)
-        return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld groups for %lld rows", (long long)n_groups, (long long)n);
-    if (n > 0 && (!d_pred || !d_label || !d_order)) return fail(MAMDR_EINVAL, "mamdr_group_auc: null pred / label / order pointer");
-    if (n_tiles < 0 || n_tiles > n) return fail(MAMDR_EINVAL, "mamdr_group_auc: n_tiles %lld for %lld rows", (long long)n_tiles, (long long)n);
-    if (n_tiles == 0 && (d_tile_group || d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: a tile list given without tiles");
-    if (n_tiles > 0 && (!d_tile_group || !d_tile_first)) return fail(MAMDR_EINVAL, "mamdr_group_auc: %lld tiles need both of their lists", (long long)n_tiles);
-    if ((((uintptr_t)d_pred | (uintptr_t)d_label | (uintptr_t)d_order | (uintptr_t)d_tile_group | (uintptr_t)d_P) & 3) ||
-        (((uintptr_t)d_group_off | (uintptr_t)d_tile_first | (uintptr_t)d_T | (uintptr_t)d_result) & 7))
-        return fail(MAMDR_EINVAL, "mamdr_group_auc: a pointer is not aligned to its element size");
-    hipStream_t s = (hipStream_t)stream;
-    GaucArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pred = d_pred;
-    a.label = d_label;
-    a.order = d_order;
-    a.group_off = d_group_off;
-    a.tile_group = d_tile_group;
-    a.tile_first = d_tile_first;
-    a.n = n;
-    a.n_groups = n_groups;
-    a.n_tiles = n_tiles;
-    a.n_parts = gauc_parts(n_groups);
-    a.result = d_result;
-    // the call's own scratch, ordered on its stream: [T if not given | partial sums | P if not given]
-    const size_t t_bytes = d_T ? 0 : (size_t)n_groups * sizeof(uint64_t);
-    const size_t part_bytes = (size_t)a.n_parts * (sizeof(double) + 2 * sizeof(uint64_t));
-    const size_t p_bytes = d_P ? 0 : (size_t)n_groups * sizeof(uint32_t);
-    char* ws = nullptr;
-    if (t_bytes + part_bytes + p_bytes) HIP_TRY(hipMallocAsync((void**)&ws, t_bytes + part_bytes + p_bytes, s));
-    a.T = d_T ? reinterpret_cast<unsigned long long*>(d_T) : reinterpret_cast<unsigned long long*>(ws);
-    a.part_num = reinterpret_cast<double*>(ws + t_bytes);
-    a.part_rows = reinterpret_cast<unsigned long long*>(a.part_num + a.n_parts);
-    a.part_valid = a.part_rows + a.n_parts;
-    a.P = d_P ? d_P : reinterpret_cast<uint32_t*>(ws + t_bytes + part_bytes);
-    hipError_t e = hipSuccess;
-    if (n_groups > 0) {
-        e = hipMemsetAsync(a.T, 0, (size_t)n_groups * sizeof(uint64_t), s);
-        if (e == hipSuccess) e = hipMemsetAsync(a.P, 0, (size_t)n_groups * sizeof(uint32_t), s);
-    }
-    if (e == hipSuccess) {
-        launch_gauc(a, s);
-        e = hipGetLastError();
-    }
-    if (ws) {
-        const hipError_t ef = hipFreeAsync(ws, s);
-        if (e == hipSuccess) e = ef;
-    }
-    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_group_auc: %s", hipGetErrorString(e));
-    return MAMDR_OK;
-}
-
-// ---- exact AUC, average precision and calibration bins of one split (exact_kernels.hip): stateless as well
-int mamdr_exact_metrics(const float* d_pred, const float* d_label, int64_t n, int32_t n_bins, int64_t* d_counts, double* d_ap,
-                        int64_t* d_bins, int64_t* d_sorted_out, void* stream) {
-    if (!d_counts || !d_ap || !d_bins) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: null counts / ap / bins pointer");
-    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: n %lld outside [0, 2^31)", (long long)n);
-    if (n_bins < 1 || n_bins > MAMDR_EXACT_MAX_BINS)
-        return fail(MAMDR_EINVAL, "mamdr_exact_metrics: n_bins %d outside 1..%d", (int)n_bins, MAMDR_EXACT_MAX_BINS);
-    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_exact_metrics: null pred / label pointer");
-    if ((((uintptr_t)d_pred | (uintptr_t)d_label) & 3) ||
-        (((uintptr_t)d_counts | (uintptr_t)d_ap | (uintptr_t)d_bins | (uintptr_t)d_sorted_out) & 7))
-        return fail(MAMDR_EINVAL, "mamdr_exact_metrics: a pointer is not aligned to its element size");
-    hipStream_t s = (hipStream_t)stream;
-    ExactArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pred = d_pred;
-    a.label = d_label;
-    a.n = n;
-    a.n_bins = n_bins;
-    a.counts = reinterpret_cast<unsigned long long*>(d_counts);
-    a.ap = d_ap;
-    a.bins = reinterpret_cast<unsigned long long*>(d_bins);
-    a.sorted_out = reinterpret_cast<unsigned long long*>(d_sorted_out);
-    HIP_TRY(hipMemsetAsync(d_counts, 0, 5 * sizeof(int64_t), s));
-    HIP_TRY(hipMemsetAsync(d_ap, 0, sizeof(double), s));
-    HIP_TRY(hipMemsetAsync(d_bins, 0, 3 * (size_t)n_bins * sizeof(int64_t), s));
-    if (n == 0) return MAMDR_OK;
-    // the call's own scratch, ordered on its stream
-    HIP_TRY(hipMallocAsync((void**)&a.ws, exact_workspace_bytes(n), s));
-    launch_exact(a, s);
-    hipError_t e = hipGetLastError();
-    const hipError_t ef = hipFreeAsync(a.ws, s);
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_exact_metrics: %s", hipGetErrorString(e));
-    return MAMDR_OK;
-}
-
-// ---- bootstrap replicates of the exact AUC's integers (bootstrap_kernels.hip): stateless as well
-int mamdr_auc_bootstrap_bounded(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
-                                uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, int64_t part_words, void* stream) {
-    if (!d_T || !d_P || !d_N) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: null T / P / N pointer");
-    if (n < 0 || n >= ((int64_t)1 << 27)) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: n %lld outside [0, 2^27)", (long long)n);
-    if (n_rep < 0 || n_rep > 65535) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: n_rep %d outside 0..65535", (int)n_rep);
-    if (part_words <= 0) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: part_words %lld is not positive", (long long)part_words);
-    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: null pred / label pointer");
-    if ((((uintptr_t)d_pred | (uintptr_t)d_label | (uintptr_t)d_unit) & 3) || (((uintptr_t)d_T | (uintptr_t)d_P | (uintptr_t)d_N) & 7))
-        return fail(MAMDR_EINVAL, "mamdr_auc_bootstrap: a pointer is not aligned to its element size");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t out_bytes = ((size_t)n_rep + 1) * sizeof(uint64_t);
-    HIP_TRY(hipMemsetAsync(d_T, 0, out_bytes, s));
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(d_P, 0, out_bytes, s));
-        HIP_TRY(hipMemsetAsync(d_N, 0, out_bytes, s));
-        return MAMDR_OK;
-    }
-    BootArgs a;
-    memset(&a, 0, sizeof(a));
-    a.pred = d_pred;
-    a.label = d_label;
-    a.unit = d_unit;
-    a.n = n;
-    a.n_rep = n_rep;
-    a.seed = seed;
-    a.T = reinterpret_cast<unsigned long long*>(d_T);
-    a.P = reinterpret_cast<long long*>(d_P);
-    a.N = reinterpret_cast<long long*>(d_N);
-    a.part_words = part_words;
-    // the call's own scratch, ordered on its stream
-    HIP_TRY(hipMallocAsync((void**)&a.ws, boot_workspace_bytes(n, n_rep, part_words), s));
-    launch_boot(a, s);
-    hipError_t e = hipGetLastError();
-    const hipError_t ef = hipFreeAsync(a.ws, s);
-    if (e == hipSuccess) e = ef;
-    if (e != hipSuccess) return fail(MAMDR_EHIP, "mamdr_auc_bootstrap: %s", hipGetErrorString(e));
-    return MAMDR_OK;
-}
-
-int mamdr_auc_bootstrap(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
-                        uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, void* stream) {
-    return mamdr_auc_bootstrap_bounded(d_pred, d_label, d_unit, n, n_rep, seed, d_T, d_P, d_N, BOOT_PART_WORDS, stream);
 }
 
 }  // extern "C"

@@ -24,6 +24,7 @@ from . import _lib as L
 from . import bootstrap
 from . import exact
 from . import gauc
+from . import reports
 from .recommend import exclusion_csr, slates_csr
 
 
@@ -298,7 +299,6 @@ class DeviceEngine(FlatVectorOps):
             self._check(self._c_bind_aux(self.ctx, _ptr(self.aux)))
         self.tables = {}
         self.data = {}          # (domain, split) -> dict of device columns
-        self._gauc_plans = {}   # (domain, split) -> the split's grouping by uid on the device (group_auc_plan)
         self._acc = None
         self._ema = None            # set_moving_average
         self._hist = torch.zeros(2 * 501, dtype=torch.int32, device=self.device)
@@ -387,7 +387,6 @@ class DeviceEngine(FlatVectorOps):
             "label": torch.from_numpy(np.ascontiguousarray(label, np.float32)).to(self.device),
         }
         self.data[(domain, split)] = cols
-        self._gauc_plans.pop((domain, split), None)         # (the grouping by uid of the rows bound before)
         self._check(self._c_bind_domain_data(self.ctx, domain, split_id, _ptr(cols["uid"]), _ptr(cols["pid"]),
                                              _ptr(cols["domain"]), _ptr(cols["label"]), uid.shape[0]))
 
@@ -429,44 +428,35 @@ class DeviceEngine(FlatVectorOps):
 
     def evaluate(self, domain, split, want_preds=False, want_gauc=False, want_exact=0, want_ci=None):
         """model.evaluate(data, steps=n_step) -> (loss, auc[, hist, preds][, gauc report][, exact report][, ci report]); syncs
-        to read back.  want_gauc (no reference counterpart): the predictions stay on the device, mamdr_group_auc runs behind the
-        evaluation on the engine's stream over the split's uid groups, and gauc.finish's report dict ends the tuple.
-        want_exact = B > 0 (no reference counterpart either): mamdr_exact_metrics runs behind the evaluation likewise, with B
-        calibration bins, and exact.finish's report dict ends the tuple, after GAUC's when both are asked for.
-        want_ci = (n_rep, seed, "row" | "user") (no reference counterpart either): mamdr_auc_bootstrap runs behind the
-        evaluation likewise -- "user" resamples the bound split's uid column, "row" its rows --, and bootstrap.finish's report
-        dict ends the tuple, after GAUC's and exact's."""
+        to read back.  The reports (reports.EVAL_REPORTS; none has a reference counterpart): the predictions stay on the device,
+        the report's chain runs behind the evaluation on the engine's stream, and its finished dict ends the tuple, in table
+        order.  want_gauc: mamdr_group_auc over the split's uid groups (gauc.finish).  want_exact = B > 0: mamdr_exact_metrics
+        with B calibration bins (exact.finish).  want_ci = (n_rep, seed, "row" | "user"): mamdr_auc_bootstrap, "user"
+        resampling the bound split's uid column, "row" its rows (bootstrap.finish)."""
         n = self.n_rows(domain, split)
-        want_exact = int(want_exact or 0)
-        if want_ci is not None:
-            n_rep, ci_seed, ci_unit = want_ci
+        want = {"want_gauc": want_gauc, "want_exact": int(want_exact or 0), "want_ci": want_ci}
+        wanted = [(e, want[e.keyword]) for e in reports.EVAL_REPORTS if want[e.keyword] not in (None, False, 0)]   # (the defaults)
+        if want_ci is not None:             # (before anything is launched)
+            _, _, ci_unit = want_ci
             if ci_unit not in ("row", "user"):
                 raise ValueError("want_ci: the unit is 'row' or 'user', got %r" % (ci_unit,))
-        preds = torch.empty(n, dtype=torch.float32, device=self.device) \
-            if (want_preds or want_gauc or want_exact or want_ci is not None) else None
+        preds = torch.empty(n, dtype=torch.float32, device=self.device) if (want_preds or wanted) else None
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         self._check(self._c_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1),
                                         _ptr(self._hist), _ptr(preds)))
-        if want_gauc:
-            res4 = self._group_auc_launch(preds, self.data[(domain, split)]["label"], self.group_auc_plan(domain, split))
-        if want_exact:
-            exact_out = self._exact_launch(preds, self.data[(domain, split)]["label"], want_exact)
-        if want_ci is not None:
-            cols = self.data[(domain, split)]
-            ci_out = self._bootstrap_launch(preds, cols["label"], n_rep, ci_seed, cols["uid"] if ci_unit == "user" else None)
+        launched = [(e, e.launch(self, preds, self.data[(domain, split)], req)) for e, req in wanted]
         hist = self._hist.cpu().numpy().astype(np.int64)
         loss = float(self._loss1.cpu().numpy()[0])
         auc, _ = auc_from_histogram(hist)
         out = (loss, auc)
         if want_preds:
             out += (hist.reshape(2, 501), preds.cpu().numpy())
-        if want_gauc:
-            out += (gauc.finish(*res4.cpu().numpy().tolist()),)
-        if want_exact:
-            out += (exact.finish(*[t.cpu().numpy() for t in exact_out[:3]]),)
-        if want_ci is not None:
-            out += (bootstrap.finish(*[t.cpu().numpy() for t in ci_out]),)
-        return out
+        return out + tuple(e.finish(tensors) for e, tensors in launched)
+
+    def _check_pair(self, what, preds, labels):
+        if preds.numel() != labels.numel() or preds.dtype != torch.float32 or labels.dtype != torch.float32 \
+                or preds.device != self.device or labels.device != self.device:
+            raise ValueError("%s: preds and labels must be fp32 tensors of one length on the engine's device" % what)
 
     # ------------------------------------------------------------ bootstrap replicates of the exact AUC (no reference counterpart)
     def _bootstrap_launch(self, preds, labels, n_rep, seed, unit=None, part_words=None):
@@ -486,9 +476,7 @@ class DeviceEngine(FlatVectorOps):
     def auc_bootstrap(self, preds, labels, n_rep, seed=0, unit=None, level=0.95):
         """bootstrap replicates of the exact AUC (bootstrap.py's definition) of device tensors preds / labels [n] fp32 and,
         optionally, unit [n] int32 (the resampling unit of every row; None resamples rows) -> bootstrap.finish's report."""
-        if preds.numel() != labels.numel() or preds.dtype != torch.float32 or labels.dtype != torch.float32 \
-                or preds.device != self.device or labels.device != self.device:
-            raise ValueError("auc_bootstrap: preds and labels must be fp32 tensors of one length on the engine's device")
+        self._check_pair("auc_bootstrap", preds, labels)
         if unit is not None and (unit.numel() != preds.numel() or unit.dtype != torch.int32 or unit.device != self.device):
             raise ValueError("auc_bootstrap: unit must be an int32 tensor of the predictions' length on the engine's device")
         T, P, N = self._bootstrap_launch(preds.contiguous(), labels.contiguous(), n_rep, seed,
@@ -513,9 +501,7 @@ class DeviceEngine(FlatVectorOps):
     def exact_metrics(self, preds, labels, n_bins, want_sorted=False):
         """exact AUC, average precision and calibration (exact.py's definition) of device tensors preds / labels [n] fp32
         -> exact.finish's report; want_sorted adds "sorted", the sorted composites (int64 numpy)."""
-        if preds.numel() != labels.numel() or preds.dtype != torch.float32 or labels.dtype != torch.float32 \
-                or preds.device != self.device or labels.device != self.device:
-            raise ValueError("exact_metrics: preds and labels must be fp32 tensors of one length on the engine's device")
+        self._check_pair("exact_metrics", preds, labels)
         counts, ap, bins, out = self._exact_launch(preds.contiguous(), labels.contiguous(), n_bins, want_sorted)
         rep = exact.finish(counts.cpu().numpy(), ap.cpu().numpy()[0], bins.cpu().numpy())
         if want_sorted:
@@ -524,13 +510,14 @@ class DeviceEngine(FlatVectorOps):
 
     # ------------------------------------------------------------ per-user grouped AUC (no reference counterpart)
     def group_auc_plan(self, domain, split):
-        """the device copy of gauc.group_plan over the bound split's uid column: built at first use, uploaded once, dropped
-        when bind_domain_data replaces the split."""
-        plan = self._gauc_plans.get((domain, split))
-        if plan is None:
-            plan = self.upload_group_plan(gauc.group_plan(self.data[(domain, split)]["uid"].cpu().numpy()))
-            self._gauc_plans[(domain, split)] = plan
-        return plan
+        """the device copy of gauc.group_plan over the bound split's uid column: built at first use, uploaded once, kept with
+        the split's columns (bind_domain_data replaces both)."""
+        return self._group_plan_of(self.data[(domain, split)])
+
+    def _group_plan_of(self, cols):
+        if "gauc_plan" not in cols:
+            cols["gauc_plan"] = self.upload_group_plan(gauc.group_plan(cols["uid"].cpu().numpy()))
+        return cols["gauc_plan"]
 
     def upload_group_plan(self, plan):
         """gauc.GroupPlan of numpy arrays -> the same of device tensors."""

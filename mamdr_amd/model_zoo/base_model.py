@@ -18,6 +18,7 @@ import numpy as np
 
 from .. import meta, parallel
 from .. import plan as mplan
+from ..reports import EVAL_REPORTS, requested
 
 
 class BaseModel(object):
@@ -41,9 +42,8 @@ class BaseModel(object):
         sizes = {d: v["n_data"] for d, v in dataset.train_dataset.items()}
         self.shuffler = mplan.PassShuffler(sizes, dataset.shuffle_buffer_size, dataset.seed,
                                            shuffle=getattr(dataset, "shuffle_train", True))
-        self.gauc_reports = {}        # train.report_gauc: {(mode, domain): gauc.finish's report of the latest evaluation}
-        self.exact_reports = {}       # train.report_exact: {(mode, domain): exact.finish's report of the latest evaluation}
-        self.ci_reports = {}          # train.report_auc_ci: {(mode, domain): bootstrap.finish's report of the latest evaluation}
+        self.reports = {e.name: {} for e in EVAL_REPORTS}        # {name: {(mode, domain): the latest evaluation's report}}
+        self.gauc_reports, self.exact_reports, self.ci_reports = (self.reports[n] for n in ("gauc", "exact", "ci"))
         self.model = self.build_model()
         self._build_early_stop()
 
@@ -109,38 +109,14 @@ class BaseModel(object):
                              phase, max_steps, optimizer)
 
     def evaluate_domain(self, idx, mode):
-        """model.evaluate(d['data'], steps=d['n_step']) -> (loss, auc).  Under train.report_gauc (not a key of the
-        reference's configs) the evaluation also yields the split's per-user grouped AUC (gauc.py) -- of whatever weights the
-        caller has installed: the merged per-domain ones under MAMDR / DN, the finetuned ones in the finetune stage --,
-        remembered per (mode, domain) for _summarise / save_result.  Under train.report_exact = B (not a key of the
-        reference's configs either) it yields the exact AUC, average precision and B-bin calibration of the split (exact.py),
-        remembered likewise; early stopping, checkpoints and finetune decisions stay on the 500-threshold AUC.  Under
-        train.report_auc_ci = B (not a key of the reference's configs either) it yields B bootstrap replicates of the exact
-        AUC (bootstrap.py; train.auc_ci_unit "user" | "row", train.auc_ci_seed), remembered likewise; it decides nothing either."""
-        want = {}
-        if self.train_config.get("report_gauc"):
-            want["want_gauc"] = True
-        if self.train_config.get("report_exact"):
-            want["want_exact"] = int(self.train_config["report_exact"])
-        if self.train_config.get("report_auc_ci"):
-            want["want_ci"] = self._auc_ci_request()
-        out = self.model.evaluate(idx, mode, **want)          # (an engine sees a keyword only when its key is set)
-        for key, store in (("want_ci", self.ci_reports), ("want_exact", self.exact_reports),
-                           ("want_gauc", self.gauc_reports)):      # from the tuple's end
-            if key in want:
-                store[(mode, idx)] = out[-1]
-                out = out[:-1]
-        return out
-
-    def _auc_ci_request(self):
-        """train.report_auc_ci / auc_ci_seed / auc_ci_unit -> the engines' want_ci = (n_rep, seed, "row" | "user")."""
-        tc = self.train_config
-        n_rep, unit = int(tc["report_auc_ci"]), tc.get("auc_ci_unit", "user")
-        if not 1 <= n_rep <= 65535:
-            raise ValueError("train.report_auc_ci %d outside 1..65535" % n_rep)
-        if unit not in ("row", "user"):
-            raise ValueError("train.auc_ci_unit is 'row' or 'user', got %r" % (unit,))
-        return n_rep, int(tc.get("auc_ci_seed", 0)), unit
+        """model.evaluate(d['data'], steps=d['n_step']) -> (loss, auc).  It also yields every report of reports.EVAL_REPORTS
+        whose train-config key is set (no key of the reference's configs), of whatever weights the caller has installed, kept
+        per (mode, domain) for _summarise / save_result; every decision stays on the 500-threshold AUC."""
+        wanted = requested(self.train_config)
+        out = self.model.evaluate(idx, mode, **{e.keyword: req for e, req in wanted})   # (an engine sees a keyword only when its key is set)
+        for (e, _), report in zip(wanted, out[2:]):           # the tuple's tail, in table order
+            self.reports[e.name][(mode, idx)] = report
+        return out[:2]
 
     # ------------------------------------------------------------------ retrieval (no reference counterpart)
     def _retrieval_problem(self, domain, users, exclude_seen):
@@ -324,32 +300,13 @@ class BaseModel(object):
         self._format_print_domain_metric("AUC", domain_auc)
         print("Overall {} Loss: {}, AUC: {}, Weighted AUC: {}".format(mode, avg_loss, avg_auc,
                                                                      self._weighted_auc(mode, domain_auc)))
-        if self.train_config.get("report_gauc"):
-            domain_gauc = {d: self.gauc_reports[(mode, d)]["gauc"] for d in domain_auc if (mode, d) in self.gauc_reports}
-            self._format_print_domain_metric("GAUC", domain_gauc)
-            print("Overall {} GAUC: {}, Weighted GAUC: {}".format(mode, *self._gauc_summary(mode, domain_gauc)))
-        if self.train_config.get("report_exact"):
-            from .. import exact
-            reps = {d: self.exact_reports[(mode, d)] for d in domain_auc if (mode, d) in self.exact_reports}
-            overall = exact.summarise(reps)
-            for name, key in (("Exact AUC", "auc"), ("AP", "ap"), ("ECE", "ece")):
-                self._format_print_domain_metric(name, {d: r[key] for d, r in reps.items()})
-                print("Overall {} {}: {}, Weighted {}: {}".format(mode, name, overall[key][0], name, overall[key][1]))
-        if self.train_config.get("report_auc_ci"):
-            n_rep, seed, unit = self._auc_ci_request()
-            print("Exact AUC, {} bootstrap replicates by {} (seed {}): estimate [95 % interval] standard error, valid".format(
-                n_rep, unit, seed))
-            for d in domain_auc:
-                if (mode, d) in self.ci_reports:
-                    r = self.ci_reports[(mode, d)]
-                    print("{}: {} [{}, {}] {}, {}".format(d, r["auc"], r["ci_lo"], r["ci_hi"], r["se"], r["n_valid"]))
+        for e, req in requested(self.train_config):
+            e.print_summary(mode, self._reports_of(e, mode, domain_auc), req, self._format_print_domain_metric)
         return avg_loss, avg_auc, domain_loss, domain_auc
 
-    def _gauc_summary(self, mode, domains):
-        """(plain mean over the domains with a valid user, sum rows_valid_d * gauc_d / sum rows_valid_d) of the remembered
-        reports of `mode`."""
-        from .. import gauc
-        return gauc.summarise({d: self.gauc_reports[(mode, d)] for d in domains})
+    def _reports_of(self, entry, mode, domains):
+        store = self.reports[entry.name]          # -> {domain: the remembered report of `mode`}, in the order of `domains`
+        return {d: store[(mode, d)] for d in domains if (mode, d) in store}
 
     def _format_print_domain_metric(self, name, domain_metric):
         print("{}: ".format(name))
@@ -405,33 +362,8 @@ class BaseModel(object):
             json.dump(self.config, f)
         with open(osp.join(result_path, "result.json"), "w") as f:
             result = {"avg_loss": avg_loss, "avg_auc": avg_auc, "domain_loss": domain_loss, "domain_auc": domain_auc}
-            if self.train_config.get("report_gauc"):         # the test evaluations behind domain_auc
-                reps = {d: self.gauc_reports[("test", d)] for d in domain_auc if ("test", d) in self.gauc_reports}
-                result["avg_gauc"], result["weighted_gauc"] = self._gauc_summary("test", reps)
-                result["domain_gauc"] = {d: r["gauc"] for d, r in reps.items()}
-                result["domain_gauc_users"] = {d: r["n_valid"] for d, r in reps.items()}
-            if self.train_config.get("report_exact"):        # likewise
-                from .. import exact
-                reps = {d: self.exact_reports[("test", d)] for d in domain_auc if ("test", d) in self.exact_reports}
-                result["avg_auc_exact"], result["weighted_auc_exact"] = exact.summarise(reps)["auc"]
-                result["domain_auc_exact"] = {d: r["auc"] for d, r in reps.items()}
-                for key in ("ap", "ece", "pcoc"):
-                    result["domain_" + key] = {d: r[key] for d, r in reps.items()}
-                # the calibration bins behind ece / pcoc: [domains][n_bins], the rows of `domains` in its order
-                np.savez(osp.join(result_path, "exact_metrics.npz"), domains=np.array(list(reps), np.int64),
-                         **{k: np.array([r[k] for r in reps.values()]).reshape(len(reps), -1)
-                            for k in ("bin_rows", "bin_positives", "bin_pred_sum")})
-            if self.train_config.get("report_auc_ci"):       # likewise
-                from .. import bootstrap
-                reps = {d: self.ci_reports[("test", d)] for d in domain_auc if ("test", d) in self.ci_reports}
-                result.update(bootstrap.summarise(reps))
-                # what bootstrap.paired needs to compare two runs: per domain d the replicates and their integers
-                n_rep, seed, unit = self._auc_ci_request()
-                arrays = {"n_rep": np.int64(n_rep), "seed": np.uint64(seed & 0xFFFFFFFFFFFFFFFF), "unit": np.array(unit)}
-                for d, r in reps.items():
-                    for k in ("replicates", "T", "P", "N"):
-                        arrays["%s_%s" % (k, d)] = r[k]
-                np.savez(osp.join(result_path, "auc_bootstrap.npz"), **arrays)
+            for e, req in requested(self.train_config):          # the test evaluations behind domain_auc
+                e.save(result, result_path, self._reports_of(e, "test", domain_auc), req)
             json.dump(result, f)
         self.save_model(osp.join(result_path, "model_parameters.npz"))
         return result_path

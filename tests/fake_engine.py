@@ -201,6 +201,29 @@ class FakeEngine(object):
         pass
 
 
+class ReportingFakeEngine(FakeEngine):
+    """FakeEngine whose `evaluate` honours the keywords of reports.EVAL_REPORTS as DeviceEngine.evaluate does, through the
+    entries' host definitions, in table order.  It records every call's keywords in `seen` and, per requested report,
+    (domain, split, name, the live weights, the report) in `log`."""
+    seen, log = [], []
+
+    def evaluate(self, domain, split, want_preds=False, **kw):
+        from mamdr_amd.reports import EVAL_REPORTS
+        type(self).seen.append(dict(kw))
+        if not kw:
+            return FakeEngine.evaluate(self, domain, split, want_preds)
+        assert set(kw) <= {e.keyword for e in EVAL_REPORTS}
+        cols = self.data[(domain, split)]
+        loss, preds = self.oracle.evaluate(cols, self.batch_size)
+        out = (float(loss), float(oauc.auc500(cols["label"], preds, self.batch_size)))
+        for e in EVAL_REPORTS:
+            if kw.get(e.keyword) not in (None, False, 0):        # (evaluate's defaults ask for nothing)
+                report = e.host(preds, cols, kw[e.keyword])
+                type(self).log.append((domain, split, e.name, self.weights.numpy().copy(), report))
+                out += (report,)
+        return out
+
+
 class FakeGraphEngine(object):
     """CPU stand-in for mamdr_amd.graph_engine.GraphEngine (multi-task towers), built on oracle/mtl.py (tests only)."""
     compiled = ("adam", None)

@@ -10,9 +10,8 @@ import re
 import numpy as np
 import pytest
 
-from fake_engine import FakeEngine
+from fake_engine import ReportingFakeEngine
 from mamdr_amd import _lib, bootstrap, cli, exact, gauc
-from oracle import auc as oauc
 from oracle import rng as orng
 from test_gauc_host import patch_emb_dim, result_json, tiny_config
 
@@ -305,32 +304,6 @@ def test_bad_arguments_are_refused_without_a_device():
 
 
 # ------------------------------------------------------------------ run.py --auc-ci over a CPU stand-in
-class CiEngine(FakeEngine):
-    """FakeEngine whose `evaluate` honours want_ci (and want_gauc, want_exact) as DeviceEngine.evaluate does, through the
-    host definitions; it records every call's keywords and every bootstrap report with the predictions behind it."""
-    seen, log = [], []
-
-    def evaluate(self, domain, split, want_preds=False, **kw):
-        type(self).seen.append(dict(kw))
-        if not kw:
-            return FakeEngine.evaluate(self, domain, split, want_preds)
-        assert set(kw) <= {"want_gauc", "want_exact", "want_ci"}
-        cols = self.data[(domain, split)]
-        loss, preds = self.oracle.evaluate(cols, self.batch_size)
-        out = (float(loss), float(oauc.auc500(cols["label"], preds, self.batch_size)))
-        if kw.get("want_gauc"):
-            out += (gauc.group_auc_host(preds, cols["label"], cols["uid"]),)
-        if kw.get("want_exact"):
-            out += (exact.report_host(preds, cols["label"], kw["want_exact"]),)
-        if kw.get("want_ci") is not None:
-            n_rep, seed, unit = kw["want_ci"]
-            report = bootstrap.finish(*bootstrap.replicates_host(preds, cols["label"], n_rep, seed,
-                                                                 cols["uid"] if unit == "user" else None))
-            type(self).log.append((domain, split, report))
-            out += (report,)
-        return out
-
-
 OLD_KEYS = {"avg_loss", "avg_auc", "domain_loss", "domain_auc"}
 CI_KEYS = {"domain_auc_ci_lo", "domain_auc_ci_hi", "domain_auc_se", "domain_auc_ci_valid"}
 EXACT_KEYS = {"domain_auc_exact", "avg_auc_exact", "weighted_auc_exact", "domain_ap", "domain_ece", "domain_pcoc"}
@@ -347,19 +320,19 @@ def run_folder(tmp_path, cfg):
 @pytest.mark.parametrize("name,others,unit", [("mlp", False, "row"), ("mlp_meta_mamdr", True, None)])
 def test_run_auc_ci_on_a_cpu_stand_in(tmp_path, monkeypatch, capsys, name, others, unit):
     patch_emb_dim(monkeypatch)
-    CiEngine.seen, CiEngine.log = [], []
+    ReportingFakeEngine.seen, ReportingFakeEngine.log = [], []
     extra = dict(report_gauc=True, report_exact=7) if others else {}
     if unit:
         extra.update(auc_ci_unit=unit, auc_ci_seed=11)
     cfg = tiny_config(tmp_path, name, epochs=2, report_auc_ci=40, **extra)
     built = []
-    res = cli.main(cfg, CiEngine, on_model=built.append)
+    res = cli.main(cfg, ReportingFakeEngine, on_model=built.append)
     assert len(res) == 4 and set(res[3]) == {0, 1, 2}                  # still (loss, auc) per domain
     want_kw = dict(want_ci=(40, 11, "row") if unit else (40, 0, "user"), **({"want_gauc": True, "want_exact": 7} if others else {}))
-    assert CiEngine.seen and all(kw == want_kw for kw in CiEngine.seen)
+    assert ReportingFakeEngine.seen and all(kw == want_kw for kw in ReportingFakeEngine.seen)
     result = result_json(tmp_path, cfg)
     assert set(result) == OLD_KEYS | CI_KEYS | ((GAUC_KEYS | EXACT_KEYS) if others else set())
-    last = {d: rep for d, split, rep in CiEngine.log if split == "test"}          # the LAST test evaluation of every domain
+    last = {d: rep for d, split, name, _, rep in ReportingFakeEngine.log if split == "test" and name == "ci"}          # the LAST test evaluation of every domain
     for d in range(3):
         rep = last[d]
         assert built[0].ci_reports[("test", d)] is rep
@@ -392,21 +365,21 @@ def test_run_auc_ci_on_a_cpu_stand_in(tmp_path, monkeypatch, capsys, name, other
 
 def test_without_the_flag_nothing_changes(tmp_path, monkeypatch, capsys):
     patch_emb_dim(monkeypatch)
-    CiEngine.seen, CiEngine.log = [], []
+    ReportingFakeEngine.seen, ReportingFakeEngine.log = [], []
     cfg = tiny_config(tmp_path, "mlp", epochs=1)
-    without = cli.main(cfg, CiEngine)
-    assert CiEngine.seen and all(kw == {} for kw in CiEngine.seen)          # evaluate never receives want_ci
+    without = cli.main(cfg, ReportingFakeEngine)
+    assert ReportingFakeEngine.seen and all(kw == {} for kw in ReportingFakeEngine.seen)          # evaluate never receives want_ci
     assert set(result_json(tmp_path, cfg)) == OLD_KEYS
     assert "auc_bootstrap.npz" not in os.listdir(run_folder(tmp_path, cfg))
     assert "bootstrap" not in capsys.readouterr().out
     # ... and the flag changes neither the returned tuple nor what was saved before: decisions stay on AUC-500
     cfg2 = tiny_config(tmp_path / "b", "mlp", epochs=1, report_auc_ci=20)
-    assert cli.main(cfg2, CiEngine) == without
+    assert cli.main(cfg2, ReportingFakeEngine) == without
     both = result_json(tmp_path / "b", cfg2)
     assert {k: both[k] for k in OLD_KEYS} == result_json(tmp_path, cfg)
     for bad in (dict(report_auc_ci=65536), dict(report_auc_ci=5, auc_ci_unit="item")):
         with pytest.raises(ValueError, match="auc_ci"):
-            cli.main(tiny_config(tmp_path / "c", "mlp", epochs=1, **bad), CiEngine)
+            cli.main(tiny_config(tmp_path / "c", "mlp", epochs=1, **bad), ReportingFakeEngine)
 
 
 def test_the_command_line(monkeypatch):
@@ -436,7 +409,7 @@ def test_lanes_refuse_report_auc_ci_by_name(tmp_path, monkeypatch):
     monkeypatch.setattr(utils, "MultiDomainDataset", lambda *a, **k: loaded.append(a))
     cfg = tiny_config(tmp_path, "mlp_meta_mamdr", report_auc_ci=100, lanes=2)
     with pytest.raises(NotImplementedError, match="train.report_auc_ci"):
-        cli.main(cfg, CiEngine)
+        cli.main(cfg, ReportingFakeEngine)
     assert not loaded                    # refused before the data is loaded
 
 

@@ -10,7 +10,7 @@ import re
 import numpy as np
 import pytest
 
-from fake_engine import FakeEngine
+from fake_engine import ReportingFakeEngine
 from mamdr_amd import _lib, cli, exact, gauc
 from oracle import auc as oauc
 from test_gauc_host import patch_emb_dim, result_json, tiny_config
@@ -207,28 +207,6 @@ def test_auc500_is_off_by_the_tabled_amount(case):
 
 
 # ------------------------------------------------------------------ run.py --exact-metrics over a CPU stand-in
-class ExactEngine(FakeEngine):
-    """FakeEngine whose `evaluate` honours want_exact (and want_gauc) as DeviceEngine.evaluate does, through the host
-    definitions; it records every call's keywords and every exact report."""
-    seen, log = [], []
-
-    def evaluate(self, domain, split, want_preds=False, **kw):
-        type(self).seen.append(dict(kw))
-        if not kw:
-            return FakeEngine.evaluate(self, domain, split, want_preds)
-        assert set(kw) <= {"want_gauc", "want_exact"}
-        cols = self.data[(domain, split)]
-        loss, preds = self.oracle.evaluate(cols, self.batch_size)
-        out = (float(loss), float(oauc.auc500(cols["label"], preds, self.batch_size)))
-        if kw.get("want_gauc"):
-            out += (gauc.group_auc_host(preds, cols["label"], cols["uid"]),)
-        if kw.get("want_exact"):
-            report = exact.report_host(preds, cols["label"], kw["want_exact"])
-            type(self).log.append((domain, split, report))
-            out += (report,)
-        return out
-
-
 OLD_KEYS = {"avg_loss", "avg_auc", "domain_loss", "domain_auc"}
 NEW_KEYS = {"domain_auc_exact", "avg_auc_exact", "weighted_auc_exact", "domain_ap", "domain_ece", "domain_pcoc"}
 GAUC_KEYS = {"avg_gauc", "weighted_gauc", "domain_gauc", "domain_gauc_users"}
@@ -244,16 +222,16 @@ def run_folder(tmp_path, cfg):
 @pytest.mark.parametrize("name,with_gauc", [("mlp", False), ("mlp_meta_mamdr", True)])
 def test_run_exact_flag_on_a_cpu_stand_in(tmp_path, monkeypatch, capsys, name, with_gauc):
     patch_emb_dim(monkeypatch)
-    ExactEngine.seen, ExactEngine.log = [], []
+    ReportingFakeEngine.seen, ReportingFakeEngine.log = [], []
     extra = dict(report_gauc=True) if with_gauc else {}
     cfg = tiny_config(tmp_path, name, epochs=2, report_exact=7, **extra)
-    res = cli.main(cfg, ExactEngine)
+    res = cli.main(cfg, ReportingFakeEngine)
     assert len(res) == 4 and set(res[3]) == {0, 1, 2}                  # still (loss, auc) per domain
     want_kw = dict(want_exact=7, **({"want_gauc": True} if with_gauc else {}))
-    assert ExactEngine.seen and all(kw == want_kw for kw in ExactEngine.seen)
+    assert ReportingFakeEngine.seen and all(kw == want_kw for kw in ReportingFakeEngine.seen)
     result = result_json(tmp_path, cfg)
     assert set(result) == OLD_KEYS | NEW_KEYS | (GAUC_KEYS if with_gauc else set())
-    last = {d: rep for d, split, rep in ExactEngine.log if split == "test"}          # the LAST test evaluation of every domain
+    last = {d: rep for d, split, name, _, rep in ReportingFakeEngine.log if split == "test" and name == "exact"}          # the LAST test evaluation of every domain
     for d in range(3):
         assert result["domain_auc_exact"][str(d)] == last[d]["auc"] and 0.0 < last[d]["auc"] < 1.0
         for key in ("ap", "ece", "pcoc"):
@@ -287,10 +265,10 @@ def test_run_exact_flag_on_a_cpu_stand_in(tmp_path, monkeypatch, capsys, name, w
 
 def test_without_the_flag_nothing_changes(tmp_path, monkeypatch, capsys):
     patch_emb_dim(monkeypatch)
-    ExactEngine.seen, ExactEngine.log = [], []
+    ReportingFakeEngine.seen, ReportingFakeEngine.log = [], []
     cfg = tiny_config(tmp_path, "mlp", epochs=1)
-    without = cli.main(cfg, ExactEngine)
-    assert ExactEngine.seen and all(kw == {} for kw in ExactEngine.seen)          # evaluate never receives want_exact
+    without = cli.main(cfg, ReportingFakeEngine)
+    assert ReportingFakeEngine.seen and all(kw == {} for kw in ReportingFakeEngine.seen)          # evaluate never receives want_exact
     assert set(result_json(tmp_path, cfg)) == OLD_KEYS
     assert sorted(os.listdir(run_folder(tmp_path, cfg))) == ["config.json.example", "dataset_info.json", "model_parameters.npz",
                                                              "result.json"]
@@ -298,7 +276,7 @@ def test_without_the_flag_nothing_changes(tmp_path, monkeypatch, capsys):
     assert "Exact AUC" not in out and "ECE" not in out and "AP:" not in out
     # ... and the flag changes neither the returned tuple nor what was saved before: decisions stay on AUC-500
     cfg2 = tiny_config(tmp_path / "b", "mlp", epochs=1, report_exact=20)
-    assert cli.main(cfg2, ExactEngine) == without
+    assert cli.main(cfg2, ReportingFakeEngine) == without
     both = result_json(tmp_path / "b", cfg2)
     assert {k: both[k] for k in OLD_KEYS} == result_json(tmp_path, cfg)
     # the command line: --exact-metrics [B] sets train.report_exact, its absence calls main exactly as before
@@ -324,7 +302,7 @@ def test_lanes_refuse_report_exact_by_name(tmp_path, monkeypatch):
     monkeypatch.setattr(utils, "MultiDomainDataset", lambda *a, **k: loaded.append(a))
     cfg = tiny_config(tmp_path, "mlp_meta_mamdr", report_exact=20, lanes=2)
     with pytest.raises(NotImplementedError, match="train.report_exact"):
-        cli.main(cfg, ExactEngine)
+        cli.main(cfg, ReportingFakeEngine)
     assert not loaded                    # refused before the data is loaded
 
 

@@ -11,9 +11,8 @@ import numpy as np
 import pytest
 import torch
 
-from fake_engine import FakeEngine
+from fake_engine import ReportingFakeEngine
 from mamdr_amd import _lib, cli, gauc, synthetic
-from oracle import auc as oauc
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -221,23 +220,6 @@ def test_group_auc_host_against_brute_force():
 
 
 # ------------------------------------------------------------------ run.py --gauc over a CPU stand-in
-class GaucEngine(FakeEngine):
-    """FakeEngine whose `evaluate` honours want_gauc through gauc.group_auc_host (DeviceEngine.evaluate's contract); it
-    records every call's keywords and, for a want_gauc call, the live weights and the report."""
-    seen, log = [], []
-
-    def evaluate(self, domain, split, want_preds=False, **kw):
-        type(self).seen.append(dict(kw))
-        if not kw:
-            return FakeEngine.evaluate(self, domain, split, want_preds)
-        assert kw == {"want_gauc": True}
-        cols = self.data[(domain, split)]
-        loss, preds = self.oracle.evaluate(cols, self.batch_size)
-        report = gauc.group_auc_host(preds, cols["label"], cols["uid"])
-        type(self).log.append((domain, split, self.weights.numpy().copy(), report))
-        return float(loss), float(oauc.auc500(cols["label"], preds, self.batch_size)), report
-
-
 def result_json(tmp_path, cfg):
     rdir = os.path.join(str(tmp_path / "result"), cfg["model"]["name"], "Taobao", cfg["dataset"]["domain_split_path"])
     runs = os.listdir(rdir)
@@ -249,21 +231,21 @@ def result_json(tmp_path, cfg):
 @pytest.mark.parametrize("name", ["mlp", "mlp_meta_mamdr"])
 def test_run_gauc_flag_on_a_cpu_stand_in(tmp_path, monkeypatch, capsys, name):
     patch_emb_dim(monkeypatch)
-    GaucEngine.seen, GaucEngine.log = [], []
+    ReportingFakeEngine.seen, ReportingFakeEngine.log = [], []
     cfg = tiny_config(tmp_path, name, epochs=2, report_gauc=True)
     built = []
-    res = cli.main(cfg, GaucEngine, on_model=built.append)
+    res = cli.main(cfg, ReportingFakeEngine, on_model=built.append)
     assert len(res) == 4 and set(res[3]) == {0, 1, 2}                  # still (loss, auc) per domain
     model = built[0]
-    assert GaucEngine.seen and all(kw == {"want_gauc": True} for kw in GaucEngine.seen)
+    assert ReportingFakeEngine.seen and all(kw == {"want_gauc": True} for kw in ReportingFakeEngine.seen)
     result = result_json(tmp_path, cfg)
     assert set(result) == {"avg_loss", "avg_auc", "domain_loss", "domain_auc", "avg_gauc", "weighted_gauc", "domain_gauc",
                            "domain_gauc_users"}
     assert set(result["domain_gauc"]) == set(result["domain_gauc_users"]) == {"0", "1", "2"}
     # the saved values are those of the LAST test evaluation of every domain
     last = {}
-    for d, split, weights, report in GaucEngine.log:
-        if split == "test":
+    for d, split, report_name, weights, report in ReportingFakeEngine.log:
+        if split == "test" and report_name == "gauc":
             last[d] = (weights, report)
     valid = [d for d in range(3) if last[d][1]["n_valid"] > 0]
     assert valid, "the stand-in's test splits hold no user with both classes"
@@ -298,15 +280,15 @@ def test_run_gauc_flag_on_a_cpu_stand_in(tmp_path, monkeypatch, capsys, name):
 
 def test_without_the_flag_nothing_changes(tmp_path, monkeypatch, capsys):
     patch_emb_dim(monkeypatch)
-    GaucEngine.seen, GaucEngine.log = [], []
+    ReportingFakeEngine.seen, ReportingFakeEngine.log = [], []
     cfg = tiny_config(tmp_path, "mlp", epochs=1)
-    without = cli.main(cfg, GaucEngine)
-    assert GaucEngine.seen and all(kw == {} for kw in GaucEngine.seen)          # evaluate never receives want_gauc
+    without = cli.main(cfg, ReportingFakeEngine)
+    assert ReportingFakeEngine.seen and all(kw == {} for kw in ReportingFakeEngine.seen)          # evaluate never receives want_gauc
     assert set(result_json(tmp_path, cfg)) == {"avg_loss", "avg_auc", "domain_loss", "domain_auc"}
     assert "GAUC" not in capsys.readouterr().out
     # ... and the flag changes neither the returned tuple nor what was saved before
     cfg2 = tiny_config(tmp_path / "b", "mlp", epochs=1, report_gauc=True)
-    assert cli.main(cfg2, GaucEngine) == without
+    assert cli.main(cfg2, ReportingFakeEngine) == without
     both = result_json(tmp_path / "b", cfg2)
     assert {k: both[k] for k in ("avg_loss", "avg_auc", "domain_loss", "domain_auc")} == result_json(tmp_path, cfg)
     # the command line: --gauc sets train.report_gauc, its absence calls main exactly as before
@@ -326,5 +308,5 @@ def test_lanes_refuse_report_gauc_by_name(tmp_path, monkeypatch):
     monkeypatch.setattr(utils, "MultiDomainDataset", lambda *a, **k: loaded.append(a))
     cfg = tiny_config(tmp_path, "mlp_meta_mamdr", report_gauc=True, lanes=2)
     with pytest.raises(NotImplementedError, match="report_gauc"):
-        cli.main(cfg, GaucEngine)
+        cli.main(cfg, ReportingFakeEngine)
     assert not loaded                    # refused before the data is loaded

@@ -519,6 +519,55 @@ int mamdr_auc_bootstrap(const float* d_pred, const float* d_label, const int32_t
 int mamdr_auc_bootstrap_bounded(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
                                 uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, int64_t part_words, void* stream);
 
+/* Isotonic regression of one split's (prediction, label) pairs -- the pool-adjacent-violators fit behind recalibration and
+ * the CORP score decomposition (mamdr_amd/isotonic.py: corp, finish) --, its application to other predictions, and the Brier
+ * and log-loss sums of a split.  NO REFERENCE COUNTERPART: the reference never looks at calibration.  Stateless, any stream.
+ * Rows and runs.  Per row: key is GAUC's order-preserving 32-bit key (NaN is lowest and equals NaN, -0 equals +0); positive
+ * is label != 0.  Sort by key ascending.  A run is a maximal set of rows with one key; run j has r_j rows and s_j positives.
+ * Points Q_0 = (0, 0), Q_{j+1} = Q_j + (r_j, s_j), R runs in all.  NaN predictions form the lowest run and take part like
+ * any other; n_nan is reported.
+ * Fit.  The blocks are the maximal groups of consecutive runs between consecutive STRICT vertices of the lower convex hull
+ * of Q_0 .. Q_R: with A, B, C consecutive candidates, B is dropped exactly when
+ * (B.x - A.x) * (C.y - B.y) - (B.y - A.y) * (C.x - B.x) <= 0 in int64 (coordinates are below 2^31, the products below 2^62).
+ * Equivalently: PAV over the runs, pooling the last two blocks while mean_left >= mean_right.  Block means are strictly
+ * increasing.  Value v_b = (float)((double)positives[b] / (double)rows[b]): one fp64 division, rounded once to fp32.
+ * mamdr_isotonic_fit (device pointers; nothing is read back by the call):
+ *   d_pred, d_label [n]   fp32 predictions and labels in file order, 0 <= n < 2^31; read only
+ *   d_counts [4]          int64 words n_blocks, n_runs, n_nan, P (the positives)
+ *   d_first_key, d_rows, d_positives   capacity n each (uint32, int64, int64); the first n_blocks entries are written:
+ *                         the key of the block's first run, its rows, its positives
+ * mamdr_isotonic_fit_bounded is the same call with tile_points given, the points per tile of the hull's levels
+ * (>= MAMDR_ISOTONIC_MIN_TILE; mamdr_isotonic_fit uses 64; the tests force several tiles and levels on small inputs with
+ * it): the outputs do not depend on it.
+ * Determinism.  The fit is integer arithmetic throughout -- no floating point, no atomics -- and the hull is unique: the
+ * outputs are the same bits from run to run, under any permutation of the rows and under any tile_points.
+ * The sort is mamdr_exact_metrics' radix sort; run heads and positives are counted by three-launch scans; the hull is built
+ * by levels of per-tile monotone chains (a strict vertex of the whole hull is a strict vertex of the hull of every
+ * contiguous subset that holds it) whose number the host fixes from n and tile_points alone, and finished by one chain
+ * over what is left; the kernel boundary is the only hand-off between workgroups (csrc/isotonic_kernels.hip).  A diagram
+ * that never shrinks (strictly convex: every run its own block) leaves all its points to that last chain, on one lane.
+ * Nothing synchronises the device; the only memory written is the outputs and a stream-ordered allocation of the call
+ * (hipMallocAsync / hipFreeAsync on `stream`) of about 33 bytes per row.
+ * mamdr_isotonic_apply: for a row with key k, b = max(0, #{blocks with first_key <= k} - 1), d_out[i] = v_b -- a step
+ * function, clipped at both ends (a NaN prediction, the lowest key, gets block 0).  n_blocks >= 1 when n > 0.  No allocation.
+ * mamdr_score_sums: d_out [2] doubles, with y = positive and p widened to fp64: the Brier sum, sum (p - y)^2, and the
+ * log-loss sum, sum -[y ln q + (1 - y) ln(1 - q)] with q = clamp(p, 1e-7, 1 - 1e-7) (the Keras epsilon).  A NaN prediction
+ * makes both NaN.  Each sum runs over one fixed tree per n, without floating-point atomics: the same bits from run to run.
+ * Workspace: a stream-ordered allocation of 16 bytes per 1,024 rows.
+ * n = 0 writes zeros (nothing, for mamdr_isotonic_apply) and returns MAMDR_OK.
+ * MAMDR_EINVAL, before any device call: a null d_counts / d_out, or (n > 0) any other null pointer; a pointer that is not
+ * aligned to its element size; n < 0 or n >= 2^31; tile_points < MAMDR_ISOTONIC_MIN_TILE; n_blocks < 0 or >= 2^31, or
+ * n_blocks = 0 while n > 0.
+ * (Added within ABI 19: new entry points only, no structure or existing call changed.) */
+#define MAMDR_ISOTONIC_MIN_TILE 4
+int mamdr_isotonic_fit(const float* d_pred, const float* d_label, int64_t n, int64_t* d_counts, uint32_t* d_first_key,
+                       int64_t* d_rows, int64_t* d_positives, void* stream);
+int mamdr_isotonic_fit_bounded(const float* d_pred, const float* d_label, int64_t n, int64_t* d_counts, uint32_t* d_first_key,
+                               int64_t* d_rows, int64_t* d_positives, int32_t tile_points, void* stream);
+int mamdr_isotonic_apply(const uint32_t* d_first_key, const int64_t* d_rows, const int64_t* d_positives, int64_t n_blocks,
+                         const float* d_pred, int64_t n, float* d_out, void* stream);
+int mamdr_score_sums(const float* d_pred, const float* d_label, int64_t n, double* d_out, void* stream);
+
 /* Gram matrices of up to MAMDR_GRAM_MAX_VEC flat fp32 vectors over column ranges, in fp64 -- the reduction behind the
  * domain-conflict report (the cosines between the domains' gradients).  NO REFERENCE COUNTERPART: the reference argues
  * that domains conflict and never measures it.  Stateless, any stream, no synchronisation, no allocation: the workspace

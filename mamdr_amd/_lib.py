@@ -113,6 +113,10 @@ SIGNATURES = {
     "mamdr_exact_metrics": (C.c_int, [_VP, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _VP]),
     "mamdr_auc_bootstrap": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _U64, _VP, _VP, _VP, _VP]),
     "mamdr_auc_bootstrap_bounded": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _U64, _VP, _VP, _VP, _I64, _VP]),
+    "mamdr_isotonic_fit": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
+    "mamdr_isotonic_fit_bounded": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _I32, _VP]),
+    "mamdr_isotonic_apply": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _VP]),
+    "mamdr_score_sums": (C.c_int, [_VP, _VP, _I64, _VP, _VP]),
     "mamdr_gram_work": (_I64, [_I32, _VP, _VP, _I32]),
     "mamdr_gram": (C.c_int, [_VP, _I64, _I32, _I64, _VP, _VP, _I32, _VP, _I64, _VP, _VP]),
     "mamdr_interp": (C.c_int, [_VP, _VP, _VP, _F, _I64, _VP]),

@@ -38,6 +38,9 @@ SOURCES = [
     ("exact_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
     # bootstrap_kernels: integers only; its register / LDS / scratch report: profiles/auc_bootstrap.txt
     ("bootstrap_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
+    # isotonic_kernels: the fit is integers only; the score sums' terms are the host definition's operations -> no fma
+    # fusion; its register / LDS / scratch report: profiles/isotonic_bench.txt
+    ("isotonic_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
     # gram_kernels: its register / LDS / scratch report: profiles/conflict_bench.txt
     ("gram_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)

@@ -15,7 +15,8 @@ Not options of the reference's run.py: --lanes, --recommend K (top-K lists per d
 --rank-eval [KS] (train.rank_eval: the exact full-catalogue rank of every held-out positive, recommend.rank_report),
 --sampled-eval [N] with --sampled-eval-ks KS (train.sampled_eval, train.sampled_eval_ks, train.sampled_eval_seed: every held-out
 positive ranked among N sampled items the user never interacted with, recommend.sampled_report), and
---conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report).
+--conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report), and
+--isotonic [B] with --isotonic-out FILE (train.isotonic: isotonic recalibration fitted on val, applied to test, and the CORP decomposition of the test Brier score, isotonic.report).
 """
 import argparse
 import json
@@ -123,7 +124,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     (default [10]) (recommend.sampled_report) --, written under train.result_save_path.  train.conflict = N (run.py --conflict [N]; no key of the
     reference's configs): once the pipeline has ended, the domain-conflict report (conflict.report) over N batches per domain
     (0: whole passes), written to train.conflict_out or under train.result_save_path; result.json gains conflict_rate_all,
-    mean_cosine_all, conflict_rate_meta and mean_cosine_meta."""
+    mean_cosine_all, conflict_rate_meta and mean_cosine_meta.  train.isotonic = B (run.py --isotonic [B]; no key of the
+    reference's configs): once the pipeline has ended, the isotonic report (isotonic.report) with B calibration bins, written
+    to train.isotonic_out or under train.result_save_path; result.json gains isotonic.headline's keys (domain_brier,
+    domain_mcb, ..., avg_mcb, weighted_mcb)."""
     from .reports import EVAL_REPORTS
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
@@ -148,6 +152,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     if config["train"].get("conflict") is not None and (world > 1 or lanes > 1):
         raise NotImplementedError("train.conflict (run.py --conflict): the domain-conflict report is not computed across processes "
                                   "or lanes (one engine measures every domain's gradient at one point); run it with one process "
+                                  "and train.lanes = 1")
+    if config["train"].get("isotonic") is not None and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.isotonic (run.py --isotonic): the isotonic report is not computed across processes "
+                                  "or lanes (the best phi_d slots are current only on their owners); run it with one process "
                                   "and train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
     if lanes > 1:
@@ -197,13 +205,22 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
         if config["train"].get("conflict") is not None:
             from . import conflict
             _, res = conflict.report(model, int(config["train"]["conflict"]), config["train"].get("conflict_out"))
-            path = os.path.join(saved, "result.json")        # (written by save_result above: the report runs after it)
-            with open(path) as f:
-                result = json.load(f)
-            result.update(conflict.headline(res))
-            with open(path, "w") as f:
-                json.dump(result, f)
+            _extend_result(saved, conflict.headline(res))
+        if config["train"].get("isotonic") is not None:
+            from . import isotonic
+            _, reports = isotonic.report(model, int(config["train"]["isotonic"]), config["train"].get("isotonic_out"))
+            _extend_result(saved, isotonic.headline(reports))
     return avg_loss, avg_auc, domain_loss, domain_auc
+
+
+def _extend_result(saved, extra):
+    """the keys of a post-run report into the result.json that save_result wrote (the report runs after it)."""
+    path = os.path.join(saved, "result.json")
+    with open(path) as f:
+        result = json.load(f)
+    result.update(extra)
+    with open(path, "w") as f:
+        json.dump(result, f)
 
 
 def cli(argv=None):
@@ -242,6 +259,12 @@ def cli(argv=None):
                              "(train.conflict)")
     parser.add_argument("--conflict-out", type=str, default=None, metavar="FILE",
                         help=".npz the domain-conflict report goes to (default: under train.result_save_path)")
+    parser.add_argument("--isotonic", type=int, default=None, nargs="?", const=20, metavar="B",
+                        help="after the run: isotonic recalibration of every domain -- fitted on its val split, applied to its "
+                             "test split -- with Brier / log loss / ECE / PCOC (B equal-mass bins, default 20, 1 .. 4096) before "
+                             "and after, and the CORP decomposition of the test Brier score (train.isotonic)")
+    parser.add_argument("--isotonic-out", type=str, default=None, metavar="FILE",
+                        help=".npz the isotonic fits go to (default: under train.result_save_path)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -281,6 +304,12 @@ def cli(argv=None):
         config["train"]["conflict"] = args.conflict
     if args.conflict_out is not None:
         config["train"]["conflict_out"] = args.conflict_out
+    if args.isotonic is not None:
+        if not 1 <= args.isotonic <= 4096:
+            parser.error("--isotonic B: B calibration bins, 1 .. 4096")
+        config["train"]["isotonic"] = args.isotonic
+    if args.isotonic_out is not None:
+        config["train"]["isotonic_out"] = args.isotonic_out
     if args.recommend is None:
         return main(config)
     return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

@@ -1,5 +1,6 @@
-// C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics and
-// mamdr_auc_bootstrap(_bounded).  Stateless, like the outer updates: no context, the caller's stream.  Host code only.
+// C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics,
+// mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply and mamdr_score_sums.  Stateless, like
+// the outer updates: no context, the caller's stream.  Host code only.
 #include "step_ctx.h"
 
 // a call's own scratch, ordered on its stream: `bytes` are allocated (nothing for 0), `run(ws)` launches and returns its
@@ -136,6 +137,91 @@ int mamdr_auc_bootstrap_bounded(const float* d_pred, const float* d_label, const
 int mamdr_auc_bootstrap(const float* d_pred, const float* d_label, const int32_t* d_unit, int64_t n, int32_t n_rep,
                         uint64_t seed, uint64_t* d_T, int64_t* d_P, int64_t* d_N, void* stream) {
     return mamdr_auc_bootstrap_bounded(d_pred, d_label, d_unit, n, n_rep, seed, d_T, d_P, d_N, BOOT_PART_WORDS, stream);
+}
+
+// ---- isotonic fit, its application and the score sums (isotonic_kernels.hip)
+int mamdr_isotonic_fit_bounded(const float* d_pred, const float* d_label, int64_t n, int64_t* d_counts, uint32_t* d_first_key,
+                               int64_t* d_rows, int64_t* d_positives, int32_t tile_points, void* stream) {
+    if (!d_counts) return fail(MAMDR_EINVAL, "mamdr_isotonic_fit: null counts pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_isotonic_fit: n %lld outside [0, 2^31)", (long long)n);
+    if (tile_points < MAMDR_ISOTONIC_MIN_TILE)
+        return fail(MAMDR_EINVAL, "mamdr_isotonic_fit: tile_points %d below %d", (int)tile_points, MAMDR_ISOTONIC_MIN_TILE);
+    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_isotonic_fit: null pred / label pointer");
+    if (n > 0 && (!d_first_key || !d_rows || !d_positives))
+        return fail(MAMDR_EINVAL, "mamdr_isotonic_fit: null first_key / rows / positives pointer");
+    if (misaligned(3, d_pred, d_label, d_first_key) || misaligned(7, d_counts, d_rows, d_positives))
+        return fail(MAMDR_EINVAL, "mamdr_isotonic_fit: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * sizeof(int64_t), s));
+    if (n == 0) return MAMDR_OK;
+    IsoFitArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.n = n;
+    a.tile = tile_points;
+    a.counts = reinterpret_cast<long long*>(d_counts);
+    a.first_key = d_first_key;
+    a.rows = reinterpret_cast<long long*>(d_rows);
+    a.positives = reinterpret_cast<long long*>(d_positives);
+    return with_scratch("mamdr_isotonic_fit", iso_fit_workspace_bytes(n, tile_points), s, [&](char* ws) {
+        a.ws = ws;
+        launch_iso_fit(a, s);
+        return hipGetLastError();
+    });
+}
+
+int mamdr_isotonic_fit(const float* d_pred, const float* d_label, int64_t n, int64_t* d_counts, uint32_t* d_first_key,
+                       int64_t* d_rows, int64_t* d_positives, void* stream) {
+    return mamdr_isotonic_fit_bounded(d_pred, d_label, n, d_counts, d_first_key, d_rows, d_positives, ISO_HULL_TILE, stream);
+}
+
+int mamdr_isotonic_apply(const uint32_t* d_first_key, const int64_t* d_rows, const int64_t* d_positives, int64_t n_blocks,
+                         const float* d_pred, int64_t n, float* d_out, void* stream) {
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_isotonic_apply: n %lld outside [0, 2^31)", (long long)n);
+    if (n_blocks < 0 || n_blocks > INT32_MAX || (n > 0 && n_blocks == 0))
+        return fail(MAMDR_EINVAL, "mamdr_isotonic_apply: %lld blocks for %lld rows", (long long)n_blocks, (long long)n);
+    if (n > 0 && (!d_first_key || !d_rows || !d_positives || !d_pred || !d_out))
+        return fail(MAMDR_EINVAL, "mamdr_isotonic_apply: null first_key / rows / positives / pred / out pointer");
+    if (misaligned(3, d_first_key, d_pred, d_out) || misaligned(7, d_rows, d_positives))
+        return fail(MAMDR_EINVAL, "mamdr_isotonic_apply: a pointer is not aligned to its element size");
+    if (n == 0) return MAMDR_OK;
+    IsoApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.first_key = d_first_key;
+    a.rows = reinterpret_cast<const long long*>(d_rows);
+    a.positives = reinterpret_cast<const long long*>(d_positives);
+    a.n_blocks = n_blocks;
+    a.pred = d_pred;
+    a.n = n;
+    a.out = d_out;
+    launch_iso_apply(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_score_sums(const float* d_pred, const float* d_label, int64_t n, double* d_out, void* stream) {
+    if (!d_out) return fail(MAMDR_EINVAL, "mamdr_score_sums: null out pointer");
+    if (n < 0 || n > INT32_MAX) return fail(MAMDR_EINVAL, "mamdr_score_sums: n %lld outside [0, 2^31)", (long long)n);
+    if (n > 0 && (!d_pred || !d_label)) return fail(MAMDR_EINVAL, "mamdr_score_sums: null pred / label pointer");
+    if (misaligned(3, d_pred, d_label) || misaligned(7, d_out))
+        return fail(MAMDR_EINVAL, "mamdr_score_sums: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(d_out, 0, 2 * sizeof(double), s));
+        return MAMDR_OK;
+    }
+    ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pred = d_pred;
+    a.label = d_label;
+    a.n = n;
+    a.out = d_out;
+    return with_scratch("mamdr_score_sums", score_workspace_bytes(n), s, [&](char* ws) {
+        a.part = reinterpret_cast<double*>(ws);
+        launch_score_sums(a, s);
+        return hipGetLastError();
+    });
 }
 
 }  // extern "C"

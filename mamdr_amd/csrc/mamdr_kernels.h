@@ -992,6 +992,51 @@ int boot_chunk(int64_t n, int n_rep, int64_t part_words);       // replicate slo
 size_t boot_workspace_bytes(int64_t n, int n_rep, int64_t part_words);
 void launch_boot(const BootArgs& a, hipStream_t s);        // n > 0
 
+// isotonic_kernels.hip: the isotonic (PAV) fit of one split, its application and the Brier / log-loss sums
+// (mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply, mamdr_score_sums).
+// (mamdr_amd/isotonic.py carries the same constants for the tests)
+constexpr int ISO_POINT_TILE = 1024;          // sorted positions per workgroup of k_iso_run_sums / k_iso_points
+constexpr int ISO_SCAN_TILE = 1024;           // 64-bit words per workgroup of the device-wide scans
+constexpr int ISO_HULL_TILE = 64;             // points per tile of the hull's levels (one thread each): mamdr_isotonic_fit's
+constexpr int ISO_MIN_TILE = 4;               // smallest tile_points of mamdr_isotonic_fit_bounded (= MAMDR_ISOTONIC_MIN_TILE)
+constexpr int ISO_MAX_LEVELS = 32;            // levels of the hull at most (a tile of 4 halves 2^31 points 30 times)
+constexpr int ISO_APPLY_TILE = 2048;          // rows per workgroup of k_iso_apply
+constexpr int ISO_APPLY_LDS = 4096;           // blocks up to which k_iso_apply searches first_key in LDS
+constexpr int ISO_SCORE_TILE = 1024;          // rows per workgroup of k_score_parts
+struct IsoFitArgs {
+    const float* pred;                 // [n] in file order
+    const float* label;                // [n]
+    int64_t n;
+    int tile;                          // points per tile of the hull's levels, >= ISO_MIN_TILE
+    long long* counts;                 // [4] n_blocks, n_runs, n_nan, P; zeroed by the call
+    uint32_t* first_key;               // [n] capacity; n_blocks entries are written
+    long long* rows;
+    long long* positives;
+    char* ws;                          // iso_fit_workspace_bytes(n, tile) bytes, 16-byte aligned
+};
+int iso_levels(int64_t n, int tile);                       // levels of tiles before the final chain
+size_t iso_fit_workspace_bytes(int64_t n, int tile);
+void launch_iso_fit(const IsoFitArgs& a, hipStream_t s);   // n > 0
+struct IsoApplyArgs {
+    const uint32_t* first_key;         // [n_blocks] ascending
+    const long long* rows;
+    const long long* positives;
+    int64_t n_blocks;                  // > 0
+    const float* pred;                 // [n]
+    int64_t n;
+    float* out;                        // [n]
+};
+void launch_iso_apply(const IsoApplyArgs& a, hipStream_t s);        // n > 0
+struct ScoreArgs {
+    const float* pred;                 // [n]
+    const float* label;                // [n]
+    int64_t n;
+    double* part;                      // score_workspace_bytes(n): [tiles][2]
+    double* out;                       // [2] Brier sum, log-loss sum
+};
+size_t score_workspace_bytes(int64_t n);
+void launch_score_sums(const ScoreArgs& a, hipStream_t s);          // n > 0
+
 // gram_kernels.hip: fp64 Gram matrices of up to GRAM_MAX_VEC flat vectors over column ranges (mamdr_gram).  One GramArgs
 // describes a batch of up to GRAM_MAX_RANGES ranges: two launches
 constexpr int GRAM_SLAB = 16384;      // columns per workgroup of k_gram_slab (= MAMDR_GRAM_SLAB)

@@ -7,7 +7,7 @@
 //   step_queries.hip    the queries of a context: mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain),
 //                       mamdr_rank_domain, mamdr_rank_slates
 //   eval_metrics.hip    the metrics of an evaluation's predictions, no context: mamdr_group_auc, mamdr_exact_metrics,
-//                       mamdr_auc_bootstrap(_bounded)
+//                       mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply, mamdr_score_sums
 //   step_stateless.hip  the outer updates, mamdr_adam_apply, mamdr_pcgrad_project, mamdr_copy, mamdr_gram, the shuffle
 // Helpers that one file uses stay static in it.
 #pragma once

@@ -508,6 +508,78 @@ class DeviceEngine(FlatVectorOps):
             rep["sorted"] = out.cpu().numpy()
         return rep
 
+    # ------------------------------------------------------------ isotonic fit / apply / score sums (no reference counterpart)
+    def predict_device(self, domain, split):
+        """the fp32 predictions of a bound split as a DEVICE tensor [n]: the launch of evaluate(..., want_preds=True) on the
+        engine's stream, without the copy -- nothing is read back."""
+        preds = torch.empty(self.n_rows(domain, split), dtype=torch.float32, device=self.device)
+        split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
+        self._check(self._c_eval_domain(self.ctx, domain, split_id, self.eval_batch, _ptr(self._loss1), _ptr(self._hist),
+                                        _ptr(preds)))
+        return preds
+
+    def _isotonic_fit_launch(self, preds, labels, tile_points=None):
+        """mamdr_isotonic_fit on the engine's stream -> the device tensors (counts [4] int64, first_key [n] int32 holding
+        uint32 words, rows [n] int64, positives [n] int64); nothing is read back.  tile_points (tests):
+        mamdr_isotonic_fit_bounded with that tile of the hull's levels."""
+        from . import isotonic          # (here, not at the top: a run without --isotonic never imports the module)
+        n = int(preds.numel())
+        if tile_points is not None and int(tile_points) < isotonic.MIN_TILE:
+            raise ValueError("isotonic fit: tile_points %d below %d" % (int(tile_points), isotonic.MIN_TILE))
+        counts = torch.empty(4, dtype=torch.int64, device=self.device)
+        first_key = torch.empty(n, dtype=torch.int32, device=self.device)
+        rows, positives = [torch.empty(n, dtype=torch.int64, device=self.device) for _ in range(2)]
+        args = (_ptr(preds if n else None), _ptr(labels if n else None), n, _ptr(counts), _ptr(first_key if n else None),
+                _ptr(rows if n else None), _ptr(positives if n else None))
+        if tile_points is None:
+            L.check(self.lib.mamdr_isotonic_fit(*args, self._s()))
+        else:
+            L.check(self.lib.mamdr_isotonic_fit_bounded(*args, int(tile_points), self._s()))
+        return counts, first_key, rows, positives
+
+    def isotonic_fit(self, preds, labels, tile_points=None):
+        """the isotonic (PAV) fit (isotonic.py's definition) of device tensors preds / labels [n] fp32 -> isotonic.table's
+        dict: the counts and the block table as numpy arrays."""
+        from . import isotonic
+        self._check_pair("isotonic_fit", preds, labels)
+        counts, first_key, rows, positives = self._isotonic_fit_launch(preds.contiguous(), labels.contiguous(), tile_points)
+        nb = int(counts.cpu().numpy()[0])
+        return isotonic.table(counts.cpu().numpy(), first_key[:nb].cpu().numpy(), rows[:nb].cpu().numpy(),
+                              positives[:nb].cpu().numpy())
+
+    def _isotonic_apply_launch(self, first_key, rows, positives, n_blocks, preds):
+        """mamdr_isotonic_apply on the engine's stream over device tensors -> the device tensor of fitted values [n] fp32."""
+        n = int(preds.numel())
+        out = torch.empty(n, dtype=torch.float32, device=self.device)
+        L.check(self.lib.mamdr_isotonic_apply(_ptr(first_key), _ptr(rows), _ptr(positives), int(n_blocks),
+                                              _ptr(preds if n else None), n, _ptr(out if n else None), self._s()))
+        return out
+
+    def isotonic_apply(self, fit, preds):
+        """the step function of `fit` (isotonic_fit's / isotonic.table's dict) at the device tensor preds [n] fp32 -> the
+        DEVICE tensor of fitted values [n] fp32 (isotonic.apply_host's)."""
+        if preds.dtype != torch.float32 or preds.device != self.device:
+            raise ValueError("isotonic_apply: preds must be an fp32 tensor on the engine's device")
+        nb = int(fit["n_blocks"])
+        if preds.numel() and nb < 1:
+            raise ValueError("isotonic_apply: a fit without blocks cannot be applied")
+        up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a[:nb]).view(t)).to(self.device)      # noqa: E731
+        return self._isotonic_apply_launch(up(fit["first_key"], np.int32), up(fit["rows"], np.int64),
+                                           up(fit["positives"], np.int64), nb, preds.contiguous())
+
+    def _score_sums_launch(self, preds, labels):
+        """mamdr_score_sums on the engine's stream -> the device tensor [2] fp64 (Brier sum, log-loss sum)."""
+        n = int(preds.numel())
+        out = torch.empty(2, dtype=torch.float64, device=self.device)
+        L.check(self.lib.mamdr_score_sums(_ptr(preds if n else None), _ptr(labels if n else None), n, _ptr(out), self._s()))
+        return out
+
+    def score_sums(self, preds, labels):
+        """(Brier sum, log-loss sum) (isotonic.py's definition) of device tensors preds / labels [n] fp32, as floats."""
+        self._check_pair("score_sums", preds, labels)
+        out = self._score_sums_launch(preds.contiguous(), labels.contiguous()).cpu().numpy()
+        return float(out[0]), float(out[1])
+
     # ------------------------------------------------------------ per-user grouped AUC (no reference counterpart)
     def group_auc_plan(self, domain, split):
         """the device copy of gauc.group_plan over the bound split's uid column: built at first use, uploaded once, kept with

@@ -212,6 +212,23 @@ class BaseModel(object):
                    n_short=int((slate_len < int(n_neg) + 1).sum()))
         return res
 
+    # ------------------------------------------------------------------ isotonic recalibration (no reference counterpart)
+    def isotonic_eval(self, domain, n_bins=20):
+        """isotonic recalibration of `domain` from the live weights, on the device: the val and the test split are evaluated
+        with their predictions kept there; the isotonic (PAV) fit of the val split is applied to the test split; the test
+        split's Brier / log-loss sums and its ECE / PCOC over `n_bins` equal-mass bins (the existing exact metrics) are taken
+        before and after; the test split's OWN fit gives the CORP decomposition of its Brier score.  -> isotonic.finish's
+        report."""
+        from .. import isotonic
+        n_bins = isotonic.check_bins(n_bins)
+        eng = self.model
+        val_p, test_p = eng.predict_device(domain, "val"), eng.predict_device(domain, "test")
+        val_y, test_y = eng.data[(domain, "val")]["label"], eng.data[(domain, "test")]["label"]
+        val_fit, test_fit = eng.isotonic_fit(val_p, val_y), eng.isotonic_fit(test_p, test_y)
+        fitted = eng.isotonic_apply(val_fit, test_p)
+        return isotonic.finish(val_fit, test_fit, eng.score_sums(test_p, test_y), eng.score_sums(fitted, test_y),
+                               eng.exact_metrics(test_p, test_y, n_bins), eng.exact_metrics(fitted, test_y, n_bins))
+
     # ------------------------------------------------------------------ domain conflict (no reference counterpart)
     def domain_conflict(self, n_batches=None):
         """conflict.measure at the live weights: one gradient per train domain over its first `n_batches` batches (None or 0:

@@ -137,6 +137,13 @@ class SpecificBase(MAML):
         with self._best_of_domain(domain):
             return self.base_model.sampled_eval(domain, n_neg, seed, users, exclude_seen)
 
+    def isotonic_eval(self, domain, n_bins=20):
+        """BaseModel.isotonic_eval under domain `domain`'s own weights, installed and put back as rank_eval does: the best
+        theta (+|*) phi_domain for the call, the previous live flat vector afterwards, bit for bit.  A finetune run is
+        evaluated with the un-finetuned best merged weights: the per-domain finetuned models are not kept."""
+        with self._best_of_domain(domain):
+            return self.base_model.isotonic_eval(domain, n_bins)
+
     def domain_conflict(self, n_batches=None):
         """BaseModel.domain_conflict at the best theta ALONE -- the shared point that Domain Negotiation negotiates, without
         any domain's phi_d: it is assigned to the meta parameters for the call and the previous live flat vector is put

@@ -16,13 +16,25 @@ from oracle import torch_ref as tref      # noqa: E402
 from oracle import tower as otower        # noqa: E402
 
 F32 = np.float32
+# row counts at which kernels change path (one row, less than a 4-row tile, one past a 16-row and a 64-row tile): the
+# oracles judge the HIP engines there (tests/test_gpu_edge_batches.py), so float64 autograd judges the oracles there first
+EDGE_B = (1, 2, 3, 17, 65)
+# Inputs on which float64 cannot judge fp32 at the bars of _check_grads get another seed; the bars stay.  Two causes:
+#  * relu kink: one pre-activation is within fp32 rounding of zero (star, B = 65, seed 12: row 42, unit 0 of the last
+#    hidden layer is 2.8e-8 in float64 and 0 in fp32), so the two sides differentiate different functions;
+#  * cancellation: with 2 or 3 rows of both labels a column sum of (p - y) / B -- gb, wo, a bias -- is a difference of
+#    O(0.3) terms that leaves 1e-3 (seed 12, pn/dense, B = 2: -0.26501 + 0.26631), so one ulp of p is > 2e-6 of the sum.
+EDGE_SEEDS = {("star", 65): 13,                                              # relu kink
+              ("nfm", True, 0.5, True, 2): 32, ("pnn", False, 0.5, True, 17): 32,      # gb: cancellation
+              ("ccpm", True, 0.0, False, 2): 38}                             # wo: cancellation
 
 
 def _batch(rs, n_user, n_item, n_domain, B, single_domain=None):
     uid = rs.randint(0, n_user, B).astype(np.int32)
     pid = rs.randint(0, n_item, B).astype(np.int32)
     uid[: B // 8] = uid[0]                  # repeated rows: the scatter-add paths must sum them
-    pid[B // 2:B // 2 + 5] = pid[1]
+    if B > 1:                               # (one row has no second row to repeat: the draws above are the whole batch)
+        pid[B // 2:B // 2 + 5] = pid[1]
     dom = (np.full(B, single_domain) if single_domain is not None else rs.randint(0, n_domain, B)).astype(np.int32)
     label = (rs.uniform(size=B) < 0.3).astype(F32)
     return uid, pid, dom, label
@@ -55,12 +67,25 @@ def _check_grads(got32, want64, names, rtol=3e-4):
         assert rel < (2e-6 if n != "log_var" else 2e-6 * max(1.0, 2.0 / max(np.linalg.norm(w), 1e-30))), (n, rel)
 
 
-@pytest.mark.parametrize("tower,emb_trainable,rate,uncertainty", [
+DEEPCTR_CASES = [
     ("mlp", False, 0.5, False), ("mlp", True, 0.5, False), ("mlp", False, 0.0, False), ("mlp", False, 0.5, True),
-    ("deepfm", True, 0.5, False), ("deepfm", False, 0.0, False), ("wdl", True, 0.5, False)])
+    ("deepfm", True, 0.5, False), ("deepfm", False, 0.0, False), ("wdl", True, 0.5, False)]
+
+
+@pytest.mark.parametrize("tower,emb_trainable,rate,uncertainty", DEEPCTR_CASES)
 def test_deepctr_towers_gradients_vs_float64_autograd(tower, emb_trainable, rate, uncertainty):
-    rs = np.random.RandomState(11)
-    n_user, n_item, n_domain, B = 300, 200, 5, 192
+    _deepctr_case(tower, emb_trainable, rate, uncertainty, 192)
+
+
+@pytest.mark.parametrize("B", EDGE_B)
+@pytest.mark.parametrize("tower,emb_trainable,rate,uncertainty", DEEPCTR_CASES)
+def test_deepctr_towers_gradients_vs_float64_autograd_at_edge_batches(tower, emb_trainable, rate, uncertainty, B):
+    _deepctr_case(tower, emb_trainable, rate, uncertainty, B)
+
+
+def _deepctr_case(tower, emb_trainable, rate, uncertainty, B, seed=11):
+    rs = np.random.RandomState(seed)
+    n_user, n_item, n_domain = 300, 200, 5
     p = _params(rs, n_user, n_item, n_domain, tower, uncertainty)
     uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=2 if uncertainty else None)
     deepfm = {"deepfm": 1, "wdl": 2}.get(tower, 0)
@@ -108,8 +133,18 @@ def test_deepctr_towers_other_hidden_dims_vs_float64_autograd(tower, emb_trainab
 
 @pytest.mark.parametrize("emb_trainable", [True, False])
 def test_star_tower_gradients_vs_float64_autograd(emb_trainable):
-    rs = np.random.RandomState(12)
-    n_user, n_item, n_domain, B = 300, 200, 4, 192
+    _star_case(emb_trainable, 192)
+
+
+@pytest.mark.parametrize("B", EDGE_B)
+@pytest.mark.parametrize("emb_trainable", [True, False])
+def test_star_tower_gradients_vs_float64_autograd_at_edge_batches(emb_trainable, B):
+    _star_case(emb_trainable, B, EDGE_SEEDS.get(("star", B), 12))
+
+
+def _star_case(emb_trainable, B, seed=12):
+    rs = np.random.RandomState(seed)
+    n_user, n_item, n_domain = 300, 200, 4
     p = ostar.init_params(rs, n_user, n_item, n_domain)
     for n in ("pn_gamma_shared", "pn_gamma_spec"):
         p[n] = (p[n] + rs.standard_normal(p[n].shape) * 0.2).astype(F32)
@@ -196,17 +231,26 @@ def test_torch_cpu_model_follows_the_oracle():
 
 
 # ------------------------------------------------------------------ multi-task towers (oracle/mtl.py)
-@pytest.mark.parametrize("kind,emb_trainable,rate", [
+MTL_CASES = [
     ("shared_bottom", False, 0.5), ("shared_bottom", True, 0.0), ("mmoe", False, 0.5), ("mmoe", True, 0.5),
-    ("ple", False, 0.5), ("ple", False, 0.0)])
-def test_mtl_towers_gradients_vs_float64_autograd(kind, emb_trainable, rate):
+    ("ple", False, 0.5), ("ple", False, 0.0)]
+
+
+@pytest.mark.parametrize("B", EDGE_B)
+@pytest.mark.parametrize("kind,emb_trainable,rate", MTL_CASES)
+def test_mtl_towers_gradients_vs_float64_autograd_at_edge_batches(kind, emb_trainable, rate, B):
+    test_mtl_towers_gradients_vs_float64_autograd(kind, emb_trainable, rate, B)
+
+
+@pytest.mark.parametrize("kind,emb_trainable,rate", MTL_CASES)
+def test_mtl_towers_gradients_vs_float64_autograd(kind, emb_trainable, rate, B=48, seed=23):
     """oracle/mtl.py (deepctr SharedBottom / MMOE / PLE under deep_mtl_ctr.py's per-domain models): the hand-derived
     gradients of task d -- experts, softmax gate and its DNN, tower, head, domain table, trainable tables with
     repeated rows -- against float64 autograd of oracle/torch_ref.mtl_forward; tensors outside task d's model get no
     gradient on either side."""
     from oracle import mtl as omtl
-    rs = np.random.RandomState(23)
-    n_user, n_item, D, B = 60, 40, 4, 48
+    rs = np.random.RandomState(seed)
+    n_user, n_item, D = 60, 40, 4
     spec = omtl.Spec(kind, D, expert_hidden=(32, 16), tower_hidden=(8,), gate_hidden=(8,), num_experts=3,
                      shared_expert_num=2, specific_expert_num=2, emb_dim=8)
     p = omtl.init_params(rs, spec, n_user, n_item)
@@ -250,13 +294,23 @@ def test_mtl_adam_shares_the_beta_powers_between_the_domain_models():
 
 
 # ------------------------------------------------------------------ NFM / PNN (oracle/fmnets.py)
-@pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", [
+NFM_PNN_CASES = [
     ("nfm", False, 0.5, False), ("nfm", True, 0.5, False), ("pnn", False, 0.5, False), ("pnn", True, 0.0, False),
-    ("nfm", True, 0.5, True), ("pnn", False, 0.5, True)])
-def test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty):
+    ("nfm", True, 0.5, True), ("pnn", False, 0.5, True)]
+
+
+@pytest.mark.parametrize("B", EDGE_B)
+@pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", NFM_PNN_CASES)
+def test_nfm_pnn_gradients_vs_float64_autograd_at_edge_batches(kind, emb_trainable, rate, uncertainty, B):
+    test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty, B,
+                                               EDGE_SEEDS.get((kind, emb_trainable, rate, uncertainty, B), 31))
+
+
+@pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", NFM_PNN_CASES)
+def test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty, B=48, seed=31):
     from oracle import fmnets as ofm
-    rs = np.random.RandomState(31)
-    n_user, n_item, D, B = 60, 40, 4, 48
+    rs = np.random.RandomState(seed)
+    n_user, n_item, D = 60, 40, 4
     p = ofm.init_params(rs, kind, n_user, n_item, D, emb_dim=8, hidden=(16, 8, 4))
     p["domain_emb"] = (rs.standard_normal(p["domain_emb"].shape) * 0.05).astype(F32)
     for n in ("b0", "b1", "b2", "lin_user", "lin_item", "lin_domain"):
@@ -276,16 +330,26 @@ def test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncert
     _check_grads(g, g64, names)
 
 
-@pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", [
+CCPM_AUTOINT_CASES = [
     ("ccpm", False, 0.5, False), ("ccpm", True, 0.0, False), ("autoint", False, 0.5, False), ("autoint", True, 0.5, False),
-    ("ccpm", False, 0.5, True), ("autoint", True, 0.5, True)])
-def test_ccpm_autoint_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty):
+    ("ccpm", False, 0.5, True), ("autoint", True, 0.5, True)]
+
+
+@pytest.mark.parametrize("B", EDGE_B)
+@pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", CCPM_AUTOINT_CASES)
+def test_ccpm_autoint_gradients_vs_float64_autograd_at_edge_batches(kind, emb_trainable, rate, uncertainty, B):
+    test_ccpm_autoint_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty, B,
+                                                    EDGE_SEEDS.get((kind, emb_trainable, rate, uncertainty, B), 37))
+
+
+@pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", CCPM_AUTOINT_CASES)
+def test_ccpm_autoint_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty, B=48, seed=37):
     """oracle/fmnets.py's CCPM (convolution over the field axis, max over the fields, tanh) and AutoInt (three multi-head
     self-attention layers with residuals) -- hand-derived fp32 backward passes -- against float64 autograd of a forward
     written with torch's own conv2d / softmax."""
     from oracle import fmnets as ofm
-    rs = np.random.RandomState(37)
-    n_user, n_item, D, B = 60, 40, 4, 48
+    rs = np.random.RandomState(seed)
+    n_user, n_item, D = 60, 40, 4
     E = 128 if kind == "autoint" else 8            # (the attention layers' second and third inputs are 32 wide whatever E is)
     E = 8
     p = ofm.init_params_conv(rs, kind, n_user, n_item, D, emb_dim=E, hidden=(16, 8, 4))

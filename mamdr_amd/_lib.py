@@ -16,6 +16,7 @@ SPLIT_TRAIN, SPLIT_VAL, SPLIT_TEST = 0, 1, 2
 OPT_ADAM, OPT_SGD, OPT_ACCUMULATE = 0, 1, 2
 MERGE_PLUS, MERGE_TIMES = 0, 1
 GRAM_SLAB, GRAM_MAX_VEC = 16384, 32         # MAMDR_GRAM_SLAB, MAMDR_GRAM_MAX_VEC (mamdr_gram)
+PCG_MAX_SEG, PCG_MAX_COLS = 24, 4096        # tensors per mamdr_pcgrad_project call, longest slice (include/mamdr_hip.h)
 (SEG_USER_EMB, SEG_ITEM_EMB, SEG_DOMAIN_EMB, SEG_W0, SEG_W1, SEG_W2, SEG_B0, SEG_B1, SEG_B2, SEG_WO,
  SEG_GB, SEG_LIN_USER, SEG_LIN_ITEM, SEG_LIN_DOMAIN) = range(14)
 SEG_NAMES = ("user_emb", "item_emb", "domain_emb", "W0", "W1", "W2", "b0", "b1", "b2", "wo", "gb",

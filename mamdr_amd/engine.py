@@ -169,16 +169,20 @@ class FlatVectorOps(object):
 
     def pcgrad_project(self, final, aux, tensors=None):
         """PCGrad.PCGrad with final_grads is current_grads (pcgrad.py:107-124,152-160) on flat device vectors.
-        tensors: [(offset, rows, cols)], default = every segment inside the vectors."""
+        tensors: [(offset, rows, cols)], default = every segment inside the vectors.  Any number of tensors: one call
+        takes at most L.PCG_MAX_SEG of them (its table travels as a kernel argument), the tensors are independent of
+        each other, so the list goes out in calls of that many -- the same bytes as one call would leave."""
         if tensors is None:
             shapes = self.segment_shapes()
             tensors = [(off, shapes[n][0], shapes[n][1]) for n, (off, cnt) in self.segments.items()
                        if off + cnt <= final.numel()]
-        n = len(tensors)
-        offs = (C.c_int64 * n)(*[t[0] for t in tensors])
-        rows = (C.c_int64 * n)(*[t[1] for t in tensors])
-        cols = (C.c_int32 * n)(*[t[2] for t in tensors])
-        L.check(self.lib.mamdr_pcgrad_project(_ptr(final), _ptr(aux), offs, rows, cols, n, self._s()))
+        for lo in range(0, max(len(tensors), 1), L.PCG_MAX_SEG):
+            part = tensors[lo:lo + L.PCG_MAX_SEG]
+            n = len(part)
+            offs = (C.c_int64 * n)(*[t[0] for t in part])
+            rows = (C.c_int64 * n)(*[t[1] for t in part])
+            cols = (C.c_int32 * n)(*[t[2] for t in part])
+            L.check(self.lib.mamdr_pcgrad_project(_ptr(final), _ptr(aux), offs, rows, cols, n, self._s()))
 
     # ---- fp64 Gram matrices of flat vectors (mamdr_gram; no reference counterpart)
     _gram_work = None       # the slab partials' workspace: kept by the engine, grown on demand

@@ -100,12 +100,17 @@ class GraphEngine(DeviceEngine):
     def segment_shapes(self):
         """{tensor: (slices along the last axis, slice length)} of the Keras variables behind the tensors -- what numpy's
         axis=-1 reductions in the reference's PCGrad see (model_zoo/pcgrad.py:152-160): rows of a kernel / table, a bias
-        as one slice, the Dense(1) head kernels and deepctr's 1-d linear tables ([n, 1]) as n slices of one element."""
+        as one slice, the Dense(1) head kernels and deepctr's 1-d linear tables ([n, 1]) as n slices of one element.
+        AutoInt's `att<l>_w` [d][128] holds FOUR Keras variables [d, 32] side by side (W_query | W_key | W_value | W_res):
+        the reference reduces over the 32 columns of one of them, and the four column blocks of a row-major [d][128] are
+        the rows of a contiguous [4 d][32]."""
         out = {}
         for name, (rows, cols) in self.shapes.items():
             cnt = rows * cols
             if name.startswith("lin_") or name.endswith("/w") or name in ("wo", "gb") or name.endswith("/gb"):
                 out[name] = (cnt, 1)
+            elif self.kind == "autoint" and name.startswith("att") and name.endswith("_w"):
+                out[name] = (rows * 4, cols // 4)
             else:
                 out[name] = (rows, cols)
         return out

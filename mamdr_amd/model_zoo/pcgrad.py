@@ -6,11 +6,25 @@ each one's pass-gradient onto the running gradient (`mamdr_pcgrad_project`, bit-
 numpy) and take one outer-Adam step (lr = meta_learning_rate) of the model with the result.  The passes run
 the step kernels in accumulate mode (dropout off, no update).
 """
+from .. import _lib as L
 from .. import meta
 from .maml import MAML
 
 
 class PCGrad(MAML):
+    def __init__(self, base_model):
+        """Any number of tensors projects (engine.pcgrad_project sends the table in calls the library takes); a variable
+        whose slices along the last axis are longer than the kernel walks (one thread per slice) is refused HERE, not
+        by the library inside the first epoch.  The check covers EVERY tensor of the tower: `meta_parms` is applied when
+        training starts, so a tower whose only such variable lies outside the selection is refused as well."""
+        MAML.__init__(self, base_model)
+        shapes = getattr(self.model, "segment_shapes", None)
+        wide = {n: c for n, (r, c) in shapes().items() if c > L.PCG_MAX_COLS} if shapes is not None else {}
+        if wide:
+            raise NotImplementedError("pcgrad: the projection (mamdr_pcgrad_project) walks slices of up to %d elements along a "
+                                      "variable's last axis; this tower has %s (every tensor is checked, whatever meta_parms selects)"
+                                      % (L.PCG_MAX_COLS, wide))
+
     def train(self):
         print("Start PCGrad training on model: {}".format(self.model_config["name"]))
         tc = self.train_config

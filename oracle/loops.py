@@ -105,11 +105,15 @@ def mldg_epoch(model, theta, outer, acc, data, seq, perm_fn, batch_size, meta_lr
 
 def tensor_views(model, flat):
     """per-tensor views of a flat vector in the shapes the Keras variables have (the 1-d linear tables and the
-    uncertainty scalars are [n, 1] there) -- what numpy's axis=-1 reductions see in the reference."""
+    uncertainty scalars are [n, 1] there) -- what numpy's axis=-1 reductions see in the reference.  AutoInt's `att<l>_w`
+    [d, 128] is four Keras variables [d, 32] side by side (fmnets.py: W_query | W_key | W_value | W_res); their rows are
+    the rows of the same memory read as [4 d, 32].  (tests/keras_variables.py holds the table these shapes are held to.)"""
     views, o = [], 0
     for name in model.names:
         p = model.params[name]
         shape = (-1, 1) if name in ("lin_user", "lin_item", "lin_domain", "log_var") else p.shape
+        if name.startswith("att") and name.endswith("_w"):
+            shape = (-1, p.shape[-1] // 4)
         views.append(flat[o:o + p.size].reshape(shape))
         o += p.size
     return views

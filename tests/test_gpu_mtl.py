@@ -15,18 +15,15 @@ torch = pytest.importorskip("torch")
 
 import oracle_jobs                      # noqa: E402
 from ensemble import Ensemble, TWIN_SEEDS      # noqa: E402
+from keras_variables import MTL_SHAPES  # noqa: E402
 from oracle import auc as oauc          # noqa: E402
 from oracle import mtl as omtl          # noqa: E402
 from oracle import rng as orng          # noqa: E402
 
 F32 = np.float32
 
-SHAPES = {
-    # (expert_hidden, tower_hidden, gate_hidden, num_experts, shared_expert_num, specific_expert_num)
-    "shared_bottom": ((256, 128), (64,), (), 0, 0, 0),
-    "mmoe": ((128, 64), (64,), (64,), 3, 0, 0),
-    "ple": ((128,), (64,), (64,), 0, 2, 2),
-}
+# (expert_hidden, tower_hidden, gate_hidden, num_experts, shared_expert_num, specific_expert_num) per kind
+SHAPES = MTL_SHAPES
 
 
 # the reference's own shapes: config/Taobao-10/{shared_bottom,mmoe,ple}.json (batch_size 1024, 10 domains)

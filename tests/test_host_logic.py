@@ -619,7 +619,8 @@ def test_mtl_ple_levels_and_trainable_tables_are_named(tmp_path, monkeypatch):
                                   "nfm_meta_mamdr_finetune"])
 def test_nfm_pnn_run_entry(tmp_path, monkeypatch, name):
     """deepctr NFM / PNN through run.py's entry (plain alternate training; the meta wrappers on top: the outer updates
-    are the same flat-vector operations whatever the tower, the accumulate passes of MAML / MLDG / PCGrad run the tower's
+    are the same flat-vector operations whatever the tower -- PCGrad's projection excepted, which follows the variables'
+    shapes: tests/test_pcgrad_tables_host.py, tests/test_gpu_pcgrad_towers.py --, the accumulate passes of MAML / MLDG / PCGrad run the tower's
     step in learning phase 0)."""
     patch_emb_dim(monkeypatch)
     cfg = tiny_config(tmp_path, name, epochs=2)

@@ -86,12 +86,16 @@ def test_mamdr_batch_and_domain_weights(G, method):
             assert same_bits(outer.mamdr_domain_weights(n1, merged), wdw)
 
 
-def test_pcgrad_projection_matches_reference_goldens(golden_dir):
-    """oracle.outer.pcgrad_project against vectors produced by the reference's own PCGrad.PCGrad
-    (tests/golden/make_pcgrad_goldens.py): two successive projections, every tensor shape of the tower."""
+@pytest.mark.parametrize("golden", ["pcgrad_goldens.npz", "pcgrad_shape_goldens.npz"])
+def test_pcgrad_projection_matches_reference_goldens(golden_dir, golden):
+    """oracle.outer.pcgrad_project against vectors produced by the reference's own PCGrad.PCGrad: two successive
+    projections.  pcgrad_goldens.npz (tests/golden/make_pcgrad_goldens.py): every tensor shape of the tower;
+    pcgrad_shape_goldens.npz (make_pcgrad_shape_goldens.py): every regime of numpy's pairwise summation, 1-d / 3-d /
+    [n, 1] variables, all-zero and equal rows, and rows whose products, dot product and squared norm are denormal while
+    the projection still moves the auxiliary gradient."""
     import os
     from oracle import outer as oouter
-    G = np.load(os.path.join(golden_dir, "pcgrad_goldens.npz"))
+    G = np.load(os.path.join(golden_dir, golden))
     n = int(G["n_tensors"])
     cur = [G["current_%d" % i].copy() for i in range(n)]
     for tag, step in (("aux1", "after1"), ("aux2", "after2")):

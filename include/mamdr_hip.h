@@ -598,6 +598,45 @@ int mamdr_gram(const float* d_vecs, int64_t stride, int32_t n_vec, int64_t n_col
                const int64_t* h_off, const int64_t* h_count, int32_t n_range,
                double* d_work, int64_t work_doubles, double* d_out, void* stream);
 
+/* What top-K lists are made of -- the two device reductions behind the beyond-accuracy report (mamdr_amd/list_metrics.py:
+ * coverage, Gini, entropy, novelty, personalisation, intra-list diversity).  NO REFERENCE COUNTERPART: the reference never
+ * builds a list.  Stateless, any stream, no synchronisation, no allocation; both calls take lists from anywhere.
+ *
+ * mamdr_id_counts: a histogram of int32 ids.
+ *   d_ids [n], d_label [n] or null  d_counts[i] = the number of positions j with d_ids[j] == i -- with a label column, of
+ *                                   those with d_label[j] != 0 (fp32 compare: -0.0 is 0, NaN is not).  An id outside
+ *                                   [0, n_bins) counts nowhere: the -1 padding of a short list, a foreign id
+ *   d_counts [n_bins]               zeroed by the call on `stream`, then counted into
+ *   The two inputs it serves: item EXPOSURE -- the flattened [Q][K] lists, no labels -- and item POPULARITY -- a train
+ *   split's pid and label columns, which already live on the device.  Integer atomics only: the same bits whatever order
+ *   the workgroups run in.  n == 0 zeroes the counts and returns MAMDR_OK (the two input pointers may then be null).
+ *   MAMDR_EINVAL, nothing launched: a null d_counts, a null d_ids with n > 0, a pointer not 4-byte aligned, n < 0,
+ *   n >= 2^32 (a count is 32 bits), n_bins <= 0.
+ *
+ * mamdr_list_similarity: the sum of pairwise cosines inside every list, over rows of an embedding table.
+ *   d_ids [n_list][k]               k in 1 .. MAMDR_LIST_MAX_K.  An entry of list q is VALID when its id lies inside
+ *                                   [0, n_rows); every other id is padding, wherever it sits in the list.  Duplicate ids
+ *                                   are simply two entries
+ *   d_rows [n_rows][emb_dim]        fp32, 16-byte aligned, emb_dim 32, 64, 128 or 256 (the widths the project trains at)
+ *   d_pairs [n_list]                L (L - 1) / 2 with L the list's valid entries
+ *   d_sim_sum [n_list]              sum over the valid entries a < b, in list order, of cos(x_a, x_b)
+ * Arithmetic.  cos = (x_a . x_b) / (|x_a| |x_b|), exactly 0 when either norm is 0.  Dots and squared norms are fp32, on
+ * the fp32 matrix cores: one fma chain per dot product over the columns in a fixed order; the squared norms are the Gram
+ * matrix's own diagonal.  Square root and the two divisions (g / |x_a|) / |x_b| are IEEE (correctly rounded).  The fp32
+ * cosines are added in fp64.  Against the fp64 definition on the same fp32 rows (list_metrics.list_similarity_host):
+ * |d_sim_sum - host| <= d_pairs * (2 emb_dim + 8) * 2^-24.  NaN and Inf rows propagate as IEEE into their own pairs.
+ * Order.  Every order -- of the columns inside a dot product, of the cosines inside the sum -- depends on the list's own
+ * valid entries alone.  No floating-point atomics.  A list's two outputs are the same bits from run to run, wherever the
+ * list sits in the call, whatever its neighbours are, wherever its padding sits and whatever k the call has.
+ * MAMDR_EINVAL, nothing launched: a null pointer; d_ids / d_pairs not 4-byte, d_sim_sum not 8-byte, d_rows not 16-byte
+ * aligned; n_list <= 0; k outside 1 .. MAMDR_LIST_MAX_K; emb_dim not one of the four widths; n_rows <= 0.
+ * (Added within ABI 19: new entry points only, no structure or existing call changed.) */
+#define MAMDR_LIST_MAX_K 128
+int mamdr_id_counts(const int32_t* d_ids, const float* d_label, int64_t n, int64_t n_bins, uint32_t* d_counts,
+                    void* stream);
+int mamdr_list_similarity(const int32_t* d_ids, int32_t n_list, int32_t k, const float* d_rows, int64_t n_rows,
+                          int32_t emb_dim, double* d_sim_sum, int32_t* d_pairs, void* stream);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

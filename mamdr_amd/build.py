@@ -43,6 +43,9 @@ SOURCES = [
     ("isotonic_kernels.hip", ["-ffp-contract=off", "-Rpass-analysis=kernel-resource-usage"]),
     # gram_kernels: its register / LDS / scratch report: profiles/conflict_bench.txt
     ("gram_kernels.hip", ["-Rpass-analysis=kernel-resource-usage"]),
+    # list_kernels: the cosines' square root and divisions are IEEE (correctly rounded; hipcc's default, spelled out here);
+    # its register / LDS / scratch report: profiles/list_metrics.txt
+    ("list_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)
     ("mamdr_api.hip", []),
     ("step_context.hip", []),

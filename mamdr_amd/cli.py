@@ -16,7 +16,8 @@ Not options of the reference's run.py: --lanes, --recommend K (top-K lists per d
 --sampled-eval [N] with --sampled-eval-ks KS (train.sampled_eval, train.sampled_eval_ks, train.sampled_eval_seed: every held-out
 positive ranked among N sampled items the user never interacted with, recommend.sampled_report), and
 --conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report), and
---isotonic [B] with --isotonic-out FILE (train.isotonic: isotonic recalibration fitted on val, applied to test, and the CORP decomposition of the test Brier score, isotonic.report).
+--isotonic [B] with --isotonic-out FILE (train.isotonic: isotonic recalibration fitted on val, applied to test, and the CORP decomposition of the test Brier score, isotonic.report), and
+--list-metrics [K] with --list-metrics-out FILE (train.list_metrics: what the top-K lists are made of -- coverage, Gini, entropy, novelty, tail share, personalisation and intra-list diversity per domain, list_metrics.report).
 """
 import argparse
 import json
@@ -157,6 +158,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
         raise NotImplementedError("train.isotonic (run.py --isotonic): the isotonic report is not computed across processes "
                                   "or lanes (the best phi_d slots are current only on their owners); run it with one process "
                                   "and train.lanes = 1")
+    if config["train"].get("list_metrics") is not None and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.list_metrics (run.py --list-metrics): the list metrics are not computed across processes "
+                                  "or lanes (the best phi_d slots are current only on their owners); run it with one process "
+                                  "and train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
     if lanes > 1:
         # (under N processes the lanes of every rank are a slice of ONE world of N * lanes participants: a rank's DR queries
@@ -210,6 +215,10 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
             from . import isotonic
             _, reports = isotonic.report(model, int(config["train"]["isotonic"]), config["train"].get("isotonic_out"))
             _extend_result(saved, isotonic.headline(reports))
+        if config["train"].get("list_metrics") is not None:
+            from . import list_metrics
+            _, reports = list_metrics.report(model, int(config["train"]["list_metrics"]), config["train"].get("list_metrics_out"))
+            _extend_result(saved, list_metrics.headline(reports))
     return avg_loss, avg_auc, domain_loss, domain_auc
 
 
@@ -265,6 +274,12 @@ def cli(argv=None):
                              "and after, and the CORP decomposition of the test Brier score (train.isotonic)")
     parser.add_argument("--isotonic-out", type=str, default=None, metavar="FILE",
                         help=".npz the isotonic fits go to (default: under train.result_save_path)")
+    parser.add_argument("--list-metrics", type=int, default=None, nargs="?", const=-1, metavar="K",
+                        help="after the run: what every domain's top-K lists are made of -- catalogue coverage, Gini and entropy "
+                             "of exposure, novelty, average popularity, tail share, personalisation and intra-list diversity "
+                             "(K 1 .. 128; default: --recommend's K, or 10) (train.list_metrics)")
+    parser.add_argument("--list-metrics-out", type=str, default=None, metavar="FILE",
+                        help=".npz the list metrics go to (default: under train.result_save_path)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -310,6 +325,13 @@ def cli(argv=None):
         config["train"]["isotonic"] = args.isotonic
     if args.isotonic_out is not None:
         config["train"]["isotonic_out"] = args.isotonic_out
+    if args.list_metrics is not None:
+        k = args.list_metrics if args.list_metrics != -1 else (args.recommend or 10)          # (no value: --recommend's K, or 10)
+        if not 1 <= k <= 128:
+            parser.error("--list-metrics K: lists of K items, 1 .. 128")
+        config["train"]["list_metrics"] = k
+    if args.list_metrics_out is not None:
+        config["train"]["list_metrics_out"] = args.list_metrics_out
     if args.recommend is None:
         return main(config)
     return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

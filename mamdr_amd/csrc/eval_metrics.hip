@@ -1,6 +1,7 @@
 // C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics,
-// mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply and mamdr_score_sums.  Stateless, like
-// the outer updates: no context, the caller's stream.  Host code only.
+// mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply and mamdr_score_sums, and of top-K lists:
+// mamdr_id_counts and mamdr_list_similarity.  Stateless, like the outer updates: no context, the caller's stream.  Host code
+// only.
 #include "step_ctx.h"
 
 // a call's own scratch, ordered on its stream: `bytes` are allocated (nothing for 0), `run(ws)` launches and returns its
@@ -222,6 +223,56 @@ int mamdr_score_sums(const float* d_pred, const float* d_label, int64_t n, doubl
         launch_score_sums(a, s);
         return hipGetLastError();
     });
+}
+
+// ---- what top-K lists are made of: id counts and intra-list similarity (list_kernels.hip)
+int mamdr_id_counts(const int32_t* d_ids, const float* d_label, int64_t n, int64_t n_bins, uint32_t* d_counts, void* stream) {
+    if (!d_counts) return fail(MAMDR_EINVAL, "mamdr_id_counts: null counts pointer");
+    if (n < 0 || n >= ((int64_t)1 << 32)) return fail(MAMDR_EINVAL, "mamdr_id_counts: n %lld outside [0, 2^32)", (long long)n);
+    if (n_bins <= 0) return fail(MAMDR_EINVAL, "mamdr_id_counts: n_bins %lld is not positive", (long long)n_bins);
+    if (n > 0 && !d_ids) return fail(MAMDR_EINVAL, "mamdr_id_counts: null ids pointer");
+    if (misaligned(3, d_ids, d_label, d_counts))
+        return fail(MAMDR_EINVAL, "mamdr_id_counts: a pointer is not aligned to its element size");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)n_bins * sizeof(uint32_t), s));
+    if (n == 0) return MAMDR_OK;
+    IdCountArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = d_ids;
+    a.label = d_label;
+    a.n = n;
+    a.n_bins = n_bins;
+    a.counts = d_counts;
+    launch_id_counts(a, s);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_list_similarity(const int32_t* d_ids, int32_t n_list, int32_t k, const float* d_rows, int64_t n_rows, int32_t emb_dim,
+                          double* d_sim_sum, int32_t* d_pairs, void* stream) {
+    if (!d_ids || !d_rows || !d_sim_sum || !d_pairs)
+        return fail(MAMDR_EINVAL, "mamdr_list_similarity: null ids / rows / sim_sum / pairs pointer");
+    if (n_list <= 0) return fail(MAMDR_EINVAL, "mamdr_list_similarity: n_list %d is not positive", (int)n_list);
+    if (k < 1 || k > MAMDR_LIST_MAX_K)
+        return fail(MAMDR_EINVAL, "mamdr_list_similarity: k %d outside 1..%d", (int)k, MAMDR_LIST_MAX_K);
+    if (emb_dim != 32 && emb_dim != 64 && emb_dim != 128 && emb_dim != 256)
+        return fail(MAMDR_EINVAL, "mamdr_list_similarity: emb_dim %d is not 32, 64, 128 or 256", (int)emb_dim);
+    if (n_rows <= 0) return fail(MAMDR_EINVAL, "mamdr_list_similarity: n_rows %lld is not positive", (long long)n_rows);
+    if (misaligned(3, d_ids, d_pairs) || misaligned(7, d_sim_sum) || misaligned(15, d_rows))
+        return fail(MAMDR_EINVAL, "mamdr_list_similarity: a pointer is not aligned (ids / pairs 4, sim_sum 8, rows 16 bytes)");
+    ListSimArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = d_ids;
+    a.n_list = n_list;
+    a.k = k;
+    a.rows = d_rows;
+    a.n_rows = n_rows;
+    a.emb_dim = emb_dim;
+    a.sim_sum = d_sim_sum;
+    a.pairs = d_pairs;
+    launch_list_sim(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
 }
 
 }  // extern "C"

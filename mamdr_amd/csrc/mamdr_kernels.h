@@ -1055,4 +1055,24 @@ struct GramArgs {
 };
 void launch_gram(const GramArgs& a, hipStream_t s);
 
+// list_kernels.hip: what top-K lists are made of (mamdr_id_counts, mamdr_list_similarity)
+constexpr int LIST_SIM_MAX_K = 128;   // = MAMDR_LIST_MAX_K
+struct IdCountArgs {
+    const int32_t* ids;            // [n]
+    const float* label;            // [n] or null: every position counts
+    int64_t n, n_bins;
+    uint32_t* counts;              // [n_bins], zeroed on the stream before the launch
+};
+void launch_id_counts(const IdCountArgs& a, hipStream_t s);         // n > 0
+struct ListSimArgs {
+    const int32_t* ids;            // [n_list][k]
+    int n_list, k;
+    const float* rows;             // [n_rows][emb_dim], 16-byte aligned
+    int64_t n_rows;
+    int emb_dim;                   // 32, 64, 128 or 256
+    double* sim_sum;               // [n_list]
+    int32_t* pairs;                // [n_list]
+};
+void launch_list_sim(const ListSimArgs& a, hipStream_t s);          // n_list > 0
+
 }  // namespace mamdr

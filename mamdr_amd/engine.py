@@ -284,6 +284,7 @@ class DeviceEngine(FlatVectorOps):
         # the family's entry points, resolved once (train_steps runs inside the benchmark's timed region)
         for name in self.SHARED_CALLS:
             setattr(self, "_c_" + name, getattr(self.lib, self.PREFIX + name))
+        self._c_id_counts, self._c_list_similarity = self.lib.mamdr_id_counts, self.lib.mamdr_list_similarity
 
     def _check(self, code):
         return L.check(code, graph=self.GRAPH)
@@ -628,6 +629,44 @@ class DeviceEngine(FlatVectorOps):
             rep.update(T=T.cpu().numpy()[:G].view(np.uint64), P=P.cpu().numpy()[:G].view(np.uint32))
         return rep
 
+    # ------------------------------------------------------------ what top-K lists are made of (no reference counterpart)
+    def id_counts(self, ids, n_bins, label=None):
+        """mamdr_id_counts on the engine's stream: ids -- an int32 device tensor of any shape, taken flat -- counted into
+        n_bins bins, with `label` (fp32, as many elements) only the positions whose label is not 0.  An id outside
+        [0, n_bins) counts nowhere.  -> the device tensor [n_bins] int32, holding the uint32 counts; nothing is read back."""
+        n, n_bins = int(ids.numel()), int(n_bins)
+        if ids.dtype != torch.int32 or ids.device != self.device:
+            raise ValueError("id_counts: ids must be an int32 tensor on the engine's device")
+        if label is not None and (label.dtype != torch.float32 or label.device != self.device or label.numel() != n):
+            raise ValueError("id_counts: label must be an fp32 tensor of the ids' length on the engine's device")
+        if n_bins <= 0 or n >= 2 ** 32:
+            raise ValueError("id_counts: %d bins for %d ids (n_bins > 0, n < 2^32)" % (n_bins, n))
+        ids = ids.contiguous()
+        label = label.contiguous() if label is not None else None
+        counts = torch.empty(n_bins, dtype=torch.int32, device=self.device)
+        L.check(self._c_id_counts(_ptr(ids if n else None), _ptr(label if n else None), n, n_bins, _ptr(counts), self._s()))
+        return counts
+
+    def list_similarity(self, ids, rows):
+        """mamdr_list_similarity on the engine's stream: ids [Q, K] int32 (K <= 128; an id outside [0, n_rows) is padding),
+        rows [n_rows, E] fp32 (E 32, 64, 128 or 256; contiguous, 16-byte aligned), both device tensors -> the device tensors
+        (sim_sum [Q] float64: per list the sum of its valid entries' pairwise cosines, pairs [Q] int32: how many that is);
+        nothing is read back."""
+        if ids.dim() != 2 or ids.dtype != torch.int32 or ids.device != self.device:
+            raise ValueError("list_similarity: ids must be a [Q, K] int32 tensor on the engine's device")
+        if rows.dim() != 2 or rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous():
+            raise ValueError("list_similarity: rows must be a contiguous [n_rows, E] fp32 tensor on the engine's device")
+        Q, K = int(ids.shape[0]), int(ids.shape[1])
+        if not 1 <= K <= L.LIST_MAX_K or int(rows.shape[1]) not in L.LIST_EMB_DIMS or rows.shape[0] < 1:
+            raise ValueError("list_similarity: K %d (1 to %d), rows %d x %d (width one of %s)" % (
+                K, L.LIST_MAX_K, rows.shape[0], rows.shape[1], (L.LIST_EMB_DIMS,)))
+        sim_sum = torch.empty(Q, dtype=torch.float64, device=self.device)
+        pairs = torch.empty(Q, dtype=torch.int32, device=self.device)
+        if Q:
+            L.check(self._c_list_similarity(_ptr(ids.contiguous()), Q, K, _ptr(rows), int(rows.shape[0]), int(rows.shape[1]),
+                                            _ptr(sim_sum), _ptr(pairs), self._s()))
+        return sim_sum, pairs
+
     def bind_accumulator(self, acc):
         """meta-gradient accumulator of the MAML / MLDG / PCGrad meta passes (maml.py:202); optimizer="accumulate" adds
         to it (or, after set_moving_average, moves it towards every batch's gradient)."""
@@ -737,7 +776,7 @@ class TowerEngine(DeviceEngine):
             tower_tile = 16 if (group is not None and group.n >= 4 and tower in ("mlp", "deepfm", "wdl")) else 0
         if tower_tile:
             self.set_tower_tile(tower_tile)
-        self.tower = tower
+        self.tower, self.emb_dim = tower, int(emb_dim)
         self.n_params = int(self.lib.mamdr_param_count(self.ctx))
         # theta / phi vectors cover the META prefix only (all of it except for the Star tower)
         self.n_meta = int(self.lib.mamdr_meta_count(self.ctx))
@@ -889,6 +928,18 @@ class TowerEngine(DeviceEngine):
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         L.check(self.lib.mamdr_gather_rows(self.ctx, domain, split_id, _ptr(perm), first_row, n, _ptr(out)))
         return out
+
+    def item_rows(self):
+        """the item table the live weights score with, as a DEVICE view [n_item, emb_dim] fp32: the bound frozen table, or --
+        trainable tables -- the item segment of the live flat vector after mamdr_sync_tables (rows the library advances
+        lazily are made current first).  A view, not a copy: it is read on the engine's stream before the weights change."""
+        if not self.emb_trainable:
+            return self.tables["item_emb"]
+        off, cnt = self.segments["item_emb"]
+        if cnt != self.n_item * self.emb_dim or off % 4:
+            raise RuntimeError("item_rows: the item segment (%d floats at %d) is not [%d, %d] at a 16-byte offset" % (
+                cnt, off, self.n_item, self.emb_dim))
+        return self.weights[off:off + cnt].view(self.n_item, self.emb_dim)
 
     def recommend(self, uids, domains, k, candidates=None, exclude=None, want_scores=False):
         """top-K items for the queries (uids[q], domains[q]) from the live weights (mamdr_recommend: mlp / wdl / deepfm; no

@@ -212,6 +212,35 @@ class BaseModel(object):
                    n_short=int((slate_len < int(n_neg) + 1).sum()))
         return res
 
+    # ------------------------------------------------------------------ what the lists are made of (no reference counterpart)
+    def list_eval(self, domain, k):
+        """what list_metrics.summarise needs of `domain`, from the live weights: the lists of `recommend(domain, k)` and, on
+        the device, their exposure counts and the train split's label-1 popularity counts (the engine's id_counts:
+        mamdr_id_counts, over the whole item range) and the lists' pairwise similarity on the engine's item_rows() -- the
+        item table of the same weights -- (list_similarity: mamdr_list_similarity).  -> {"users" [Q], "ids" [Q, k],
+        "catalogue" (the candidate ids), "exposure" / "popularity" [n_item] int64, "sim_sum" [Q] float64, "pairs" [Q]
+        int32}.  It reads state only."""
+        import torch
+        from .. import list_metrics
+        k = list_metrics.check_k(k)
+        eng = self.model
+        r = self.recommend(domain, k)
+        catalogue = self._retrieval_problem(domain, r["users"], False)[0]
+        ids = torch.from_numpy(np.ascontiguousarray(r["ids"], np.int32)).to(eng.device)
+        n_item = int(eng.n_item)
+        exposure = eng.id_counts(ids, n_item)
+        popularity = None
+        if domain in self.dataset.train_dataset:
+            cols = eng.data[(domain, "train")]
+            popularity = eng.id_counts(cols["pid"], n_item, cols["label"])
+        sim_sum, pairs = eng.list_similarity(ids, eng.item_rows()) if ids.shape[0] else (np.zeros(0), np.zeros(0, np.int32))
+        def counts(t):          # (a device tensor holds the uint32 counts as int32: reinterpret, do not convert)
+            a = list_metrics.to_host(t)
+            return (a.view(np.uint32) if a.dtype == np.int32 else a).astype(np.int64)
+        return {"users": r["users"], "ids": r["ids"], "catalogue": catalogue, "exposure": counts(exposure),
+                "popularity": counts(popularity) if popularity is not None else np.zeros(n_item, np.int64),
+                "sim_sum": list_metrics.to_host(sim_sum).astype(np.float64), "pairs": list_metrics.to_host(pairs).astype(np.int32)}
+
     # ------------------------------------------------------------------ isotonic recalibration (no reference counterpart)
     def isotonic_eval(self, domain, n_bins=20):
         """isotonic recalibration of `domain` from the live weights, on the device: the val and the test split are evaluated

@@ -144,6 +144,12 @@ class SpecificBase(MAML):
         with self._best_of_domain(domain):
             return self.base_model.isotonic_eval(domain, n_bins)
 
+    def list_eval(self, domain, k):
+        """BaseModel.list_eval under domain `domain`'s own weights, installed and put back as rank_eval does: the lists are
+        scored and the item table is read while the best theta (+|*) phi_domain is installed."""
+        with self._best_of_domain(domain):
+            return self.base_model.list_eval(domain, k)
+
     def domain_conflict(self, n_batches=None):
         """BaseModel.domain_conflict at the best theta ALONE -- the shared point that Domain Negotiation negotiates, without
         any domain's phi_d: it is assigned to the meta parameters for the call and the previous live flat vector is put

@@ -45,7 +45,19 @@
 //            _bwd), Dense or StarFCN layers on the kernels of the batch's first-row domain (k_star_eff, k_star_chain), the auxiliary
 //            network joined at the head (k_star_join_fwd / _bwd); moving statistics outside the flat vector (mamdr_graph_bind_aux)
 //
-// Host side, from "host side: structure of the tower" on:
+// Device side: five headers that this file alone includes, in this order (ONE translation unit; the code object lists the
+// plain kernels in the order their definitions are read, so the headers are cut along the order the code has always had)
+//   graph_gemm.h     GemmArgs / GroupTab, gemm_tile (64 x 64) and gemm_tile32 (32 x 32), k_graph_gemm / _gemm32 and their _group
+//                    forms (apply_member)
+//   graph_reduce.h   colsum_body and split_sum4 (every column sum / split sum of the engine), k_graph_colsum, k_graph_wfinish /
+//                    _group, the queue (WMulti: k_graph_wgrad_multi; WFinish: wfinish_multi_body), GradSink / opt_elem / opt_step4 /
+//                    sink1 / sink4 / no_sink, k_graph_dx_reduce, k_graph_small_tn
+//   graph_towers.h   k_graph_gather, wave_sum, feat / fm (NFM, PNN, DeepFM) and NFM's linear domain table, CCPM, attention,
+//                    k_graph_small_nt / _add_x, gate, head, loss, scale
+//   graph_tail.h     the step's end: the domain table's gradient, TailJobs / k_graph_tail, AdamArgs / k_graph_adam
+//   graph_star.h     StarNormArgs .. k_star_join_bwd
+//
+// Host side, here (GLAUNCH, the error buffer, the launch_* helpers, then "host side: structure of the tower"):
 //   contractions   gemm_args / fwd_args / din_args describe a GemmArgs by role, launch_wgrad takes a weight gradient's operands;
 //                  dnn_forward / dnn_backward walk ONE DNN over its layers' operands of this step (LayerOps: layers_of, and
 //                  star_layers / star_aux_net for the scratch blocks of k_star_eff / k_star_chain), dnn_forward_group /
@@ -70,6 +82,11 @@
 #include "../../include/mamdr_hip.h"
 #include "mamdr_kernels.h"
 #include "host_common.h"
+#include "graph_gemm.h"
+#include "graph_reduce.h"
+#include "graph_towers.h"
+#include "graph_tail.h"
+#include "graph_star.h"
 
 // every kernel launch of this engine goes through here: the count is what tools/graph_bench.py reports as launches per step
 static std::atomic<long long> g_graph_launches{0};      // (contexts may be driven from several host threads: lanes)
@@ -88,92 +105,6 @@ template <typename... A>
 int gfail(int code, const char* fmt, A... a) { return g_gerr.fail(code, fmt, a...); }
 #define GHIP(expr) MAMDR_HIP_TRY(g_gerr, expr, #expr)
 
-constexpr int GT = 64;      // output tile (rows and columns)
-constexpr int GK = 16;      // reduction depth per staged tile
-constexpr int GLD = 68;     // LDS row stride (floats): the two half-waves of an operand read hit disjoint banks
-constexpr int MAX_MIX = 32; // experts one task mixes (PLE: specific + shared)
-
-// ------------------------------------------------------------------ gather
-struct GatherArgs {
-    const float *user_tab, *item_tab, *dm;
-    const int32_t *uid, *pid, *dom, *perm;
-    const float* label;
-    int64_t row_base, n_rows_split;
-    int rows, rows_pad, n_user, n_item, n_domain;
-    float* x;
-    int ld;
-    int32_t* domrow;
-    float* y;
-    int32_t *urow, *irow, *map_u, *map_i;      // trainable tables: row of each position, first position of each row
-    const float *lin_u, *lin_i, *lin_d;         // NFM: 1-d linear tables (lin_u / lin_i null while frozen at their zero init)
-    float* extra;                               // NFM: sum of the linear terms per position
-    float* xt;                                  // AutoInt: compact [rows_pad][384] copy of x (token-major: row 3 b + t)
-};
-// E = 128: one wave per batch position -- lanes 0..31 copy the user row, 32..63 the item row, then lanes 0..31 the domain row.
-// Any accepted width E (32 / 64 / 128 / 256): a row's [user | item] pair is 2 E floats = E / 2 lanes of 16 bytes, so a wave
-// serves 128 / E rows (4 at E = 32, where a table row is exactly one 128-byte line and 8 neighbouring lanes read it whole;
-// 2 at E = 64) and at E = 256 every lane takes two vectors per field.  The first E / 4 lanes of a row's group then copy
-// the domain row.  `sub` = the lane's float4 within the 2 E floats of [user | item].
-template <int E>
-__global__ __launch_bounds__(256) void k_graph_gather(const GatherArgs a) {
-    constexpr int LPF = E / 4;                              // lanes (float4s) per field
-    constexpr int GROUP = 2 * LPF < 64 ? 2 * LPF : 64;      // lanes that share a row
-    constexpr int RPW = 64 / GROUP;                         // rows per wave
-    constexpr int NJ = 2 * LPF / GROUP;                     // vectors per lane and pass
-    const int lane = threadIdx.x & 63;
-    const int r = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / GROUP, sub0 = lane % GROUP;
-    if (r >= a.rows_pad) return;
-    float* xr = a.x + (size_t)r * a.ld;
-    if (r >= a.rows) {          // padding rows: zeros in, nothing out (their d loss / d logit is zero)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int sub = sub0 + 64 * j;
-            *reinterpret_cast<f32x4*>(xr + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (sub < LPF) *reinterpret_cast<f32x4*>(xr + 2 * E + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (E == EMB && a.xt) {
-                *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
-                if (sub < LPF) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 2 * EMB + 4 * sub) = (f32x4){0.f, 0.f, 0.f, 0.f};
-            }
-        }
-        if (sub0 == 0) {
-            a.domrow[r] = -1;
-            a.y[r] = 0.f;
-            if (a.urow) { a.urow[r] = -1; a.irow[r] = -1; }
-            if (a.extra) a.extra[r] = 0.f;
-        }
-        return;
-    }
-    int64_t src = a.perm ? (int64_t)a.perm[a.row_base + r] : a.row_base + r;
-    src = src < 0 ? 0 : (src >= a.n_rows_split ? a.n_rows_split - 1 : src);
-    int u = a.uid[src], it = a.pid[src], d = a.dom[src];
-    u = u < 0 ? 0 : (u >= a.n_user ? a.n_user - 1 : u);
-    it = it < 0 ? 0 : (it >= a.n_item ? a.n_item - 1 : it);
-    d = d < 0 ? 0 : (d >= a.n_domain ? a.n_domain - 1 : d);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int sub = sub0 + 64 * j;
-        const float* row = sub < LPF ? a.user_tab + (size_t)u * E + 4 * sub : a.item_tab + (size_t)it * E + 4 * (sub - LPF);
-        const f32x4 v0 = *reinterpret_cast<const f32x4*>(row);
-        *reinterpret_cast<f32x4*>(xr + 4 * sub) = v0;
-        if (E == EMB && a.xt) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 4 * sub) = v0;
-        if (sub < LPF) {
-            const f32x4 v1 = *reinterpret_cast<const f32x4*>(a.dm + (size_t)d * E + 4 * sub);
-            *reinterpret_cast<f32x4*>(xr + 2 * E + 4 * sub) = v1;
-            if (E == EMB && a.xt) *reinterpret_cast<f32x4*>(a.xt + (size_t)r * XDIM + 2 * EMB + 4 * sub) = v1;
-        }
-    }
-    if (sub0 == 0) {
-        a.domrow[r] = d;
-        a.y[r] = a.label[src];
-        if (a.extra) a.extra[r] = ((a.lin_u ? a.lin_u[u] : 0.f) + (a.lin_i ? a.lin_i[it] : 0.f)) + a.lin_d[d];
-        if (a.urow) {       // representative of a table row = its smallest batch position (integer atomicMin: exact)
-            a.urow[r] = u;
-            a.irow[r] = it;
-            atomicMin(a.map_u + u, r);
-            atomicMin(a.map_i + it, r);
-        }
-    }
-}
 // rows_pad is a multiple of 64, a workgroup serves 4 waves x 128 / E rows (at most 16)
 static void launch_graph_gather(const GatherArgs& a, int emb, hipStream_t s) {
     switch (emb) {
@@ -183,1598 +114,17 @@ static void launch_graph_gather(const GatherArgs& a, int emb, hipStream_t s) {
         default: GLAUNCH(k_graph_gather<EMB>, dim3(a.rows_pad / 4), dim3(256), 0, s, a); break;
     }
 }
-
-// ------------------------------------------------------------------ dense contractions
-// MODE 0:  C[M x N] = A[M x K] . B[K x N]        + bias, relu, dropout           (layer forward)
-// MODE 1:  C[M x N] = A[M x K] . B[N x K]^T      x the gate of gate_y, += C        (d input = dz . W^T)
-// MODE 2:  C[M x N] = A[K x M]^T . B[K x N]                                        (dW = in^T . dz, K = batch rows)
-// M, N multiples of 64, K a multiple of 16 (MODE 2: M may end inside its last tile, see m_rows).  64x64 tile per workgroup, 4 waves own its 32x32 quadrants
-// (`32x32x2`, A / B fragments read from LDS as one float per lane: [k][m] images, conflict-free).
-struct GemmArgs {
-    const float* A; int lda;
-    const float* B; int ldb;
-    float* C; int ldc;
-    int K;
-    const float* bias; int relu;
-    uint32_t drop_key, drop_thresh; float keep_scale; int n_cols; int use_dropout;
-    const float* gate_y; int gate_ld; float gate_scale; int accumulate;
-    // forward only: + sum_{j < n_xe} xe[row][j] * we[j][col] before the bias (PNN: the inner products feed the last three
-    // rows of the first kernel, whose 384 + 3 rows are no multiple of the tile depth)
-    const float* xe; int xe_ld; const float* we; int n_xe;
-    // MODE 2 only: blockIdx.z owns K rows [z K, (z + 1) K) of A and B and writes its partial product at C + z zstride
-    size_t zstride;
-    // MODE 2 only: rows of C that exist (0: every tile is whole).  A first layer on 3 E input columns has M = 96 at E = 32:
-    // the last tile reads 64 columns of A (its neighbours in the workspace, whatever they hold -- row m of C depends on
-    // column m of A alone) and stores the rows below m_rows only
-    int m_rows;
-};
-constexpr int MAX_GROUP = 32;
-struct GroupTab {
-    int n, tiles_y;
-    int64_t a_off[MAX_GROUP], b_off[MAX_GROUP], c_off[MAX_GROUP];      // floats added to A / B / C
-    int64_t bias_off[MAX_GROUP];                                       // ... to bias (MODE 0) or to the bias gradient (finish)
-    int64_t gate_off[MAX_GROUP];                                       // ... to gate_y (MODE 1)
-    uint32_t drop_key[MAX_GROUP];
-};
-// KCAT (MODE 1 only): C = sum over the group's members of A_e . B_e^T -- ONE contraction whose reduction index runs through
-// every member (the first layers' d x, which adds up over the experts: d x = [dz_1 .. dz_E] . [W_1 .. W_E]^T)
-template <int MODE, bool KCAT = false>
-__device__ __forceinline__ void gemm_tile(const GemmArgs& a, const int bx, const int by, const int bz, const GroupTab* tab = nullptr) {
-    __shared__ __attribute__((aligned(16))) float As[2][GK * GLD];
-    __shared__ __attribute__((aligned(16))) float Bs[2][GK * GLD];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int m0 = by * GT, n0 = bx * GT;
-    const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-    constexpr bool A_KC = MODE != 2;        // A's reduction index is the contiguous one in memory
-    constexpr bool B_KC = MODE == 1;
-    const int r4 = tid >> 2, k4 = (tid & 3) * 4;        // k-contiguous operand: row r4 of the tile, 4 k's
-    const int kr = tid >> 4, c4 = (tid & 15) * 4;       // otherwise: k row kr, 4 columns
-    f32x4 ra, rb;
-    const float *A = a.A, *B = a.B;
-    float* C = a.C;
-    if (MODE == 2) {
-        A += (size_t)bz * a.K * a.lda;
-        B += (size_t)bz * a.K * a.ldb;
-        C += (size_t)bz * a.zstride;
-    }
-    const int nk = a.K / GK;
-    auto gload = [&](int kt) {
-        int k0 = kt * GK;
-        if (KCAT) {
-            const int e = kt / nk;
-            k0 = (kt - e * nk) * GK;
-            A = a.A + tab->a_off[e];
-            B = a.B + tab->b_off[e];
-        }
-        ra = A_KC ? *reinterpret_cast<const f32x4*>(A + (size_t)(m0 + r4) * a.lda + k0 + k4)
-                  : *reinterpret_cast<const f32x4*>(A + (size_t)(k0 + kr) * a.lda + m0 + c4);
-        rb = B_KC ? *reinterpret_cast<const f32x4*>(B + (size_t)(n0 + r4) * a.ldb + k0 + k4)
-                  : *reinterpret_cast<const f32x4*>(B + (size_t)(k0 + kr) * a.ldb + n0 + c4);
-    };
-    auto lstore = [&](int buf) {
-        if (A_KC) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) As[buf][(k4 + j) * GLD + r4] = ra[j];
-        } else {
-            *reinterpret_cast<f32x4*>(&As[buf][kr * GLD + c4]) = ra;
-        }
-        if (B_KC) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) Bs[buf][(k4 + j) * GLD + r4] = rb[j];
-        } else {
-            *reinterpret_cast<f32x4*>(&Bs[buf][kr * GLD + c4]) = rb;
-        }
-    };
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const int nkt = KCAT ? nk * tab->n : nk;
-    gload(0);
-    lstore(0);
-    __syncthreads();
-    const int kk = lane >> 5, c = lane & 31;
-    for (int kt = 0; kt < nkt; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < nkt) gload(kt + 1);
-        const float* ap = &As[buf][kk * GLD + wm + c];
-        const float* bp = &Bs[buf][kk * GLD + wn + c];
-#pragma unroll
-        for (int i = 0; i < GK / 2; ++i) acc = MAMDR_MFMA32(ap[2 * i * GLD], bp[2 * i * GLD], acc);
-        if (kt + 1 < nkt) lstore(buf ^ 1);
-        __syncthreads();
-    }
-    // D layout of 32x32x2: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const int col = n0 + wn + c;
-    const float bias = (MODE == 0 && a.bias) ? a.bias[col] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm + (r & 3) + 8 * (r >> 2) + 4 * kk;
-        if (MODE == 2 && a.m_rows && row >= a.m_rows) continue;
-        float v = acc[r];
-        if (MODE == 0) {
-            for (int j = 0; j < a.n_xe; ++j) v = fmaf(a.xe[(size_t)row * a.xe_ld + j], a.we[(size_t)j * a.n_cols + col], v);
-            v += bias;
-            if (a.relu) v = fmaxf(v, 0.f);
-            if (a.use_dropout) {
-                const uint32_t u = mamdr_dropout_u32(a.drop_key, (uint32_t)row * (uint32_t)a.n_cols + (uint32_t)col);
-                v = u >= a.drop_thresh ? v * a.keep_scale : 0.f;
-            }
-        } else if (MODE == 1) {
-            if (a.gate_y) v = a.gate_y[(size_t)row * a.gate_ld + col] > 0.f ? v * a.gate_scale : 0.f;
-            if (a.accumulate) v += C[(size_t)row * a.ldc + col];
-        }
-        C[(size_t)row * a.ldc + col] = v;
-    }
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_graph_gemm(const GemmArgs a) {
-    gemm_tile<MODE>(a, blockIdx.x, blockIdx.y, blockIdx.z);
-}
-
-// ---- the same contraction for a GROUP of problems of one shape in ONE launch: the experts a task mixes share their input
-// and their layer shapes (deep_mtl_ctr.py:31-49: num_experts / specific + shared experts, every one DNN(hidden_dim)), so a
-// layer of all of them is one grid -- 12 experts x 64 tiles instead of 12 launches of 64 workgroups on 256 CUs.
-// MODE 0 / 1: blockIdx.z = the problem; MODE 2: blockIdx.y = problem x row tile (blockIdx.z stays the split of the rows).
-__global__ __launch_bounds__(256) void k_graph_gemm_kcat(const GemmArgs a, const GroupTab t) {
-    gemm_tile<1, true>(a, blockIdx.x, blockIdx.y, 0, &t);
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_graph_gemm_group(GemmArgs a, const GroupTab t) {
-    int gi, by = blockIdx.y, bz = blockIdx.z;
-    if (MODE == 2) {
-        gi = (int)blockIdx.y / t.tiles_y;
-        by = (int)blockIdx.y - gi * t.tiles_y;
-    } else {
-        gi = blockIdx.z;
-        bz = 0;
-    }
-    a.A += t.a_off[gi];
-    a.B += t.b_off[gi];
-    a.C += t.c_off[gi];
-    if (MODE == 0) {
-        a.bias += t.bias_off[gi];
-        a.drop_key = t.drop_key[gi];
-    }
-    if (MODE == 1 && a.gate_y) a.gate_y += t.gate_off[gi];
-    gemm_tile<MODE>(a, blockIdx.x, by, bz);
-}
-
-// ---- the same contractions (MODE 0 / 1) on 32 x 32 tiles with the reduction index split over the workgroup's four waves.
-// A 1,024-row layer of 512 / 256 / 128 / 64 units is 128 / 64 / 32 / 16 tiles of 64 x 64: half to a sixteenth of the 256
-// CUs, each walking a serial chain of K / 2 `32x32x2` MFMAs per wave behind one staged 16-deep tile per round trip
-// (12.6 us per launch on the Taobao-10 multi-task configs, profiles/r04g_*).  Here a workgroup owns a 32 x 32 tile
-// (4 x the workgroups), stages T32_K = 128 reduction indices per round trip (4 + 4 float4 loads in flight per thread, the
-// next stage requested before this one's MFMAs) and every wave contracts its own 32 of them into a full-tile accumulator:
-// the MFMA chain per wave is K / 8 long.  The four partial tiles meet in LDS in wave order (fixed: bit-stable), and the
-// epilogue runs on 4 neighbouring outputs per thread.  K needs no multiple of 128: the tail is staged as zeros.
-constexpr int T32 = 32, T32_K = 128, T32_LD = 36;
-template <int MODE, bool KCAT = false>
-__device__ __forceinline__ void gemm_tile32(const GemmArgs& a, const int bx, const int by, const GroupTab* tab = nullptr) {
-    __shared__ __attribute__((aligned(16))) float As[T32_K * T32_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[T32_K * T32_LD];
-    static_assert(MODE == 0 || MODE == 1, "weight gradients keep the 64 x 64 tiles");
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int m0 = by * T32, n0 = bx * T32;
-    constexpr bool B_KC = MODE == 1;
-    const int r8 = tid >> 3, q8 = tid & 7;          // k-contiguous operand: tile row r8, float4s q8 + 8 j of its 128 k's
-    f32x4 ra[4], rb[4];
-    const float *A = a.A, *B = a.B;
-    const int nk = (a.K + T32_K - 1) / T32_K;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    auto gload = [&](int kt) {
-        int k0 = kt * T32_K;
-        if (KCAT) {
-            const int e = kt / nk;
-            k0 = (kt - e * nk) * T32_K;
-            A = a.A + tab->a_off[e];
-            B = a.B + tab->b_off[e];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = k0 + 4 * (q8 + 8 * j);
-            ra[j] = k < a.K ? *reinterpret_cast<const f32x4*>(A + (size_t)(m0 + r8) * a.lda + k) : zero;
-            if (B_KC) {
-                rb[j] = k < a.K ? *reinterpret_cast<const f32x4*>(B + (size_t)(n0 + r8) * a.ldb + k) : zero;
-            } else {            // B [K x N]: k row r8 + 32 j, float4 q8 of the tile's 32 columns
-                const int kr = k0 + r8 + 32 * j;
-                rb[j] = kr < a.K ? *reinterpret_cast<const f32x4*>(B + (size_t)kr * a.ldb + n0 + 4 * q8) : zero;
-            }
-        }
-    };
-    auto lstore = [&]() {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = 4 * (q8 + 8 * j);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) As[(k + i) * T32_LD + r8] = ra[j][i];
-            if (B_KC) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) Bs[(k + i) * T32_LD + r8] = rb[j][i];
-            } else {
-                *reinterpret_cast<f32x4*>(&Bs[(r8 + 32 * j) * T32_LD + 4 * q8]) = rb[j];
-            }
-        }
-    };
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const int nkt = KCAT ? nk * tab->n : nk;
-    const int kk = lane >> 5, c = lane & 31;
-    gload(0);
-    for (int kt = 0; kt < nkt; ++kt) {
-        lstore();
-        __syncthreads();
-        if (kt + 1 < nkt) gload(kt + 1);
-        const float* ap = &As[(32 * w + kk) * T32_LD + c];
-        const float* bp = &Bs[(32 * w + kk) * T32_LD + c];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc = MAMDR_MFMA32(ap[2 * i * T32_LD], bp[2 * i * T32_LD], acc);
-        __syncthreads();
-    }
-    // the waves' partial tiles -> LDS (D layout of 32x32x2: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5))
-    float* red = As;            // (the A stage is free after the loop's last barrier)
-    static_assert(4 * 32 * 33 <= T32_K * T32_LD, "the partial tiles fit the A stage");
-#pragma unroll
-    for (int r = 0; r < 16; ++r) red[(w * 32 + (r & 3) + 8 * (r >> 2) + 4 * kk) * 33 + c] = acc[r];
-    __syncthreads();
-    const int row = m0 + r8, col = n0 + 4 * q8;
-    f32x4 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float t = red[(0 * 32 + r8) * 33 + 4 * q8 + j];
-#pragma unroll
-        for (int ww = 1; ww < 4; ++ww) t += red[(ww * 32 + r8) * 33 + 4 * q8 + j];
-        v[j] = t;
-    }
-    float* cp = a.C + (size_t)row * a.ldc + col;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        float x = v[j];
-        if (MODE == 0) {
-            for (int e = 0; e < a.n_xe; ++e) x = fmaf(a.xe[(size_t)row * a.xe_ld + e], a.we[(size_t)e * a.n_cols + col + j], x);
-            if (a.bias) x += a.bias[col + j];
-            if (a.relu) x = fmaxf(x, 0.f);
-            if (a.use_dropout) {
-                const uint32_t u = mamdr_dropout_u32(a.drop_key, (uint32_t)row * (uint32_t)a.n_cols + (uint32_t)(col + j));
-                x = u >= a.drop_thresh ? x * a.keep_scale : 0.f;
-            }
-        } else {
-            if (a.gate_y) x = a.gate_y[(size_t)row * a.gate_ld + col + j] > 0.f ? x * a.gate_scale : 0.f;
-            if (a.accumulate) x += cp[j];
-        }
-        v[j] = x;
-    }
-    if ((reinterpret_cast<uintptr_t>(cp) & 15) == 0) {
-        *reinterpret_cast<f32x4*>(cp) = v;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) cp[j] = v[j];
-    }
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_graph_gemm32(const GemmArgs a) {
-    gemm_tile32<MODE>(a, blockIdx.x, blockIdx.y);
-}
-__global__ __launch_bounds__(256) void k_graph_gemm32_kcat(const GemmArgs a, const GroupTab t) {
-    gemm_tile32<1, true>(a, blockIdx.x, blockIdx.y, &t);
-}
-template <int MODE>
-__global__ __launch_bounds__(256) void k_graph_gemm32_group(GemmArgs a, const GroupTab t) {
-    const int gi = blockIdx.z;
-    a.A += t.a_off[gi];
-    a.B += t.b_off[gi];
-    a.C += t.c_off[gi];
-    if (MODE == 0) {
-        a.bias += t.bias_off[gi];
-        a.drop_key = t.drop_key[gi];
-    }
-    if (MODE == 1 && a.gate_y) a.gate_y += t.gate_off[gi];
-    gemm_tile32<MODE>(a, blockIdx.x, blockIdx.y);
-}
-
-// db[n] = sum over the batch rows of dz[b][n]: 16 columns per workgroup, 16 row groups (8 loads in flight each) summed
-// through LDS in a fixed order
-constexpr int CS_COLS = 16, CS_GROUPS = 16;
-__global__ __launch_bounds__(256) void k_graph_colsum(const float* dz, int ld, int rows, float* out, int n_valid) {
-    __shared__ float red[CS_GROUPS][CS_COLS + 1];
-    const int c = threadIdx.x & (CS_COLS - 1), g = threadIdx.x / CS_COLS;
-    const int col = blockIdx.x * CS_COLS + c;
-    float s = 0.f;
-    if (col < n_valid) {
-        const float* p = dz + col;
-        int b = g;
-        for (; b + 7 * CS_GROUPS < rows; b += 8 * CS_GROUPS) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(b + k * CS_GROUPS) * ld];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; b < rows; b += CS_GROUPS) s += p[(size_t)b * ld];
-    }
-    red[g][c] = s;
-    __syncthreads();
-    if (g == 0 && col < n_valid) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CS_GROUPS; ++k) t += red[k][c];
-        out[col] = t;
-    }
-}
-// the end of a layer's weight gradient: workgroups [0, nb_red) add the split-K partial products of dW in a fixed order,
-// the rest are the bias column sums above
-__global__ __launch_bounds__(256) void k_graph_wfinish(const float* part, int n_split, size_t stride, int64_t n4, float* out,
-                                                       int nb_red, const float* dz, int ld, int rows, float* db, int n_valid) {
-    if ((int)blockIdx.x < nb_red) {
-        const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        if (i >= n4) return;
-        f32x4 t = reinterpret_cast<const f32x4*>(part)[i];
-        for (int z = 1; z < n_split; ++z) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(part + z * stride)[i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] += v[k];
-        }
-        reinterpret_cast<f32x4*>(out)[i] = t;
-        return;
-    }
-    __shared__ float red[CS_GROUPS][CS_COLS + 1];
-    const int c = threadIdx.x & (CS_COLS - 1), g = threadIdx.x / CS_COLS;
-    const int col = ((int)blockIdx.x - nb_red) * CS_COLS + c;
-    float s = 0.f;
-    if (col < n_valid) {
-        const float* p = dz + col;
-        int b = g;
-        for (; b + 7 * CS_GROUPS < rows; b += 8 * CS_GROUPS) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(b + k * CS_GROUPS) * ld];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; b < rows; b += CS_GROUPS) s += p[(size_t)b * ld];
-    }
-    red[g][c] = s;
-    __syncthreads();
-    if (g == 0 && col < n_valid) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CS_GROUPS; ++k) t += red[k][c];
-        db[col] = t;
-    }
-}
-// the same for a group of weight gradients (blockIdx.y = the problem): partial products at part + (y n_split + z) stride,
-// outputs at out + c_off[y], bias column sums of dz + a_off[y] into db + bias_off[y]
-__global__ __launch_bounds__(256) void k_graph_wfinish_group(const float* part, int n_split, size_t stride, int64_t n4, float* out,
-                                                             int nb_red, const float* dz, int ld, int rows, float* db, int n_valid,
-                                                             const GroupTab t) {
-    const int gi = blockIdx.y;
-    if ((int)blockIdx.x < nb_red) {
-        const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        if (i >= n4) return;
-        const float* p0 = part + (size_t)gi * n_split * stride;
-        f32x4 v0 = reinterpret_cast<const f32x4*>(p0)[i];
-        for (int z = 1; z < n_split; ++z) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(p0 + z * stride)[i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v0[k] += v[k];
-        }
-        reinterpret_cast<f32x4*>(out + t.c_off[gi])[i] = v0;
-        return;
-    }
-    __shared__ float red[CS_GROUPS][CS_COLS + 1];
-    const int c = threadIdx.x & (CS_COLS - 1), g = threadIdx.x / CS_COLS;
-    const int col = ((int)blockIdx.x - nb_red) * CS_COLS + c;
-    float s = 0.f;
-    if (col < n_valid) {
-        const float* p = dz + t.a_off[gi] + col;
-        int b = g;
-        for (; b + 7 * CS_GROUPS < rows; b += 8 * CS_GROUPS) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(b + k * CS_GROUPS) * ld];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; b < rows; b += CS_GROUPS) s += p[(size_t)b * ld];
-    }
-    red[g][c] = s;
-    __syncthreads();
-    if (g == 0 && col < n_valid) {
-        float v = 0.f;
-#pragma unroll
-        for (int k = 0; k < CS_GROUPS; ++k) v += red[k][c];
-        db[t.bias_off[gi] + col] = v;
-    }
-}
-// ---- every weight gradient of a step in ONE launch.  dW_l = in_l^T dz_l needs nothing but the activations and the d z's,
-// which stay in the workspaces until the step ends: the backward pass runs its chain of d-input contractions first and
-// queues the weight gradients (host: queue_wgrad / flush_wgrads); here a flat grid walks the queue -- workgroup ->
-// (problem, tile, split of the batch rows) through the prefix table -- so that 90 tiles of four layers (shared_bottom) or of
-// an expert group + gate + tower share the 256 CUs instead of following one another in 2 launches per layer.
-constexpr int MAX_WQ = 40;
-struct WMulti {
-    int n;
-    int first[MAX_WQ + 1];          // first workgroup of problem p
-    const float* A[MAX_WQ]; const float* B[MAX_WQ]; float* C[MAX_WQ];       // C: the partial products' base, or dW itself (split 1)
-    int lda[MAX_WQ], ldb[MAX_WQ], N[MAX_WQ], tx[MAX_WQ], ty[MAX_WQ], K[MAX_WQ];     // K = batch rows per split
-    int mn[MAX_WQ];                 // M x N (stride between the splits' partial products)
-    int M[MAX_WQ];                  // rows of dW (ty = the tiles that cover them, the last one possibly in part)
-};
-__global__ __launch_bounds__(256) void k_graph_wgrad_multi(const WMulti t) {
-    int p = 0;
-    while (p + 1 < t.n && (int)blockIdx.x >= t.first[p + 1]) ++p;
-    int b = (int)blockIdx.x - t.first[p];
-    const int tiles = t.tx[p] * t.ty[p];
-    const int bz = b / tiles;
-    b -= bz * tiles;
-    const int by = b / t.tx[p], bx = b - by * t.tx[p];
-    GemmArgs a;
-    a.A = t.A[p];
-    a.lda = t.lda[p];
-    a.B = t.B[p];
-    a.ldb = t.ldb[p];
-    a.C = t.C[p];
-    a.ldc = t.N[p];
-    a.K = t.K[p];
-    a.zstride = (size_t)t.mn[p];
-    a.m_rows = t.M[p];
-    gemm_tile<2>(a, bx, by, bz);
-}
-// ... and their ends: per problem, the workgroups that add the splits' partial products in a fixed order, then the ones
-// that sum the columns of d z into the bias gradient (k_graph_wfinish's two halves, the queue's problems side by side)
-// where a finished gradient element goes: into the gradient vector (p null), or straight through the optimiser -- the
-// step's k_graph_adam launch folded into the launch that finishes the gradients (the same arithmetic per element: opt_elem)
-struct GradSink {
-    const float* g_base;        // base of the gradient vector (element 0 = flat-vector element `table_floats`)
-    float *p, *m, *v;           // parameters / slots addressed like g_base (m: the accumulator for MAMDR_OPT_ACCUMULATE)
-    int optimizer;
-    float alpha, omb1, omb2, eps;
-};
-// (opt_step's arithmetic, mamdr_device.h, with the SGD test first.  It stays a copy: with opt_step's order of the tests
-// k_graph_tail, k_graph_adam and k_graph_fm_bwd<256> compile to different code -- profiles/step_kernels_refactor.txt)
-__device__ __forceinline__ void opt_elem(const int optimizer, const float g, float& p, float& m, float& v, const float alpha,
-                                         const float omb1, const float omb2, const float eps) {
-    if (optimizer == MAMDR_OPT_SGD) {
-        p = p - g * alpha;
-    } else if (optimizer == MAMDR_OPT_ACCUMULATE) {
-        m = m + g;
-    } else {        // TF1 ApplyAdam: m += (g - m)(1 - b1); v += (g^2 - v)(1 - b2); p -= m alpha / (sqrt(v) + eps)
-        m = m + (g - m) * omb1;
-        v = v + (g * g - v) * omb2;
-        p = p - (m * alpha) / (sqrtf(v) + eps);
-    }
-}
-__device__ __forceinline__ void sink1(const GradSink& s, float* gptr, const float g) {
-    if (!s.p) {
-        *gptr = g;
-        return;
-    }
-    const size_t i = (size_t)(gptr - s.g_base);
-    float p = s.p[i], m = s.m[i], v = s.optimizer == MAMDR_OPT_ADAM ? s.v[i] : 0.f;
-    opt_elem(s.optimizer, g, p, m, v, s.alpha, s.omb1, s.omb2, s.eps);
-    if (s.optimizer != MAMDR_OPT_ACCUMULATE) s.p[i] = p;
-    if (s.optimizer != MAMDR_OPT_SGD) s.m[i] = m;
-    if (s.optimizer == MAMDR_OPT_ADAM) s.v[i] = v;
-}
-__device__ __forceinline__ void sink4(const GradSink& s, float* gptr, const f32x4 g) {
-    if (!s.p) {
-        *reinterpret_cast<f32x4*>(gptr) = g;
-        return;
-    }
-    const size_t i = (size_t)(gptr - s.g_base);
-    f32x4 p = *reinterpret_cast<const f32x4*>(s.p + i), m = *reinterpret_cast<const f32x4*>(s.m + i);
-    f32x4 v = s.optimizer == MAMDR_OPT_ADAM ? *reinterpret_cast<const f32x4*>(s.v + i) : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float pk = p[k], mk = m[k], vk = v[k];
-        opt_elem(s.optimizer, g[k], pk, mk, vk, s.alpha, s.omb1, s.omb2, s.eps);
-        p[k] = pk; m[k] = mk; v[k] = vk;
-    }
-    if (s.optimizer != MAMDR_OPT_ACCUMULATE) *reinterpret_cast<f32x4*>(s.p + i) = p;
-    if (s.optimizer != MAMDR_OPT_SGD) *reinterpret_cast<f32x4*>(s.m + i) = m;
-    if (s.optimizer == MAMDR_OPT_ADAM) *reinterpret_cast<f32x4*>(s.v + i) = v;
-}
-struct WFinish {
-    int n;
-    int first[MAX_WQ + 1];
-    const float* part[MAX_WQ]; float* out[MAX_WQ]; const float* dz[MAX_WQ]; float* db[MAX_WQ];
-    int split[MAX_WQ], nb_red[MAX_WQ], N[MAX_WQ], rows[MAX_WQ], ld[MAX_WQ], mn[MAX_WQ];
-};
-__device__ __forceinline__ void wfinish_multi_body(const WFinish& t, const int bid, const GradSink& sk) {
-    int p = 0;
-    while (p + 1 < t.n && bid >= t.first[p + 1]) ++p;
-    const int bi = bid - t.first[p];
-    if (bi < t.nb_red[p]) {
-        const int64_t i = (int64_t)bi * 256 + threadIdx.x;
-        if (i >= t.mn[p] / 4) return;
-        const float* part = t.part[p];
-        const size_t stride = (size_t)t.mn[p];
-        f32x4 v0 = reinterpret_cast<const f32x4*>(part)[i];
-        for (int z = 1; z < t.split[p]; ++z) {
-            const f32x4 v = reinterpret_cast<const f32x4*>(part + z * stride)[i];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v0[k] += v[k];
-        }
-        sink4(sk, t.out[p] + 4 * i, v0);
-        return;
-    }
-    __shared__ float red[CS_GROUPS][CS_COLS + 1];
-    const int c = threadIdx.x & (CS_COLS - 1), g = threadIdx.x / CS_COLS;
-    const int col = (bi - t.nb_red[p]) * CS_COLS + c;
-    const int rows = t.rows[p], ld = t.ld[p];
-    float s = 0.f;
-    if (col < t.N[p]) {
-        const float* q = t.dz[p] + col;
-        int b = g;
-        for (; b + 7 * CS_GROUPS < rows; b += 8 * CS_GROUPS) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = q[(size_t)(b + k * CS_GROUPS) * ld];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; b < rows; b += CS_GROUPS) s += q[(size_t)b * ld];
-    }
-    red[g][c] = s;
-    __syncthreads();
-    if (g == 0 && col < t.N[p]) {
-        float v = 0.f;
-#pragma unroll
-        for (int k = 0; k < CS_GROUPS; ++k) v += red[k][c];
-        sink1(sk, t.db[p] + col, v);
-    }
-}
-// d x of a group's first layers: out[b][c] (+)= sum over the members of part[e][b][c], in member order
-__global__ __launch_bounds__(256) void k_graph_dx_reduce(const float* part, int n_part, size_t stride, int rows, int n4_row,
-                                                         float* out, int ld, int accumulate) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)rows * n4_row) return;
-    const int b = (int)(i / n4_row), c4 = (int)(i - (int64_t)b * n4_row);
-    f32x4 v = reinterpret_cast<const f32x4*>(part)[i];
-    for (int e = 1; e < n_part; ++e) {
-        const f32x4 w = reinterpret_cast<const f32x4*>(part + e * stride)[i];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] += w[k];
-    }
-    float* o = out + (size_t)b * ld + 4 * c4;
-    if (accumulate) {
-        const f32x4 w = *reinterpret_cast<const f32x4*>(o);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = w[k] + v[k];
-    }
-    *reinterpret_cast<f32x4*>(o) = v;
-}
 static void launch_colsum(hipStream_t s, const float* dz, int ld, int rows, float* out, int n_valid) {
     GLAUNCH(k_graph_colsum, dim3((n_valid + CS_COLS - 1) / CS_COLS), dim3(256), 0, s, dz, ld, rows, out, n_valid);
-}
-
-// out[j][e] = sum_b in[b][j] * d[b][e]  for narrow right-hand sides (gate kernel Wg: e < n_e <= 32; head: n_e = 1; the
-// attention projections: n_e = 128): 16 outputs per workgroup, the rows split over 16 groups summed through LDS in order
-__device__ __forceinline__ void small_tn_body(const float* in, int in_ld, const float* d, int d_ld, int rows, int n_j, int n_e,
-                                              float* out, float* sum_out, const int bid, const int nblk, const GradSink& sk) {
-    __shared__ float red[CS_GROUPS][CS_COLS + 1];
-    if (sum_out && bid == nblk - 1) {       // one more workgroup: sum_out[0] = sum over the rows of d[b][0], fixed order
-        float* r1 = &red[0][0];                         // (the head's d global bias beside its d kernel: one launch less)
-        float s1 = 0.f;
-        for (int b = threadIdx.x; b < rows; b += 256) s1 += d[(size_t)b * d_ld];
-        r1[threadIdx.x] = s1;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) r1[threadIdx.x] += r1[threadIdx.x + o];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) sink1(sk, sum_out, r1[0]);
-        return;
-    }
-    const int c = threadIdx.x & (CS_COLS - 1), g = threadIdx.x / CS_COLS;
-    const int idx = bid * CS_COLS + c;
-    float s = 0.f;
-    if (idx < n_j * n_e) {
-        const int j = idx / n_e, e = idx - j * n_e;
-        const float *pi = in + j, *pd = d + e;
-        int b = g;
-        for (; b + 3 * CS_GROUPS < rows; b += 4 * CS_GROUPS) {
-            float x[4], y[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                x[k] = pi[(size_t)(b + k * CS_GROUPS) * in_ld];
-                y[k] = pd[(size_t)(b + k * CS_GROUPS) * d_ld];
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s = fmaf(x[k], y[k], s);
-        }
-        for (; b < rows; b += CS_GROUPS) s = fmaf(pi[(size_t)b * in_ld], pd[(size_t)b * d_ld], s);
-    }
-    red[g][c] = s;
-    __syncthreads();
-    if (g == 0 && idx < n_j * n_e) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CS_GROUPS; ++k) t += red[k][c];
-        sink1(sk, out + idx, t);
-    }
-}
-__global__ __launch_bounds__(256) void k_graph_small_tn(const float* in, int in_ld, const float* d, int d_ld, int rows,
-                                                        int n_j, int n_e, float* out, float* sum_out) {
-    GradSink none;
-    none.p = nullptr;
-    small_tn_body(in, in_ld, d, d_ld, rows, n_j, n_e, out, sum_out, blockIdx.x, gridDim.x, none);
 }
 static void launch_small_tn(hipStream_t s, const float* in, int in_ld, const float* d, int d_ld, int rows, int n_j, int n_e,
                             float* out, float* sum_out = nullptr) {
     GLAUNCH(k_graph_small_tn, dim3((n_j * n_e + CS_COLS - 1) / CS_COLS + (sum_out ? 1 : 0)), dim3(256), 0, s, in, in_ld,
                        d, d_ld, rows, n_j, n_e, out, sum_out);
 }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-// ------------------------------------------------------------------ NFM / PNN: interactions of the three fields, one wave per row
-// kind 0 (NFM): f[c] = u i + u d + i d (= 1/2 ((u+i+d)^2 - u^2 - i^2 - d^2), BiInteractionPooling), 128 columns
-// kind 1 (PNN): f[0..2] = <u,i>, <u,d>, <i,d> (InnerProductLayer over the pairs (0,1), (0,2), (1,2))
-// kind 2 (DeepFM): the FM second-order term  sum_k (u i + u d + i d)_k  joins the linear logit of the row (`extra`); no columns
-struct FeatArgs {
-    float* act; float* dact; int ld; int f_col; int rows_pad; int kind; int dx_all;
-    const float* w_ip;      // PNN: rows 384..386 of the first kernel [3][n_out]
-    int z_col, n_out;       // PNN: d z of the first layer
-    float* extra;           // DeepFM: the per-row logit terms outside the DNN (linear part; the FM term is added here)
-    const float* dlogit;    // DeepFM: d loss / d logit of the row
-};
-__global__ __launch_bounds__(256) void k_graph_feat_fwd(const FeatArgs a) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= a.rows_pad) return;
-    float* row = a.act + (size_t)r * a.ld;
-    const f32x2 u = *reinterpret_cast<const f32x2*>(row + 2 * lane), it = *reinterpret_cast<const f32x2*>(row + EMB + 2 * lane),
-                d = *reinterpret_cast<const f32x2*>(row + 2 * EMB + 2 * lane);
-    if (a.kind == 0) {
-        f32x2 f;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) f[k] = fmaf(it[k], d[k], fmaf(u[k], d[k], u[k] * it[k]));
-        *reinterpret_cast<f32x2*>(row + a.f_col + 2 * lane) = f;
-    } else if (a.kind == 2) {
-        float f = 0.f;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) f += fmaf(it[k], d[k], fmaf(u[k], d[k], u[k] * it[k]));
-        f = wave_sum(f);
-        if (lane == 0) a.extra[r] += f;
-    } else {
-        const float ui = wave_sum(fmaf(u[1], it[1], u[0] * it[0])), ud = wave_sum(fmaf(u[1], d[1], u[0] * d[0])),
-                    id = wave_sum(fmaf(it[1], d[1], it[0] * d[0]));
-        if (lane == 0) {
-            row[a.f_col + 0] = ui;
-            row[a.f_col + 1] = ud;
-            row[a.f_col + 2] = id;
-            row[a.f_col + 3] = 0.f;
-        }
-    }
-}
-// d f -> d x.  NFM: d u = df (i + d), d i = df (u + d), d d = df (u + i), WRITTEN (nothing else feeds d x).
-// PNN: dip_j = sum_c dz[c] W0[384 + j][c]; d u += dip0 i + dip1 d, d i += dip0 u + dip2 d, d d += dip1 u + dip2 i, ADDED
-// to what the first layer's d x = dz W0[0:384]^T left there.  User / item columns only when the tables train.
-__global__ __launch_bounds__(256) void k_graph_feat_bwd(const FeatArgs a) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= a.rows_pad) return;
-    const float* row = a.act + (size_t)r * a.ld;
-    float* drow = a.dact + (size_t)r * a.ld;
-    const f32x2 u = *reinterpret_cast<const f32x2*>(row + 2 * lane), it = *reinterpret_cast<const f32x2*>(row + EMB + 2 * lane),
-                d = *reinterpret_cast<const f32x2*>(row + 2 * EMB + 2 * lane);
-    f32x2 du, di, dd;
-    if (a.kind == 0) {
-        const f32x2 df = *reinterpret_cast<const f32x2*>(drow + a.f_col + 2 * lane);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            du[k] = df[k] * (it[k] + d[k]);
-            di[k] = df[k] * (u[k] + d[k]);
-            dd[k] = df[k] * (u[k] + it[k]);
-        }
-    } else if (a.kind == 2) {
-        // DeepFM: d fm / d e_f = the sum of the other two fields' rows, ADDED to what the DNN's first layer left in d x
-        const float dl = a.dlogit[r];
-        const f32x2 du0 = *reinterpret_cast<const f32x2*>(drow + 2 * lane), di0 = *reinterpret_cast<const f32x2*>(drow + EMB + 2 * lane),
-                    dd0 = *reinterpret_cast<const f32x2*>(drow + 2 * EMB + 2 * lane);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            du[k] = du0[k] + dl * (it[k] + d[k]);
-            di[k] = di0[k] + dl * (u[k] + d[k]);
-            dd[k] = dd0[k] + dl * (u[k] + it[k]);
-        }
-    } else {
-        float p0 = 0.f, p1 = 0.f, p2 = 0.f;
-        for (int c = lane; c < a.n_out; c += 64) {
-            const float z = drow[a.z_col + c];
-            p0 = fmaf(z, a.w_ip[c], p0);
-            p1 = fmaf(z, a.w_ip[a.n_out + c], p1);
-            p2 = fmaf(z, a.w_ip[2 * a.n_out + c], p2);
-        }
-        p0 = wave_sum(p0);
-        p1 = wave_sum(p1);
-        p2 = wave_sum(p2);
-        const f32x2 du0 = *reinterpret_cast<const f32x2*>(drow + 2 * lane), di0 = *reinterpret_cast<const f32x2*>(drow + EMB + 2 * lane),
-                    dd0 = *reinterpret_cast<const f32x2*>(drow + 2 * EMB + 2 * lane);
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            du[k] = du0[k] + (p0 * it[k] + p1 * d[k]);
-            di[k] = di0[k] + (p0 * u[k] + p2 * d[k]);
-            dd[k] = dd0[k] + (p1 * u[k] + p2 * it[k]);
-        }
-    }
-    if (a.dx_all) {
-        *reinterpret_cast<f32x2*>(drow + 2 * lane) = du;
-        *reinterpret_cast<f32x2*>(drow + EMB + 2 * lane) = di;
-    }
-    *reinterpret_cast<f32x2*>(drow + 2 * EMB + 2 * lane) = dd;
-}
-// DeepFM at a field width E other than 128 (32 / 64 / 256; the 128-wide tower stays on kind 2 above, whose summation order
-// its recorded results are held to).  A row's field is E / 4 lanes of 16 bytes, so a wave serves 256 / E rows (8 at E = 32,
-// 4 at E = 64, 1 at E = 256) and the FM term  sum_k (u i + u d + i d)_k  is a butterfly over the row's lanes alone.
-template <int E>
-__global__ __launch_bounds__(256) void k_graph_fm_fwd(const FeatArgs a) {
-    constexpr int LPR = E / 4, RPW = 64 / LPR;              // lanes per row, rows per wave
-    const int lane = threadIdx.x & 63, c4 = lane % LPR;
-    const int r = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    if (r >= a.rows_pad) return;        // (rows_pad is a multiple of 64: the row's lanes leave together)
-    const float* row = a.act + (size_t)r * a.ld + 4 * c4;
-    const f32x4 u = *reinterpret_cast<const f32x4*>(row), it = *reinterpret_cast<const f32x4*>(row + E),
-                d = *reinterpret_cast<const f32x4*>(row + 2 * E);
-    float f = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) f += fmaf(it[k], d[k], fmaf(u[k], d[k], u[k] * it[k]));
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) f += __shfl_xor(f, o);
-    if (c4 == 0) a.extra[r] += f;
-}
-// d fm / d e_f = d logit x the sum of the other two fields' rows, ADDED to what the DNN's first layer left in d x
-// (user / item columns only when the tables train)
-template <int E>
-__global__ __launch_bounds__(256) void k_graph_fm_bwd(const FeatArgs a) {
-    constexpr int LPR = E / 4, RPW = 64 / LPR;
-    const int lane = threadIdx.x & 63, c4 = lane % LPR;
-    const int r = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
-    if (r >= a.rows_pad) return;
-    const float* row = a.act + (size_t)r * a.ld + 4 * c4;
-    float* drow = a.dact + (size_t)r * a.ld + 4 * c4;
-    const f32x4 u = *reinterpret_cast<const f32x4*>(row), it = *reinterpret_cast<const f32x4*>(row + E),
-                d = *reinterpret_cast<const f32x4*>(row + 2 * E);
-    const float dl = a.dlogit[r];
-    f32x4 dd = *reinterpret_cast<const f32x4*>(drow + 2 * E);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) dd[k] = dd[k] + dl * (u[k] + it[k]);
-    *reinterpret_cast<f32x4*>(drow + 2 * E) = dd;
-    if (a.dx_all) {
-        f32x4 du = *reinterpret_cast<const f32x4*>(drow), di = *reinterpret_cast<const f32x4*>(drow + E);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            du[k] = du[k] + dl * (it[k] + d[k]);
-            di[k] = di[k] + dl * (u[k] + d[k]);
-        }
-        *reinterpret_cast<f32x4*>(drow) = du;
-        *reinterpret_cast<f32x4*>(drow + E) = di;
-    }
-}
-// NFM's linear domain table: g[d] = sum over the batch rows of domain d of d loss / d logit  +  2 l2_lin w[d]
-// one workgroup per domain: rows strided over the 256 threads, LDS tree in a fixed order
-__device__ __forceinline__ void lin_domain_grad_body(const float* dlogit, const int32_t* domrow, int rows, const float* w, float two_l2,
-                                                     float* g, const int d, const GradSink& sk) {
-    __shared__ float red[256];
-    float s = 0.f;
-    for (int b = threadIdx.x; b < rows; b += 256) s += domrow[b] == d ? dlogit[b] : 0.f;
-    red[threadIdx.x] = s;
-    __syncthreads();
-#pragma unroll
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sink1(sk, g + d, red[0] + two_l2 * w[d]);
-}
-__global__ __launch_bounds__(256) void k_graph_lin_domain_grad(const float* dlogit, const int32_t* domrow, int rows, const float* w,
-                                                               float two_l2, int n_domain, float* g) {
-    GradSink none;
-    none.p = nullptr;
-    lin_domain_grad_body(dlogit, domrow, rows, w, two_l2, g, blockIdx.x, none);
-}
 static void launch_lin_domain_grad(hipStream_t s, const float* dlogit, const int32_t* domrow, int rows, const float* w, float two_l2,
                                    int n_domain, float* g) {
     GLAUNCH(k_graph_lin_domain_grad, dim3(n_domain), dim3(256), 0, s, dlogit, domrow, rows, w, two_l2, n_domain, g);
-}
-
-// ------------------------------------------------------------------ CCPM: convolutions over the FIELD axis, one wave per row
-// (deepctr CCPM with the three fields of this model, conv_kernel_width (6, 5), conv_filters (4, 4) -- oracle/fmnets.py:
-// Conv2D((6, 1), 'same', tanh) over [3 fields x 128], maximum over the fields (KMaxPooling, k = 1), Conv2D((5, 1)) on the
-// one row left = its centre tap, tanh; features [128 x 4]).  conv = [w1 6x4 | b1 4 | w2 4x4 (in, out) | b2 4] = 48 floats.
-struct CcpmArgs {
-    float* act; float* dact; int ld; int f_col, cg_col; int rows_pad; int dx_all;
-    const float* conv;
-};
-// a1 of (position, filter) for the three raw values of one embedding column, its maximum and where it sits
-__device__ __forceinline__ void ccpm_unit(const float* __restrict__ cv, const float (&x)[3], float (&m1)[4], int (&arg)[4],
-                                          float (&a2)[4]) {
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        float best = -3.0e38f;
-        int at = 0;
-#pragma unroll
-        for (int pos = 0; pos < 3; ++pos) {
-            float pre = 0.f;
-#pragma unroll
-            for (int t = 0; t < 6; ++t) {
-                const int src = pos + t - 2;        // TF 'same' for an even kernel: 2 taps before, 3 after
-                if (src >= 0 && src < 3) pre += x[src] * cv[t * 4 + f];
-            }
-            const float a = tanhf(pre + cv[24 + f]);
-            if (a > best) { best = a; at = pos; }  // (the first maximum wins a tie, as numpy's argmax)
-        }
-        m1[f] = best;
-        arg[f] = at;
-    }
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-        float pre = 0.f;
-#pragma unroll
-        for (int f = 0; f < 4; ++f) pre += m1[f] * cv[28 + f * 4 + o];
-        a2[o] = tanhf(pre + cv[44 + o]);
-    }
-}
-__global__ __launch_bounds__(256) void k_graph_ccpm_fwd(const CcpmArgs a) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= a.rows_pad) return;
-    float* row = a.act + (size_t)r * a.ld;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int e = 2 * lane + q;
-        const float x[3] = {row[e], row[EMB + e], row[2 * EMB + e]};
-        float m1[4], a2[4];
-        int arg[4];
-        ccpm_unit(a.conv, x, m1, arg, a2);
-        *reinterpret_cast<f32x4*>(row + a.f_col + 4 * e) = (f32x4){a2[0], a2[1], a2[2], a2[3]};
-    }
-}
-// d features -> d x and the row's share of the 48 convolution gradients (summed over the batch by k_graph_colsum)
-__global__ __launch_bounds__(256) void k_graph_ccpm_bwd(const CcpmArgs a) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= a.rows_pad) return;
-    const float* row = a.act + (size_t)r * a.ld;
-    float* drow = a.dact + (size_t)r * a.ld;
-    const float* cv = a.conv;
-    float gc[48];
-#pragma unroll
-    for (int k = 0; k < 48; ++k) gc[k] = 0.f;
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int e = 2 * lane + q;
-        const float x[3] = {row[e], row[EMB + e], row[2 * EMB + e]};
-        float m1[4], a2[4], dx[3] = {0.f, 0.f, 0.f};
-        int arg[4];
-        ccpm_unit(cv, x, m1, arg, a2);
-        const f32x4 df = *reinterpret_cast<const f32x4*>(drow + a.f_col + 4 * e);
-        float dm1[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const float dp2 = df[o] * (1.0f - a2[o] * a2[o]);
-            gc[44 + o] += dp2;
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                gc[28 + f * 4 + o] += m1[f] * dp2;
-                dm1[f] += dp2 * cv[28 + f * 4 + o];
-            }
-        }
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            const float dp1 = dm1[f] * (1.0f - m1[f] * m1[f]);      // m1 = a1 at its maximum
-            gc[24 + f] += dp1;
-#pragma unroll
-            for (int t = 0; t < 6; ++t) {
-#pragma unroll
-                for (int pos = 0; pos < 3; ++pos) {
-                    const int src = pos + t - 2;
-                    if (src >= 0 && src < 3 && pos == arg[f]) {
-                        gc[t * 4 + f] += x[src] * dp1;
-                        dx[src] += dp1 * cv[t * 4 + f];
-                    }
-                }
-            }
-        }
-        if (a.dx_all) {
-            drow[e] = dx[0];
-            drow[EMB + e] = dx[1];
-        }
-        drow[2 * EMB + e] = dx[2];
-    }
-#pragma unroll
-    for (int k = 0; k < 48; ++k) {
-        const float v = wave_sum(gc[k]);
-        if (lane == 0) drow[a.cg_col + k] = v;
-    }
-}
-
-// ------------------------------------------------------------------ AutoInt: multi-head self-attention over the three fields
-// (deepctr InteractingLayer, att_embedding_size 8, 4 heads, residual, no scaling -- oracle/fmnets.py).  Token-major compact
-// buffers: row 3 b + t = field t of batch row b.  Per layer: P = X W (k_graph_gemm, W = [W_query | W_key | W_value | W_res],
-// [d][128]) -> per batch row (one wave): scores Q_h K_h^T [3 x 3] per head, softmax over the fields, A V, + R, relu.
-constexpr int ATT_OUT = 32, ATT_DIM = 8, ATT_P = 4 * ATT_OUT;      // 4 heads x 8; 128 projection columns per token
-struct AttArgs {
-    const float* P;      // [3 rows_pad][128]
-    float* A;            // [rows_pad][36]: probabilities [head][field][field]
-    float* Y;            // [3 rows_pad][32]
-    const float* dY;     // [3 rows_pad][32] (backward)
-    float* dP;           // [3 rows_pad][128] (backward)
-    float* top; int top_ld;      // forward, last layer: also [rows_pad][96] inside the activation workspace (for the head)
-    const float* dtop; int dtop_ld;   // backward, last layer: d Y comes from the gradient workspace
-    int rows_pad;
-};
-__global__ __launch_bounds__(256) void k_graph_att_fwd(const AttArgs a) {
-    __shared__ float lds[4][3 * ATT_P + 48];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + w;
-    if (r >= a.rows_pad) return;
-    float* p = lds[w];
-    float* sc = p + 3 * ATT_P;
-    for (int i = lane; i < 3 * ATT_P; i += 64) p[i] = a.P[(size_t)r * 3 * ATT_P + i];
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 36) {
-        const int h = lane / 9, t = (lane % 9) / 3, s_ = lane % 3;
-        float v = 0.f;
-#pragma unroll
-        for (int j = 0; j < ATT_DIM; ++j) v = fmaf(p[t * ATT_P + h * ATT_DIM + j], p[s_ * ATT_P + ATT_OUT + h * ATT_DIM + j], v);
-        sc[lane] = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 36) {
-        const int base = lane - lane % 3;
-        const float m = fmaxf(fmaxf(sc[base], sc[base + 1]), sc[base + 2]);
-        const float e0 = __expf(sc[base] - m), e1 = __expf(sc[base + 1] - m), e2 = __expf(sc[base + 2] - m);
-        const float mine = __expf(sc[lane] - m) / ((e0 + e1) + e2);
-        a.A[(size_t)r * 36 + lane] = mine;
-        __builtin_amdgcn_wave_barrier();
-        sc[lane] = mine;
-    } else {
-        __builtin_amdgcn_wave_barrier();
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < 3 * ATT_OUT; i += 64) {
-        const int t = i / ATT_OUT, c = i % ATT_OUT, h = c / ATT_DIM;
-        float o = 0.f;
-#pragma unroll
-        for (int s_ = 0; s_ < 3; ++s_) o = fmaf(sc[h * 9 + t * 3 + s_], p[s_ * ATT_P + 2 * ATT_OUT + c], o);
-        const float y = fmaxf(o + p[t * ATT_P + 3 * ATT_OUT + c], 0.f);
-        a.Y[(size_t)r * 3 * ATT_OUT + i] = y;
-        if (a.top) a.top[(size_t)r * a.top_ld + i] = y;
-    }
-}
-__global__ __launch_bounds__(256) void k_graph_att_bwd(const AttArgs a) {
-    __shared__ float lds[4][3 * ATT_P + 48 + 48 + 96];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + w;
-    if (r >= a.rows_pad) return;
-    float* p = lds[w];
-    float* pa = p + 3 * ATT_P;       // probabilities
-    float* ds = pa + 48;             // d scores
-    float* dz = ds + 48;             // d (O + R) = d Y through the relu
-    for (int i = lane; i < 3 * ATT_P; i += 64) p[i] = a.P[(size_t)r * 3 * ATT_P + i];
-    if (lane < 36) pa[lane] = a.A[(size_t)r * 36 + lane];
-    for (int i = lane; i < 3 * ATT_OUT; i += 64) {
-        const float dy = a.dtop ? a.dtop[(size_t)r * a.dtop_ld + i] : a.dY[(size_t)r * 3 * ATT_OUT + i];
-        dz[i] = a.Y[(size_t)r * 3 * ATT_OUT + i] > 0.f ? dy : 0.f;
-    }
-    __builtin_amdgcn_wave_barrier();
-    float da = 0.f;
-    if (lane < 36) {
-        const int h = lane / 9, t = (lane % 9) / 3, s_ = lane % 3;
-#pragma unroll
-        for (int j = 0; j < ATT_DIM; ++j) da = fmaf(dz[t * ATT_OUT + h * ATT_DIM + j], p[s_ * ATT_P + 2 * ATT_OUT + h * ATT_DIM + j], da);
-        ds[lane] = da * pa[lane];
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 36) {
-        const int base = lane - lane % 3;
-        const float dot = (ds[base] + ds[base + 1]) + ds[base + 2];
-        const float v = pa[lane] * (da - dot);
-        __builtin_amdgcn_wave_barrier();
-        ds[lane] = v;
-    } else {
-        __builtin_amdgcn_wave_barrier();
-    }
-    __builtin_amdgcn_wave_barrier();
-    float* dp = a.dP + (size_t)r * 3 * ATT_P;
-    for (int i = lane; i < 3 * ATT_OUT; i += 64) {
-        const int t = i / ATT_OUT, c = i % ATT_OUT, h = c / ATT_DIM;
-        float dq = 0.f, dk = 0.f, dv = 0.f;
-#pragma unroll
-        for (int s_ = 0; s_ < 3; ++s_) {
-            dq = fmaf(ds[h * 9 + t * 3 + s_], p[s_ * ATT_P + ATT_OUT + c], dq);           // d Q[t] = sum_s dS[t][s] K[s]
-            dk = fmaf(ds[h * 9 + s_ * 3 + t], p[s_ * ATT_P + c], dk);                      // d K[t] = sum_s dS[s][t] Q[s]
-            dv = fmaf(pa[h * 9 + s_ * 3 + t], dz[s_ * ATT_OUT + c], dv);                   // d V[t] = sum_s A[s][t] dZ[s]
-        }
-        dp[t * ATT_P + c] = dq;
-        dp[t * ATT_P + ATT_OUT + c] = dk;
-        dp[t * ATT_P + 2 * ATT_OUT + c] = dv;
-        dp[t * ATT_P + 3 * ATT_OUT + c] = dz[i];
-    }
-}
-// out[r][k] = sum_c d[r][c] W[k][c] for a NARROW result (k < n_k <= 32; c < n_c): d X of the 32-wide attention layers
-__global__ __launch_bounds__(256) void k_graph_small_nt(const float* d, int n_c, const float* W, int n_k, int rows, float* out) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * n_k) return;
-    const int r = idx / n_k, k = idx - r * n_k;
-    const f32x4* dr = reinterpret_cast<const f32x4*>(d + (size_t)r * n_c);       // n_c is a multiple of 4 (128)
-    const f32x4* wr = reinterpret_cast<const f32x4*>(W + (size_t)k * n_c);
-    float s = 0.f;
-    for (int c4 = 0; c4 < n_c / 4; c4 += 4) {           // 16-B loads, eight in flight; the chain keeps its order
-        f32x4 x[4], y[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            x[u] = dr[c4 + u];
-            y[u] = wr[c4 + u];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) s = fmaf(x[u][q], y[u][q], s);
-    }
-    out[idx] = s;
-}
-// d x[:, first .. first + n) (+)= compact [rows][384] columns first .. first + n
-__global__ __launch_bounds__(256) void k_graph_add_x(float* dact, int ld, const float* src, int rows, int first, int n) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= rows * n) return;
-    const int r = idx / n, c = first + (idx - r * n);
-    dact[(size_t)r * ld + c] += src[(size_t)r * XDIM + c];
-}
-
-// ------------------------------------------------------------------ gate: softmax(q Wg) and the mixture, one wave per row
-struct GateArgs {
-    float* act; float* dact; int ld;
-    int q_col, n_q;             // gate DNN output
-    const float* wg; int n_e;   // [n_q][n_e]
-    int e_col[MAX_MIX];         // last-layer output of each mixed expert
-    int n_h;                    // expert width
-    int g_col, m_col;           // gate probabilities (n_e columns), mixture (n_h columns)
-    int rows_pad;
-    float gate_scale;           // 1 / keep of the dropout behind every DNN layer (1 in inference)
-};
-// One workgroup per batch row (4 waves: the gate logits / the d gate sums are dealt over the waves, the expert width over all
-// 256 lanes) -- with one wave per row the 1,024 rows of a batch were 1,024 waves on 1,024 SIMDs, each walking its experts'
-// reductions one after the other (23 us for 12 experts).  Same summation orders as that form: bit-identical results.
-__global__ __launch_bounds__(256) void k_graph_gate_fwd(const GateArgs a) {
-    __shared__ float sl[MAX_MIX];
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    float* row = a.act + (size_t)r * a.ld;
-    for (int e = w; e < a.n_e; e += 4) {
-        float s = 0.f;
-        for (int j = lane; j < a.n_q; j += 64) s = fmaf(row[a.q_col + j], a.wg[j * a.n_e + e], s);
-        s = wave_sum(s);
-        if (lane == 0) sl[e] = s;
-    }
-    __syncthreads();
-    float mx = -3.0e38f;
-    for (int e = 0; e < a.n_e; ++e) mx = fmaxf(mx, sl[e]);
-    float den = 0.f;
-    for (int e = 0; e < a.n_e; ++e) den += __expf(sl[e] - mx);
-    if (tid < a.n_e) row[a.g_col + tid] = __expf(sl[tid] - mx) / den;
-    for (int cidx = tid; cidx < a.n_h; cidx += 256) {
-        float m = 0.f;
-        for (int e = 0; e < a.n_e; ++e) m += (__expf(sl[e] - mx) / den) * row[a.e_col[e] + cidx];
-        row[a.m_col + cidx] = m;
-    }
-}
-// d mixture -> d expert outputs (times their relu / dropout gate = d z of the experts' last layers), d gate logits
-// (kept: dWg = q^T dgl) and d q (times q's gate = d z of the gate DNN's last layer)
-__global__ __launch_bounds__(256) void k_graph_gate_bwd(const GateArgs a) {
-    __shared__ float sdg[MAX_MIX], sgp[MAX_MIX];
-    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const float* row = a.act + (size_t)r * a.ld;
-    float* drow = a.dact + (size_t)r * a.ld;
-    for (int e = w; e < a.n_e; e += 4) {
-        float t = 0.f;
-        for (int cidx = lane; cidx < a.n_h; cidx += 64) t = fmaf(drow[a.m_col + cidx], row[a.e_col[e] + cidx], t);
-        t = wave_sum(t);
-        if (lane == 0) {
-            sdg[e] = t;
-            sgp[e] = row[a.g_col + e];
-        }
-    }
-    __syncthreads();
-    float s = 0.f;
-    for (int e = 0; e < a.n_e; ++e) s = fmaf(sgp[e], sdg[e], s);
-    for (int cidx = tid; cidx < a.n_h; cidx += 256) {
-        const float dm = drow[a.m_col + cidx];
-        for (int e = 0; e < a.n_e; ++e) {
-            const float h = row[a.e_col[e] + cidx];
-            drow[a.e_col[e] + cidx] = h > 0.f ? (sgp[e] * dm) * a.gate_scale : 0.f;
-        }
-    }
-    __syncthreads();        // (every read of d mixture is done before g_col / q_col, which may neighbour it, are written)
-    if (tid < a.n_e) drow[a.g_col + tid] = sgp[tid] * (sdg[tid] - s);        // d gate logit
-    for (int j = tid; j < a.n_q; j += 256) {
-        float v = 0.f;
-        for (int e = 0; e < a.n_e; ++e) v = fmaf(sgp[e] * (sdg[e] - s), a.wg[j * a.n_e + e], v);
-        drow[a.q_col + j] = row[a.q_col + j] > 0.f ? v * a.gate_scale : 0.f;
-    }
-}
-
-// ------------------------------------------------------------------ head: Dense(1, no bias) + global bias, sigmoid, Keras BCE
-struct HeadArgs {
-    const float* act; float* dact; int ld;
-    int t_col, n_t;
-    int n_plain;                // leading columns that no dropout follows (AutoInt: the attention output): gate only
-    const float* w; const float* gb;
-    const float* y; int rows, rows_pad;
-    const float* extra;         // NFM: the linear logit of every position (null otherwise)
-    float* dlogit; float* rowloss;
-    int train; float gate_scale;
-    const float* thresholds; uint32_t* hist; float* pred_out;       // inference
-    const float* log_var; const int32_t* domrow;    // weighted loss (training only): d logit scaled by 1 / var^2, var =
-                                                    // log_var[domain of the batch's FIRST row] (weighted_loss.py:38-41)
-};
-__global__ __launch_bounds__(256) void k_graph_head(const HeadArgs a) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= a.rows_pad) return;
-    const float* row = a.act + (size_t)r * a.ld;
-    float s = 0.f;
-    for (int cidx = lane; cidx < a.n_t; cidx += 64) s = fmaf(row[a.t_col + cidx], a.w[cidx], s);
-    const float logit = wave_sum(s) + a.gb[0] + (a.extra ? a.extra[r] : 0.f);
-    float p;
-    if (logit >= 0.f) {
-        p = 1.0f / (1.0f + __expf(-logit));
-    } else {
-        const float ez = __expf(logit);
-        p = ez / (1.0f + ez);
-    }
-    const bool valid = r < a.rows;
-    const float y = a.y[r];
-    const float lo = 1e-7f, hi = 1.0f - 1e-7f;
-    const float pc = fminf(fmaxf(p, lo), hi);
-    const float zc = __logf(pc / (1.0f - pc));
-    const float loss = fmaxf(zc, 0.f) - zc * y + __logf(1.0f + __expf(-fabsf(zc)));
-    if (lane == 0) a.rowloss[r] = valid ? loss : 0.f;
-    if (a.train) {
-        const float inside = (p >= lo && p <= hi) ? 1.0f : 0.0f;
-        float dl = valid ? ((p - y) * inside) / (float)a.rows : 0.f;
-        if (a.log_var) {
-            const float var = a.log_var[a.domrow[0]];
-            dl *= 1.0f / (var * var);
-        }
-        if (lane == 0) a.dlogit[r] = dl;
-        float* drow = a.dact + (size_t)r * a.ld;
-        for (int cidx = lane; cidx < a.n_t; cidx += 64)
-            drow[a.t_col + cidx] = row[a.t_col + cidx] > 0.f ? (dl * a.w[cidx]) * (cidx < a.n_plain ? 1.0f : a.gate_scale) : 0.f;
-    } else if (lane == 0 && valid) {
-        int blo = 0, bhi = 500;          // AUC bin = number of thresholds strictly below p (utils/metrics_utils.py:309)
-        while (blo < bhi) {
-            const int mid = (blo + bhi) >> 1;
-            if (a.thresholds[mid] < p) blo = mid + 1; else bhi = mid;
-        }
-        atomicAdd(a.hist + (y != 0.f ? 501 : 0) + blo, 1u);
-        if (a.pred_out) a.pred_out[r] = p;
-    }
-}
-
-// batch loss = mean of the rows' BCE + l2 (sum of squares of the three tables); one workgroup, fixed order.
-// mode 0: out[0] = loss;  mode 1 (evaluation): out[0] += loss
-__global__ __launch_bounds__(256) void k_graph_loss(const float* rowloss, int rows, const float* dm, int dm_count, float l2,
-                                                    const float* frozen_sumsq, float* out, int mode, const float* lin_d,
-                                                    int n_lin_d, float l2_lin, const float* log_var = nullptr,
-                                                    const int32_t* domrow = nullptr, float* g_log_var = nullptr,
-                                                    int n_domain = 0) {
-    __shared__ float red[256];
-    float s = 0.f, q = 0.f;
-    for (int b = threadIdx.x; b < rows; b += 256) s += rowloss[b];
-    for (int e = threadIdx.x; e < dm_count; e += 256) q = fmaf(dm[e], dm[e], q);
-    float ql = 0.f;         // NFM: l2_lin * (sum of squares of the three 1-d linear tables)
-    if (threadIdx.x == 0 && lin_d) {
-        for (int e = 0; e < n_lin_d; ++e) ql = fmaf(lin_d[e], lin_d[e], ql);
-        ql = l2_lin * ((frozen_sumsq[2] + frozen_sumsq[3]) + ql);
-    }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    const float tot = red[0];
-    __syncthreads();
-    red[threadIdx.x] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float data = tot / (float)rows;
-        if (log_var) {      // weighted_loss.py:30-35: mean(BCE / var^2 + log var); d / d var = -2 mean(BCE) / var^3 + 1 / var
-            const int d0 = domrow[0];
-            const float var = log_var[d0];
-            for (int d = 0; d < n_domain; ++d) g_log_var[d] = d == d0 ? -2.0f * data / (var * var * var) + 1.0f / var : 0.f;
-            data = (1.0f / (var * var)) * data + logf(var);
-        }
-        const float loss = data + l2 * ((frozen_sumsq[0] + frozen_sumsq[1]) + red[0]) + ql;
-        out[0] = mode ? out[0] + loss : loss;
-    }
-}
-__global__ void k_graph_scale(float* x, float s) { x[0] *= s; }
-// ------------------------------------------------------------------ domain table gradient
-// g[d][c] = sum over the batch rows of domain d of d x[b][256 + c]  +  2 l2 Dm[d][c]   (rows in batch order)
-// grid (8 column blocks, domains): 16 columns x 16 row groups per workgroup, 8 loads in flight, summed through LDS in a
-// fixed order; a domain with no row in the batch (all but one of them in a domain step) leaves after one look at the ids.
-// (emb = the table's width: emb / 16 column blocks, first column x_col = 2 emb of d x)
-__device__ __forceinline__ void domain_grad_body(const float* dx, int ld, int x_col, const int32_t* domrow, int rows,
-                                                 const float* dm, float two_l2, float* g, const int bx, const int by,
-                                                 const int emb, const GradSink& sk) {
-    __shared__ float red[CS_GROUPS][CS_COLS + 1];
-    const int d = by, c = threadIdx.x & (CS_COLS - 1), rg = threadIdx.x / CS_COLS;
-    const int col = bx * CS_COLS + c;
-    int mine = 0;
-    for (int b = threadIdx.x; b < rows; b += 256) mine |= domrow[b] == d;
-    if (!__syncthreads_or(mine)) {
-        if (rg == 0) sink1(sk, g + d * emb + col, two_l2 * dm[d * emb + col]);
-        return;
-    }
-    const float* p = dx + x_col + col;
-    float s = 0.f;
-    int b = rg;
-    for (; b + 7 * CS_GROUPS < rows; b += 8 * CS_GROUPS) {
-        float v[8];
-        int id[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            id[k] = domrow[b + k * CS_GROUPS];
-            v[k] = p[(size_t)(b + k * CS_GROUPS) * ld];
-        }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += id[k] == d ? v[k] : 0.f;
-    }
-    for (; b < rows; b += CS_GROUPS) s += domrow[b] == d ? p[(size_t)b * ld] : 0.f;
-    red[rg][c] = s;
-    __syncthreads();
-    if (rg == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CS_GROUPS; ++k) t += red[k][c];
-        sink1(sk, g + d * emb + col, t + two_l2 * dm[d * emb + col]);
-    }
-}
-__global__ __launch_bounds__(256) void k_graph_domain_grad(const float* dx, int ld, int x_col, const int32_t* domrow, int rows,
-                                                           const float* dm, float two_l2, float* g, int emb) {
-    GradSink none;
-    none.p = nullptr;
-    domain_grad_body(dx, ld, x_col, domrow, rows, dm, two_l2, g, blockIdx.x, blockIdx.y, emb, none);
-}
-// ---- the tail of a step's backward pass in ONE launch: the ends of the queued weight gradients (wfinish_multi_body's
-// workgroups), the narrow contractions that were queued with them (head / gate kernels, PNN's inner-product rows, the
-// attention projections: k_graph_small_tn's workgroups) and the domain table's gradient (k_graph_domain_grad's) -- all of
-// them read what the backward pass left in the workspaces and write gradients nothing but the optimiser reads.
-constexpr int MAX_TQ = 6;
-struct TailJobs {
-    int n_tn;
-    int tn_first[MAX_TQ + 1];       // first workgroup (behind the weight gradients' ends) of narrow contraction q
-    const float* in[MAX_TQ]; const float* d[MAX_TQ]; float* out[MAX_TQ]; float* sum_out[MAX_TQ];
-    int in_ld[MAX_TQ], d_ld[MAX_TQ], rows[MAX_TQ], n_j[MAX_TQ], n_e[MAX_TQ];
-    int dg_first, dg_blocks;        // the domain table's gradient: dg_emb / 16 column blocks x n_domain (0 blocks: not in this launch)
-    int dg_emb;                     // ... its width
-    const float* dx; int ld, x_col; const int32_t* domrow; int dg_rows; const float* dm; float two_l2; float* g_dm;
-    int lin_blocks;                 // the 1-d linear domain table's gradient (k_graph_lin_domain_grad's workgroups: one per domain)
-    const float* lin_dlogit; const float* lin_w; float lin_two_l2; float* lin_g;
-    GradSink sink;                  // p non-null: every finished gradient element steps its parameter right here
-};
-__global__ __launch_bounds__(256) void k_graph_tail(const WFinish f, const TailJobs j) {
-    const int nf = f.n ? f.first[f.n] : 0;
-    int bid = blockIdx.x;
-    if (bid < nf) {
-        wfinish_multi_body(f, bid, j.sink);
-        return;
-    }
-    bid -= nf;
-    if (bid < j.dg_first) {
-        int q = 0;
-        while (q + 1 < j.n_tn && bid >= j.tn_first[q + 1]) ++q;
-        small_tn_body(j.in[q], j.in_ld[q], j.d[q], j.d_ld[q], j.rows[q], j.n_j[q], j.n_e[q], j.out[q], j.sum_out[q],
-                      bid - j.tn_first[q], j.tn_first[q + 1] - j.tn_first[q], j.sink);
-        return;
-    }
-    bid -= j.dg_first;
-    if (bid < j.dg_blocks) {
-        const int cb = j.dg_emb / CS_COLS;
-        domain_grad_body(j.dx, j.ld, j.x_col, j.domrow, j.dg_rows, j.dm, j.two_l2, j.g_dm, bid % cb, bid / cb, j.dg_emb, j.sink);
-        return;
-    }
-    bid -= j.dg_blocks;
-    if (bid < j.lin_blocks) lin_domain_grad_body(j.lin_dlogit, j.domrow, j.dg_rows, j.lin_w, j.lin_two_l2, j.lin_g, bid, j.sink);
-}
-
-// ------------------------------------------------------------------ optimiser on a range of the flat vector
-struct AdamArgs {           // up to two ranges of the flat vector in one launch (the shared block and the task's block)
-    float *p, *m, *v;       // bases of the flat vector / its slots (m: the accumulator for MAMDR_OPT_ACCUMULATE)
-    const float* g;         // gradient base, addressed like p
-    int64_t off4[2], n4[2]; // float4 offsets / counts of the ranges
-    int optimizer;          // MAMDR_OPT_ADAM / MAMDR_OPT_SGD / MAMDR_OPT_ACCUMULATE (m += g, nothing else)
-    float alpha, omb1, omb2, eps;
-};
-__global__ __launch_bounds__(256) void k_graph_adam(const AdamArgs a) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < a.n4[0]) i += a.off4[0];
-    else if (i - a.n4[0] < a.n4[1]) i = i - a.n4[0] + a.off4[1];
-    else return;
-    f32x4 p = reinterpret_cast<const f32x4*>(a.p)[i];
-    const f32x4 g = reinterpret_cast<const f32x4*>(a.g)[i];
-    f32x4 m = a.optimizer != MAMDR_OPT_SGD ? reinterpret_cast<const f32x4*>(a.m)[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 v = a.optimizer == MAMDR_OPT_ADAM ? reinterpret_cast<const f32x4*>(a.v)[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        float pk = p[k], mk = m[k], vk = v[k];
-        opt_elem(a.optimizer, g[k], pk, mk, vk, a.alpha, a.omb1, a.omb2, a.eps);
-        p[k] = pk; m[k] = mk; v[k] = vk;
-    }
-    if (a.optimizer != MAMDR_OPT_ACCUMULATE) reinterpret_cast<f32x4*>(a.p)[i] = p;
-    if (a.optimizer != MAMDR_OPT_SGD) reinterpret_cast<f32x4*>(a.m)[i] = m;
-    if (a.optimizer == MAMDR_OPT_ADAM) reinterpret_cast<f32x4*>(a.v)[i] = v;
-}
-
-// ------------------------------------------------------------------ Star forms (MAMDR_GRAPH_STAR)
-// model_zoo/Star/star.py:70-96 as a family: norm none / PartitionedNorm / BatchNormalization, Dense / StarFCN hidden layers,
-// the auxiliary network.  Everything per-domain is selected by d = the domain id of the batch's FIRST row, read on the
-// device (partitioned_norm.py:136, star_fcn.py:112, auxiliary_net.py:100).  The contractions are the engine's own; here:
-//   k_star_colstats<false>  per-chunk sum x / sum x^2 of the 384 input columns, double partials          (forward)
-//   k_star_norm_fwd         the partials summed in chunk order, batch moments, x -> xn, the moving statistics' update of the
-//                           right flavour (PN: domain d's pair, zero-debiased; BN: one pair, plain); evaluation: moving statistics
-//   k_star_colstats<true>   per-chunk sum dxn / sum dxn x^                                                 (backward)
-//   k_star_norm_bwd         s1, s2 finished in chunk order, dx, the norm's parameter gradients (zeros for the other domains)
-//   k_star_eff              the step's effective tensors into scratch: Ws (.) Wd[d], bs + bd[d], aux_W[d], aux_b[d]
-//   k_star_chain            scratch gradients dK / db -> g(Ws), g(Wd[d]), g(bs), g(bd[d]), g(aux_W[d]), g(aux_b[d]), zeros elsewhere
-//   k_star_join_fwd / bwd   top = h_n + a; d top through both relu gates
-// BatchNormalization's moving-average rule is restated from Keras' `_assign_moving_average` of TF 1.12 (no zero-debias) and,
-// like every inner-step statement of this project, is PARITY UNPINNED against TF itself.
-constexpr int SN_ROWS = 128;            // batch rows per chunk of a column reduction
-constexpr int SN_VEC = XDIM / 4;        // float4 columns of a row (96); a block = 96 x 4 row lanes
-constexpr float BN_DECAY = 0.01f;       // float32(1.0 - 0.99): Keras hands `1.0 - momentum` over as a Python float
-struct StarNormArgs {
-    const float* x; float* xn; int ld;          // raw input columns / normalised columns of the activation workspace
-    const float* dxn; float* dx;                // their gradients
-    int rows, rows_pad, n_chunks, n_domain;
-    int norm, train;                            // 1 pn, 2 bn
-    const int32_t* domrow;
-    double* part;                               // [n_chunks][2][384]
-    float* pnv;                                 // this step's [mean | inv | gamma inv], 3 x 384
-    const float *gs, *bs, *gd, *bd;             // pn: shared / specific; bn: gs = gamma, bs = beta
-    float *g_gs, *g_bs, *g_gd, *g_bd;
-    float* aux;                                 // pn: [mov_mean | mov_var | biased_mean | biased_var] [D][384] each, steps [D]; bn: [mov_mean | mov_var] [384]
-};
-template <bool BWD>
-__global__ __launch_bounds__(XDIM) void k_star_colstats(const StarNormArgs a) {
-    __shared__ double sh[4][2][XDIM];
-    const int tid = threadIdx.x, v = tid % SN_VEC, rl = tid / SN_VEC;
-    const int r0 = blockIdx.x * SN_ROWS, r1 = min(r0 + SN_ROWS, a.rows);
-    double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
-    f32x4 mean = {0.f, 0.f, 0.f, 0.f}, inv = mean;
-    if (BWD) {
-        mean = *reinterpret_cast<const f32x4*>(a.pnv + 4 * v);
-        inv = *reinterpret_cast<const f32x4*>(a.pnv + XDIM + 4 * v);
-    }
-    for (int r = r0 + rl; r < r1; r += 4) {
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + (size_t)r * a.ld + 4 * v);
-        if (BWD) {
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(a.dxn + (size_t)r * a.ld + 4 * v);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xh = __fmul_rn(__fsub_rn(xv[k], mean[k]), inv[k]);
-                s1[k] += (double)gv[k];
-                s2[k] += (double)__fmul_rn(gv[k], xh);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const double xd = (double)xv[k];
-                s1[k] += xd;
-                s2[k] += xd * xd;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sh[rl][0][4 * v + k] = s1[k];
-        sh[rl][1][4 * v + k] = s2[k];
-    }
-    __syncthreads();
-    double t1 = 0.0, t2 = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {       // row lanes in lane order: fixed
-        t1 += sh[q][0][tid];
-        t2 += sh[q][1][tid];
-    }
-    a.part[(size_t)blockIdx.x * 2 * XDIM + tid] = t1;
-    a.part[(size_t)blockIdx.x * 2 * XDIM + XDIM + tid] = t2;
-}
-// every block sums the chunks' partials itself (chunk order: the same bits in every block), block 0 keeps the results
-__global__ __launch_bounds__(XDIM) void k_star_norm_fwd(const StarNormArgs a) {
-    __shared__ __attribute__((aligned(16))) float sh_scale[XDIM], sh_shift[XDIM];
-    const int c = threadIdx.x, d = a.domrow[0];
-    const bool pn = a.norm == 1, keep = blockIdx.x == 0;
-    const size_t o = pn ? (size_t)d * XDIM + c : (size_t)c;
-    const size_t dx = pn ? (size_t)a.n_domain * XDIM : (size_t)XDIM;       // floats per statistic
-    float mean, var;
-    if (a.train) {
-        double S1 = 0.0, S2 = 0.0;
-        for (int ch = 0; ch < a.n_chunks; ++ch) {
-            S1 += a.part[(size_t)ch * 2 * XDIM + c];
-            S2 += a.part[(size_t)ch * 2 * XDIM + XDIM + c];
-        }
-        // nn.moments: mean, then the population variance about that fp32 mean -- E[x^2] - 2 mean E[x] + mean^2 in double
-        const double B = (double)a.rows, mu = S1 / B;
-        mean = (float)mu;
-        const double mf = (double)mean, vd = S2 / B - 2.0 * mf * mu + mf * mf;
-        var = (float)(vd > 0.0 ? vd : 0.0);
-        if (keep && pn) {
-            // assign_moving_average(zero_debias=True): biased += (value - biased)(1 - momentum); moving = biased / (1 - momentum^step)
-            const float t_step = a.aux[4 * dx + d] + 1.0f;
-            const float factor = 1.0f - powf(PN_MOMENTUM, t_step), omm = 1.0f - PN_MOMENTUM;
-            float bm = a.aux[2 * dx + o], bv = a.aux[3 * dx + o];
-            bm += (mean - bm) * omm;
-            bv += (var - bv) * omm;
-            a.aux[2 * dx + o] = bm;
-            a.aux[3 * dx + o] = bv;
-            a.aux[o] = bm / factor;
-            a.aux[dx + o] = bv / factor;
-            __syncthreads();            // (every thread of the block has read the old step)
-            if (c == 0) a.aux[4 * dx + d] = t_step;
-        } else if (keep) {
-            // Keras BatchNormalization._assign_moving_average (TF 1.12): moving -= (moving - value)(1 - momentum)
-            const float mm = a.aux[o], mv = a.aux[dx + o];
-            a.aux[o] = __fsub_rn(mm, __fmul_rn(__fsub_rn(mm, mean), BN_DECAY));
-            a.aux[dx + o] = __fsub_rn(mv, __fmul_rn(__fsub_rn(mv, var), BN_DECAY));
-        }
-    } else {
-        mean = a.aux[o];
-        var = a.aux[dx + o];
-    }
-    const float inv = 1.0f / sqrtf(var + PN_EPS);
-    const float gamma = pn ? a.gs[c] * a.gd[(size_t)d * XDIM + c] : a.gs[c];
-    const float beta = pn ? a.bs[c] + a.bd[(size_t)d * XDIM + c] : a.bs[c];
-    const float scale = __fmul_rn(inv, gamma);
-    sh_scale[c] = scale;
-    sh_shift[c] = __fsub_rn(beta, __fmul_rn(mean, scale));
-    if (keep && a.train) {
-        a.pnv[c] = mean;
-        a.pnv[XDIM + c] = inv;
-        a.pnv[2 * XDIM + c] = __fmul_rn(gamma, inv);
-    }
-    __syncthreads();
-    const int v = c % SN_VEC, rl = c / SN_VEC;
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(sh_scale + 4 * v), sf = *reinterpret_cast<const f32x4*>(sh_shift + 4 * v);
-    const int r0 = blockIdx.x * SN_ROWS, r1 = min(r0 + SN_ROWS, a.rows_pad);
-    for (int r = r0 + rl; r < r1; r += 4) {
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + (size_t)r * a.ld + 4 * v);
-        f32x4 y;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) y[k] = __fadd_rn(__fmul_rn(xv[k], sc[k]), sf[k]);
-        *reinterpret_cast<f32x4*>(a.xn + (size_t)r * a.ld + 4 * v) = y;
-    }
-}
-// s1 = sum dxn, s2 = sum dxn x^ (chunk order); dx = gamma inv (dxn - s1 / B - x^ s2 / B); block 0: the parameter gradients
-__global__ __launch_bounds__(XDIM) void k_star_norm_bwd(const StarNormArgs a) {
-    __shared__ __attribute__((aligned(16))) float sh_t1[XDIM], sh_t2[XDIM];
-    const int c = threadIdx.x, d = a.domrow[0];
-    double S1 = 0.0, S2 = 0.0;
-    for (int ch = 0; ch < a.n_chunks; ++ch) {
-        S1 += a.part[(size_t)ch * 2 * XDIM + c];
-        S2 += a.part[(size_t)ch * 2 * XDIM + XDIM + c];
-    }
-    const float s1 = (float)S1, s2 = (float)S2, B = (float)a.rows;
-    sh_t1[c] = __fdiv_rn(s1, B);
-    sh_t2[c] = __fdiv_rn(s2, B);
-    if (blockIdx.x == 0) {
-        if (a.norm == 1) {
-            a.g_bs[c] = s1;
-            a.g_gs[c] = __fmul_rn(s2, a.gd[(size_t)d * XDIM + c]);
-            const float gg = __fmul_rn(s2, a.gs[c]);
-            for (int j = 0; j < a.n_domain; ++j) {
-                a.g_gd[(size_t)j * XDIM + c] = j == d ? gg : 0.f;
-                a.g_bd[(size_t)j * XDIM + c] = j == d ? s1 : 0.f;
-            }
-        } else {
-            a.g_bs[c] = s1;
-            a.g_gs[c] = s2;
-        }
-    }
-    __syncthreads();
-    const int v = c % SN_VEC, rl = c / SN_VEC;
-    const f32x4 t1 = *reinterpret_cast<const f32x4*>(sh_t1 + 4 * v), t2 = *reinterpret_cast<const f32x4*>(sh_t2 + 4 * v);
-    const f32x4 mean = *reinterpret_cast<const f32x4*>(a.pnv + 4 * v), inv = *reinterpret_cast<const f32x4*>(a.pnv + XDIM + 4 * v);
-    const f32x4 coef = *reinterpret_cast<const f32x4*>(a.pnv + 2 * XDIM + 4 * v);
-    const int r0 = blockIdx.x * SN_ROWS, r1 = min(r0 + SN_ROWS, a.rows_pad);
-    for (int r = r0 + rl; r < r1; r += 4) {
-        f32x4 y = {0.f, 0.f, 0.f, 0.f};
-        if (r < a.rows) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(a.x + (size_t)r * a.ld + 4 * v);
-            const f32x4 gv = *reinterpret_cast<const f32x4*>(a.dxn + (size_t)r * a.ld + 4 * v);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float xh = __fmul_rn(__fsub_rn(xv[k], mean[k]), inv[k]);
-                y[k] = __fmul_rn(coef[k], __fsub_rn(__fsub_rn(gv[k], t1[k]), __fmul_rn(xh, t2[k])));
-            }
-        }
-        *reinterpret_cast<f32x4*>(a.dx + (size_t)r * a.ld + 4 * v) = y;
-    }
-}
-// the per-domain tensors of a step: segment s of the scratch block = op(shared tensor, slice d of the specific tensor)
-constexpr int MAX_SSEG = 10;            // 4 layers x (kernel, bias) + the auxiliary network's pair
-enum { SSEG_MUL = 0, SSEG_ADD = 1, SSEG_COPY = 2 };
-struct StarTab {
-    int n;
-    int first4[MAX_SSEG + 1];           // first float4 of segment s in the scratch block
-    int64_t shared[MAX_SSEG], spec[MAX_SSEG];       // flat-vector offsets (shared unused for SSEG_COPY)
-    int cnt[MAX_SSEG], op[MAX_SSEG];    // floats per slice
-};
-__global__ __launch_bounds__(256) void k_star_eff(const StarTab t, const float* params, const int32_t* domrow, float* eff) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= t.first4[t.n]) return;
-    int s = 0;
-    while (s + 1 < t.n && i >= t.first4[s + 1]) ++s;
-    const int e = 4 * (i - t.first4[s]), d = domrow[0];
-    const f32x4 sp = *reinterpret_cast<const f32x4*>(params + t.spec[s] + (size_t)d * t.cnt[s] + e);
-    f32x4 out = sp;
-    if (t.op[s] != SSEG_COPY) {
-        const f32x4 sh = *reinterpret_cast<const f32x4*>(params + t.shared[s] + e);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) out[k] = t.op[s] == SSEG_MUL ? __fmul_rn(sh[k], sp[k]) : __fadd_rn(sh[k], sp[k]);
-    }
-    *reinterpret_cast<f32x4*>(eff + 4 * (size_t)i) = out;
-}
-// gbase is addressed like the flat vector (gradient of element `off` at gbase + off)
-__global__ __launch_bounds__(256) void k_star_chain(const StarTab t, const float* params, const int32_t* domrow, const float* deff,
-                                                    float* gbase, int n_domain) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= t.first4[t.n]) return;
-    int s = 0;
-    while (s + 1 < t.n && i >= t.first4[s + 1]) ++s;
-    const int e = 4 * (i - t.first4[s]), d = domrow[0];
-    const f32x4 dk = *reinterpret_cast<const f32x4*>(deff + 4 * (size_t)i);
-    f32x4 gd = dk;
-    if (t.op[s] == SSEG_MUL) {
-        const f32x4 ws = *reinterpret_cast<const f32x4*>(params + t.shared[s] + e);
-        const f32x4 wd = *reinterpret_cast<const f32x4*>(params + t.spec[s] + (size_t)d * t.cnt[s] + e);
-        f32x4 gs;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            gs[k] = __fmul_rn(dk[k], wd[k]);
-            gd[k] = __fmul_rn(dk[k], ws[k]);
-        }
-        *reinterpret_cast<f32x4*>(gbase + t.shared[s] + e) = gs;
-    } else if (t.op[s] == SSEG_ADD) {
-        *reinterpret_cast<f32x4*>(gbase + t.shared[s] + e) = dk;
-    }
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (int j = 0; j < n_domain; ++j)
-        *reinterpret_cast<f32x4*>(gbase + t.spec[s] + (size_t)j * t.cnt[s] + e) = j == d ? gd : zero;
-}
-// the auxiliary branch's join (star.py:92-93): top = h_n + a; backward: d top through the relu of each summand
-__global__ __launch_bounds__(256) void k_star_join_fwd(float* act, int ld, int h_col, int a_col, int top_col, int n, int rows_pad) {
-    const int i = blockIdx.x * 256 + threadIdx.x, n4 = n / 4;
-    if (i >= rows_pad * n4) return;
-    float* row = act + (size_t)(i / n4) * ld;
-    const int c = 4 * (i % n4);
-    const f32x4 h = *reinterpret_cast<const f32x4*>(row + h_col + c), av = *reinterpret_cast<const f32x4*>(row + a_col + c);
-    f32x4 y;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) y[k] = __fadd_rn(h[k], av[k]);
-    *reinterpret_cast<f32x4*>(row + top_col + c) = y;
-}
-__global__ __launch_bounds__(256) void k_star_join_bwd(const float* act, float* dact, int ld, int h_col, int a_col, int top_col, int n,
-                                                       int rows_pad) {
-    const int i = blockIdx.x * 256 + threadIdx.x, n4 = n / 4;
-    if (i >= rows_pad * n4) return;
-    const size_t ro = (size_t)(i / n4) * ld;
-    const int c = 4 * (i % n4);
-    const f32x4 h = *reinterpret_cast<const f32x4*>(act + ro + h_col + c), av = *reinterpret_cast<const f32x4*>(act + ro + a_col + c);
-    const f32x4 dt = *reinterpret_cast<const f32x4*>(dact + ro + top_col + c);
-    f32x4 dh, da;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        dh[k] = h[k] > 0.f ? dt[k] : 0.f;
-        da[k] = av[k] > 0.f ? dt[k] : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(dact + ro + h_col + c) = dh;
-    *reinterpret_cast<f32x4*>(dact + ro + a_col + c) = da;
 }
 
 // ------------------------------------------------------------------ host side: structure of the tower
@@ -2126,6 +476,16 @@ void queue_wgrad(mamdr_graph* g, const float* A, int lda, const float* B, int ld
     }
     g->wq.push_back(mamdr_graph::WProb{A, lda, B, ldb, out, M, N, rows, dz, db});
 }
+// a weight gradient launched on its own: the ways its batch rows are split -- doubled while the grid stays under 256 workgroups,
+// a split keeps a whole number (at least 4) of staged tiles and the partial products (`floats` per split) fit the workspace
+int pick_split(const mamdr_graph* g, int tiles, int rows, size_t floats) {
+    const int nkt = rows / GK;
+    int split = 1;
+    while (split < 16 && tiles * split < 256 && nkt % (2 * split) == 0 && nkt / (2 * split) >= 4 &&
+           (size_t)(2 * split) * floats <= g->wpart_floats)
+        split *= 2;
+    return split;
+}
 // weight gradient out[M x N] = A^T B over `rows` rows (+ db = column sums of dz): queued, or a pair of launches right here
 void launch_wgrad(mamdr_graph* g, const float* A, int lda, const float* B, int ldb, float* out, int M, int N, int rows,
                   const float* dz, float* db) {
@@ -2133,11 +493,7 @@ void launch_wgrad(mamdr_graph* g, const float* A, int lda, const float* B, int l
         queue_wgrad(g, A, lda, B, ldb, out, M, N, rows, dz, db);
         return;
     }
-    const int ty = (M + GT - 1) / GT, tiles = ty * (N / GT), nkt = rows / GK;
-    int split = 1;
-    while (split < 16 && tiles * split < 256 && nkt % (2 * split) == 0 && nkt / (2 * split) >= 4 &&
-           (size_t)(2 * split) * M * N <= g->wpart_floats)
-        split *= 2;
+    const int ty = (M + GT - 1) / GT, split = pick_split(g, ty * (N / GT), rows, (size_t)M * N);
     GemmArgs a = gemm_args(A, lda, B, ldb, split > 1 ? g->wpart : out, N, rows / split);
     a.zstride = (size_t)M * N;
     a.m_rows = M;
@@ -2217,6 +573,12 @@ void dnn_backward(mamdr_graph* g, const DnnOps& d, const int* cols, int in_col, 
 
 // ---- a group of DNNs of ONE shape on ONE input (the experts a task mixes), layer by layer in single launches.  The
 // members' operands are offsets (GroupTab) from the workspaces' and the flat vector's bases; cols[e] = member e's columns
+GroupTab group_tab(int n) {      // n members, every offset zero
+    GroupTab t;
+    memset(&t, 0, sizeof(t));
+    t.n = n;
+    return t;
+}
 bool same_shape(const mamdr_graph* g, const std::vector<int>& ids) {
     if (ids.size() < 2 || ids.size() > (size_t)MAX_GROUP) return false;
     const Dnn& d0 = g->dnns[ids[0]];
@@ -2234,9 +596,7 @@ void dnn_forward_group(mamdr_graph* g, const std::vector<int>& ids, const std::v
     for (size_t l = 0; l < d0.layers.size(); ++l) {
         const Layer& L0 = d0.layers[l];
         const GemmArgs a = fwd_args(g, LayerOps{g->params, g->params, nullptr, nullptr, L0.in, L0.out, 0}, 0, 0, sc);
-        GroupTab t;
-        memset(&t, 0, sizeof(t));
-        t.n = n;
+        GroupTab t = group_tab(n);
         for (int e = 0; e < n; ++e) {
             const Layer& L = g->dnns[ids[e]].layers[l];
             t.a_off[e] = l == 0 ? in_col : cols[e][l - 1];
@@ -2264,17 +624,10 @@ void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::
                             sc.rp, g->dact + cols[e][l], g->G(L.b_off));
             }
         } else {    // dW_e = in_e^T dz_e, db_e = column sums of dz_e
-            const int tiles = (M / GT) * (N / GT), nkt = sc.rp / GK;
-            int split = 1;
-            while (split < 16 && tiles * n * split < 256 && nkt % (2 * split) == 0 && nkt / (2 * split) >= 4 &&
-                   (size_t)(2 * split) * n * M * N <= g->wpart_floats)
-                split *= 2;
+            const int split = pick_split(g, (M / GT) * (N / GT) * n, sc.rp, (size_t)n * M * N);
             GemmArgs a = gemm_args(g->act, g->ld, g->dact, g->ld, split > 1 ? g->wpart : g->grad, N, sc.rp / split);
             a.zstride = (size_t)M * N;
-            GroupTab t, f;
-            memset(&t, 0, sizeof(t));
-            memset(&f, 0, sizeof(f));
-            t.n = f.n = n;
+            GroupTab t = group_tab(n), f = group_tab(n);
             t.tiles_y = M / GT;
             for (int e = 0; e < n; ++e) {
                 const Layer& L = g->dnns[ids[e]].layers[l];
@@ -2291,9 +644,7 @@ void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::
             GLAUNCH(k_graph_wfinish_group, dim3(nb_red + nb_cs, n), dim3(256), 0, g->stream, g->wpart, split,
                                a.zstride, n4, g->grad, nb_red, g->dact, g->ld, sc.rp, g->grad, N, f);
         }
-        GroupTab t;
-        memset(&t, 0, sizeof(t));
-        t.n = n;
+        GroupTab t = group_tab(n);
         if (l > 0) {    // d in_e = dz_e W_e^T through the producer's relu / dropout gate
             const GemmArgs a = din_args(g, 0, N, g->params, 0, 0, false, sc);
             for (int e = 0; e < n; ++e) {
@@ -2312,23 +663,17 @@ void dnn_backward_group(mamdr_graph* g, const std::vector<int>& ids, const std::
             t.a_off[e] = cols[e][0];
             t.b_off[e] = g->dnns[ids[e]].layers[0].w_off;
         }
+        // every member's product as a launch-mate of the others (n x the tiles), summed in member order.  The products fit
+        // dxpart: the one caller (gated_backward) hands over dx_first() / dx_n(), so nn = XDIM with trainable tables (the experts
+        // read x: in = XDIM) and EMB without, n <= the largest mix and sc.rp <= rows_pad_max -- alloc_workspace's very product
         const size_t stride = (size_t)sc.rp * nn;
-        if ((size_t)n * stride <= g->dxpart_floats) {
-            // every member's product as a launch-mate of the others (n x the tiles), summed in member order
-            a.C = g->dxpart;
-            a.ldc = nn;
-            for (int e = 0; e < n; ++e) t.c_off[e] = (int64_t)e * stride;
-            launch_gemm_group<1>(g, a, t, nn, sc);
-            const int64_t tot = (int64_t)sc.rp * (nn / 4);
-            GLAUNCH(k_graph_dx_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, g->stream, g->dxpart, n,
-                               stride, sc.rp, nn / 4, g->dact + in_col + first, g->ld, din_acc ? 1 : 0);
-        } else {    // one contraction whose reduction index runs through all members
-            a.accumulate = din_acc ? 1 : 0;
-            if (use_tile32(sc.rp, nn))
-                GLAUNCH(k_graph_gemm32_kcat, dim3(nn / T32, sc.rp / T32), dim3(256), 0, g->stream, a, t);
-            else
-                GLAUNCH(k_graph_gemm_kcat, dim3(nn / GT, sc.rp / GT), dim3(256), 0, g->stream, a, t);
-        }
+        a.C = g->dxpart;
+        a.ldc = nn;
+        for (int e = 0; e < n; ++e) t.c_off[e] = (int64_t)e * stride;
+        launch_gemm_group<1>(g, a, t, nn, sc);
+        const int64_t tot = (int64_t)sc.rp * (nn / 4);
+        GLAUNCH(k_graph_dx_reduce, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, g->stream, g->dxpart, n, stride, sc.rp,
+                nn / 4, g->dact + in_col + first, g->ld, din_acc ? 1 : 0);
     }
 }
 

@@ -14,7 +14,8 @@
 //                 workgroup, is the unit of work: every wave holds the whole tile in registers -- lane l the 16 consecutive
 //                 positions 16 l .. 16 l + 15: the unit id gathered through the row, and three 16-bit masks (valid, positive,
 //                 starts a run of equal keys) -- and takes 4 of the group's replicates in turn.  No LDS, no barrier: the scans
-//                 over the tile are a serial walk over a lane's 16 positions and wave-64 shuffles across the lanes.  Per
+//                 over the tile are a serial walk over a lane's 16 positions and wave-64 shuffles across the lanes
+//                 (wave_reduce / wave_scan over AddU32 and MaxU32, eval_device.h).  Per
 //                 (replicate, tile) it writes the tile's negative weight, positive weight, and `head`: 0 when no run starts
 //                 in the tile, else 1 + the negative weight in front of the LAST run start of the tile.
 //   k_boot_carry  one wave per replicate walks the tiles 64 at a time: the exclusive sum of the negative weights gives tile
@@ -28,16 +29,12 @@
 //   chunks through the same buffers (a chunk is a multiple of BOOT_GROUP and at least one group).
 //
 // Determinism: integers only.  Integer atomics commute, every other value has one writer.  No floating-point instruction.
-#include "mamdr_kernels.h"
-#include "../../include/mamdr_hip.h"
+#include "eval_device.h"
+#include "host_common.h"
 
 namespace mamdr {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
 constexpr int ITEMS = BOOT_TILE / 64;                  // positions per lane
 constexpr int REPS = BOOT_GROUP / WAVES;               // replicates per wave
 static_assert(ITEMS == 16, "the masks of a lane are 16 bits");
@@ -110,37 +107,15 @@ __device__ __forceinline__ void boot_weights(const BootTile& t, u64 seed, int b,
     }
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return __shfl(v, 0);
-}
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t x = __shfl_down(v, o);
-        v = x > v ? x : v;
-    }
-    return __shfl(v, 0);
+// the wave's sum / maximum, in every lane (wave_reduce, wave_scan: eval_device.h)
+template <class Op>
+__device__ __forceinline__ uint32_t wave_all(uint32_t v) {
+    return __shfl(wave_reduce<Op>(v), 0);
 }
 // what lies in front of this lane's value
-__device__ __forceinline__ uint32_t wave_excl_add(uint32_t v, int lane) {
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    return inc - v;
-}
+__device__ __forceinline__ uint32_t wave_excl_add(uint32_t v, int lane) { return wave_scan<AddU32>(v, lane) - v; }
 __device__ __forceinline__ uint32_t wave_excl_max(uint32_t v, int lane) {
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(inc, o);
-        if (lane >= o && up > inc) inc = up;
-    }
-    const uint32_t before = __shfl_up(inc, 1);
+    const uint32_t before = __shfl_up(wave_scan<MaxU32>(v, lane), 1);
     return lane == 0 ? 0u : before;
 }
 
@@ -151,7 +126,7 @@ __global__ __launch_bounds__(THREADS) void k_boot_parts(const BootPass p) {
     boot_load(p, tile, lane, t);
     // the tile's last run start, as 1 + its position in the tile (0: none), and the lane's positions in front of it
     const uint32_t mine = t.head ? (uint32_t)(lane * ITEMS + (31 - __clz((int)t.head)) + 1) : 0u;
-    const uint32_t last = wave_max(mine);
+    const uint32_t last = wave_all<MaxU32>(mine);
     uint32_t front = 0u;
 #pragma unroll
     for (int j = 0; j < ITEMS; ++j) front |= ((uint32_t)(lane * ITEMS + j + 1) < last ? 1u : 0u) << j;
@@ -168,9 +143,9 @@ __global__ __launch_bounds__(THREADS) void k_boot_parts(const BootPass p) {
             sn += positive ? 0u : wt[j];
             sf += (!positive && ((front >> j) & 1u)) ? wt[j] : 0u;
         }
-        sn = wave_sum(sn);
-        sp = wave_sum(sp);
-        sf = wave_sum(sf);
+        sn = wave_all<AddU32>(sn);
+        sp = wave_all<AddU32>(sp);
+        sf = wave_all<AddU32>(sf);
         if (lane == 0) {
             const int64_t at = (int64_t)slot * p.n_tiles + tile;
             p.part_n[at] = sn;
@@ -199,9 +174,9 @@ __global__ __launch_bounds__(THREADS) void k_boot_carry(const BootPass p) {
             part_n[t] = cn;
             part_h[t] = before > head ? before : head;
         }
-        carry += wave_sum(wn);
-        positives += wave_sum(wp);
-        const uint32_t m = wave_max(at_head);
+        carry += wave_all<AddU32>(wn);
+        positives += wave_all<AddU32>(wp);
+        const uint32_t m = wave_all<MaxU32>(at_head);
         head = m > head ? m : head;
     }
     if (lane == 0) {
@@ -242,14 +217,30 @@ __global__ __launch_bounds__(THREADS) void k_boot_T(const BootPass p) {
             if (positive) sum += (u64)wt[j] * ((u64)cn_rs + (u64)cn);
             cn += positive ? 0u : wt[j];
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+        sum = wave_reduce<AddU64>(sum);
         if (lane == 0 && sum) atomicAdd(p.T + p.first + slot, sum);
     }
 }
 
 int64_t boot_tiles(int64_t n) { return (n + BOOT_TILE - 1) / BOOT_TILE; }
-size_t align16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// the call's workspace behind the sort's: the three partials of one chunk of replicates
+struct BootLayout {
+    int chunk;
+    size_t part_n, part_p, part_h, bytes;
+};
+BootLayout boot_layout(int64_t n, int n_rep, int64_t part_words) {
+    BootLayout l;
+    l.chunk = boot_chunk(n, n_rep, part_words);
+    const size_t part = (size_t)l.chunk * boot_tiles(n) * sizeof(uint32_t);
+    WsCursor ws;
+    ws.take(exact_sort_workspace_bytes(n));          // the sort's part leads
+    l.part_n = ws.take(part);
+    l.part_p = ws.take(part);
+    l.part_h = ws.take(part);
+    l.bytes = ws.at;
+    return l;
+}
 
 }  // namespace
 
@@ -260,10 +251,7 @@ int boot_chunk(int64_t n, int n_rep, int64_t part_words) {
     return (int)(fit < all ? fit : all);
 }
 
-size_t boot_workspace_bytes(int64_t n, int n_rep, int64_t part_words) {
-    const size_t part = align16((size_t)boot_chunk(n, n_rep, part_words) * boot_tiles(n) * sizeof(uint32_t));
-    return align16(exact_sort_workspace_bytes(n)) + 3 * part;
-}
+size_t boot_workspace_bytes(int64_t n, int n_rep, int64_t part_words) { return boot_layout(n, n_rep, part_words).bytes; }
 
 void launch_boot(const BootArgs& a, hipStream_t s) {
     ExactSortArgs sort;
@@ -279,12 +267,11 @@ void launch_boot(const BootArgs& a, hipStream_t s) {
     p.n = a.n;
     p.n_tiles = boot_tiles(a.n);
     p.seed = a.seed;
-    const int chunk = boot_chunk(a.n, a.n_rep, a.part_words);
-    const size_t part = align16((size_t)chunk * p.n_tiles * sizeof(uint32_t));
-    char* parts = a.ws + align16(exact_sort_workspace_bytes(a.n));
-    p.part_n = reinterpret_cast<uint32_t*>(parts);
-    p.part_p = reinterpret_cast<uint32_t*>(parts + part);
-    p.part_h = reinterpret_cast<uint32_t*>(parts + 2 * part);
+    const BootLayout l = boot_layout(a.n, a.n_rep, a.part_words);
+    const int chunk = l.chunk;
+    p.part_n = reinterpret_cast<uint32_t*>(a.ws + l.part_n);
+    p.part_p = reinterpret_cast<uint32_t*>(a.ws + l.part_p);
+    p.part_h = reinterpret_cast<uint32_t*>(a.ws + l.part_h);
     p.T = a.T;
     p.P = a.P;
     p.N = a.N;

@@ -16,9 +16,8 @@
 //            The same five passes sort mamdr_auc_bootstrap's wider word, key << 32 | positive << 31 | row, on its upper
 //            33 bits (launch_exact_sort with `rows`: every digit sits 31 bits higher, pass 0 forms that word).  The sort is
 //            stable and starts from file order, so the rows ascend inside equal (key, positive) pairs.
-//   scan     the device-wide scans are the three-launch form -- k_scan_sums (tile totals), the scan of the totals (the
-//            same two kernels again while they do not fit one tile), k_scan_apply (exclusive scan in place with the tile's
-//            carry) -- over a combine operator: AddU32 for the histograms, RunOp for the sorted array.
+//   scan     the device-wide scans are eval_device.h's three-launch scan_exclusive<Op, EXACT_SCAN_TILE> over a combine
+//            operator: AddU32 for the histograms, RunOp for the sorted array.
 //   RunOp    element i of the sorted array is (positive_i, i if i starts a run of equal keys else 0, i if i starts a run of
 //            equal composites else 0), combined as (sum, max, max): its scan yields cp(i), rs(i) and cs(i), the first
 //            position of i's composite.  For a positive i the positives of its run below it are i - cs(i), so
@@ -34,23 +33,19 @@
 //
 // Determinism: every integer is exact and integer atomics commute.  The AP term of a position is one division of two
 // integers converted to fp64; the sum has ONE order per n -- thread t of tile b adds positions 1024 b + 4 t + j for j = 0 .. 3
-// in turn, lanes by a shuffle-down tree, waves 0 .. 3 in turn, then thread t of k_exact_finish adds tiles t + 256 i in turn
-// and the same tree -- so it is the same bits from run to run and, since the sorted array is unique, under any permutation
-// of the rows.  No floating-point atomics.  Compiled with -ffp-contract=off.
-#include "mamdr_kernels.h"
+// in turn, then block_sum's tree (eval_device.h), then thread t of k_exact_finish adds tiles t + 256 i in turn and the same
+// tree -- so it is the same bits from run to run and, since the sorted array is unique, under any permutation of the rows.
+// No floating-point atomics.  Compiled with -ffp-contract=off.
+#include "eval_device.h"
+#include "host_common.h"
 
 namespace mamdr {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
 constexpr int RADIX = 1 << EXACT_RADIX_BITS;
 constexpr int PASSES = (33 + EXACT_RADIX_BITS - 1) / EXACT_RADIX_BITS;
 constexpr int SORT_ITEMS = EXACT_SORT_TILE / THREADS;          // composites per thread, in registers
 constexpr int SORT_ROUNDS = EXACT_SORT_TILE / WAVES / 64;      // rounds of 64 per wave
-constexpr int SCAN_ITEMS = EXACT_SCAN_TILE / THREADS;
 constexpr int METRIC_ITEMS = EXACT_METRIC_TILE / THREADS;
 constexpr int SLOTS = EXACT_METRIC_TILE + 2;                   // LDS bin slots of k_exact_metrics
 static_assert(RADIX == THREADS, "thread d owns digit d");
@@ -139,112 +134,6 @@ __global__ __launch_bounds__(THREADS) void k_exact_scatter(const SortPass p) {
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------------- scan
-struct AddU32 {
-    typedef uint32_t T;
-    static __device__ __forceinline__ T identity() { return 0u; }
-    static __device__ __forceinline__ T combine(T a, T b) { return a + b; }
-    static __device__ __forceinline__ T shfl_up(T v, int o) { return __shfl_up(v, o); }
-    static __device__ __forceinline__ T shfl_down(T v, int o) { return __shfl_down(v, o); }
-};
-
-struct ExactRun {
-    uint32_t cp, rs, cs;         // positives; last start of a run of equal keys; last start of a run of equal composites
-};
-struct RunOp {
-    typedef ExactRun T;
-    static __device__ __forceinline__ T identity() { return T{0u, 0u, 0u}; }
-    static __device__ __forceinline__ T combine(T a, T b) { return T{a.cp + b.cp, a.rs > b.rs ? a.rs : b.rs, a.cs > b.cs ? a.cs : b.cs}; }
-    static __device__ __forceinline__ T shfl_up(T v, int o) { return T{__shfl_up(v.cp, o), __shfl_up(v.rs, o), __shfl_up(v.cs, o)}; }
-};
-
-// exclusive scan of one value per thread over the workgroup (lanes by shuffles, the four waves through LDS) -> what lies
-// before this thread's value; `total` is the whole workgroup's.  Ends behind a barrier: `lds` may be reused at once
-template <class Op>
-__device__ __forceinline__ typename Op::T block_scan(typename Op::T v, typename Op::T* lds, typename Op::T& total) {
-    typedef typename Op::T T;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = Op::shfl_up(inc, o);
-        if (lane >= o) inc = Op::combine(up, inc);
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    T before = Op::identity();
-    total = Op::identity();
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) {
-        const T s = lds[i];
-        if (i < w) before = Op::combine(before, s);
-        total = Op::combine(total, s);
-    }
-    __syncthreads();
-    T excl = Op::shfl_up(inc, 1);
-    if (lane == 0) excl = Op::identity();
-    return Op::combine(before, excl);
-}
-
-template <class Op>
-__global__ __launch_bounds__(THREADS) void k_scan_sums(const typename Op::T* in, typename Op::T* sums, int64_t len) {
-    typedef typename Op::T T;
-    __shared__ T lds[WAVES];
-    const int64_t first = (int64_t)blockIdx.x * EXACT_SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    T v = Op::identity();
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j)
-        if (first + j < len) v = Op::combine(v, in[first + j]);
-    T total;
-    block_scan<Op>(v, lds, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// exclusive scan in place; carry (nullable: a single tile) holds what lies before every tile
-template <class Op>
-__global__ __launch_bounds__(THREADS) void k_scan_apply(typename Op::T* data, const typename Op::T* carry, int64_t len) {
-    typedef typename Op::T T;
-    __shared__ T lds[WAVES];
-    const int64_t first = (int64_t)blockIdx.x * EXACT_SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    T item[SCAN_ITEMS];
-    T v = Op::identity();
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-        item[j] = first + j < len ? data[first + j] : Op::identity();
-        v = Op::combine(v, item[j]);
-    }
-    T total;
-    T running = block_scan<Op>(v, lds, total);
-    if (carry) running = Op::combine(carry[blockIdx.x], running);
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-        if (first + j < len) data[first + j] = running;
-        running = Op::combine(running, item[j]);
-    }
-}
-
-// elements of the workspace the levels above `len` need: the tile totals of every level
-int64_t scan_work(int64_t len) {
-    int64_t total = 0;
-    while (len > EXACT_SCAN_TILE) {
-        len = (len + EXACT_SCAN_TILE - 1) / EXACT_SCAN_TILE;
-        total += len;
-    }
-    return total;
-}
-
-template <class Op>
-void scan_exclusive(typename Op::T* data, int64_t len, typename Op::T* work, hipStream_t s) {
-    if (len <= EXACT_SCAN_TILE) {
-        MAMDR_LAUNCH(k_scan_apply<Op>, dim3(1), dim3(THREADS), 0, s, data, (const typename Op::T*)nullptr, len);
-        return;
-    }
-    const int64_t tiles = (len + EXACT_SCAN_TILE - 1) / EXACT_SCAN_TILE;
-    MAMDR_LAUNCH(k_scan_sums<Op>, dim3((unsigned)tiles), dim3(THREADS), 0, s, (const typename Op::T*)data, work, len);
-    scan_exclusive<Op>(work, tiles, work + tiles, s);
-    MAMDR_LAUNCH(k_scan_apply<Op>, dim3((unsigned)tiles), dim3(THREADS), 0, s, data, (const typename Op::T*)work, len);
-}
-
 // ------------------------------------------------------------------------------------------------------------- metrics
 struct MetricPass {
     const u64* sorted;           // [n]
@@ -317,32 +206,20 @@ __device__ __forceinline__ void bin_flush(const BinAcc& b, BinSlots& lds, const 
     }
 }
 
-// fixed tree over one workgroup: lanes by shuffle-down, then waves 0 .. 3 in turn; the result is thread 0's
-struct ExactSum {
+struct ExactSum {                // (block_sum, eval_device.h)
     double ap;
     u64 T;
     uint32_t runs, nan;
+    __device__ __forceinline__ void add(const ExactSum& o) {
+        ap += o.ap;
+        T += o.T;
+        runs += o.runs;
+        nan += o.nan;
+    }
+    __device__ __forceinline__ ExactSum down(int o) const {
+        return ExactSum{__shfl_down(ap, o), __shfl_down(T, o), __shfl_down(runs, o), __shfl_down(nan, o)};
+    }
 };
-__device__ __forceinline__ ExactSum exact_block_sum(ExactSum v, ExactSum* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        v.ap += __shfl_down(v.ap, o);
-        v.T += __shfl_down(v.T, o);
-        v.runs += __shfl_down(v.runs, o);
-        v.nan += __shfl_down(v.nan, o);
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    ExactSum s = lds[0];
-#pragma unroll
-    for (int i = 1; i < WAVES; ++i) {
-        s.ap += lds[i].ap;
-        s.T += lds[i].T;
-        s.runs += lds[i].runs;
-        s.nan += lds[i].nan;
-    }
-    return s;
-}
 
 __global__ __launch_bounds__(THREADS) void k_exact_metrics(const MetricPass m) {
     __shared__ ExactRun lds_run[WAVES];
@@ -417,18 +294,15 @@ __global__ __launch_bounds__(THREADS) void k_exact_metrics(const MetricPass m) {
             pend.bin = bin0;
         }
         if (__all(pend.slot == slot0 && pend.bin == bin0)) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                pend.rows += __shfl_down(pend.rows, o);
-                pend.positives += __shfl_down(pend.positives, o);
-                pend.sum += __shfl_down(pend.sum, o);
-            }
+            pend.rows = wave_reduce<AddU32>(pend.rows);
+            pend.positives = wave_reduce<AddU32>(pend.positives);
+            pend.sum = wave_reduce<AddU64>(pend.sum);
             if ((tid & 63) == 0) bin_flush(pend, slots, m);
         } else {
             bin_flush(pend, slots, m);
         }
     }
-    const ExactSum sum = exact_block_sum(acc, lds_sum);          // (its barrier: every slot add has landed)
+    const ExactSum sum = block_sum(acc, lds_sum);          // (its barrier: every slot add has landed)
     if (tid == 0) {
         m.ap_part[blockIdx.x] = sum.ap;
         atomicAdd(m.counts + 0, sum.T);
@@ -450,7 +324,7 @@ __global__ __launch_bounds__(THREADS) void k_exact_finish(const MetricPass m) {
     __shared__ ExactSum lds[WAVES];
     ExactSum v = {0.0, 0ull, 0u, 0u};
     for (int64_t b = threadIdx.x; b < m.n_tiles; b += THREADS) v.ap += m.ap_part[b];
-    const ExactSum s = exact_block_sum(v, lds);
+    const ExactSum s = block_sum(v, lds);
     if (threadIdx.x == 0) {
         m.ap[0] = s.ap;
         m.counts[2] = (u64)m.n - m.counts[1];
@@ -467,21 +341,16 @@ ExactLayout exact_layout(int64_t n) {
     ExactLayout l;
     l.sort_tiles = (n + EXACT_SORT_TILE - 1) / EXACT_SORT_TILE;
     l.metric_tiles = (n + EXACT_METRIC_TILE - 1) / EXACT_METRIC_TILE;
-    size_t at = 0;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 15) & ~(size_t)15;
-        return here;
-    };
-    l.buf_a = take((size_t)n * sizeof(u64));
-    l.buf_b = take((size_t)n * sizeof(u64));
-    l.hist = take((size_t)RADIX * l.sort_tiles * sizeof(uint32_t));
-    l.hist_work = take((size_t)scan_work((int64_t)RADIX * l.sort_tiles) * sizeof(uint32_t));
-    l.sort_bytes = at;
-    l.runs = take((size_t)l.metric_tiles * sizeof(ExactRun));
-    l.runs_work = take((size_t)scan_work(l.metric_tiles) * sizeof(ExactRun));
-    l.ap_part = take((size_t)l.metric_tiles * sizeof(double));
-    l.bytes = at;
+    WsCursor ws;
+    l.buf_a = ws.take((size_t)n * sizeof(u64));
+    l.buf_b = ws.take((size_t)n * sizeof(u64));
+    l.hist = ws.take((size_t)RADIX * l.sort_tiles * sizeof(uint32_t));
+    l.hist_work = ws.take((size_t)scan_work((int64_t)RADIX * l.sort_tiles, EXACT_SCAN_TILE) * sizeof(uint32_t));
+    l.sort_bytes = ws.at;
+    l.runs = ws.take((size_t)l.metric_tiles * sizeof(ExactRun));
+    l.runs_work = ws.take((size_t)scan_work(l.metric_tiles, EXACT_SCAN_TILE) * sizeof(ExactRun));
+    l.ap_part = ws.take((size_t)l.metric_tiles * sizeof(double));
+    l.bytes = ws.at;
     return l;
 }
 
@@ -508,7 +377,7 @@ const unsigned long long* launch_exact_sort(const ExactSortArgs& a, hipStream_t 
         if (pass == PASSES - 1 && a.sorted_out) p.dst = a.sorted_out;
         p.shift = (a.rows ? 31 : 0) + pass * EXACT_RADIX_BITS;
         MAMDR_LAUNCH(k_exact_hist, dim3((unsigned)l.sort_tiles), dim3(THREADS), 0, s, p);
-        scan_exclusive<AddU32>(p.hist, (int64_t)RADIX * l.sort_tiles, reinterpret_cast<uint32_t*>(a.ws + l.hist_work), s);
+        scan_exclusive<AddU32, EXACT_SCAN_TILE>(p.hist, (int64_t)RADIX * l.sort_tiles, reinterpret_cast<uint32_t*>(a.ws + l.hist_work), s);
         MAMDR_LAUNCH(k_exact_scatter, dim3((unsigned)l.sort_tiles), dim3(THREADS), 0, s, p);
         sorted = p.dst;
     }
@@ -536,7 +405,7 @@ void launch_exact(const ExactArgs& a, hipStream_t s) {
     m.ap = a.ap;
     m.bins = a.bins;
     MAMDR_LAUNCH(k_exact_runs, dim3((unsigned)l.metric_tiles), dim3(THREADS), 0, s, m);
-    scan_exclusive<RunOp>(m.runs, l.metric_tiles, reinterpret_cast<ExactRun*>(a.ws + l.runs_work), s);
+    scan_exclusive<RunOp, EXACT_SCAN_TILE>(m.runs, l.metric_tiles, reinterpret_cast<ExactRun*>(a.ws + l.runs_work), s);
     MAMDR_LAUNCH(k_exact_metrics, dim3((unsigned)l.metric_tiles), dim3(THREADS), 0, s, m);
     MAMDR_LAUNCH(k_exact_finish, dim3(1), dim3(THREADS), 0, s, m);
 }

@@ -26,20 +26,18 @@
 //   k_gauc_finish   one workgroup adds the blocks' partials by the same tree and writes the four results.
 //
 // Determinism: T_u and P_u are integers (integer atomics commute); the fp64 sum has ONE order per G -- thread t of block
-// b adds groups 2048 b + t + 256 i for i = 0 .. 7 in turn, lanes by a shuffle-down tree, waves 0 .. 3 in turn, blocks
-// likewise -- so the scalar is the same bits from run to run, and, since T_u, P_u and r_u do not depend on where a
-// group's rows sit in the file or in `order`, under any row permutation.  No floating-point atomics.  This unit is
-// compiled with -ffp-contract=off: the term is one division, one multiplication and then additions, as the host
-// definition (mamdr_amd/gauc.py) computes it.
-#include "mamdr_kernels.h"
+// b adds groups 2048 b + t + 256 i for i = 0 .. 7 in turn, then block_sum's tree (eval_device.h); thread t of the finish
+// adds blocks t + 256 i in turn and the same tree -- so the scalar is the same bits from run to run, and, since T_u, P_u
+// and r_u do not depend on where a group's rows sit in the file or in `order`, under any row permutation.  No
+// floating-point atomics.  This unit is compiled with -ffp-contract=off: the term is one division, one multiplication and
+// then additions, as the host definition (mamdr_amd/gauc.py) computes it.
+#include "eval_device.h"
 
 namespace mamdr {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int GAUC_THREADS = 256;
-constexpr int GAUC_WAVES = GAUC_THREADS / 64;
+constexpr int GAUC_THREADS = THREADS;
+constexpr int GAUC_WAVES = WAVES;
 constexpr int TERMS_PER_THREAD = 8;
 constexpr int TERMS_PER_BLOCK = GAUC_THREADS * TERMS_PER_THREAD;       // 2,048 groups per block of k_gauc_terms
 static_assert(GAUC_TILE == GAUC_THREADS, "one thread per tile position");
@@ -113,10 +111,10 @@ __global__ __launch_bounds__(GAUC_THREADS) void k_gauc_tiles(const GaucArgs a) {
             }
         }
     }
-    u64 t = counts ? (u64)above + (u64)not_below : 0ull;
-    uint32_t pcount = (uint32_t)__popcll(__ballot(counts));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o);
+    // integers: any order gives the same sums.  Not block_sum: the positives of a wave are one popcount, and a (u64, uint32)
+    // struct per wave would pad the LDS parts from 48 to 64 bytes
+    const u64 t = wave_reduce<AddU64>(counts ? (u64)above + (u64)not_below : 0ull);
+    const uint32_t pcount = (uint32_t)__popcll(__ballot(counts));
     if (lane == 0) {
         part_t[w] = t;
         part_p[w] = pcount;
@@ -135,29 +133,16 @@ __global__ __launch_bounds__(GAUC_THREADS) void k_gauc_tiles(const GaucArgs a) {
     }
 }
 
-// fixed tree over one workgroup: lanes by shuffle-down, then waves 0 .. 3 in turn; the result is thread 0's
-struct GaucSum {
+struct GaucSum {                 // (block_sum, eval_device.h)
     double num;
     u64 rows, valid;
+    __device__ __forceinline__ void add(const GaucSum& o) {
+        num += o.num;
+        rows += o.rows;
+        valid += o.valid;
+    }
+    __device__ __forceinline__ GaucSum down(int o) const { return GaucSum{__shfl_down(num, o), __shfl_down(rows, o), __shfl_down(valid, o)}; }
 };
-__device__ __forceinline__ GaucSum gauc_block_sum(GaucSum v, GaucSum* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        v.num += __shfl_down(v.num, o);
-        v.rows += __shfl_down(v.rows, o);
-        v.valid += __shfl_down(v.valid, o);
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    GaucSum s = lds[0];
-#pragma unroll
-    for (int i = 1; i < GAUC_WAVES; ++i) {
-        s.num += lds[i].num;
-        s.rows += lds[i].rows;
-        s.valid += lds[i].valid;
-    }
-    return s;
-}
 
 __global__ __launch_bounds__(GAUC_THREADS) void k_gauc_terms(const GaucArgs a) {
     __shared__ GaucSum lds[GAUC_WAVES];
@@ -174,7 +159,7 @@ __global__ __launch_bounds__(GAUC_THREADS) void k_gauc_terms(const GaucArgs a) {
         v.rows += r;
         v.valid += 1ull;
     }
-    const GaucSum s = gauc_block_sum(v, lds);
+    const GaucSum s = block_sum(v, lds);
     if (threadIdx.x == 0) {
         a.part_num[blockIdx.x] = s.num;
         a.part_rows[blockIdx.x] = s.rows;
@@ -190,7 +175,7 @@ __global__ __launch_bounds__(GAUC_THREADS) void k_gauc_finish(const GaucArgs a) 
         v.rows += a.part_rows[b];
         v.valid += a.part_valid[b];
     }
-    const GaucSum s = gauc_block_sum(v, lds);
+    const GaucSum s = block_sum(v, lds);
     if (threadIdx.x == 0) {
         a.result[0] = s.num;
         a.result[1] = (double)s.rows;

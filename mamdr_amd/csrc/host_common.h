@@ -1,7 +1,8 @@
 // Host-side pieces the two engines share (the step kernels' C ABI in mamdr_api.hip and its sibling files, the
 // generic-layer engine in graph_engine.hip): the bound data columns, the error buffer behind *_last_error, the record of a
 // context's device allocations, the two host-computed tables (AUC thresholds, TF's running beta powers) and the argument
-// checks both C-ABI front ends make with the same texts.  Host code only: nothing here is for a kernel file.
+// checks both C-ABI front ends make with the same texts; and WsCursor, with which the launchers of the evaluation kernel
+// files (exact, isotonic, bootstrap) lay out a call's workspace.  Host code only: nothing here runs in a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,17 @@ struct DevAllocs {
     void free_all() {
         for (void* p : ptrs) (void)hipFree(p);
         ptrs.clear();
+    }
+};
+
+// carves one workspace allocation into parts: take(bytes) is where the part starts, `at` the bytes used so far.  Every part
+// starts 16-byte aligned (given an aligned base and start)
+struct WsCursor {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t here = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return here;
     }
 };
 

@@ -14,8 +14,7 @@
 // kernel needs stays on the device, nothing is read back:
 //   sort      launch_exact_sort (exact_kernels.hip): the composites key << 1 | positive, ascending
 //   points    k_iso_run_sums   per tile of 1,024 sorted positions (run heads << 32 | positives)
-//             scan             exclusive, over the tiles (the three-launch form of exact_kernels.hip on 64-bit sums; that
-//                              file's scan is private to it, this one adds 64-bit words only)
+//             scan             exclusive, over the tiles (eval_device.h's scan_exclusive<AddU64, ISO_SCAN_TILE>: 64-bit sums)
 //             k_iso_points     the scan inside the tile from its carry; the head of run j at sorted position i writes
 //                              point j = (i, positives below i); the last position writes point R = (n, P), n_runs, P and
 //                              the number of points; n_nan is the length of the run of key 0
@@ -40,103 +39,18 @@
 //   apply     k_iso_apply      per row the key, a binary search over first_key (staged in LDS up to 4,096 blocks), one
 //                              fp64 division rounded once to fp32, one store
 //   sums      k_score_parts / k_score_finish   fp64, ONE order per n: thread t of tile b adds rows 1024 b + 4 t + j for
-//                              j = 0 .. 3 in turn, lanes by a shuffle-down tree, waves 0 .. 3 in turn; thread t of the
-//                              finish adds tiles t + 256 i in turn and the same tree.  No floating-point atomics.
+//                              j = 0 .. 3 in turn, then block_sum's tree (eval_device.h); thread t of the finish adds
+//                              tiles t + 256 i in turn and the same tree.  No floating-point atomics.
 //                              Compiled with -ffp-contract=off.
-#include "mamdr_kernels.h"
+#include "eval_device.h"
+#include "host_common.h"
 
 namespace mamdr {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / 64;
 constexpr int POINT_ITEMS = ISO_POINT_TILE / THREADS;
-constexpr int SCAN_ITEMS = ISO_SCAN_TILE / THREADS;
 constexpr int APPLY_ITEMS = ISO_APPLY_TILE / THREADS;
 constexpr int SCORE_ITEMS = ISO_SCORE_TILE / THREADS;
-
-// ---------------------------------------------------------------------------------------------------------------- scan
-// exclusive sum of one 64-bit word per thread over the workgroup (lanes by shuffles, the four waves through LDS) -> what
-// lies before this thread's word; `total` is the whole workgroup's.  Ends behind a barrier: `lds` may be reused at once
-__device__ __forceinline__ u64 block_scan(u64 v, u64* lds, u64& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) lds[w] = inc;
-    __syncthreads();
-    u64 before = 0ull;
-    total = 0ull;
-#pragma unroll
-    for (int i = 0; i < WAVES; ++i) {
-        const u64 s = lds[i];
-        if (i < w) before += s;
-        total += s;
-    }
-    __syncthreads();
-    u64 excl = __shfl_up(inc, 1);
-    if (lane == 0) excl = 0ull;
-    return before + excl;
-}
-
-__global__ __launch_bounds__(THREADS) void k_iso_scan_sums(const u64* in, u64* sums, int64_t len) {
-    __shared__ u64 lds[WAVES];
-    const int64_t first = (int64_t)blockIdx.x * ISO_SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    u64 v = 0ull;
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j)
-        if (first + j < len) v += in[first + j];
-    u64 total;
-    block_scan(v, lds, total);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// exclusive scan in place; carry (nullable: a single tile) holds what lies before every tile
-__global__ __launch_bounds__(THREADS) void k_iso_scan_apply(u64* data, const u64* carry, int64_t len) {
-    __shared__ u64 lds[WAVES];
-    const int64_t first = (int64_t)blockIdx.x * ISO_SCAN_TILE + threadIdx.x * SCAN_ITEMS;
-    u64 item[SCAN_ITEMS];
-    u64 v = 0ull;
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-        item[j] = first + j < len ? data[first + j] : 0ull;
-        v += item[j];
-    }
-    u64 total;
-    u64 running = block_scan(v, lds, total);
-    if (carry) running += carry[blockIdx.x];
-#pragma unroll
-    for (int j = 0; j < SCAN_ITEMS; ++j) {
-        if (first + j < len) data[first + j] = running;
-        running += item[j];
-    }
-}
-
-// words of the workspace the levels above `len` need: the tile totals of every level
-int64_t scan_work(int64_t len) {
-    int64_t total = 0;
-    while (len > ISO_SCAN_TILE) {
-        len = (len + ISO_SCAN_TILE - 1) / ISO_SCAN_TILE;
-        total += len;
-    }
-    return total;
-}
-
-void scan_exclusive(u64* data, int64_t len, u64* work, hipStream_t s) {
-    if (len <= ISO_SCAN_TILE) {
-        MAMDR_LAUNCH(k_iso_scan_apply, dim3(1), dim3(THREADS), 0, s, data, (const u64*)nullptr, len);
-        return;
-    }
-    const int64_t tiles = (len + ISO_SCAN_TILE - 1) / ISO_SCAN_TILE;
-    MAMDR_LAUNCH(k_iso_scan_sums, dim3((unsigned)tiles), dim3(THREADS), 0, s, (const u64*)data, work, len);
-    scan_exclusive(work, tiles, work + tiles, s);
-    MAMDR_LAUNCH(k_iso_scan_apply, dim3((unsigned)tiles), dim3(THREADS), 0, s, data, (const u64*)work, len);
-}
 
 // -------------------------------------------------------------------------------------------------------------- points
 struct PointPass {
@@ -167,7 +81,7 @@ __global__ __launch_bounds__(THREADS) void k_iso_run_sums(const PointPass p) {
         prev = c;
     }
     u64 total;
-    block_scan(v, lds, total);
+    block_scan<AddU64>(v, lds, total);
     if (threadIdx.x == 0) p.tile_sum[blockIdx.x] = total;
 }
 
@@ -188,7 +102,7 @@ __global__ __launch_bounds__(THREADS) void k_iso_points(const PointPass p) {
         prev = c;
     }
     u64 total;
-    u64 running = p.tile_sum[blockIdx.x] + block_scan(v, lds, total);       // heads and positives below position `first`
+    u64 running = p.tile_sum[blockIdx.x] + block_scan<AddU64>(v, lds, total);       // heads and positives below position `first`
     const bool nan_first = (p.sorted[0] >> 1) == 0ull;                      // (n > 0) NaN predictions are the lowest run
 #pragma unroll
     for (int j = 0; j < POINT_ITEMS; ++j) {
@@ -323,20 +237,16 @@ IsoLayout iso_layout(int64_t n, int tile) {
     l.point_tiles = (n + ISO_POINT_TILE - 1) / ISO_POINT_TILE;
     l.cap = n + 1;
     l.hull_tiles = (l.cap + tile - 1) / tile;
-    size_t at = (exact_sort_workspace_bytes(n) + 15) & ~(size_t)15;
-    auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += (bytes + 15) & ~(size_t)15;
-        return here;
-    };
-    l.tile_sum = take((size_t)l.point_tiles * sizeof(u64));
-    l.tile_work = take((size_t)scan_work(l.point_tiles) * sizeof(u64));
-    l.pts_a = take((size_t)l.cap * sizeof(u64));
-    l.pts_b = take((size_t)l.cap * sizeof(u64));
-    l.cnt = take((size_t)(l.hull_tiles + 1) * sizeof(u64));
-    l.cnt_work = take((size_t)scan_work(l.hull_tiles + 1) * sizeof(u64));
-    l.m = take((size_t)(ISO_MAX_LEVELS + 1) * sizeof(long long));
-    l.bytes = at;
+    WsCursor ws;
+    ws.take(exact_sort_workspace_bytes(n));          // the sort's part leads
+    l.tile_sum = ws.take((size_t)l.point_tiles * sizeof(u64));
+    l.tile_work = ws.take((size_t)scan_work(l.point_tiles, ISO_SCAN_TILE) * sizeof(u64));
+    l.pts_a = ws.take((size_t)l.cap * sizeof(u64));
+    l.pts_b = ws.take((size_t)l.cap * sizeof(u64));
+    l.cnt = ws.take((size_t)(l.hull_tiles + 1) * sizeof(u64));
+    l.cnt_work = ws.take((size_t)scan_work(l.hull_tiles + 1, ISO_SCAN_TILE) * sizeof(u64));
+    l.m = ws.take((size_t)(ISO_MAX_LEVELS + 1) * sizeof(long long));
+    l.bytes = ws.at;
     return l;
 }
 
@@ -366,26 +276,14 @@ __global__ __launch_bounds__(THREADS) void k_iso_apply(const IsoApplyArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- sums
-struct ScoreSum {
+struct ScoreSum {                // (block_sum, eval_device.h)
     double brier, logloss;
+    __device__ __forceinline__ void add(const ScoreSum& o) {
+        brier += o.brier;
+        logloss += o.logloss;
+    }
+    __device__ __forceinline__ ScoreSum down(int o) const { return ScoreSum{__shfl_down(brier, o), __shfl_down(logloss, o)}; }
 };
-// fixed tree over one workgroup: lanes by shuffle-down, then waves 0 .. 3 in turn; the result is thread 0's
-__device__ __forceinline__ ScoreSum score_block_sum(ScoreSum v, ScoreSum* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        v.brier += __shfl_down(v.brier, o);
-        v.logloss += __shfl_down(v.logloss, o);
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    ScoreSum s = lds[0];
-#pragma unroll
-    for (int i = 1; i < WAVES; ++i) {
-        s.brier += lds[i].brier;
-        s.logloss += lds[i].logloss;
-    }
-    return s;
-}
 
 __global__ __launch_bounds__(THREADS) void k_score_parts(const ScoreArgs a) {
     __shared__ ScoreSum lds[WAVES];
@@ -402,7 +300,7 @@ __global__ __launch_bounds__(THREADS) void k_score_parts(const ScoreArgs a) {
         const double q = p < 1e-7 ? 1e-7 : (p > 1.0 - 1e-7 ? 1.0 - 1e-7 : p);       // (a NaN stays a NaN)
         v.logloss += -log(positive ? q : 1.0 - q);
     }
-    const ScoreSum s = score_block_sum(v, lds);
+    const ScoreSum s = block_sum(v, lds);
     if (threadIdx.x == 0) {
         a.part[2 * (int64_t)blockIdx.x] = s.brier;
         a.part[2 * (int64_t)blockIdx.x + 1] = s.logloss;
@@ -416,7 +314,7 @@ __global__ __launch_bounds__(THREADS) void k_score_finish(const ScoreArgs a, int
         v.brier += a.part[2 * b];
         v.logloss += a.part[2 * b + 1];
     }
-    const ScoreSum s = score_block_sum(v, lds);
+    const ScoreSum s = block_sum(v, lds);
     if (threadIdx.x == 0) {
         a.out[0] = s.brier;
         a.out[1] = s.logloss;
@@ -456,7 +354,7 @@ void launch_iso_fit(const IsoFitArgs& f, hipStream_t s) {
     p.counts = f.counts;
     p.m0 = m;
     MAMDR_LAUNCH(k_iso_run_sums, dim3((unsigned)l.point_tiles), dim3(THREADS), 0, s, p);
-    scan_exclusive(p.tile_sum, l.point_tiles, reinterpret_cast<u64*>(f.ws + l.tile_work), s);
+    scan_exclusive<AddU64, ISO_SCAN_TILE>(p.tile_sum, l.point_tiles, reinterpret_cast<u64*>(f.ws + l.tile_work), s);
     MAMDR_LAUNCH(k_iso_points, dim3((unsigned)l.point_tiles), dim3(THREADS), 0, s, p);
     HullPass h;
     h.src = p.pts;
@@ -470,7 +368,7 @@ void launch_iso_fit(const IsoFitArgs& f, hipStream_t s) {
         h.m_in = m + level;
         h.m_out = m + level + 1;
         MAMDR_LAUNCH(k_iso_tile_chain, dim3((unsigned)((l.hull_tiles + 1 + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, h);
-        scan_exclusive(h.cnt, l.hull_tiles + 1, reinterpret_cast<u64*>(f.ws + l.cnt_work), s);
+        scan_exclusive<AddU64, ISO_SCAN_TILE>(h.cnt, l.hull_tiles + 1, reinterpret_cast<u64*>(f.ws + l.cnt_work), s);
         MAMDR_LAUNCH(k_iso_compact, dim3((unsigned)((l.cap + THREADS - 1) / THREADS)), dim3(THREADS), 0, s, h);
     }
     h.m_in = m + levels;

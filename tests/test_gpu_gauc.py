@@ -7,6 +7,7 @@ terms are within (G - 1) * 2^-53 of the exact sum each.
 
 Shapes: one crafted split of about 6,000 rows -- group sizes 1, 2, 63, 64, 65 (the wave path's edge and the first tiled
 size), 255, 256, 257 (a full tile and its remainders), 513 and 1,100 (three and five tiles) plus 200 groups of 1 .. 30 rows;
+one split of 2,049 groups of two rows (one more group than a block of k_gauc_terms takes: the finish adds two partials);
 the engines run at tests/test_gpu_recommend.py's problem (taobao10 at scale 0.05: 1,188 users, 10 domains).
 """
 import copy
@@ -172,6 +173,41 @@ def test_exact_values():
     users, bT, bP, _ = brute_force(pred, label, uid)
     assert bT.tolist() == T.tolist() and bP.tolist() == P.tolist()
     assert rep["gauc"] == (7 * (9 / 24.0) + 140 * (3600 / 9600.0)) / 147
+
+
+def two_row_groups(G, rs):
+    """G users of one positive and one negative row each, seven of them with two positives instead (never the user of the
+    highest id), predictions on 4 levels (wins, ties and losses), in a shuffled file order -> (pred, label, uid)."""
+    uid = np.repeat(np.sort(rs.permutation(100000)[:G]), 2).astype(np.int32)
+    label = np.tile(np.array([1, 0], F32), G)
+    label[2 * rs.choice(G - 1, 7, replace=False) + 1] = 1
+    pred = (rs.randint(0, 4, uid.size) / 4.0).astype(F32)
+    file_order = rs.permutation(uid.size)
+    return pred[file_order], label[file_order], uid[file_order]
+
+
+def test_more_groups_than_one_block_of_terms():
+    """2,049 groups of two rows: k_gauc_terms writes two partials (a block takes 2,048 groups) and k_gauc_finish adds more
+    than one.  Held to the brute force as the crafted split is."""
+    need_gpu()
+    rs = np.random.RandomState(29)
+    G = 2049
+    pred, label, uid = two_row_groups(G, rs)
+    plan = gauc.group_plan(uid)
+    assert plan.group_off.size - 1 == G and plan.tile_group.size == 0
+    rep, T, P, bits = device_call(pred, label, plan)
+    _, bT, bP, bR = brute_force(pred, label, uid)
+    assert np.array_equal(T, bT) and np.array_equal(P, bP)
+    assert bP[-1] == 1 and set(bT.tolist()) == {0, 1, 2}          # the second block's one group counts; every outcome occurs
+    want = float64_report(bT, bP, bR)
+    assert (rep["n_groups"], rep["n_valid"], rep["rows_valid"]) == (want["n_groups"], want["n_valid"], want["rows_valid"])
+    assert (want["n_groups"], want["n_valid"], want["rows_valid"]) == (G, G - 7, 2 * (G - 7))
+    print("2049 groups: relative difference %.3e, bound %.3e" % (abs(rep["gauc"] - want["gauc"]) / want["gauc"], bound(G)))
+    assert abs(rep["gauc"] - want["gauc"]) <= bound(G) * want["gauc"]
+    # a second run, and the same rows in another file order: the same bits
+    assert device_call(pred, label, plan)[3] == bits
+    p = rs.permutation(uid.size)
+    assert device_call(pred[p], label[p], gauc.group_plan(uid[p]))[3] == bits
 
 
 def test_invariance_under_row_and_member_order():

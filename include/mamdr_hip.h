@@ -882,6 +882,57 @@ int mamdr_graph_bind_accumulator(mamdr_graph* g, float* d_acc);
 int mamdr_graph_eval_domain(mamdr_graph* g, int domain, int split, int32_t batch, float* d_loss_out, uint32_t* d_hist,
                             float* d_pred_out);
 
+/* Top-K lists, exact ranks and per-query slates from the live weights of the generic-layer engine's SINGLE-OUTPUT towers:
+ * MAMDR_GRAPH_NFM, _PNN, _CCPM, _AUTOINT, _MLP, _WDL and _DEEPFM, at every hidden shape and field width that
+ * mamdr_graph_create accepts, with frozen or trainable tables, with or without the weighted loss (retrieval, like
+ * evaluation, is unweighted).  NO REFERENCE COUNTERPART, as mamdr_recommend.  The argument lists are those of
+ * mamdr_recommend, mamdr_recommend_domain, mamdr_rank_domain and mamdr_rank_slates with the graph handle in place of the
+ * context, and the header text of those four calls applies as written -- the 64-bit key (order-preserving logit bits << 32)
+ * | ~id, ties by ascending id, a NaN logit behind every number, -0 as +0, key 0 = no entry, k in 1 .. 128 with -1 / 0
+ * padding, d_scores_all in d_cand order with 0 for an excluded pair, Rank, Score, Live, Position, Order, the link
+ * "rank r < k <=> position r of the top-K list", integer-only counting, one stream synchronisation to read offsets back,
+ * the MAMDR_EINVAL and MAMDR_ESTATE cases (reported through mamdr_graph_last_error) -- except where listed here:
+ * 1. The whole tower runs per pair.  These towers' inputs do not separate into a query term and an item term (inner
+ *    products, bi-interaction, convolutions and attention act across the fields), so every (user, item, domain) pair goes
+ *    through the engine's inference forward: the pair rows (k_graph_pair_rows), the gather, the tower, and a head that
+ *    ends in the key (k_graph_head_keys) instead of the loss.  The logit is formed by the very device function
+ *    mamdr_graph_eval_domain's head uses: the retrieval score IS the evaluation score.
+ * 2. Bit rule: every forward batch is padded to max_batch rows (rounded up to 64).  On this engine a layer's rounding
+ *    depends on the padded row count of the batch (it picks the 32 x 32 tile form, which splits the reduction over four
+ *    waves, or the 64 x 64 form), so a remainder batch would score a pair to other bits than a full one.  All forward
+ *    batches of these calls therefore run at the full padded height whatever their row count, and a pair's logit is the
+ *    same bits in any chunk, at any position, beside any neighbours, across all four calls -- and the bits
+ *    mamdr_graph_eval_domain(batch = max_batch) writes to d_pred_out for the same triple in a FULL batch.  Evaluation's
+ *    own remainder batch (rows < max_batch, padded to the next 64 only) may round differently; that is unchanged.
+ * 3. Chunking: candidates are passed MAMDR_REC_CHUNK at a time (default 16384, rounded up to 64; read at
+ *    mamdr_graph_create) in blocks of up to 256 queries; within a pass the pairs are query-major with each query's chunk
+ *    padded to a multiple of 64, so a 64-key tile never straddles two queries.  Any chunking gives the same bytes.  The
+ *    workspaces (pair rows, keys, per-tile lists, running best, target keys) belong to the handle, grow on demand and are
+ *    freed by mamdr_graph_destroy.
+ * 4. Reads the state only: parameters, Adam slots, the accumulator, the optimizer and dropout counters and the bound splits
+ *    are unchanged.  The activation workspaces the forward overwrites (the activations, AutoInt's token buffers and
+ *    attention buffers, the linear-logit column, the label and domain-row columns) are rebuilt by every training and
+ *    evaluation call before use.  No loss, histogram or regulariser work is done.
+ * MAMDR_ENOTBUILT: shared_bottom / mmoe / ple (one task per domain) and every MAMDR_GRAPH_STAR form (per-domain tensors,
+ * BatchNorm state); the message names the kind.  (Added within ABI 19: new entry points only, no structure or existing
+ * call changed.) */
+int mamdr_graph_recommend(mamdr_graph* g, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain,
+                          const int32_t* d_cand, int64_t n_cand,
+                          const int64_t* d_excl_off, const int32_t* d_excl_ids,
+                          int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all);
+int mamdr_graph_recommend_domain(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                                 const int32_t* d_cand, int64_t n_cand,
+                                 const int64_t* d_excl_off, const int32_t* d_excl_ids,
+                                 int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all);
+int mamdr_graph_rank_domain(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                            const int32_t* d_cand, int64_t n_cand,
+                            const int64_t* d_excl_off, const int32_t* d_excl_ids,
+                            const int64_t* d_tgt_off, const int32_t* d_tgt_ids,
+                            int32_t* d_rank_out, float* d_score_out, int32_t* d_live_out);
+int mamdr_graph_rank_slates(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                            const int64_t* d_slate_off, const int32_t* d_slate_ids,
+                            float* d_score_out, int32_t* d_pos_out, int32_t* d_order_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -167,6 +167,10 @@ SIGNATURES = {
     "mamdr_graph_train_steps_n": (C.c_int, [_VP, C.c_int, _VP, _I64, _I64, _I64, _I32, _U32, _I32, _F, _VP]),
     "mamdr_graph_bind_accumulator": (C.c_int, [_VP, _VP]),
     "mamdr_graph_eval_domain": (C.c_int, [_VP, C.c_int, C.c_int, _I32, _VP, _VP, _VP]),
+    "mamdr_graph_recommend": (C.c_int, [_VP, _I32, _VP, _VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mamdr_graph_recommend_domain": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
+    "mamdr_graph_rank_domain": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mamdr_graph_rank_slates": (C.c_int, [_VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
 }
 
 _lib = None

@@ -35,7 +35,7 @@ static const EnvSwitch kEnvSwitches[] = {
     {"MAMDR_FZ_DEAL_RESIDUE", "lib", "1: k_wgrad_adam deals every XCD the same mix of S blocks and tiles of all three matrices instead of one rectangle of one matrix (A/B switch; same bits)"},
     {"MAMDR_FZ_S_INORDER", "lib", "1: S workgroup b of k_wgrad_adam takes column block b of dz1 instead of one its XCD's tiles read (A/B switch; same bits)"},
     {"MAMDR_STAR_DENSE_SLICES", "lib", "1: every per-domain Star slice swept every step (diagnostic; same bits)"},
-    {"MAMDR_REC_CHUNK", "lib,tests", "candidates per pass of mamdr_recommend's phases (default 16384; rounded up to 64; tests: several chunks at tiny sizes; same bits)"},
+    {"MAMDR_REC_CHUNK", "lib,tests", "candidates per pass of the retrieval calls' phases, mamdr_recommend* / mamdr_rank_* and their mamdr_graph_* forms (default 16384; rounded up to 64; read when the context or graph handle is created; tests: several chunks at tiny sizes; same bits)"},
     // ---- library, generic-layer engine (read at mamdr_graph_create)
     {"MAMDR_GRAPH_NO_DEFER", "lib", "1: a pair of weight-gradient launches per layer instead of the queued flat grid"},
     {"MAMDR_GRAPH_TILE32_BELOW", "lib", "row count below which the 32 x 32 GEMM tile is used (0: 64 x 64 everywhere)"},

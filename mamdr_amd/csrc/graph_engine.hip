@@ -45,7 +45,7 @@
 //            _bwd), Dense or StarFCN layers on the kernels of the batch's first-row domain (k_star_eff, k_star_chain), the auxiliary
 //            network joined at the head (k_star_join_fwd / _bwd); moving statistics outside the flat vector (mamdr_graph_bind_aux)
 //
-// Device side: five headers that this file alone includes, in this order (ONE translation unit; the code object lists the
+// Device side: six headers that this file alone includes, in this order (ONE translation unit; the code object lists the
 // plain kernels in the order their definitions are read, so the headers are cut along the order the code has always had)
 //   graph_gemm.h     GemmArgs / GroupTab, gemm_tile (64 x 64) and gemm_tile32 (32 x 32), k_graph_gemm / _gemm32 and their _group
 //                    forms (apply_member)
@@ -56,6 +56,9 @@
 //                    k_graph_small_nt / _add_x, gate, head, loss, scale
 //   graph_tail.h     the step's end: the domain table's gradient, TailJobs / k_graph_tail, AdamArgs / k_graph_adam
 //   graph_star.h     StarNormArgs .. k_star_join_bwd
+//   graph_retrieval.h  retrieval from the single-output towers: k_graph_pair_rows, k_graph_head_keys (head_logit of
+//                    graph_towers.h with a key ending), k_graph_tile_topk, k_graph_rank_count; last, so the kernels before it
+//                    keep their places in the code object
 //
 // Host side, here (GLAUNCH, the error buffer, the launch_* helpers, then "host side: structure of the tower"):
 //   contractions   gemm_args / fwd_args / din_args describe a GemmArgs by role, launch_wgrad takes a weight gradient's operands;
@@ -67,6 +70,9 @@
 //   a step         mamdr_graph_train_steps_n: step_ctx, advance_optimizer, open_sink, launch_gather, task_forward, launch_head,
 //                  launch_loss, task_backward, finish_grads, star_chain, table_step, adam_step; mamdr_graph_eval_domain shares
 //                  step_ctx / launch_gather / task_forward / launch_head / launch_loss.  Nothing in a step allocates.
+//   retrieval      mamdr_graph_recommend / _recommend_domain / _rank_domain / _rank_slates: retrieval_kind, grow_retrieval,
+//                  retrieval_forward (launch_gather + task_forward at the full padded height), grid_pass / list_pass, and the
+//                  step engine's k_rec_merge / k_slate_order through their launchers (mamdr_kernels.h)
 //   a context      mamdr_graph_create: validate_config, read_switches, layout_one_task (layout_star / layout_single) or
 //                  layout_multi_task, alloc_workspace; every device pointer is freed from the record it came from (mamdr_graph::dev)
 #include <hip/hip_runtime.h>
@@ -87,6 +93,7 @@
 #include "graph_towers.h"
 #include "graph_tail.h"
 #include "graph_star.h"
+#include "graph_retrieval.h"
 
 // every kernel launch of this engine goes through here: the count is what tools/graph_bench.py reports as launches per step
 static std::atomic<long long> g_graph_launches{0};      // (contexts may be driven from several host threads: lanes)
@@ -232,6 +239,13 @@ struct mamdr_graph {
     int32_t *urow = nullptr, *irow = nullptr, *map_u = nullptr, *map_i = nullptr, *hasdup_u = nullptr, *hasdup_i = nullptr;
     float *gbuf_u = nullptr, *gbuf_i = nullptr;
     float* G(int64_t off) const { return grad + (off - table_floats); }      // gradient of the flat vector's element `off`
+    // retrieval (graph_retrieval.h): the pair rows and keys of one forward batch [rows_pad_max], the per-tile lists and the
+    // running best of a block of queries, the target / slate keys of a call.  Allocated on first use, grown on demand
+    int rec_chunk = 16384;      // candidates per pass (MAMDR_REC_CHUNK)
+    int32_t *ret_uid = nullptr, *ret_pid = nullptr, *ret_dom = nullptr, *ret_rowq = nullptr;
+    float* ret_label = nullptr;
+    unsigned long long *ret_keys = nullptr, *ret_part = nullptr, *ret_best = nullptr, *ret_tkey = nullptr;
+    size_t ret_part_cap = 0, ret_tkey_cap = 0;
     // the x columns of the gradient workspace that a first layer on x fills: the domain columns alone while the tables are
     // frozen (n 0: all of them)
     int dx_first() const { return tables ? 0 : 2 * emb; }
@@ -1115,7 +1129,7 @@ void launch_gather(mamdr_graph* g, const SplitData& d, const int32_t* perm, int6
 }
 // the head over columns [t_col, ...) of the activation workspace (AutoInt: [attention output | last DNN layer]).  A training
 // step leaves d logit and the head's d input; evaluation counts the histogram and writes the predictions.  -> its width
-int launch_head(mamdr_graph* g, const Task& t, const StepCtx& sc, int t_col, uint32_t* hist, float* pred_out) {
+HeadArgs head_args(const mamdr_graph* g, const Task& t, const StepCtx& sc, int t_col) {
     const bool autoint = g->cfg.kind == MAMDR_GRAPH_AUTOINT;
     HeadArgs ha;
     memset(&ha, 0, sizeof(ha));
@@ -1135,6 +1149,10 @@ int launch_head(mamdr_graph* g, const Task& t, const StepCtx& sc, int t_col, uin
     ha.extra = g->extra;
     ha.train = sc.train ? 1 : 0;
     ha.gate_scale = sc.keep_scale;
+    return ha;
+}
+int launch_head(mamdr_graph* g, const Task& t, const StepCtx& sc, int t_col, uint32_t* hist, float* pred_out) {
+    HeadArgs ha = head_args(g, t, sc, t_col);
     if (sc.train && g->lv_off >= 0) {
         ha.log_var = g->params + g->lv_off;
         ha.domrow = g->domrow;
@@ -1566,6 +1584,234 @@ void read_switches(mamdr_graph* g) {
         g_tile32_below.store(ev ? atoi(ev) : TILE32_BELOW_DEFAULT, std::memory_order_relaxed);
     }
     if (const char* ev = getenv("MAMDR_GRAPH_NO_TAIL_OPT")) g->tail_opt = atoi(ev) == 0;
+    if (const char* ev = getenv("MAMDR_REC_CHUNK"))
+        if (atoi(ev) > 0) g->rec_chunk = (int)std::min<int64_t>(((int64_t)atoi(ev) + REC_TILE - 1) / REC_TILE * REC_TILE, 1 << 20);
+}
+
+// ================================================================== retrieval from the single-output towers (graph_retrieval.h)
+const char* kind_name(int kind) {
+    static const char* const names[] = {"shared_bottom", "mmoe", "ple", "nfm", "pnn", "ccpm", "autoint", "mlp", "wdl", "deepfm", "star"};
+    return kind >= 0 && kind < (int)(sizeof(names) / sizeof(names[0])) ? names[kind] : "?";
+}
+// the kinds these calls serve: ONE task for every domain and no state outside the flat vector
+int retrieval_kind(const mamdr_graph* g, const char* fn) {
+    if (g->single && !g->star) return MAMDR_OK;
+    return gfail(MAMDR_ENOTBUILT, "%s: the %s tower is not built for retrieval (%s); nfm, pnn, ccpm, autoint, mlp, wdl and deepfm are",
+                 fn, kind_name(g->cfg.kind),
+                 g->star ? "its per-domain tensors and norm state are not prepared for inference here" : "it holds one task per domain");
+}
+// the handle's retrieval workspaces: the per-batch columns on first use; `part_keys` keys of per-tile lists and `n_tkey`
+// target / slate keys grown on demand (0: not needed by this call)
+int grow_retrieval(mamdr_graph* g, size_t part_keys, size_t n_tkey) {
+    const size_t rp = (size_t)g->rows_pad_max;
+    if (!g->ret_uid) {
+        g->dev.alloc(&g->ret_uid, rp);
+        g->dev.alloc(&g->ret_pid, rp);
+        g->dev.alloc(&g->ret_dom, rp);
+        g->dev.alloc(&g->ret_rowq, rp);
+        g->dev.alloc(&g->ret_label, rp);
+        g->dev.alloc(&g->ret_keys, rp);
+        g->dev.alloc(&g->ret_best, (size_t)REC_QBLOCK * REC_KMAX);
+        if (g->dev.err != hipSuccess) {     // all or nothing: the next call starts over
+            for (void* p : {(void*)g->ret_uid, (void*)g->ret_pid, (void*)g->ret_dom, (void*)g->ret_rowq, (void*)g->ret_label,
+                            (void*)g->ret_keys, (void*)g->ret_best})
+                g->dev.release(p);
+            g->ret_uid = g->ret_pid = g->ret_dom = g->ret_rowq = nullptr;
+            g->ret_label = nullptr;
+            g->ret_keys = g->ret_best = nullptr;
+            return g->dev.check(g_gerr);
+        }
+    }
+    if (part_keys > g->ret_part_cap) {
+        g->dev.release(g->ret_part);
+        g->ret_part = nullptr;
+        g->ret_part_cap = 0;
+        g->dev.alloc(&g->ret_part, part_keys);
+        if (const int rc = g->dev.check(g_gerr)) return rc;
+        g->ret_part_cap = part_keys;
+    }
+    if (n_tkey > g->ret_tkey_cap) {
+        g->dev.release(g->ret_tkey);
+        g->ret_tkey = nullptr;
+        g->ret_tkey_cap = 0;
+        g->dev.alloc(&g->ret_tkey, n_tkey);
+        if (const int rc = g->dev.check(g_gerr)) return rc;
+        g->ret_tkey_cap = n_tkey;
+    }
+    return MAMDR_OK;
+}
+// what a block of queries hands to its passes
+struct RetBlock {
+    int n_query;
+    const int32_t *uid, *dom;       // of the block (dom null: every query in `domain`)
+    int domain;
+};
+PairArgs pair_args(const mamdr_graph* g, const RetBlock& b) {
+    PairArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    pa.uid = g->ret_uid;
+    pa.pid = g->ret_pid;
+    pa.dom = g->ret_dom;
+    pa.label = g->ret_label;
+    pa.rowq = g->ret_rowq;
+    pa.n_user = g->cfg.n_user;
+    pa.n_item = g->cfg.n_item;
+    pa.n_domain = g->cfg.n_domain;
+    pa.q_uid = b.uid;
+    pa.q_dom = b.dom;
+    pa.dom_all = b.domain;
+    pa.n_query = b.n_query;
+    return pa;
+}
+// the inference forward over the `rows` pair rows in the workspace -- ALWAYS at the full padded height: a layer picks its
+// tile form, and with it its rounding, from the padded row count (use_tile32), so every batch of these calls runs as a full
+// evaluation batch does and a pair's logit does not depend on where the pair sits.  -> the head's operands
+HeadArgs retrieval_forward(mamdr_graph* g, int rows) {
+    StepCtx sc;
+    memset(&sc, 0, sizeof(sc));
+    sc.rows = rows;
+    sc.rp = g->rows_pad_max;
+    sc.keep_scale = 1.0f;
+    SplitData d;
+    d.uid = g->ret_uid;
+    d.pid = g->ret_pid;
+    d.dom = g->ret_dom;
+    d.label = g->ret_label;
+    d.n = g->rows_pad_max;
+    d.bound = true;
+    launch_gather(g, d, nullptr, 0, sc);
+    const Task& t = g->tasks[0];
+    return head_args(g, t, sc, task_forward(g, t, sc));
+}
+// one chunk of candidates x the block's queries: the [n_query][chunk_pad] grid of pairs, query-major, a forward batch at a
+// time; `ta` carries the ending's operands (count: k_graph_rank_count, otherwise k_graph_tile_topk)
+void grid_pass(mamdr_graph* g, const RetBlock& b, const int32_t* d_cand, int64_t n_cand, int64_t c_base, int n_chunk,
+               const int64_t* excl_off, const int32_t* excl_ids, float* scores_all, TileArgs ta, bool count) {
+    const int chunk_pad = (n_chunk + REC_TILE - 1) / REC_TILE * REC_TILE;
+    const int64_t total = (int64_t)b.n_query * chunk_pad;
+    PairArgs pa = pair_args(g, b);
+    pa.ids = d_cand;
+    pa.c_base = c_base;
+    pa.chunk_pad = chunk_pad;
+    pa.n_chunk = n_chunk;
+    for (int64_t base = 0; base < total; base += g->rows_pad_max) {
+        const int rows = (int)std::min<int64_t>(g->rows_pad_max, total - base);
+        pa.rows = rows;
+        pa.row_base = base;
+        GLAUNCH(k_graph_pair_rows<false>, dim3((rows + 255) / 256), dim3(256), 0, g->stream, pa);
+        KeyArgs ka;
+        memset(&ka, 0, sizeof(ka));
+        ka.h = retrieval_forward(g, rows);
+        ka.pid = g->ret_pid;
+        ka.rowq = g->ret_rowq;
+        ka.excl_off = excl_off;
+        ka.excl_ids = excl_ids;
+        ka.scores_all = scores_all;
+        ka.n_cand = n_cand;
+        ka.c_base = c_base;
+        ka.row_base = base;
+        ka.chunk_pad = chunk_pad;
+        ka.keys = g->ret_keys;
+        GLAUNCH(k_graph_head_keys<false>, dim3((rows + 3) / 4), dim3(256), 0, g->stream, ka);
+        ta.keys = g->ret_keys;
+        ta.n_tiles = rows / REC_TILE;
+        ta.row_base = base;
+        ta.chunk_pad = chunk_pad;
+        if (count) GLAUNCH(k_graph_rank_count, dim3((ta.n_tiles + 3) / 4), dim3(256), 0, g->stream, ta);
+        else GLAUNCH(k_graph_tile_topk, dim3((ta.n_tiles + 3) / 4), dim3(256), 0, g->stream, ta);
+    }
+}
+// entries [j0, j1) of the call's flat list (targets, slate entries) that belong to the block's queries (`off`: the block's
+// CSR with the call's absolute positions): their keys into ret_tkey, their scores into score_out when asked
+void list_pass(mamdr_graph* g, const RetBlock& b, const int64_t* off, const int32_t* ids, int64_t j0, int64_t j1, float* score_out) {
+    PairArgs pa = pair_args(g, b);
+    pa.ids = ids;
+    pa.off = off;
+    for (int64_t base = j0; base < j1; base += g->rows_pad_max) {
+        const int rows = (int)std::min<int64_t>(g->rows_pad_max, j1 - base);
+        pa.rows = rows;
+        pa.list_base = base;
+        GLAUNCH(k_graph_pair_rows<true>, dim3((rows + 255) / 256), dim3(256), 0, g->stream, pa);
+        KeyArgs ka;
+        memset(&ka, 0, sizeof(ka));
+        ka.h = retrieval_forward(g, rows);
+        ka.pid = g->ret_pid;
+        ka.rowq = g->ret_rowq;
+        ka.tkey = g->ret_tkey;
+        ka.score_out = score_out;
+        ka.list_base = base;
+        GLAUNCH(k_graph_head_keys<true>, dim3((rows + 3) / 4), dim3(256), 0, g->stream, ka);
+    }
+}
+// candidates per pass of a call over n_cand candidates
+int chunk_of(const mamdr_graph* g, int64_t n_cand) {
+    return (int)std::min<int64_t>(g->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
+}
+// the CSR offsets of a call's targets / slate entries, read back once (the call's one synchronisation of the handle's stream)
+// and held to their contract here, so that no kernel indexes past the list
+int read_offsets(mamdr_graph* g, const char* fn, const char* what, const int64_t* d_off, int32_t n_query, std::vector<int64_t>& off) {
+    off.resize((size_t)n_query + 1);
+    GHIP(hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    GHIP(hipStreamSynchronize(g->stream));
+    if (off[0] != 0) return gfail(MAMDR_EINVAL, "%s: the %s offsets start at %lld, not 0", fn, what, (long long)off[0]);
+    for (int32_t q = 0; q < n_query; ++q)
+        if (off[q + 1] < off[q]) return gfail(MAMDR_EINVAL, "%s: the %s offsets descend at query %d", fn, what, q);
+    return MAMDR_OK;
+}
+
+// the body of both top-K entry points: `domain` < 0 = mamdr_graph_recommend (query q in d_domain[q])
+int graph_recommend_body(mamdr_graph* g, const char* fn, int32_t domain, int32_t n_query, const int32_t* d_uid,
+                         const int32_t* d_domain, const int32_t* d_cand, int64_t n_cand, const int64_t* d_excl_off,
+                         const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    const bool per_query = domain < 0;
+    if (n_query <= 0) return gfail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (k < 1 || k > REC_KMAX) return gfail(MAMDR_EINVAL, "%s: k %d outside [1, %d]", fn, k, REC_KMAX);
+    if (d_cand && n_cand <= 0) return gfail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
+    if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
+        return gfail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
+    if (misaligned(3, d_uid, d_domain, d_cand, d_excl_ids, d_ids_out, d_scores_out, d_scores_all) || misaligned(7, d_excl_off))
+        return gfail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return gfail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
+    if (ready(g)) return MAMDR_ESTATE;
+    if (!d_cand) n_cand = g->cfg.n_item;
+    const int chunk = chunk_of(g, n_cand), kt = std::min<int>(k, REC_TILE), tiles_cap = chunk / REC_TILE;
+    const int q_cap = std::min<int32_t>(REC_QBLOCK, n_query);
+    if (const int rc = grow_retrieval(g, (size_t)q_cap * tiles_cap * REC_TILE, 0)) return rc;
+    RecArgs ma;                     // what k_rec_merge reads
+    memset(&ma, 0, sizeof(ma));
+    ma.k = k;
+    ma.kt = kt;
+    ma.tiles_cap = tiles_cap;
+    ma.part = g->ret_part;
+    ma.best = g->ret_best;
+    TileArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.part = g->ret_part;
+    ta.tiles_cap = tiles_cap;
+    ta.kt = kt;
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        const RetBlock b{std::min<int32_t>(REC_QBLOCK, n_query - qb), d_uid + qb, per_query ? d_domain + qb : nullptr, domain};
+        ma.n_query = b.n_query;
+        ma.ids_out = d_ids_out + (size_t)qb * k;
+        ma.scores_out = d_scores_out + (size_t)qb * k;
+        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
+            const int n_chunk = (int)std::min<int64_t>(chunk, n_cand - c0);
+            grid_pass(g, b, d_cand, n_cand, c0, n_chunk, d_excl_off ? d_excl_off + qb : nullptr, d_excl_ids,
+                      d_scores_all ? d_scores_all + (size_t)qb * n_cand : nullptr, ta, false);
+            ma.tiles = (n_chunk + REC_TILE - 1) / REC_TILE;
+            ma.first_chunk = c0 == 0;
+            ma.last_chunk = c0 + chunk >= n_cand;
+            ++g_graph_launches;
+            launch_rec_merge(ma, g->stream);
+        }
+    }
+    GHIP(hipGetLastError());
+    return MAMDR_OK;
+}
+int check_domain(const mamdr_graph* g, const char* fn, int32_t domain) {
+    if (domain < 0 || domain >= g->cfg.n_domain) return gfail(MAMDR_EINVAL, "%s: domain %d outside [0, %d)", fn, domain, g->cfg.n_domain);
+    return MAMDR_OK;
 }
 
 }  // namespace
@@ -1801,6 +2047,117 @@ int mamdr_graph_eval_domain(mamdr_graph* g, int domain, int split, int32_t batch
     }
     GLAUNCH(k_graph_scale, dim3(1), dim3(1), 0, g->stream, g->eval_acc, 1.0f / (float)n_batches);
     GHIP(hipMemcpyAsync(d_loss_out, g->eval_acc, sizeof(float), hipMemcpyDeviceToDevice, g->stream));
+    GHIP(hipGetLastError());
+    return MAMDR_OK;
+}
+
+// ---- retrieval from the single-output towers (include/mamdr_hip.h; device side: graph_retrieval.h)
+int mamdr_graph_recommend(mamdr_graph* g, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain, const int32_t* d_cand,
+                          int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
+                          float* d_scores_out, float* d_scores_all) {
+    const char* fn = "mamdr_graph_recommend";
+    if (check(g)) return MAMDR_EINVAL;
+    if (const int rc = retrieval_kind(g, fn)) return rc;
+    return graph_recommend_body(g, fn, -1, n_query, d_uid, d_domain, d_cand, n_cand, d_excl_off, d_excl_ids, k, d_ids_out,
+                                d_scores_out, d_scores_all);
+}
+
+int mamdr_graph_recommend_domain(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
+                                 int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k,
+                                 int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
+    const char* fn = "mamdr_graph_recommend_domain";
+    if (check(g)) return MAMDR_EINVAL;
+    if (const int rc = retrieval_kind(g, fn)) return rc;
+    if (const int rc = check_domain(g, fn, domain)) return rc;
+    return graph_recommend_body(g, fn, domain, n_query, d_uid, nullptr, d_cand, n_cand, d_excl_off, d_excl_ids, k, d_ids_out,
+                                d_scores_out, d_scores_all);
+}
+
+// exact ranks: the targets' keys through the list form first, then the candidate passes with the counting ending
+int mamdr_graph_rank_domain(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
+                            int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, const int64_t* d_tgt_off,
+                            const int32_t* d_tgt_ids, int32_t* d_rank_out, float* d_score_out, int32_t* d_live_out) {
+    const char* fn = "mamdr_graph_rank_domain";
+    if (check(g)) return MAMDR_EINVAL;
+    if (const int rc = retrieval_kind(g, fn)) return rc;
+    if (const int rc = check_domain(g, fn, domain)) return rc;
+    if (n_query <= 0) return gfail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (d_cand && n_cand <= 0) return gfail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
+    if (!d_uid || !d_tgt_off || !d_rank_out || !d_live_out)
+        return gfail(MAMDR_EINVAL, "%s: null uid / target offsets / rank / live output pointer", fn);
+    if (misaligned(3, d_uid, d_cand, d_excl_ids, d_tgt_ids, d_rank_out, d_score_out, d_live_out) || misaligned(7, d_excl_off, d_tgt_off))
+        return gfail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return gfail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
+    if (ready(g)) return MAMDR_ESTATE;
+    std::vector<int64_t> off;
+    if (const int rc = read_offsets(g, fn, "target", d_tgt_off, n_query, off)) return rc;
+    const int64_t n_tgt = off[n_query];
+    if (n_tgt > 0 && !d_tgt_ids) return gfail(MAMDR_EINVAL, "%s: %lld targets without their ids", fn, (long long)n_tgt);
+    if (!d_cand) n_cand = g->cfg.n_item;
+    const int chunk = chunk_of(g, n_cand);
+    if (const int rc = grow_retrieval(g, 0, (size_t)n_tgt)) return rc;
+    if (n_tgt > 0) GHIP(hipMemsetAsync(d_rank_out, 0, (size_t)n_tgt * sizeof(int32_t), g->stream));
+    GHIP(hipMemsetAsync(d_live_out, 0, (size_t)n_query * sizeof(int32_t), g->stream));
+    TileArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.tkey = g->ret_tkey;
+    ta.rank_out = d_rank_out;
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        const RetBlock b{std::min<int32_t>(REC_QBLOCK, n_query - qb), d_uid + qb, nullptr, domain};
+        list_pass(g, b, d_tgt_off + qb, d_tgt_ids, off[qb], off[qb + b.n_query], d_score_out);
+        ta.tgt_off = d_tgt_off + qb;
+        ta.live_out = d_live_out + qb;
+        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk)
+            grid_pass(g, b, d_cand, n_cand, c0, (int)std::min<int64_t>(chunk, n_cand - c0), d_excl_off ? d_excl_off + qb : nullptr,
+                      d_excl_ids, nullptr, ta, true);
+    }
+    GHIP(hipGetLastError());
+    return MAMDR_OK;
+}
+
+// per-query slates: the entries' keys through the list form, then the step engine's k_slate_order, unchanged
+int mamdr_graph_rank_slates(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid, const int64_t* d_slate_off,
+                            const int32_t* d_slate_ids, float* d_score_out, int32_t* d_pos_out, int32_t* d_order_out) {
+    const char* fn = "mamdr_graph_rank_slates";
+    if (check(g)) return MAMDR_EINVAL;
+    if (const int rc = retrieval_kind(g, fn)) return rc;
+    if (const int rc = check_domain(g, fn, domain)) return rc;
+    if (n_query <= 0) return gfail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
+    if (!d_uid || !d_slate_off || !d_pos_out) return gfail(MAMDR_EINVAL, "%s: null uid / slate offsets / position output pointer", fn);
+    if (misaligned(3, d_uid, d_slate_ids, d_score_out, d_pos_out, d_order_out) || misaligned(7, d_slate_off))
+        return gfail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
+    if (ready(g)) return MAMDR_ESTATE;
+    std::vector<int64_t> off;
+    if (const int rc = read_offsets(g, fn, "slate", d_slate_off, n_query, off)) return rc;
+    for (int32_t q = 0; q < n_query; ++q)
+        if (off[q + 1] - off[q] > INT32_MAX)
+            return gfail(MAMDR_EINVAL, "%s: slate %d has %lld entries: positions are int32", fn, q, (long long)(off[q + 1] - off[q]));
+    const int64_t n_ent = off[n_query];
+    if (n_ent == 0) return MAMDR_OK;
+    if (!d_slate_ids) return gfail(MAMDR_EINVAL, "%s: %lld entries without their ids", fn, (long long)n_ent);
+    if (const int rc = grow_retrieval(g, 0, (size_t)n_ent)) return rc;
+    SlateArgs sa;
+    sa.tkey = g->ret_tkey;
+    sa.pos_out = d_pos_out;
+    sa.order_out = d_order_out;
+    if (d_order_out) GHIP(hipMemsetAsync(d_order_out, 0xff, (size_t)n_ent * sizeof(int32_t), g->stream));
+    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
+        const RetBlock b{std::min<int32_t>(REC_QBLOCK, n_query - qb), d_uid + qb, nullptr, domain};
+        if (off[qb + b.n_query] == off[qb]) continue;           // a block of empty slates
+        list_pass(g, b, d_slate_off + qb, d_slate_ids, off[qb], off[qb + b.n_query], d_score_out);
+        int64_t max_len = 0;
+        bool any_short = false;
+        for (int32_t q = qb; q < qb + b.n_query; ++q) {
+            const int64_t len = off[q + 1] - off[q];
+            max_len = std::max(max_len, len);
+            any_short = any_short || (len >= 1 && len <= SLATE_WAVE);
+        }
+        sa.off = d_slate_off + qb;
+        sa.n_query = b.n_query;
+        g_graph_launches += (any_short ? 1 : 0) + (max_len > SLATE_WAVE ? 1 : 0);
+        launch_slate_order(sa, max_len, any_short, g->stream);
+    }
     GHIP(hipGetLastError());
     return MAMDR_OK;
 }

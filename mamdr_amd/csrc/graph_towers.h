@@ -587,13 +587,19 @@ struct HeadArgs {
     const float* log_var; const int32_t* domrow;    // weighted loss (training only): d logit scaled by 1 / var^2, var =
                                                     // log_var[domain of the batch's FIRST row] (weighted_loss.py:38-41)
 };
+// the logit of row r, in every lane of its wave: the head's one reduction order (k_graph_head and the retrieval head of
+// graph_retrieval.h form it here, so a retrieval score is the evaluation's score)
+__device__ __forceinline__ float head_logit(const HeadArgs& a, int r, int lane) {
+    const float* row = a.act + (size_t)r * a.ld;
+    float s = 0.f;
+    for (int cidx = lane; cidx < a.n_t; cidx += 64) s = fmaf(row[a.t_col + cidx], a.w[cidx], s);
+    return wave_sum(s) + a.gb[0] + (a.extra ? a.extra[r] : 0.f);
+}
 __global__ __launch_bounds__(256) void k_graph_head(const HeadArgs a) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (r >= a.rows_pad) return;
     const float* row = a.act + (size_t)r * a.ld;
-    float s = 0.f;
-    for (int cidx = lane; cidx < a.n_t; cidx += 64) s = fmaf(row[a.t_col + cidx], a.w[cidx], s);
-    const float logit = wave_sum(s) + a.gb[0] + (a.extra ? a.extra[r] : 0.f);
+    const float logit = head_logit(a, r, lane);
     float p;
     if (logit >= 0.f) {
         p = 1.0f / (1.0f + __expf(-logit));

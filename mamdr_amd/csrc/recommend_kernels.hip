@@ -28,11 +28,10 @@
 // k_rec_score<REC_EPI_COUNT>: a tile counts its keys above each target key of its query by ballot + popcount and adds the
 // count with one integer atomic.  No sort, no merge; integers only, so the sums do not depend on the tiles' order.
 #include "mamdr_kernels.h"
+#include "rec_device.h"
 
 namespace mamdr {
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int REC_THREADS = 256;
 constexpr int IP_ROWS = 32;                   // candidates per workgroup of k_rec_item_proj
@@ -48,22 +47,6 @@ constexpr int SC_UD_OFF = REC_TILE * H0_LD;                   // 16,640: deepfm'
 constexpr int SC_FLOATS = SC_UD_OFF + EMB;
 static_assert(SC_KEY_OFF + 2 * REC_TILE <= SC_UD_OFF && (SC_KEY_OFF % 2) == 0, "keys inside the h0 region");
 
-__device__ __forceinline__ float rec_sigmoid(float logit) {          // as the evaluation's tower computes it
-    if (logit >= 0.f) return 1.0f / (1.0f + __expf(-logit));
-    const float ez = __expf(logit);
-    return ez / (1.0f + ez);
-}
-__device__ __forceinline__ u64 rec_key(float logit, int id) {
-    const uint32_t b = __float_as_uint(logit);
-    uint32_t hi = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    if (logit != logit) hi = 1u;                  // below -inf (0x007fffff), above "no entry"
-    return ((u64)hi << 32) | (u64)(~(uint32_t)id);
-}
-__device__ __forceinline__ float rec_key_logit(u64 key) {
-    const uint32_t hi = (uint32_t)(key >> 32);
-    if (hi == 1u) return __uint_as_float(0x7fc00000u);
-    return __uint_as_float((hi & 0x80000000u) ? (hi & 0x7fffffffu) : ~hi);
-}
 __device__ __forceinline__ int rec_cand_id(const RecArgs& a, int pos) {      // pos < n_chunk
     const int id = a.cand ? a.cand[a.c_base + pos] : (int)(a.c_base + pos);
     return clampi(id, 0, a.n_item - 1);
@@ -160,21 +143,6 @@ __global__ __launch_bounds__(REC_THREADS) void k_rec_query_proj(const RecArgs a)
         a.qs[2 * q] = a.mode == 1 ? red[0] + red[1] : 0.f;
         a.qs[2 * q + 1] = a.mode != 0 ? (a.lin_user ? a.lin_user[uid] : 0.f) + a.dense[a.L.ld + dom] : 0.f;
     }
-}
-
-// descending bitonic sort of one key per lane of a wave
-__device__ __forceinline__ u64 rec_wave_sort(u64 key, int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const uint32_t olo = __shfl_xor((uint32_t)key, j), ohi = __shfl_xor((uint32_t)(key >> 32), j);
-            const u64 other = ((u64)ohi << 32) | olo;
-            const bool take_max = ((lane & j) == 0) == ((lane & k) == 0);
-            key = take_max ? (key > other ? key : other) : (key < other ? key : other);
-        }
-    }
-    return key;
 }
 
 // ---- layers 1 and 2 of a 64-row tile whose h0 [64][260] the caller has staged in LDS (entered before the barrier that

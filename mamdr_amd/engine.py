@@ -747,6 +747,155 @@ class DeviceEngine(FlatVectorOps):
     def _after_domain_gradients(self):
         pass
 
+    # ------------------------------------------------------------ retrieval (the family's recommend / recommend_domain /
+    # rank_domain / rank_slates entry points: the same argument lists on both engines, the same range checks before any launch)
+    def item_rows(self):
+        """the item table the live weights score with, as a DEVICE view [n_item, emb_dim] fp32: the bound frozen table, or --
+        trainable tables -- the item segment of the live flat vector (the step engine's `weights` first makes the rows it
+        advances lazily current: mamdr_sync_tables; the generic-layer engine steps every row with the batch).  A view, not a copy: it is read on the engine's stream before the weights change."""
+        if not self.emb_trainable:
+            return self.tables["item_emb"]
+        off, cnt = self.segments["item_emb"]
+        if cnt != self.n_item * self.emb_dim or off % 4:
+            raise RuntimeError("item_rows: the item segment (%d floats at %d) is not [%d, %d] at a 16-byte offset" % (
+                cnt, off, self.n_item, self.emb_dim))
+        return self.weights[off:off + cnt].view(self.n_item, self.emb_dim)
+
+    def recommend(self, uids, domains, k, candidates=None, exclude=None, want_scores=False):
+        """top-K items for the queries (uids[q], domains[q]) from the live weights (mamdr_recommend: the step engine's mlp /
+        wdl / deepfm; mamdr_graph_recommend: the generic-layer engine's single-output towers; no reference counterpart).
+        candidates: distinct item ids (None: the whole item table); exclude: one array of item ids per query that must not be returned (any order, duplicates allowed).  -> (ids [Q, k] int32, scores [Q, k] float32
+        [, all_scores [Q, n_cand]]) as numpy: by logit descending, equal logits by ascending id, scores = sigmoid(logit);
+        a query with fewer than k candidates left ends in id -1 / score 0; all_scores holds 0 for an excluded pair."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        dom = np.array(np.broadcast_to(np.asarray(domains), uid.shape), np.int32)          # (a writable copy)
+        if uid.size and (dom.min() < 0 or dom.max() >= self.n_domain):
+            raise ValueError("recommend: user or domain id out of range")
+        return self._recommend(uid, dom, None, k, candidates, exclude, want_scores)
+
+    def recommend_domain(self, uids, domain, k, candidates=None, exclude=None, want_scores=False):
+        """`recommend` with every query in the one domain `domain` (mamdr_recommend_domain: mlp / wdl / deepfm, whose
+        results are `recommend`'s with a constant domain vector, byte for byte, and star, which retrieves through this call
+        only: its item term depends on the domain).  Same arguments otherwise, same return contract."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
+            raise ValueError("recommend_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
+        return self._recommend(uid, None, int(domain), k, candidates, exclude, want_scores)
+
+    def _retrieval_inputs(self, uid, candidates, exclude):
+        """the host arrays and range checks every retrieval call shares -> (n_query, candidates int32 or None, n_cand,
+        exclusion offsets, exclusion ids), the CSR None when nothing is excluded."""
+        nq = int(uid.shape[0])
+        if nq and (uid.min() < 0 or uid.max() >= self.n_user):
+            raise ValueError("recommend: user or domain id out of range")
+        cand = None
+        n_cand = self.n_item
+        if candidates is not None:
+            cand = np.ascontiguousarray(np.asarray(candidates).ravel(), np.int32)
+            n_cand = int(cand.shape[0])
+            if n_cand and (cand.min() < 0 or cand.max() >= self.n_item):
+                raise ValueError("recommend: candidate id out of range")
+            if np.unique(cand).shape[0] != n_cand:
+                raise ValueError("recommend: candidate ids must be distinct")
+        off = ids = None
+        if exclude is not None:
+            off, ids = exclusion_csr(exclude, nq)
+            if ids.size and ids.max() >= self.n_item:
+                raise ValueError("recommend: excluded item id out of range")
+            ids = ids if ids.size else np.zeros(1, np.int32)       # (a non-null pointer for an all-empty list)
+        return nq, cand, n_cand, off, ids
+
+    def rank_domain(self, uids, domain, targets, candidates=None, exclude=None, want_scores=False):
+        """exact ranks (mamdr_rank_domain) of `targets` -- one array of item ids per query, any order, duplicates allowed: made
+        ascending and distinct as `exclude` is -- among the candidates, every query in the one domain `domain`, from the
+        live weights.  candidates / exclude: as recommend_domain.  -> {"offsets" [Q + 1] int64, "ids" [T] int32 (the targets'
+        CSR), "ranks" [T] int32: the live candidates that order strictly before the pair (higher logit, or equal logit and
+        smaller id), "listed" [T] bool: the target is a candidate and not excluded for its query (only then is its rank its
+        0-based position in the query's ordering), "live" [Q] int32: live candidates per query [, "scores" [T]: sigmoid(logit)
+        of the pair]} as numpy.  Every range check runs before the launch."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
+            raise ValueError("rank_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
+        nq, cand, n_cand, off, ids = self._retrieval_inputs(uid, candidates, exclude)
+        t_off, t_ids = exclusion_csr(targets, nq, "targets")
+        if t_ids.size and t_ids.max() >= self.n_item:
+            raise ValueError("rank_domain: target item id out of range")
+        n_tgt = int(t_ids.shape[0])
+        in_cand = np.ones(n_tgt, bool) if cand is None else np.isin(t_ids, cand)
+        listed = in_cand.copy()
+        if off is not None:
+            for q in range(nq):
+                sl = slice(t_off[q], t_off[q + 1])
+                listed[sl] &= ~np.isin(t_ids[sl], ids[off[q]:off[q + 1]])
+        dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
+        d_uid, d_cand, d_off, d_ids, d_toff = dev(uid), dev(cand), dev(off), dev(ids), dev(t_off)
+        d_tids = dev(t_ids if n_tgt else np.zeros(1, np.int32))
+        ranks = torch.empty(max(n_tgt, 1), dtype=torch.int32, device=self.device)
+        live = torch.empty(max(nq, 1), dtype=torch.int32, device=self.device)
+        scores = torch.empty(max(n_tgt, 1), dtype=torch.float32, device=self.device) if want_scores else None
+        self._check(getattr(self.lib, self.PREFIX + "rank_domain")(
+            self.ctx, int(domain), nq, _ptr(d_uid), _ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids), _ptr(d_toff), _ptr(d_tids),
+            _ptr(ranks), _ptr(scores), _ptr(live)))
+        res = {"offsets": t_off, "ids": t_ids, "ranks": ranks.cpu().numpy()[:n_tgt], "listed": listed,
+               "live": live.cpu().numpy()[:nq]}
+        if want_scores:
+            res["scores"] = scores.cpu().numpy()[:n_tgt]
+        return res
+
+    def rank_slates(self, uids, domain, slates, want_order=False):
+        """every query's own candidate slate scored and ordered (mamdr_rank_slates): `slates` is one array of DISTINCT item
+        ids per query, kept in the caller's order (a slate may be empty), every query in the one domain `domain`, from the
+        live weights.  -> {"offsets" [Q + 1] int64, "ids" [E] int32 (the slates' CSR), "scores" [E] float32: sigmoid(logit)
+        of the pair -- the bits rank_domain and recommend_domain give it --, "pos" [E] int32: the entries of the same slate
+        that order strictly before the entry (higher logit, or equal logit and smaller id), a permutation of 0 .. L - 1 per
+        slate [, "order" [E] int32: order[offsets[q] + pos[j]] = j - offsets[q], the slate-local index of the entry at each
+        position]} as numpy.  Every check runs before the launch: the work is sum of the slates' lengths pairs, and
+        O(L^2) integer compares per slate -- a whole catalogue is rank_domain's job."""
+        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
+        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
+            raise ValueError("rank_slates: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
+        nq = int(uid.shape[0])
+        off, ids = slates_csr(slates, nq)
+        if nq and (uid.min() < 0 or uid.max() >= self.n_user):
+            raise ValueError("rank_slates: user id out of range")
+        if ids.size and ids.max() >= self.n_item:
+            raise ValueError("rank_slates: item id out of range")
+        n_ent = int(ids.shape[0])
+        res = {"offsets": off, "ids": ids}
+        if nq == 0 or n_ent == 0:
+            res.update(scores=np.zeros(0, np.float32), pos=np.zeros(0, np.int32))
+            if want_order:
+                res["order"] = np.zeros(0, np.int32)
+            return res
+        d_uid, d_off, d_ids = (torch.from_numpy(a).to(self.device) for a in (uid, off, ids))
+        scores = torch.empty(n_ent, dtype=torch.float32, device=self.device)
+        pos = torch.empty(n_ent, dtype=torch.int32, device=self.device)
+        order = torch.empty(n_ent, dtype=torch.int32, device=self.device) if want_order else None
+        self._check(getattr(self.lib, self.PREFIX + "rank_slates")(
+            self.ctx, int(domain), nq, _ptr(d_uid), _ptr(d_off), _ptr(d_ids), _ptr(scores), _ptr(pos), _ptr(order)))
+        res.update(scores=scores.cpu().numpy(), pos=pos.cpu().numpy())
+        if want_order:
+            res["order"] = order.cpu().numpy()
+        return res
+
+    def _recommend(self, uid, dom, domain, k, candidates, exclude, want_scores):
+        """the marshalling of both retrieval calls: dom [Q] int32 per query (mamdr_recommend) or None and the host integer
+        `domain` (mamdr_recommend_domain).  Every range check runs before the launch."""
+        nq, cand, n_cand, off, ids = self._retrieval_inputs(uid, candidates, exclude)
+        dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
+        d_uid, d_dom, d_cand, d_off, d_ids = dev(uid), dev(dom), dev(cand), dev(off), dev(ids)
+        kk = max(int(k), 1)
+        out_ids = torch.empty((max(nq, 1), kk), dtype=torch.int32, device=self.device)
+        out_scores = torch.empty((max(nq, 1), kk), dtype=torch.float32, device=self.device)
+        all_scores = torch.empty((max(nq, 1), max(n_cand, 1)), dtype=torch.float32, device=self.device) if want_scores else None
+        tail = (_ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids), int(k), _ptr(out_ids), _ptr(out_scores), _ptr(all_scores))
+        if domain is None:
+            self._check(getattr(self.lib, self.PREFIX + "recommend")(self.ctx, nq, _ptr(d_uid), _ptr(d_dom), *tail))
+        else:
+            self._check(getattr(self.lib, self.PREFIX + "recommend_domain")(self.ctx, domain, nq, _ptr(d_uid), *tail))
+        res = (out_ids.cpu().numpy()[:nq, :int(k)], out_scores.cpu().numpy()[:nq, :int(k)])
+        return res + (all_scores.cpu().numpy()[:nq, :n_cand],) if want_scores else res
+
 
 class TowerEngine(DeviceEngine):
     PREFIX, KERAS_NAMES = "mamdr_", KERAS_NAMES
@@ -928,152 +1077,6 @@ class TowerEngine(DeviceEngine):
         split_id = {"train": L.SPLIT_TRAIN, "val": L.SPLIT_VAL, "test": L.SPLIT_TEST}[split]
         L.check(self.lib.mamdr_gather_rows(self.ctx, domain, split_id, _ptr(perm), first_row, n, _ptr(out)))
         return out
-
-    def item_rows(self):
-        """the item table the live weights score with, as a DEVICE view [n_item, emb_dim] fp32: the bound frozen table, or --
-        trainable tables -- the item segment of the live flat vector after mamdr_sync_tables (rows the library advances
-        lazily are made current first).  A view, not a copy: it is read on the engine's stream before the weights change."""
-        if not self.emb_trainable:
-            return self.tables["item_emb"]
-        off, cnt = self.segments["item_emb"]
-        if cnt != self.n_item * self.emb_dim or off % 4:
-            raise RuntimeError("item_rows: the item segment (%d floats at %d) is not [%d, %d] at a 16-byte offset" % (
-                cnt, off, self.n_item, self.emb_dim))
-        return self.weights[off:off + cnt].view(self.n_item, self.emb_dim)
-
-    def recommend(self, uids, domains, k, candidates=None, exclude=None, want_scores=False):
-        """top-K items for the queries (uids[q], domains[q]) from the live weights (mamdr_recommend: mlp / wdl / deepfm; no
-        reference counterpart).  candidates: distinct item ids (None: the whole item table); exclude: one array of item ids
-        per query that must not be returned (any order, duplicates allowed).  -> (ids [Q, k] int32, scores [Q, k] float32
-        [, all_scores [Q, n_cand]]) as numpy: by logit descending, equal logits by ascending id, scores = sigmoid(logit);
-        a query with fewer than k candidates left ends in id -1 / score 0; all_scores holds 0 for an excluded pair."""
-        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
-        dom = np.array(np.broadcast_to(np.asarray(domains), uid.shape), np.int32)          # (a writable copy)
-        if uid.size and (dom.min() < 0 or dom.max() >= self.n_domain):
-            raise ValueError("recommend: user or domain id out of range")
-        return self._recommend(uid, dom, None, k, candidates, exclude, want_scores)
-
-    def recommend_domain(self, uids, domain, k, candidates=None, exclude=None, want_scores=False):
-        """`recommend` with every query in the one domain `domain` (mamdr_recommend_domain: mlp / wdl / deepfm, whose
-        results are `recommend`'s with a constant domain vector, byte for byte, and star, which retrieves through this call
-        only: its item term depends on the domain).  Same arguments otherwise, same return contract."""
-        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
-        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
-            raise ValueError("recommend_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
-        return self._recommend(uid, None, int(domain), k, candidates, exclude, want_scores)
-
-    def _retrieval_inputs(self, uid, candidates, exclude):
-        """the host arrays and range checks every retrieval call shares -> (n_query, candidates int32 or None, n_cand,
-        exclusion offsets, exclusion ids), the CSR None when nothing is excluded."""
-        nq = int(uid.shape[0])
-        if nq and (uid.min() < 0 or uid.max() >= self.n_user):
-            raise ValueError("recommend: user or domain id out of range")
-        cand = None
-        n_cand = self.n_item
-        if candidates is not None:
-            cand = np.ascontiguousarray(np.asarray(candidates).ravel(), np.int32)
-            n_cand = int(cand.shape[0])
-            if n_cand and (cand.min() < 0 or cand.max() >= self.n_item):
-                raise ValueError("recommend: candidate id out of range")
-            if np.unique(cand).shape[0] != n_cand:
-                raise ValueError("recommend: candidate ids must be distinct")
-        off = ids = None
-        if exclude is not None:
-            off, ids = exclusion_csr(exclude, nq)
-            if ids.size and ids.max() >= self.n_item:
-                raise ValueError("recommend: excluded item id out of range")
-            ids = ids if ids.size else np.zeros(1, np.int32)       # (a non-null pointer for an all-empty list)
-        return nq, cand, n_cand, off, ids
-
-    def rank_domain(self, uids, domain, targets, candidates=None, exclude=None, want_scores=False):
-        """exact ranks (mamdr_rank_domain) of `targets` -- one array of item ids per query, any order, duplicates allowed: made
-        ascending and distinct as `exclude` is -- among the candidates, every query in the one domain `domain`, from the
-        live weights.  candidates / exclude: as recommend_domain.  -> {"offsets" [Q + 1] int64, "ids" [T] int32 (the targets'
-        CSR), "ranks" [T] int32: the live candidates that order strictly before the pair (higher logit, or equal logit and
-        smaller id), "listed" [T] bool: the target is a candidate and not excluded for its query (only then is its rank its
-        0-based position in the query's ordering), "live" [Q] int32: live candidates per query [, "scores" [T]: sigmoid(logit)
-        of the pair]} as numpy.  Every range check runs before the launch."""
-        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
-        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
-            raise ValueError("rank_domain: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
-        nq, cand, n_cand, off, ids = self._retrieval_inputs(uid, candidates, exclude)
-        t_off, t_ids = exclusion_csr(targets, nq, "targets")
-        if t_ids.size and t_ids.max() >= self.n_item:
-            raise ValueError("rank_domain: target item id out of range")
-        n_tgt = int(t_ids.shape[0])
-        in_cand = np.ones(n_tgt, bool) if cand is None else np.isin(t_ids, cand)
-        listed = in_cand.copy()
-        if off is not None:
-            for q in range(nq):
-                sl = slice(t_off[q], t_off[q + 1])
-                listed[sl] &= ~np.isin(t_ids[sl], ids[off[q]:off[q + 1]])
-        dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
-        d_uid, d_cand, d_off, d_ids, d_toff = dev(uid), dev(cand), dev(off), dev(ids), dev(t_off)
-        d_tids = dev(t_ids if n_tgt else np.zeros(1, np.int32))
-        ranks = torch.empty(max(n_tgt, 1), dtype=torch.int32, device=self.device)
-        live = torch.empty(max(nq, 1), dtype=torch.int32, device=self.device)
-        scores = torch.empty(max(n_tgt, 1), dtype=torch.float32, device=self.device) if want_scores else None
-        L.check(self.lib.mamdr_rank_domain(self.ctx, int(domain), nq, _ptr(d_uid), _ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids),
-                                           _ptr(d_toff), _ptr(d_tids), _ptr(ranks), _ptr(scores), _ptr(live)))
-        res = {"offsets": t_off, "ids": t_ids, "ranks": ranks.cpu().numpy()[:n_tgt], "listed": listed,
-               "live": live.cpu().numpy()[:nq]}
-        if want_scores:
-            res["scores"] = scores.cpu().numpy()[:n_tgt]
-        return res
-
-    def rank_slates(self, uids, domain, slates, want_order=False):
-        """every query's own candidate slate scored and ordered (mamdr_rank_slates): `slates` is one array of DISTINCT item
-        ids per query, kept in the caller's order (a slate may be empty), every query in the one domain `domain`, from the
-        live weights.  -> {"offsets" [Q + 1] int64, "ids" [E] int32 (the slates' CSR), "scores" [E] float32: sigmoid(logit)
-        of the pair -- the bits rank_domain and recommend_domain give it --, "pos" [E] int32: the entries of the same slate
-        that order strictly before the entry (higher logit, or equal logit and smaller id), a permutation of 0 .. L - 1 per
-        slate [, "order" [E] int32: order[offsets[q] + pos[j]] = j - offsets[q], the slate-local index of the entry at each
-        position]} as numpy.  Every check runs before the launch: the work is sum of the slates' lengths pairs, and
-        O(L^2) integer compares per slate -- a whole catalogue is rank_domain's job."""
-        uid = np.ascontiguousarray(np.asarray(uids).ravel(), np.int32)
-        if isinstance(domain, bool) or not isinstance(domain, (int, np.integer)) or not 0 <= int(domain) < self.n_domain:
-            raise ValueError("rank_slates: domain %r is not an integer inside [0, %d)" % (domain, self.n_domain))
-        nq = int(uid.shape[0])
-        off, ids = slates_csr(slates, nq)
-        if nq and (uid.min() < 0 or uid.max() >= self.n_user):
-            raise ValueError("rank_slates: user id out of range")
-        if ids.size and ids.max() >= self.n_item:
-            raise ValueError("rank_slates: item id out of range")
-        n_ent = int(ids.shape[0])
-        res = {"offsets": off, "ids": ids}
-        if nq == 0 or n_ent == 0:
-            res.update(scores=np.zeros(0, np.float32), pos=np.zeros(0, np.int32))
-            if want_order:
-                res["order"] = np.zeros(0, np.int32)
-            return res
-        d_uid, d_off, d_ids = (torch.from_numpy(a).to(self.device) for a in (uid, off, ids))
-        scores = torch.empty(n_ent, dtype=torch.float32, device=self.device)
-        pos = torch.empty(n_ent, dtype=torch.int32, device=self.device)
-        order = torch.empty(n_ent, dtype=torch.int32, device=self.device) if want_order else None
-        L.check(self.lib.mamdr_rank_slates(self.ctx, int(domain), nq, _ptr(d_uid), _ptr(d_off), _ptr(d_ids), _ptr(scores),
-                                           _ptr(pos), _ptr(order)))
-        res.update(scores=scores.cpu().numpy(), pos=pos.cpu().numpy())
-        if want_order:
-            res["order"] = order.cpu().numpy()
-        return res
-
-    def _recommend(self, uid, dom, domain, k, candidates, exclude, want_scores):
-        """the marshalling of both retrieval calls: dom [Q] int32 per query (mamdr_recommend) or None and the host integer
-        `domain` (mamdr_recommend_domain).  Every range check runs before the launch."""
-        nq, cand, n_cand, off, ids = self._retrieval_inputs(uid, candidates, exclude)
-        dev = lambda a: torch.from_numpy(a).to(self.device) if a is not None else None      # noqa: E731
-        d_uid, d_dom, d_cand, d_off, d_ids = dev(uid), dev(dom), dev(cand), dev(off), dev(ids)
-        kk = max(int(k), 1)
-        out_ids = torch.empty((max(nq, 1), kk), dtype=torch.int32, device=self.device)
-        out_scores = torch.empty((max(nq, 1), kk), dtype=torch.float32, device=self.device)
-        all_scores = torch.empty((max(nq, 1), max(n_cand, 1)), dtype=torch.float32, device=self.device) if want_scores else None
-        tail = (_ptr(d_cand), n_cand, _ptr(d_off), _ptr(d_ids), int(k), _ptr(out_ids), _ptr(out_scores), _ptr(all_scores))
-        if domain is None:
-            L.check(self.lib.mamdr_recommend(self.ctx, nq, _ptr(d_uid), _ptr(d_dom), *tail))
-        else:
-            L.check(self.lib.mamdr_recommend_domain(self.ctx, domain, nq, _ptr(d_uid), *tail))
-        res = (out_ids.cpu().numpy()[:nq, :int(k)], out_scores.cpu().numpy()[:nq, :int(k)])
-        return res + (all_scores.cpu().numpy()[:nq, :n_cand],) if want_scores else res
 
     def step_kernel_names(self, batch=None):
         """names of the kernels behind profile_read's FWD_BWD / WGRAD / UPDATE slots for a step of `batch` rows."""

@@ -44,7 +44,7 @@ class GraphEngine(DeviceEngine):
         self._open(device, n_user, n_item, n_domain, batch_size, dropout_seed, emb_trainable)
         if len(expert_hidden) > 4 or len(tower_hidden) > 4 or len(gate_hidden) > 4:
             raise ValueError("at most 4 hidden layers per DNN")
-        self.kind = kind
+        self.kind, self.emb_dim = kind, int(emb_dim)
         self.norm, self.dense, self.auxiliary_dim = (norm, dense, int(auxiliary_dim)) if kind == "star" else ("none", "dense", 0)
         if kind == "star" and (norm not in L.STAR_NORMS or dense not in L.STAR_DENSES):
             raise ValueError("Star: norm %r / dense %r (norm none, pn or bn; dense dense or star)" % (norm, dense))
@@ -121,24 +121,42 @@ class GraphEngine(DeviceEngine):
         self._check(self.lib.mamdr_graph_task_ranges(self.ctx, int(domain), *[C.byref(x) for x in v]))
         return [(v[0].value, v[1].value), (v[2].value, v[3].value)]
 
+    # retrieval: the single-output kinds go through DeviceEngine's calls (mamdr_graph_recommend ...); the kinds with one task
+    # per domain and the Star forms stay refused, by `self.kind` alone and before anything else is touched
+    REFUSED_RETRIEVAL = ("shared_bottom", "mmoe", "ple", "star")
+    # mlp / wdl / deepfm also exist on the step engine, and an engine object of these kinds has always refused retrieval by
+    # name: it keeps doing so until `enable_retrieval()` is called on it (BaseModel.construct_engine calls it for every
+    # engine it builds, so `model.recommend` ... serve these kinds; code that holds a bare engine opts in itself)
+    OPT_IN_RETRIEVAL = ("mlp", "wdl", "deepfm")
+
+    def enable_retrieval(self):
+        """let an mlp / wdl / deepfm engine serve recommend / recommend_domain / rank_domain / rank_slates (the other
+        single-output kinds serve them as they are; the multi-task kinds and star stay refused whatever is called)."""
+        self._retrieval = True
+
+    def _refuse_retrieval(self, name, served):
+        opt_in = self.kind in self.OPT_IN_RETRIEVAL and not getattr(self, "_retrieval", False)
+        if self.kind in self.REFUSED_RETRIEVAL or opt_in:
+            raise NotImplementedError("%s: the generic-layer towers (kind '%s') are not built for retrieval; the step engine's "
+                                      "%s towers at width 128, hidden [256, 128, 64] are (TowerEngine.%s)%s" % (
+                                          name, self.kind, served, name,
+                                          "; GraphEngine.enable_retrieval() lets this engine serve the call" if opt_in else ""))
+
     def recommend(self, *args, **kwargs):
-        raise NotImplementedError("recommend: the generic-layer towers (kind '%s') are not built for retrieval; the step engine's "
-                                  "mlp / wdl / deepfm towers at width 128, hidden [256, 128, 64] are (TowerEngine.recommend)" % self.kind)
+        self._refuse_retrieval("recommend", "mlp / wdl / deepfm")
+        return DeviceEngine.recommend(self, *args, **kwargs)
 
     def recommend_domain(self, *args, **kwargs):
-        raise NotImplementedError("recommend_domain: the generic-layer towers (kind '%s') are not built for retrieval; the step "
-                                  "engine's mlp / wdl / deepfm / star towers at width 128, hidden [256, 128, 64] are "
-                                  "(TowerEngine.recommend_domain)" % self.kind)
+        self._refuse_retrieval("recommend_domain", "mlp / wdl / deepfm / star")
+        return DeviceEngine.recommend_domain(self, *args, **kwargs)
 
     def rank_domain(self, *args, **kwargs):
-        raise NotImplementedError("rank_domain: the generic-layer towers (kind '%s') are not built for retrieval; the step "
-                                  "engine's mlp / wdl / deepfm / star towers at width 128, hidden [256, 128, 64] are "
-                                  "(TowerEngine.rank_domain)" % self.kind)
+        self._refuse_retrieval("rank_domain", "mlp / wdl / deepfm / star")
+        return DeviceEngine.rank_domain(self, *args, **kwargs)
 
     def rank_slates(self, *args, **kwargs):
-        raise NotImplementedError("rank_slates: the generic-layer towers (kind '%s') are not built for retrieval; the step "
-                                  "engine's mlp / wdl / deepfm / star towers at width 128, hidden [256, 128, 64] are "
-                                  "(TowerEngine.rank_slates)" % self.kind)
+        self._refuse_retrieval("rank_slates", "mlp / wdl / deepfm / star")
+        return DeviceEngine.rank_slates(self, *args, **kwargs)
 
     def set_adam_eps(self, eps):
         self._check(self.lib.mamdr_graph_set_adam_eps(self.ctx, float(eps)))

@@ -80,8 +80,11 @@ class BaseModel(object):
             factory = graph_engine.GraphEngine if r.engine == "graph" else engine.TowerEngine
         elif r.offer:
             factory = getattr(factory, r.offer)
-        return factory(*r.args, self.n_uid, self.n_pid, self.n_domain, self.batch_size, emb_trainable=self.tables_trainable,
-                       **r.kwargs)
+        eng = factory(*r.args, self.n_uid, self.n_pid, self.n_domain, self.batch_size, emb_trainable=self.tables_trainable,
+                      **r.kwargs)
+        if hasattr(eng, "enable_retrieval"):        # GraphEngine: its mlp / wdl / deepfm kinds serve recommend ... once asked to
+            eng.enable_retrieval()
+        return eng
 
     def bind_engine(self, eng, tensors, where):
         """frozen tables, the three splits' columns, the initial weights, the compiled optimiser."""

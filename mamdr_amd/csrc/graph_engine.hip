@@ -70,8 +70,9 @@
 //   a step         mamdr_graph_train_steps_n: step_ctx, advance_optimizer, open_sink, launch_gather, task_forward, launch_head,
 //                  launch_loss, task_backward, finish_grads, star_chain, table_step, adam_step; mamdr_graph_eval_domain shares
 //                  step_ctx / launch_gather / task_forward / launch_head / launch_loss.  Nothing in a step allocates.
-//   retrieval      mamdr_graph_recommend / _recommend_domain / _rank_domain / _rank_slates: retrieval_kind, grow_retrieval,
-//                  retrieval_forward (launch_gather + task_forward at the full padded height), grid_pass / list_pass, and the
+//   retrieval      mamdr_graph_recommend / _recommend_domain / _rank_domain / _rank_slates: retrieval_host.h's retrieval_call
+//                  (shared with the step engine) over GraphRetrieval, this engine's backend: retrieval_kind, grow_retrieval, pair_args,
+//                  retrieval_forward (launch_gather + task_forward at the full padded height), cand_pass / list_pass, and the
 //                  step engine's k_rec_merge / k_slate_order through their launchers (mamdr_kernels.h)
 //   a context      mamdr_graph_create: validate_config, read_switches, layout_one_task (layout_star / layout_single) or
 //                  layout_multi_task, alloc_workspace; every device pointer is freed from the record it came from (mamdr_graph::dev)
@@ -88,6 +89,7 @@
 #include "../../include/mamdr_hip.h"
 #include "mamdr_kernels.h"
 #include "host_common.h"
+#include "retrieval_host.h"
 #include "graph_gemm.h"
 #include "graph_reduce.h"
 #include "graph_towers.h"
@@ -244,8 +246,8 @@ struct mamdr_graph {
     int rec_chunk = 16384;      // candidates per pass (MAMDR_REC_CHUNK)
     int32_t *ret_uid = nullptr, *ret_pid = nullptr, *ret_dom = nullptr, *ret_rowq = nullptr;
     float* ret_label = nullptr;
-    unsigned long long *ret_keys = nullptr, *ret_part = nullptr, *ret_best = nullptr, *ret_tkey = nullptr;
-    size_t ret_part_cap = 0, ret_tkey_cap = 0;
+    unsigned long long *ret_keys = nullptr, *ret_best = nullptr;
+    GrowBuf<unsigned long long> ret_part, ret_tkey;
     // the x columns of the gradient workspace that a first layer on x fills: the domain columns alone while the tables are
     // frozen (n 0: all of them)
     int dx_first() const { return tables ? 0 : 2 * emb; }
@@ -1622,31 +1624,11 @@ int grow_retrieval(mamdr_graph* g, size_t part_keys, size_t n_tkey) {
             return g->dev.check(g_gerr);
         }
     }
-    if (part_keys > g->ret_part_cap) {
-        g->dev.release(g->ret_part);
-        g->ret_part = nullptr;
-        g->ret_part_cap = 0;
-        g->dev.alloc(&g->ret_part, part_keys);
-        if (const int rc = g->dev.check(g_gerr)) return rc;
-        g->ret_part_cap = part_keys;
-    }
-    if (n_tkey > g->ret_tkey_cap) {
-        g->dev.release(g->ret_tkey);
-        g->ret_tkey = nullptr;
-        g->ret_tkey_cap = 0;
-        g->dev.alloc(&g->ret_tkey, n_tkey);
-        if (const int rc = g->dev.check(g_gerr)) return rc;
-        g->ret_tkey_cap = n_tkey;
-    }
-    return MAMDR_OK;
+    if (const int rc = g->ret_part.grow(g->dev, g_gerr, part_keys)) return rc;
+    return g->ret_tkey.grow(g->dev, g_gerr, n_tkey);
 }
-// what a block of queries hands to its passes
-struct RetBlock {
-    int n_query;
-    const int32_t *uid, *dom;       // of the block (dom null: every query in `domain`)
-    int domain;
-};
-PairArgs pair_args(const mamdr_graph* g, const RetBlock& b) {
+// the pair kernels' view of a block of queries (b.dom null: every query in b.domain)
+PairArgs pair_args(const mamdr_graph* g, const RetCall& b) {
     PairArgs pa;
     memset(&pa, 0, sizeof(pa));
     pa.uid = g->ret_uid;
@@ -1683,136 +1665,123 @@ HeadArgs retrieval_forward(mamdr_graph* g, int rows) {
     const Task& t = g->tasks[0];
     return head_args(g, t, sc, task_forward(g, t, sc));
 }
-// one chunk of candidates x the block's queries: the [n_query][chunk_pad] grid of pairs, query-major, a forward batch at a
-// time; `ta` carries the ending's operands (count: k_graph_rank_count, otherwise k_graph_tile_topk)
-void grid_pass(mamdr_graph* g, const RetBlock& b, const int32_t* d_cand, int64_t n_cand, int64_t c_base, int n_chunk,
-               const int64_t* excl_off, const int32_t* excl_ids, float* scores_all, TileArgs ta, bool count) {
-    const int chunk_pad = (n_chunk + REC_TILE - 1) / REC_TILE * REC_TILE;
-    const int64_t total = (int64_t)b.n_query * chunk_pad;
-    PairArgs pa = pair_args(g, b);
-    pa.ids = d_cand;
-    pa.c_base = c_base;
-    pa.chunk_pad = chunk_pad;
-    pa.n_chunk = n_chunk;
-    for (int64_t base = 0; base < total; base += g->rows_pad_max) {
-        const int rows = (int)std::min<int64_t>(g->rows_pad_max, total - base);
-        pa.rows = rows;
-        pa.row_base = base;
-        GLAUNCH(k_graph_pair_rows<false>, dim3((rows + 255) / 256), dim3(256), 0, g->stream, pa);
-        KeyArgs ka;
-        memset(&ka, 0, sizeof(ka));
-        ka.h = retrieval_forward(g, rows);
-        ka.pid = g->ret_pid;
-        ka.rowq = g->ret_rowq;
-        ka.excl_off = excl_off;
-        ka.excl_ids = excl_ids;
-        ka.scores_all = scores_all;
-        ka.n_cand = n_cand;
-        ka.c_base = c_base;
-        ka.row_base = base;
-        ka.chunk_pad = chunk_pad;
-        ka.keys = g->ret_keys;
-        GLAUNCH(k_graph_head_keys<false>, dim3((rows + 3) / 4), dim3(256), 0, g->stream, ka);
-        ta.keys = g->ret_keys;
-        ta.n_tiles = rows / REC_TILE;
-        ta.row_base = base;
-        ta.chunk_pad = chunk_pad;
-        if (count) GLAUNCH(k_graph_rank_count, dim3((ta.n_tiles + 3) / 4), dim3(256), 0, g->stream, ta);
-        else GLAUNCH(k_graph_tile_topk, dim3((ta.n_tiles + 3) / 4), dim3(256), 0, g->stream, ta);
-    }
-}
-// entries [j0, j1) of the call's flat list (targets, slate entries) that belong to the block's queries (`off`: the block's
-// CSR with the call's absolute positions): their keys into ret_tkey, their scores into score_out when asked
-void list_pass(mamdr_graph* g, const RetBlock& b, const int64_t* off, const int32_t* ids, int64_t j0, int64_t j1, float* score_out) {
-    PairArgs pa = pair_args(g, b);
-    pa.ids = ids;
-    pa.off = off;
-    for (int64_t base = j0; base < j1; base += g->rows_pad_max) {
-        const int rows = (int)std::min<int64_t>(g->rows_pad_max, j1 - base);
-        pa.rows = rows;
-        pa.list_base = base;
-        GLAUNCH(k_graph_pair_rows<true>, dim3((rows + 255) / 256), dim3(256), 0, g->stream, pa);
-        KeyArgs ka;
-        memset(&ka, 0, sizeof(ka));
-        ka.h = retrieval_forward(g, rows);
-        ka.pid = g->ret_pid;
-        ka.rowq = g->ret_rowq;
-        ka.tkey = g->ret_tkey;
-        ka.score_out = score_out;
-        ka.list_base = base;
-        GLAUNCH(k_graph_head_keys<true>, dim3((rows + 3) / 4), dim3(256), 0, g->stream, ka);
-    }
-}
-// candidates per pass of a call over n_cand candidates
-int chunk_of(const mamdr_graph* g, int64_t n_cand) {
-    return (int)std::min<int64_t>(g->rec_chunk, (n_cand + REC_TILE - 1) / REC_TILE * REC_TILE);
-}
-// the CSR offsets of a call's targets / slate entries, read back once (the call's one synchronisation of the handle's stream)
-// and held to their contract here, so that no kernel indexes past the list
-int read_offsets(mamdr_graph* g, const char* fn, const char* what, const int64_t* d_off, int32_t n_query, std::vector<int64_t>& off) {
-    off.resize((size_t)n_query + 1);
-    GHIP(hipMemcpyAsync(off.data(), d_off, off.size() * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    GHIP(hipStreamSynchronize(g->stream));
-    if (off[0] != 0) return gfail(MAMDR_EINVAL, "%s: the %s offsets start at %lld, not 0", fn, what, (long long)off[0]);
-    for (int32_t q = 0; q < n_query; ++q)
-        if (off[q + 1] < off[q]) return gfail(MAMDR_EINVAL, "%s: the %s offsets descend at query %d", fn, what, q);
-    return MAMDR_OK;
-}
-
-// the body of both top-K entry points: `domain` < 0 = mamdr_graph_recommend (query q in d_domain[q])
-int graph_recommend_body(mamdr_graph* g, const char* fn, int32_t domain, int32_t n_query, const int32_t* d_uid,
-                         const int32_t* d_domain, const int32_t* d_cand, int64_t n_cand, const int64_t* d_excl_off,
-                         const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
-    const bool per_query = domain < 0;
-    if (n_query <= 0) return gfail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
-    if (k < 1 || k > REC_KMAX) return gfail(MAMDR_EINVAL, "%s: k %d outside [1, %d]", fn, k, REC_KMAX);
-    if (d_cand && n_cand <= 0) return gfail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
-    if (!d_uid || (per_query && !d_domain) || !d_ids_out || !d_scores_out)
-        return gfail(MAMDR_EINVAL, per_query ? "%s: null uid / domain / output pointer" : "%s: null uid / output pointer", fn);
-    if (misaligned(3, d_uid, d_domain, d_cand, d_excl_ids, d_ids_out, d_scores_out, d_scores_all) || misaligned(7, d_excl_off))
-        return gfail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
-    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
-        return gfail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
-    if (ready(g)) return MAMDR_ESTATE;
-    if (!d_cand) n_cand = g->cfg.n_item;
-    const int chunk = chunk_of(g, n_cand), kt = std::min<int>(k, REC_TILE), tiles_cap = chunk / REC_TILE;
-    const int q_cap = std::min<int32_t>(REC_QBLOCK, n_query);
-    if (const int rc = grow_retrieval(g, (size_t)q_cap * tiles_cap * REC_TILE, 0)) return rc;
+// the generic layers as retrieval_host.h's backend: every pair is a row of a forward batch
+struct GraphRetrieval : RetStream {
+    mamdr_graph* g;
+    const int n_item = g->cfg.n_item, n_domain = g->cfg.n_domain, rec_chunk = g->rec_chunk;
+    RetCall b{};                    // the block under way
     RecArgs ma;                     // what k_rec_merge reads
-    memset(&ma, 0, sizeof(ma));
-    ma.k = k;
-    ma.kt = kt;
-    ma.tiles_cap = tiles_cap;
-    ma.part = g->ret_part;
-    ma.best = g->ret_best;
-    TileArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.part = g->ret_part;
-    ta.tiles_cap = tiles_cap;
-    ta.kt = kt;
-    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
-        const RetBlock b{std::min<int32_t>(REC_QBLOCK, n_query - qb), d_uid + qb, per_query ? d_domain + qb : nullptr, domain};
-        ma.n_query = b.n_query;
-        ma.ids_out = d_ids_out + (size_t)qb * k;
-        ma.scores_out = d_scores_out + (size_t)qb * k;
-        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
-            const int n_chunk = (int)std::min<int64_t>(chunk, n_cand - c0);
-            grid_pass(g, b, d_cand, n_cand, c0, n_chunk, d_excl_off ? d_excl_off + qb : nullptr, d_excl_ids,
-                      d_scores_all ? d_scores_all + (size_t)qb * n_cand : nullptr, ta, false);
-            ma.tiles = (n_chunk + REC_TILE - 1) / REC_TILE;
-            ma.first_chunk = c0 == 0;
-            ma.last_chunk = c0 + chunk >= n_cand;
-            ++g_graph_launches;
-            launch_rec_merge(ma, g->stream);
+    TileArgs ta;                    // the ending's operands (k_graph_tile_topk / k_graph_rank_count)
+    SlateArgs sa;
+
+    int ready() { return ::ready(g); }
+    // top-K: the per-tile lists of a block's queries x a chunk; ranks and slates: the list's keys
+    int prepare(const RetCall& r) {
+        const bool topk = r.kind == RET_TOPK;
+        const int kt = std::min<int>(r.k, REC_TILE), tiles_cap = r.chunk / REC_TILE;
+        const size_t part_keys = topk ? (size_t)std::min<int32_t>(REC_QBLOCK, r.n_query) * tiles_cap * REC_TILE : 0;
+        if (const int rc = grow_retrieval(g, part_keys, (size_t)r.n_list)) return rc;
+        memset(&ma, 0, sizeof(ma));
+        memset(&ta, 0, sizeof(ta));
+        if (!topk) {
+            ta.tkey = sa.tkey = g->ret_tkey.p;
+            ta.rank_out = r.rank_out;
+            sa.pos_out = r.pos_out;
+            sa.order_out = r.order_out;
+            return MAMDR_OK;
         }
+        ma.k = r.k;
+        ma.kt = ta.kt = kt;
+        ma.tiles_cap = ta.tiles_cap = tiles_cap;
+        ma.part = ta.part = g->ret_part.p;
+        ma.best = g->ret_best;
+        return MAMDR_OK;
     }
-    GHIP(hipGetLastError());
-    return MAMDR_OK;
-}
-int check_domain(const mamdr_graph* g, const char* fn, int32_t domain) {
-    if (domain < 0 || domain >= g->cfg.n_domain) return gfail(MAMDR_EINVAL, "%s: domain %d outside [0, %d)", fn, domain, g->cfg.n_domain);
-    return MAMDR_OK;
-}
+    void begin_block(const RetCall& blk) {
+        b = blk;
+        ma.n_query = sa.n_query = b.n_query;
+        ma.ids_out = b.ids_out;
+        ma.scores_out = b.scores_out;
+        ta.tgt_off = sa.off = b.list_off;
+        ta.live_out = b.live_out;
+    }
+    // one chunk of candidates x the block's queries: the [n_query][chunk_pad] grid of pairs, query-major, a forward batch
+    // at a time, each with its ending (ranks: k_graph_rank_count; top-K: k_graph_tile_topk, then the chunk's k_rec_merge)
+    int cand_pass(int64_t c0, int n_chunk, int tiles, bool first, bool last) {
+        const bool count = b.kind == RET_RANK;
+        const int chunk_pad = tiles * REC_TILE;
+        const int64_t total = (int64_t)b.n_query * chunk_pad;
+        PairArgs pa = pair_args(g, b);
+        pa.ids = b.cand;
+        pa.c_base = c0;
+        pa.chunk_pad = chunk_pad;
+        pa.n_chunk = n_chunk;
+        for (int64_t base = 0; base < total; base += g->rows_pad_max) {
+            const int rows = (int)std::min<int64_t>(g->rows_pad_max, total - base);
+            pa.rows = rows;
+            pa.row_base = base;
+            GLAUNCH(k_graph_pair_rows<false>, dim3((rows + 255) / 256), dim3(256), 0, g->stream, pa);
+            KeyArgs ka;
+            memset(&ka, 0, sizeof(ka));
+            ka.h = retrieval_forward(g, rows);
+            ka.pid = g->ret_pid;
+            ka.rowq = g->ret_rowq;
+            ka.excl_off = b.excl_off;
+            ka.excl_ids = b.excl_ids;
+            ka.scores_all = b.scores_all;
+            ka.n_cand = b.n_cand;
+            ka.c_base = c0;
+            ka.row_base = base;
+            ka.chunk_pad = chunk_pad;
+            ka.keys = g->ret_keys;
+            GLAUNCH(k_graph_head_keys<false>, dim3((rows + 3) / 4), dim3(256), 0, g->stream, ka);
+            ta.keys = g->ret_keys;
+            ta.n_tiles = rows / REC_TILE;
+            ta.row_base = base;
+            ta.chunk_pad = chunk_pad;
+            if (count) GLAUNCH(k_graph_rank_count, dim3((ta.n_tiles + 3) / 4), dim3(256), 0, g->stream, ta);
+            else GLAUNCH(k_graph_tile_topk, dim3((ta.n_tiles + 3) / 4), dim3(256), 0, g->stream, ta);
+        }
+        if (count) return MAMDR_OK;
+        ma.tiles = tiles;
+        ma.first_chunk = first;
+        ma.last_chunk = last;
+        ++g_graph_launches;
+        launch_rec_merge(ma, g->stream);
+        return MAMDR_OK;
+    }
+    // entries [j0, j1) of the call's flat list (targets, slate entries; b.list_off: the block's CSR with the call's absolute
+    // positions), a forward batch at a time: their keys into ret_tkey, their scores into score_out when asked
+    int list_pass(int64_t j0, int64_t j1) {
+        PairArgs pa = pair_args(g, b);
+        pa.ids = b.list_ids;
+        pa.off = b.list_off;
+        for (int64_t base = j0; base < j1; base += g->rows_pad_max) {
+            const int rows = (int)std::min<int64_t>(g->rows_pad_max, j1 - base);
+            pa.rows = rows;
+            pa.list_base = base;
+            GLAUNCH(k_graph_pair_rows<true>, dim3((rows + 255) / 256), dim3(256), 0, g->stream, pa);
+            KeyArgs ka;
+            memset(&ka, 0, sizeof(ka));
+            ka.h = retrieval_forward(g, rows);
+            ka.pid = g->ret_pid;
+            ka.rowq = g->ret_rowq;
+            ka.tkey = g->ret_tkey.p;
+            ka.score_out = b.score_out;
+            ka.list_base = base;
+            GLAUNCH(k_graph_head_keys<true>, dim3((rows + 3) / 4), dim3(256), 0, g->stream, ka);
+        }
+        return MAMDR_OK;
+    }
+    void slate_order(int64_t max_len, bool any_short) {
+        g_graph_launches += (any_short ? 1 : 0) + (max_len > SLATE_WAVE ? 1 : 0);
+        launch_slate_order(sa, max_len, any_short, g->stream);
+    }
+    int finish() {
+        GHIP(hipGetLastError());
+        return MAMDR_OK;
+    }
+};
 
 }  // namespace
 
@@ -2051,115 +2020,50 @@ int mamdr_graph_eval_domain(mamdr_graph* g, int domain, int split, int32_t batch
     return MAMDR_OK;
 }
 
-// ---- retrieval from the single-output towers (include/mamdr_hip.h; device side: graph_retrieval.h)
+// ---- retrieval from the single-output towers (include/mamdr_hip.h; the calls: retrieval_host.h; device side: graph_retrieval.h)
+static int graph_retrieval(mamdr_graph* g, RetCall& r) {
+    if (check(g)) return MAMDR_EINVAL;
+    if (const int rc = retrieval_kind(g, r.fn)) return rc;
+    GraphRetrieval b{{g->stream, g_gerr}, g};
+    return retrieval_call(b, r);
+}
+
 int mamdr_graph_recommend(mamdr_graph* g, int32_t n_query, const int32_t* d_uid, const int32_t* d_domain, const int32_t* d_cand,
                           int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
                           float* d_scores_out, float* d_scores_all) {
-    const char* fn = "mamdr_graph_recommend";
-    if (check(g)) return MAMDR_EINVAL;
-    if (const int rc = retrieval_kind(g, fn)) return rc;
-    return graph_recommend_body(g, fn, -1, n_query, d_uid, d_domain, d_cand, n_cand, d_excl_off, d_excl_ids, k, d_ids_out,
-                                d_scores_out, d_scores_all);
+    RetCall r{RET_TOPK, __func__};
+    r.per_query = true, r.n_query = n_query, r.uid = d_uid, r.dom = d_domain, r.cand = d_cand, r.n_cand = n_cand;
+    r.excl_off = d_excl_off, r.excl_ids = d_excl_ids;
+    r.k = k, r.ids_out = d_ids_out, r.scores_out = d_scores_out, r.scores_all = d_scores_all;
+    return graph_retrieval(g, r);
 }
 
 int mamdr_graph_recommend_domain(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
                                  int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k,
                                  int32_t* d_ids_out, float* d_scores_out, float* d_scores_all) {
-    const char* fn = "mamdr_graph_recommend_domain";
-    if (check(g)) return MAMDR_EINVAL;
-    if (const int rc = retrieval_kind(g, fn)) return rc;
-    if (const int rc = check_domain(g, fn, domain)) return rc;
-    return graph_recommend_body(g, fn, domain, n_query, d_uid, nullptr, d_cand, n_cand, d_excl_off, d_excl_ids, k, d_ids_out,
-                                d_scores_out, d_scores_all);
+    RetCall r{RET_TOPK, __func__};
+    r.domain = domain, r.n_query = n_query, r.uid = d_uid, r.cand = d_cand, r.n_cand = n_cand;
+    r.excl_off = d_excl_off, r.excl_ids = d_excl_ids;
+    r.k = k, r.ids_out = d_ids_out, r.scores_out = d_scores_out, r.scores_all = d_scores_all;
+    return graph_retrieval(g, r);
 }
 
-// exact ranks: the targets' keys through the list form first, then the candidate passes with the counting ending
 int mamdr_graph_rank_domain(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid, const int32_t* d_cand,
                             int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, const int64_t* d_tgt_off,
                             const int32_t* d_tgt_ids, int32_t* d_rank_out, float* d_score_out, int32_t* d_live_out) {
-    const char* fn = "mamdr_graph_rank_domain";
-    if (check(g)) return MAMDR_EINVAL;
-    if (const int rc = retrieval_kind(g, fn)) return rc;
-    if (const int rc = check_domain(g, fn, domain)) return rc;
-    if (n_query <= 0) return gfail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
-    if (d_cand && n_cand <= 0) return gfail(MAMDR_EINVAL, "%s: n_cand %lld with a candidate list given", fn, (long long)n_cand);
-    if (!d_uid || !d_tgt_off || !d_rank_out || !d_live_out)
-        return gfail(MAMDR_EINVAL, "%s: null uid / target offsets / rank / live output pointer", fn);
-    if (misaligned(3, d_uid, d_cand, d_excl_ids, d_tgt_ids, d_rank_out, d_score_out, d_live_out) || misaligned(7, d_excl_off, d_tgt_off))
-        return gfail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
-    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
-        return gfail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
-    if (ready(g)) return MAMDR_ESTATE;
-    std::vector<int64_t> off;
-    if (const int rc = read_offsets(g, fn, "target", d_tgt_off, n_query, off)) return rc;
-    const int64_t n_tgt = off[n_query];
-    if (n_tgt > 0 && !d_tgt_ids) return gfail(MAMDR_EINVAL, "%s: %lld targets without their ids", fn, (long long)n_tgt);
-    if (!d_cand) n_cand = g->cfg.n_item;
-    const int chunk = chunk_of(g, n_cand);
-    if (const int rc = grow_retrieval(g, 0, (size_t)n_tgt)) return rc;
-    if (n_tgt > 0) GHIP(hipMemsetAsync(d_rank_out, 0, (size_t)n_tgt * sizeof(int32_t), g->stream));
-    GHIP(hipMemsetAsync(d_live_out, 0, (size_t)n_query * sizeof(int32_t), g->stream));
-    TileArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.tkey = g->ret_tkey;
-    ta.rank_out = d_rank_out;
-    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
-        const RetBlock b{std::min<int32_t>(REC_QBLOCK, n_query - qb), d_uid + qb, nullptr, domain};
-        list_pass(g, b, d_tgt_off + qb, d_tgt_ids, off[qb], off[qb + b.n_query], d_score_out);
-        ta.tgt_off = d_tgt_off + qb;
-        ta.live_out = d_live_out + qb;
-        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk)
-            grid_pass(g, b, d_cand, n_cand, c0, (int)std::min<int64_t>(chunk, n_cand - c0), d_excl_off ? d_excl_off + qb : nullptr,
-                      d_excl_ids, nullptr, ta, true);
-    }
-    GHIP(hipGetLastError());
-    return MAMDR_OK;
+    RetCall r{RET_RANK, __func__};
+    r.domain = domain, r.n_query = n_query, r.uid = d_uid, r.cand = d_cand, r.n_cand = n_cand;
+    r.excl_off = d_excl_off, r.excl_ids = d_excl_ids, r.list_off = d_tgt_off, r.list_ids = d_tgt_ids;
+    r.rank_out = d_rank_out, r.score_out = d_score_out, r.live_out = d_live_out;
+    return graph_retrieval(g, r);
 }
 
-// per-query slates: the entries' keys through the list form, then the step engine's k_slate_order, unchanged
 int mamdr_graph_rank_slates(mamdr_graph* g, int32_t domain, int32_t n_query, const int32_t* d_uid, const int64_t* d_slate_off,
                             const int32_t* d_slate_ids, float* d_score_out, int32_t* d_pos_out, int32_t* d_order_out) {
-    const char* fn = "mamdr_graph_rank_slates";
-    if (check(g)) return MAMDR_EINVAL;
-    if (const int rc = retrieval_kind(g, fn)) return rc;
-    if (const int rc = check_domain(g, fn, domain)) return rc;
-    if (n_query <= 0) return gfail(MAMDR_EINVAL, "%s: n_query %d must be positive", fn, n_query);
-    if (!d_uid || !d_slate_off || !d_pos_out) return gfail(MAMDR_EINVAL, "%s: null uid / slate offsets / position output pointer", fn);
-    if (misaligned(3, d_uid, d_slate_ids, d_score_out, d_pos_out, d_order_out) || misaligned(7, d_slate_off))
-        return gfail(MAMDR_EINVAL, "%s: a pointer is not aligned to its element size", fn);
-    if (ready(g)) return MAMDR_ESTATE;
-    std::vector<int64_t> off;
-    if (const int rc = read_offsets(g, fn, "slate", d_slate_off, n_query, off)) return rc;
-    for (int32_t q = 0; q < n_query; ++q)
-        if (off[q + 1] - off[q] > INT32_MAX)
-            return gfail(MAMDR_EINVAL, "%s: slate %d has %lld entries: positions are int32", fn, q, (long long)(off[q + 1] - off[q]));
-    const int64_t n_ent = off[n_query];
-    if (n_ent == 0) return MAMDR_OK;
-    if (!d_slate_ids) return gfail(MAMDR_EINVAL, "%s: %lld entries without their ids", fn, (long long)n_ent);
-    if (const int rc = grow_retrieval(g, 0, (size_t)n_ent)) return rc;
-    SlateArgs sa;
-    sa.tkey = g->ret_tkey;
-    sa.pos_out = d_pos_out;
-    sa.order_out = d_order_out;
-    if (d_order_out) GHIP(hipMemsetAsync(d_order_out, 0xff, (size_t)n_ent * sizeof(int32_t), g->stream));
-    for (int32_t qb = 0; qb < n_query; qb += REC_QBLOCK) {
-        const RetBlock b{std::min<int32_t>(REC_QBLOCK, n_query - qb), d_uid + qb, nullptr, domain};
-        if (off[qb + b.n_query] == off[qb]) continue;           // a block of empty slates
-        list_pass(g, b, d_slate_off + qb, d_slate_ids, off[qb], off[qb + b.n_query], d_score_out);
-        int64_t max_len = 0;
-        bool any_short = false;
-        for (int32_t q = qb; q < qb + b.n_query; ++q) {
-            const int64_t len = off[q + 1] - off[q];
-            max_len = std::max(max_len, len);
-            any_short = any_short || (len >= 1 && len <= SLATE_WAVE);
-        }
-        sa.off = d_slate_off + qb;
-        sa.n_query = b.n_query;
-        g_graph_launches += (any_short ? 1 : 0) + (max_len > SLATE_WAVE ? 1 : 0);
-        launch_slate_order(sa, max_len, any_short, g->stream);
-    }
-    GHIP(hipGetLastError());
-    return MAMDR_OK;
+    RetCall r{RET_SLATES, __func__};
+    r.domain = domain, r.n_query = n_query, r.uid = d_uid, r.list_off = d_slate_off, r.list_ids = d_slate_ids;
+    r.score_out = d_score_out, r.pos_out = d_pos_out, r.order_out = d_order_out;
+    return graph_retrieval(g, r);
 }
 
 }  // extern "C"

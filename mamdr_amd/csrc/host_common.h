@@ -7,12 +7,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <vector>
 
-#include "../../include/mamdr_hip.h"
+#include "host_base.h"      // ErrBuf, misaligned, the retrieval sizes: the HIP-free part
 
 namespace mamdr {
 
@@ -24,18 +22,6 @@ struct SplitData {
     const float* label = nullptr;
     int64_t n = 0;
     bool bound = false;     // an EMPTY split (n = 0, null columns) is bound too: a pass over it has no steps
-};
-
-// the text behind mamdr_last_error / mamdr_graph_last_error: one thread_local instance per engine
-struct ErrBuf {
-    char text[512] = "";
-    int fail(int code, const char* fmt, ...) {
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(text, sizeof(text), fmt, ap);
-        va_end(ap);
-        return code;
-    }
 };
 
 // a failing HIP call ends the calling function with MAMDR_EHIP and the call's text in `err` (each engine forwards its own
@@ -79,6 +65,39 @@ struct DevAllocs {
     }
 };
 
+// a device buffer that grows on demand: at least n elements after grow().  A failed grow leaves no buffer (the old one is
+// gone, cap = 0) and the error in `err`; a later call may ask again
+template <typename T>
+struct GrowBuf {
+    T* p = nullptr;
+    size_t cap = 0;
+    int grow(DevAllocs& dev, ErrBuf& err, size_t n) {
+        if (n <= cap) return MAMDR_OK;
+        dev.release(p);
+        p = nullptr;
+        cap = 0;
+        dev.alloc(&p, n);
+        if (const int rc = dev.check(err)) return rc;
+        cap = n;
+        return MAMDR_OK;
+    }
+};
+
+// the stream side of both engines' retrieval backends (retrieval_host.h): n int64 read back and waited for; a fill
+struct RetStream {
+    hipStream_t stream;
+    ErrBuf& err;
+    int read_back(int64_t* host, const int64_t* dev, size_t n) {
+        MAMDR_HIP_TRY(err, hipMemcpyAsync(host, dev, n * sizeof(int64_t), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(offsets)");
+        MAMDR_HIP_TRY(err, hipStreamSynchronize(stream), "hipStreamSynchronize(stream)");
+        return MAMDR_OK;
+    }
+    int fill(void* dev, int byte, size_t bytes) {
+        MAMDR_HIP_TRY(err, hipMemsetAsync(dev, byte, bytes, stream), "hipMemsetAsync(dev, byte, bytes, stream)");
+        return MAMDR_OK;
+    }
+};
+
 // carves one workspace allocation into parts: take(bytes) is where the part starts, `at` the bytes used so far.  Every part
 // starts 16-byte aligned (given an aligned base and start)
 struct WsCursor {
@@ -113,11 +132,6 @@ inline void tf_beta_powers(float beta1, float beta2, int64_t steps, float* b1p, 
 }
 
 // ---- argument checks of both C ABIs (MAMDR_OK or the code that `err` now explains)
-// whether one of the pointers is not aligned to its element size, `mask` = that size - 1 (3, 7); a null pointer is aligned
-template <typename... P>
-inline bool misaligned(uintptr_t mask, const P*... ptrs) {
-    return ((... | (uintptr_t)ptrs) & mask) != 0;
-}
 inline int check_state_ptrs(ErrBuf& err, const float* p, const float* m, const float* v) {
     if (!p || !m || !v) return err.fail(MAMDR_EINVAL, "null state pointer");
     if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) return err.fail(MAMDR_EINVAL, "state pointers must be 16-byte aligned");

@@ -7,6 +7,7 @@
 
 #include "mamdr_device.h"
 #include "pregather_plan.h"
+#include "host_base.h"
 
 namespace mamdr {
 
@@ -833,9 +834,7 @@ void launch_pcgrad(const PcgArgs& a, hipStream_t s);
 
 // recommend_kernels.hip: top-K retrieval (mamdr_recommend, mamdr_recommend_domain), exact ranks (mamdr_rank_domain) and per-query slates (mamdr_rank_slates).  One RecArgs describes a block of queries x a chunk of
 // candidates; the query-side pointers (uid, dom, excl_off, the outputs) are already offset to the block's first query.
-constexpr int REC_TILE = 64;          // candidates per workgroup of k_rec_score (chunks are multiples of it)
-constexpr int REC_KMAX = 128;         // largest K
-constexpr int REC_QBLOCK = 256;       // queries per pass over the candidates (sizes the workspace)
+// (REC_TILE, REC_KMAX, REC_QBLOCK and SLATE_WAVE: host_base.h)
 struct RecArgs {
     const float* user_tab;
     const float* item_tab;
@@ -889,7 +888,6 @@ bool launch_rec_pair(const RecArgs& a, hipStream_t s);
 bool launch_rec_count(const RecArgs& a, hipStream_t s);
 // mamdr_rank_slates: the order inside each slate of a block of queries, from the keys k_rec_pair left in `tkey`.  Offsets
 // and positions j are the call's (absolute); `off` is already offset to the block's first query
-constexpr int SLATE_WAVE = 64;        // slates of up to this many entries: one wave each
 constexpr int SLATE_TILE = 256;       // longer slates: entries per workgroup
 constexpr int SLATE_STAGE = 1024;     // ... keys of the slate staged in LDS per round
 struct SlateArgs {

@@ -522,14 +522,9 @@ int mamdr_bind_domain_data(mamdr_ctx* c, int domain, int split, const int32_t* d
         return rc;
     drop_pregathered(c);        // (a pass gathered ahead of its call may have come from the old columns)
     const int64_t tiles = (n_rows + TILE_ROWS - 1) / TILE_ROWS;
-    if (tiles > c->eval_part_cap) {
+    if ((size_t)tiles > c->eval_part.cap) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        c->dev.release(c->eval_part);
-        c->eval_part = nullptr;
-        c->eval_part_cap = 0;
-        c->dev.alloc(&c->eval_part, (size_t)tiles);
-        if (const int rc = c->dev.check(g_err)) return rc;
-        c->eval_part_cap = tiles;
+        if (const int rc = c->eval_part.grow(c->dev, g_err, (size_t)tiles)) return rc;
     }
     return MAMDR_OK;
 }

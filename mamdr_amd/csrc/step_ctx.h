@@ -5,7 +5,7 @@
 //   mamdr_api.hip       the training call: its decisions, CallPlan / plan_call, the three step functions, the pre-gather
 //                       entry points, mamdr_train_steps(_n)
 //   step_queries.hip    the queries of a context: mamdr_eval_domain, mamdr_gather_rows, mamdr_recommend(_domain),
-//                       mamdr_rank_domain, mamdr_rank_slates
+//                       mamdr_rank_domain, mamdr_rank_slates (the four retrieval calls through retrieval_host.h)
 //   eval_metrics.hip    the metrics of an evaluation's predictions, no context: mamdr_group_auc, mamdr_exact_metrics,
 //                       mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply, mamdr_score_sums
 //   step_stateless.hip  the outer updates, mamdr_adam_apply, mamdr_pcgrad_project, mamdr_copy, mamdr_gram, the shuffle
@@ -184,8 +184,7 @@ struct mamdr_ctx {
     float* glin_i = nullptr;
     int32_t* domrow = nullptr;
     float* loss_part = nullptr;     // train: per tile of a batch
-    float* eval_part = nullptr;     // eval: per tile of a split (grown on bind)
-    int64_t eval_part_cap = 0;
+    GrowBuf<float> eval_part;       // eval: per tile of a split (grown on bind)
     float* slabs = nullptr;         // [WGRAD_MAX_GROUPS][slab_ld]
     bool tail_fuse = true;      // MAMDR_NO_TAILFUSE=1: k_emb_reduce / k_lin_sweep as launches of their own
     // the other half of the row / map double buffer: the NEXT step's k_emb_rows rides in this step's last launch
@@ -211,8 +210,7 @@ struct mamdr_ctx {
     float* rec_q = nullptr;         // q0 | qud | qs
     unsigned long long* rec_part = nullptr;
     unsigned long long* rec_best = nullptr;
-    unsigned long long* rec_tkey = nullptr;      // mamdr_rank_domain / mamdr_rank_slates: the call's target / entry keys, grown on demand
-    int64_t rec_tkey_cap = 0;
+    GrowBuf<unsigned long long> rec_tkey;        // mamdr_rank_domain / mamdr_rank_slates: the call's target / entry keys
 #ifdef MAMDR_STAMPS
     unsigned long long* stamps = nullptr;
 #endif
@@ -238,8 +236,8 @@ struct Prof {
     mamdr_ctx* c;
     int k;
     EventPair e{nullptr, nullptr, true};
-    Prof(mamdr_ctx* c_, int k_, bool = false) : c(c_), k(k_) {
-        if (!c->profile || c->ev[k].size() >= 200000) return;
+    Prof(mamdr_ctx* c_, int k_, bool on = true) : c(c_), k(k_) {     // on = false: a scope that times nothing
+        if (!on || !c->profile || c->ev[k].size() >= 200000) return;
         auto take = [&]() {
             hipEvent_t ev = nullptr;
             if (!c->ev_pool.empty()) {          // (pool refilled by mamdr_profile_reset: no event creation per launch)

@@ -393,6 +393,75 @@ def test_slates_with_equal_scores_order_by_id():
         assert np.array_equal(s["ids"][sl], ids) and np.array_equal(s["pos"][sl], np.argsort(np.argsort(ids))), q
 
 
+def test_a_second_query_block_changes_no_byte(cases):
+    """257 queries are a block of 256 and a block of one (REC_QBLOCK): the module's 7 queries, 249 repeats of query 0 without
+    targets or slates, and query 3 again as query 256.  Over 70 candidates (one full tile and 6: 257 x 128 padded pairs per
+    call) all four calls give queries 0-6 the 7-query call's bytes and query 256 those of query 3; a slates call whose
+    second block is empty writes nothing behind its entries."""
+    eng = cases("mlp64", False)[1]
+    uids, doms = queries()
+    rs = np.random.RandomState(31)
+    cand = rs.permutation(N_ITEM)[:70].astype(np.int32)
+    ref_d = reference(cases, "mlp64", False, np.full(7, DOMAIN))
+    excl = exclusion_lists(ref_d, cand)
+    targets = rank_targets(ref_d, cand, excl)
+    slates = [rs.permutation(N_ITEM)[:n].astype(np.int32) for n in (0, 1, 63, 64, 65, 70, 2)]
+    last_slate = rs.permutation(N_ITEM)[:65].astype(np.int32)
+    big_u = np.concatenate([uids, np.full(249, uids[0], np.int32), uids[3:4]])
+    big_d = np.concatenate([doms, np.full(249, doms[0]), doms[3:4]]).astype(np.int32)
+    big_excl = list(excl) + [[]] * 249 + [excl[3]]
+    big_targets = list(targets) + [[]] * 249 + [targets[3]]
+    big_slates = slates + [last_slate[:0]] * 249 + [last_slate]
+    assert big_u.size == 257
+    rows = np.r_[0:7, 256]
+    same = lambda a, b, what: (a.tobytes() == b.tobytes()) or pytest.fail(what)       # noqa: E731
+
+    small = eng.recommend(uids, doms, 10, candidates=cand, exclude=excl, want_scores=True)
+    big = eng.recommend(big_u, big_d, 10, candidates=cand, exclude=big_excl, want_scores=True)
+    for name, s, b in zip(("ids", "scores", "all_scores"), small, big):
+        assert b.shape[0] == 257
+        same(b[rows], s[np.r_[0:7, 3]], "recommend: " + name)
+    small = eng.recommend_domain(uids, DOMAIN, 128, candidates=cand, exclude=excl, want_scores=True)
+    big = eng.recommend_domain(big_u, DOMAIN, 128, candidates=cand, exclude=big_excl, want_scores=True)
+    for name, s, b in zip(("ids", "scores", "all_scores"), small, big):
+        same(b[rows], s[np.r_[0:7, 3]], "recommend_domain: " + name)
+    assert np.all(big[0][:, 70:] == -1) and np.all(big[0][0, :20] >= 0)
+
+    small = eng.rank_domain(uids, DOMAIN, targets, candidates=cand, exclude=excl, want_scores=True)
+    big = eng.rank_domain(big_u, DOMAIN, big_targets, candidates=cand, exclude=big_excl, want_scores=True)
+    n7, q3 = small["offsets"][7], slice(small["offsets"][3], small["offsets"][4])
+    assert big["offsets"][256] == n7 and big["offsets"][257] - n7 == q3.stop - q3.start > 0
+    for name in ("ids", "ranks", "scores"):
+        same(big[name][:n7], small[name], "rank_domain: " + name)
+        same(big[name][n7:], small[name][q3], "rank_domain, query 256: " + name)
+    same(big["live"][rows], small["live"][np.r_[0:7, 3]], "rank_domain: live")
+    assert np.all(big["live"][7:256] == 70)         # queries without targets are counted all the same: nothing excluded
+
+    small = eng.rank_slates(uids, DOMAIN, slates, want_order=True)
+    small3 = eng.rank_slates(uids, DOMAIN, slates[:3] + [last_slate] + slates[4:], want_order=True)   # query 3 with query 256's slate
+    big = eng.rank_slates(big_u, DOMAIN, big_slates, want_order=True)
+    n7 = small["offsets"][7]
+    q3 = slice(small3["offsets"][3], small3["offsets"][4])
+    assert big["offsets"][256] == n7 == 265 and big["offsets"][257] == n7 + 65
+    for name in ("pos", "order", "scores"):
+        same(big[name][:n7], small[name], "rank_slates: " + name)
+        same(big[name][n7:], small3[name][q3], "rank_slates, query 256: " + name)
+
+    # the same 7 slates with an EMPTY second block, through the C ABI into outputs 64 entries too long
+    dev = torch.device("cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    off = np.concatenate([small["offsets"], np.full(250, n7)]).astype(np.int64)
+    assert off.size == 258
+    d_uid, d_off, d_ids = (torch.from_numpy(a).to(dev) for a in (big_u, off, small["ids"]))
+    outs = [torch.full((n7 + 64,), -7, dtype=torch.int32, device=dev), torch.full((n7 + 64,), -7, dtype=torch.int32, device=dev),
+            torch.full((n7 + 64,), -7.0, dtype=torch.float32, device=dev)]
+    assert eng.lib.mamdr_graph_rank_slates(eng.ctx, DOMAIN, 257, p(d_uid), p(d_off), p(d_ids), p(outs[2]), p(outs[0]), p(outs[1])) == 0
+    for name, t in zip(("pos", "order", "scores"), outs):
+        got = t.cpu().numpy()
+        same(got[:n7], small[name], "rank_slates, empty second block: " + name)
+        assert np.all(got[n7:] == -7), name
+
+
 # ---------------------------------------------------------------------------------------------------------------- 8
 def state_digest(eng):
     return [hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest() for t in (eng.weights, eng.adam_m, eng.adam_v)] + list(eng.counters())

@@ -637,6 +637,43 @@ int mamdr_id_counts(const int32_t* d_ids, const float* d_label, int64_t n, int64
 int mamdr_list_similarity(const int32_t* d_ids, int32_t n_list, int32_t k, const float* d_rows, int64_t n_rows,
                           int32_t emb_dim, double* d_sim_sum, int32_t* d_pairs, void* stream);
 
+/* mamdr_list_diversify: greedy Maximal Marginal Relevance (Carbonell & Goldstein 1998) -- out of every list's n candidates,
+ * k picks that trade relevance against similarity to what is already picked.  NO REFERENCE COUNTERPART.  Stateless, any
+ * stream, no synchronisation, no allocation; the only memory written is the two outputs.
+ *   d_ids [n_list][n]               n in 1 .. MAMDR_LIST_MAX_K; valid / padding as mamdr_list_similarity: an id inside
+ *                                   [0, n_rows) is valid, anything else is padding wherever it sits.  Valid ids are
+ *                                   DISTINCT within a list (not checked; which of two duplicates wins a tie is unspecified)
+ *   d_rel [n_list][n]               each entry's relevance, fp32, used as given (not normalised)
+ *   d_rows [n_rows][emb_dim]        as mamdr_list_similarity: fp32, 16-byte aligned, emb_dim 32, 64, 128 or 256
+ *   k in 1 .. n, lambda in [0, 1]
+ *   d_pos_out [n_list][k]           the position in the input list (0 .. n - 1) of pick t; -1 behind a short list
+ *   d_value_out [n_list][k] or null the value pick t won with (its relevance at step 0); 0 behind a short list
+ * Definition, per list: its valid entries in list order are e_0 .. e_{L-1}.
+ *   cos(a, b), a < b                exactly the fp32 number mamdr_list_similarity forms for that pair standing in that
+ *                                   order: the same fma chain for the dot product and the squared norms, the quotient
+ *                                   (g / sqrtf(n_a)) / sqrtf(n_b) with a the earlier entry, 0 when either squared norm is 0
+ *   oml = 1.0f - lambda             in fp32
+ *   step 0                          the entry with the largest key (rel, id): the highest relevance, equal relevance by
+ *                                   ascending id, NaN behind every number (the retrieval family's ranking key: fp32
+ *                                   values order by their bits, so -0.0 stands behind +0.0)
+ *   step t >= 1                     for every entry c not yet picked, m_c = the running maximum of cos(c, s) over the
+ *                                   picks s so far (the first pick's cosine, then `cos > m ? cos : m`) and
+ *                                   v_c = (lambda * rel_c) - (oml * m_c): three fp32 roundings, no fused multiply-add.  The
+ *                                   entry with the largest key (v_c, id_c) is picked
+ *   stop                            after min(k, L) picks
+ * A list's outputs are the same bits from run to run, wherever the list sits in the call, whatever its neighbours hold,
+ * wherever its padding sits and for any n >= its last valid position + 1.  At lambda = 1 and finite rows the picks are
+ * the stable order by (rel descending, id ascending).  No floating-point atomics.  Against the float64 definition on the
+ * same fp32 inputs (list_metrics.diversify_host), with rel in [0, 1]: a pick's float64 value is within
+ * 2 tol of the step's best, tol = ((1 - lambda) (2 emb_dim + 8) + 8) * 2^-24.
+ * MAMDR_EINVAL, nothing launched: a null required pointer; d_ids / d_rel / d_pos_out / d_value_out not 4-byte, d_rows not
+ * 16-byte aligned; n_list <= 0; n outside 1 .. MAMDR_LIST_MAX_K; k outside 1 .. n; emb_dim not one of the four widths;
+ * n_rows <= 0; lambda outside [0, 1] or NaN.
+ * (Added within ABI 19: a new entry point only, no structure or existing call changed.) */
+int mamdr_list_diversify(const int32_t* d_ids, const float* d_rel, int32_t n_list, int32_t n, int32_t k, float lambda,
+                         const float* d_rows, int64_t n_rows, int32_t emb_dim, int32_t* d_pos_out, float* d_value_out,
+                         void* stream);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

@@ -123,6 +123,7 @@ SIGNATURES = {
     "mamdr_gram": (C.c_int, [_VP, _I64, _I32, _I64, _VP, _VP, _I32, _VP, _I64, _VP, _VP]),
     "mamdr_id_counts": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP]),
     "mamdr_list_similarity": (C.c_int, [_VP, _I32, _I32, _VP, _I64, _I32, _VP, _VP, _VP]),
+    "mamdr_list_diversify": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _F, _VP, _I64, _I32, _VP, _VP, _VP]),
     "mamdr_interp": (C.c_int, [_VP, _VP, _VP, _F, _I64, _VP]),
     "mamdr_moving_average": (C.c_int, [_VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mamdr_merge": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP]),

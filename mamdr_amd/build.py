@@ -46,6 +46,10 @@ SOURCES = [
     # list_kernels: the cosines' square root and divisions are IEEE (correctly rounded; hipcc's default, spelled out here);
     # its register / LDS / scratch report: profiles/list_metrics.txt
     ("list_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]),
+    # diversify_kernels: list_kernels' cosines (same flag), and a value is three separately rounded operations -> no fma
+    # fusion; its register / LDS / scratch report: profiles/list_diversify.txt
+    ("diversify_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off",
+                               "-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)
     ("mamdr_api.hip", []),
     ("step_context.hip", []),

@@ -17,7 +17,8 @@ Not options of the reference's run.py: --lanes, --recommend K (top-K lists per d
 positive ranked among N sampled items the user never interacted with, recommend.sampled_report), and
 --conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report), and
 --isotonic [B] with --isotonic-out FILE (train.isotonic: isotonic recalibration fitted on val, applied to test, and the CORP decomposition of the test Brier score, isotonic.report), and
---list-metrics [K] with --list-metrics-out FILE (train.list_metrics: what the top-K lists are made of -- coverage, Gini, entropy, novelty, tail share, personalisation and intra-list diversity per domain, list_metrics.report).
+--list-metrics [K] with --list-metrics-out FILE (train.list_metrics: what the top-K lists are made of -- coverage, Gini, entropy, novelty, tail share, personalisation and intra-list diversity per domain, list_metrics.report), and
+--diversify [LAMBDA] with --diversify-pool N and --diversify-out FILE (train.diversify, train.diversify_pool, train.diversify_out: every test user's top-N pool re-ranked to K items by greedy Maximal Marginal Relevance on the device, with HitRate / NDCG and the list metrics of both the base and the re-ranked lists, list_metrics.diversify_report).
 """
 import argparse
 import json
@@ -128,7 +129,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     mean_cosine_all, conflict_rate_meta and mean_cosine_meta.  train.isotonic = B (run.py --isotonic [B]; no key of the
     reference's configs): once the pipeline has ended, the isotonic report (isotonic.report) with B calibration bins, written
     to train.isotonic_out or under train.result_save_path; result.json gains isotonic.headline's keys (domain_brier,
-    domain_mcb, ..., avg_mcb, weighted_mcb)."""
+    domain_mcb, ..., avg_mcb, weighted_mcb).  train.diversify = LAMBDA (run.py --diversify [LAMBDA]; no key of the reference's
+    configs): once the pipeline has ended, every test user's top-N pool (train.diversify_pool, default min(128, 5 K)) is
+    re-ranked to K items (recommend, or 10) by greedy Maximal Marginal Relevance (list_metrics.diversify_report), written to
+    train.diversify_out or under train.result_save_path; result.json gains list_metrics.diversify_headline's keys."""
     from .reports import EVAL_REPORTS
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
@@ -160,6 +164,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
                                   "and train.lanes = 1")
     if config["train"].get("list_metrics") is not None and (world > 1 or lanes > 1):
         raise NotImplementedError("train.list_metrics (run.py --list-metrics): the list metrics are not computed across processes "
+                                  "or lanes (the best phi_d slots are current only on their owners); run it with one process "
+                                  "and train.lanes = 1")
+    if config["train"].get("diversify") is not None and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.diversify (run.py --diversify): the diversified lists are not computed across processes "
                                   "or lanes (the best phi_d slots are current only on their owners); run it with one process "
                                   "and train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
@@ -219,6 +227,13 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
             from . import list_metrics
             _, reports = list_metrics.report(model, int(config["train"]["list_metrics"]), config["train"].get("list_metrics_out"))
             _extend_result(saved, list_metrics.headline(reports))
+        if config["train"].get("diversify") is not None:
+            from . import list_metrics
+            k, pool = list_metrics.check_pool(int(recommend) if recommend else list_metrics.DEFAULT_K,
+                                              config["train"].get("diversify_pool"))
+            lam = list_metrics.check_lambda(config["train"]["diversify"])
+            _, reports = list_metrics.diversify_report(model, k, lam, pool, config["train"].get("diversify_out"))
+            _extend_result(saved, list_metrics.diversify_headline(reports, lam, pool))
     return avg_loss, avg_auc, domain_loss, domain_auc
 
 
@@ -280,6 +295,15 @@ def cli(argv=None):
                              "(K 1 .. 128; default: --recommend's K, or 10) (train.list_metrics)")
     parser.add_argument("--list-metrics-out", type=str, default=None, metavar="FILE",
                         help=".npz the list metrics go to (default: under train.result_save_path)")
+    parser.add_argument("--diversify", type=float, default=None, nargs="?", const=0.7, metavar="LAMBDA",
+                        help="after the run: every test user's top-N pool re-ranked to K items (--recommend's K, or 10) by greedy "
+                             "Maximal Marginal Relevance, lambda * relevance - (1 - lambda) * (largest cosine with a pick so far) "
+                             "(LAMBDA 0 .. 1, default 0.7), with HitRate / NDCG and the list metrics of both sides (train.diversify)")
+    parser.add_argument("--diversify-pool", type=int, default=None, metavar="N",
+                        help="the pool --diversify picks from: each user's top N (K .. 128; default min(128, 5 K)) "
+                             "(train.diversify_pool)")
+    parser.add_argument("--diversify-out", type=str, default=None, metavar="FILE",
+                        help=".npz the diversified lists go to (default: under train.result_save_path)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -332,6 +356,21 @@ def cli(argv=None):
         config["train"]["list_metrics"] = k
     if args.list_metrics_out is not None:
         config["train"]["list_metrics_out"] = args.list_metrics_out
+    if args.diversify is not None:
+        if not 0.0 <= args.diversify <= 1.0:          # (NaN fails both comparisons)
+            parser.error("--diversify LAMBDA: the weight of relevance, 0 .. 1")
+        config["train"]["diversify"] = args.diversify
+    if args.diversify_pool is not None:
+        if config["train"].get("diversify") is None:
+            parser.error("--diversify-pool N needs --diversify [LAMBDA] (or train.diversify in the config)")
+        config["train"]["diversify_pool"] = args.diversify_pool
+    if args.diversify_out is not None:
+        config["train"]["diversify_out"] = args.diversify_out
+    if config["train"].get("diversify") is not None:
+        k = args.recommend or 10
+        n = config["train"].get("diversify_pool")
+        if not 1 <= k <= 128 or (n is not None and not k <= int(n) <= 128):
+            parser.error("--diversify: K = %d (--recommend's, or 10) of a pool of N items, K <= N <= 128" % k)
     if args.recommend is None:
         return main(config)
     return main(config, recommend=args.recommend, recommend_out=args.recommend_out)

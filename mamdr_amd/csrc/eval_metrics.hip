@@ -1,6 +1,6 @@
 // C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics,
 // mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply and mamdr_score_sums, and of top-K lists:
-// mamdr_id_counts and mamdr_list_similarity.  Stateless, like the outer updates: no context, the caller's stream.  Host code
+// mamdr_id_counts, mamdr_list_similarity and mamdr_list_diversify.  Stateless, like the outer updates: no context, the caller's stream.  Host code
 // only.
 #include "step_ctx.h"
 
@@ -271,6 +271,41 @@ int mamdr_list_similarity(const int32_t* d_ids, int32_t n_list, int32_t k, const
     a.sim_sum = d_sim_sum;
     a.pairs = d_pairs;
     launch_list_sim(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+// ---- greedy MMR re-ranking of candidate lists (diversify_kernels.hip)
+int mamdr_list_diversify(const int32_t* d_ids, const float* d_rel, int32_t n_list, int32_t n, int32_t k, float lambda,
+                         const float* d_rows, int64_t n_rows, int32_t emb_dim, int32_t* d_pos_out, float* d_value_out,
+                         void* stream) {
+    if (!d_ids || !d_rel || !d_rows || !d_pos_out)
+        return fail(MAMDR_EINVAL, "mamdr_list_diversify: null ids / rel / rows / pos_out pointer");
+    if (n_list <= 0) return fail(MAMDR_EINVAL, "mamdr_list_diversify: n_list %d is not positive", (int)n_list);
+    if (n < 1 || n > MAMDR_LIST_MAX_K)
+        return fail(MAMDR_EINVAL, "mamdr_list_diversify: n %d outside 1..%d", (int)n, MAMDR_LIST_MAX_K);
+    if (k < 1 || k > n) return fail(MAMDR_EINVAL, "mamdr_list_diversify: k %d outside 1..n = %d", (int)k, (int)n);
+    if (!(lambda >= 0.f && lambda <= 1.f))
+        return fail(MAMDR_EINVAL, "mamdr_list_diversify: lambda %g outside [0, 1]", (double)lambda);
+    if (emb_dim != 32 && emb_dim != 64 && emb_dim != 128 && emb_dim != 256)
+        return fail(MAMDR_EINVAL, "mamdr_list_diversify: emb_dim %d is not 32, 64, 128 or 256", (int)emb_dim);
+    if (n_rows <= 0) return fail(MAMDR_EINVAL, "mamdr_list_diversify: n_rows %lld is not positive", (long long)n_rows);
+    if (misaligned(3, d_ids, d_rel, d_pos_out, d_value_out) || misaligned(15, d_rows))
+        return fail(MAMDR_EINVAL, "mamdr_list_diversify: a pointer is not aligned (ids / rel / pos_out / value_out 4, rows 16 bytes)");
+    ListDivArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ids = d_ids;
+    a.rel = d_rel;
+    a.n_list = n_list;
+    a.n = n;
+    a.k = k;
+    a.lambda = lambda;
+    a.rows = d_rows;
+    a.n_rows = n_rows;
+    a.emb_dim = emb_dim;
+    a.pos_out = d_pos_out;
+    a.value_out = d_value_out;
+    launch_list_div(a, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;
 }

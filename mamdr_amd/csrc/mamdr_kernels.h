@@ -1073,4 +1073,18 @@ struct ListSimArgs {
 };
 void launch_list_sim(const ListSimArgs& a, hipStream_t s);          // n_list > 0
 
+// diversify_kernels.hip: greedy MMR re-ranking of candidate lists (mamdr_list_diversify)
+struct ListDivArgs {
+    const int32_t* ids;            // [n_list][n]
+    const float* rel;              // [n_list][n]
+    int n_list, n, k;              // 1 <= k <= n <= LIST_SIM_MAX_K
+    float lambda;                  // in [0, 1]
+    const float* rows;             // [n_rows][emb_dim], 16-byte aligned
+    int64_t n_rows;
+    int emb_dim;                   // 32, 64, 128 or 256
+    int32_t* pos_out;              // [n_list][k]
+    float* value_out;              // [n_list][k] or null
+};
+void launch_list_div(const ListDivArgs& a, hipStream_t s);          // n_list > 0
+
 }  // namespace mamdr

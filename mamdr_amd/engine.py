@@ -285,6 +285,7 @@ class DeviceEngine(FlatVectorOps):
         for name in self.SHARED_CALLS:
             setattr(self, "_c_" + name, getattr(self.lib, self.PREFIX + name))
         self._c_id_counts, self._c_list_similarity = self.lib.mamdr_id_counts, self.lib.mamdr_list_similarity
+        self._c_list_diversify = self.lib.mamdr_list_diversify
 
     def _check(self, code):
         return L.check(code, graph=self.GRAPH)
@@ -666,6 +667,31 @@ class DeviceEngine(FlatVectorOps):
             L.check(self._c_list_similarity(_ptr(ids.contiguous()), Q, K, _ptr(rows), int(rows.shape[0]), int(rows.shape[1]),
                                             _ptr(sim_sum), _ptr(pairs), self._s()))
         return sim_sum, pairs
+
+    def list_diversify(self, ids, rel, rows, k, lam, want_values=False):
+        """mamdr_list_diversify on the engine's stream -- greedy MMR: ids [Q, N] int32 (N <= 128; an id outside [0, n_rows) is
+        padding; valid ids distinct within a list), rel [Q, N] fp32 (each entry's relevance, used as given), rows [n_rows, E]
+        fp32 as list_similarity takes them, all device tensors; 1 <= k <= N, 0 <= lam <= 1 -> (pos [Q, k] int32: the
+        position in its list of pick t, -1 behind a short list; values [Q, k] fp32: what the pick won with, or None
+        without want_values); nothing is read back."""
+        if ids.dim() != 2 or ids.dtype != torch.int32 or ids.device != self.device:
+            raise ValueError("list_diversify: ids must be a [Q, N] int32 tensor on the engine's device")
+        if rel.shape != ids.shape or rel.dtype != torch.float32 or rel.device != self.device:
+            raise ValueError("list_diversify: rel must be an fp32 tensor of the ids' shape on the engine's device")
+        if rows.dim() != 2 or rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous():
+            raise ValueError("list_diversify: rows must be a contiguous [n_rows, E] fp32 tensor on the engine's device")
+        Q, N, k, lam = int(ids.shape[0]), int(ids.shape[1]), int(k), float(lam)
+        if not 1 <= N <= L.LIST_MAX_K or int(rows.shape[1]) not in L.LIST_EMB_DIMS or rows.shape[0] < 1:
+            raise ValueError("list_diversify: N %d (1 to %d), rows %d x %d (width one of %s)" % (
+                N, L.LIST_MAX_K, rows.shape[0], rows.shape[1], (L.LIST_EMB_DIMS,)))
+        if not 1 <= k <= N or not 0.0 <= lam <= 1.0:
+            raise ValueError("list_diversify: k %d (1 to N = %d), lambda %r (0 to 1)" % (k, N, lam))
+        pos = torch.empty((Q, k), dtype=torch.int32, device=self.device)
+        values = torch.empty((Q, k), dtype=torch.float32, device=self.device) if want_values else None
+        if Q:
+            L.check(self._c_list_diversify(_ptr(ids.contiguous()), _ptr(rel.contiguous()), Q, N, k, lam, _ptr(rows),
+                                           int(rows.shape[0]), int(rows.shape[1]), _ptr(pos), _ptr(values), self._s()))
+        return pos, values
 
     def bind_accumulator(self, acc):
         """meta-gradient accumulator of the MAML / MLDG / PCGrad meta passes (maml.py:202); optimizer="accumulate" adds

@@ -244,6 +244,74 @@ class BaseModel(object):
                 "popularity": counts(popularity) if popularity is not None else np.zeros(n_item, np.int64),
                 "sim_sum": list_metrics.to_host(sim_sum).astype(np.float64), "pairs": list_metrics.to_host(pairs).astype(np.int32)}
 
+    # ------------------------------------------------------------------ diversified re-ranking (no reference counterpart)
+    def diversify(self, domain, k, pool, lam, relevance="minmax"):
+        """`domain`'s top-`pool` lists of `recommend(domain, pool)` re-ranked to k items each by greedy Maximal Marginal
+        Relevance on the engine's item_rows() (list_diversify: mamdr_list_diversify) from the live weights.  relevance:
+        "minmax" -- each list's scores scaled to [0, 1] on the device, list_metrics.minmax_relevance's fp32 formula -- or
+        "score" -- the scores as they are.  -> {"users" [Q], "ids" [Q, k] (-1 behind a short list), "scores" [Q, k] (the
+        picked items' scores), "pos" [Q, k] (their positions in the pool), "values" [Q, k] (what each pick won with),
+        "base_ids" [Q, k] (the pool's first k: `recommend(domain, k)`'s lists), "pool_ids" [Q, pool], "catalogue": its
+        size}.  With lam = 1 and "score" the picks are the base lists (as long as no two of a list's scores that the
+        tower tells apart round to the same fp32 probability).  It reads state only."""
+        import torch
+        from .. import list_metrics
+        k, pool = list_metrics.check_pool(k, pool)
+        lam = list_metrics.check_lambda(lam)
+        if relevance not in ("minmax", "score"):
+            raise ValueError("diversify: relevance %r is neither 'minmax' nor 'score'" % (relevance,))
+        eng = self.model
+        r = self.recommend(domain, pool)
+        pool_ids = np.ascontiguousarray(r["ids"])
+        ids = torch.from_numpy(pool_ids.astype(np.int32)).to(eng.device)
+        scores = torch.from_numpy(np.ascontiguousarray(r["scores"], np.float32)).to(eng.device)
+        rows = eng.item_rows()
+        rel = scores
+        if relevance == "minmax":
+            valid = (ids >= 0) & (ids < int(rows.shape[0]))
+            inf = torch.full_like(scores, float("inf"))
+            lo = torch.where(valid, scores, inf).amin(dim=1, keepdim=True)
+            hi = torch.where(valid, scores, -inf).amax(dim=1, keepdim=True)
+            rel = torch.where(valid & (hi > lo), (scores - lo) / (hi - lo), torch.zeros_like(scores))
+        if ids.shape[0]:
+            pos, values = eng.list_diversify(ids, rel.contiguous(), rows, k, lam, want_values=True)
+        else:
+            pos, values = np.zeros((0, k), np.int32), np.zeros((0, k), np.float32)
+        pos = torch.as_tensor(pos).to(torch.int64)
+        at = pos.clamp(min=0)
+        picked_ids = torch.where(pos >= 0, ids.gather(1, at), torch.full_like(ids[:, :k], -1))
+        picked_scores = torch.where(pos >= 0, scores.gather(1, at), torch.zeros_like(scores[:, :k]))
+        return {"users": r["users"], "ids": list_metrics.to_host(picked_ids).astype(pool_ids.dtype),
+                "scores": list_metrics.to_host(picked_scores), "pos": list_metrics.to_host(pos).astype(np.int32),
+                "values": np.asarray(list_metrics.to_host(values), np.float32), "base_ids": pool_ids[:, :k].copy(),
+                "pool_ids": pool_ids, "catalogue": r["catalogue"]}
+
+    def diversify_eval(self, domain, k, pool, lam, relevance="minmax"):
+        """what list_metrics.diversify_report needs of `domain`: `diversify`'s dict plus, as list_eval gives them and from
+        the same weights, "catalogue_ids", "popularity" [n_item] and, for the re-ranked lists, "exposure" [n_item] /
+        "sim_sum" [Q] / "pairs" [Q], and for the base lists "base_exposure" / "base_sim_sum" / "base_pairs"."""
+        import torch
+        from .. import list_metrics
+        eng = self.model
+        res = self.diversify(domain, k, pool, lam, relevance)
+        n_item = int(eng.n_item)
+        def counts(t):          # (a device tensor holds the uint32 counts as int32: reinterpret, do not convert)
+            a = list_metrics.to_host(t)
+            return (a.view(np.uint32) if a.dtype == np.int32 else a).astype(np.int64)
+        res["catalogue_ids"] = self._retrieval_problem(domain, res["users"], False)[0]
+        res["popularity"] = np.zeros(n_item, np.int64)
+        if domain in self.dataset.train_dataset:
+            cols = eng.data[(domain, "train")]
+            res["popularity"] = counts(eng.id_counts(cols["pid"], n_item, cols["label"]))
+        rows = eng.item_rows()
+        for pre, lists in (("base_", res["base_ids"]), ("", res["ids"])):
+            ids = torch.from_numpy(np.ascontiguousarray(lists, np.int32)).to(eng.device)
+            res[pre + "exposure"] = counts(eng.id_counts(ids, n_item))
+            sim_sum, pairs = eng.list_similarity(ids, rows) if ids.shape[0] else (np.zeros(0), np.zeros(0, np.int32))
+            res[pre + "sim_sum"] = list_metrics.to_host(sim_sum).astype(np.float64)
+            res[pre + "pairs"] = list_metrics.to_host(pairs).astype(np.int32)
+        return res
+
     # ------------------------------------------------------------------ isotonic recalibration (no reference counterpart)
     def isotonic_eval(self, domain, n_bins=20):
         """isotonic recalibration of `domain` from the live weights, on the device: the val and the test split are evaluated

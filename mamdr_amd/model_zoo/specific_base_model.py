@@ -150,6 +150,17 @@ class SpecificBase(MAML):
         with self._best_of_domain(domain):
             return self.base_model.list_eval(domain, k)
 
+    def diversify(self, domain, k, pool, lam, relevance="minmax"):
+        """BaseModel.diversify under domain `domain`'s own weights, installed and put back as rank_eval does: the pool is
+        scored and the item table is read while the best theta (+|*) phi_domain is installed."""
+        with self._best_of_domain(domain):
+            return self.base_model.diversify(domain, k, pool, lam, relevance)
+
+    def diversify_eval(self, domain, k, pool, lam, relevance="minmax"):
+        """BaseModel.diversify_eval under domain `domain`'s own weights, as `diversify`."""
+        with self._best_of_domain(domain):
+            return self.base_model.diversify_eval(domain, k, pool, lam, relevance)
+
     def domain_conflict(self, n_batches=None):
         """BaseModel.domain_conflict at the best theta ALONE -- the shared point that Domain Negotiation negotiates, without
         any domain's phi_d: it is assigned to the meta parameters for the call and the previous live flat vector is put

@@ -674,6 +674,44 @@ int mamdr_list_diversify(const int32_t* d_ids, const float* d_rel, int32_t n_lis
                          const float* d_rows, int64_t n_rows, int32_t emb_dim, int32_t* d_pos_out, float* d_value_out,
                          void* stream);
 
+/* mamdr_row_neighbours: for every query row of a table, its k nearest candidate rows by cosine -- exact, the whole
+ * query set x candidate set cosine matrix with the per-query selection fused behind it ("items like this one", and across
+ * catalogues "the items of B closest to this item of A").  NO REFERENCE COUNTERPART.  Stateless, any stream, no
+ * synchronisation; the only memory written is the two outputs and a stream-ordered allocation of the call's own (squared
+ * norms of the queries and of a pass's candidates, and each query's running lists).
+ *   d_rows [n_rows][emb_dim]        fp32, 16-byte aligned; emb_dim 32, 64, 128 or 256, as mamdr_list_similarity takes them
+ *   d_query [n_query]               row ids.  An id outside [0, n_rows) is no error: that query's list is all padding
+ *   d_cand [n_cand] or null         candidate row ids; null = "candidate p is row p", with n_cand = n_rows.  Ids are
+ *                                   DISTINCT (not checked; with duplicates, which copies appear is unspecified).  An id
+ *                                   outside [0, n_rows) is never returned
+ *   exclude_self                    != 0: the candidate whose id equals the query's id is skipped
+ *   k in 1 .. MAMDR_KNN_MAX_K
+ *   d_ids_out, d_sim_out [n_query][k]  the query's eligible candidates by cosine descending, equal cosines by ascending
+ *                                   id -- the retrieval family's ranking key on (cos, id): fp32 values order by their bits
+ *                                   (-0.0 behind +0.0), a NaN cosine stands behind every number (and is returned as the
+ *                                   quiet NaN 0x7fc00000).  A list with fewer than k eligible candidates ends in
+ *                                   id -1 / sim 0.0f
+ * Definition: cos(q, c) is exactly the fp32 number mamdr_list_similarity forms for the two-entry list [q, c]: the same
+ * fma chain over the columns for the dot product, the squared norms with the bits of that chain applied to the row with
+ * itself, the quotient (g / sqrtf(n_q)) / sqrtf(n_c) with IEEE square root and division and the query in the earlier
+ * entry's place, exactly 0 when either squared norm is 0 (IEEE propagation otherwise).
+ * Determinism: distinct ids give distinct keys, so a query's list is ONE list; its bytes do not depend on where the query
+ * stands in the call or what its neighbours are, on the order of d_cand, on the grid, the tile shapes or `chunk`.  No
+ * floating-point atomics.
+ * mamdr_row_neighbours_bounded is the same call with the number of candidates per pass given: chunk > 0, rounded up to the
+ * tile width (64); passes carry every query's running best.  The plain call picks a default.
+ * MAMDR_EINVAL, nothing launched: a null d_rows / d_query / d_ids_out / d_sim_out; d_rows not 16-byte, the others not
+ * 4-byte aligned; n_rows <= 0 or >= 2^31; emb_dim not one of the four widths; n_query <= 0; n_cand <= 0, or
+ * n_cand != n_rows with a null d_cand; k outside 1 .. MAMDR_KNN_MAX_K; chunk <= 0.
+ * (Added within ABI 19: new entry points only, no structure or existing call changed.) */
+#define MAMDR_KNN_MAX_K 128
+int mamdr_row_neighbours(const float* d_rows, int64_t n_rows, int32_t emb_dim, const int32_t* d_query, int32_t n_query,
+                         const int32_t* d_cand, int64_t n_cand, int32_t exclude_self, int32_t k, int32_t* d_ids_out,
+                         float* d_sim_out, void* stream);
+int mamdr_row_neighbours_bounded(const float* d_rows, int64_t n_rows, int32_t emb_dim, const int32_t* d_query,
+                                 int32_t n_query, const int32_t* d_cand, int64_t n_cand, int32_t exclude_self, int32_t k,
+                                 int32_t* d_ids_out, float* d_sim_out, int32_t chunk, void* stream);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

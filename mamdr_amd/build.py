@@ -50,6 +50,8 @@ SOURCES = [
     # fusion; its register / LDS / scratch report: profiles/list_diversify.txt
     ("diversify_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off",
                                "-Rpass-analysis=kernel-resource-usage"]),
+    # knn_kernels: list_kernels' cosines (same flag); its register / LDS / scratch report: profiles/knn_bench.txt
+    ("knn_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)
     ("mamdr_api.hip", []),
     ("step_context.hip", []),

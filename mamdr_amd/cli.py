@@ -18,7 +18,8 @@ positive ranked among N sampled items the user never interacted with, recommend.
 --conflict [N] (train.conflict: the cosines between the domains' gradients on the same weights, conflict.report), and
 --isotonic [B] with --isotonic-out FILE (train.isotonic: isotonic recalibration fitted on val, applied to test, and the CORP decomposition of the test Brier score, isotonic.report), and
 --list-metrics [K] with --list-metrics-out FILE (train.list_metrics: what the top-K lists are made of -- coverage, Gini, entropy, novelty, tail share, personalisation and intra-list diversity per domain, list_metrics.report), and
---diversify [LAMBDA] with --diversify-pool N and --diversify-out FILE (train.diversify, train.diversify_pool, train.diversify_out: every test user's top-N pool re-ranked to K items by greedy Maximal Marginal Relevance on the device, with HitRate / NDCG and the list metrics of both the base and the re-ranked lists, list_metrics.diversify_report).
+--diversify [LAMBDA] with --diversify-pool N and --diversify-out FILE (train.diversify, train.diversify_pool, train.diversify_out: every test user's top-N pool re-ranked to K items by greedy Maximal Marginal Relevance on the device, with HitRate / NDCG and the list metrics of both the base and the re-ranked lists, list_metrics.diversify_report), and
+--similar-items [K] with --similar-items-out FILE (train.similar_items, train.similar_items_out: every catalogue item's K exact cosine nearest neighbours on the item table, computed on the device, with the neighbour graph's hubness, orphan share and reciprocity per domain and the embedding-space affinity between the domains, neighbours.report).
 """
 import argparse
 import json
@@ -132,7 +133,11 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     domain_mcb, ..., avg_mcb, weighted_mcb).  train.diversify = LAMBDA (run.py --diversify [LAMBDA]; no key of the reference's
     configs): once the pipeline has ended, every test user's top-N pool (train.diversify_pool, default min(128, 5 K)) is
     re-ranked to K items (recommend, or 10) by greedy Maximal Marginal Relevance (list_metrics.diversify_report), written to
-    train.diversify_out or under train.result_save_path; result.json gains list_metrics.diversify_headline's keys."""
+    train.diversify_out or under train.result_save_path; result.json gains list_metrics.diversify_headline's keys.
+    train.similar_items = K (run.py --similar-items [K]; no key of the reference's configs): once the pipeline has ended, every
+    catalogue item's K exact cosine nearest neighbours on the item table of its domain's weights and the figures of that
+    neighbour graph (neighbours.report), written to train.similar_items_out or under train.result_save_path; result.json
+    gains neighbours.headline's keys (domain_<figure>, avg_<figure>, domain_affinity)."""
     from .reports import EVAL_REPORTS
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
@@ -168,6 +173,10 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
                                   "and train.lanes = 1")
     if config["train"].get("diversify") is not None and (world > 1 or lanes > 1):
         raise NotImplementedError("train.diversify (run.py --diversify): the diversified lists are not computed across processes "
+                                  "or lanes (the best phi_d slots are current only on their owners); run it with one process "
+                                  "and train.lanes = 1")
+    if config["train"].get("similar_items") is not None and (world > 1 or lanes > 1):
+        raise NotImplementedError("train.similar_items (run.py --similar-items): the neighbours are not computed across processes "
                                   "or lanes (the best phi_d slots are current only on their owners); run it with one process "
                                   "and train.lanes = 1")
     dataset = MultiDomainDataset(config["dataset"])
@@ -234,6 +243,10 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
             lam = list_metrics.check_lambda(config["train"]["diversify"])
             _, reports = list_metrics.diversify_report(model, k, lam, pool, config["train"].get("diversify_out"))
             _extend_result(saved, list_metrics.diversify_headline(reports, lam, pool))
+        if config["train"].get("similar_items") is not None:
+            from . import neighbours
+            _, reports = neighbours.report(model, int(config["train"]["similar_items"]), config["train"].get("similar_items_out"))
+            _extend_result(saved, neighbours.headline(reports))
     return avg_loss, avg_auc, domain_loss, domain_auc
 
 
@@ -304,6 +317,12 @@ def cli(argv=None):
                              "(train.diversify_pool)")
     parser.add_argument("--diversify-out", type=str, default=None, metavar="FILE",
                         help=".npz the diversified lists go to (default: under train.result_save_path)")
+    parser.add_argument("--similar-items", type=int, default=None, nargs="?", const=10, metavar="K",
+                        help="after the run: every catalogue item's K exact cosine nearest neighbours on the item table, per "
+                             "domain, with mean similarity, hubness, orphan share and reciprocity of the neighbour graph and the "
+                             "embedding-space affinity between the domains (K 1 .. 128, default 10) (train.similar_items)")
+    parser.add_argument("--similar-items-out", type=str, default=None, metavar="FILE",
+                        help=".npz the neighbour lists go to (default: under train.result_save_path)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -366,6 +385,12 @@ def cli(argv=None):
         config["train"]["diversify_pool"] = args.diversify_pool
     if args.diversify_out is not None:
         config["train"]["diversify_out"] = args.diversify_out
+    if args.similar_items is not None:
+        if not 1 <= args.similar_items <= 128:
+            parser.error("--similar-items K: K neighbours per item, 1 .. 128")
+        config["train"]["similar_items"] = args.similar_items
+    if args.similar_items_out is not None:
+        config["train"]["similar_items_out"] = args.similar_items_out
     if config["train"].get("diversify") is not None:
         k = args.recommend or 10
         n = config["train"].get("diversify_pool")

@@ -1,6 +1,6 @@
 // C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics,
 // mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply and mamdr_score_sums, and of top-K lists:
-// mamdr_id_counts, mamdr_list_similarity and mamdr_list_diversify.  Stateless, like the outer updates: no context, the caller's stream.  Host code
+// mamdr_id_counts, mamdr_list_similarity, mamdr_list_diversify and mamdr_row_neighbours(_bounded).  Stateless, like the outer updates: no context, the caller's stream.  Host code
 // only.
 #include "step_ctx.h"
 
@@ -308,6 +308,90 @@ int mamdr_list_diversify(const int32_t* d_ids, const float* d_rel, int32_t n_lis
     launch_list_div(a, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return MAMDR_OK;
+}
+
+// ---- exact cosine nearest neighbours of table rows (knn_kernels.hip)
+constexpr int64_t KNN_DEFAULT_CHUNK = (int64_t)1 << 20;     // candidates of a pass of the plain call
+constexpr int KNN_GRID_TARGET = 256;                         // workgroups the tile kernel aims at: one per CU
+constexpr int KNN_MAX_SPLITS = 64;
+
+static int row_neighbours(const char* fn, const float* d_rows, int64_t n_rows, int32_t emb_dim, const int32_t* d_query,
+                          int32_t n_query, const int32_t* d_cand, int64_t n_cand, int32_t exclude_self, int32_t k,
+                          int32_t* d_ids_out, float* d_sim_out, int64_t chunk, void* stream) {
+    if (!d_rows || !d_query || !d_ids_out || !d_sim_out)
+        return fail(MAMDR_EINVAL, "%s: null d_rows / d_query / d_ids_out / d_sim_out pointer", fn);
+    if (misaligned(15, d_rows)) return fail(MAMDR_EINVAL, "%s: d_rows is not 16-byte aligned", fn);
+    if (misaligned(3, d_query, d_cand, d_ids_out, d_sim_out))
+        return fail(MAMDR_EINVAL, "%s: d_query / d_cand / d_ids_out / d_sim_out is not 4-byte aligned", fn);
+    if (n_rows <= 0 || n_rows > INT32_MAX) return fail(MAMDR_EINVAL, "%s: n_rows %lld outside [1, 2^31)", fn, (long long)n_rows);
+    if (emb_dim != 32 && emb_dim != 64 && emb_dim != 128 && emb_dim != 256)
+        return fail(MAMDR_EINVAL, "%s: emb_dim %d is not 32, 64, 128 or 256", fn, (int)emb_dim);
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d is not positive", fn, (int)n_query);
+    if (n_cand <= 0) return fail(MAMDR_EINVAL, "%s: n_cand %lld is not positive", fn, (long long)n_cand);
+    if (!d_cand && n_cand != n_rows)
+        return fail(MAMDR_EINVAL, "%s: n_cand %lld with a null d_cand (every row: n_cand = n_rows = %lld)", fn, (long long)n_cand,
+                    (long long)n_rows);
+    if (k < 1 || k > MAMDR_KNN_MAX_K) return fail(MAMDR_EINVAL, "%s: k %d outside 1..%d", fn, (int)k, MAMDR_KNN_MAX_K);
+    if (chunk <= 0) return fail(MAMDR_EINVAL, "%s: chunk %lld is not positive", fn, (long long)chunk);
+    static_assert(KNN_MAX_K == MAMDR_KNN_MAX_K, "the running lists hold the longest list");
+    hipStream_t s = (hipStream_t)stream;
+    chunk = (chunk + KNN_TILE - 1) / KNN_TILE * KNN_TILE;
+    if (chunk > n_cand) chunk = (n_cand + KNN_TILE - 1) / KNN_TILE * KNN_TILE;
+    const int64_t q_blocks = ((int64_t)n_query + KNN_QBLOCK - 1) / KNN_QBLOCK, tiles = chunk / KNN_TILE;
+    int64_t splits = KNN_GRID_TARGET / q_blocks;
+    if (splits > KNN_MAX_SPLITS) splits = KNN_MAX_SPLITS;
+    if (splits > tiles) splits = tiles;
+    if (splits < 1) splits = 1;
+    KnnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rows = d_rows;
+    a.n_rows = n_rows;
+    a.emb_dim = emb_dim;
+    a.query = d_query;
+    a.n_query = n_query;
+    a.cand = d_cand;
+    a.exclude_self = exclude_self != 0;
+    a.k = k;
+    a.splits = (int)splits;
+    a.ids_out = d_ids_out;
+    a.sim_out = d_sim_out;
+    // the scratch: [running lists | query norms | candidate norms of a pass]
+    const size_t best_bytes = (size_t)q_blocks * KNN_QBLOCK * splits * KNN_MAX_K * sizeof(unsigned long long);
+    const size_t qn_bytes = ((size_t)n_query * sizeof(float) + 15) / 16 * 16;
+    bool lds_ok = true;
+    const int rc = with_scratch(fn, best_bytes + qn_bytes + (size_t)chunk * sizeof(float), s, [&](char* ws) {
+        a.best = reinterpret_cast<unsigned long long*>(ws);
+        a.qn2 = reinterpret_cast<float*>(ws + best_bytes);
+        a.cn2 = reinterpret_cast<float*>(ws + best_bytes + qn_bytes);
+        launch_knn_query_norms(a, s);
+        for (int64_t c0 = 0; c0 < n_cand; c0 += chunk) {
+            a.c_base = c0;
+            a.n_chunk = (int)(n_cand - c0 < chunk ? n_cand - c0 : chunk);
+            a.first_chunk = c0 == 0;
+            launch_knn_cand_norms(a, s);
+            if (!launch_knn_tile(a, s)) {
+                lds_ok = false;
+                return hipGetLastError();
+            }
+        }
+        launch_knn_merge(a, s);
+        return hipGetLastError();
+    });
+    if (rc == MAMDR_OK && !lds_ok) return fail(MAMDR_EHIP, "%s: the tile kernel's LDS was refused", fn);
+    return rc;
+}
+
+int mamdr_row_neighbours(const float* d_rows, int64_t n_rows, int32_t emb_dim, const int32_t* d_query, int32_t n_query,
+                         const int32_t* d_cand, int64_t n_cand, int32_t exclude_self, int32_t k, int32_t* d_ids_out,
+                         float* d_sim_out, void* stream) {
+    return row_neighbours("mamdr_row_neighbours", d_rows, n_rows, emb_dim, d_query, n_query, d_cand, n_cand, exclude_self, k,
+                          d_ids_out, d_sim_out, KNN_DEFAULT_CHUNK, stream);
+}
+int mamdr_row_neighbours_bounded(const float* d_rows, int64_t n_rows, int32_t emb_dim, const int32_t* d_query,
+                                 int32_t n_query, const int32_t* d_cand, int64_t n_cand, int32_t exclude_self, int32_t k,
+                                 int32_t* d_ids_out, float* d_sim_out, int32_t chunk, void* stream) {
+    return row_neighbours("mamdr_row_neighbours_bounded", d_rows, n_rows, emb_dim, d_query, n_query, d_cand, n_cand,
+                          exclude_self, k, d_ids_out, d_sim_out, chunk, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // The cosines of a list's item rows, as far as k_list_sim (list_kernels.hip) and k_list_div (diversify_kernels.hip) share
 // them: steps 1 - 3 at the head of list_kernels.hip and the cosine's own quotient.  One definition each, so the fp32 cosine
-// of a pair is the same bits in both calls, whichever variant and tile computes it.
+// of a pair is the same bits in both calls, whichever variant and tile computes it.  The contraction's step (ls_fma8) and the
+// quotient (ls_cos) are also what knn_kernels.hip forms its query x candidate cosines with: the same bits again.
 //
 // MFMA maps (32x32x2 f32): A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31]; C/D register g of lane l is
 // (row = (g & 3) + 8 (g >> 2) + 4 (l >> 5), col = l & 31).
@@ -40,6 +41,14 @@ struct LsTiles {
 
 // row of C/D register g of a lane of half h, inside its tile
 __device__ __forceinline__ int ls_acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
+
+// the contraction's one step: columns c .. c + 7 of a row pair, x / y the float4 at [row][c + 4 h] of the A / B side.  MFMA j
+// multiplies the column pair (c + j, c + 4 + j): every dot product of the family (ls_gram here, knn_kernels.hip) is one fp32
+// fma chain over the columns in the order c + j, c + 4 + j (c ascending by 8, j = 0 .. 3).
+__device__ __forceinline__ void ls_fma8(const ls_f32x4 x, const ls_f32x4 y, ls_f32x16& acc) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(x[j], y[j], acc, 0, 0, 0);
+}
 
 // 1. the valid entries (0 <= id < n_rows) of list q, compacted in list order (entry t on thread t: waves 0 and 1 hold them
 // all) -> L; `slot` is this thread's entry's place among them, or -1.  s_row[0 .. L) is written; the caller's barrier
@@ -110,8 +119,7 @@ __device__ __forceinline__ void ls_gram(const float* rows, int emb_dim, int L, c
                 if (!T.live[s]) continue;                          // (wave-uniform)
                 const ls_f32x4 x = *reinterpret_cast<const ls_f32x4*>(tile + (32 * T.ti[s] + r) * LS_LD + c + 4 * h);
                 const ls_f32x4 y = *reinterpret_cast<const ls_f32x4*>(tile + (32 * T.tj[s] + r) * LS_LD + c + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) T.acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(x[j], y[j], T.acc[s], 0, 0, 0);
+                ls_fma8(x, y, T.acc[s]);
             }
         }
     }

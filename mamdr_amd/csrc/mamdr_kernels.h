@@ -1087,4 +1087,31 @@ struct ListDivArgs {
 };
 void launch_list_div(const ListDivArgs& a, hipStream_t s);          // n_list > 0
 
+// knn_kernels.hip: exact cosine nearest neighbours of table rows (mamdr_row_neighbours)
+constexpr int KNN_MAX_K = 128;        // = MAMDR_KNN_MAX_K: entries of a running list
+constexpr int KNN_QBLOCK = 64;        // queries of a workgroup
+constexpr int KNN_TILE = 64;          // candidates of a tile
+struct KnnArgs {
+    const float* rows;             // [n_rows][emb_dim], 16-byte aligned
+    int64_t n_rows;
+    int emb_dim;                   // 32, 64, 128 or 256
+    const int32_t* query;          // [n_query]
+    int n_query;
+    const int32_t* cand;           // [n_cand] or null: candidate p is row p
+    int64_t c_base;                // candidates of the call before this pass
+    int n_chunk;                   // candidates of this pass
+    int exclude_self, k;
+    float* qn2;                    // [n_query] squared norms of the query rows (0 for an id out of range)
+    float* cn2;                    // [n_chunk] squared norms of the pass's candidate rows
+    unsigned long long* best;      // [n_query rounded up to KNN_QBLOCK][splits][KNN_MAX_K] running lists, sorted descending
+    int splits;                    // gridDim.y of the tile kernel: the same in every pass of a call
+    int first_chunk;               // the running lists start empty
+    int32_t* ids_out;              // [n_query][k]
+    float* sim_out;                // [n_query][k]
+};
+void launch_knn_query_norms(const KnnArgs& a, hipStream_t s);       // qn2 of all queries
+void launch_knn_cand_norms(const KnnArgs& a, hipStream_t s);        // cn2 of the pass
+bool launch_knn_tile(const KnnArgs& a, hipStream_t s);              // -> false: the LDS was refused, nothing was launched
+void launch_knn_merge(const KnnArgs& a, hipStream_t s);             // the splits' lists -> the outputs
+
 }  // namespace mamdr

@@ -286,6 +286,8 @@ class DeviceEngine(FlatVectorOps):
             setattr(self, "_c_" + name, getattr(self.lib, self.PREFIX + name))
         self._c_id_counts, self._c_list_similarity = self.lib.mamdr_id_counts, self.lib.mamdr_list_similarity
         self._c_list_diversify = self.lib.mamdr_list_diversify
+        self._c_row_neighbours = self.lib.mamdr_row_neighbours
+        self._c_row_neighbours_bounded = self.lib.mamdr_row_neighbours_bounded
 
     def _check(self, code):
         return L.check(code, graph=self.GRAPH)
@@ -692,6 +694,38 @@ class DeviceEngine(FlatVectorOps):
             L.check(self._c_list_diversify(_ptr(ids.contiguous()), _ptr(rel.contiguous()), Q, N, k, lam, _ptr(rows),
                                            int(rows.shape[0]), int(rows.shape[1]), _ptr(pos), _ptr(values), self._s()))
         return pos, values
+
+    def row_neighbours(self, rows, queries, k, candidates=None, exclude_self=True, chunk=None):
+        """mamdr_row_neighbours on the engine's stream -- exact cosine nearest neighbours: rows [n_rows, E] fp32 as
+        list_similarity takes them, queries [Q] int32 row ids (an id outside [0, n_rows) gets an all-padding list),
+        candidates [C] int32 distinct row ids or None (every row), all device tensors; 1 <= k <= 128; exclude_self: a query
+        is not its own neighbour; chunk: candidates per pass (mamdr_row_neighbours_bounded; None: the library's default)
+        -> (ids [Q, k] int32, -1 behind a short list; sims [Q, k] float32, 0 there) as device tensors; nothing is read
+        back."""
+        if rows.dim() != 2 or rows.dtype != torch.float32 or rows.device != self.device or not rows.is_contiguous():
+            raise ValueError("row_neighbours: rows must be a contiguous [n_rows, E] fp32 tensor on the engine's device")
+        if queries.dim() != 1 or queries.dtype != torch.int32 or queries.device != self.device:
+            raise ValueError("row_neighbours: queries must be a [Q] int32 tensor on the engine's device")
+        if candidates is not None and (candidates.dim() != 1 or candidates.dtype != torch.int32 or candidates.device != self.device):
+            raise ValueError("row_neighbours: candidates must be a [C] int32 tensor on the engine's device, or None")
+        Q, k, n_rows = int(queries.shape[0]), int(k), int(rows.shape[0])
+        if not 1 <= k <= L.KNN_MAX_K or int(rows.shape[1]) not in L.LIST_EMB_DIMS or not 1 <= n_rows < 2 ** 31:
+            raise ValueError("row_neighbours: k %d (1 to %d), rows %d x %d (width one of %s)" % (
+                k, L.KNN_MAX_K, n_rows, rows.shape[1], (L.LIST_EMB_DIMS,)))
+        if chunk is not None and int(chunk) <= 0:
+            raise ValueError("row_neighbours: chunk %r is not positive" % (chunk,))
+        ids = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
+        sims = torch.zeros((Q, k), dtype=torch.float32, device=self.device)
+        n_cand = n_rows if candidates is None else int(candidates.shape[0])
+        if Q and n_cand:
+            head = (_ptr(rows), n_rows, int(rows.shape[1]), _ptr(queries.contiguous()), Q,
+                    _ptr(candidates.contiguous()) if candidates is not None else None, n_cand, int(bool(exclude_self)), k,
+                    _ptr(ids), _ptr(sims))
+            if chunk is None:
+                L.check(self._c_row_neighbours(*head, self._s()))
+            else:
+                L.check(self._c_row_neighbours_bounded(*head, int(chunk), self._s()))
+        return ids, sims
 
     def bind_accumulator(self, acc):
         """meta-gradient accumulator of the MAML / MLDG / PCGrad meta passes (maml.py:202); optimizer="accumulate" adds

@@ -312,6 +312,28 @@ class BaseModel(object):
             res[pre + "pairs"] = list_metrics.to_host(pairs).astype(np.int32)
         return res
 
+    # ------------------------------------------------------------------ similar items (no reference counterpart)
+    def similar_items(self, domain, k, items=None, target_domain=None):
+        """the k nearest neighbours by cosine, on the engine's item_rows() -- the item table of the live weights --, of
+        `items` (default: `domain`'s catalogue, the distinct pids of its three splits) among the catalogue of
+        `target_domain` (default: the same domain); an item is not its own neighbour (the engine's row_neighbours:
+        mamdr_row_neighbours).  -> {"items" [Q], "ids" [Q, k] (-1 behind a short list), "sims" [Q, k] fp32, "catalogue"
+        (the candidate ids)}.  It reads state only."""
+        import torch
+        from .. import list_metrics, neighbours
+        k = neighbours.check_k(k)
+        eng = self.model
+        nobody = np.zeros(0, np.int64)
+        catalogue = self._retrieval_problem(int(domain if target_domain is None else target_domain), nobody, False)[0]
+        items = self._retrieval_problem(domain, nobody, False)[0] if items is None else np.asarray(items, np.int64).ravel()
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(eng.device)
+        if items.size and catalogue.size:
+            ids, sims = eng.row_neighbours(eng.item_rows(), dev(items), k, candidates=dev(catalogue), exclude_self=True)
+            ids, sims = list_metrics.to_host(ids), np.asarray(list_metrics.to_host(sims), np.float32)
+        else:
+            ids, sims = np.full((items.size, k), -1, np.int32), np.zeros((items.size, k), np.float32)
+        return {"items": items, "ids": ids, "sims": sims, "catalogue": catalogue}
+
     # ------------------------------------------------------------------ isotonic recalibration (no reference counterpart)
     def isotonic_eval(self, domain, n_bins=20):
         """isotonic recalibration of `domain` from the live weights, on the device: the val and the test split are evaluated

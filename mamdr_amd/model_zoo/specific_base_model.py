@@ -161,6 +161,12 @@ class SpecificBase(MAML):
         with self._best_of_domain(domain):
             return self.base_model.diversify_eval(domain, k, pool, lam, relevance)
 
+    def similar_items(self, domain, k, items=None, target_domain=None):
+        """BaseModel.similar_items under domain `domain`'s own weights, installed and put back as rank_eval does: the item
+        table is read while the best theta (+|*) phi_domain of the QUERY domain is installed."""
+        with self._best_of_domain(domain):
+            return self.base_model.similar_items(domain, k, items, target_domain)
+
     def domain_conflict(self, n_batches=None):
         """BaseModel.domain_conflict at the best theta ALONE -- the shared point that Domain Negotiation negotiates, without
         any domain's phi_d: it is assigned to the meta parameters for the call and the previous live flat vector is put

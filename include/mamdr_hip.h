@@ -712,6 +712,89 @@ int mamdr_row_neighbours_bounded(const float* d_rows, int64_t n_rows, int32_t em
                                  int32_t n_query, const int32_t* d_cand, int64_t n_cand, int32_t exclude_self, int32_t k,
                                  int32_t* d_ids_out, float* d_sim_out, int32_t chunk, void* stream);
 
+/* The baselines a ranking table is read against -- MostPopular and ItemKNN under the protocol of mamdr_rank_domain -- and
+ * the two calls that rank from a score matrix no tower produced: mamdr_item_cooc, mamdr_history_scores, mamdr_rank_scores,
+ * mamdr_topk_scores (mamdr_amd/baselines.py holds the host definitions and the report).  NO REFERENCE COUNTERPART: the
+ * reference never ranks.  Stateless: no context, any stream, no synchronisation, nothing read back; the only memory written
+ * is the outputs and, in mamdr_history_scores, a stream-ordered allocation of the call's own (m floats).  Wave64; integer
+ * atomics only; nothing depends on the order in which workgroups arrive.
+ *
+ * Histories.  A CSR over users: d_hist_off [n_user + 1] int64 ascending from 0 to nnz, d_hist_pos [nnz] int32 positions in a
+ * catalogue of m items, inside [0, m), ascending and distinct within a user (build and check it on the host:
+ * baselines.histories).  nnz is a host argument.  The kernels clamp both ends of every user's range into [0, nnz] and skip a
+ * position outside [0, m): a broken CSR gives wrong numbers, never an access outside the arrays.
+ *
+ * mamdr_item_cooc: d_cooc [m][m] uint32, zeroed by the call on `stream`, then C[a][b] = the number of users whose history
+ *   holds both a and b; the diagonal C[a][a] is the number of users that hold a.  The full symmetric matrix is stored: the
+ *   scorer reads row j as contiguous memory.  One integer atomic per ordered pair of a history (sum over users of L_u^2
+ *   adds; a history longer than a workgroup is strided over, all L^2 pairs are made; one wave-instruction's adds go along
+ *   one row of C).  Integers only: the same bits whatever order the workgroups run in.
+ *   MAMDR_EINVAL, nothing launched: a null d_hist_off or d_cooc; a null d_hist_pos with nnz > 0; d_hist_off not 8-byte,
+ *   d_hist_pos / d_cooc not 4-byte aligned; nnz < 0; m <= 0 or m > 65,535; n_user <= 0.
+ *
+ * mamdr_history_scores: the ItemKNN score of every catalogue item for the users d_query [n_query] (indices into the CSR; an
+ *   index outside [0, n_user) is no error: that row is all +0.0f), d_scores [n_query][m] fp32.  Fixed to the bit: with
+ *   n_a = float(C[a][a]) (exact: counts stay below 2^24 -- the call checks n_user < 2^24; a caller's own matrix with a
+ *   larger diagonal is outside the contract),
+ *     sim(c, j) = float(C[c][j]) / (sqrtf(n_c) * sqrtf(n_j) + shrink)     for c != j and C[c][j] > 0,
+ *     sim(c, j) = +0.0f                                                   otherwise,
+ *   every operation separately rounded, IEEE square root and division, no contraction; score[q][c] is the fp32 sum of
+ *   sim(c, j) over j in H(q) in ascending history order, started from +0.0f, one add per history entry.
+ *   Consequences: a row's bytes do not depend on where the query stands in the call, on its neighbours or on the grid
+ *   (every output element is owned by one lane for the whole sum); an empty history gives an all-zero row; an item's own
+ *   entry contributes nothing (a user's own items still collect the similarities to the user's OTHER items: exclude them
+ *   in the ranking calls); an item nobody holds scores +0.0f everywhere, at shrink = 0 too (its counts are all 0).
+ *   d_cooc is read with 16-byte loads where m is a multiple of 4 and d_cooc / d_scores are 16-byte aligned, with 4-byte
+ *   loads otherwise: the same bits either way.
+ *   MAMDR_EINVAL, nothing launched: a null d_cooc, d_hist_off, d_query or d_scores; a null d_hist_pos with nnz > 0; a
+ *   misaligned pointer (d_hist_off 8, the others 4 bytes); nnz < 0; m <= 0 or m > 65,535; n_user <= 0 or >= 2^24;
+ *   n_query <= 0; shrink outside [0, 2^20] or NaN.
+ *
+ * mamdr_rank_scores: mamdr_rank_domain's Rank and Live with "logit" replaced by d_scores[q * row_stride + p] for
+ *   candidate position p.
+ *   d_scores, row_stride            fp32; row_stride int64 counts elements: 0 = one row serves every query (MostPopular),
+ *                                   otherwise >= n_cand
+ *   d_cand [n_cand] or null         the id of position p, ASCENDING and distinct (the caller's contract: a catalogue is
+ *                                   np.unique's output); null = "the id of position p is p"
+ *   d_excl_off [n_query + 1], d_excl_ids   as in the tower calls: CSR by query, ids ascending; both or neither
+ *   d_tgt_off [n_query + 1], d_tgt_ids [n_tgt]   the targets' CSR, ids ascending and distinct per query; n_tgt is a host
+ *                                   argument (nothing is read back); offsets are clamped into [0, n_tgt]
+ *   d_rank_out [n_tgt] int32, d_score_out [n_tgt] fp32 or null, d_live_out [n_query] int32
+ *   key(q, p) = rec_key(score, id of p): (order-preserving bits of the score << 32) | ~id -- a larger key is a higher score
+ *   or an equal score and a smaller id; -0 counts as +0; a NaN is behind every number.  A position is live for q when its
+ *   id is not in q's exclusion list.
+ *   Rank.  A target's key is the key of the candidate position that holds its id (binary search).  d_rank_out[j] =
+ *     #{ p live for q : key(q, p) > key(q, target) }.  A target that is not among the candidates gets rank -1 and score 0.
+ *     A target that is among the candidates but excluded is ranked as mamdr_rank_domain ranks it: against the live ones.
+ *   Score.  d_score_out[j] = the raw bits d_scores holds for the pair.   Live.  d_live_out[q] = live positions of q.
+ *   Link to top-K.  A live candidate t sits at position r of mamdr_topk_scores' list exactly when its rank is r < k.
+ *   All outputs are integers or copied bits -- no floating-point arithmetic at all: a pure function of the input bits.
+ *   MAMDR_EINVAL, nothing launched: a null d_scores, d_tgt_off or d_live_out; a null d_rank_out or d_tgt_ids with
+ *   n_tgt > 0; exclusion offsets without ids or ids without offsets; a misaligned pointer (the offsets 8, the others 4
+ *   bytes); n_query <= 0; n_cand <= 0 or >= 2^31; row_stride < 0 or 0 < row_stride < n_cand; n_tgt < 0.
+ *
+ * mamdr_topk_scores: the first k <= MAMDR_SCORES_MAX_K live positions of the same ordering, as (id, score) in
+ *   d_ids_out / d_scores_out [n_query][k]; a short list ends in id -1 / score 0.0f; the score is decoded from the key (a
+ *   NaN leaves as 0x7fc00000, as mamdr_row_neighbours returns it; a -0.0 as +0.0).  Distinct ids give distinct keys: a
+ *   query's list is ONE list, whatever the tiles.
+ *   MAMDR_EINVAL, nothing launched: a null d_scores, d_ids_out or d_scores_out; the exclusion lists, alignment, n_query,
+ *   n_cand and row_stride as above; k outside 1 .. MAMDR_SCORES_MAX_K.
+ * Slates from scores (the sampled-negatives protocol) are out of scope: with the dense matrix on the device a caller
+ * gathers them.  (Added within ABI 19: new entry points only, no structure or existing call changed.) */
+#define MAMDR_SCORES_MAX_K 128
+int mamdr_item_cooc(const int64_t* d_hist_off, const int32_t* d_hist_pos, int64_t nnz, int32_t n_user, int32_t m,
+                    uint32_t* d_cooc, void* stream);
+int mamdr_history_scores(const uint32_t* d_cooc, int32_t m, const int64_t* d_hist_off, const int32_t* d_hist_pos,
+                         int64_t nnz, int32_t n_user, const int32_t* d_query, int32_t n_query, float shrink,
+                         float* d_scores, void* stream);
+int mamdr_rank_scores(const float* d_scores, int64_t row_stride, int32_t n_query, const int32_t* d_cand, int64_t n_cand,
+                      const int64_t* d_excl_off, const int32_t* d_excl_ids, const int64_t* d_tgt_off,
+                      const int32_t* d_tgt_ids, int64_t n_tgt, int32_t* d_rank_out, float* d_score_out,
+                      int32_t* d_live_out, void* stream);
+int mamdr_topk_scores(const float* d_scores, int64_t row_stride, int32_t n_query, const int32_t* d_cand, int64_t n_cand,
+                      const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
+                      float* d_scores_out, void* stream);
+
 /* --- outer (meta) updates on flat vectors; stateless, any stream.  Each op is
  *     evaluated with one fp32 rounding per arithmetic step in the reference's
  *     order (no FMA contraction) and matches its numpy result bit-for-bit.

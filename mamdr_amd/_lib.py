@@ -18,7 +18,8 @@ MERGE_PLUS, MERGE_TIMES = 0, 1
 GRAM_SLAB, GRAM_MAX_VEC = 16384, 32         # MAMDR_GRAM_SLAB, MAMDR_GRAM_MAX_VEC (mamdr_gram)
 LIST_MAX_K, LIST_EMB_DIMS = 128, (32, 64, 128, 256)     # MAMDR_LIST_MAX_K and the widths of mamdr_list_similarity
 KNN_MAX_K = 128                             # MAMDR_KNN_MAX_K (mamdr_row_neighbours)
-PCG_MAX_SEG, PCG_MAX_COLS = 24, 4096        # tensors per mamdr_pcgrad_project call, longest slice (include/mamdr_hip.h)
+SCORES_MAX_K, COOC_MAX_ITEMS = 128, 65535   # MAMDR_SCORES_MAX_K (mamdr_topk_scores); the largest m of mamdr_item_cooc
+PCG_MAX_SEG, PCG_MAX_COLS = 24, 4096       # tensors per mamdr_pcgrad_project call, longest slice (include/mamdr_hip.h)
 (SEG_USER_EMB, SEG_ITEM_EMB, SEG_DOMAIN_EMB, SEG_W0, SEG_W1, SEG_W2, SEG_B0, SEG_B1, SEG_B2, SEG_WO,
  SEG_GB, SEG_LIN_USER, SEG_LIN_ITEM, SEG_LIN_DOMAIN) = range(14)
 SEG_NAMES = ("user_emb", "item_emb", "domain_emb", "W0", "W1", "W2", "b0", "b1", "b2", "wo", "gb",
@@ -127,6 +128,10 @@ SIGNATURES = {
     "mamdr_list_diversify": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _F, _VP, _I64, _I32, _VP, _VP, _VP]),
     "mamdr_row_neighbours": (C.c_int, [_VP, _I64, _I32, _VP, _I32, _VP, _I64, _I32, _I32, _VP, _VP, _VP]),
     "mamdr_row_neighbours_bounded": (C.c_int, [_VP, _I64, _I32, _VP, _I32, _VP, _I64, _I32, _I32, _VP, _VP, _I32, _VP]),
+    "mamdr_item_cooc": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP]),
+    "mamdr_history_scores": (C.c_int, [_VP, _I32, _VP, _VP, _I64, _I32, _VP, _I32, _F, _VP, _VP]),
+    "mamdr_rank_scores": (C.c_int, [_VP, _I64, _I32, _VP, _I64, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP]),
+    "mamdr_topk_scores": (C.c_int, [_VP, _I64, _I32, _VP, _I64, _VP, _VP, _I32, _VP, _VP, _VP]),
     "mamdr_interp": (C.c_int, [_VP, _VP, _VP, _F, _I64, _VP]),
     "mamdr_moving_average": (C.c_int, [_VP, _VP, _VP, _F, _F, _I64, _VP]),
     "mamdr_merge": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP]),

@@ -52,6 +52,10 @@ SOURCES = [
                                "-Rpass-analysis=kernel-resource-usage"]),
     # knn_kernels: list_kernels' cosines (same flag); its register / LDS / scratch report: profiles/knn_bench.txt
     ("knn_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-Rpass-analysis=kernel-resource-usage"]),
+    # baseline_kernels: a similarity is a product, a sum and an IEEE division, separately rounded -> no fma fusion, correctly
+    # rounded square root and division; its register / LDS / scratch report: profiles/baselines_bench.txt
+    ("baseline_kernels.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off",
+                              "-Rpass-analysis=kernel-resource-usage"]),
     # host code only: the step engine's C ABI (map: csrc/step_ctx.h)
     ("mamdr_api.hip", []),
     ("step_context.hip", []),

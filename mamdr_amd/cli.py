@@ -19,7 +19,8 @@ positive ranked among N sampled items the user never interacted with, recommend.
 --isotonic [B] with --isotonic-out FILE (train.isotonic: isotonic recalibration fitted on val, applied to test, and the CORP decomposition of the test Brier score, isotonic.report), and
 --list-metrics [K] with --list-metrics-out FILE (train.list_metrics: what the top-K lists are made of -- coverage, Gini, entropy, novelty, tail share, personalisation and intra-list diversity per domain, list_metrics.report), and
 --diversify [LAMBDA] with --diversify-pool N and --diversify-out FILE (train.diversify, train.diversify_pool, train.diversify_out: every test user's top-N pool re-ranked to K items by greedy Maximal Marginal Relevance on the device, with HitRate / NDCG and the list metrics of both the base and the re-ranked lists, list_metrics.diversify_report), and
---similar-items [K] with --similar-items-out FILE (train.similar_items, train.similar_items_out: every catalogue item's K exact cosine nearest neighbours on the item table, computed on the device, with the neighbour graph's hubness, orphan share and reciprocity per domain and the embedding-space affinity between the domains, neighbours.report).
+--similar-items [K] with --similar-items-out FILE (train.similar_items, train.similar_items_out: every catalogue item's K exact cosine nearest neighbours on the item table, computed on the device, with the neighbour graph's hubness, orphan share and reciprocity per domain and the embedding-space affinity between the domains, neighbours.report), and
+--baselines [SHRINK] with --baselines-out FILE and --baselines-max-items N (train.baselines, train.baselines_out, train.baselines_max_items; needs --rank-eval: MostPopular and ItemKNN -- cosine over the train split's co-occurrence counts with that shrinkage -- ranked on the device under the rank-eval protocol, printed beside the tower's own figures, with the overlap of their top-K lists with the tower's under --recommend K, baselines.report).
 """
 import argparse
 import json
@@ -137,7 +138,13 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
     train.similar_items = K (run.py --similar-items [K]; no key of the reference's configs): once the pipeline has ended, every
     catalogue item's K exact cosine nearest neighbours on the item table of its domain's weights and the figures of that
     neighbour graph (neighbours.report), written to train.similar_items_out or under train.result_save_path; result.json
-    gains neighbours.headline's keys (domain_<figure>, avg_<figure>, domain_affinity)."""
+    gains neighbours.headline's keys (domain_<figure>, avg_<figure>, domain_affinity).  train.baselines = SHRINK (run.py
+    --rank-eval [KS] --baselines [SHRINK]; no key of the reference's configs): behind the rank-eval report, MostPopular and
+    ItemKNN (shrinkage SHRINK) under the same protocol beside the tower's figures (baselines.report), ItemKNN only for
+    catalogues of at most train.baselines_max_items (default 16384) items, written to train.baselines_out or under
+    train.result_save_path; result.json gains baselines.headline's keys (baselines_shrink, domain_<figure>_pop,
+    domain_<figure>_itemknn, avg_<figure>_pop, avg_<figure>_itemknn, domain_overlap_pop, domain_overlap_itemknn,
+    domain_cold_users, baselines_skipped)."""
     from .reports import EVAL_REPORTS
     from .utils import MultiDomainDataset
     rank, world = init_distributed()
@@ -151,6 +158,12 @@ def main(config, engine_factory=None, on_model=None, recommend=None, recommend_o
             raise NotImplementedError("train.%s (run.py %s): %s not gathered across processes or lanes "
                                       "(parallel.gather_domain_scalars carries loss and AUC only); run it with one process and "
                                       "train.lanes = 1" % (e.config_key, e.flag, e.refusal))
+    if config["train"].get("baselines") is not None and (world > 1 or lanes > 1):       # (before rank_eval's: named as asked)
+        raise NotImplementedError("train.baselines (run.py --baselines): the baselines are not ranked across processes "
+                                  "or lanes (they are reported beside train.rank_eval's figures, which are not); run it with one "
+                                  "process and train.lanes = 1")
+    if config["train"].get("baselines") is not None and not config["train"].get("rank_eval"):
+        raise ValueError("train.baselines needs train.rank_eval (run.py --rank-eval [KS] --baselines [SHRINK])")
     if config["train"].get("rank_eval") and (world > 1 or lanes > 1):
         raise NotImplementedError("train.rank_eval (run.py --rank-eval): the ranks are not computed across processes or lanes "
                                   "(the best phi_d slots are current only on their owners); run it with one process and "
@@ -220,7 +233,15 @@ def _run(config, dataset, engine_factory, on_model, rank, recommend=None, recomm
         if recommend:
             rec.report(model, int(recommend), recommend_out)
         if config["train"].get("rank_eval"):
-            rec.rank_report(model, config["train"]["rank_eval"])
+            _, tower_ranks = rec.rank_report(model, config["train"]["rank_eval"])
+            if config["train"].get("baselines") is not None:
+                from . import baselines
+                shrink = baselines.check_shrink(config["train"]["baselines"])
+                _, reports = baselines.report(model, config["train"]["rank_eval"], int(recommend) if recommend else None,
+                                              config["train"].get("baselines_out"), shrink,
+                                              int(config["train"].get("baselines_max_items", baselines.DEFAULT_MAX_ITEMS)),
+                                              tower=tower_ranks)
+                _extend_result(saved, baselines.headline(reports, shrink))
         if config["train"].get("sampled_eval"):
             rec.sampled_report(model, int(config["train"]["sampled_eval"]), config["train"].get("sampled_eval_ks", [10]),
                                seed=int(config["train"].get("sampled_eval_seed", 0)))
@@ -323,6 +344,15 @@ def cli(argv=None):
                              "embedding-space affinity between the domains (K 1 .. 128, default 10) (train.similar_items)")
     parser.add_argument("--similar-items-out", type=str, default=None, metavar="FILE",
                         help=".npz the neighbour lists go to (default: under train.result_save_path)")
+    parser.add_argument("--baselines", type=float, default=None, nargs="?", const=10.0, metavar="SHRINK",
+                        help="with --rank-eval: MostPopular and ItemKNN (cosine over co-occurrence counts, shrinkage SHRINK 0 .. 2^20, "
+                             "default 10) under the same protocol, beside the tower's figures; with --recommend K also the "
+                             "overlap of their top-K lists with the tower's (train.baselines)")
+    parser.add_argument("--baselines-out", type=str, default=None, metavar="FILE",
+                        help=".npz the baselines' ranks and lists go to (default: under train.result_save_path)")
+    parser.add_argument("--baselines-max-items", type=int, default=None, metavar="N",
+                        help="the largest catalogue ItemKNN is computed for (its co-occurrence matrix takes 4 N^2 bytes; default "
+                             "16384, at most 65535); a larger domain gets MostPopular only and is named (train.baselines_max_items)")
     args = parser.parse_args(argv)
     with open(args.config, "r") as f:
         config = json.load(f)
@@ -391,6 +421,24 @@ def cli(argv=None):
         config["train"]["similar_items"] = args.similar_items
     if args.similar_items_out is not None:
         config["train"]["similar_items_out"] = args.similar_items_out
+    if args.baselines is not None:
+        if not 0.0 <= args.baselines <= 2.0 ** 20:          # (NaN fails both comparisons)
+            parser.error("--baselines SHRINK: the shrinkage of the ItemKNN similarity, 0 .. 2^20")
+        config["train"]["baselines"] = args.baselines
+    for flag, value, key in (("--baselines-out", args.baselines_out, "baselines_out"),
+                             ("--baselines-max-items", args.baselines_max_items, "baselines_max_items")):
+        if value is not None:
+            if config["train"].get("baselines") is None:
+                parser.error("%s needs --baselines [SHRINK] (or train.baselines in the config)" % flag)
+            config["train"][key] = value
+    if args.baselines_max_items is not None and not 1 <= args.baselines_max_items <= 65535:
+        parser.error("--baselines-max-items N: items, 1 .. 65535")
+    if config["train"].get("baselines") is not None:
+        if not config["train"].get("rank_eval"):
+            parser.error("--baselines needs --rank-eval [KS] (or train.rank_eval in the config): the baselines are reported "
+                         "under its protocol, beside its figures")
+        if args.recommend is not None and not 1 <= args.recommend <= 128:
+            parser.error("--baselines with --recommend K: lists of K items, 1 .. 128")
     if config["train"].get("diversify") is not None:
         k = args.recommend or 10
         n = config["train"].get("diversify_pool")

@@ -1,6 +1,7 @@
 // C ABI of libmamdr_hip.so, the metrics of an evaluation's predictions: mamdr_group_auc, mamdr_exact_metrics,
 // mamdr_auc_bootstrap(_bounded), mamdr_isotonic_fit(_bounded), mamdr_isotonic_apply and mamdr_score_sums, and of top-K lists:
-// mamdr_id_counts, mamdr_list_similarity, mamdr_list_diversify and mamdr_row_neighbours(_bounded).  Stateless, like the outer updates: no context, the caller's stream.  Host code
+// mamdr_id_counts, mamdr_list_similarity, mamdr_list_diversify and mamdr_row_neighbours(_bounded), and of the baselines:
+// mamdr_item_cooc, mamdr_history_scores, mamdr_rank_scores and mamdr_topk_scores.  Stateless, like the outer updates: no context, the caller's stream.  Host code
 // only.
 #include "step_ctx.h"
 
@@ -392,6 +393,155 @@ int mamdr_row_neighbours_bounded(const float* d_rows, int64_t n_rows, int32_t em
                                  int32_t* d_ids_out, float* d_sim_out, int32_t chunk, void* stream) {
     return row_neighbours("mamdr_row_neighbours_bounded", d_rows, n_rows, emb_dim, d_query, n_query, d_cand, n_cand,
                           exclude_self, k, d_ids_out, d_sim_out, chunk, stream);
+}
+
+// ---- baselines: item co-occurrence, ItemKNN scores, ranks and top-K lists from a score matrix (baseline_kernels.hip)
+static int check_histories(const char* fn, const int64_t* d_hist_off, const int32_t* d_hist_pos, int64_t nnz, int32_t n_user,
+                           int32_t m, int64_t max_user) {
+    if (!d_hist_off) return fail(MAMDR_EINVAL, "%s: null d_hist_off pointer", fn);
+    if (nnz < 0) return fail(MAMDR_EINVAL, "%s: nnz %lld is negative", fn, (long long)nnz);
+    if (nnz > 0 && !d_hist_pos) return fail(MAMDR_EINVAL, "%s: null d_hist_pos pointer with nnz %lld", fn, (long long)nnz);
+    if (misaligned(7, d_hist_off) || misaligned(3, d_hist_pos))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned (d_hist_off 8, the others 4 bytes)", fn);
+    if (m <= 0 || m > BASE_MAX_ITEMS) return fail(MAMDR_EINVAL, "%s: m %d outside 1..%d", fn, (int)m, BASE_MAX_ITEMS);
+    if (n_user <= 0 || n_user >= max_user)
+        return fail(MAMDR_EINVAL, "%s: n_user %d outside [1, %lld)", fn, (int)n_user, (long long)max_user);
+    return MAMDR_OK;
+}
+
+int mamdr_item_cooc(const int64_t* d_hist_off, const int32_t* d_hist_pos, int64_t nnz, int32_t n_user, int32_t m,
+                    uint32_t* d_cooc, void* stream) {
+    if (!d_cooc) return fail(MAMDR_EINVAL, "mamdr_item_cooc: null d_cooc pointer");
+    if (misaligned(3, d_cooc)) return fail(MAMDR_EINVAL, "mamdr_item_cooc: a pointer is not aligned (d_hist_off 8, the others 4 bytes)");
+    if (const int rc = check_histories("mamdr_item_cooc", d_hist_off, d_hist_pos, nnz, n_user, m, (int64_t)1 << 31)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(d_cooc, 0, (size_t)m * m * sizeof(uint32_t), s));
+    HistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hist_off = d_hist_off;
+    a.hist_pos = d_hist_pos;
+    a.nnz = nnz;
+    a.n_user = n_user;
+    a.m = m;
+    a.cooc = d_cooc;
+    if (nnz > 0) launch_item_cooc(a, s);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_history_scores(const uint32_t* d_cooc, int32_t m, const int64_t* d_hist_off, const int32_t* d_hist_pos,
+                         int64_t nnz, int32_t n_user, const int32_t* d_query, int32_t n_query, float shrink,
+                         float* d_scores, void* stream) {
+    const char* fn = "mamdr_history_scores";
+    if (!d_cooc || !d_query || !d_scores) return fail(MAMDR_EINVAL, "%s: null d_cooc / d_query / d_scores pointer", fn);
+    if (misaligned(3, d_cooc, d_query, d_scores))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned (d_hist_off 8, the others 4 bytes)", fn);
+    if (const int rc = check_histories(fn, d_hist_off, d_hist_pos, nnz, n_user, m, (int64_t)1 << 24)) return rc;
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d is not positive", fn, (int)n_query);
+    if (!(shrink >= 0.f && shrink <= 1048576.f)) return fail(MAMDR_EINVAL, "%s: shrink %g outside [0, 2^20]", fn, (double)shrink);
+    HistArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hist_off = d_hist_off;
+    a.hist_pos = d_hist_pos;
+    a.nnz = nnz;
+    a.n_user = n_user;
+    a.m = m;
+    a.cooc = const_cast<uint32_t*>(d_cooc);
+    a.query = d_query;
+    a.n_query = n_query;
+    a.shrink = shrink;
+    a.scores = d_scores;
+    a.vec4 = m % 4 == 0 && !misaligned(15, d_cooc, d_scores);
+    // (one workgroup per query and column tile, in one grid dimension)
+    const int64_t tiles = ((int64_t)m + (a.vec4 ? 1024 : 256) - 1) / (a.vec4 ? 1024 : 256);
+    if ((int64_t)n_query * tiles > INT32_MAX)
+        return fail(MAMDR_EINVAL, "%s: n_query %d x %lld column tiles exceed one grid: score in blocks of queries", fn,
+                    (int)n_query, (long long)tiles);
+    hipStream_t s = (hipStream_t)stream;
+    return with_scratch(fn, (size_t)m * sizeof(float), s, [&](char* ws) {
+        a.root = reinterpret_cast<float*>(ws);
+        launch_hist_scores(a, s);
+        return hipGetLastError();
+    });
+}
+
+static int check_score_call(const char* fn, const float* d_scores, int64_t row_stride, int32_t n_query, const int32_t* d_cand,
+                            int64_t n_cand, const int64_t* d_excl_off, const int32_t* d_excl_ids, int64_t per_tile) {
+    if (!d_scores) return fail(MAMDR_EINVAL, "%s: null d_scores pointer", fn);
+    if (misaligned(3, d_scores, d_cand, d_excl_ids) || misaligned(7, d_excl_off))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned (the offsets 8, the others 4 bytes)", fn);
+    if ((d_excl_off == nullptr) != (d_excl_ids == nullptr))
+        return fail(MAMDR_EINVAL, "%s: the exclusion lists need both their offsets and their ids", fn);
+    if (n_query <= 0) return fail(MAMDR_EINVAL, "%s: n_query %d is not positive", fn, (int)n_query);
+    if (n_cand <= 0 || n_cand > INT32_MAX) return fail(MAMDR_EINVAL, "%s: n_cand %lld outside [1, 2^31)", fn, (long long)n_cand);
+    if (row_stride < 0 || (row_stride > 0 && row_stride < n_cand))
+        return fail(MAMDR_EINVAL, "%s: row_stride %lld is neither 0 nor at least n_cand = %lld", fn, (long long)row_stride,
+                    (long long)n_cand);
+    if ((int64_t)n_query * ((n_cand + per_tile - 1) / per_tile) > INT32_MAX)
+        return fail(MAMDR_EINVAL, "%s: n_query %d x n_cand %lld exceed one grid: rank in blocks of queries", fn, (int)n_query,
+                    (long long)n_cand);
+    return MAMDR_OK;
+}
+
+int mamdr_rank_scores(const float* d_scores, int64_t row_stride, int32_t n_query, const int32_t* d_cand, int64_t n_cand,
+                      const int64_t* d_excl_off, const int32_t* d_excl_ids, const int64_t* d_tgt_off,
+                      const int32_t* d_tgt_ids, int64_t n_tgt, int32_t* d_rank_out, float* d_score_out,
+                      int32_t* d_live_out, void* stream) {
+    const char* fn = "mamdr_rank_scores";
+    if (!d_tgt_off || !d_live_out) return fail(MAMDR_EINVAL, "%s: null d_tgt_off / d_live_out pointer", fn);
+    if (n_tgt < 0) return fail(MAMDR_EINVAL, "%s: n_tgt %lld is negative", fn, (long long)n_tgt);
+    if (n_tgt > 0 && (!d_tgt_ids || !d_rank_out)) return fail(MAMDR_EINVAL, "%s: null d_tgt_ids / d_rank_out pointer with targets", fn);
+    if (misaligned(3, d_tgt_ids, d_rank_out, d_score_out, d_live_out) || misaligned(7, d_tgt_off))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned (the offsets 8, the others 4 bytes)", fn);
+    if (const int rc = check_score_call(fn, d_scores, row_stride, n_query, d_cand, n_cand, d_excl_off, d_excl_ids, 1024)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (n_tgt > 0) HIP_TRY(hipMemsetAsync(d_rank_out, 0, (size_t)n_tgt * sizeof(int32_t), s));
+    HIP_TRY(hipMemsetAsync(d_live_out, 0, (size_t)n_query * sizeof(int32_t), s));
+    ScoreRankArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scores = d_scores;
+    a.row_stride = row_stride;
+    a.n_query = n_query;
+    a.cand = d_cand;
+    a.n_cand = (int)n_cand;
+    a.excl_off = d_excl_off;
+    a.excl_ids = d_excl_ids;
+    a.tgt_off = d_tgt_off;
+    a.tgt_ids = d_tgt_ids;
+    a.n_tgt = n_tgt;
+    a.rank_out = d_rank_out;
+    a.score_out = d_score_out;
+    a.live_out = d_live_out;
+    launch_rank_scores(a, s);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
+}
+
+int mamdr_topk_scores(const float* d_scores, int64_t row_stride, int32_t n_query, const int32_t* d_cand, int64_t n_cand,
+                      const int64_t* d_excl_off, const int32_t* d_excl_ids, int32_t k, int32_t* d_ids_out,
+                      float* d_scores_out, void* stream) {
+    const char* fn = "mamdr_topk_scores";
+    if (!d_ids_out || !d_scores_out) return fail(MAMDR_EINVAL, "%s: null d_ids_out / d_scores_out pointer", fn);
+    if (misaligned(3, d_ids_out, d_scores_out))
+        return fail(MAMDR_EINVAL, "%s: a pointer is not aligned (the offsets 8, the others 4 bytes)", fn);
+    if (const int rc = check_score_call(fn, d_scores, row_stride, n_query, d_cand, n_cand, d_excl_off, d_excl_ids, INT32_MAX)) return rc;
+    if (k < 1 || k > MAMDR_SCORES_MAX_K) return fail(MAMDR_EINVAL, "%s: k %d outside 1..%d", fn, (int)k, MAMDR_SCORES_MAX_K);
+    static_assert(BASE_MAX_K == MAMDR_SCORES_MAX_K, "the running list holds the longest list");
+    ScoreRankArgs a;
+    memset(&a, 0, sizeof(a));
+    a.scores = d_scores;
+    a.row_stride = row_stride;
+    a.n_query = n_query;
+    a.cand = d_cand;
+    a.n_cand = (int)n_cand;
+    a.excl_off = d_excl_off;
+    a.excl_ids = d_excl_ids;
+    a.k = k;
+    a.ids_out = d_ids_out;
+    a.topk_out = d_scores_out;
+    launch_topk_scores(a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return MAMDR_OK;
 }
 
 }  // extern "C"

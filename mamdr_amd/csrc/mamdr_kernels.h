@@ -1114,4 +1114,44 @@ void launch_knn_cand_norms(const KnnArgs& a, hipStream_t s);        // cn2 of th
 bool launch_knn_tile(const KnnArgs& a, hipStream_t s);              // -> false: the LDS was refused, nothing was launched
 void launch_knn_merge(const KnnArgs& a, hipStream_t s);             // the splits' lists -> the outputs
 
+// baseline_kernels.hip: item co-occurrence, ItemKNN scores of user histories, ranks and top-K lists from a caller's score
+// matrix (mamdr_item_cooc, mamdr_history_scores, mamdr_rank_scores, mamdr_topk_scores)
+constexpr int BASE_MAX_ITEMS = 65535;   // m of the co-occurrence matrix: m * m * 4 bytes stays below 2^34
+constexpr int BASE_MAX_K = 128;         // = MAMDR_SCORES_MAX_K
+struct HistArgs {
+    const int64_t* hist_off;       // [n_user + 1], clamped into [0, nnz] by every reader
+    const int32_t* hist_pos;       // [nnz] catalogue positions; one outside [0, m) is skipped
+    int64_t nnz;
+    int n_user, m;
+    uint32_t* cooc;                // [m][m]; k_item_cooc adds into it (zeroed on the stream before), k_hist_scores reads it
+    const int32_t* query;          // [n_query] user indices, one outside [0, n_user) scores all +0.0f
+    int n_query;
+    float shrink;
+    float* root;                   // [m] sqrtf(float(cooc[a][a])): the call's own scratch
+    float* scores;                 // [n_query][m]
+    int vec4;                      // rows of cooc / scores are 16-byte aligned: four columns per lane
+};
+void launch_item_cooc(const HistArgs& a, hipStream_t s);            // n_user > 0
+void launch_hist_scores(const HistArgs& a, hipStream_t s);          // the roots, then the scores; n_query > 0
+struct ScoreRankArgs {
+    const float* scores;           // candidate position p of query q: scores[q * row_stride + p]
+    int64_t row_stride;            // 0: one row serves every query
+    int n_query;
+    const int32_t* cand;           // [n_cand] ascending distinct ids, or null: the id of position p is p
+    int n_cand;
+    const int64_t* excl_off;       // [n_query + 1] or null
+    const int32_t* excl_ids;
+    const int64_t* tgt_off;        // [n_query + 1], clamped into [0, n_tgt]
+    const int32_t* tgt_ids;
+    int64_t n_tgt;
+    int32_t* rank_out;             // [n_tgt], zeroed on the stream before the launch
+    float* score_out;              // [n_tgt] or null
+    int32_t* live_out;             // [n_query], zeroed on the stream before the launch
+    int k;                         // top-K only
+    int32_t* ids_out;              // [n_query][k]
+    float* topk_out;               // [n_query][k]
+};
+void launch_rank_scores(const ScoreRankArgs& a, hipStream_t s);     // n_query > 0, n_cand > 0
+void launch_topk_scores(const ScoreRankArgs& a, hipStream_t s);     // n_query > 0, n_cand > 0, 1 <= k <= BASE_MAX_K
+
 }  // namespace mamdr

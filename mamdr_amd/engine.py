@@ -727,6 +727,112 @@ class DeviceEngine(FlatVectorOps):
                 L.check(self._c_row_neighbours_bounded(*head, int(chunk), self._s()))
         return ids, sims
 
+    # ------------------------------------------------------------ baselines: co-occurrence, ItemKNN scores, ranks and lists
+    # from a score matrix (no reference counterpart; the host definitions: baselines.py)
+    def _check_dev(self, fn, what, t, dtype, dim):
+        if t.dtype != dtype or t.device != self.device or t.dim() != dim or not t.is_contiguous():
+            raise ValueError("%s: %s must be a contiguous %d-d %s tensor on the engine's device" % (fn, what, dim, dtype))
+
+    def _check_hist(self, fn, off, pos):
+        self._check_dev(fn, "off", off, torch.int64, 1)
+        self._check_dev(fn, "pos", pos, torch.int32, 1)
+        if off.shape[0] < 2:
+            raise ValueError("%s: off must hold n_user + 1 >= 2 offsets" % fn)
+        return int(off.shape[0]) - 1, int(pos.shape[0])
+
+    def item_cooc(self, off, pos, m):
+        """mamdr_item_cooc on the engine's stream: the histories' CSR (off [n_user + 1] int64, pos [nnz] int32 positions in
+        [0, m); baselines.histories builds and checks it), device tensors -> the device tensor [m, m] int32 holding the uint32
+        co-occurrence counts; nothing is read back."""
+        n_user, nnz = self._check_hist("item_cooc", off, pos)
+        m = int(m)
+        if not 1 <= m <= L.COOC_MAX_ITEMS:
+            raise ValueError("item_cooc: m %d outside 1..%d" % (m, L.COOC_MAX_ITEMS))
+        cooc = torch.empty((m, m), dtype=torch.int32, device=self.device)
+        L.check(self.lib.mamdr_item_cooc(_ptr(off), _ptr(pos if nnz else None), nnz, n_user, m, _ptr(cooc), self._s()))
+        return cooc
+
+    def history_scores(self, cooc, off, pos, queries, shrink):
+        """mamdr_history_scores on the engine's stream: cooc [m, m] int32 (item_cooc's), the histories' CSR, queries [Q] int32
+        user indices into it (one outside [0, n_user) scores all zero), 0 <= shrink <= 2^20 -> the device tensor [Q, m] fp32
+        of ItemKNN scores; nothing is read back."""
+        n_user, nnz = self._check_hist("history_scores", off, pos)
+        self._check_dev("history_scores", "cooc", cooc, torch.int32, 2)
+        self._check_dev("history_scores", "queries", queries, torch.int32, 1)
+        m, Q, shrink = int(cooc.shape[0]), int(queries.shape[0]), float(shrink)
+        if cooc.shape[1] != m or not 1 <= m <= L.COOC_MAX_ITEMS or not 0.0 <= shrink <= 2.0 ** 20 or n_user >= 2 ** 24:
+            raise ValueError("history_scores: cooc %r (square, 1..%d), shrink %r (0 to 2^20), %d users (below 2^24)" % (
+                tuple(cooc.shape), L.COOC_MAX_ITEMS, shrink, n_user))
+        scores = torch.empty((Q, m), dtype=torch.float32, device=self.device)
+        if Q:
+            L.check(self.lib.mamdr_history_scores(_ptr(cooc), m, _ptr(off), _ptr(pos if nnz else None), nnz, n_user,
+                                                  _ptr(queries), Q, shrink, _ptr(scores), self._s()))
+        return scores
+
+    def _check_scores(self, fn, scores, n_query, candidates, excl_off, excl_ids):
+        """the arguments rank_scores and topk_scores share -> (row_stride, n_cand)."""
+        if scores.dtype != torch.float32 or scores.device != self.device or scores.dim() not in (1, 2) or not scores.is_contiguous():
+            raise ValueError("%s: scores must be a contiguous fp32 tensor [Q, n_cand] (or [n_cand]: one row for every query) on "
+                             "the engine's device" % fn)
+        n_cand = int(scores.shape[-1])
+        if scores.dim() == 2 and int(scores.shape[0]) != n_query:
+            raise ValueError("%s: %d score rows for %d queries" % (fn, scores.shape[0], n_query))
+        if candidates is not None:
+            self._check_dev(fn, "candidates", candidates, torch.int32, 1)
+            if int(candidates.shape[0]) != n_cand:
+                raise ValueError("%s: %d candidate ids for %d score columns" % (fn, candidates.shape[0], n_cand))
+        if (excl_off is None) != (excl_ids is None):
+            raise ValueError("%s: the exclusion lists need both their offsets and their ids" % fn)
+        if excl_off is not None:
+            self._check_dev(fn, "excl_off", excl_off, torch.int64, 1)
+            self._check_dev(fn, "excl_ids", excl_ids, torch.int32, 1)
+            if int(excl_off.shape[0]) != n_query + 1:
+                raise ValueError("%s: %d exclusion offsets for %d queries" % (fn, excl_off.shape[0], n_query))
+        return (n_cand if scores.dim() == 2 else 0), n_cand
+
+    def rank_scores(self, scores, n_query, tgt_off, tgt_ids, candidates=None, excl_off=None, excl_ids=None, want_scores=False):
+        """mamdr_rank_scores on the engine's stream: scores [Q, n_cand] fp32 -- or [n_cand], one row for every query --,
+        candidates [n_cand] int32 ascending distinct ids or None (the id of position p is p), the exclusion lists' and the
+        targets' CSR (offsets [Q + 1] int64, ids int32 ascending per query; recommend.exclusion_csr), all device tensors ->
+        (ranks [T] int32: the live positions that order strictly before the target, -1 for a target that is no candidate;
+        live [Q] int32 [; scores [T] fp32: the targets' raw scores]) as device tensors; nothing is read back."""
+        fn = "rank_scores"
+        n_query = int(n_query)
+        stride, n_cand = self._check_scores(fn, scores, n_query, candidates, excl_off, excl_ids)
+        self._check_dev(fn, "tgt_off", tgt_off, torch.int64, 1)
+        self._check_dev(fn, "tgt_ids", tgt_ids, torch.int32, 1)
+        if int(tgt_off.shape[0]) != n_query + 1:
+            raise ValueError("%s: %d target offsets for %d queries" % (fn, tgt_off.shape[0], n_query))
+        n_tgt = int(tgt_ids.shape[0])
+        ranks = torch.empty(n_tgt, dtype=torch.int32, device=self.device)
+        live = torch.zeros(n_query, dtype=torch.int32, device=self.device)
+        out = torch.empty(n_tgt, dtype=torch.float32, device=self.device) if want_scores else None
+        if n_query and n_cand:
+            L.check(self.lib.mamdr_rank_scores(_ptr(scores), stride, n_query, _ptr(candidates), n_cand, _ptr(excl_off),
+                                               _ptr(excl_ids), _ptr(tgt_off), _ptr(tgt_ids if n_tgt else None), n_tgt,
+                                               _ptr(ranks if n_tgt else None), _ptr(out if n_tgt else None), _ptr(live), self._s()))
+        else:
+            ranks.fill_(-1)
+            if out is not None:
+                out.zero_()
+        return (ranks, live, out) if want_scores else (ranks, live)
+
+    def topk_scores(self, scores, n_query, k, candidates=None, excl_off=None, excl_ids=None):
+        """mamdr_topk_scores on the engine's stream: rank_scores' scores / candidates / exclusion lists, 1 <= k <= 128 ->
+        (ids [Q, k] int32, -1 behind a short list; scores [Q, k] fp32, 0 there) as device tensors: the first k live
+        positions of rank_scores' ordering; nothing is read back."""
+        fn = "topk_scores"
+        n_query, k = int(n_query), int(k)
+        stride, n_cand = self._check_scores(fn, scores, n_query, candidates, excl_off, excl_ids)
+        if not 1 <= k <= L.SCORES_MAX_K:
+            raise ValueError("%s: k %d outside 1..%d" % (fn, k, L.SCORES_MAX_K))
+        ids = torch.full((n_query, k), -1, dtype=torch.int32, device=self.device)
+        out = torch.zeros((n_query, k), dtype=torch.float32, device=self.device)
+        if n_query and n_cand:
+            L.check(self.lib.mamdr_topk_scores(_ptr(scores), stride, n_query, _ptr(candidates), n_cand, _ptr(excl_off),
+                                               _ptr(excl_ids), k, _ptr(ids), _ptr(out), self._s()))
+        return ids, out
+
     def bind_accumulator(self, acc):
         """meta-gradient accumulator of the MAML / MLDG / PCGrad meta passes (maml.py:202); optimizer="accumulate" adds
         to it (or, after set_moving_average, moves it towards every batch's gradient)."""

@@ -46,6 +46,7 @@ def slates_csr(slates, n_query):
 
 
 SAMPLE_ROUNDS = 16      # vectorised rejection rounds of sample_negatives before the per-slate completion
+SAMPLE_SCAN_MAX = 8     # forbidden lists up to this length are compared entry by entry, longer ones searched (the same answer)
 
 
 def sample_negatives(catalogue, forbid_off, forbid_ids, n_neg, seed):
@@ -73,30 +74,49 @@ def sample_negatives(catalogue, forbid_off, forbid_ids, n_neg, seed):
         keys = np.unique(np.repeat(np.arange(n_slate, dtype=np.int64), np.diff(off))[hit] * n_cat + idx[hit])
     n_forbid = np.bincount(keys // max(n_cat, 1), minlength=n_slate)[:n_slate] if n_slate else np.zeros(0, np.int64)
     want = np.minimum(n_neg, n_cat - n_forbid).astype(np.int64)
+    # short forbidden lists as a table [slate][SAMPLE_SCAN_MAX or fewer] of catalogue indices (-1: none): a few whole-array
+    # comparisons per round instead of one binary search per draw
+    f_max = int(n_forbid.max()) if n_slate else 0
+    forbid = None
+    if keys.size and f_max <= SAMPLE_SCAN_MAX:
+        ks = keys // n_cat
+        forbid = np.full((n_slate, f_max), -1, np.int32)
+        forbid[ks, np.arange(keys.size) - (np.cumsum(n_forbid) - n_forbid)[ks]] = keys - ks * n_cat
     rs = np.random.RandomState(int(seed))
     draws = np.zeros((n_slate, n_neg), np.int32)          # (catalogue indices; the sentinels below reach n_cat + n_neg)
     col = np.arange(n_neg, dtype=np.int32)[None, :]
     todo = np.flatnonzero(want > 0)
     redraw = col < want[todo][:, None]
+    # (value, position) packed into one integer per draw: a plain sort of distinct keys is the stable sort by value
+    shift = max(int(max(n_neg, 1) - 1).bit_length(), 1)
+    packed = np.int32 if ((n_cat + n_neg) << shift) < 2 ** 31 else np.int64
     for _ in range(SAMPLE_ROUNDS):
         if not todo.size:
             break
         active = col < want[todo][:, None]
         d = draws[todo]
-        d[redraw] = rs.randint(0, n_cat, size=int(redraw.sum()))
+        new = rs.randint(0, n_cat, size=int(redraw.sum()))
+        d[redraw] = new
         bad = np.zeros_like(active)
-        if keys.size:
-            k = todo[:, None] * n_cat + d.astype(np.int64)
-            bad = keys[np.minimum(np.searchsorted(keys, k), keys.size - 1)] == k
-        # equal positions of a slate: a stable sort per row (positions behind the slate's end under distinct sentinels)
-        # brings them together in position order; all but the first are drawn again
-        v = np.where(active, d, np.int32(n_cat) + col)
-        o = np.argsort(v, axis=1, kind="stable")
-        vs = np.take_along_axis(v, o, 1)
+        if forbid is not None:
+            f = forbid[todo]
+            for j in range(f_max):
+                bad |= d == f[:, j:j + 1]
+        elif keys.size:     # (only the positions drawn in this round can be forbidden: the others passed when they were drawn)
+            k = np.repeat(todo * n_cat, redraw.sum(1)) + new
+            bad[redraw] = keys[np.minimum(np.searchsorted(keys, k), keys.size - 1)] == k
+        # equal positions of a slate: sorted per row (positions behind the slate's end under distinct sentinels) they come
+        # together in position order; all but the first are drawn again
+        v = np.where(active, d, np.int32(n_cat) + col).astype(packed)
+        v <<= shift
+        v |= col
+        v.sort(axis=1)
+        pos = v & ((1 << shift) - 1)
+        v >>= shift
         dup_sorted = np.zeros_like(active)
-        dup_sorted[:, 1:] = vs[:, 1:] == vs[:, :-1]
+        dup_sorted[:, 1:] = v[:, 1:] == v[:, :-1]
         dup = np.zeros_like(active)
-        np.put_along_axis(dup, o, dup_sorted, 1)
+        np.put_along_axis(dup, pos.astype(np.intp), dup_sorted, 1)
         redraw = (bad | dup) & active
         draws[todo] = d
         open_ = redraw.any(1)

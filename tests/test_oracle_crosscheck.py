@@ -83,11 +83,15 @@ def test_deepctr_towers_gradients_vs_float64_autograd_at_edge_batches(tower, emb
     _deepctr_case(tower, emb_trainable, rate, uncertainty, B)
 
 
-def _deepctr_case(tower, emb_trainable, rate, uncertainty, B, seed=11):
+def _deepctr_case(tower, emb_trainable, rate, uncertainty, B, seed=11, n_domain=5, single_domain="default"):
     rs = np.random.RandomState(seed)
-    n_user, n_item, n_domain = 300, 200, 5
+    n_user, n_item = 300, 200
     p = _params(rs, n_user, n_item, n_domain, tower, uncertainty)
-    uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=2 if uncertainty else None)
+    if single_domain == "default":
+        single_domain = 2 if uncertainty else None
+    uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=single_domain)
+    if single_domain is None and n_domain != 5:        # every id occurs
+        dom = rs.permutation(np.arange(B) % n_domain).astype(np.int32)
     deepfm = {"deepfm": 1, "wdl": 2}.get(tower, 0)
     names = otower.param_names(emb_trainable, deepfm, uncertainty)
     masks = otower.train_masks(1024, 3, B, (256, 128, 64), rate) if rate > 0 else None
@@ -142,9 +146,9 @@ def test_star_tower_gradients_vs_float64_autograd_at_edge_batches(emb_trainable,
     _star_case(emb_trainable, B, EDGE_SEEDS.get(("star", B), 12))
 
 
-def _star_case(emb_trainable, B, seed=12):
+def _star_case(emb_trainable, B, seed=12, n_domain=4, domain=1):
     rs = np.random.RandomState(seed)
-    n_user, n_item, n_domain = 300, 200, 4
+    n_user, n_item = 300, 200
     p = ostar.init_params(rs, n_user, n_item, n_domain)
     for n in ("pn_gamma_shared", "pn_gamma_spec"):
         p[n] = (p[n] + rs.standard_normal(p[n].shape) * 0.2).astype(F32)
@@ -152,7 +156,7 @@ def _star_case(emb_trainable, B, seed=12):
         p[n] = (rs.standard_normal(p[n].shape) * 0.05).astype(F32)
     for l in range(3):
         p["Wd%d" % l] = (p["Wd%d" % l] * 8).astype(F32)
-    uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=1)
+    uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=domain)
     meta, rest = ostar.param_names(emb_trainable)
     names = meta + rest
     state = ostar.init_state(n_domain)
@@ -168,7 +172,85 @@ def _star_case(emb_trainable, B, seed=12):
     _check_grads(g32, g64, [n for n in names if n != "domain_emb"], rtol=1e-3)
     # the slices of the other domains carry exactly zero gradient on both sides
     for n in ("Wd0", "bd1", "pn_gamma_spec"):
-        assert not np.any(g32[n][0]) and not np.any(g64[n][0])
+        for j in range(n_domain):
+            if j != domain:
+                assert not np.any(g32[n][j]) and not np.any(g64[n][j])
+
+
+# ---------------------------------------------------------------------------------------------- the domain-count edges
+# tests/test_gpu_domain_counts.py holds the step engine to the oracles at the domain counts where its kernels change path
+# (1, 8 | 9, 16 | 17, 32 | 33, 48 | 49, 64 | 65); float64 autograd judges the oracles there first.
+import domain_counts as dc                # noqa: E402
+
+EDGE_D = (1, 33, 65)
+
+
+@pytest.mark.parametrize("mixed", [True, False], ids=["mixed", "one-domain"])
+@pytest.mark.parametrize("n_domain", EDGE_D)
+@pytest.mark.parametrize("tower,emb_trainable,rate,uncertainty", [("mlp", False, 0.5, False), ("mlp", False, 0.5, True),
+                                                                  ("deepfm", True, 0.5, False), ("deepfm", False, 0.5, False)])
+def test_deepctr_towers_gradients_vs_float64_autograd_at_edge_domain_counts(tower, emb_trainable, rate, uncertainty, n_domain, mixed):
+    """256 rows at 1, 33 and 65 domains: every id in one batch (the uncertainty scalar is the first row's), and the highest
+    id alone."""
+    _deepctr_case(tower, emb_trainable, rate, uncertainty, 256, n_domain=n_domain, single_domain=None if mixed else n_domain - 1)
+
+
+@pytest.mark.parametrize("mixed", [True, False], ids=["mixed", "one-domain"])
+@pytest.mark.parametrize("n_domain", EDGE_D)
+def test_pnn_gradients_vs_float64_autograd_at_edge_domain_counts(n_domain, mixed):
+    test_nfm_pnn_gradients_vs_float64_autograd("pnn", False, 0.5, False, 256, 31, n_domain, None if mixed else n_domain - 1)
+
+
+@pytest.mark.parametrize("n_domain", EDGE_D)
+@pytest.mark.parametrize("emb_trainable", [True, False])
+def test_star_tower_gradients_vs_float64_autograd_at_edge_domain_counts(emb_trainable, n_domain):
+    """oracle/star.py states the Star step for one-domain batches (the first row's domain serves the batch); the mixed
+    batch of the Star family is tests/test_star_forms_ref.py's."""
+    _star_case(emb_trainable, 256, n_domain=n_domain, domain=n_domain - 1)
+
+
+@pytest.mark.parametrize("case,which", [(c, w) for c in dc.distinct_inputs() for w in dc.which_of(c)],
+                         ids=lambda v: v if isinstance(v, str) else v.name)
+def test_domain_count_inputs_are_fit(case, which):
+    """Every first batch tests/test_gpu_domain_counts.py probes, through the oracle alone: loss 2e-6 and `_check_grads`' bars
+    against float64 autograd (the Star tower at its rtol 1e-3), so no hidden unit of these inputs sits within rounding of
+    the relu kink.  Inputs that were moved: domain_counts.MOVED_SEEDS (none had to be)."""
+    params, splits, _ = dc.make_inputs(case)
+    args = dc.batch_of(splits[which][1], 0, case.batch)
+    if which == "mixed":
+        assert np.unique(args[2]).shape[0] == min(case.D, case.batch) and args[2].max() == case.D - 1
+    else:
+        assert np.all(args[2] == case.D - 1)
+    model = dc.make_model(case, params)
+    loss32, g32, _ = dc.oracle_step(case, model, args, frozen_reg=False)
+    loss64, g64 = dc.float64_step(case, model, args)
+    assert abs(float(loss32) - loss64) < 2e-6 * max(1.0, abs(loss64))
+    names = list(dc.names_of(case))
+    assert sorted(g32) == sorted(names)
+    if case.tower == "star":
+        assert np.abs(g32["domain_emb"]).max() < 1e-5 and np.abs(g64["domain_emb"]).max() < 1e-12
+        _check_grads(g32, g64, [n for n in names if n != "domain_emb"], rtol=1e-3)
+    else:
+        _check_grads(g32, g64, names)
+
+
+@pytest.mark.parametrize("n_domain", dc.GRAPH_D)
+@pytest.mark.parametrize("kind", dc.MTL_KINDS)
+def test_domain_count_mtl_inputs_are_fit(kind, n_domain):
+    """the multi-task towers at 1 and 33 domains (their first run at these counts): the batches tests/test_gpu_domain_counts.py
+    probes on the generic-layer engine, through oracle/mtl.py alone against float64 autograd.  No input had to be moved."""
+    from oracle import mtl as omtl
+    g, spec, p = dc.mtl_problem(kind, n_domain)
+    names = [n for n, _ in spec.tensors(False, g["n_user"], g["n_item"])]
+    for step, (d, args) in enumerate(dc.probe_batches(g)):
+        masks = omtl.train_masks(spec, dc.DROPOUT_SEED, step, args[0].shape[0], 0.5)
+        loss, g32, pred = omtl.loss_and_grads(p, spec, d, *args, masks, 0.5, False)
+        loss64, g64, pred64 = tref.mtl_loss_and_grads(p, names, spec, d, *args, masks, 0.5)
+        assert abs(float(loss) - loss64) < 2e-6 * max(1.0, abs(loss64))
+        np.testing.assert_allclose(pred, pred64, rtol=2e-5, atol=2e-7)
+        on_path = [n for n in names if g64[n] is not None]
+        assert sorted(on_path) == sorted(g32)
+        _check_grads(g32, g64, on_path)
 
 
 def test_tf1_adam_step_formula_vs_float64():
@@ -307,10 +389,10 @@ def test_nfm_pnn_gradients_vs_float64_autograd_at_edge_batches(kind, emb_trainab
 
 
 @pytest.mark.parametrize("kind,emb_trainable,rate,uncertainty", NFM_PNN_CASES)
-def test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty, B=48, seed=31):
+def test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncertainty, B=48, seed=31, D=4, single_domain="default"):
     from oracle import fmnets as ofm
     rs = np.random.RandomState(seed)
-    n_user, n_item, D = 60, 40, 4
+    n_user, n_item = 60, 40
     p = ofm.init_params(rs, kind, n_user, n_item, D, emb_dim=8, hidden=(16, 8, 4))
     p["domain_emb"] = (rs.standard_normal(p["domain_emb"].shape) * 0.05).astype(F32)
     for n in ("b0", "b1", "b2", "lin_user", "lin_item", "lin_domain"):
@@ -320,7 +402,11 @@ def test_nfm_pnn_gradients_vs_float64_autograd(kind, emb_trainable, rate, uncert
     names = list(ofm.param_names(kind, emb_trainable, uncertainty))
     if uncertainty:            # distinct per-domain scales around the initial value 1 (weighted_loss.py:23-28)
         p["log_var"] = (1.0 + rs.uniform(-0.3, 0.3, D)).astype(F32)
-    uid, pid, dom, label = _batch(rs, n_user, n_item, D, B, single_domain=2 if uncertainty else None)
+    if single_domain == "default":
+        single_domain = 2 if uncertainty else None
+    uid, pid, dom, label = _batch(rs, n_user, n_item, D, B, single_domain=single_domain)
+    if single_domain is None and D != 4:               # every id occurs
+        dom = rs.permutation(np.arange(B) % D).astype(np.int32)
     masks = otower.train_masks(1024, 3, B, (16, 8, 4), rate) if rate > 0 else None
     loss, g, pred = ofm.loss_and_grads(p, kind, uid, pid, dom, label, masks, rate, emb_trainable, None, uncertainty)
     loss64, g64, pred64 = tref.fmnet_loss_and_grads(p, names, kind, uid, pid, dom, label, masks, rate, uncertainty=uncertainty)

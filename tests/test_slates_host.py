@@ -107,6 +107,30 @@ def test_sample_negatives_properties():
         recommend.sample_negatives(cat, [0, 3], [1], 2, seed=0)
 
 
+def _pinned_case(f_len, n_neg):
+    rs = np.random.RandomState(3)
+    cat = rs.choice(5000, 400, replace=False)
+    cnt = rs.randint(0, f_len + 1, 500)
+    f_ids = np.concatenate([cat, [7, 9]])[rs.randint(0, 402, int(cnt.sum()))]
+    return cat, np.concatenate([[0], np.cumsum(cnt)]), f_ids, n_neg, 21
+
+
+@pytest.mark.parametrize("f_len,n_neg,digest", [(4, 30, "1f9b0f0ec3716494416c55f1141f5b424a507903"),
+                                                (60, 30, "f8f17981681ca511b0c0beb539092ff7f2d265c5"),
+                                                (4, 200, "31845082281dbe179b21c6b25b3df28808590fb2")])
+def test_sample_negatives_draws_are_pinned(f_len, n_neg, digest, monkeypatch):
+    """The draws are part of the function (evaluation protocols are compared across runs): the bytes that the first
+    implementation -- one binary search per draw, a stable argsort per slate -- gave for forbidden lists of up to 4 ids (now
+    compared through the per-slate table), of up to 60 (still searched) and for more draws per slate than 128; and the table
+    and the search give the same bytes on the same input."""
+    import hashlib
+    off, ids = recommend.sample_negatives(*_pinned_case(f_len, n_neg))
+    assert hashlib.sha1(off.tobytes() + ids.tobytes()).hexdigest() == digest
+    monkeypatch.setattr(recommend, "SAMPLE_SCAN_MAX", 0 if f_len <= recommend.SAMPLE_SCAN_MAX else 64)
+    off2, ids2 = recommend.sample_negatives(*_pinned_case(f_len, n_neg))
+    assert off2.tobytes() == off.tobytes() and ids2.tobytes() == ids.tobytes()
+
+
 def test_sample_negatives_is_uniform():
     """50 items, 10 forbidden, 5 of the 40 free ones per slate, 4,000 slates: every free item is expected 500 times with
     sigma = sqrt(4000 * (1/8) * (7/8)) = 20.9: all 40 counts within 5 sigma, [395, 605]."""

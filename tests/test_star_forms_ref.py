@@ -89,11 +89,48 @@ def test_forms_gradients_vs_float64_autograd_at_edge_batches(norm, dense, aux, h
     _forms_case(norm, dense, aux, hidden, mixed, B, FORMS_EDGE_SEEDS.get((norm, dense, aux, hidden, mixed, B), 12))
 
 
-def _forms_case(norm, dense, aux, hidden, mixed, B, seed=12):
+@pytest.mark.parametrize("mixed", [False, True], ids=["one-domain", "mixed"])
+@pytest.mark.parametrize("n_domain", [1, 33, 65])
+@pytest.mark.parametrize("norm,dense,aux,hidden", [FORMS[0], FORMS[9]])
+def test_forms_gradients_vs_float64_autograd_at_edge_domain_counts(norm, dense, aux, hidden, n_domain, mixed):
+    """pn + star with and without the auxiliary network at 1, 33 and 65 domains (tests/test_gpu_domain_counts.py runs the
+    step kernels' Star and the generic-layer engine there): 256 rows of the highest domain id, and 256 rows in which every
+    id occurs, led by the highest (the first row's domain serves the batch).  One input was moved: pn/star/64 at 33 domains,
+    one-domain, seed 12 puts a hidden unit within fp32 rounding of the relu kink (user_emb off by 7.6e-5 of 0.073 on 0.6 % of
+    its elements, the signature of one flipped unit); seed 13, the same bars."""
+    seed = {("pn", "star", 64, 33, False): 13}.get((norm, dense, aux, n_domain, mixed), 12)
+    _forms_case(norm, dense, aux, hidden, mixed, 256, seed, n_domain=n_domain, domain=n_domain - 1)
+
+
+@pytest.mark.parametrize("n_domain", [1, 33])
+def test_domain_count_star_form_inputs(n_domain):
+    """the batches tests/test_gpu_domain_counts.py probes with pn/star/64 on the generic-layer engine, through the reference
+    alone.  That file applies tests/test_gpu_star_forms.py::fit_reference per batch, so a batch at the kink is judged by
+    float64 there; here the distance is measured and every tensor off the kink's signature is held to `_check_grads`."""
+    import domain_counts as dc
+    g = dc.star_form_problem(n_domain)
+    rs = np.random.RandomState(11)
+    p = perturbed(rs, g["n_user"], g["n_item"], n_domain, "pn", "star", 64, (256, 128, 64))
+    p["user_emb"], p["item_emb"] = g["tables"]["user_emb"].copy(), g["tables"]["item_emb"].copy()
+    meta, rest = sref.param_names(False, "pn", "star", 64, 3)
+    names = meta + rest
+    for d, args in dc.probe_batches(g):
+        state = sref.init_state("pn", n_domain)
+        loss32, g32, p32, _ = sref.loss_and_grads(p, state, *args, False, "pn", "star", 64)
+        loss64, g64, p64, _ = sref.loss_and_grads64(p, names, *args, "pn", "star", 64)
+        assert abs(float(loss32) - loss64) < 2e-6 * max(1.0, abs(loss64))
+        np.testing.assert_allclose(p32, p64, rtol=5e-5, atol=5e-7)
+        assert np.all(args[2] == d)
+        _check_grads(g32, g64, [n for n in names if n != "domain_emb"], rtol=1e-3)
+
+
+def _forms_case(norm, dense, aux, hidden, mixed, B, seed=12, n_domain=4, domain=1):
     rs = np.random.RandomState(seed)
-    n_user, n_item, n_domain = 300, 200, 4
+    n_user, n_item = 300, 200
     p = perturbed(rs, n_user, n_item, n_domain, norm, dense, aux, hidden)
-    uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=None if mixed else 1)
+    uid, pid, dom, label = _batch(rs, n_user, n_item, n_domain, B, single_domain=None if mixed else domain)
+    if mixed and n_domain != 4:             # every id occurs, the highest first
+        dom = np.concatenate([[n_domain - 1], rs.permutation(np.arange(1, B) % n_domain)]).astype(np.int32)
     d = int(dom[0])
     meta, rest = sref.param_names(True, norm, dense, aux, len(hidden))
     names = meta + rest

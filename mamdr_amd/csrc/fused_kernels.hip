@@ -243,10 +243,8 @@ __device__ __forceinline__ void fz_tile_body(const FusedArgs& a, const FzTile ft
         *reinterpret_cast<f32x2*>(lds + (w * 16 + 4 * kq + r) * 32 + 2 * j) = (f32x2){acc[0][r], acc[1][r]};
     if (bias_tile) {
         // column sums: the four k lanes of a column pair, in lane order
-        csum[0] += __shfl_xor(csum[0], 16);
-        csum[1] += __shfl_xor(csum[1], 16);
-        csum[0] += __shfl_xor(csum[0], 32);
-        csum[1] += __shfl_xor(csum[1], 32);
+        csum[0] = wave_xor_sum_16_32(csum[0]);
+        csum[1] = wave_xor_sum_16_32(csum[1]);
         if (lane < 16) *reinterpret_cast<f32x2*>(lds + FZ_CS + w * 32 + 2 * j) = csum;
     }
     FZSTAMP(2);
@@ -469,8 +467,7 @@ __device__ __forceinline__ void fz_out_body(const FusedArgs& a, int ob, float* l
         for (int r = 0; r < 4; ++r)
             *reinterpret_cast<f32x2*>(lds + w * 32 + 2 * (4 * kq + r)) = (f32x2){acc[0][r], acc[1][r]};
     }
-    sg += __shfl_xor(sg, 16);          // the four k lanes of column 0 (the other lanes hold 0)
-    sg += __shfl_xor(sg, 32);
+    sg = wave_xor_sum_16_32(sg);       // the four k lanes of column 0 (the other lanes hold 0)
     if (lane == 0) lds[256 + w] = sg;
     FZSTAMP(2);
     __syncthreads();
@@ -501,10 +498,8 @@ __device__ __forceinline__ void fz_loss_body(const FusedArgs& a, float* lds) {
     float ss = 0.f, ls = 0.f;
     for (int e = tid; e < a.n_domain * EMB; e += FZ_THREADS) ss = fmaf(a.p[e], a.p[e], ss);
     for (int e = tid; e < a.n_loss_tiles; e += FZ_THREADS) ls += a.loss_part[e];
-    for (int o = 32; o > 0; o >>= 1) {
-        ss += __shfl_xor(ss, o);
-        ls += __shfl_xor(ls, o);
-    }
+    ss = wave_xor_sum64(ss);
+    ls = wave_xor_sum64(ls);
     if ((tid & 63) == 0) {
         lds[tid >> 6] = ss;
         lds[8 + (tid >> 6)] = ls;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "mamdr_device.h"
+#include "wave_exchange.h"
 #include "pregather_plan.h"
 #include "host_base.h"
 
@@ -323,10 +324,10 @@ __device__ __forceinline__ void dm_wave_begin(const TowerArgs& a, int tile, bool
 }
 __device__ __forceinline__ float dm_wave_sum(const float (&x)[8]) {
 #pragma clang fp contract(off)
-    const int l = (int)threadIdx.x & 15;
     const float G = (((x[0] + x[1]) + (x[2] + x[3])) + (x[4] + x[5])) + (x[6] + x[7]);
-    const float G0 = __shfl(G, l), G1 = __shfl(G, l + 16), G2 = __shfl(G, l + 32), G3 = __shfl(G, l + 48);
-    return ((G0 + G1) + G2) + G3;
+    float Gq[4];                   // G of lanes l, l + 16, l + 32, l + 48 (l = lane & 15), on the vector ALU: wave_exchange.h
+    wave_gather_rows16(G, Gq);
+    return ((Gq[0] + Gq[1]) + Gq[2]) + Gq[3];
 }
 // one element: the 16 staged pair sums of column c in order, then the step (the scalar form of dm_step4: same bits)
 __device__ __forceinline__ void dm_elem_finish(const DmStep& q, int c, const float* parts, float& p, float& m, float& v) {

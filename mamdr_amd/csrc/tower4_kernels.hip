@@ -283,27 +283,55 @@ __device__ __forceinline__ void t4_w1_request(const float* __restrict__ W1, floa
 // every request of this wave has landed (a workgroup barrier must follow before another wave reads the image)
 __device__ __forceinline__ void t4_w1_landed() { w1_image_landed(); }
 
-// forward: the wave's 32 rows in chunks of 8, the next chunk's reads issued before the current chunk's MFMAs
-template <typename Mid>
-__device__ __forceinline__ void t4_contract_w1f(const float* w1s, const float* As, float* red, Mid mid) {
+// The B operand of either contraction does not depend on the barriers that guard its A operand (h1, dz2): a wave's
+// whole share of the image -- 64 VGPRs in either direction -- is REQUESTED ahead of them (t4_w1f_request: the wave's own
+// 32 rows, landed at t4_w1_landed() and requested by this wave itself; t4_w1b_request: the image is complete and unchanged
+// from the first workgroup barrier behind layer 0 onwards), and the contraction proper waits for its A fragments alone.
+// The sched_barrier behind the requests keeps the scheduler from sinking them to their first use.  Every workgroup barrier
+// waits lgkmcnt(0), so a share is complete at the first barrier behind its request: the backward share's LDS time hides in
+// the output-unit phase, the forward share's reappears in front of layer 0's exchange (profiles/ab_tower4_tail.txt).
+struct T4W1F {
+    f32x2 b[32];                   // row 32 w + k of the image: columns 2 l, 2 l + 1
+};
+struct T4W1B {
+    f32x4 b[4][4];                 // [chunk column c][t]: columns 4 (4 w + c) .. + 3 of row l + 64 t
+};
+__device__ __forceinline__ void t4_w1f_request(const float* w1s, T4W1F& q) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const float* ap = As + (lane & 3) * T4_H1LD + 32 * w;
     const float* wp = w1s + (32 * w) * H2 + 2 * (lane & 1);
     const int half = lane >> 1;
+#pragma unroll
+    for (int k = 0; k < 32; ++k)                                  // k = row & 31 (the wave's first row is a multiple of 32)
+        q.b[k] = *reinterpret_cast<const f32x2*>(wp + k * H2 + 4 * (half ^ k));
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void t4_w1b_request(const float* w1s, T4W1B& q) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float* rp = w1s + lane * H2;
+    const int sw = lane & 31;                                     // (l + 64 t) & 31
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const int pos = 4 * ((4 * w + c) ^ sw);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) q.b[c][t] = *reinterpret_cast<const f32x4*>(rp + t * 64 * H2 + pos);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+// forward: the wave's 32 rows in chunks of 8 (B requested ahead: t4_w1f_request), the next chunk's A fragments issued
+// before the current chunk's MFMAs
+template <typename Stamp, typename Mid>
+__device__ __forceinline__ void t4_contract_w1f(const T4W1F& q, const float* As, float* red, Stamp first_mfma, Mid mid) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const float* ap = As + (lane & 3) * T4_H1LD + 32 * w;
     f32x4 acc[2];
     acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x2 b[2][8];
     f32x4 a4[2][2];
     auto request = [&](int c, int buf) {
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int k = 8 * c + u;                              // = row & 31 (the wave's first row is a multiple of 32)
-            b[buf][u] = *reinterpret_cast<const f32x2*>(wp + k * H2 + 4 * (half ^ k));
-        }
         a4[buf][0] = *reinterpret_cast<const f32x4*>(ap + 8 * c);
         a4[buf][1] = *reinterpret_cast<const f32x4*>(ap + 8 * c + 4);
     };
     request(0, 0);
+    first_mfma();                  // (diagnostic build: the first chunk's operands are here)
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int cur = c & 1;
@@ -312,41 +340,35 @@ __device__ __forceinline__ void t4_contract_w1f(const float* w1s, const float* A
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-            acc[0] = MAMDR_MFMA4(a4[cur][u >> 2][u & 3], b[cur][u][0], acc[0]);
-            acc[1] = MAMDR_MFMA4(a4[cur][u >> 2][u & 3], b[cur][u][1], acc[1]);
+            acc[0] = MAMDR_MFMA4(a4[cur][u >> 2][u & 3], q.b[8 * c + u][0], acc[0]);
+            acc[1] = MAMDR_MFMA4(a4[cur][u >> 2][u & 3], q.b[8 * c + u][1], acc[1]);
         }
     }
     mid();
     t4_put<H2, 2, false>(acc, red);
 }
-// backward: the wave's 4 chunk columns (16 k of the transposed contraction), reads one chunk column ahead
-template <typename Mid>
-__device__ __forceinline__ void t4_contract_w1b(const float* w1s, const float* As, float* red, Mid mid) {
+// backward: the wave's 4 chunk columns (16 k of the transposed contraction; B requested ahead: t4_w1b_request), A fragments
+// one chunk column ahead
+template <typename Stamp, typename Mid>
+__device__ __forceinline__ void t4_contract_w1b(const T4W1B& q, const float* As, float* red, Stamp first_mfma, Mid mid) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const float* ap = As + (lane & 3) * T4_H2LD + 16 * w;
-    const float* rp = w1s + lane * H2;
-    const int sw = lane & 31;                                     // (l + 64 t) & 31
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    f32x4 b[2][4], a4[2];
-    auto request = [&](int c, int buf) {
-        const int pos = 4 * ((4 * w + c) ^ sw);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) b[buf][t] = *reinterpret_cast<const f32x4*>(rp + t * 64 * H2 + pos);
-        a4[buf] = *reinterpret_cast<const f32x4*>(ap + 4 * c);
-    };
-    request(0, 0);
+    f32x4 a4[2];
+    a4[0] = *reinterpret_cast<const f32x4*>(ap);
+    first_mfma();
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int cur = c & 1;
         __builtin_amdgcn_sched_barrier(0);
-        if (c + 1 < 4) request(c + 1, cur ^ 1);
+        if (c + 1 < 4) a4[cur ^ 1] = *reinterpret_cast<const f32x4*>(ap + 4 * (c + 1));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int t = 0; t < 4; ++t) acc[t] = MAMDR_MFMA4(a4[cur][j], b[cur][t][j], acc[t]);
+            for (int t = 0; t < 4; ++t) acc[t] = MAMDR_MFMA4(a4[cur][j], q.b[c][t][j], acc[t]);
     }
     mid();
     t4_put<H1, 4, true>(acc, red);
@@ -366,6 +388,8 @@ __device__ __forceinline__ float t4_sum(const float* red, int row, int col) {
 // of the stamp buffer), and the device-wide counter
 #define T4STAMP(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 16 + (k)])
 #define T4STAMP_W4(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 256, a.stamps[(blockIdx.x + 256) * 16 + (k)])
+// (wave 0's stamps beyond its sixteen: slots 8.. of wave 4's row)
+#define T4STAMP_X(k) MAMDR_STAMP(MAMDR_CYCLES, a.stamps && threadIdx.x == 0, a.stamps[(blockIdx.x + 256) * 16 + 8 + (k)])
 #define T4REAL(k) MAMDR_STAMP(MAMDR_REALTIME, a.stamps && threadIdx.x == 0, a.stamps[blockIdx.x * 16 + (k)])
 
 // DX: trainable user / item tables -> d loss / d [user | item] row = dz1 . W0[0:256,:]^T through the
@@ -404,6 +428,8 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     T4W<H3, H2> v2;      // backward: dz3 . W2^T through the transposed copy W2T [64][128]
     T4W<H2, H1, T4_DEEP> v1;      // backward: dz2 . W1^T through W1T [128][256] (W1L: unused)
     float* w1s = smem + T4_W1S;
+    T4W1F w1f;           // W1L: the wave's share of the image, forward / backward (requested ahead of the barriers in front
+    T4W1B w1b;           // of the contractions, see t4_w1f_request)
     T4W<H1, 2 * EMB> v0; // DX: dz1 . W0[0:256,:]^T through W0T [256][256]
     // layer 0's accumulators are zeroed HERE: initialised in front of the contraction, they took the registers of the
     // gather's (divergent-branch) table loads and the compiler drained every outstanding load -- the pending
@@ -665,6 +691,9 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
                    [&]() {
                        if (W1L) {
                            t4_w1_landed();           // (layer 0's ring is empty: nothing else is outstanding)
+                           // layer 1's B operand: the wave's own rows of the image, ahead of layer 0's exchange and
+                           // epilogue (three barriers)
+                           t4_w1f_request(w1s, w1f);
                            w2.prefetch(P + a.L.w2);
                        } else {
                            w1.prefetch(P + a.L.w1);
@@ -699,7 +728,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
 
     T4STAMP(3);
     // ---- layer 1: 256 -> 128
-    if (W1L) t4_contract_w1f(w1s, smem + T4_H1, red, [&]() {
+    if (W1L) t4_contract_w1f(w1f, smem + T4_H1, red, [&]() { T4STAMP_X(0); }, [&]() {
         if constexpr (W2D) v2.prefetch_untransposed(P + a.L.w2);     // W2T stale: the call's first tower
         else v2.prefetch(a.wT + W2T_OFF);
     });
@@ -741,8 +770,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
             h = (u >= a.drop_thresh) ? h * scale : 0.f;
         }
         ws_store1(&acts_t[(size_t)row * ACT_LD + XDIM + H1 + H2 + col], h);
-        float s = h * wor;
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const float s = wave_xor_dot64(h, wor);         // (wave_exchange.h: the butterfly 32 .. 1 on the vector ALU)
         float logit = s + gbr;
         if (FM) logit += rowf[8 + row];
         float p;
@@ -782,6 +810,10 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
         smem[T4_DZ3 + row * T4_H3LD + col] = d;
         ws_store1(&dz_t[(size_t)row * DZ_LD + H1 + H2 + col], d);
     }
+    // backward 1's B operand (W1^T from the image, complete since layer 0's barrier): waves 4..7, idle in this phase, ask
+    // at once, waves 0..3 behind their rows' work -- the reads land under this phase (behind its barrier they cost the
+    // kernel 50 - 200 cycles more: profiles/ab_tower4_tail.txt)
+    if (W1L) t4_w1b_request(w1s, w1b);
     __syncthreads();
     if (tid == 0) a.loss_part[tile] = (rowf[4] + rowf[5]) + (rowf[6] + rowf[7]);
     if (FM && !pnn && !nfm) {     // d fm / d domain embedding = u + i: per-row term of the domain-table gradient
@@ -804,7 +836,7 @@ __global__ __launch_bounds__(T4_THREADS) void k_tower4(const float* __restrict__
     __syncthreads();
     T4STAMP(8);
     // ---- dz1 = (dz2 . W1^T) * gate(h1); the domain-table gradient follows from dz1 by linearity
-    if (W1L) t4_contract_w1b(w1s, smem + T4_DZ2, red, []() {});
+    if (W1L) t4_contract_w1b(w1b, smem + T4_DZ2, red, [&]() { T4STAMP_X(1); }, []() {});
     else t4_contract(v1, a.wT + W1T_OFF, smem + T4_DZ2, T4_H2LD, red, [&]() { if (DX) v0.prefetch(a.wT + W0T_OFF); });
     __syncthreads();
     float dip[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};      // PNN: this thread's share of d loss / d ip of its two rows
